@@ -21,7 +21,11 @@ rank 0 also drives all N devices once through the C ABI's own gpsacq_multi_searc
 
 Other lines (the default stays the one the driver records): --config 2|3|4 (BASELINE configs[2..4]), --input iq8 (8-bit IQ capture
 converted inside the forward transform), --capture FILE (a 1-bit capture file, e.g. gps.samples.1bit.I.fs5456.if4092.bin).
---bare: the timed steps only (what the profiling and PMC child runs use).  Exit code 3: the GPU's results disagree with the oracle.
+A plain run is lean: set-up, the W warm-up and K timed steps, the outputs (--dump-outputs DIR) and the JSON line.  Everything else -- the
+clock sampling and cycle stamps of the roofline, the soak, weak and side legs, live traffic, the CPU baselines and the parity verdict against
+the oracle, the rocFFT baseline, the in-process multi-GPU leg, the front end -- runs with --full only.
+--bare: the timed steps only, cells kept for --dump-outputs alone (what the profiling and PMC child runs use).  Exit code 3 (--full):
+the GPU's results disagree with the oracle.
 """
 import argparse
 import json
@@ -174,7 +178,50 @@ def emit(line):
         os.write(_REAL_STDOUT, (line + "\n").encode())
 
 
-def parse_args():
+# --dump-outputs stays under 64 MB: at most 1.6 M cells (20 bytes each as written: 32 MB; the default line has 794 240), 400 k peaks and
+# 400 k keys (32 and 28 bytes each with their sample index: 24 MB); more than that is a fixed, seeded sample of rows
+DUMP_CELLS_MAX = 1_600_000
+DUMP_ROWS_MAX = 400_000
+
+
+def _dump_rows(n, cap):
+    """Row indices of a fixed, seeded sample of n rows (sorted), or None when all n fit under cap."""
+    return None if n <= cap else np.sort(np.random.default_rng(0).choice(n, size=cap, replace=False))
+
+
+def dump_outputs(out_dir, leg, best, kmax, gdist):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy (float32 / float64, every value exact) -- the merged
+    keys (per PRN; per (position, PRN) on the grid configs) decoded to snr / lo_shift / ca_shift, this rank's per-task peaks, and its cells
+    when the step kept them.  Larger outputs than DUMP_CELLS_MAX cells / DUMP_ROWS_MAX peaks or keys are a fixed, seeded sample of rows
+    (the indices in <group>_index.npy).  Returns the names written."""
+    from gpsacq import CELL_DTYPE, PEAK_DTYPE
+    arrays = {}
+    snr, lo, ca = gdist.unpack_keys(best.cpu(), kmax)
+    keys = {"snr": snr.numpy(), "lo_shift": lo.numpy(), "ca_shift": ca.numpy()}
+    groups = [("keys", keys, _dump_rows(len(keys["snr"]), DUMP_ROWS_MAX))]
+    if leg.n_tasks > 0:
+        pk = leg.d_peaks[(leg.step_no - 1) % leg.NBUF][:leg.n_tasks].cpu().numpy().view(PEAK_DTYPE).reshape(-1)
+        groups.append(("peaks", {f: pk[f] for f in PEAK_DTYPE.names}, _dump_rows(leg.n_tasks, DUMP_ROWS_MAX)))
+    if leg.d_cells is not None:
+        rows = _dump_rows(leg.n_tasks, max(1, DUMP_CELLS_MAX // leg.d_cells.shape[1]))
+        d = leg.d_cells if rows is None else leg.d_cells[leg.torch.from_numpy(rows).to(leg.dev)]
+        cells = d.cpu().numpy().view(CELL_DTYPE).reshape(d.shape[0], d.shape[1])
+        groups.append(("cells", {f: cells[f] for f in CELL_DTYPE.names}, None))
+        if rows is not None:
+            arrays["cells_index"] = rows.astype(np.float64)
+    for group, fields, rows in groups:
+        for f, a in fields.items():
+            a = a if rows is None else a[rows]
+            arrays[f"{group}_{f}"] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)  # integers as float64: exact
+        if rows is not None:
+            arrays[f"{group}_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)  # 100 x 42 ms: a GPU leg long enough for a 5-second SMI sampler to see it
@@ -202,10 +249,15 @@ def parse_args():
     ap.add_argument("--pk-fma-seconds", type=float, default=3.0, help="N = 1: seconds of the pure v_pk_fma_f32 stream behind roofline.pk_fma_stream_TF (0: skip)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the gps_test end-to-end leg")
     ap.add_argument("--spawn-check", action="store_true", help="launcher check without a GPU: every rank joins a gloo group, rank 0 prints the ranks it saw")
-    a = ap.parse_args()
-    if a.bare:
+    ap.add_argument("--full", action="store_true", help="also run everything beside the timed steps (clock sampling, side legs, baselines, parity verdict); "
+                                                        "a plain run times the steps and prints the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64")
+    a = ap.parse_args(argv)
+    if a.bare or not a.full:
         a.weak_blocks, a.soak_seconds, a.pk_fma_seconds = 0, 0.0, 0.0
-        a.no_cpu_baseline = a.no_live_traffic = a.no_library_baseline = a.no_inproc_multi = a.no_e2e = True
+        a.no_live_traffic = a.no_library_baseline = a.no_inproc_multi = a.no_e2e = True
+    if a.bare:
+        a.no_cpu_baseline = True
     return a
 
 
@@ -394,10 +446,11 @@ def main():
         blocks_per_rank, devices = [int(v) for v in t[:, 0].tolist()], [int(v) for v in t[:, 1].tolist()]
 
     n_keys = tasks.shape[0] if grid else 32
-    # rank 0's share of the LAST TIMED STEP is checked against the oracle afterwards (peaks and cells): its cells are kept
-    check_parity = rank == 0 and not grid and not iq8 and n_tasks > 0 and not args.no_cpu_baseline and args.config in (1, 2)
-    leg = Leg(torch, eng, dev, dist, backend, nblk, n_tasks, d_bits, d_tasks, stride, grid, n_keys=n_keys, iq=iq_in, keep_cells=check_parity)
-    if rank == 0:
+    # rank 0 keeps the cells of the LAST TIMED STEP (the same kernels, the same launches); --full checks them and the peaks against the oracle
+    keep_cells = rank == 0 and not grid and not iq8 and n_tasks > 0 and args.config in (1, 2) and (not args.no_cpu_baseline or args.dump_outputs is not None)
+    check_parity = keep_cells and args.full and not args.no_cpu_baseline
+    leg = Leg(torch, eng, dev, dist, backend, nblk, n_tasks, d_bits, d_tasks, stride, grid, n_keys=n_keys, iq=iq_in, keep_cells=keep_cells)
+    if rank == 0 and args.full:
         leg.sampler = ClockSampler(torch, dev_index)  # sclk / power during the K timed steps (roofline.sclk_mhz, .power_w)
     elapsed, kern_ms, best = leg.run(args.steps, args.warmup)
     timing = eng.last_timing() if n_tasks > 0 else None
@@ -410,6 +463,9 @@ def main():
         from oracle_lib import CELL_DTYPE as _CL, PEAK_DTYPE as _PK
         gpu_peaks = leg.d_peaks[(leg.step_no - 1) % leg.NBUF][:n_tasks].cpu().numpy().view(_PK).reshape(-1)
         gpu_cells = leg.d_cells.cpu().numpy().view(_CL).reshape(n_tasks, eng.num_doppler)
+    if rank == 0 and args.dump_outputs is not None:
+        names = dump_outputs(args.dump_outputs, leg, best, eng.kmax, gdist)
+        print(f"bench.py: {len(names)} arrays of the last timed step in {args.dump_outputs}", file=sys.stderr)
 
     side = world == 1 and n_tasks > 0 and args.soak_seconds > 0  # the N = 1 side legs
     soak_leg = X.soak(leg, cells_job, args.soak_seconds) if side else None

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bench_extras.py -- everything bench.py reports BESIDE the K timed steps (none of it inside the timed region):
+"""bench_extras.py -- everything bench.py reports BESIDE the K timed steps, with --full only (none of it inside the timed region):
 
   ClockSampler / cu_clocks      the clock the roofline is quoted at (sysfs readings; the CUs' own cycle counters)
   soak                          the timed step repeated for >= 6 s (an SMI sampler beside the run sees the GPU busy)
@@ -894,7 +894,8 @@ def build_line(c):
             out["injected_prns_all_ranks"] = sorted(set().union(*[synth_sats(CAPTURE_SEED + r, c.fs)[0] for r in range(c.world)])) if c.iq8 else c.injected
     out["extras"] = {"one_rank_process_group": c.dist is not None and c.world == 1, "soak": c.soak_leg is not None, "strong_share_at_8": c.share is not None,
                      "weak_scaling": c.weak is not None, "live_traffic": traffic_live is not None, "pk_fma_stream": c.pk_stream is not None,
-                     "cpu_baseline": c.world == 1 and not c.args.no_cpu_baseline, "e2e_cli": c.world == 1 and not c.args.no_e2e,
+                     "cpu_baseline": c.world == 1 and not c.args.no_cpu_baseline and c.args.full, "e2e_cli": c.world == 1 and not c.args.no_e2e,
+                     "full": c.args.full,
                      "keys": "gpsacq_peak_keys_device (library, engine stream)"}
     for k, v in (("one_rank_collective", c.no_coll), ("soak", c.soak_leg), ("strong_share_at_8", c.share), ("weak_scaling", c.weak)):
         if v is not None:

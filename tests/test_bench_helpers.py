@@ -208,3 +208,71 @@ def test_keys_digest_and_host_packing():
     assert keys[0] > keys[1] > keys[2] > keys[3]  # equal SNR: the lower Doppler bin wins
     d = b.keys_digest(keys)
     assert len(d) == 16 and d == b.keys_digest(keys.copy()) and d != b.keys_digest(keys[::-1])
+
+
+def _bench_core():
+    spec = importlib.util.spec_from_file_location("bench_core_mod", os.path.join(ROOT, "bench.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def test_plain_run_times_the_steps_only_and_full_keeps_the_rest():
+    """bench.py without --full: set-up, warm-up, the K timed steps and the line -- no side legs, live traffic, rocFFT baseline,
+    in-process multi-GPU leg or front end (the CPU baseline and parity verdict need --full in main()); --full runs them as before;
+    --bare is the timed steps alone either way."""
+    b = _bench_core()
+    p = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert p.steps == 7 and p.warmup == 2 and not p.full and p.dump_outputs is None
+    assert (p.weak_blocks, p.soak_seconds, p.pk_fma_seconds) == (0, 0.0, 0.0)
+    assert p.no_live_traffic and p.no_library_baseline and p.no_inproc_multi and p.no_e2e and not p.no_cpu_baseline
+    f = b.parse_args(["--full", "--dump-outputs", "out"])
+    assert f.full and f.dump_outputs == "out" and (f.weak_blocks, f.soak_seconds, f.pk_fma_seconds) == (4096, 6.0, 3.0)
+    assert not (f.no_live_traffic or f.no_library_baseline or f.no_inproc_multi or f.no_e2e or f.no_cpu_baseline)
+    fb = b.parse_args(["--full", "--bare"])
+    assert fb.no_cpu_baseline and fb.no_e2e and fb.no_live_traffic and (fb.weak_blocks, fb.soak_seconds) == (0, 0.0)
+
+
+def test_dump_outputs_writes_exact_float_arrays_and_samples_large_ones(tmp_path, monkeypatch):
+    """bench.dump_outputs on host tensors shaped like a Leg's: the decoded merged keys, the last step's peaks (three buffers: the
+    one step_no points at) and cells, as float32 / float64 .npy holding every value exactly; above the cell budget a seeded sample of
+    whole tasks, the same rows in every run."""
+    import types
+    import numpy as np
+    import torch
+    from gpsacq import CELL_DTYPE, PEAK_DTYPE
+    from gpsacq import dist as gdist
+    b = _bench_core()
+    rng = np.random.default_rng(5)
+    n_tasks, ndop, kmax = 96, 73, 36
+    pk = np.zeros(n_tasks, dtype=PEAK_DTYPE)
+    pk["snr"] = rng.uniform(1, 200, n_tasks).astype(np.float32)
+    pk["lo_shift"] = rng.integers(-kmax, kmax + 1, n_tasks)
+    pk["ca_shift"] = rng.integers(0, 5456, n_tasks)
+    pk["max_pwr"] = rng.uniform(1e3, 1e9, n_tasks).astype(np.float32)
+    cells = np.zeros((n_tasks, ndop), dtype=CELL_DTYPE)
+    for f in ("max_pwr", "tot_pwr", "snr"):
+        cells[f] = rng.uniform(0, 1e9, cells.shape).astype(np.float32)
+    cells["max_i"] = rng.integers(0, 5456, cells.shape)
+    d_peaks = [torch.zeros((n_tasks, 4), dtype=torch.int32) for _ in range(3)]
+    d_peaks[1] = torch.from_numpy(pk.view(np.int32).reshape(n_tasks, 4).copy())
+    peaks_t = d_peaks[1]
+    best = gdist.per_prn_best(gdist.pack_keys(peaks_t, kmax))
+    leg = types.SimpleNamespace(torch=torch, dev=torch.device("cpu"), n_tasks=n_tasks, NBUF=3, step_no=5, d_peaks=d_peaks,
+                                d_cells=torch.from_numpy(cells.view(np.int32).reshape(n_tasks, ndop, 4).copy()))
+    names = b.dump_outputs(str(tmp_path / "a"), leg, best, kmax, gdist)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["peaks_snr"], pk["snr"]) and np.array_equal(got["peaks_ca_shift"], pk["ca_shift"].astype(np.float64))
+    assert np.array_equal(got["peaks_lo_shift"], pk["lo_shift"].astype(np.float64)) and np.array_equal(got["peaks_max_pwr"], pk["max_pwr"])
+    assert np.array_equal(got["cells_max_i"], cells["max_i"].astype(np.float64)) and np.array_equal(got["cells_tot_pwr"], cells["tot_pwr"])
+    for sv in range(32):  # the merged keys, decoded: the best peak of each PRN (block t <-> PRN t % 32)
+        i = sv + 32 * int(np.argmax(pk["snr"][sv::32]))
+        assert got["keys_snr"][sv] == pk["snr"][i] and got["keys_ca_shift"][sv] == pk["ca_shift"][i] and got["keys_lo_shift"][sv] == pk["lo_shift"][i]
+    assert "cells_index" not in got and got["cells_snr"].shape == (n_tasks, ndop)
+    monkeypatch.setattr(b, "DUMP_CELLS_MAX", 10 * ndop)
+    for d in ("b", "c"):
+        names = b.dump_outputs(str(tmp_path / d), leg, best, kmax, gdist)
+    idx = np.load(tmp_path / "b" / "cells_index.npy")
+    assert idx.shape == (10,) and np.array_equal(idx, np.load(tmp_path / "c" / "cells_index.npy")) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "cells_max_pwr.npy"), cells["max_pwr"][idx.astype(np.int64)])

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +19,7 @@ def _bench(*args, env=None):
     e.update(env or {})
     if "--soak-seconds" not in args:
         args = ("--soak-seconds", "0") + tuple(args)  # the soak leg has its own test (tests/test_gpu_round4.py)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-live-traffic", *args],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-live-traffic", *args],
                        capture_output=True, text=True, timeout=600, env=e)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -87,7 +88,7 @@ def test_eight_ranks_share_the_nottingham_sized_capture():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--blocks-total", "10880", "--steps", "3",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--blocks-total", "10880", "--steps", "3",
                         "--no-cpu-baseline", "--no-e2e"], capture_output=True, text=True, timeout=900, env=e)
     assert r.returncode == 0, r.stderr[-3000:]
     out_lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -102,3 +103,40 @@ def test_eight_ranks_share_the_nottingham_sized_capture():
     assert "error" not in im and im["keys_equal_digest"] is True and im["runs"] == 340, im
     assert j["weak_scaling"]["blocks_per_gpu"] == 4096 and j["weak_scaling"]["value"] > 0
     assert j["value"] > 0 and 0 < j["roofline"]["frac"] < 1 and "cpu_baseline" not in j
+
+
+def test_plain_line_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """A plain run (no --full): the K timed steps and the line, nothing beside them; --dump-outputs writes what the last timed step
+    computed as float32 / float64 arrays, identical from run to run, and consistent with the line (merged keys = the best peak of
+    each PRN, `detected` = the keys at snr >= 25)."""
+    e = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GPSACQ_DIST_BACKEND"):
+        e.pop(k, None)
+    got = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--blocks-total", "640",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600, env=e)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["unit"] == "cells/s" and j["dtype"] == "f32"
+        assert abs(j["value"] * j["ms_per_step"] * 1e-3 / (640 * 73) - 1) < 1e-9
+        for k in ("cpu_baseline", "soak", "strong_share_at_8", "one_rank_collective", "weak_scaling", "e2e_cli"):
+            assert k not in j, k
+        assert j["extras"]["full"] is False and "gpu_library_baseline" not in j["extras"] and j["roofline"]["traffic_live"] is None
+        assert j["roofline"]["clock_sampling"] is None and j["roofline"]["pk_fma_stream"] is None
+        files = sorted(os.listdir(tmp_path / d))
+        got.append((j, {f[:-4]: np.load(tmp_path / d / f) for f in files}))
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64 << 20
+    (j, a), (j2, b) = got
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a) and j["keys_digest"] == j2["keys_digest"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["peaks_snr"].shape == (640,) and a["cells_max_pwr"].shape == (640, 73) and a["keys_snr"].shape == (32,)
+    for sv in range(32):
+        assert a["keys_snr"][sv] == a["peaks_snr"][sv::32].max()
+    det = [{"prn": sv + 1, "snr": round(float(a["keys_snr"][sv]), 3), "lo_shift": int(a["keys_lo_shift"][sv]), "ca_shift": int(a["keys_ca_shift"][sv])}
+           for sv in range(32) if a["keys_snr"][sv] >= 25]
+    assert det == j["detected"] and set(j["detected_prns"]) >= set(j["injected_prns_all_ranks"])
+    best_bin = np.argmax(a["cells_snr"], axis=1)  # the block's peak: its cell of highest snr, ties to the lower bin (k_peaks)
+    assert np.array_equal(a["peaks_snr"], a["cells_snr"].max(axis=1)) and np.array_equal(a["peaks_max_pwr"], a["cells_max_pwr"][np.arange(640), best_bin])

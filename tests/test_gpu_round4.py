@@ -103,7 +103,7 @@ def _bench(*args):
         e.pop(k, None)
     if "--live-traffic" not in args:
         args = ("--no-live-traffic",) + tuple(args)  # its own flag since round 5 (it used to follow --no-cpu-baseline)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-e2e", *args],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-e2e", *args],
                        capture_output=True, text=True, timeout=600, env=e)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -16,7 +16,7 @@ def _run_bench(*args):
     e = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GPSACQ_DIST_BACKEND"):
         e.pop(k, None)
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=900, env=e)
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *args], capture_output=True, text=True, timeout=900, env=e)
 
 
 def _line(r):

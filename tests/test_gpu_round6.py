@@ -29,7 +29,7 @@ def _line(r):
 
 
 def _bench(*args, **env):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=1200, env=_env(**env))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *args], capture_output=True, text=True, timeout=1200, env=_env(**env))
     assert r.returncode == 0, r.stderr[-3000:]
     return _line(r)
 
@@ -39,7 +39,7 @@ def _torchrun(n, *args):
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), *args],
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), *args],
                        capture_output=True, text=True, timeout=1500, env=_env(GPSACQ_DIST_BACKEND="gloo"))
     assert r.returncode == 0, r.stderr[-3000:]
     return _line(r)

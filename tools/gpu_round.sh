@@ -8,21 +8,21 @@ OUT=$R/gpurun_out/round_$TAG
 mkdir -p $OUT
 cd $R
 timeout 1700 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc $?" >> $OUT/pytest_gpu.log; tail -4 $OUT/pytest_gpu.log
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-python bench.py --config 2 --bare > $OUT/bench_config2.json 2> $OUT/bench_config2.err
-python bench.py --config 3 --doppler-step 250 --bare --steps 5 > $OUT/bench_config3.json 2> $OUT/bench_config3.err
-python bench.py --config 4 --doppler-step 50 --bare --steps 5 > $OUT/bench_config4.json 2> $OUT/bench_config4.err
-python bench.py --config 1 --input iq8 --steps 5 --bare > $OUT/bench_iq8_config1.json 2> $OUT/bench_iq8_config1.err
-python bench.py --config 3 --input iq8 --blocks-total 1024 --steps 3 --bare > $OUT/bench_iq8_config3.json 2> $OUT/bench_iq8_config3.err
-GPSACQ_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 5 --warmup 2 --no-e2e 2> $OUT/bench_two_rank_selfspawn.err | grep '^{' > $OUT/bench_two_rank_selfspawn.json
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --config 2 --bare > $OUT/bench_config2.json 2> $OUT/bench_config2.err
+python bench.py --full --config 3 --doppler-step 250 --bare --steps 5 > $OUT/bench_config3.json 2> $OUT/bench_config3.err
+python bench.py --full --config 4 --doppler-step 50 --bare --steps 5 > $OUT/bench_config4.json 2> $OUT/bench_config4.err
+python bench.py --full --config 1 --input iq8 --steps 5 --bare > $OUT/bench_iq8_config1.json 2> $OUT/bench_iq8_config1.err
+python bench.py --full --config 3 --input iq8 --blocks-total 1024 --steps 3 --bare > $OUT/bench_iq8_config3.json 2> $OUT/bench_iq8_config3.err
+GPSACQ_DIST_BACKEND=gloo python bench.py --full --gpus 2 --steps 5 --warmup 2 --no-e2e 2> $OUT/bench_two_rank_selfspawn.err | grep '^{' > $OUT/bench_two_rank_selfspawn.json
 GPSACQ_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 2 --steps 5 --warmup 2 --no-e2e 2> $OUT/bench_two_rank_gloo.err | grep '^{' > $OUT/bench_two_rank_gloo.json
-GPSACQ_DIST_BACKEND=gloo python bench.py --gpus 2 --config 4 --doppler-step 50 --steps 3 --warmup 1 2> $OUT/bench_two_rank_gloo_config4.err | grep '^{' > $OUT/bench_two_rank_gloo_config4.json
+    bench.py --full --gpus 2 --steps 5 --warmup 2 --no-e2e 2> $OUT/bench_two_rank_gloo.err | grep '^{' > $OUT/bench_two_rank_gloo.json
+GPSACQ_DIST_BACKEND=gloo python bench.py --full --gpus 2 --config 4 --doppler-step 50 --steps 3 --warmup 1 2> $OUT/bench_two_rank_gloo_config4.err | grep '^{' > $OUT/bench_two_rank_gloo_config4.json
 # the driver's N = 8 launch line on the one GPU (gloo collectives, eight ranks on device 0): the Nottingham-sized capture split 43 x 4 + 42 x 4
 # runs -- the SAME capture as the default line: keys_digest / detected must equal bench_default.json's; rank 0's share checked against the
 # oracle; the in-process multi-GPU leg (eight engines of the C ABI) over the same capture
 GPSACQ_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29519 \
-    bench.py --gpus 8 --steps 5 --warmup 2 > $OUT/bench_eight_rank_gloo.json 2> $OUT/bench_eight_rank_gloo.err
+    bench.py --full --gpus 8 --steps 5 --warmup 2 > $OUT/bench_eight_rank_gloo.json 2> $OUT/bench_eight_rank_gloo.err
 python tools/multi_enqueue.py > $OUT/multi_enqueue.json 2> $OUT/multi_enqueue.err
 GPSACQ_MULTI_FORCE_RCCL=1 python tools/multi_enqueue.py 2> $OUT/multi_enqueue_force_rccl.err | grep "^{" > $OUT/multi_enqueue_force_rccl.json  # (RCCL prints a version banner to stdout)
 for i in 1 2 3; do GPSACQ_TRACE=1 gnss-gps-sdr_amd/bin/gps_test tests/golden/gps_sig_tmp.bin 2.046e6 8.184e6 5000 2>&1 >/dev/null | grep trace; done > $OUT/cli_trace.log; cat $OUT/cli_trace.log
