@@ -38,7 +38,14 @@ __global__ __launch_bounds__(256) void k_generate(GenArgs a) {
             const long long q = (long long)floor(r);
             int idx = (int)(q % 1023);
             if (idx < 0) idx += 1023;
-            const float chip = ((c_chips[sat.sv][idx >> 5] >> (idx & 31)) & 1u) ? -1.0f : 1.0f;
+            float chip = ((c_chips[sat.sv][idx >> 5] >> (idx & 31)) & 1u) ? -1.0f : 1.0f;
+            if (a.nav) {  // gpsacq_generate_nav_range: bit floor(q / 20460) mod n_nav of this satellite's data (+-1: exact)
+                long long b = q / 20460;
+                if (q < 0 && b * 20460 != q) --b;
+                b %= a.n_nav;
+                if (b < 0) b += a.n_nav;
+                chip *= (float)a.nav[(size_t)s * a.n_nav + (size_t)b];
+            }
             double ph = sat.cycles_per_sample * (double)m + sat.carrier_phase;
             ph -= floor(ph);
             y += sat.amplitude * chip * cospif(2.0f * (float)ph);

@@ -22,6 +22,8 @@ struct GenArgs {
     const GenSat* sats;  // device
     int n_sats;
     float noise_sigma;
+    const int8_t* nav;   // [n_sats][n_nav] navigation bits +-1 (device), or nullptr: no data
+    int n_nav;
 };
 
 // gps_sig_gen.m's own signal (gen_kernels.hip, k_siggen)

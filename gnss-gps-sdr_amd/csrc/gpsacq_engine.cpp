@@ -21,6 +21,7 @@
 #include "acq_tables.hpp"
 #include "iq_launch.hpp"
 #include "gen_launch.hpp"
+#include "track_launch.hpp"
 
 using namespace acq;
 
@@ -102,6 +103,18 @@ struct gpsacq_engine {
     size_t sats_cap = 0;
     uint8_t* d_gen = nullptr;
     size_t gen_cap = 0;
+    int8_t* d_nav = nullptr;  // navigation bits of gpsacq_generate_nav_range
+    size_t nav_cap = 0;
+    // tracking channels (gpsacq_track*)
+    uint32_t* d_track_chips = nullptr;  // [32][32] C/A chips
+    gpsacq_track_chan* d_chans = nullptr;
+    size_t chans_cap = 0;
+    int32_t* d_track_n = nullptr;
+    size_t track_n_cap = 0;
+    int32_t* d_prompt = nullptr;
+    size_t prompt_cap = 0;
+    gpsacq_track_record* d_records = nullptr;
+    size_t records_cap = 0;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;
@@ -221,7 +234,7 @@ extern "C" void gpsacq_destroy(gpsacq_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->p.device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    void* bufs[] = {e->d_t1, e->d_t2, e->d_bq, e->d_fold, e->d_tn, e->d_rho, e->d_cos, e->d_sin, e->d_cos_t, e->d_sin_t, e->d_code, e->d_patch_blocks, e->d_bits, e->d_iq, e->d_iqbits, e->d_fsamp, e->d_pdump, e->d_sums, e->d_sats, e->d_gen, e->d_persist, e->d_lutc,
+    void* bufs[] = {e->d_t1, e->d_t2, e->d_bq, e->d_fold, e->d_tn, e->d_rho, e->d_cos, e->d_sin, e->d_cos_t, e->d_sin_t, e->d_code, e->d_patch_blocks, e->d_bits, e->d_iq, e->d_iqbits, e->d_fsamp, e->d_pdump, e->d_sums, e->d_sats, e->d_gen, e->d_nav, e->d_track_chips, e->d_chans, e->d_track_n, e->d_prompt, e->d_records, e->d_persist, e->d_lutc,
                     e->d_dpp, e->d_parts, e->d_tasks, e->d_cells, e->d_peaks};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -1062,9 +1075,10 @@ extern "C" void* gpsacq_stream(gpsacq_engine* e) { return e ? (void*)e->stream :
 // Synthetic capture on the device (gps_sig_gen.m's role; signal model of SURVEY.md section 8d).  The stream is a function of
 // (seed, satellites, absolute sample index) alone: any byte range of it can be generated anywhere -- a rank of a multi-GPU job
 // makes exactly its own blocks of the one capture every world size searches.
-extern "C" int gpsacq_generate_range_device(gpsacq_engine* e, void* d_bits, size_t n_bytes, uint64_t first_sample, const gpsacq_sat* sats,
-                                            int n_sats, float noise_sigma, uint64_t seed, int sync) {
+extern "C" int gpsacq_generate_nav_range_device(gpsacq_engine* e, void* d_bits, size_t n_bytes, uint64_t first_sample, const gpsacq_sat* sats,
+                                                int n_sats, const int8_t* nav, int n_nav, float noise_sigma, uint64_t seed, int sync) {
     if (!e || !d_bits || n_bytes == 0 || n_sats < 0 || (n_sats > 0 && !sats)) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_range_device: bad argument");
+    if (nav && n_nav <= 0) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_nav_range: n_nav_bits = %d", n_nav);
     if (first_sample & 7) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_range_device: first_sample %llu is not a multiple of 8 (a byte boundary)", (unsigned long long)first_sample);
     HIPCHK(hipSetDevice(e->p.device));
     const double L1 = 1575.42e6, CPS = 1.023e6;
@@ -1081,6 +1095,11 @@ extern "C" int gpsacq_generate_range_device(gpsacq_engine* e, void* d_bits, size
     if (n_sats > 0) {
         if (int rc = grow(e->d_sats, e->sats_cap, (size_t)n_sats, e->stream)) return rc;
         HIPCHK(hipMemcpyAsync(e->d_sats, gs.data(), gs.size() * sizeof(GenSat), hipMemcpyHostToDevice, e->stream));
+        if (nav) {
+            const size_t nn = (size_t)n_sats * n_nav;
+            if (int rc = grow(e->d_nav, e->nav_cap, nn, e->stream)) return rc;
+            HIPCHK(hipMemcpyAsync(e->d_nav, nav, nn, hipMemcpyHostToDevice, e->stream));
+        }
         HIPCHK(hipStreamSynchronize(e->stream));  // gs goes out of scope
     }
     GenArgs a{};
@@ -1091,25 +1110,35 @@ extern "C" int gpsacq_generate_range_device(gpsacq_engine* e, void* d_bits, size
     a.sats = e->d_sats;
     a.n_sats = n_sats;
     a.noise_sigma = noise_sigma;
+    a.nav = nav && n_sats > 0 ? e->d_nav : nullptr;
+    a.n_nav = n_nav;
     launch_generate(a, e->stream);
     HIPCHK(hipGetLastError());
     if (sync) HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
+}
+extern "C" int gpsacq_generate_range_device(gpsacq_engine* e, void* d_bits, size_t n_bytes, uint64_t first_sample, const gpsacq_sat* sats,
+                                            int n_sats, float noise_sigma, uint64_t seed, int sync) {
+    return gpsacq_generate_nav_range_device(e, d_bits, n_bytes, first_sample, sats, n_sats, nullptr, 0, noise_sigma, seed, sync);
 }
 extern "C" int gpsacq_generate_device(gpsacq_engine* e, void* d_bits, size_t n_bytes, const gpsacq_sat* sats, int n_sats,
                                       float noise_sigma, uint64_t seed, int sync) {
     return gpsacq_generate_range_device(e, d_bits, n_bytes, 0, sats, n_sats, noise_sigma, seed, sync);
 }
 
-extern "C" int gpsacq_generate_range(gpsacq_engine* e, uint8_t* bits_out, size_t n_bytes, uint64_t first_sample, const gpsacq_sat* sats,
-                                     int n_sats, float noise_sigma, uint64_t seed) {
+extern "C" int gpsacq_generate_nav_range(gpsacq_engine* e, uint8_t* bits_out, size_t n_bytes, uint64_t first_sample, const gpsacq_sat* sats,
+                                         int n_sats, const int8_t* nav, int n_nav, float noise_sigma, uint64_t seed) {
     if (!e || !bits_out || n_bytes == 0) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_range: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = grow(e->d_gen, e->gen_cap, n_bytes, e->stream)) return rc;
-    if (int rc = gpsacq_generate_range_device(e, e->d_gen, n_bytes, first_sample, sats, n_sats, noise_sigma, seed, 0)) return rc;
+    if (int rc = gpsacq_generate_nav_range_device(e, e->d_gen, n_bytes, first_sample, sats, n_sats, nav, n_nav, noise_sigma, seed, 0)) return rc;
     HIPCHK(hipMemcpyAsync(bits_out, e->d_gen, n_bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
+}
+extern "C" int gpsacq_generate_range(gpsacq_engine* e, uint8_t* bits_out, size_t n_bytes, uint64_t first_sample, const gpsacq_sat* sats,
+                                     int n_sats, float noise_sigma, uint64_t seed) {
+    return gpsacq_generate_nav_range(e, bits_out, n_bytes, first_sample, sats, n_sats, nullptr, 0, noise_sigma, seed);
 }
 extern "C" int gpsacq_generate(gpsacq_engine* e, uint8_t* bits_out, size_t n_bytes, const gpsacq_sat* sats, int n_sats,
                                float noise_sigma, uint64_t seed) {
@@ -1297,6 +1326,148 @@ extern "C" int gpsacq_handoff_engine(const gpsacq_engine* e, const gpsacq_peak* 
     if (!e) return fail(GPSACQ_ERR_ARG, "gpsacq_handoff_engine: null engine");
     const bool ref_grid = e->sub == 1 && e->dstride == 1;
     return gpsacq_handoff_step(peak, e->p.fc, e->p.fs, ref_grid ? 0.0 : e->p.fs / N_FFT * e->dstride / e->sub, secs, out);
+}
+
+// ---- tracking channels (track_kernels.hip; the model is in include/gpsacq.h) ----------------------------------------------
+extern "C" int gpsacq_track_default_params(const gpsacq_engine* e, gpsacq_track_params* p) {
+    if (!e || !p) return fail(GPSACQ_ERR_ARG, "gpsacq_track_default_params: null argument");
+    const double fs = e->p.fs, r = (double)e->nlags / 10000.0;
+    const int adj = (int)std::lround(2.0 * std::log2(10000.0 / e->nlags));  // round(log2((10000 / spm)^2))
+    p->lo_ki = 20 + adj;
+    p->lo_kp = 27 + adj;
+    p->ca_ki = 11 + adj;
+    p->ca_kp = 23 + adj;
+    p->fll_k = 25 + adj;
+    p->fll_epochs = 500;
+    p->aid_epoch = -1;
+    p->agc_period = 250;
+    p->agc_lo = (int64_t)std::floor(1200.0 * 1200.0 * r * r);
+    p->agc_hi = (int64_t)std::floor(1400.0 * 1400.0 * r * r);
+    const double two64 = 4294967296.0 * 4294967296.0;
+    p->lo_window = (int64_t)(10000.0 / fs * two64);
+    p->ca_window = (int64_t)(4.0 * 10000.0 / 1540.0 / fs * two64);
+    p->min_epoch = e->nlags / 2;
+    p->max_epoch = 2 * e->nlags;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_track_start(const gpsacq_engine* e, int prn, const gpsacq_peak* peak, uint64_t block_first_sample,
+                                  const gpsacq_track_params* params, gpsacq_track_chan* ch) {
+    if (!e || !peak || !ch || prn < 1 || prn > GPSACQ_NUM_SATS) return fail(GPSACQ_ERR_ARG, "gpsacq_track_start: bad argument");
+    gpsacq_track_params p;
+    if (params) p = *params;
+    else if (int rc = gpsacq_track_default_params(e, &p)) return rc;
+    gpsacq_handoff_t h;
+    if (int rc = gpsacq_handoff_engine(e, peak, 0.0, &h)) return rc;
+    if (peak->ca_shift < 0 || h.ca_rate == 0) return fail(GPSACQ_ERR_ARG, "gpsacq_track_start: bad hit (ca_shift %d)", peak->ca_shift);
+    const uint64_t full = 1023ull << 32;
+    std::memset(ch, 0, sizeof *ch);
+    ch->prn = prn;
+    ch->status = GPSACQ_TRACK_OK;
+    ch->lo_rate = h.lo_rate;
+    ch->ca_rate = h.ca_rate;
+    ch->lo_int = (int64_t)((uint64_t)h.lo_rate << 32);
+    ch->ca_int = (int64_t)((uint64_t)h.ca_rate << 32);
+    ch->lo_nom = (int64_t)((uint64_t)(uint32_t)(e->p.fc / e->p.fs * 4294967296.0) << 32);
+    ch->ca_nom = (int64_t)((uint64_t)(uint32_t)(1.023e6 / e->p.fs * 4294967296.0) << 32);
+    ch->fll_left = p.fll_epochs;
+    // the prompt position at block_first_sample is ca_shift samples of the code NCO; then the pause to the next code epoch
+    const uint64_t pos = ((uint64_t)peak->ca_shift * h.ca_rate) % full;
+    const uint64_t n0 = (full - pos + h.ca_rate - 1) / h.ca_rate;
+    ch->next_sample = block_first_sample + n0;
+    ch->lo_phase = (uint32_t)((block_first_sample + n0) * (uint64_t)h.lo_rate);
+    ch->ca_pos = pos + n0 * h.ca_rate - full;
+    return GPSACQ_OK;
+}
+
+static int track_check_params(const gpsacq_track_params& p) {
+    const int sh[] = {p.lo_ki - 1, p.lo_kp - 1, p.ca_ki, p.ca_kp, p.fll_k};  // the carrier shifts must stay >= 0 with gain_adj = -1
+    for (int v : sh)
+        if (v < 0 || v > 62) return fail(GPSACQ_ERR_ARG, "gpsacq_track: a loop shift is outside [0, 62] (lo_ki/lo_kp >= 1)");
+    if (p.min_epoch < 1 || p.max_epoch < p.min_epoch || p.max_epoch >= 32768 || p.lo_window < 0 || p.ca_window < 0)
+        return fail(GPSACQ_ERR_ARG, "gpsacq_track: need 1 <= min_epoch <= max_epoch < 32768 and windows >= 0");
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_track_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, uint64_t first_sample, gpsacq_track_chan* chans,
+                                   int n_chans, const gpsacq_track_params* params, void* d_prompt, void* d_records, int max_epochs,
+                                   int32_t* n_epochs_out) {
+    if (!e || !d_bits || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
+        return fail(GPSACQ_ERR_ARG, "gpsacq_track: bad argument");
+    if (((uintptr_t)d_bits & 3) || (first_sample & 7)) return fail(GPSACQ_ERR_ARG, "gpsacq_track: bits must be 4-byte aligned, first_sample a multiple of 8");
+    gpsacq_track_params p;
+    if (params) p = *params;
+    else if (int rc = gpsacq_track_default_params(e, &p)) return rc;
+    if (int rc = track_check_params(p)) return rc;
+    for (int c = 0; c < n_chans; ++c) {
+        const gpsacq_track_chan& ch = chans[c];
+        if (ch.prn < 1 || ch.prn > GPSACQ_NUM_SATS || ch.ca_rate == 0 || ch.ca_pos >= (1023ull << 32) || ch.pwr_pos < 0 || ch.pwr_pos > 7)
+            return fail(GPSACQ_ERR_ARG, "gpsacq_track: channel %d is not a valid state", c);
+        if (ch.next_sample < first_sample)
+            return fail(GPSACQ_ERR_ARG, "gpsacq_track: channel %d continues at sample %llu, before the window's first sample %llu", c,
+                        (unsigned long long)ch.next_sample, (unsigned long long)first_sample);
+    }
+    HIPCHK(hipSetDevice(e->p.device));
+    if (!e->d_track_chips) {
+        std::vector<uint32_t> chips(32 * 32, 0u);
+        for (int sv = 0; sv < GPSACQ_NUM_SATS; ++sv) {
+            CaCode ca(kTaps[sv][0], kTaps[sv][1]);
+            for (int i = 0; i < 1023; ++i) {
+                if (ca.chip()) chips[sv * 32 + (i >> 5)] |= 1u << (i & 31);
+                ca.clock();
+            }
+        }
+        HIPCHK(hipMalloc((void**)&e->d_track_chips, chips.size() * sizeof(uint32_t)));
+        HIPCHK(hipMemcpy(e->d_track_chips, chips.data(), chips.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (int rc = grow(e->d_chans, e->chans_cap, (size_t)n_chans, e->stream)) return rc;
+    if (int rc = grow(e->d_track_n, e->track_n_cap, (size_t)n_chans, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_chans, chans, n_chans * sizeof(gpsacq_track_chan), hipMemcpyHostToDevice, e->stream));
+    TrackArgs a{};
+    a.bits = (const uint8_t*)d_bits;
+    a.n_bytes = n_bytes;
+    a.first_sample = first_sample;
+    a.chans = e->d_chans;
+    a.n_chans = n_chans;
+    a.prm = p;
+    a.chips = e->d_track_chips;
+    a.prompt = (int32_t*)d_prompt;
+    a.records = (gpsacq_track_record*)d_records;
+    a.max_epochs = max_epochs;
+    a.n_epochs = e->d_track_n;
+    launch_track(a, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(chans, e->d_chans, n_chans * sizeof(gpsacq_track_chan), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(n_epochs_out, e->d_track_n, n_chans * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_track(gpsacq_engine* e, const uint8_t* bits, size_t n_bytes, uint64_t first_sample, gpsacq_track_chan* chans,
+                            int n_chans, const gpsacq_track_params* params, int32_t* prompt, gpsacq_track_record* records,
+                            int max_epochs, int32_t* n_epochs_out) {
+    if (!e || !bits || n_bytes == 0 || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
+        return fail(GPSACQ_ERR_ARG, "gpsacq_track: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t per = (size_t)n_chans * (size_t)max_epochs;
+    if (int rc = grow(e->d_gen, e->gen_cap, n_bytes, e->stream)) return rc;
+    if (prompt && per)
+        if (int rc = grow(e->d_prompt, e->prompt_cap, 2 * per, e->stream)) return rc;
+    if (records && per)
+        if (int rc = grow(e->d_records, e->records_cap, per, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_gen, bits, n_bytes, hipMemcpyHostToDevice, e->stream));
+    if (int rc = gpsacq_track_device(e, e->d_gen, n_bytes, first_sample, chans, n_chans, params, prompt && per ? e->d_prompt : nullptr,
+                                     records && per ? e->d_records : nullptr, max_epochs, n_epochs_out))
+        return rc;
+    // only the epochs each channel ran are defined; copy them row by row
+    for (int c = 0; c < n_chans; ++c) {
+        const size_t ne = (size_t)n_epochs_out[c], r = (size_t)c * max_epochs;
+        if (!ne) continue;
+        if (prompt) HIPCHK(hipMemcpyAsync(prompt + 2 * r, e->d_prompt + 2 * r, 2 * ne * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        if (records) HIPCHK(hipMemcpyAsync(records + r, e->d_records + r, ne * sizeof(gpsacq_track_record), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
 }
 
 extern "C" int gpsacq_search_code(int sv, int g1) {

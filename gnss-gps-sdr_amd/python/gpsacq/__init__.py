@@ -62,13 +62,33 @@ class Sat(ctypes.Structure):
                 ("code_phase_samples", ctypes.c_double), ("carrier_phase_cycles", ctypes.c_double)]
 
 
+# tracking channels and NAV data (include/gpsacq.h, "Tracking channels and NAV data")
+TRACK_OK, TRACK_LOST = 0, 1
+TRACK_CHAN_DTYPE = np.dtype([("prn", "<i4"), ("status", "<i4"), ("next_sample", "<u8"), ("lo_phase", "<u4"), ("lo_rate", "<u4"),
+                             ("lo_int", "<i8"), ("ca_pos", "<u8"), ("ca_rate", "<u4"), ("epoch", "<i4"), ("ca_int", "<i8"),
+                             ("lo_nom", "<i8"), ("ca_nom", "<i8"), ("gain_adj", "<i4"), ("pwr_pos", "<i4"), ("pwr", "<i8", (8,)),
+                             ("prev_ip", "<i4"), ("prev_qp", "<i4"), ("fll_left", "<i4"), ("reserved", "<i4")])
+TRACK_RECORD_DTYPE = np.dtype([("sample", "<u8"), ("ie", "<i4"), ("qe", "<i4"), ("ip", "<i4"), ("qp", "<i4"), ("il", "<i4"),
+                               ("ql", "<i4"), ("lo_rate", "<u4"), ("ca_rate", "<u4")])
+SUBFRAME_DTYPE = np.dtype([("bit_offset", "<i4"), ("inverted", "<i4"), ("words", "<u4", (10,)), ("id", "<i4"), ("tow", "<i4")])
+
+
+class TrackParams(ctypes.Structure):
+    _fields_ = [("lo_ki", ctypes.c_int32), ("lo_kp", ctypes.c_int32), ("ca_ki", ctypes.c_int32), ("ca_kp", ctypes.c_int32),
+                ("fll_k", ctypes.c_int32), ("fll_epochs", ctypes.c_int32), ("aid_epoch", ctypes.c_int32), ("agc_period", ctypes.c_int32),
+                ("agc_lo", ctypes.c_int64), ("agc_hi", ctypes.c_int64), ("lo_window", ctypes.c_int64), ("ca_window", ctypes.c_int64),
+                ("min_epoch", ctypes.c_int32), ("max_epoch", ctypes.c_int32)]
+
+
 EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range", "gpsacq_generate_range_device", "gpsacq_generate_sig", "gpsacq_sig_bytes", "gpsacq_handoff", "gpsacq_iq8_to_bits", "gpsacq_iq8_to_bits_device", "gpsacq_create", "gpsacq_destroy", "gpsacq_last_error", "gpsacq_get_info", "gpsacq_search",
            "gpsacq_search_device", "gpsacq_set_doppler_window", "gpsacq_set_cell_handout", "gpsacq_set_doppler_step", "gpsacq_set_noncoherent", "gpsacq_set_creep_compensation", "gpsacq_set_block_alignment", "gpsacq_aligned_stride", "gpsacq_synchronize", "gpsacq_last_timing", "gpsacq_timing_ago", "gpsacq_stream", "gpsacq_search_code",
            "gpsacq_sample_spectrum", "gpsacq_code_spectrum", "gpsacq_multi_create", "gpsacq_multi_destroy",
            "gpsacq_multi_set_doppler_step", "gpsacq_multi_get_info", "gpsacq_multi_search_grid", "gpsacq_multi_search_blocks",
            "gpsacq_pipe_buffer", "gpsacq_pipe_submit", "gpsacq_pipe_collect", "gpsacq_search_iq8", "gpsacq_search_iq8_device",
            "gpsacq_iq8_accumulate_sums", "gpsacq_handoff_step", "gpsacq_handoff_engine", "gpsacq_reserve", "gpsacq_multi_last_call_ms",
-           "gpsacq_sig_tx_samples", "gpsacq_generate_sig_tx", "gpsacq_peak_keys_device", "gpsacq_cycle_stamp_device"]
+           "gpsacq_sig_tx_samples", "gpsacq_generate_sig_tx", "gpsacq_peak_keys_device", "gpsacq_cycle_stamp_device",
+           "gpsacq_track_default_params", "gpsacq_track_start", "gpsacq_track", "gpsacq_track_device", "gpsacq_nav_bits",
+           "gpsacq_nav_subframes", "gpsacq_generate_nav_range", "gpsacq_generate_nav_range_device"]
 
 _lib = None
 
@@ -202,6 +222,23 @@ def load_library(path=None):
     lib.gpsacq_cycle_stamp_device.restype = ctypes.c_int
     lib.gpsacq_multi_last_call_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
     lib.gpsacq_multi_last_call_ms.restype = ctypes.c_int
+    lib.gpsacq_track_default_params.argtypes = [vp, ctypes.POINTER(TrackParams)]
+    lib.gpsacq_track_default_params.restype = ctypes.c_int
+    lib.gpsacq_track_start.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint64, ctypes.POINTER(TrackParams), vp]
+    lib.gpsacq_track_start.restype = ctypes.c_int
+    lib.gpsacq_track.argtypes = [vp, vp, sz, ctypes.c_uint64, vp, ctypes.c_int, ctypes.POINTER(TrackParams), vp, vp, ctypes.c_int, vp]
+    lib.gpsacq_track.restype = ctypes.c_int
+    lib.gpsacq_track_device.argtypes = [vp, vp, sz, ctypes.c_uint64, vp, ctypes.c_int, ctypes.POINTER(TrackParams), vp, vp, ctypes.c_int, vp]
+    lib.gpsacq_track_device.restype = ctypes.c_int
+    lib.gpsacq_nav_bits.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.gpsacq_nav_bits.restype = ctypes.c_int
+    lib.gpsacq_nav_subframes.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.gpsacq_nav_subframes.restype = ctypes.c_int
+    lib.gpsacq_generate_nav_range.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.POINTER(Sat), ctypes.c_int, vp, ctypes.c_int, ctypes.c_float, ctypes.c_uint64]
+    lib.gpsacq_generate_nav_range.restype = ctypes.c_int
+    lib.gpsacq_generate_nav_range_device.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.POINTER(Sat), ctypes.c_int, vp, ctypes.c_int, ctypes.c_float,
+                                                     ctypes.c_uint64, ctypes.c_int]
+    lib.gpsacq_generate_nav_range_device.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -228,6 +265,31 @@ def handoff(peak, fc, fs, secs_since_sample=0.0, step_hz=0.0):
     h = Handoff()
     _check(lib, lib.gpsacq_handoff_step(pk.ctypes.data_as(ctypes.c_void_p), float(fc), float(fs), float(step_hz), float(secs_since_sample), ctypes.byref(h)))
     return {k: getattr(h, k) for k, _ in Handoff._fields_}
+
+
+def nav_bits(ip, first_epoch=0, sync_epochs=0):
+    """gpsacq_nav_bits: bit sync on the prompt I arm, then one NAV bit (0/1, 1 = negative I) per whole 20-epoch window.
+    Returns (bits uint8 array, epoch where bit 0 starts); (empty array, -1) when there is no bit sync."""
+    lib = load_library()
+    a = np.ascontiguousarray(np.asarray(ip, dtype=np.int32))
+    out = np.zeros(a.size // 20 + 1, dtype=np.uint8)
+    e0, nb = ctypes.c_int(), ctypes.c_int()
+    rc = lib.gpsacq_nav_bits(a.ctypes.data_as(ctypes.c_void_p), int(a.size), int(first_epoch), int(sync_epochs),
+                             out.ctypes.data_as(ctypes.c_void_p), int(out.size), ctypes.byref(e0), ctypes.byref(nb))
+    if rc != 0:
+        return np.zeros(0, dtype=np.uint8), -1
+    return out[:nb.value].copy(), e0.value
+
+
+def nav_subframes(bits):
+    """gpsacq_nav_subframes: (SUBFRAME_DTYPE array, parity failures) of a 0/1 bit stream."""
+    lib = load_library()
+    b = np.ascontiguousarray(np.asarray(bits, dtype=np.uint8))
+    out = np.zeros(b.size // 300 + 1, dtype=SUBFRAME_DTYPE)
+    n, nf = ctypes.c_int(), ctypes.c_int()
+    _check(lib, lib.gpsacq_nav_subframes(b.ctypes.data_as(ctypes.c_void_p), int(b.size), out.ctypes.data_as(ctypes.c_void_p), int(out.size),
+                                         ctypes.byref(n), ctypes.byref(nf)))
+    return out[:n.value].copy(), nf.value
 
 
 def search_code(sv, g1):
@@ -448,14 +510,79 @@ class Engine:
             arr[i] = Sat(int(prn), float(amp), float(dop), float(ca), float(ph))
         return arr
 
-    def generate(self, n_bytes, sats=(), noise_sigma=1.0, seed=1, first_sample=0):
+    def generate(self, n_bytes, sats=(), noise_sigma=1.0, seed=1, first_sample=0, nav=None):
         """Synthetic 1-bit real-IF capture made on the device: sats = [(prn, amplitude, doppler_hz,
         code_phase_samples, carrier_phase_cycles), ...] on top of white noise (gps_sig_gen.m's role).  first_sample (a multiple
-        of 8): the n_bytes that start there in the stream -- any range of one capture, bit for bit."""
+        of 8): the n_bytes that start there in the stream -- any range of one capture, bit for bit.  nav: None, or
+        [len(sats)][n_nav_bits] navigation bits +-1 (gpsacq_generate_nav_range: 20 code periods per bit, repeating)."""
         out = np.zeros(int(n_bytes), dtype=np.uint8)
-        _check(self._lib, self._lib.gpsacq_generate_range(self._h, out.ctypes.data_as(ctypes.c_void_p), int(n_bytes), int(first_sample),
-                                                          self._sats(sats), len(sats), float(noise_sigma), int(seed)))
+        if nav is None:
+            _check(self._lib, self._lib.gpsacq_generate_range(self._h, out.ctypes.data_as(ctypes.c_void_p), int(n_bytes), int(first_sample),
+                                                              self._sats(sats), len(sats), float(noise_sigma), int(seed)))
+            return out
+        nv = np.ascontiguousarray(np.asarray(nav, dtype=np.int8).reshape(len(sats), -1))
+        _check(self._lib, self._lib.gpsacq_generate_nav_range(self._h, out.ctypes.data_as(ctypes.c_void_p), int(n_bytes), int(first_sample),
+                                                              self._sats(sats), len(sats), nv.ctypes.data_as(ctypes.c_void_p), int(nv.shape[1]),
+                                                              float(noise_sigma), int(seed)))
         return out
+
+    # ---- tracking channels ----------------------------------------------------------------
+    def track_params(self, **overrides):
+        """gpsacq_track_default_params for this engine's fs, with any field overridden by name."""
+        p = TrackParams()
+        _check(self._lib, self._lib.gpsacq_track_default_params(self._h, ctypes.byref(p)))
+        for k, v in overrides.items():
+            if k not in dict(TrackParams._fields_):
+                raise KeyError(f"no tracking parameter {k!r}")
+            setattr(p, k, int(v))
+        return p
+
+    def _params(self, params):
+        if params is None:
+            return self.track_params()
+        if isinstance(params, dict):
+            return self.track_params(**params)
+        return params
+
+    def track_start(self, prn, peak, block_first_sample, params=None, **overrides):
+        """gpsacq_track_start: a channel (TRACK_CHAN_DTYPE, shape (1,)) for PRN `prn` from a search hit (a PEAK_DTYPE record) of the
+        block that starts at absolute sample block_first_sample."""
+        p = self._params(params) if not overrides else self.track_params(**overrides)
+        pk = np.zeros(1, dtype=PEAK_DTYPE)
+        pk[0] = peak
+        ch = np.zeros(1, dtype=TRACK_CHAN_DTYPE)
+        _check(self._lib, self._lib.gpsacq_track_start(self._h, int(prn), pk.ctypes.data_as(ctypes.c_void_p), int(block_first_sample),
+                                                       ctypes.byref(p), ch.ctypes.data_as(ctypes.c_void_p)))
+        return ch
+
+    def track(self, bits, chans, first_sample=0, max_epochs=None, records=False, params=None):
+        """gpsacq_track over a window (bytes / uint8 array of samples first_sample.. ).  chans: TRACK_CHAN_DTYPE array, updated in
+        place.  Returns (prompt int32 [n_chans][max_epochs][2], records [n_chans][max_epochs] or None, n_epochs int32 [n_chans]);
+        only the first n_epochs[c] rows of channel c are defined."""
+        buf = np.ascontiguousarray(np.frombuffer(bits, dtype=np.uint8) if not isinstance(bits, np.ndarray) else bits.view(np.uint8))
+        if chans.dtype != TRACK_CHAN_DTYPE or not chans.flags.c_contiguous:
+            raise TypeError("chans must be a contiguous TRACK_CHAN_DTYPE array")
+        if max_epochs is None:
+            max_epochs = int(buf.size * 8 // max(1, self.num_lags // 2)) + 1
+        p = self._params(params)
+        n = chans.size
+        prompt = np.zeros((n, max_epochs, 2), dtype=np.int32)
+        rec = np.zeros((n, max_epochs), dtype=TRACK_RECORD_DTYPE) if records else None
+        ne = np.zeros(n, dtype=np.int32)
+        _check(self._lib, self._lib.gpsacq_track(self._h, buf.ctypes.data_as(ctypes.c_void_p), int(buf.size), int(first_sample),
+                                                 chans.ctypes.data_as(ctypes.c_void_p), int(n), ctypes.byref(p),
+                                                 prompt.ctypes.data_as(ctypes.c_void_p), rec.ctypes.data_as(ctypes.c_void_p) if records else None,
+                                                 int(max_epochs), ne.ctypes.data_as(ctypes.c_void_p)))
+        return prompt, rec, ne
+
+    def track_device(self, d_bits_ptr, n_bytes, chans, first_sample=0, max_epochs=0, d_prompt_ptr=None, d_records_ptr=None, params=None):
+        """gpsacq_track_device: the capture window and the outputs in device memory; chans (host) updated in place.  Returns n_epochs."""
+        p = self._params(params)
+        ne = np.zeros(chans.size, dtype=np.int32)
+        _check(self._lib, self._lib.gpsacq_track_device(self._h, d_bits_ptr, int(n_bytes), int(first_sample), chans.ctypes.data_as(ctypes.c_void_p),
+                                                        int(chans.size), ctypes.byref(p), d_prompt_ptr, d_records_ptr, int(max_epochs),
+                                                        ne.ctypes.data_as(ctypes.c_void_p)))
+        return ne
 
     def generate_sig(self, prn, data_bits):
         """gps_sig_gen.m's signal on the device: PRN `prn`, navigation bits +-1 (20 code periods each), 8.184 Msps,

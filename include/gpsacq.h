@@ -36,6 +36,13 @@
  *   gpsacq_generate_sig_tx   gps_sig_gen.m:21-30, the script's int8 complex-baseband file for HackRF replay
  *   gpsacq_handoff           CHANNEL::Start()'s NCO set-up from a search hit, c/channel.cpp:134-163
  *                            (the first consumer of the search result in the online receiver)
+ *   gpsacq_track_start       CHANNEL::Start() + Reset(), c/channel.cpp:104-163: a tracking channel's state from a search hit
+ *   gpsacq_track             the FPGA's early/prompt/late integrate-and-dump and the embedded CPU's 1 kHz PI loops
+ *                            ("Homemade GPS Receiver", sections "Hardware / software split" and after), plus the host's
+ *                            AGC (CHANNEL::CheckPower(), c/channel.cpp:265-288) and code-aided carrier reset (:199-206)
+ *   gpsacq_nav_bits          the FPGA's NAV bit decision (sign of the I arm over a 20-epoch bit)
+ *   gpsacq_nav_subframes     CHANNEL::ParityCheck(), c/channel.cpp:329-353, with the IS-GPS-200 Table 20-XIV parity
+ *   gpsacq_generate_nav_range  gpsacq_generate_range with navigation data on every satellite
  *   gpsacq_sample_spectrum   Sample()'s fwd_buf      c/search_offline.cpp:161 (parity probe)
  *   gpsacq_code_spectrum     SearchInit()'s code[sv] c/search_offline.cpp:105-106 (parity probe)
  *
@@ -438,6 +445,153 @@ GPSACQ_API int gpsacq_multi_search_blocks(gpsacq_multi* m, const uint8_t* bits, 
  * merge were enqueued (what the calling thread costs the devices; flat in the number of devices), total_ms = the whole call;
  * rccl_allreduces = ncclAllReduce groups issued by this handle so far (0 when no communicator exists).  Any pointer may be NULL. */
 GPSACQ_API int gpsacq_multi_last_call_ms(const gpsacq_multi* m, double* enqueue_ms, double* total_ms, int64_t* rccl_allreduces);
+
+/*
+ * ---- Tracking channels and NAV data (offline, on a recorded 1-bit real-IF capture) ----------------------------------------
+ *
+ * THE CHANNEL MODEL.  Integer arithmetic only; the kernel (csrc/track_kernels.hip) and the CPU model of the tests
+ * (tests/c/track_model.c) are both written from this text, and agree bit for bit.  "mod 2^N" arithmetic is unsigned
+ * wrap-around; the int64 fields below are two's-complement bit patterns of that arithmetic.  spm = samples per millisecond
+ * (gpsacq_info.num_lags).  The sample stream is the one gpsacq_search() reads: sample m is bit m % 8 of byte m / 8, 1 = negative.
+ * Chip values come from the C/A table of the engine (1 = chip value -1).
+ *
+ * One EPOCH is one code period.  It covers samples [s, s + n), s = next_sample, n = ceil((1023 * 2^32 - ca_pos) / ca_rate).
+ * For sample s + j (0 <= j < n):
+ *   carrier phase  ph = lo_phase + j * lo_rate (mod 2^32);  cos bit = bit31(ph) ^ bit30(ph),  sin bit = !bit31(ph)
+ *                  (the bits are the signs of cos(2 pi ph) and of -sin(2 pi ph): the mix is x * exp(-i 2 pi ph), so a
+ *                  signal ahead of the NCO gives Q > 0)
+ *   prompt         P = ca_pos + j * ca_rate  (always < 1023 * 2^32);  early E = P + 2^31, late L = P - 2^31, each wrapped
+ *                  into [0, 1023 * 2^32);  the chip at position X is chip[X >> 32]
+ *   sums           I_X = sum (1 - 2 (x ^ chip_X ^ cos bit)),  Q_X = sum (1 - 2 (x ^ chip_X ^ sin bit)),  X in E, P, L
+ * After the epoch:  lo_phase += n * lo_rate (mod 2^32);  ca_pos += n * ca_rate - 1023 * 2^32;  next_sample += n;  epoch += 1.
+ * Then, with k = the epoch count just reached:
+ *   AGC (c/channel.cpp:265-288)  if k % agc_period == 0: pwr[pwr_pos] = IP^2 + QP^2, pwr_pos = (pwr_pos + 1) % 8;
+ *                  S = sum of the 8 entries (zeros at start);  gain_adj != 0: S < 8 agc_lo -> gain_adj = 0;
+ *                  gain_adj == 0: S > 8 agc_hi -> gain_adj = -1.  The carrier shifts are lo_ki + gain_adj, lo_kp + gain_adj.
+ *   carrier        while fll_left > 0 (FLL pull-in, then fll_left -= 1):
+ *                      dot = IP' IP + QP' QP,  cross = IP' QP - QP' IP  (IP', QP' = the previous epoch's prompt, 0 at start)
+ *                      e = sign(dot) * cross;  lo_int += e * 2^fll_k;  lo_rate = lo_int >> 32
+ *                  else (Costas):  e = IP * QP;  lo_int += e * 2^(lo_ki + gain_adj);  lo_rate = (lo_int + e * 2^(lo_kp + gain_adj)) >> 32
+ *                  then IP' = IP, QP' = QP.
+ *   code (DLL)     e = (IE^2 + QE^2) - (IL^2 + QL^2);  ca_int += e * 2^ca_ki;  ca_rate = (ca_int + e * 2^ca_kp) >> 32
+ *                  (early stronger = the signal's code is ahead = raise the rate)
+ *   aid            if k == aid_epoch (c/channel.cpp:199-206, L1 / 1.023 MHz = 1540):
+ *                      lo_int = lo_nom + (ca_int - ca_nom) * 1540;  lo_rate = lo_int >> 32
+ *   window         the channel is LOST (status = GPSACQ_TRACK_LOST, it runs no further epoch) when |lo_int - lo_nom| or
+ *                  |(lo_rate << 32) - lo_nom| exceeds lo_window, or |ca_int - ca_nom| or |(ca_rate << 32) - ca_nom| exceeds
+ *                  ca_window (differences as signed 64-bit), or when the next epoch's n is outside [min_epoch, max_epoch].
+ * ">> 32" keeps bits 32..63 of the 64-bit sum as the new 32-bit rate word.
+ */
+#define GPSACQ_TRACK_OK 0
+#define GPSACQ_TRACK_LOST 1
+typedef struct {
+    int32_t prn;            /* 1..32 */
+    int32_t status;         /* GPSACQ_TRACK_OK / GPSACQ_TRACK_LOST */
+    uint64_t next_sample;   /* absolute sample index where the next epoch starts */
+    uint32_t lo_phase;      /* carrier NCO phase at next_sample, cycles * 2^32 */
+    uint32_t lo_rate;       /* carrier NCO word, cycles per sample * 2^32 */
+    int64_t lo_int;         /* carrier PI integrator, cycles per sample * 2^64 (mod 2^64) */
+    uint64_t ca_pos;        /* prompt code position at next_sample, chips * 2^32, in [0, 1023 * 2^32) */
+    uint32_t ca_rate;       /* code NCO word, chips per sample * 2^32 */
+    int32_t epoch;          /* epochs run since gpsacq_track_start */
+    int64_t ca_int;         /* code PI integrator, chips per sample * 2^64 */
+    int64_t lo_nom;         /* nominal carrier word, fc / fs: (uint64)(uint32)(fc / fs * 2^32) << 32 */
+    int64_t ca_nom;         /* nominal code word, 1.023 MHz / fs, the same way */
+    int32_t gain_adj;       /* AGC: 0 or -1 */
+    int32_t pwr_pos;        /* next slot of the power ring */
+    int64_t pwr[8];         /* power ring, IP^2 + QP^2 */
+    int32_t prev_ip, prev_qp; /* previous epoch's prompt (FLL) */
+    int32_t fll_left;       /* FLL epochs still to run */
+    int32_t reserved;
+} gpsacq_track_chan;        /* 160 bytes */
+
+/* Loop settings; gpsacq_track_default_params() fills them for the engine's fs and every field may then be changed.
+ * Defaults: the reference's 10 MHz shifts (c/channel.cpp:104-130: lo ki/kp 20/27, ca ki/kp 11/23) plus
+ * round(log2((10000 / spm)^2)) -- both discriminators scale with the square of the correlation amplitude, which scales with spm;
+ * fll_k 25 at 10 MHz the same way; fll_epochs 500; aid_epoch -1 (off: the FLL covers the up-to-half-bin error of the hit);
+ * agc_period 250 (4 polls per second, :201), agc_lo / agc_hi = floor(1200^2 (spm / 10000)^2), floor(1400^2 (spm / 10000)^2);
+ * lo_window = 10 kHz, ca_window = 4 x 10 kHz / 1540 (26 Hz), both in the * 2^64 units of the integrators;
+ * min_epoch / max_epoch = spm / 2, 2 spm.  Every shift must lie in [0, 62]. */
+typedef struct {
+    int32_t lo_ki, lo_kp, ca_ki, ca_kp, fll_k;
+    int32_t fll_epochs;
+    int32_t aid_epoch;      /* < 0: no aid */
+    int32_t agc_period;
+    int64_t agc_lo, agc_hi;
+    int64_t lo_window, ca_window;
+    int32_t min_epoch, max_epoch;
+} gpsacq_track_params;      /* 72 bytes */
+
+/* One record per epoch (optional output of gpsacq_track): where it started, its six sums, and the NCO words it ran at. */
+typedef struct {
+    uint64_t sample;
+    int32_t ie, qe, ip, qp, il, ql;
+    uint32_t lo_rate, ca_rate;
+} gpsacq_track_record;      /* 40 bytes */
+
+GPSACQ_API int gpsacq_track_default_params(const gpsacq_engine* e, gpsacq_track_params* params);
+/*
+ * A channel for PRN prn (1..32) from a search hit (host arithmetic; CHANNEL::Start(), c/channel.cpp:134-163).  peak: the hit of a search whose block
+ * started at absolute sample block_first_sample, on the engine's current Doppler grid (gpsacq_handoff_engine gives lo_rate and
+ * ca_rate).  By the generator's law (gpsacq_sat) the prompt position at block_first_sample is ca_shift * 1.023e6 / fs chips: the
+ * channel starts there at ca_pos = ca_shift * ca_rate (mod 1023 * 2^32) and lo_phase = block_first_sample * lo_rate (mod 2^32), then
+ * pauses (c/channel.cpp:162-163) to the next code epoch: next_sample advances by n = ceil((1023 * 2^32 - ca_pos) / ca_rate) with the
+ * NCOs, so that every epoch it runs is a whole one.  lo_int = lo_rate << 32, ca_int = ca_rate << 32, fll_left = params->fll_epochs.
+ * params NULL: the defaults.
+ */
+GPSACQ_API int gpsacq_track_start(const gpsacq_engine* e, int prn, const gpsacq_peak* peak, uint64_t block_first_sample,
+                                  const gpsacq_track_params* params, gpsacq_track_chan* chan);
+/*
+ * Run channels over a window of the capture: bits[n_bytes] holds samples first_sample .. first_sample + 8 n_bytes - 1
+ * (first_sample a multiple of 8).  Every channel needs first_sample <= next_sample (GPSACQ_ERR_ARG otherwise); each runs every
+ * epoch that ends inside the window, at most max_epochs, and stops early when LOST.  chans[n_chans] are read and written back,
+ * so a later call on a window that starts at or before each next_sample continues them.  Outputs: prompt[n_chans][max_epochs][2]
+ * (IP, QP of the epochs of this call; may be NULL), records[n_chans][max_epochs] (may be NULL), n_epochs_out[n_chans] (epochs
+ * run by this call).  params NULL: the defaults.  One wave64 per channel on the device; the _device form takes device pointers
+ * for bits (4-byte aligned), prompt and records, host pointers for the rest, and returns after completion.
+ */
+GPSACQ_API int gpsacq_track(gpsacq_engine* e, const uint8_t* bits, size_t n_bytes, uint64_t first_sample, gpsacq_track_chan* chans,
+                            int n_chans, const gpsacq_track_params* params, int32_t* prompt, gpsacq_track_record* records,
+                            int max_epochs, int32_t* n_epochs_out);
+GPSACQ_API int gpsacq_track_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, uint64_t first_sample, gpsacq_track_chan* chans,
+                                   int n_chans, const gpsacq_track_params* params, void* d_prompt, void* d_records, int max_epochs,
+                                   int32_t* n_epochs_out);
+/*
+ * NAV bits from the prompt I arm (host only).  ip[n_epochs] are consecutive epochs, the first being epoch first_epoch of the channel.
+ * Bit sync: over the first sync_epochs epochs (all if <= 0 or more than given), the sign changes between epochs k-1 and k are
+ * counted in bin (first_epoch + k) % 20; the fullest bin wins (ties to the lowest), and if it holds fewer than twice the
+ * runner-up, or no change was seen, there is no sync: returns GPSACQ_ERR_ARG with *n_bits = 0.  Then one bit per whole 20-epoch
+ * window that starts at an epoch of the winning bin: 1 if the summed ip < 0, else 0 (the sign of the I arm; 180 degrees
+ * ambiguous, resolved by the preamble).  bits[max_bits]; *bit_epoch0 = the channel epoch where bit 0 starts.
+ */
+GPSACQ_API int gpsacq_nav_bits(const int32_t* ip, int n_epochs, int first_epoch, int sync_epochs, uint8_t* bits, int max_bits,
+                               int* bit_epoch0, int* n_bits);
+/* one subframe found by gpsacq_nav_subframes */
+typedef struct {
+    int32_t bit_offset;     /* index of its first bit in the stream */
+    int32_t inverted;       /* 1: found through the inverted preamble */
+    uint32_t words[10];     /* the ten 24-bit data words d1..d24 (d1 = bit 23), D30* already removed */
+    int32_t id;             /* subframe ID: word 2 bits 20-22 */
+    int32_t tow;            /* TOW count: word 2 bits 1-17 */
+} gpsacq_subframe;          /* 56 bytes */
+/*
+ * Subframes of a bit stream (0/1 per byte), scanned like CHANNEL::ParityCheck() (c/channel.cpp:329-353): at position i an upright
+ * preamble 10001011 sets D29* = D30* = 0, an inverted one 01110100 sets both to 1, else i += 1.  Then ten 30-bit words are checked
+ * with the parity equations of IS-GPS-200 Table 20-XIV (d_k = D_k ^ D30*, D29*, D30* of the previous word carried on); all pass: a
+ * subframe, i += 300; word w (0-based) fails: *n_parity_fail += 1, i += 30 (w + 1).  Scanning stops when fewer than 300 bits are
+ * left.  out[max_out] (more are counted in *n_out but not written).
+ */
+GPSACQ_API int gpsacq_nav_subframes(const uint8_t* bits, int n_bits, gpsacq_subframe* out, int max_out, int* n_out, int* n_parity_fail);
+/*
+ * gpsacq_generate_range with navigation data: satellite s is multiplied by nav[s * n_nav_bits + (floor(q / 20460) mod n_nav_bits)]
+ * (+1 / -1), q being the chip count of gpsacq_generate's law (floor((m + code_phase) * 1.023e6 (1 + doppler / L1) / fs)), so a bit
+ * lasts 20 code periods and bit 0 starts at q = 0.  nav == NULL: exactly gpsacq_generate_range.
+ */
+GPSACQ_API int gpsacq_generate_nav_range(gpsacq_engine* e, uint8_t* bits_out, size_t n_bytes, uint64_t first_sample, const gpsacq_sat* sats,
+                                         int n_sats, const int8_t* nav, int n_nav_bits, float noise_sigma, uint64_t seed);
+GPSACQ_API int gpsacq_generate_nav_range_device(gpsacq_engine* e, void* d_bits_out, size_t n_bytes, uint64_t first_sample,
+                                                const gpsacq_sat* sats, int n_sats, const int8_t* nav, int n_nav_bits, float noise_sigma,
+                                                uint64_t seed, int sync);
 
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);
