@@ -1331,8 +1331,13 @@ extern "C" int gpsacq_handoff_engine(const gpsacq_engine* e, const gpsacq_peak* 
 // ---- tracking channels (track_kernels.hip; the model is in include/gpsacq.h) ----------------------------------------------
 extern "C" int gpsacq_track_default_params(const gpsacq_engine* e, gpsacq_track_params* p) {
     if (!e || !p) return fail(GPSACQ_ERR_ARG, "gpsacq_track_default_params: null argument");
+    // above 40 MHz num_lags saturates at N_FFT = 40000 and is no longer samples per millisecond: no defaults can be built from it
+    if (e->p.fs > 40.0e6) return fail(GPSACQ_ERR_UNSUPPORTED, "gpsacq_track_default_params: fs %.0f Hz is above 40 MHz", e->p.fs);
     const double fs = e->p.fs, r = (double)e->nlags / 10000.0;
-    const int adj = (int)std::lround(2.0 * std::log2(10000.0 / e->nlags));  // round(log2((10000 / spm)^2))
+    // round(log2((10000 / spm)^2)) up to 10 MHz; above it round(log2((10000 / spm)^3)): a step of the NCO word is worth fs / 2^32 Hz,
+    // so with the square rule the loops' bandwidth in Hz grows with fs (at 40 MHz the Costas loop no longer holds the phase)
+    const double octaves = std::log2(10000.0 / e->nlags);
+    const int adj = (int)std::lround((e->nlags > 10000 ? 3.0 : 2.0) * octaves);
     p->lo_ki = 20 + adj;
     p->lo_kp = 27 + adj;
     p->ca_ki = 11 + adj;
@@ -1347,7 +1352,7 @@ extern "C" int gpsacq_track_default_params(const gpsacq_engine* e, gpsacq_track_
     p->lo_window = (int64_t)(10000.0 / fs * two64);
     p->ca_window = (int64_t)(4.0 * 10000.0 / 1540.0 / fs * two64);
     p->min_epoch = e->nlags / 2;
-    p->max_epoch = 2 * e->nlags;
+    p->max_epoch = std::min(2 * e->nlags, 65535);  // the kernel packs two counts <= max_epoch per 32-bit word
     return GPSACQ_OK;
 }
 
@@ -1384,8 +1389,8 @@ static int track_check_params(const gpsacq_track_params& p) {
     const int sh[] = {p.lo_ki - 1, p.lo_kp - 1, p.ca_ki, p.ca_kp, p.fll_k};  // the carrier shifts must stay >= 0 with gain_adj = -1
     for (int v : sh)
         if (v < 0 || v > 62) return fail(GPSACQ_ERR_ARG, "gpsacq_track: a loop shift is outside [0, 62] (lo_ki/lo_kp >= 1)");
-    if (p.min_epoch < 1 || p.max_epoch < p.min_epoch || p.max_epoch >= 32768 || p.lo_window < 0 || p.ca_window < 0)
-        return fail(GPSACQ_ERR_ARG, "gpsacq_track: need 1 <= min_epoch <= max_epoch < 32768 and windows >= 0");
+    if (p.min_epoch < 1 || p.max_epoch < p.min_epoch || p.max_epoch > 65535 || p.lo_window < 0 || p.ca_window < 0)
+        return fail(GPSACQ_ERR_ARG, "gpsacq_track: need 1 <= min_epoch <= max_epoch <= 65535 and windows >= 0");
     return GPSACQ_OK;
 }
 

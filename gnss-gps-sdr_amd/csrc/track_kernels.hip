@@ -8,7 +8,7 @@
 // Layout: TRACK_WAVES independent channels per workgroup, no barrier in the epoch loop.  Each epoch's samples are cut into
 // 32-sample words of the window; lane l takes words l, l + 64, ...  Per word it builds five 32-bit masks (cos, -sin, early,
 // prompt, late chips) one sample at a time from the NCO words and takes six popcounts against the sample word.  The six counts
-// of ones are packed in pairs (each fits 16 bits: 2 spm < 65536) and summed over the wave with xor shuffles; every lane then runs
+// of ones are packed in pairs (each fits 16 bits: each count <= n <= max_epoch <= 65535) and summed over the wave with xor shuffles; every lane then runs
 // the same integer loop update, and lane 0 writes the outputs with plain stores.  All arithmetic is integer: the result does not
 // depend on the order of the sums.
 #include <hip/hip_runtime.h>
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(64 * TRACK_WAVES) void k_track(TrackArgs a) {
         uint32_t ones[6] = {0, 0, 0, 0, 0, 0};  // IE QE IP QP IL QL: samples whose product is -1
         for (uint64_t wi = w0 + lane; wi <= w1; wi += 64) {
             const uint32_t x = load_word(a.bits, a.n_bytes, wi);
-            const int j0 = (int)((int64_t)(wi * 32) - (int64_t)o);  // epoch sample index of bit 0 of this word (> -32, < 2 spm)
+            const int j0 = (int)((int64_t)(wi * 32) - (int64_t)o);  // epoch sample index of bit 0 of this word (> -32, < max_epoch)
             uint32_t cm = 0, sm = 0, em = 0, pm = 0, lm = 0, valid = 0;
 #pragma unroll 8
             for (int b = 0; b < 32; ++b) {

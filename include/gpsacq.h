@@ -507,11 +507,13 @@ typedef struct {
 
 /* Loop settings; gpsacq_track_default_params() fills them for the engine's fs and every field may then be changed.
  * Defaults: the reference's 10 MHz shifts (c/channel.cpp:104-130: lo ki/kp 20/27, ca ki/kp 11/23) plus
- * round(log2((10000 / spm)^2)) -- both discriminators scale with the square of the correlation amplitude, which scales with spm;
+ * round(log2((10000 / spm)^2)) -- both discriminators scale with the square of the correlation amplitude, which scales with spm --
+ * and above spm = 10000 round(log2((10000 / spm)^3)), as one step of an NCO word is also worth fs / 2^32 more Hz;
  * fll_k 25 at 10 MHz the same way; fll_epochs 500; aid_epoch -1 (off: the FLL covers the up-to-half-bin error of the hit);
  * agc_period 250 (4 polls per second, :201), agc_lo / agc_hi = floor(1200^2 (spm / 10000)^2), floor(1400^2 (spm / 10000)^2);
  * lo_window = 10 kHz, ca_window = 4 x 10 kHz / 1540 (26 Hz), both in the * 2^64 units of the integrators;
- * min_epoch / max_epoch = spm / 2, 2 spm.  Every shift must lie in [0, 62]. */
+ * min_epoch / max_epoch = spm / 2, min(2 spm, 65535).  Every shift must lie in [0, 62]; 1 <= min_epoch <= max_epoch <= 65535.
+ * Above fs = 40 MHz there are no defaults (GPSACQ_ERR_UNSUPPORTED: spm would no longer be samples per millisecond). */
 typedef struct {
     int32_t lo_ki, lo_kp, ca_ki, ca_kp, fll_k;
     int32_t fll_epochs;
