@@ -22,6 +22,7 @@
 #include "iq_launch.hpp"
 #include "gen_launch.hpp"
 #include "track_launch.hpp"
+#include "track_iq_launch.hpp"
 
 using namespace acq;
 
@@ -115,6 +116,8 @@ struct gpsacq_engine {
     size_t prompt_cap = 0;
     gpsacq_track_record* d_records = nullptr;
     size_t records_cap = 0;
+    hipEvent_t tiq_ev[3] = {};  // gpsacq_track_iq8*: before the conversion, between it and the channels, after them
+    bool tiq_timed = false;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;
@@ -241,6 +244,8 @@ extern "C" void gpsacq_destroy(gpsacq_engine* e) {
     for (auto& set : e->ev)
         for (auto& ev : set)
             if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : e->tiq_ev)
+        if (ev) (void)hipEventDestroy(ev);
     if (e->copy_stream) (void)hipStreamSynchronize(e->copy_stream);
     for (auto& sl : e->pipe) {
         if (sl.h_in) (void)hipHostFree(sl.h_in);
@@ -1394,16 +1399,24 @@ static int track_check_params(const gpsacq_track_params& p) {
     return GPSACQ_OK;
 }
 
-extern "C" int gpsacq_track_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, uint64_t first_sample, gpsacq_track_chan* chans,
-                                   int n_chans, const gpsacq_track_params* params, void* d_prompt, void* d_records, int max_epochs,
-                                   int32_t* n_epochs_out) {
-    if (!e || !d_bits || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
-        return fail(GPSACQ_ERR_ARG, "gpsacq_track: bad argument");
-    if (((uintptr_t)d_bits & 3) || (first_sample & 7)) return fail(GPSACQ_ERR_ARG, "gpsacq_track: bits must be 4-byte aligned, first_sample a multiple of 8");
-    gpsacq_track_params p;
-    if (params) p = *params;
-    else if (int rc = gpsacq_track_default_params(e, &p)) return rc;
-    if (int rc = track_check_params(p)) return rc;
+// the C/A chip table of the channels (and of the 8-bit IQ generator), built on first use
+static int ensure_track_chips(gpsacq_engine* e) {
+    if (e->d_track_chips) return GPSACQ_OK;
+    std::vector<uint32_t> chips(32 * 32, 0u);
+    for (int sv = 0; sv < GPSACQ_NUM_SATS; ++sv) {
+        CaCode ca(kTaps[sv][0], kTaps[sv][1]);
+        for (int i = 0; i < 1023; ++i) {
+            if (ca.chip()) chips[sv * 32 + (i >> 5)] |= 1u << (i & 31);
+            ca.clock();
+        }
+    }
+    HIPCHK(hipMalloc((void**)&e->d_track_chips, chips.size() * sizeof(uint32_t)));
+    HIPCHK(hipMemcpy(e->d_track_chips, chips.data(), chips.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return GPSACQ_OK;
+}
+
+// what every gpsacq_track* call does before its kernel: the channel states are checked and uploaded to e->d_chans ...
+static int track_prepare(gpsacq_engine* e, uint64_t first_sample, const gpsacq_track_chan* chans, int n_chans) {
     for (int c = 0; c < n_chans; ++c) {
         const gpsacq_track_chan& ch = chans[c];
         if (ch.prn < 1 || ch.prn > GPSACQ_NUM_SATS || ch.ca_rate == 0 || ch.ca_pos >= (1023ull << 32) || ch.pwr_pos < 0 || ch.pwr_pos > 7)
@@ -1413,21 +1426,22 @@ extern "C" int gpsacq_track_device(gpsacq_engine* e, const void* d_bits, size_t 
                         (unsigned long long)ch.next_sample, (unsigned long long)first_sample);
     }
     HIPCHK(hipSetDevice(e->p.device));
-    if (!e->d_track_chips) {
-        std::vector<uint32_t> chips(32 * 32, 0u);
-        for (int sv = 0; sv < GPSACQ_NUM_SATS; ++sv) {
-            CaCode ca(kTaps[sv][0], kTaps[sv][1]);
-            for (int i = 0; i < 1023; ++i) {
-                if (ca.chip()) chips[sv * 32 + (i >> 5)] |= 1u << (i & 31);
-                ca.clock();
-            }
-        }
-        HIPCHK(hipMalloc((void**)&e->d_track_chips, chips.size() * sizeof(uint32_t)));
-        HIPCHK(hipMemcpy(e->d_track_chips, chips.data(), chips.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
+    if (int rc = ensure_track_chips(e)) return rc;
     if (int rc = grow(e->d_chans, e->chans_cap, (size_t)n_chans, e->stream)) return rc;
     if (int rc = grow(e->d_track_n, e->track_n_cap, (size_t)n_chans, e->stream)) return rc;
     HIPCHK(hipMemcpyAsync(e->d_chans, chans, n_chans * sizeof(gpsacq_track_chan), hipMemcpyHostToDevice, e->stream));
+    return GPSACQ_OK;
+}
+// ... and after it: states and epoch counts back, wait
+static int track_collect(gpsacq_engine* e, gpsacq_track_chan* chans, int n_chans, int32_t* n_epochs_out) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(chans, e->d_chans, n_chans * sizeof(gpsacq_track_chan), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(n_epochs_out, e->d_track_n, n_chans * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+static void track_launch_bits(gpsacq_engine* e, const void* d_bits, size_t n_bytes, uint64_t first_sample, int n_chans, const gpsacq_track_params& p,
+                              void* d_prompt, void* d_records, int max_epochs) {
     TrackArgs a{};
     a.bits = (const uint8_t*)d_bits;
     a.n_bytes = n_bytes;
@@ -1441,9 +1455,31 @@ extern "C" int gpsacq_track_device(gpsacq_engine* e, const void* d_bits, size_t 
     a.max_epochs = max_epochs;
     a.n_epochs = e->d_track_n;
     launch_track(a, e->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(chans, e->d_chans, n_chans * sizeof(gpsacq_track_chan), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(n_epochs_out, e->d_track_n, n_chans * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+}
+
+extern "C" int gpsacq_track_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, uint64_t first_sample, gpsacq_track_chan* chans,
+                                   int n_chans, const gpsacq_track_params* params, void* d_prompt, void* d_records, int max_epochs,
+                                   int32_t* n_epochs_out) {
+    if (!e || !d_bits || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
+        return fail(GPSACQ_ERR_ARG, "gpsacq_track: bad argument");
+    if (((uintptr_t)d_bits & 3) || (first_sample & 7)) return fail(GPSACQ_ERR_ARG, "gpsacq_track: bits must be 4-byte aligned, first_sample a multiple of 8");
+    gpsacq_track_params p;
+    if (params) p = *params;
+    else if (int rc = gpsacq_track_default_params(e, &p)) return rc;
+    if (int rc = track_check_params(p)) return rc;
+    if (int rc = track_prepare(e, first_sample, chans, n_chans)) return rc;
+    track_launch_bits(e, d_bits, n_bytes, first_sample, n_chans, p, d_prompt, d_records, max_epochs);
+    return track_collect(e, chans, n_chans, n_epochs_out);
+}
+
+// only the epochs each channel ran are defined; copy them row by row
+static int track_rows_to_host(gpsacq_engine* e, int n_chans, int max_epochs, const int32_t* n_epochs, int32_t* prompt, gpsacq_track_record* records) {
+    for (int c = 0; c < n_chans; ++c) {
+        const size_t ne = (size_t)n_epochs[c], r = (size_t)c * max_epochs;
+        if (!ne) continue;
+        if (prompt) HIPCHK(hipMemcpyAsync(prompt + 2 * r, e->d_prompt + 2 * r, 2 * ne * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        if (records) HIPCHK(hipMemcpyAsync(records + r, e->d_records + r, ne * sizeof(gpsacq_track_record), hipMemcpyDeviceToHost, e->stream));
+    }
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -1464,13 +1500,209 @@ extern "C" int gpsacq_track(gpsacq_engine* e, const uint8_t* bits, size_t n_byte
     if (int rc = gpsacq_track_device(e, e->d_gen, n_bytes, first_sample, chans, n_chans, params, prompt && per ? e->d_prompt : nullptr,
                                      records && per ? e->d_records : nullptr, max_epochs, n_epochs_out))
         return rc;
-    // only the epochs each channel ran are defined; copy them row by row
-    for (int c = 0; c < n_chans; ++c) {
-        const size_t ne = (size_t)n_epochs_out[c], r = (size_t)c * max_epochs;
-        if (!ne) continue;
-        if (prompt) HIPCHK(hipMemcpyAsync(prompt + 2 * r, e->d_prompt + 2 * r, 2 * ne * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-        if (records) HIPCHK(hipMemcpyAsync(records + r, e->d_records + r, ne * sizeof(gpsacq_track_record), hipMemcpyDeviceToHost, e->stream));
+    return track_rows_to_host(e, n_chans, max_epochs, n_epochs_out, prompt, records);
+}
+
+// ---- tracking channels on an 8-bit IQ capture (track_iq_kernels.hip; include/gpsacq.h) -------------------------------------
+extern "C" int gpsacq_track_default_params_iq8(const gpsacq_engine* e, double sample_rms, gpsacq_track_params* p) {
+    if (!e || !p) return fail(GPSACQ_ERR_ARG, "gpsacq_track_default_params_iq8: null argument");
+    if (!(sample_rms > 0) || !std::isfinite(sample_rms)) return fail(GPSACQ_ERR_UNSUPPORTED, "gpsacq_track_default_params_iq8: sample_rms %g", sample_rms);
+    if (int rc = gpsacq_track_default_params(e, p)) return rc;
+    int g = (int)std::lround(std::log2((double)GPSACQ_TRACK_IQ8_GAIN * sample_rms * sample_rms));
+    // every shift stays in [0, 62], the carrier's in [1, 62] (gain_adj = -1)
+    const int lo = std::min(std::min(p->lo_ki, p->lo_kp) - 1, std::min(std::min(p->ca_ki, p->ca_kp), p->fll_k));
+    const int hi = std::max(std::max(p->lo_ki, p->lo_kp), std::max(std::max(p->ca_ki, p->ca_kp), p->fll_k));
+    g = std::max(g, hi - 62);
+    if (g > lo) return fail(GPSACQ_ERR_UNSUPPORTED, "gpsacq_track_default_params_iq8: sample_rms %g needs shifts below 0", sample_rms);
+    p->lo_ki -= g, p->lo_kp -= g, p->ca_ki -= g, p->ca_kp -= g, p->fll_k -= g;
+    const double s = std::ldexp(1.0, g);
+    p->agc_lo = (int64_t)std::floor((double)p->agc_lo * s);
+    p->agc_hi = (int64_t)std::floor((double)p->agc_hi * s);
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_iq8_accumulate_power(const gpsacq_engine* e, const void* iq, size_t n_samples, int format, uint64_t power[2]) {
+    (void)e;  // host arithmetic: no device, the engine may be NULL
+    if (!iq || !power || n_samples == 0) return fail(GPSACQ_ERR_ARG, "gpsacq_iq8_accumulate_power: bad argument");
+    if (format != GPSACQ_IQ_U8 && format != GPSACQ_IQ_S8) return fail(GPSACQ_ERR_ARG, "unknown IQ format %d", format);
+    const uint8_t* b = (const uint8_t*)iq;
+    uint64_t pi = 0, pq = 0;
+    for (size_t s = 0; s < n_samples; ++s) {
+        const int vi = format == GPSACQ_IQ_S8 ? (int)(int8_t)b[2 * s] : (int)b[2 * s] - 128;
+        const int vq = format == GPSACQ_IQ_S8 ? (int)(int8_t)b[2 * s + 1] : (int)b[2 * s + 1] - 128;
+        pi += (uint64_t)(vi * vi);
+        pq += (uint64_t)(vq * vq);
     }
+    power[0] += pi;
+    power[1] += pq;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_track_start_iq8(const gpsacq_engine* e, const gpsacq_iq8_input* in, int prn, const gpsacq_peak* peak,
+                                      uint64_t block_first_sample, const gpsacq_track_params* params, gpsacq_track_chan* ch) {
+    if (!e || !in) return fail(GPSACQ_ERR_ARG, "gpsacq_track_start_iq8: null argument");
+    Capture cap;
+    if (int rc = iq8_capture(e, in, nullptr, 0, &cap)) return rc;
+    gpsacq_track_params p;  // the 1-bit defaults stand in where only fll_epochs is read
+    if (params) p = *params;
+    else if (int rc = gpsacq_track_default_params(e, &p)) return rc;
+    if (int rc = gpsacq_track_start(e, prn, peak, block_first_sample, &p, ch)) return rc;
+    if (in->multibit == GPSACQ_SAMPLES_SIGN) return GPSACQ_OK;
+    // the carrier in the raw capture: the search saw it turned by +mix_hz and (unless complex baseband) through Sample()'s LO at fc
+    gpsacq_handoff_t h;
+    if (int rc = gpsacq_handoff_engine(e, peak, 0.0, &h)) return rc;
+    const double f = h.lo_dop_hz - in->mix_hz + (in->multibit == GPSACQ_SAMPLES_COMPLEX ? 0.0 : e->p.fc);
+    if (!(std::fabs(f) < e->p.fs / 2)) return fail(GPSACQ_ERR_ARG, "gpsacq_track_start_iq8: carrier %g Hz outside +-fs / 2 = %g", f, e->p.fs / 2);
+    const uint32_t word = (uint32_t)(int64_t)std::llround(f / e->p.fs * 4294967296.0);
+    ch->lo_rate = word;
+    ch->lo_int = ch->lo_nom = (int64_t)((uint64_t)word << 32);
+    ch->lo_phase = (uint32_t)(ch->next_sample * (uint64_t)word);
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_track_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, uint64_t first_sample,
+                                       gpsacq_track_chan* chans, int n_chans, const gpsacq_track_params* params, void* d_prompt,
+                                       void* d_records, int max_epochs, int32_t* n_epochs_out) {
+    if (!e || !d_iq || n_samples == 0 || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
+        return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: bad argument");
+    Capture cap;
+    if (int rc = iq8_capture(e, in, d_iq, 0, &cap)) return rc;
+    if ((uintptr_t)d_iq & 15) return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: IQ buffer must be 16-byte aligned");
+    const bool sign = in->multibit == GPSACQ_SAMPLES_SIGN;
+    if (sign && (first_sample & 7))
+        return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: first_sample %llu is not a multiple of 8 (sign mode runs on the 1-bit stream's byte grid)",
+                    (unsigned long long)first_sample);
+    gpsacq_track_params p;
+    if (params) p = *params;
+    else if (!sign) return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: multi-bit channels need params (gpsacq_track_default_params_iq8)");
+    else if (int rc = gpsacq_track_default_params(e, &p)) return rc;
+    if (int rc = track_check_params(p)) return rc;
+    if (int rc = track_prepare(e, first_sample, chans, n_chans)) return rc;
+    for (auto& ev : e->tiq_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    e->tiq_timed = false;
+    HIPCHK(hipEventRecord(e->tiq_ev[0], e->stream));
+    if (sign) {
+        // the window as the 1-bit stream the scripts would have written, in engine scratch; then the 1-bit channels on it
+        const size_t n_bytes = (n_samples + 7) / 8;
+        if (int rc = grow(e->d_iqbits, e->iqbits_cap, n_bytes, e->stream)) return rc;
+        const size_t left = cap.iq_total > cap.iq_first ? cap.iq_total - cap.iq_first : 0;  // samples of the capture from iq[0] on
+        if (left < n_samples) HIPCHK(hipMemsetAsync(e->d_iqbits, 0, n_bytes, e->stream));
+        if (int rc = iq8_to_bits_enqueue(e, (const uint8_t*)d_iq, std::min(n_samples, left), cap.iq, cap.iq_first, e->d_iqbits)) return rc;
+        HIPCHK(hipEventRecord(e->tiq_ev[1], e->stream));
+        track_launch_bits(e, e->d_iqbits, n_bytes, first_sample, n_chans, p, d_prompt, d_records, max_epochs);
+    } else {
+        HIPCHK(hipEventRecord(e->tiq_ev[1], e->stream));
+        TrackIqArgs a{};
+        a.iq = (const uint8_t*)d_iq;
+        a.n_samples = n_samples;
+        a.first_sample = first_sample;
+        a.flip = in->format == GPSACQ_IQ_U8 ? 0x80808080u : 0u;
+        a.dc_i = in->remove_dc ? (int32_t)std::nearbyint(in->mean_i) : 0;
+        a.dc_q = in->remove_dc ? (int32_t)std::nearbyint(in->mean_q) : 0;
+        if (std::abs(a.dc_i) > 128 || std::abs(a.dc_q) > 128) return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: mean (%g, %g) outside +-128", in->mean_i, in->mean_q);
+        a.chans = e->d_chans;
+        a.n_chans = n_chans;
+        a.prm = p;
+        a.chips = e->d_track_chips;
+        a.prompt = (int32_t*)d_prompt;
+        a.records = (gpsacq_track_record*)d_records;
+        a.max_epochs = max_epochs;
+        a.n_epochs = e->d_track_n;
+        launch_track_iq(a, e->stream);
+    }
+    HIPCHK(hipEventRecord(e->tiq_ev[2], e->stream));
+    if (int rc = track_collect(e, chans, n_chans, n_epochs_out)) return rc;
+    e->tiq_timed = true;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_track_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, uint64_t first_sample,
+                                gpsacq_track_chan* chans, int n_chans, const gpsacq_track_params* params, int32_t* prompt,
+                                gpsacq_track_record* records, int max_epochs, int32_t* n_epochs_out) {
+    if (!e || !iq || n_samples == 0 || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
+        return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t per = (size_t)n_chans * (size_t)max_epochs;
+    if (int rc = grow(e->d_iq, e->iq_cap, 2 * n_samples + 16, e->stream)) return rc;
+    if (prompt && per)
+        if (int rc = grow(e->d_prompt, e->prompt_cap, 2 * per, e->stream)) return rc;
+    if (records && per)
+        if (int rc = grow(e->d_records, e->records_cap, per, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * n_samples, hipMemcpyHostToDevice, e->stream));
+    if (int rc = gpsacq_track_iq8_device(e, in, e->d_iq, n_samples, first_sample, chans, n_chans, params, prompt && per ? e->d_prompt : nullptr,
+                                         records && per ? e->d_records : nullptr, max_epochs, n_epochs_out))
+        return rc;
+    return track_rows_to_host(e, n_chans, max_epochs, n_epochs_out, prompt, records);
+}
+
+extern "C" int gpsacq_track_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* track_ms) {
+    if (!e || !e->tiq_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8_last_ms: no finished gpsacq_track_iq8 call");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (convert_ms) HIPCHK(hipEventElapsedTime(convert_ms, e->tiq_ev[0], e->tiq_ev[1]));
+    if (track_ms) HIPCHK(hipEventElapsedTime(track_ms, e->tiq_ev[1], e->tiq_ev[2]));
+    return GPSACQ_OK;
+}
+
+// 8-bit complex capture at a residual IF (k_generate_iq8): gpsacq_generate_nav_range's law, any sample range
+extern "C" int gpsacq_generate_iq8_range_device(gpsacq_engine* e, void* d_iq, size_t n_samples, uint64_t first_sample, int format, double if_hz,
+                                                float scale, const gpsacq_sat* sats, int n_sats, const int8_t* nav, int n_nav,
+                                                float noise_sigma, uint64_t seed, int sync) {
+    if (!e || !d_iq || n_samples == 0 || n_sats < 0 || (n_sats > 0 && !sats) || !(scale > 0)) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_iq8_range: bad argument");
+    if (format != GPSACQ_IQ_U8 && format != GPSACQ_IQ_S8) return fail(GPSACQ_ERR_ARG, "unknown IQ format %d", format);
+    if (nav && n_nav <= 0) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_iq8_range: n_nav_bits = %d", n_nav);
+    if ((uintptr_t)d_iq & 1) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_iq8_range: output must be 2-byte aligned");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = ensure_track_chips(e)) return rc;
+    const double L1 = 1575.42e6, CPS = 1.023e6;
+    std::vector<GenSat> gs((size_t)n_sats);
+    for (int i = 0; i < n_sats; ++i) {
+        if (sats[i].prn < 1 || sats[i].prn > GPSACQ_NUM_SATS) return fail(GPSACQ_ERR_ARG, "satellite %d: PRN %d out of 1..32", i, sats[i].prn);
+        gs[i].sv = sats[i].prn - 1;
+        gs[i].amplitude = sats[i].amplitude;
+        gs[i].chips_per_sample = CPS * (1.0 + sats[i].doppler_hz / L1) / e->p.fs;
+        gs[i].code_phase = sats[i].code_phase_samples;
+        gs[i].cycles_per_sample = (if_hz + sats[i].doppler_hz) / e->p.fs;
+        gs[i].carrier_phase = sats[i].carrier_phase_cycles;
+    }
+    if (n_sats > 0) {
+        if (int rc = grow(e->d_sats, e->sats_cap, (size_t)n_sats, e->stream)) return rc;
+        HIPCHK(hipMemcpyAsync(e->d_sats, gs.data(), gs.size() * sizeof(GenSat), hipMemcpyHostToDevice, e->stream));
+        if (nav) {
+            const size_t nn = (size_t)n_sats * n_nav;
+            if (int rc = grow(e->d_nav, e->nav_cap, nn, e->stream)) return rc;
+            HIPCHK(hipMemcpyAsync(e->d_nav, nav, nn, hipMemcpyHostToDevice, e->stream));
+        }
+        HIPCHK(hipStreamSynchronize(e->stream));  // gs goes out of scope
+    }
+    GenIqArgs a{};
+    a.iq = (uint8_t*)d_iq;
+    a.n_samples = n_samples;
+    a.first_sample = first_sample;
+    a.seed = seed;
+    a.sats = e->d_sats;
+    a.n_sats = n_sats;
+    a.noise_sigma = noise_sigma;
+    a.scale = scale;
+    a.offset = format == GPSACQ_IQ_U8 ? 128 : 0;
+    a.nav = nav && n_sats > 0 ? e->d_nav : nullptr;
+    a.n_nav = n_nav;
+    a.chips = e->d_track_chips;
+    launch_generate_iq8(a, e->stream);
+    HIPCHK(hipGetLastError());
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_generate_iq8_range(gpsacq_engine* e, void* iq_out, size_t n_samples, uint64_t first_sample, int format, double if_hz,
+                                         float scale, const gpsacq_sat* sats, int n_sats, const int8_t* nav, int n_nav, float noise_sigma,
+                                         uint64_t seed) {
+    if (!e || !iq_out || n_samples == 0) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_iq8_range: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_gen, e->gen_cap, 2 * n_samples, e->stream)) return rc;
+    if (int rc = gpsacq_generate_iq8_range_device(e, e->d_gen, n_samples, first_sample, format, if_hz, scale, sats, n_sats, nav, n_nav, noise_sigma, seed, 0))
+        return rc;
+    HIPCHK(hipMemcpyAsync(iq_out, e->d_gen, 2 * n_samples, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }

@@ -8,12 +8,25 @@
 //     chan K PRN P status ok|lost epochs E dop_hz D code_hz C bits B
 //     subframe PRN P id I tow T
 //     parity PRN P failures F
+//
+// With GPSACQ_INPUT=iq_u8|iq_s8 in the environment FILE is an 8-bit IQ capture (rtl-sdr / HackRF, README.md:83-115), read the way
+// gps_test reads it (host/search_api.cpp: GPSACQ_MIX_HZ, GPSACQ_IQ_KEEP_DC, GPSACQ_IQ_MULTIBIT, GPSACQ_IQ_COMPLEX; the mean of the
+// whole capture): searched with gpsacq_search_iq8, channels from gpsacq_track_start_iq8, tracked with gpsacq_track_iq8 -- as 1-bit
+// channels on the converted stream, or with GPSACQ_IQ_MULTIBIT / GPSACQ_IQ_COMPLEX as multi-bit complex channels whose loop
+// settings come from the capture's RMS (gpsacq_track_default_params_iq8).  Same output lines.
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../../include/gpsacq.h"
+
+static int env_int(const char* name, int dflt) {
+    const char* v = std::getenv(name);
+    return (v && *v) ? std::atoi(v) : dflt;
+}
 
 int main(int argc, char** argv) {
     if (argc < 4 || argc > 5) {
@@ -30,14 +43,40 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "cannot open %s\n", argv[1]);
         return 66;
     }
+    // input format: the environment gps_test honours
+    const char* fmt = std::getenv("GPSACQ_INPUT");
+    bool iq = false;
+    gpsacq_iq8_input iqin;
+    std::memset(&iqin, 0, sizeof iqin);
+    if (fmt && *fmt && std::strcmp(fmt, "bits") != 0) {
+        if (std::strcmp(fmt, "iq_u8") == 0) iqin.format = GPSACQ_IQ_U8;
+        else if (std::strcmp(fmt, "iq_s8") == 0) iqin.format = GPSACQ_IQ_S8;
+        else {
+            std::fprintf(stderr, "gps_track: GPSACQ_INPUT=%s is not one of bits, iq_u8, iq_s8\n", fmt);
+            std::fclose(fp);
+            return 64;
+        }
+        iq = true;
+        const char* mix = std::getenv("GPSACQ_MIX_HZ");
+        iqin.mix_hz = (mix && *mix) ? std::atof(mix) : 0.0;
+        iqin.fs = prm.fs;
+        iqin.remove_dc = env_int("GPSACQ_IQ_KEEP_DC", 0) ? 0 : 1;
+        iqin.multibit = env_int("GPSACQ_IQ_COMPLEX", 0) ? GPSACQ_SAMPLES_COMPLEX : env_int("GPSACQ_IQ_MULTIBIT", 0) ? GPSACQ_SAMPLES_REAL : GPSACQ_SAMPLES_SIGN;
+    }
+    const size_t block_bytes = iq ? (size_t)GPSACQ_BLOCK_BYTES * 16 : (size_t)GPSACQ_BLOCK_BYTES;  // one Sample(): 40960 samples
     std::fseek(fp, 0, SEEK_END);
     size_t n_bytes = (size_t)std::ftell(fp);
     std::fseek(fp, 0, SEEK_SET);
-    if (secs > 0 && (size_t)(secs * prm.fs / 8) < n_bytes) n_bytes = (size_t)(secs * prm.fs / 8);
+    if (iq) {
+        n_bytes &= ~(size_t)1;
+        if (secs > 0 && (size_t)(secs * prm.fs) * 2 < n_bytes) n_bytes = (size_t)(secs * prm.fs) * 2;
+    } else if (secs > 0 && (size_t)(secs * prm.fs / 8) < n_bytes) n_bytes = (size_t)(secs * prm.fs / 8);
     std::vector<uint8_t> bits(n_bytes);
     n_bytes = std::fread(bits.data(), 1, n_bytes, fp);
     std::fclose(fp);
-    const size_t n_blocks = n_bytes / GPSACQ_BLOCK_BYTES < GPSACQ_NUM_SATS ? n_bytes / GPSACQ_BLOCK_BYTES : GPSACQ_NUM_SATS;
+    if (iq) n_bytes &= ~(size_t)1;
+    const size_t n_samples = iq ? n_bytes / 2 : n_bytes * 8;
+    const size_t n_blocks = n_bytes / block_bytes < GPSACQ_NUM_SATS ? n_bytes / block_bytes : GPSACQ_NUM_SATS;
     if (n_blocks == 0) {
         std::fprintf(stderr, "capture shorter than one block\n");
         return 65;
@@ -49,20 +88,48 @@ int main(int argc, char** argv) {
         return rc;
     }
     std::vector<gpsacq_peak> peaks(n_blocks);
-    rc = gpsacq_search(e, bits.data(), n_blocks, GPSACQ_BLOCK_BYTES, nullptr, n_blocks, nullptr, peaks.data());
+    gpsacq_track_params tp;
+    const gpsacq_track_params* params = nullptr;  // the defaults, except for multi-bit channels
+    if (iq) {
+        // `y = y - mean(y)` is the mean of the capture (proc_rtl_bin_for_gps.m:17); multi-bit loops are set from its RMS
+        iqin.total_samples = n_samples;
+        int64_t sums[2] = {0, 0};
+        uint64_t power[2] = {0, 0};
+        const size_t chunk = (size_t)1 << 24;
+        for (size_t s0 = 0; rc == 0 && s0 < n_samples; s0 += chunk) {
+            const size_t m = n_samples - s0 < chunk ? n_samples - s0 : chunk;
+            if (iqin.remove_dc) rc = gpsacq_iq8_accumulate_sums(e, bits.data() + 2 * s0, m, iqin.format, sums);
+            if (rc == 0 && iqin.multibit) rc = gpsacq_iq8_accumulate_power(e, bits.data() + 2 * s0, m, iqin.format, power);
+        }
+        iqin.mean_i = (double)sums[0] / (double)n_samples;
+        iqin.mean_q = (double)sums[1] / (double)n_samples;
+        if (rc == 0 && iqin.multibit) {
+            // RMS of v = a - dc:  E[a^2] - 2 dc E[a] + dc^2 per arm
+            const double di = iqin.remove_dc ? std::nearbyint(iqin.mean_i) : 0.0, dq = iqin.remove_dc ? std::nearbyint(iqin.mean_q) : 0.0;
+            const double msq = ((double)power[0] + (double)power[1]) / (double)n_samples - 2 * di * iqin.mean_i - 2 * dq * iqin.mean_q + di * di + dq * dq;
+            rc = gpsacq_track_default_params_iq8(e, std::sqrt(msq > 0 ? msq / 2 : 0.0), &tp);
+            params = &tp;
+        }
+        if (rc == 0) rc = gpsacq_search_iq8(e, &iqin, bits.data(), n_blocks, block_bytes, nullptr, n_blocks, nullptr, peaks.data());
+    } else {
+        rc = gpsacq_search(e, bits.data(), n_blocks, GPSACQ_BLOCK_BYTES, nullptr, n_blocks, nullptr, peaks.data());
+    }
     std::vector<gpsacq_track_chan> chans;
     for (size_t b = 0; rc == 0 && b < n_blocks; ++b) {
         if (!(peaks[b].snr > 25.0f)) continue;
         gpsacq_track_chan ch;
-        rc = gpsacq_track_start(e, (int)(b % 32) + 1, &peaks[b], (uint64_t)b * GPSACQ_BLOCK_BYTES * 8, nullptr, &ch);
+        const uint64_t block_first = (uint64_t)b * GPSACQ_BLOCK_BYTES * 8;
+        rc = iq ? gpsacq_track_start_iq8(e, &iqin, (int)(b % 32) + 1, &peaks[b], block_first, params, &ch)
+                : gpsacq_track_start(e, (int)(b % 32) + 1, &peaks[b], block_first, nullptr, &ch);
         chans.push_back(ch);
     }
     gpsacq_info info;
     gpsacq_get_info(e, &info);
-    const int max_epochs = (int)(n_bytes * 8 / (size_t)info.num_lags) + 2;
+    const int max_epochs = (int)(n_samples / (size_t)info.num_lags) + 2;
     std::vector<int32_t> prompt(chans.size() * (size_t)max_epochs * 2), n_ep(chans.size());
     if (rc == 0 && !chans.empty())
-        rc = gpsacq_track(e, bits.data(), n_bytes, 0, chans.data(), (int)chans.size(), nullptr, prompt.data(), nullptr, max_epochs, n_ep.data());
+        rc = iq ? gpsacq_track_iq8(e, &iqin, bits.data(), n_samples, 0, chans.data(), (int)chans.size(), params, prompt.data(), nullptr, max_epochs, n_ep.data())
+                : gpsacq_track(e, bits.data(), n_bytes, 0, chans.data(), (int)chans.size(), nullptr, prompt.data(), nullptr, max_epochs, n_ep.data());
     if (rc) {
         std::fprintf(stderr, "gps_track: %d: %s\n", rc, gpsacq_last_error());
         gpsacq_destroy(e);
@@ -80,8 +147,13 @@ int main(int argc, char** argv) {
         std::vector<uint8_t> nb(n / 20 + 1);
         int e0 = -1, n_bits = 0;
         if (gpsacq_nav_bits(ip.data() + skip, n - skip, first_epoch, 0, nb.data(), (int)nb.size(), &e0, &n_bits) != GPSACQ_OK) n_bits = 0;
+        // Doppler: the carrier word against the IF -- fc, or for a multi-bit channel the signed word against the satellite-free
+        // carrier of the raw capture, fc - mix_hz (complex baseband: -mix_hz)
+        const double dop_hz = iq && iqin.multibit
+                                  ? (int32_t)ch.lo_rate / two32 * prm.fs - ((iqin.multibit == GPSACQ_SAMPLES_COMPLEX ? 0.0 : prm.fc) - iqin.mix_hz)
+                                  : ch.lo_rate / two32 * prm.fs - prm.fc;
         std::printf("chan %zu PRN %d status %s epochs %d dop_hz %.1f code_hz %.3f bits %d\n", c, ch.prn, ch.status ? "lost" : "ok", n,
-                    ch.lo_rate / two32 * prm.fs - prm.fc, ch.ca_rate / two32 * prm.fs, n_bits);
+                    dop_hz, ch.ca_rate / two32 * prm.fs, n_bits);
         std::vector<gpsacq_subframe> sf(n_bits / 300 + 1);
         int n_sf = 0, n_fail = 0;
         gpsacq_nav_subframes(nb.data(), n_bits, sf.data(), (int)sf.size(), &n_sf, &n_fail);

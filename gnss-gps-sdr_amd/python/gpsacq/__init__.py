@@ -88,7 +88,10 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_iq8_accumulate_sums", "gpsacq_handoff_step", "gpsacq_handoff_engine", "gpsacq_reserve", "gpsacq_multi_last_call_ms",
            "gpsacq_sig_tx_samples", "gpsacq_generate_sig_tx", "gpsacq_peak_keys_device", "gpsacq_cycle_stamp_device",
            "gpsacq_track_default_params", "gpsacq_track_start", "gpsacq_track", "gpsacq_track_device", "gpsacq_nav_bits",
-           "gpsacq_nav_subframes", "gpsacq_generate_nav_range", "gpsacq_generate_nav_range_device"]
+           "gpsacq_nav_subframes", "gpsacq_generate_nav_range", "gpsacq_generate_nav_range_device",
+           "gpsacq_track_iq8", "gpsacq_track_iq8_device", "gpsacq_track_iq8_last_ms", "gpsacq_track_start_iq8",
+           "gpsacq_track_default_params_iq8", "gpsacq_iq8_accumulate_power", "gpsacq_generate_iq8_range",
+           "gpsacq_generate_iq8_range_device"]
 
 _lib = None
 
@@ -239,6 +242,25 @@ def load_library(path=None):
     lib.gpsacq_generate_nav_range_device.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.POINTER(Sat), ctypes.c_int, vp, ctypes.c_int, ctypes.c_float,
                                                      ctypes.c_uint64, ctypes.c_int]
     lib.gpsacq_generate_nav_range_device.restype = ctypes.c_int
+    iqp = ctypes.POINTER(Iq8Input)
+    lib.gpsacq_track_iq8.argtypes = [vp, iqp, vp, sz, ctypes.c_uint64, vp, ctypes.c_int, ctypes.POINTER(TrackParams), vp, vp, ctypes.c_int, vp]
+    lib.gpsacq_track_iq8.restype = ctypes.c_int
+    lib.gpsacq_track_iq8_device.argtypes = [vp, iqp, vp, sz, ctypes.c_uint64, vp, ctypes.c_int, ctypes.POINTER(TrackParams), vp, vp, ctypes.c_int, vp]
+    lib.gpsacq_track_iq8_device.restype = ctypes.c_int
+    lib.gpsacq_track_iq8_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    lib.gpsacq_track_iq8_last_ms.restype = ctypes.c_int
+    lib.gpsacq_track_start_iq8.argtypes = [vp, iqp, ctypes.c_int, vp, ctypes.c_uint64, ctypes.POINTER(TrackParams), vp]
+    lib.gpsacq_track_start_iq8.restype = ctypes.c_int
+    lib.gpsacq_track_default_params_iq8.argtypes = [vp, ctypes.c_double, ctypes.POINTER(TrackParams)]
+    lib.gpsacq_track_default_params_iq8.restype = ctypes.c_int
+    lib.gpsacq_iq8_accumulate_power.argtypes = [vp, vp, sz, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+    lib.gpsacq_iq8_accumulate_power.restype = ctypes.c_int
+    lib.gpsacq_generate_iq8_range.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.POINTER(Sat),
+                                              ctypes.c_int, vp, ctypes.c_int, ctypes.c_float, ctypes.c_uint64]
+    lib.gpsacq_generate_iq8_range.restype = ctypes.c_int
+    lib.gpsacq_generate_iq8_range_device.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.POINTER(Sat),
+                                                     ctypes.c_int, vp, ctypes.c_int, ctypes.c_float, ctypes.c_uint64, ctypes.c_int]
+    lib.gpsacq_generate_iq8_range_device.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -583,6 +605,104 @@ class Engine:
                                                         int(chans.size), ctypes.byref(p), d_prompt_ptr, d_records_ptr, int(max_epochs),
                                                         ne.ctypes.data_as(ctypes.c_void_p)))
         return ne
+
+    # ---- tracking channels on an 8-bit IQ capture -----------------------------------------
+    def iq8_power(self, iq, signed=False):
+        """gpsacq_iq8_accumulate_power over a whole buffer: (mean of (I - off)^2, mean of (Q - off)^2), from exact integer sums."""
+        buf = np.ascontiguousarray(np.asarray(iq).view(np.uint8).ravel())
+        n = buf.size // 2
+        pw = (ctypes.c_uint64 * 2)(0, 0)
+        _check(self._lib, self._lib.gpsacq_iq8_accumulate_power(self._h, buf.ctypes.data_as(ctypes.c_void_p), n, 1 if signed else 0, pw))
+        return pw[0] / n, pw[1] / n
+
+    def iq8_rms(self, iq, inp):
+        """RMS of the samples v_i, v_q a multi-bit channel sees (offset and, with inp.remove_dc, the rounded mean removed):
+        what track_params_iq8 wants."""
+        pi, pq = self.iq8_power(iq, signed=inp.format == 1)
+        dci, dcq = (float(np.rint(inp.mean_i)), float(np.rint(inp.mean_q))) if inp.remove_dc else (0.0, 0.0)
+        # E[(a - dc)^2] = E[a^2] - 2 dc E[a] + dc^2, E[a] = the capture's mean
+        return float(np.sqrt(max(0.0, (pi + pq - 2 * dci * inp.mean_i - 2 * dcq * inp.mean_q + dci * dci + dcq * dcq) / 2)))
+
+    def track_params_iq8(self, sample_rms, **overrides):
+        """gpsacq_track_default_params_iq8: the defaults rescaled to the capture's sample RMS, any field overridden by name."""
+        p = TrackParams()
+        _check(self._lib, self._lib.gpsacq_track_default_params_iq8(self._h, float(sample_rms), ctypes.byref(p)))
+        for k, v in overrides.items():
+            if k not in dict(TrackParams._fields_):
+                raise KeyError(f"no tracking parameter {k!r}")
+            setattr(p, k, int(v))
+        return p
+
+    def track_start_iq8(self, inp, prn, peak, block_first_sample, params=None):
+        """gpsacq_track_start_iq8: a channel (TRACK_CHAN_DTYPE, shape (1,)) from a hit of search_iq8 on the capture inp describes;
+        in multi-bit mode its carrier NCO runs at the satellite's frequency in the raw capture (negative ones wrap)."""
+        p = self._params(params)
+        pk = np.zeros(1, dtype=PEAK_DTYPE)
+        pk[0] = peak
+        ch = np.zeros(1, dtype=TRACK_CHAN_DTYPE)
+        _check(self._lib, self._lib.gpsacq_track_start_iq8(self._h, ctypes.byref(inp), int(prn), pk.ctypes.data_as(ctypes.c_void_p),
+                                                           int(block_first_sample), ctypes.byref(p), ch.ctypes.data_as(ctypes.c_void_p)))
+        return ch
+
+    def track_iq8(self, iq, inp, chans, first_sample=0, max_epochs=None, records=False, params=None):
+        """gpsacq_track_iq8 over a window of interleaved 8-bit I,Q bytes (samples first_sample ..).  inp: Engine.iq8_input(...);
+        multibit 0 runs the 1-bit channels on the converted window, else the multi-bit complex channels (params required: see
+        track_params_iq8).  chans updated in place.  Returns (prompt, records or None, n_epochs) as track()."""
+        buf = np.ascontiguousarray(np.asarray(iq).view(np.uint8).ravel())
+        if chans.dtype != TRACK_CHAN_DTYPE or not chans.flags.c_contiguous:
+            raise TypeError("chans must be a contiguous TRACK_CHAN_DTYPE array")
+        n_samples = buf.size // 2
+        if max_epochs is None:
+            max_epochs = int(n_samples // max(1, self.num_lags // 2)) + 1
+        if params is None and inp.multibit:
+            raise ValueError("multi-bit channels need params (track_params_iq8)")
+        p = self._params(params)
+        n = chans.size
+        prompt = np.zeros((n, max_epochs, 2), dtype=np.int32)
+        rec = np.zeros((n, max_epochs), dtype=TRACK_RECORD_DTYPE) if records else None
+        ne = np.zeros(n, dtype=np.int32)
+        _check(self._lib, self._lib.gpsacq_track_iq8(self._h, ctypes.byref(inp), buf.ctypes.data_as(ctypes.c_void_p), int(n_samples), int(first_sample),
+                                                     chans.ctypes.data_as(ctypes.c_void_p), int(n), ctypes.byref(p),
+                                                     prompt.ctypes.data_as(ctypes.c_void_p), rec.ctypes.data_as(ctypes.c_void_p) if records else None,
+                                                     int(max_epochs), ne.ctypes.data_as(ctypes.c_void_p)))
+        return prompt, rec, ne
+
+    def track_iq8_device(self, d_iq_ptr, n_samples, inp, chans, first_sample=0, max_epochs=0, d_prompt_ptr=None, d_records_ptr=None, params=None):
+        """gpsacq_track_iq8_device: the capture window (16-byte aligned) and the outputs in device memory.  Returns n_epochs."""
+        if params is None and inp.multibit:
+            raise ValueError("multi-bit channels need params (track_params_iq8)")
+        p = self._params(params)
+        ne = np.zeros(chans.size, dtype=np.int32)
+        _check(self._lib, self._lib.gpsacq_track_iq8_device(self._h, ctypes.byref(inp), d_iq_ptr, int(n_samples), int(first_sample),
+                                                            chans.ctypes.data_as(ctypes.c_void_p), int(chans.size), ctypes.byref(p), d_prompt_ptr,
+                                                            d_records_ptr, int(max_epochs), ne.ctypes.data_as(ctypes.c_void_p)))
+        return ne
+
+    def track_iq8_last_ms(self):
+        """Device milliseconds of the last track_iq8* call: (8-bit -> 1-bit conversion, channel kernel)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(self._lib, self._lib.gpsacq_track_iq8_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def generate_iq8(self, n_samples, sats=(), if_hz=0.0, scale=16.0, signed=True, noise_sigma=1.0, seed=1, first_sample=0, nav=None):
+        """Synthetic 8-bit complex capture at residual IF if_hz made on the device (gpsacq_generate_iq8_range): generate()'s law with a
+        complex carrier and complex noise, times scale, rounded and clamped.  Returns int8 (signed) or uint8 interleaved I,Q."""
+        out = np.zeros(2 * int(n_samples), dtype=np.uint8)
+        nv = None if nav is None else np.ascontiguousarray(np.asarray(nav, dtype=np.int8).reshape(len(sats), -1))
+        _check(self._lib, self._lib.gpsacq_generate_iq8_range(self._h, out.ctypes.data_as(ctypes.c_void_p), int(n_samples), int(first_sample),
+                                                              1 if signed else 0, float(if_hz), float(scale), self._sats(sats), len(sats),
+                                                              nv.ctypes.data_as(ctypes.c_void_p) if nv is not None else None,
+                                                              int(nv.shape[1]) if nv is not None else 0, float(noise_sigma), int(seed)))
+        return out.view(np.int8) if signed else out
+
+    def generate_iq8_device(self, d_iq_ptr, n_samples, sats=(), if_hz=0.0, scale=16.0, signed=True, noise_sigma=1.0, seed=1, first_sample=0,
+                            nav=None, sync=True):
+        nv = None if nav is None else np.ascontiguousarray(np.asarray(nav, dtype=np.int8).reshape(len(sats), -1))
+        _check(self._lib, self._lib.gpsacq_generate_iq8_range_device(self._h, d_iq_ptr, int(n_samples), int(first_sample), 1 if signed else 0,
+                                                                     float(if_hz), float(scale), self._sats(sats), len(sats),
+                                                                     nv.ctypes.data_as(ctypes.c_void_p) if nv is not None else None,
+                                                                     int(nv.shape[1]) if nv is not None else 0, float(noise_sigma), int(seed),
+                                                                     1 if sync else 0))
 
     def generate_sig(self, prn, data_bits):
         """gps_sig_gen.m's signal on the device: PRN `prn`, navigation bits +-1 (20 code periods each), 8.184 Msps,

@@ -40,6 +40,14 @@
  *   gpsacq_track             the FPGA's early/prompt/late integrate-and-dump and the embedded CPU's 1 kHz PI loops
  *                            ("Homemade GPS Receiver", sections "Hardware / software split" and after), plus the host's
  *                            AGC (CHANNEL::CheckPower(), c/channel.cpp:265-288) and code-aided carrier reset (:199-206)
+ *   gpsacq_track_iq8         the same channels on an 8-bit IQ capture (README.md:83-115's rtl-sdr / HackRF flow carried on past the search):
+ *                            sign mode = the scripts' 1-bit conversion + gpsacq_track, bit for bit; multi-bit mode = complex channels
+ *                            that keep the amplitudes and the quadrature arm (no reference counterpart: its channels are 1-bit)
+ *   gpsacq_track_start_iq8   CHANNEL::Start() for such a channel: the carrier NCO where the satellite sits in the raw capture
+ *   gpsacq_track_default_params_iq8  the loop shifts of c/channel.cpp:104-130 rescaled to the capture's sample RMS
+ *   gpsacq_iq8_accumulate_power  sum(y .* conj(y)) of proc_rtl_bin_for_gps.m's y, as exact integers (for that RMS)
+ *   gpsacq_generate_iq8_range  gpsacq_generate_nav_range's law written as an 8-bit complex capture at a residual IF (no reference
+ *                            counterpart: the reference has no 8-bit generator; rtl-like test files)
  *   gpsacq_nav_bits          the FPGA's NAV bit decision (sign of the I arm over a 20-epoch bit)
  *   gpsacq_nav_subframes     CHANNEL::ParityCheck(), c/channel.cpp:329-353, with the IS-GPS-200 Table 20-XIV parity
  *   gpsacq_generate_nav_range  gpsacq_generate_range with navigation data on every satellite
@@ -594,6 +602,97 @@ GPSACQ_API int gpsacq_generate_nav_range(gpsacq_engine* e, uint8_t* bits_out, si
 GPSACQ_API int gpsacq_generate_nav_range_device(gpsacq_engine* e, void* d_bits_out, size_t n_bytes, uint64_t first_sample,
                                                 const gpsacq_sat* sats, int n_sats, const int8_t* nav, int n_nav_bits, float noise_sigma,
                                                 uint64_t seed, int sync);
+
+/*
+ * ---- Tracking channels on an 8-bit IQ capture ---------------------------------------------------------------------------------
+ *
+ * gpsacq_iq8_input describes the capture as for gpsacq_search_iq8.  Two modes, chosen by in->multibit:
+ *
+ * GPSACQ_SAMPLES_SIGN: the reference's flow (README.md:83-115: convert to a 1-bit file, then run on it), bit for bit.  The window
+ * is converted on the device into engine scratch -- iq_convert.hpp's arithmetic, once per call -- and the 1-bit channels of
+ * gpsacq_track run on it: chans, prompt, records and n_epochs equal gpsacq_iq8_to_bits() of the capture followed by gpsacq_track()
+ * on the same window, byte for byte; no 1-bit stream reaches the host.  in->first_sample is the mixer's n of iq[0] (normally equal
+ * to the window's first_sample), in->total_samples the capture's length (bits past it read 0), in->mean_i / mean_q the mean of the
+ * WHOLE capture.  The window's first_sample must be a multiple of 8 (the byte grid of the 1-bit stream).
+ *
+ * in->multibit != 0 (GPSACQ_SAMPLES_REAL and GPSACQ_SAMPLES_COMPLEX alike): MULTI-BIT COMPLEX CHANNELS (csrc/track_iq_kernels.hip;
+ * CPU model tests/c/track_model_iq.c).  THE CHANNEL MODEL above with the sample and the sums replaced by:
+ *   sample         v_i = I - off - dc_i,  v_q = Q - off - dc_q;  off = 128 for GPSACQ_IQ_U8, 0 for GPSACQ_IQ_S8;  dc_i = nearbyint(mean_i),
+ *                  dc_q = nearbyint(mean_q) (ties to even) when remove_dc, else 0.  Integers: |v| <= 256.  There is no floating-point
+ *                  mixer: mix_hz is NOT applied to the samples, the channel's carrier NCO does that work (gpsacq_track_start_iq8);
+ *                  in->fs, first_sample and total_samples are not read.
+ *   sums           with C = 1 - 2 (cos bit), S = 1 - 2 (sin bit) (the two carrier bits exactly as defined above: the signs of cos
+ *                  and of -sin) and h_X = 1 - 2 chip_X:
+ *                      I_X = sum h_X (v_i C - v_q S),   Q_X = sum h_X (v_i S + v_q C),   X in E, P, L
+ *                  -- the complex sample times the two-level exp(-i 2 pi ph).
+ * Everything else (epoch length, NCO advance, AGC, FLL, Costas, DLL, aid, windows, LOST) is that text unchanged.  With v_q = 0 and
+ * v_i = +-1 (= 1 - 2 x) the sums are the 1-bit model's.  |I_X|, |Q_X| <= 2 * 256 * 65535 < 2^26: gpsacq_track_record and prompt keep
+ * their int32 layouts; the discriminator products are formed in 64 bits and shifted mod 2^64 as above.  The window may start at any
+ * sample.
+ *
+ * gpsacq_track_iq8: iq[2 * n_samples] holds samples first_sample .. first_sample + n_samples - 1 as interleaved I, Q bytes; window
+ * and resume semantics, outputs and params as gpsacq_track (every epoch that ends inside the window, first_sample <= next_sample,
+ * chans read and written back, LOST stops a channel).  params NULL: gpsacq_track_default_params (sign mode) -- in multi-bit mode
+ * params are required (gpsacq_track_default_params_iq8 needs the capture's RMS).  The _device form takes device pointers for iq
+ * (16-byte aligned), prompt and records.
+ */
+GPSACQ_API int gpsacq_track_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, uint64_t first_sample,
+                                gpsacq_track_chan* chans, int n_chans, const gpsacq_track_params* params, int32_t* prompt,
+                                gpsacq_track_record* records, int max_epochs, int32_t* n_epochs_out);
+GPSACQ_API int gpsacq_track_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, uint64_t first_sample,
+                                       gpsacq_track_chan* chans, int n_chans, const gpsacq_track_params* params, void* d_prompt,
+                                       void* d_records, int max_epochs, int32_t* n_epochs_out);
+/* device time of the last gpsacq_track_iq8* call on this engine, milliseconds: the 8-bit -> 1-bit conversion (0 in multi-bit
+ * mode) and the channel kernel.  Either pointer may be NULL. */
+GPSACQ_API int gpsacq_track_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* track_ms);
+/*
+ * A channel from a hit of gpsacq_search_iq8 (host arithmetic).  Sign mode: exactly gpsacq_track_start.  Multi-bit mode: the code
+ * side is gpsacq_track_start's; the carrier NCO runs where the satellite sits IN THE RAW COMPLEX CAPTURE.  The search saw the
+ * capture turned by exp(+2 pi i mix_hz n / fs) (iq_convert.hpp) and then, unless in->multibit == GPSACQ_SAMPLES_COMPLEX, through
+ * Sample()'s LO exp(-2 pi i fc n / fs) (c/search_offline.cpp:143-153: I by the sign of cos, Q by the sign of -sin), so a hit at
+ * lo_dop (gpsacq_handoff_engine) is a raw-capture frequency of
+ *     f = lo_dop - mix_hz + fc        (GPSACQ_SAMPLES_COMPLEX: f = lo_dop - mix_hz, fc plays no part)
+ * f may be negative or near zero: lo_rate and lo_nom >> 32 are the two's-complement word (uint32)(int64)llround(f / fs * 2^32),
+ * lo_int = lo_nom = that word << 32 (the window tests of the model compare signed 64-bit differences, so they hold under the
+ * wrap); |f| must stay below fs / 2.  lo_phase = next_sample * lo_rate (mod 2^32).
+ */
+GPSACQ_API int gpsacq_track_start_iq8(const gpsacq_engine* e, const gpsacq_iq8_input* in, int prn, const gpsacq_peak* peak,
+                                      uint64_t block_first_sample, const gpsacq_track_params* params, gpsacq_track_chan* chan);
+/*
+ * Loop settings for multi-bit channels.  Both discriminators scale with the square of the correlation amplitude, which a 1-bit
+ * capture fixes (the quantiser) and a multi-bit one does not: it scales with the sample RMS.  sample_rms = the RMS of v_i, v_q
+ * over any stretch of the capture (gpsacq_iq8_accumulate_power / samples, less the squared mean when it is removed).  The result
+ * is gpsacq_track_default_params with lo_ki, lo_kp, ca_ki, ca_kp, fll_k lowered by g and agc_lo, agc_hi multiplied by 2^g,
+ *     g = round(log2(GPSACQ_TRACK_IQ8_GAIN * sample_rms^2)),   GPSACQ_TRACK_IQ8_GAIN = 4:
+ * next to a 1-bit channel (prompt sum ~ n a sqrt(2 / pi) (2 / pi) for a signal of amplitude a in unit noise) a complex one at
+ * RMS r collects ~ n a r (4 / pi) -- both arms, no limiter -- 2.5 r times the amplitude, 6.2 r^2 times its square (the CPU model on
+ * synthetic captures gives 6.0 r^2).  A plain g = round(log2(sample_rms^2)) would leave every loop gain about six times a 1-bit
+ * channel's and trip the AGC on the stronger satellites; the constant is therefore two bits more, 4, the power of two nearest
+ * to 6.2, which puts the loops at the 1-bit channels' bandwidths.  g is clamped so that every shift stays in [0, 62] (lo_ki, lo_kp >= 1);
+ * GPSACQ_ERR_UNSUPPORTED if it cannot be (sample_rms <= 0, not finite, or so large that a shift would go negative).
+ */
+#define GPSACQ_TRACK_IQ8_GAIN 4
+GPSACQ_API int gpsacq_track_default_params_iq8(const gpsacq_engine* e, double sample_rms, gpsacq_track_params* params);
+/* adds the exact integer sums of (I - off)^2 and (Q - off)^2 over n_samples of a host buffer to power[0..1] (host arithmetic, e may be NULL;
+ * off as in gpsacq_iq8_accumulate_sums).  RMS of v over N samples: sqrt((power[0] + power[1]) / (2 N) - (dc_i^2 + dc_q^2) / 2). */
+GPSACQ_API int gpsacq_iq8_accumulate_power(const gpsacq_engine* e, const void* iq, size_t n_samples, int format, uint64_t power[2]);
+/*
+ * Synthetic 8-bit complex capture at a residual IF, generated on the device (no reference counterpart; the source of the tests, of
+ * tools/track_bench.py --input iq8 and of rtl-like test files): gpsacq_generate_nav_range's law -- gpsacq_sat, chips and
+ * navigation bits as functions of the absolute sample index m -- with a complex carrier and complex noise,
+ *     I + jQ = clamp(round(scale * (sigma (n_I + j n_Q) + sum a * nav * chip * exp(2 pi i ((if_hz + doppler) / fs * m + phase)))))
+ * n_I, n_Q two independent unit-variance Gaussian streams, round = to nearest (ties to even), clamp to [-127, 127]; written as
+ * interleaved bytes, GPSACQ_IQ_S8 as they are, GPSACQ_IQ_U8 plus 128.  iq_out[2 * n_samples] holds samples first_sample ..
+ * first_sample + n_samples - 1 (any first_sample); deterministic in (seed, arguments).  The engine's fc plays no part.  A search
+ * with mix_hz = fc - if_hz (GPSACQ_SAMPLES_SIGN / _REAL) or mix_hz = -if_hz (GPSACQ_SAMPLES_COMPLEX) reports lo_shift =
+ * round(doppler * 40000 / fs) and the code phase of gpsacq_generate.  nav == NULL: no data.
+ */
+GPSACQ_API int gpsacq_generate_iq8_range(gpsacq_engine* e, void* iq_out, size_t n_samples, uint64_t first_sample, int format, double if_hz,
+                                         float scale, const gpsacq_sat* sats, int n_sats, const int8_t* nav, int n_nav_bits,
+                                         float noise_sigma, uint64_t seed);
+GPSACQ_API int gpsacq_generate_iq8_range_device(gpsacq_engine* e, void* d_iq_out, size_t n_samples, uint64_t first_sample, int format,
+                                                double if_hz, float scale, const gpsacq_sat* sats, int n_sats, const int8_t* nav,
+                                                int n_nav_bits, float noise_sigma, uint64_t seed, int sync);
 
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);
