@@ -24,7 +24,7 @@ $(LIBDIR)/libgpsacq.so: $(CSRC)/acq_kernels.hip $(CSRC)/key_kernels.hip $(CSRC)/
 	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/gen_kernels.hip -o $(LIBDIR)/gen_kernels.o
 	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/track_kernels.hip -o $(LIBDIR)/track_kernels.o
 	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/track_iq_kernels.hip -o $(LIBDIR)/track_iq_kernels.o
-	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/gpsacq_track.cpp -o $(LIBDIR)/gpsacq_track.o
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $(CSRC)/gpsacq_track.cpp -o $(LIBDIR)/gpsacq_track.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(LIBDIR)/acq_kernels.o $(LIBDIR)/key_kernels.o $(LIBDIR)/iq_kernels.o $(LIBDIR)/gen_kernels.o $(LIBDIR)/track_kernels.o $(LIBDIR)/track_iq_kernels.o $(LIBDIR)/gpsacq_engine.o $(LIBDIR)/gpsacq_multi.o $(LIBDIR)/gpsacq_track.o -ldl -pthread
 
 host: $(LIBDIR)/libgps_search.so $(BINDIR)/gps_test $(BINDIR)/gps_track $(BINDIR)/hip_floor $(BINDIR)/pk_fma_stream

@@ -131,6 +131,19 @@ class CaCode {
     unsigned g1_, g2_, m1_, m2_;
 };
 
+// the 1023 chips of all 32 PRNs as [32][32] words: bit i & 31 of word i / 32 is chip i (1 = chip value 1 -> -1.0)
+inline std::vector<uint32_t> ca_chip_words() {
+    std::vector<uint32_t> chips(32 * 32, 0u);
+    for (int sv = 0; sv < 32; ++sv) {
+        CaCode ca(kTaps[sv][0], kTaps[sv][1]);
+        for (int i = 0; i < 1023; ++i) {
+            if (ca.chip()) chips[sv * 32 + (i >> 5)] |= 1u << (i & 31);
+            ca.clock();
+        }
+    }
+    return chips;
+}
+
 // SearchCode(), c/search_offline.cpp:205-209
 inline int search_code(int sv, int g1) {
     CaCode ca(kTaps[sv][0], kTaps[sv][1]);

@@ -4,7 +4,8 @@
 // amplitude, plus white Gaussian noise, the signal model of SURVEY.md section 8d):
 //   y[m] = sigma n[m] + sum_k a_k c_k[ floor((m + phi_k) CPS (1 + fd_k/L1) / fs) mod 1023 ]
 //                             cos(2 pi ((fc + fd_k)/fs m + theta_k)),        bit = (y < 0)
-// packed LSB first like MATLAB's 'ubit1' (gps_sig_gen.m:39-41).  One output byte per thread.
+// packed LSB first like MATLAB's 'ubit1' (gps_sig_gen.m:39-41).  One output byte per thread.  Further down: the same law as an
+// 8-bit complex capture (k_generate_iq8) and the reference's own test signal (k_siggen, k_siggen_tx).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -53,6 +54,52 @@ __global__ __launch_bounds__(256) void k_generate(GenArgs a) {
         out |= (y < 0.0f ? 1u : 0u) << k;
     }
     a.bits[byte] = (uint8_t)out;
+}
+
+// ---------------------------------------------------------------------------------------
+// 8-bit complex capture at a residual IF: k_generate's law (chips, navigation bits and noise as functions of the
+// absolute sample index) with a complex carrier and both Box-Muller outputs as the two noise streams:
+//   y[m] = sigma (n_I + j n_Q) + sum_k a_k nav_k c_k[...] exp(2 pi i ((if + fd_k) / fs m + theta_k)),  I + jQ = clamp(rint(scale y))
+// One complex sample per thread.
+__global__ __launch_bounds__(256) void k_generate_iq8(GenIqArgs a) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_samples) return;
+    const uint64_t m = a.first_sample + i;
+    const uint64_t h = mix64(a.seed ^ (m * 0x9e3779b97f4a7c15ull));
+    const float u1 = ((float)(uint32_t)(h >> 32) + 1.0f) * 2.3283064e-10f;  // (0, 1]
+    const float u2 = (float)(uint32_t)h * 2.3283064e-10f;
+    const float r = a.noise_sigma * sqrtf(-2.0f * __logf(u1));
+    float yi = r * __cosf(6.2831853f * u2), yq = r * __sinf(6.2831853f * u2);
+    for (int s = 0; s < a.n_sats; ++s) {
+        const GenSat sat = a.sats[s];
+        const double rr = ((double)m + sat.code_phase) * sat.chips_per_sample;
+        const long long q = (long long)floor(rr);
+        int idx = (int)(q % 1023);
+        if (idx < 0) idx += 1023;
+        float chip = ((a.chips[sat.sv * 32 + (idx >> 5)] >> (idx & 31)) & 1u) ? -1.0f : 1.0f;
+        if (a.nav) {
+            long long b = q / 20460;
+            if (q < 0 && b * 20460 != q) --b;
+            b %= a.n_nav;
+            if (b < 0) b += a.n_nav;
+            chip *= (float)a.nav[(size_t)s * a.n_nav + (size_t)b];
+        }
+        double ph = sat.cycles_per_sample * (double)m + sat.carrier_phase;
+        ph -= floor(ph);
+        float sn, cs;
+        sincospif(2.0f * (float)ph, &sn, &cs);
+        yi += sat.amplitude * chip * cs;
+        yq += sat.amplitude * chip * sn;
+    }
+    const float vi = fminf(fmaxf(rintf(a.scale * yi), -127.0f), 127.0f), vq = fminf(fmaxf(rintf(a.scale * yq), -127.0f), 127.0f);
+    uchar2 o2;
+    o2.x = (unsigned char)((int)vi + a.offset);
+    o2.y = (unsigned char)((int)vq + a.offset);
+    reinterpret_cast<uchar2*>(a.iq)[i] = o2;
+}
+
+void launch_generate_iq8(const GenIqArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_generate_iq8, dim3((unsigned)((a.n_samples + 255) / 256)), dim3(256), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------------------

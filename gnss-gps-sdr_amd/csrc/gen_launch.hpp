@@ -1,4 +1,4 @@
-// gen_launch.hpp -- argument block and launcher of gen_kernels.hip.
+// gen_launch.hpp -- argument blocks and launchers of gen_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -25,6 +25,20 @@ struct GenArgs {
     const int8_t* nav;   // [n_sats][n_nav] navigation bits +-1 (device), or nullptr: no data
     int n_nav;
 };
+// the same law as an 8-bit complex capture at a residual IF (gen_kernels.hip, k_generate_iq8)
+struct GenIqArgs {
+    uint8_t* iq;          // [2 * n_samples] interleaved I, Q
+    size_t n_samples;
+    uint64_t first_sample;
+    uint64_t seed;
+    const GenSat* sats;   // device; cycles_per_sample = (if_hz + fd) / fs
+    int n_sats;
+    float noise_sigma, scale;
+    int offset;           // 128 for GPSACQ_IQ_U8, 0 for GPSACQ_IQ_S8
+    const int8_t* nav;    // [n_sats][n_nav] navigation bits +-1 (device), or nullptr
+    int n_nav;
+    const uint32_t* chips; // [32][32] C/A chips, bit i of word i / 32 (device): the table of the tracking channels
+};
 
 // gps_sig_gen.m's own signal (gen_kernels.hip, k_siggen)
 struct SigArgs {
@@ -49,5 +63,6 @@ void launch_siggen_tx(const SigTxArgs& a, hipStream_t s);
 hipError_t upload_chips(const uint32_t* host);
 void launch_siggen(const SigArgs& a, hipStream_t s);
 void launch_generate(const GenArgs& a, hipStream_t s);
+void launch_generate_iq8(const GenIqArgs& a, hipStream_t s);
 
 }  // namespace acq

@@ -1,7 +1,8 @@
 // gpsacq_engine.cpp -- host side of libgpsacq.so: device state, batching and the C ABI
 // declared in include/gpsacq.h.  All arithmetic of the search runs in the HIP kernels of
 // acq_kernels.hip; there is no CPU fallback -- without a gfx950 device every entry point that
-// needs one fails with GPSACQ_ERR_DEVICE.
+// needs one fails with GPSACQ_ERR_DEVICE.  The tracking channels' entry points are in gpsacq_track.cpp; both work on the
+// engine of gpsacq_engine.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,13 +17,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/gpsacq.h"
-#include "acq_launch.hpp"
 #include "acq_tables.hpp"
+#include "gpsacq_engine.hpp"
 #include "iq_launch.hpp"
-#include "gen_launch.hpp"
-#include "track_launch.hpp"
-#include "track_iq_launch.hpp"
 
 using namespace acq;
 
@@ -30,7 +27,7 @@ static_assert(sizeof(gpsacq_cell) == sizeof(Cell) && sizeof(gpsacq_peak) == size
               "ABI structs must match the kernel structs");
 
 static thread_local std::string g_err;
-static int fail(int code, const char* fmt, ...) {
+int fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -44,129 +41,9 @@ __attribute__((visibility("hidden"))) int acq::set_last_error(int code, const ch
     g_err = msg ? msg : "";
     return code;
 }
-#define HIPCHK(expr)                                                                                  \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? GPSACQ_ERR_NOMEM : GPSACQ_ERR_DEVICE, \
-                                          "%s: %s", #expr, hipGetErrorString(e_));                    \
-    } while (0)
-
-struct gpsacq_engine {
-    gpsacq_params p{};
-    int dmax = 0, ndop = 0, dop_first = 0, nlags = 0, mc = 0, halo = 0, crow = 0;  // searched bins: dop_first .. +ndop-1
-    int n_acc = 1, acc_step = 0;  // non-coherent accumulation (gpsacq_set_noncoherent)
-    // Doppler grid (gpsacq_set_doppler_step): step = bin * dstride / sub, points -kmax..+kmax; sub = dstride = 1 is the reference's
-    int sub = 1, dstride = 1, kmax = 0;
-    cf* d_lutc = nullptr;  // [sub][8][256] look-up tables of k_fwd2
-    bool creep_comp = false;      // re-align accumulated blocks by the code creep of each Doppler bin
-    bool block_align = false;     // re-align accumulated blocks by the code phase between their starts (any stride)
-    int cus = 0;
-    char name[64] = {0};
-    hipStream_t stream = nullptr;
-    // stage events of the last kTimingRing searches (asynchronous callers read a finished search's
-    // times while the next one runs)
-    static const int kTimingRing = 8;
-    hipEvent_t ev[kTimingRing][4] = {};
-    int ring_launches[kTimingRing] = {};
-    int64_t ring_cells[kTimingRing] = {};
-    long searches = 0;  // searches enqueued so far; search k uses ring slot k % kTimingRing
-    // constants
-    cf *d_t1 = nullptr, *d_t2 = nullptr, *d_bq = nullptr, *d_tn = nullptr;
-    cf* d_fold = nullptr;  // the folded-rotation tables of k_corr<..., FOLD> (acq_tables.hpp TablesFold)
-    unsigned char* d_rho = nullptr;
-    uint8_t *d_cos = nullptr, *d_sin = nullptr;
-    uint64_t *d_cos_t = nullptr, *d_sin_t = nullptr;  // bit-transposed masks for k_fwd
-    cf* d_code = nullptr;  // [32 + patch_cap][8][crow]
-    size_t patch_cap = 0;
-    int32_t* d_patch_blocks = nullptr;
-    // scratch (grown on demand)
-    uint8_t* d_bits = nullptr;
-    size_t bits_cap = 0;
-    cf* d_dpp = nullptr;
-    size_t dpp_cap = 0;  // in blocks
-    Task* d_tasks = nullptr;
-    Cell* d_cells = nullptr;
-    Cell* d_parts = nullptr;  // partial cells of multi-pass searches (more than 10000 lags)
-    Peak* d_peaks = nullptr;
-    size_t task_cap = 0, cell_cap = 0, peak_cap = 0, parts_cap = 0;
-    // 8-bit IQ ingestion scratch
-    uint8_t* d_iq = nullptr;
-    size_t iq_cap = 0;
-    uint8_t* d_iqbits = nullptr;
-    size_t iqbits_cap = 0;
-    float* d_pdump = nullptr;  // non-coherent + creep re-alignment at fs > 10 MHz: per-lag power sums, [cell][nlags]
-    size_t pdump_cap = 0;
-    float* d_fsamp = nullptr;  // multi-bit path: the batch's samples as complex floats, LO applied ([block][40000][2])
-    size_t fsamp_cap = 0;
-    unsigned long long* d_sums = nullptr;
-    // capture generator scratch
-    GenSat* d_sats = nullptr;
-    size_t sats_cap = 0;
-    uint8_t* d_gen = nullptr;
-    size_t gen_cap = 0;
-    int8_t* d_nav = nullptr;  // navigation bits of gpsacq_generate_nav_range
-    size_t nav_cap = 0;
-    // tracking channels (gpsacq_track*)
-    uint32_t* d_track_chips = nullptr;  // [32][32] C/A chips
-    gpsacq_track_chan* d_chans = nullptr;
-    size_t chans_cap = 0;
-    int32_t* d_track_n = nullptr;
-    size_t track_n_cap = 0;
-    int32_t* d_prompt = nullptr;
-    size_t prompt_cap = 0;
-    gpsacq_track_record* d_records = nullptr;
-    size_t records_cap = 0;
-    hipEvent_t tiq_ev[3] = {};  // gpsacq_track_iq8*: before the conversion, between it and the channels, after them
-    bool tiq_timed = false;
-    // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
-    int* d_persist = nullptr;
-    size_t persist_cap = 0;
-    bool persist = false;
-    // cached default schedule (task t = block t, PRN t % 32; with ref_quirks also its patch list: blocks 0, 32, 64, ...)
-    size_t sched_tasks = 0;
-    bool sched_valid = false;
-    // pipelined host-buffer searches (gpsacq_pipe_*): a second stream for the uploads, per-slot pinned staging and device buffers
-    hipStream_t copy_stream = nullptr;
-    struct PipeSlot {
-        uint8_t* h_in = nullptr;   // pinned
-        size_t h_cap = 0;
-        uint8_t* d_in = nullptr;
-        size_t d_cap = 0;
-        Peak* d_peaks = nullptr;
-        Peak* h_peaks = nullptr;   // pinned
-        size_t peak_cap = 0;
-        hipEvent_t uploaded = nullptr, done = nullptr;
-        bool busy = false;
-        size_t n_tasks = 0;
-    } pipe[GPSACQ_PIPE_SLOTS];
-};
-
-// what a search transforms: the 1-bit stream gps_test reads, or an 8-bit IQ capture converted while it is staged
-struct Capture {
-    bool iq8 = false;
-    const uint8_t* d_src = nullptr;  // device pointer
-    size_t stride = 0;               // bytes per block in d_src
-    IqConv iq{};
-    size_t iq_first = 0, iq_total = ~(size_t)0;
-    int multibit = 0;  // 8-bit IQ kept at full amplitude (float samples) instead of its sign: 1 the real-IF value, 2 the complex sample
-};
 
 static const size_t kFwdChunk = 32768;  // blocks per forward-transform launch (grid.y bound)
 static const size_t kPdumpBytes = (size_t)1 << 30;  // per-lag power sums of the multi-pass re-alignment path, per chunk of tasks
-
-// Scratch buffers grow on demand, stream-ordered (hipFreeAsync / hipMallocAsync on the engine's stream): work already
-// enqueued keeps the old buffer until it has run, and no device-wide synchronisation happens in mid-stream.  They grow by at
-// least half so that a caller creeping up in batch size does not reallocate every call.
-template <class T> static int grow(T*& p, size_t& cap, size_t need, hipStream_t stream, size_t elem_bytes = sizeof(T)) {
-    if (need <= cap) return GPSACQ_OK;
-    need = std::max(need, cap + cap / 2);
-    if (p) HIPCHK(hipFreeAsync(p, stream));
-    p = nullptr;
-    cap = 0;
-    HIPCHK(hipMallocAsync((void**)&p, need * elem_bytes, stream));
-    cap = need;
-    return GPSACQ_OK;
-}
 
 static int ensure_code_slots(gpsacq_engine* e, size_t n_patch) {
     if (n_patch <= e->patch_cap) return GPSACQ_OK;
@@ -301,14 +178,7 @@ extern "C" int gpsacq_create(const gpsacq_params* params, gpsacq_engine** out) {
         transpose_masks(h->sinm.data(), h->sin_t.data());
         h->rep.resize((size_t)GPSACQ_NUM_SATS * N_FFT);
         for (int sv = 0; sv < GPSACQ_NUM_SATS; ++sv) code_replica(prm.fs, sv, &h->rep[(size_t)sv * N_FFT]);
-        h->chips.assign(32 * 32, 0u);  // C/A chips of all 32 PRNs for the capture generator
-        for (int sv = 0; sv < GPSACQ_NUM_SATS; ++sv) {
-            CaCode ca(kTaps[sv][0], kTaps[sv][1]);
-            for (int i = 0; i < 1023; ++i) {
-                if (ca.chip()) h->chips[sv * 32 + (i >> 5)] |= 1u << (i & 31);
-                ca.clock();
-            }
-        }
+        h->chips = ca_chip_words();  // for the capture generator
         return h;
     };
     // the worker starts BEFORE the first HIP call: the runtime's start-up is what it hides behind (an early return below waits
@@ -545,8 +415,6 @@ static int prepare_tasks(gpsacq_engine* e, const gpsacq_task* h_tasks, const voi
     return GPSACQ_OK;
 }
 
-static int iq8_to_bits_enqueue(gpsacq_engine* e, const uint8_t* d_iq, size_t n_samples, const IqConv& conv, size_t first_sample, uint8_t* d_bits);
-
 // columns of pass p when the lags need several passes (fs > 10 MHz): 40 per pass, the last one the smallest instance that covers
 // what is left (16.368 MHz: 66 columns = 40 + 28-column instance; round 2 ran 40 + 40)
 static int pass_columns(int n_cols, int p) {
@@ -742,7 +610,7 @@ static Capture bits_capture(const void* d_bits, size_t stride) {
     return c;
 }
 // validates a gpsacq_iq8_input and turns it into the kernels' argument form
-static int iq8_capture(const gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t stride, Capture* out) {
+int iq8_capture(const gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t stride, Capture* out) {
     if (!in) return fail(GPSACQ_ERR_ARG, "8-bit IQ search: null gpsacq_iq8_input");
     if (in->format != GPSACQ_IQ_U8 && in->format != GPSACQ_IQ_S8) return fail(GPSACQ_ERR_ARG, "unknown IQ format %d", in->format);
     if (in->multibit < 0 || in->multibit > GPSACQ_SAMPLES_COMPLEX) return fail(GPSACQ_ERR_ARG, "gpsacq_iq8_input.multibit %d: 0 (sign), 1 (real IF) or 2 (complex baseband)", in->multibit);
@@ -1220,7 +1088,7 @@ extern "C" int gpsacq_generate_sig_tx(gpsacq_engine* e, int prn, const int8_t* d
 }
 
 // 8-bit IQ -> 1-bit real IF (proc_rtl_bin_for_gps.m / proc_hackrf_bin_for_gps.m), device buffers
-static int iq8_to_bits_enqueue(gpsacq_engine* e, const uint8_t* d_iq, size_t n_samples, const IqConv& conv, size_t first_sample, uint8_t* d_bits) {
+int iq8_to_bits_enqueue(gpsacq_engine* e, const uint8_t* d_iq, size_t n_samples, const IqConv& conv, size_t first_sample, uint8_t* d_bits) {
     if (n_samples == 0) return GPSACQ_OK;
     IqArgs a{};
     a.iq = d_iq;
@@ -1331,317 +1199,6 @@ extern "C" int gpsacq_handoff_engine(const gpsacq_engine* e, const gpsacq_peak* 
     if (!e) return fail(GPSACQ_ERR_ARG, "gpsacq_handoff_engine: null engine");
     const bool ref_grid = e->sub == 1 && e->dstride == 1;
     return gpsacq_handoff_step(peak, e->p.fc, e->p.fs, ref_grid ? 0.0 : e->p.fs / N_FFT * e->dstride / e->sub, secs, out);
-}
-
-// ---- tracking channels (track_kernels.hip; the model is in include/gpsacq.h) ----------------------------------------------
-extern "C" int gpsacq_track_default_params(const gpsacq_engine* e, gpsacq_track_params* p) {
-    if (!e || !p) return fail(GPSACQ_ERR_ARG, "gpsacq_track_default_params: null argument");
-    // above 40 MHz num_lags saturates at N_FFT = 40000 and is no longer samples per millisecond: no defaults can be built from it
-    if (e->p.fs > 40.0e6) return fail(GPSACQ_ERR_UNSUPPORTED, "gpsacq_track_default_params: fs %.0f Hz is above 40 MHz", e->p.fs);
-    const double fs = e->p.fs, r = (double)e->nlags / 10000.0;
-    // round(log2((10000 / spm)^2)) up to 10 MHz; above it round(log2((10000 / spm)^3)): a step of the NCO word is worth fs / 2^32 Hz,
-    // so with the square rule the loops' bandwidth in Hz grows with fs (at 40 MHz the Costas loop no longer holds the phase)
-    const double octaves = std::log2(10000.0 / e->nlags);
-    const int adj = (int)std::lround((e->nlags > 10000 ? 3.0 : 2.0) * octaves);
-    p->lo_ki = 20 + adj;
-    p->lo_kp = 27 + adj;
-    p->ca_ki = 11 + adj;
-    p->ca_kp = 23 + adj;
-    p->fll_k = 25 + adj;
-    p->fll_epochs = 500;
-    p->aid_epoch = -1;
-    p->agc_period = 250;
-    p->agc_lo = (int64_t)std::floor(1200.0 * 1200.0 * r * r);
-    p->agc_hi = (int64_t)std::floor(1400.0 * 1400.0 * r * r);
-    const double two64 = 4294967296.0 * 4294967296.0;
-    p->lo_window = (int64_t)(10000.0 / fs * two64);
-    p->ca_window = (int64_t)(4.0 * 10000.0 / 1540.0 / fs * two64);
-    p->min_epoch = e->nlags / 2;
-    p->max_epoch = std::min(2 * e->nlags, 65535);  // the kernel packs two counts <= max_epoch per 32-bit word
-    return GPSACQ_OK;
-}
-
-extern "C" int gpsacq_track_start(const gpsacq_engine* e, int prn, const gpsacq_peak* peak, uint64_t block_first_sample,
-                                  const gpsacq_track_params* params, gpsacq_track_chan* ch) {
-    if (!e || !peak || !ch || prn < 1 || prn > GPSACQ_NUM_SATS) return fail(GPSACQ_ERR_ARG, "gpsacq_track_start: bad argument");
-    gpsacq_track_params p;
-    if (params) p = *params;
-    else if (int rc = gpsacq_track_default_params(e, &p)) return rc;
-    gpsacq_handoff_t h;
-    if (int rc = gpsacq_handoff_engine(e, peak, 0.0, &h)) return rc;
-    if (peak->ca_shift < 0 || h.ca_rate == 0) return fail(GPSACQ_ERR_ARG, "gpsacq_track_start: bad hit (ca_shift %d)", peak->ca_shift);
-    const uint64_t full = 1023ull << 32;
-    std::memset(ch, 0, sizeof *ch);
-    ch->prn = prn;
-    ch->status = GPSACQ_TRACK_OK;
-    ch->lo_rate = h.lo_rate;
-    ch->ca_rate = h.ca_rate;
-    ch->lo_int = (int64_t)((uint64_t)h.lo_rate << 32);
-    ch->ca_int = (int64_t)((uint64_t)h.ca_rate << 32);
-    ch->lo_nom = (int64_t)((uint64_t)(uint32_t)(e->p.fc / e->p.fs * 4294967296.0) << 32);
-    ch->ca_nom = (int64_t)((uint64_t)(uint32_t)(1.023e6 / e->p.fs * 4294967296.0) << 32);
-    ch->fll_left = p.fll_epochs;
-    // the prompt position at block_first_sample is ca_shift samples of the code NCO; then the pause to the next code epoch
-    const uint64_t pos = ((uint64_t)peak->ca_shift * h.ca_rate) % full;
-    const uint64_t n0 = (full - pos + h.ca_rate - 1) / h.ca_rate;
-    ch->next_sample = block_first_sample + n0;
-    ch->lo_phase = (uint32_t)((block_first_sample + n0) * (uint64_t)h.lo_rate);
-    ch->ca_pos = pos + n0 * h.ca_rate - full;
-    return GPSACQ_OK;
-}
-
-static int track_check_params(const gpsacq_track_params& p) {
-    const int sh[] = {p.lo_ki - 1, p.lo_kp - 1, p.ca_ki, p.ca_kp, p.fll_k};  // the carrier shifts must stay >= 0 with gain_adj = -1
-    for (int v : sh)
-        if (v < 0 || v > 62) return fail(GPSACQ_ERR_ARG, "gpsacq_track: a loop shift is outside [0, 62] (lo_ki/lo_kp >= 1)");
-    if (p.min_epoch < 1 || p.max_epoch < p.min_epoch || p.max_epoch > 65535 || p.lo_window < 0 || p.ca_window < 0)
-        return fail(GPSACQ_ERR_ARG, "gpsacq_track: need 1 <= min_epoch <= max_epoch <= 65535 and windows >= 0");
-    return GPSACQ_OK;
-}
-
-// the C/A chip table of the channels (and of the 8-bit IQ generator), built on first use
-static int ensure_track_chips(gpsacq_engine* e) {
-    if (e->d_track_chips) return GPSACQ_OK;
-    std::vector<uint32_t> chips(32 * 32, 0u);
-    for (int sv = 0; sv < GPSACQ_NUM_SATS; ++sv) {
-        CaCode ca(kTaps[sv][0], kTaps[sv][1]);
-        for (int i = 0; i < 1023; ++i) {
-            if (ca.chip()) chips[sv * 32 + (i >> 5)] |= 1u << (i & 31);
-            ca.clock();
-        }
-    }
-    HIPCHK(hipMalloc((void**)&e->d_track_chips, chips.size() * sizeof(uint32_t)));
-    HIPCHK(hipMemcpy(e->d_track_chips, chips.data(), chips.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return GPSACQ_OK;
-}
-
-// what every gpsacq_track* call does before its kernel: the channel states are checked and uploaded to e->d_chans ...
-static int track_prepare(gpsacq_engine* e, uint64_t first_sample, const gpsacq_track_chan* chans, int n_chans) {
-    for (int c = 0; c < n_chans; ++c) {
-        const gpsacq_track_chan& ch = chans[c];
-        if (ch.prn < 1 || ch.prn > GPSACQ_NUM_SATS || ch.ca_rate == 0 || ch.ca_pos >= (1023ull << 32) || ch.pwr_pos < 0 || ch.pwr_pos > 7)
-            return fail(GPSACQ_ERR_ARG, "gpsacq_track: channel %d is not a valid state", c);
-        if (ch.next_sample < first_sample)
-            return fail(GPSACQ_ERR_ARG, "gpsacq_track: channel %d continues at sample %llu, before the window's first sample %llu", c,
-                        (unsigned long long)ch.next_sample, (unsigned long long)first_sample);
-    }
-    HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = ensure_track_chips(e)) return rc;
-    if (int rc = grow(e->d_chans, e->chans_cap, (size_t)n_chans, e->stream)) return rc;
-    if (int rc = grow(e->d_track_n, e->track_n_cap, (size_t)n_chans, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_chans, chans, n_chans * sizeof(gpsacq_track_chan), hipMemcpyHostToDevice, e->stream));
-    return GPSACQ_OK;
-}
-// ... and after it: states and epoch counts back, wait
-static int track_collect(gpsacq_engine* e, gpsacq_track_chan* chans, int n_chans, int32_t* n_epochs_out) {
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(chans, e->d_chans, n_chans * sizeof(gpsacq_track_chan), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(n_epochs_out, e->d_track_n, n_chans * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return GPSACQ_OK;
-}
-static void track_launch_bits(gpsacq_engine* e, const void* d_bits, size_t n_bytes, uint64_t first_sample, int n_chans, const gpsacq_track_params& p,
-                              void* d_prompt, void* d_records, int max_epochs) {
-    TrackArgs a{};
-    a.bits = (const uint8_t*)d_bits;
-    a.n_bytes = n_bytes;
-    a.first_sample = first_sample;
-    a.chans = e->d_chans;
-    a.n_chans = n_chans;
-    a.prm = p;
-    a.chips = e->d_track_chips;
-    a.prompt = (int32_t*)d_prompt;
-    a.records = (gpsacq_track_record*)d_records;
-    a.max_epochs = max_epochs;
-    a.n_epochs = e->d_track_n;
-    launch_track(a, e->stream);
-}
-
-extern "C" int gpsacq_track_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, uint64_t first_sample, gpsacq_track_chan* chans,
-                                   int n_chans, const gpsacq_track_params* params, void* d_prompt, void* d_records, int max_epochs,
-                                   int32_t* n_epochs_out) {
-    if (!e || !d_bits || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
-        return fail(GPSACQ_ERR_ARG, "gpsacq_track: bad argument");
-    if (((uintptr_t)d_bits & 3) || (first_sample & 7)) return fail(GPSACQ_ERR_ARG, "gpsacq_track: bits must be 4-byte aligned, first_sample a multiple of 8");
-    gpsacq_track_params p;
-    if (params) p = *params;
-    else if (int rc = gpsacq_track_default_params(e, &p)) return rc;
-    if (int rc = track_check_params(p)) return rc;
-    if (int rc = track_prepare(e, first_sample, chans, n_chans)) return rc;
-    track_launch_bits(e, d_bits, n_bytes, first_sample, n_chans, p, d_prompt, d_records, max_epochs);
-    return track_collect(e, chans, n_chans, n_epochs_out);
-}
-
-// only the epochs each channel ran are defined; copy them row by row
-static int track_rows_to_host(gpsacq_engine* e, int n_chans, int max_epochs, const int32_t* n_epochs, int32_t* prompt, gpsacq_track_record* records) {
-    for (int c = 0; c < n_chans; ++c) {
-        const size_t ne = (size_t)n_epochs[c], r = (size_t)c * max_epochs;
-        if (!ne) continue;
-        if (prompt) HIPCHK(hipMemcpyAsync(prompt + 2 * r, e->d_prompt + 2 * r, 2 * ne * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-        if (records) HIPCHK(hipMemcpyAsync(records + r, e->d_records + r, ne * sizeof(gpsacq_track_record), hipMemcpyDeviceToHost, e->stream));
-    }
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return GPSACQ_OK;
-}
-
-extern "C" int gpsacq_track(gpsacq_engine* e, const uint8_t* bits, size_t n_bytes, uint64_t first_sample, gpsacq_track_chan* chans,
-                            int n_chans, const gpsacq_track_params* params, int32_t* prompt, gpsacq_track_record* records,
-                            int max_epochs, int32_t* n_epochs_out) {
-    if (!e || !bits || n_bytes == 0 || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
-        return fail(GPSACQ_ERR_ARG, "gpsacq_track: bad argument");
-    HIPCHK(hipSetDevice(e->p.device));
-    const size_t per = (size_t)n_chans * (size_t)max_epochs;
-    if (int rc = grow(e->d_gen, e->gen_cap, n_bytes, e->stream)) return rc;
-    if (prompt && per)
-        if (int rc = grow(e->d_prompt, e->prompt_cap, 2 * per, e->stream)) return rc;
-    if (records && per)
-        if (int rc = grow(e->d_records, e->records_cap, per, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_gen, bits, n_bytes, hipMemcpyHostToDevice, e->stream));
-    if (int rc = gpsacq_track_device(e, e->d_gen, n_bytes, first_sample, chans, n_chans, params, prompt && per ? e->d_prompt : nullptr,
-                                     records && per ? e->d_records : nullptr, max_epochs, n_epochs_out))
-        return rc;
-    return track_rows_to_host(e, n_chans, max_epochs, n_epochs_out, prompt, records);
-}
-
-// ---- tracking channels on an 8-bit IQ capture (track_iq_kernels.hip; include/gpsacq.h) -------------------------------------
-extern "C" int gpsacq_track_default_params_iq8(const gpsacq_engine* e, double sample_rms, gpsacq_track_params* p) {
-    if (!e || !p) return fail(GPSACQ_ERR_ARG, "gpsacq_track_default_params_iq8: null argument");
-    if (!(sample_rms > 0) || !std::isfinite(sample_rms)) return fail(GPSACQ_ERR_UNSUPPORTED, "gpsacq_track_default_params_iq8: sample_rms %g", sample_rms);
-    if (int rc = gpsacq_track_default_params(e, p)) return rc;
-    int g = (int)std::lround(std::log2((double)GPSACQ_TRACK_IQ8_GAIN * sample_rms * sample_rms));
-    // every shift stays in [0, 62], the carrier's in [1, 62] (gain_adj = -1)
-    const int lo = std::min(std::min(p->lo_ki, p->lo_kp) - 1, std::min(std::min(p->ca_ki, p->ca_kp), p->fll_k));
-    const int hi = std::max(std::max(p->lo_ki, p->lo_kp), std::max(std::max(p->ca_ki, p->ca_kp), p->fll_k));
-    g = std::max(g, hi - 62);
-    if (g > lo) return fail(GPSACQ_ERR_UNSUPPORTED, "gpsacq_track_default_params_iq8: sample_rms %g needs shifts below 0", sample_rms);
-    p->lo_ki -= g, p->lo_kp -= g, p->ca_ki -= g, p->ca_kp -= g, p->fll_k -= g;
-    const double s = std::ldexp(1.0, g);
-    p->agc_lo = (int64_t)std::floor((double)p->agc_lo * s);
-    p->agc_hi = (int64_t)std::floor((double)p->agc_hi * s);
-    return GPSACQ_OK;
-}
-
-extern "C" int gpsacq_iq8_accumulate_power(const gpsacq_engine* e, const void* iq, size_t n_samples, int format, uint64_t power[2]) {
-    (void)e;  // host arithmetic: no device, the engine may be NULL
-    if (!iq || !power || n_samples == 0) return fail(GPSACQ_ERR_ARG, "gpsacq_iq8_accumulate_power: bad argument");
-    if (format != GPSACQ_IQ_U8 && format != GPSACQ_IQ_S8) return fail(GPSACQ_ERR_ARG, "unknown IQ format %d", format);
-    const uint8_t* b = (const uint8_t*)iq;
-    uint64_t pi = 0, pq = 0;
-    for (size_t s = 0; s < n_samples; ++s) {
-        const int vi = format == GPSACQ_IQ_S8 ? (int)(int8_t)b[2 * s] : (int)b[2 * s] - 128;
-        const int vq = format == GPSACQ_IQ_S8 ? (int)(int8_t)b[2 * s + 1] : (int)b[2 * s + 1] - 128;
-        pi += (uint64_t)(vi * vi);
-        pq += (uint64_t)(vq * vq);
-    }
-    power[0] += pi;
-    power[1] += pq;
-    return GPSACQ_OK;
-}
-
-extern "C" int gpsacq_track_start_iq8(const gpsacq_engine* e, const gpsacq_iq8_input* in, int prn, const gpsacq_peak* peak,
-                                      uint64_t block_first_sample, const gpsacq_track_params* params, gpsacq_track_chan* ch) {
-    if (!e || !in) return fail(GPSACQ_ERR_ARG, "gpsacq_track_start_iq8: null argument");
-    Capture cap;
-    if (int rc = iq8_capture(e, in, nullptr, 0, &cap)) return rc;
-    gpsacq_track_params p;  // the 1-bit defaults stand in where only fll_epochs is read
-    if (params) p = *params;
-    else if (int rc = gpsacq_track_default_params(e, &p)) return rc;
-    if (int rc = gpsacq_track_start(e, prn, peak, block_first_sample, &p, ch)) return rc;
-    if (in->multibit == GPSACQ_SAMPLES_SIGN) return GPSACQ_OK;
-    // the carrier in the raw capture: the search saw it turned by +mix_hz and (unless complex baseband) through Sample()'s LO at fc
-    gpsacq_handoff_t h;
-    if (int rc = gpsacq_handoff_engine(e, peak, 0.0, &h)) return rc;
-    const double f = h.lo_dop_hz - in->mix_hz + (in->multibit == GPSACQ_SAMPLES_COMPLEX ? 0.0 : e->p.fc);
-    if (!(std::fabs(f) < e->p.fs / 2)) return fail(GPSACQ_ERR_ARG, "gpsacq_track_start_iq8: carrier %g Hz outside +-fs / 2 = %g", f, e->p.fs / 2);
-    const uint32_t word = (uint32_t)(int64_t)std::llround(f / e->p.fs * 4294967296.0);
-    ch->lo_rate = word;
-    ch->lo_int = ch->lo_nom = (int64_t)((uint64_t)word << 32);
-    ch->lo_phase = (uint32_t)(ch->next_sample * (uint64_t)word);
-    return GPSACQ_OK;
-}
-
-extern "C" int gpsacq_track_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, uint64_t first_sample,
-                                       gpsacq_track_chan* chans, int n_chans, const gpsacq_track_params* params, void* d_prompt,
-                                       void* d_records, int max_epochs, int32_t* n_epochs_out) {
-    if (!e || !d_iq || n_samples == 0 || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
-        return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: bad argument");
-    Capture cap;
-    if (int rc = iq8_capture(e, in, d_iq, 0, &cap)) return rc;
-    if ((uintptr_t)d_iq & 15) return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: IQ buffer must be 16-byte aligned");
-    const bool sign = in->multibit == GPSACQ_SAMPLES_SIGN;
-    if (sign && (first_sample & 7))
-        return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: first_sample %llu is not a multiple of 8 (sign mode runs on the 1-bit stream's byte grid)",
-                    (unsigned long long)first_sample);
-    gpsacq_track_params p;
-    if (params) p = *params;
-    else if (!sign) return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: multi-bit channels need params (gpsacq_track_default_params_iq8)");
-    else if (int rc = gpsacq_track_default_params(e, &p)) return rc;
-    if (int rc = track_check_params(p)) return rc;
-    if (int rc = track_prepare(e, first_sample, chans, n_chans)) return rc;
-    for (auto& ev : e->tiq_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
-    e->tiq_timed = false;
-    HIPCHK(hipEventRecord(e->tiq_ev[0], e->stream));
-    if (sign) {
-        // the window as the 1-bit stream the scripts would have written, in engine scratch; then the 1-bit channels on it
-        const size_t n_bytes = (n_samples + 7) / 8;
-        if (int rc = grow(e->d_iqbits, e->iqbits_cap, n_bytes, e->stream)) return rc;
-        const size_t left = cap.iq_total > cap.iq_first ? cap.iq_total - cap.iq_first : 0;  // samples of the capture from iq[0] on
-        if (left < n_samples) HIPCHK(hipMemsetAsync(e->d_iqbits, 0, n_bytes, e->stream));
-        if (int rc = iq8_to_bits_enqueue(e, (const uint8_t*)d_iq, std::min(n_samples, left), cap.iq, cap.iq_first, e->d_iqbits)) return rc;
-        HIPCHK(hipEventRecord(e->tiq_ev[1], e->stream));
-        track_launch_bits(e, e->d_iqbits, n_bytes, first_sample, n_chans, p, d_prompt, d_records, max_epochs);
-    } else {
-        HIPCHK(hipEventRecord(e->tiq_ev[1], e->stream));
-        TrackIqArgs a{};
-        a.iq = (const uint8_t*)d_iq;
-        a.n_samples = n_samples;
-        a.first_sample = first_sample;
-        a.flip = in->format == GPSACQ_IQ_U8 ? 0x80808080u : 0u;
-        a.dc_i = in->remove_dc ? (int32_t)std::nearbyint(in->mean_i) : 0;
-        a.dc_q = in->remove_dc ? (int32_t)std::nearbyint(in->mean_q) : 0;
-        if (std::abs(a.dc_i) > 128 || std::abs(a.dc_q) > 128) return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: mean (%g, %g) outside +-128", in->mean_i, in->mean_q);
-        a.chans = e->d_chans;
-        a.n_chans = n_chans;
-        a.prm = p;
-        a.chips = e->d_track_chips;
-        a.prompt = (int32_t*)d_prompt;
-        a.records = (gpsacq_track_record*)d_records;
-        a.max_epochs = max_epochs;
-        a.n_epochs = e->d_track_n;
-        launch_track_iq(a, e->stream);
-    }
-    HIPCHK(hipEventRecord(e->tiq_ev[2], e->stream));
-    if (int rc = track_collect(e, chans, n_chans, n_epochs_out)) return rc;
-    e->tiq_timed = true;
-    return GPSACQ_OK;
-}
-
-extern "C" int gpsacq_track_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, uint64_t first_sample,
-                                gpsacq_track_chan* chans, int n_chans, const gpsacq_track_params* params, int32_t* prompt,
-                                gpsacq_track_record* records, int max_epochs, int32_t* n_epochs_out) {
-    if (!e || !iq || n_samples == 0 || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
-        return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: bad argument");
-    HIPCHK(hipSetDevice(e->p.device));
-    const size_t per = (size_t)n_chans * (size_t)max_epochs;
-    if (int rc = grow(e->d_iq, e->iq_cap, 2 * n_samples + 16, e->stream)) return rc;
-    if (prompt && per)
-        if (int rc = grow(e->d_prompt, e->prompt_cap, 2 * per, e->stream)) return rc;
-    if (records && per)
-        if (int rc = grow(e->d_records, e->records_cap, per, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * n_samples, hipMemcpyHostToDevice, e->stream));
-    if (int rc = gpsacq_track_iq8_device(e, in, e->d_iq, n_samples, first_sample, chans, n_chans, params, prompt && per ? e->d_prompt : nullptr,
-                                         records && per ? e->d_records : nullptr, max_epochs, n_epochs_out))
-        return rc;
-    return track_rows_to_host(e, n_chans, max_epochs, n_epochs_out, prompt, records);
-}
-
-extern "C" int gpsacq_track_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* track_ms) {
-    if (!e || !e->tiq_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8_last_ms: no finished gpsacq_track_iq8 call");
-    HIPCHK(hipSetDevice(e->p.device));
-    if (convert_ms) HIPCHK(hipEventElapsedTime(convert_ms, e->tiq_ev[0], e->tiq_ev[1]));
-    if (track_ms) HIPCHK(hipEventElapsedTime(track_ms, e->tiq_ev[1], e->tiq_ev[2]));
-    return GPSACQ_OK;
 }
 
 // 8-bit complex capture at a residual IF (k_generate_iq8): gpsacq_generate_nav_range's law, any sample range

@@ -1,0 +1,142 @@
+// gpsacq_engine.hpp -- what the translation units of libgpsacq.so that work on an engine share: the engine itself, the error and
+// scratch helpers, and the few internal functions that cross files.  Private to the library: not installed, nothing here is
+// exported (the library is built with hidden visibility), and no layout in it is part of the ABI of include/gpsacq.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/gpsacq.h"
+#include "acq_launch.hpp"
+#include "gen_launch.hpp"
+
+// sets this thread's gpsacq_last_error() text from a printf format and returns `code` (gpsacq_engine.cpp)
+int fail(int code, const char* fmt, ...);
+#define HIPCHK(expr)                                                                                  \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? GPSACQ_ERR_NOMEM : GPSACQ_ERR_DEVICE, \
+                                          "%s: %s", #expr, hipGetErrorString(e_));                    \
+    } while (0)
+
+struct gpsacq_engine {
+    gpsacq_params p{};
+    int dmax = 0, ndop = 0, dop_first = 0, nlags = 0, mc = 0, halo = 0, crow = 0;  // searched bins: dop_first .. +ndop-1
+    int n_acc = 1, acc_step = 0;  // non-coherent accumulation (gpsacq_set_noncoherent)
+    // Doppler grid (gpsacq_set_doppler_step): step = bin * dstride / sub, points -kmax..+kmax; sub = dstride = 1 is the reference's
+    int sub = 1, dstride = 1, kmax = 0;
+    acq::cf* d_lutc = nullptr;  // [sub][8][256] look-up tables of k_fwd2
+    bool creep_comp = false;      // re-align accumulated blocks by the code creep of each Doppler bin
+    bool block_align = false;     // re-align accumulated blocks by the code phase between their starts (any stride)
+    int cus = 0;
+    char name[64] = {0};
+    hipStream_t stream = nullptr;
+    // stage events of the last kTimingRing searches (asynchronous callers read a finished search's
+    // times while the next one runs)
+    static const int kTimingRing = 8;
+    hipEvent_t ev[kTimingRing][4] = {};
+    int ring_launches[kTimingRing] = {};
+    int64_t ring_cells[kTimingRing] = {};
+    long searches = 0;  // searches enqueued so far; search k uses ring slot k % kTimingRing
+    // constants
+    acq::cf *d_t1 = nullptr, *d_t2 = nullptr, *d_bq = nullptr, *d_tn = nullptr;
+    acq::cf* d_fold = nullptr;  // the folded-rotation tables of k_corr<..., FOLD> (acq_tables.hpp TablesFold)
+    unsigned char* d_rho = nullptr;
+    uint8_t *d_cos = nullptr, *d_sin = nullptr;
+    uint64_t *d_cos_t = nullptr, *d_sin_t = nullptr;  // bit-transposed masks for k_fwd
+    acq::cf* d_code = nullptr;  // [32 + patch_cap][8][crow]
+    size_t patch_cap = 0;
+    int32_t* d_patch_blocks = nullptr;
+    // scratch (grown on demand)
+    uint8_t* d_bits = nullptr;
+    size_t bits_cap = 0;
+    acq::cf* d_dpp = nullptr;
+    size_t dpp_cap = 0;  // in blocks
+    acq::Task* d_tasks = nullptr;
+    acq::Cell* d_cells = nullptr;
+    acq::Cell* d_parts = nullptr;  // partial cells of multi-pass searches (more than 10000 lags)
+    acq::Peak* d_peaks = nullptr;
+    size_t task_cap = 0, cell_cap = 0, peak_cap = 0, parts_cap = 0;
+    // 8-bit IQ ingestion scratch
+    uint8_t* d_iq = nullptr;
+    size_t iq_cap = 0;
+    uint8_t* d_iqbits = nullptr;
+    size_t iqbits_cap = 0;
+    float* d_pdump = nullptr;  // non-coherent + creep re-alignment at fs > 10 MHz: per-lag power sums, [cell][nlags]
+    size_t pdump_cap = 0;
+    float* d_fsamp = nullptr;  // multi-bit path: the batch's samples as complex floats, LO applied ([block][40000][2])
+    size_t fsamp_cap = 0;
+    unsigned long long* d_sums = nullptr;
+    // capture generator scratch
+    acq::GenSat* d_sats = nullptr;
+    size_t sats_cap = 0;
+    uint8_t* d_gen = nullptr;
+    size_t gen_cap = 0;
+    int8_t* d_nav = nullptr;  // navigation bits of gpsacq_generate_nav_range
+    size_t nav_cap = 0;
+    // tracking channels (gpsacq_track*)
+    uint32_t* d_track_chips = nullptr;  // [32][32] C/A chips
+    gpsacq_track_chan* d_chans = nullptr;
+    size_t chans_cap = 0;
+    int32_t* d_track_n = nullptr;
+    size_t track_n_cap = 0;
+    int32_t* d_prompt = nullptr;
+    size_t prompt_cap = 0;
+    gpsacq_track_record* d_records = nullptr;
+    size_t records_cap = 0;
+    hipEvent_t tiq_ev[3] = {};  // gpsacq_track_iq8*: before the conversion, between it and the channels, after them
+    bool tiq_timed = false;
+    // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
+    int* d_persist = nullptr;
+    size_t persist_cap = 0;
+    bool persist = false;
+    // cached default schedule (task t = block t, PRN t % 32; with ref_quirks also its patch list: blocks 0, 32, 64, ...)
+    size_t sched_tasks = 0;
+    bool sched_valid = false;
+    // pipelined host-buffer searches (gpsacq_pipe_*): a second stream for the uploads, per-slot pinned staging and device buffers
+    hipStream_t copy_stream = nullptr;
+    struct PipeSlot {
+        uint8_t* h_in = nullptr;   // pinned
+        size_t h_cap = 0;
+        uint8_t* d_in = nullptr;
+        size_t d_cap = 0;
+        acq::Peak* d_peaks = nullptr;
+        acq::Peak* h_peaks = nullptr;   // pinned
+        size_t peak_cap = 0;
+        hipEvent_t uploaded = nullptr, done = nullptr;
+        bool busy = false;
+        size_t n_tasks = 0;
+    } pipe[GPSACQ_PIPE_SLOTS];
+};
+
+// what a search transforms: the 1-bit stream gps_test reads, or an 8-bit IQ capture converted while it is staged
+struct Capture {
+    bool iq8 = false;
+    const uint8_t* d_src = nullptr;  // device pointer
+    size_t stride = 0;               // bytes per block in d_src
+    acq::IqConv iq{};
+    size_t iq_first = 0, iq_total = ~(size_t)0;
+    int multibit = 0;  // 8-bit IQ kept at full amplitude (float samples) instead of its sign: 1 the real-IF value, 2 the complex sample
+};
+
+// Scratch buffers grow on demand, stream-ordered (hipFreeAsync / hipMallocAsync on the engine's stream): work already
+// enqueued keeps the old buffer until it has run, and no device-wide synchronisation happens in mid-stream.  They grow by at
+// least half so that a caller creeping up in batch size does not reallocate every call.
+template <class T> static int grow(T*& p, size_t& cap, size_t need, hipStream_t stream, size_t elem_bytes = sizeof(T)) {
+    if (need <= cap) return GPSACQ_OK;
+    need = std::max(need, cap + cap / 2);
+    if (p) HIPCHK(hipFreeAsync(p, stream));
+    p = nullptr;
+    cap = 0;
+    HIPCHK(hipMallocAsync((void**)&p, need * elem_bytes, stream));
+    cap = need;
+    return GPSACQ_OK;
+}
+
+// gpsacq_engine.cpp
+int iq8_capture(const gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t stride, Capture* out);
+int iq8_to_bits_enqueue(gpsacq_engine* e, const uint8_t* d_iq, size_t n_samples, const acq::IqConv& conv, size_t first_sample, uint8_t* d_bits);
+// gpsacq_track.cpp
+int ensure_track_chips(gpsacq_engine* e);

@@ -457,7 +457,7 @@ GPSACQ_API int gpsacq_multi_last_call_ms(const gpsacq_multi* m, double* enqueue_
 /*
  * ---- Tracking channels and NAV data (offline, on a recorded 1-bit real-IF capture) ----------------------------------------
  *
- * THE CHANNEL MODEL.  Integer arithmetic only; the kernel (csrc/track_kernels.hip) and the CPU model of the tests
+ * THE CHANNEL MODEL.  Integer arithmetic only; the kernels (csrc/track_channel.hpp) and the CPU model of the tests
  * (tests/c/track_model.c) are both written from this text, and agree bit for bit.  "mod 2^N" arithmetic is unsigned
  * wrap-around; the int64 fields below are two's-complement bit patterns of that arithmetic.  spm = samples per millisecond
  * (gpsacq_info.num_lags).  The sample stream is the one gpsacq_search() reads: sample m is bit m % 8 of byte m / 8, 1 = negative.
@@ -615,7 +615,7 @@ GPSACQ_API int gpsacq_generate_nav_range_device(gpsacq_engine* e, void* d_bits_o
  * to the window's first_sample), in->total_samples the capture's length (bits past it read 0), in->mean_i / mean_q the mean of the
  * WHOLE capture.  The window's first_sample must be a multiple of 8 (the byte grid of the 1-bit stream).
  *
- * in->multibit != 0 (GPSACQ_SAMPLES_REAL and GPSACQ_SAMPLES_COMPLEX alike): MULTI-BIT COMPLEX CHANNELS (csrc/track_iq_kernels.hip;
+ * in->multibit != 0 (GPSACQ_SAMPLES_REAL and GPSACQ_SAMPLES_COMPLEX alike): MULTI-BIT COMPLEX CHANNELS (csrc/track_iq_kernels.hip around csrc/track_channel.hpp;
  * CPU model tests/c/track_model_iq.c).  THE CHANNEL MODEL above with the sample and the sums replaced by:
  *   sample         v_i = I - off - dc_i,  v_q = Q - off - dc_q;  off = 128 for GPSACQ_IQ_U8, 0 for GPSACQ_IQ_S8;  dc_i = nearbyint(mean_i),
  *                  dc_q = nearbyint(mean_q) (ties to even) when remove_dc, else 0.  Integers: |v| <= 256.  There is no floating-point
