@@ -11,6 +11,7 @@
 #include "../../include/gpsacq.h"
 #include "acq_launch.hpp"
 #include "gen_launch.hpp"
+#include "nav_launch.hpp"
 
 // sets this thread's gpsacq_last_error() text from a printf format and returns `code` (gpsacq_engine.cpp)
 int fail(int code, const char* fmt, ...);
@@ -88,6 +89,17 @@ struct gpsacq_engine {
     size_t records_cap = 0;
     hipEvent_t tiq_ev[3] = {};  // gpsacq_track_iq8*: before the conversion, between it and the channels, after them
     bool tiq_timed = false;
+    // navigation solver (gpsacq_sat_states*, gpsacq_fix_batch*)
+    acq::NavEph* d_nav_eph = nullptr;  // the call's ephemeris table
+    size_t nav_eph_cap = 0;
+    gpsacq_obs* d_nav_obs = nullptr;  // host-buffer forms: observations and results
+    size_t nav_obs_cap = 0;
+    gpsacq_sat_state* d_nav_state = nullptr;  // k_sat_state's output, k_fix's input
+    size_t nav_state_cap = 0;
+    gpsacq_fix* d_nav_fix = nullptr;
+    size_t nav_fix_cap = 0;
+    hipEvent_t nav_ev[3] = {};  // gpsacq_fix_batch*: before k_sat_state, between the kernels, after k_fix
+    bool nav_timed = false;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;

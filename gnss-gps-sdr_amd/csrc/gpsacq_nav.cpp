@@ -1,0 +1,188 @@
+// gpsacq_nav.cpp -- host side of "Navigation solver" of include/gpsacq.h.  First the ephemeris, host only: the fields of
+// subframes 1-3 by IS-GPS-200 Tables 20-I and 20-III, read from gpsacq_subframe.words[].  Then the gpsacq_sat_states* and
+// gpsacq_fix_batch* entry points that run nav_kernels.hip on the engine of gpsacq_engine.hpp.
+// Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "gpsacq_engine.hpp"
+#include "nav_launch.hpp"
+
+using namespace acq;
+
+// ---- ephemeris ---------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr double GPS_PI = 3.1415926535898;
+
+// n bits (<= 32) that start at bit `bit` (1..24) of ICD word `word` (1..10) and run on into the data bits of the next word
+uint32_t ubits(const uint32_t* words, int word, int bit, int n) {
+    uint32_t v = 0;
+    int pos = (word - 1) * 24 + (bit - 1);  // index into the 240 data bits d1..d24 of the ten words
+    for (int k = 0; k < n; ++k, ++pos) v = (v << 1) | ((words[pos / 24] >> (23 - pos % 24)) & 1u);
+    return v;
+}
+int32_t sbits(const uint32_t* words, int word, int bit, int n) {
+    const uint32_t v = ubits(words, word, bit, n);
+    return n < 32 && (v >> (n - 1)) ? (int32_t)v - (int32_t)(1u << n) : (int32_t)v;
+}
+double scaled(double field, int exp2) { return std::ldexp(field, exp2); }
+double semicircles(double field, int exp2) { return std::ldexp(field, exp2) * GPS_PI; }
+}  // namespace
+
+extern "C" int gpsacq_ephemeris_load(gpsacq_ephemeris* eph, const gpsacq_subframe* sf, int n) {
+    if (!eph || n < 0 || (n > 0 && !sf)) return fail(GPSACQ_ERR_ARG, "gpsacq_ephemeris_load: bad argument");
+    for (int k = 0; k < n; ++k) {
+        const uint32_t* w = sf[k].words;
+        const int id = (int)ubits(w, 2, 20, 3);
+        if (id < 1 || id > 3) continue;
+        eph->tow = (int32_t)ubits(w, 2, 1, 17);
+        eph->have |= 1 << (id - 1);
+        if (id == 1) {  // Table 20-I
+            eph->week = ubits(w, 3, 1, 10);
+            eph->iodc = ubits(w, 3, 23, 2) << 8 | ubits(w, 8, 1, 8);
+            eph->t_gd = scaled(sbits(w, 7, 17, 8), -31);
+            eph->t_oc = ubits(w, 8, 9, 16) * 16u;
+            eph->a_f2 = scaled(sbits(w, 9, 1, 8), -55);
+            eph->a_f1 = scaled(sbits(w, 9, 9, 16), -43);
+            eph->a_f0 = scaled(sbits(w, 10, 1, 22), -31);
+        } else if (id == 2) {  // Table 20-III, subframe 2
+            eph->iode2 = ubits(w, 3, 1, 8);
+            eph->c_rs = scaled(sbits(w, 3, 9, 16), -5);
+            eph->dn = semicircles(sbits(w, 4, 1, 16), -43);
+            eph->m_0 = semicircles(sbits(w, 4, 17, 32), -31);
+            eph->c_uc = scaled(sbits(w, 6, 1, 16), -29);
+            eph->e = scaled(ubits(w, 6, 17, 32), -33);
+            eph->c_us = scaled(sbits(w, 8, 1, 16), -29);
+            eph->sqrt_a = scaled(ubits(w, 8, 17, 32), -19);
+            eph->t_oe = ubits(w, 10, 1, 16) * 16u;
+        } else {  // subframe 3
+            eph->c_ic = scaled(sbits(w, 3, 1, 16), -29);
+            eph->omega_0 = semicircles(sbits(w, 3, 17, 32), -31);
+            eph->c_is = scaled(sbits(w, 5, 1, 16), -29);
+            eph->i_0 = semicircles(sbits(w, 5, 17, 32), -31);
+            eph->c_rc = scaled(sbits(w, 7, 1, 16), -5);
+            eph->omega = semicircles(sbits(w, 7, 17, 32), -31);
+            eph->omega_dot = semicircles(sbits(w, 9, 1, 24), -43);
+            eph->iode3 = ubits(w, 10, 1, 8);
+            eph->idot = semicircles(sbits(w, 10, 9, 14), -43);
+        }
+    }
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_ephemeris_valid(const gpsacq_ephemeris* eph) {
+    if (!eph || (eph->have & 7) != 7) return 0;
+    return eph->iode2 != 0 && (eph->iodc & 0xffu) == eph->iode2 && eph->iode2 == eph->iode3;
+}
+
+// ---- satellite state and fixes (nav_kernels.hip) ----------------------------------------------------------------------------
+// the call's ephemerides as the kernels read them, into e->d_nav_eph
+static int nav_upload_eph(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph) {
+    std::vector<NavEph> tab((size_t)n_eph);
+    for (int k = 0; k < n_eph; ++k) {
+        const gpsacq_ephemeris& s = eph[k];
+        NavEph& d = tab[k];
+        d.t_gd = s.t_gd, d.a_f0 = s.a_f0, d.a_f1 = s.a_f1, d.a_f2 = s.a_f2;
+        d.c_rs = s.c_rs, d.dn = s.dn, d.m_0 = s.m_0, d.c_uc = s.c_uc, d.e = s.e, d.c_us = s.c_us, d.sqrt_a = s.sqrt_a;
+        d.c_ic = s.c_ic, d.omega_0 = s.omega_0, d.c_is = s.c_is, d.i_0 = s.i_0, d.c_rc = s.c_rc, d.omega = s.omega;
+        d.omega_dot = s.omega_dot, d.idot = s.idot;
+        // t_oc, t_oe: 16-bit fields * 16 s <= 1 048 560 s, so the milliseconds fit an int32; an epoch past the week is not an ephemeris
+        const bool in_week = s.t_oc < 604800u && s.t_oe < 604800u;
+        d.toc_ms = in_week ? (int32_t)(s.t_oc * 1000u) : 0;
+        d.toe_ms = in_week ? (int32_t)(s.t_oe * 1000u) : 0;
+        d.valid = in_week && gpsacq_ephemeris_valid(&s);
+        d.reserved = 0;
+    }
+    if (int rc = grow(e->d_nav_eph, e->nav_eph_cap, (size_t)n_eph, e->stream)) return rc;
+    // pageable source: the copy has left `tab` when the call returns
+    HIPCHK(hipMemcpyAsync(e->d_nav_eph, tab.data(), tab.size() * sizeof(NavEph), hipMemcpyHostToDevice, e->stream));
+    return GPSACQ_OK;
+}
+
+static int nav_check(const char* who, const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* obs, size_t n, const void* out) {
+    if (!e || !eph || n_eph <= 0 || !obs || !out || n == 0 || n > ((size_t)1 << 31)) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    return GPSACQ_OK;
+}
+static int nav_check_weights(const char* who, const gpsacq_obs* obs, size_t n) {
+    for (size_t k = 0; k < n; ++k)
+        if (!(obs[k].weight >= 0.0) || !std::isfinite(obs[k].weight))
+            return fail(GPSACQ_ERR_ARG, "%s: observation %zu has weight %g (must be finite and >= 0)", who, k, obs[k].weight);
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_sat_states_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, size_t n_obs,
+                                        void* d_out, int sync) {
+    if (int rc = nav_check("gpsacq_sat_states", e, eph, n_eph, d_obs, n_obs, d_out)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    launch_sat_state(SatStateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, (gpsacq_sat_state*)d_out}, e->stream);
+    HIPCHK(hipGetLastError());
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_sat_states(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs, size_t n_obs,
+                                 gpsacq_sat_state* out) {
+    if (int rc = nav_check("gpsacq_sat_states", e, eph, n_eph, obs, n_obs, out)) return rc;
+    if (int rc = nav_check_weights("gpsacq_sat_states", obs, n_obs)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    if (int rc = gpsacq_sat_states_device(e, eph, n_eph, e->d_nav_obs, n_obs, e->d_nav_state, 0)) return rc;
+    HIPCHK(hipMemcpyAsync(out, e->d_nav_state, n_obs * sizeof(gpsacq_sat_state), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, size_t n_fix,
+                                       int sats_per_fix, void* d_out, int sync) {
+    if (int rc = nav_check("gpsacq_fix_batch", e, eph, n_eph, d_obs, n_fix, d_out)) return rc;
+    if (sats_per_fix < 1 || sats_per_fix > GPSACQ_FIX_MAX_SATS)
+        return fail(GPSACQ_ERR_ARG, "gpsacq_fix_batch: sats_per_fix %d outside 1 .. %d", sats_per_fix, GPSACQ_FIX_MAX_SATS);
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
+    for (auto& ev : e->nav_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    e->nav_timed = false;
+    HIPCHK(hipEventRecord(e->nav_ev[0], e->stream));
+    launch_sat_state(SatStateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_nav_state}, e->stream);
+    HIPCHK(hipEventRecord(e->nav_ev[1], e->stream));
+    launch_fix(FixArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, e->d_nav_state, n_fix, sats_per_fix, (gpsacq_fix*)d_out}, e->stream);
+    HIPCHK(hipEventRecord(e->nav_ev[2], e->stream));
+    HIPCHK(hipGetLastError());
+    e->nav_timed = true;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs, size_t n_fix,
+                                int sats_per_fix, gpsacq_fix* out) {
+    if (int rc = nav_check("gpsacq_fix_batch", e, eph, n_eph, obs, n_fix, out)) return rc;
+    if (sats_per_fix < 1 || sats_per_fix > GPSACQ_FIX_MAX_SATS)
+        return fail(GPSACQ_ERR_ARG, "gpsacq_fix_batch: sats_per_fix %d outside 1 .. %d", sats_per_fix, GPSACQ_FIX_MAX_SATS);
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    if (int rc = nav_check_weights("gpsacq_fix_batch", obs, n_obs)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    if (int rc = gpsacq_fix_batch_device(e, eph, n_eph, e->d_nav_obs, n_fix, sats_per_fix, e->d_nav_fix, 0)) return rc;
+    HIPCHK(hipMemcpyAsync(out, e->d_nav_fix, n_fix * sizeof(gpsacq_fix), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* fix_ms) {
+    if (!e || !e->nav_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_last_ms: no gpsacq_fix_batch call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    HIPCHK(hipEventSynchronize(e->nav_ev[2]));
+    if (sat_state_ms) HIPCHK(hipEventElapsedTime(sat_state_ms, e->nav_ev[0], e->nav_ev[1]));
+    if (fix_ms) HIPCHK(hipEventElapsedTime(fix_ms, e->nav_ev[1], e->nav_ev[2]));
+    return GPSACQ_OK;
+}

@@ -72,6 +72,20 @@ TRACK_RECORD_DTYPE = np.dtype([("sample", "<u8"), ("ie", "<i4"), ("qe", "<i4"), 
                                ("ql", "<i4"), ("lo_rate", "<u4"), ("ca_rate", "<u4")])
 SUBFRAME_DTYPE = np.dtype([("bit_offset", "<i4"), ("inverted", "<i4"), ("words", "<u4", (10,)), ("id", "<i4"), ("tow", "<i4")])
 
+# navigation solver (include/gpsacq.h, "Navigation solver")
+FIX_OK, FIX_TOO_FEW, FIX_NO_CONVERGE = 0, 1, 2
+FIX_MAX_SATS = 12
+EPHEMERIS_DTYPE = np.dtype([("prn", "<i4"), ("have", "<i4"), ("week", "<u4"), ("iodc", "<u4"), ("iode2", "<u4"), ("iode3", "<u4"),
+                            ("t_oc", "<u4"), ("t_oe", "<u4"), ("tow", "<i4"), ("reserved", "<i4"),
+                            ("t_gd", "<f8"), ("a_f0", "<f8"), ("a_f1", "<f8"), ("a_f2", "<f8"),
+                            ("c_rs", "<f8"), ("dn", "<f8"), ("m_0", "<f8"), ("c_uc", "<f8"), ("e", "<f8"), ("c_us", "<f8"), ("sqrt_a", "<f8"),
+                            ("c_ic", "<f8"), ("omega_0", "<f8"), ("c_is", "<f8"), ("i_0", "<f8"), ("c_rc", "<f8"), ("omega", "<f8"),
+                            ("omega_dot", "<f8"), ("idot", "<f8")])
+OBS_DTYPE = np.dtype([("eph", "<i4"), ("valid", "<i4"), ("tx_ms", "<i4"), ("reserved", "<i4"), ("tx_frac", "<f8"), ("weight", "<f8")])
+SAT_STATE_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("clock_corr", "<f8")])
+FIX_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("iterations", "<i4"), ("rx_ms", "<i4"), ("rx_frac", "<f8"),
+                      ("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("lat", "<f8"), ("lon", "<f8"), ("alt", "<f8"), ("rms", "<f8")])
+
 
 class TrackParams(ctypes.Structure):
     _fields_ = [("lo_ki", ctypes.c_int32), ("lo_kp", ctypes.c_int32), ("ca_ki", ctypes.c_int32), ("ca_kp", ctypes.c_int32),
@@ -91,7 +105,9 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_nav_subframes", "gpsacq_generate_nav_range", "gpsacq_generate_nav_range_device",
            "gpsacq_track_iq8", "gpsacq_track_iq8_device", "gpsacq_track_iq8_last_ms", "gpsacq_track_start_iq8",
            "gpsacq_track_default_params_iq8", "gpsacq_iq8_accumulate_power", "gpsacq_generate_iq8_range",
-           "gpsacq_generate_iq8_range_device"]
+           "gpsacq_generate_iq8_range_device",
+           "gpsacq_ephemeris_load", "gpsacq_ephemeris_valid", "gpsacq_sat_states", "gpsacq_sat_states_device", "gpsacq_fix_batch",
+           "gpsacq_fix_batch_device", "gpsacq_fix_last_ms"]
 
 _lib = None
 
@@ -261,6 +277,20 @@ def load_library(path=None):
     lib.gpsacq_generate_iq8_range_device.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.POINTER(Sat),
                                                      ctypes.c_int, vp, ctypes.c_int, ctypes.c_float, ctypes.c_uint64, ctypes.c_int]
     lib.gpsacq_generate_iq8_range_device.restype = ctypes.c_int
+    lib.gpsacq_ephemeris_load.argtypes = [vp, vp, ctypes.c_int]
+    lib.gpsacq_ephemeris_load.restype = ctypes.c_int
+    lib.gpsacq_ephemeris_valid.argtypes = [vp]
+    lib.gpsacq_ephemeris_valid.restype = ctypes.c_int
+    lib.gpsacq_sat_states.argtypes = [vp, vp, ctypes.c_int, vp, sz, vp]
+    lib.gpsacq_sat_states.restype = ctypes.c_int
+    lib.gpsacq_sat_states_device.argtypes = [vp, vp, ctypes.c_int, vp, sz, vp, ctypes.c_int]
+    lib.gpsacq_sat_states_device.restype = ctypes.c_int
+    lib.gpsacq_fix_batch.argtypes = [vp, vp, ctypes.c_int, vp, sz, ctypes.c_int, vp]
+    lib.gpsacq_fix_batch.restype = ctypes.c_int
+    lib.gpsacq_fix_batch_device.argtypes = [vp, vp, ctypes.c_int, vp, sz, ctypes.c_int, vp, ctypes.c_int]
+    lib.gpsacq_fix_batch_device.restype = ctypes.c_int
+    lib.gpsacq_fix_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    lib.gpsacq_fix_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -312,6 +342,24 @@ def nav_subframes(bits):
     _check(lib, lib.gpsacq_nav_subframes(b.ctypes.data_as(ctypes.c_void_p), int(b.size), out.ctypes.data_as(ctypes.c_void_p), int(out.size),
                                          ctypes.byref(n), ctypes.byref(nf)))
     return out[:n.value].copy(), nf.value
+
+
+def ephemeris(subframes, prn, eph=None):
+    """gpsacq_ephemeris_load: subframes 1-3 of a SUBFRAME_DTYPE array (nav_subframes) folded, in order, into an EPHEMERIS_DTYPE
+    record of shape (1,) for PRN `prn` -- a fresh one, or a copy of `eph` to carry on from."""
+    lib = load_library()
+    sf = np.ascontiguousarray(np.asarray(subframes, dtype=SUBFRAME_DTYPE).ravel())
+    out = np.zeros(1, dtype=EPHEMERIS_DTYPE) if eph is None else np.array(eph, dtype=EPHEMERIS_DTYPE).reshape(1).copy()
+    out["prn"] = int(prn)
+    _check(lib, lib.gpsacq_ephemeris_load(out.ctypes.data_as(ctypes.c_void_p), sf.ctypes.data_as(ctypes.c_void_p) if sf.size else None,
+                                          int(sf.size)))
+    return out
+
+
+def ephemeris_valid(eph):
+    """gpsacq_ephemeris_valid of one EPHEMERIS_DTYPE record: subframes 1-3 loaded and IODC's low byte == both IODEs != 0."""
+    rec = np.array(eph, dtype=EPHEMERIS_DTYPE).reshape(1).copy()
+    return bool(load_library().gpsacq_ephemeris_valid(rec.ctypes.data_as(ctypes.c_void_p)))
 
 
 def search_code(sv, g1):
@@ -605,6 +653,50 @@ class Engine:
                                                         int(chans.size), ctypes.byref(p), d_prompt_ptr, d_records_ptr, int(max_epochs),
                                                         ne.ctypes.data_as(ctypes.c_void_p)))
         return ne
+
+    # ---- navigation solver ----------------------------------------------------------------
+    @staticmethod
+    def _nav_arrays(eph, obs):
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        if not isinstance(obs, np.ndarray) or obs.dtype != OBS_DTYPE:
+            raise TypeError("obs must be an OBS_DTYPE array")
+        return ep, np.ascontiguousarray(obs)
+
+    def sat_states(self, eph, obs):
+        """gpsacq_sat_states: ECEF position and clock correction (SAT_STATE_DTYPE, obs's shape) of every observation (OBS_DTYPE:
+        index into eph, an EPHEMERIS_DTYPE array, and the uncorrected satellite time as tx_ms, tx_frac)."""
+        ep, ob = self._nav_arrays(eph, obs)
+        out = np.zeros(ob.shape, dtype=SAT_STATE_DTYPE)
+        _check(self._lib, self._lib.gpsacq_sat_states(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), ob.ctypes.data_as(ctypes.c_void_p),
+                                                      int(ob.size), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def sat_states_device(self, eph, d_obs_ptr, n_obs, d_out_ptr, sync=True):
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        _check(self._lib, self._lib.gpsacq_sat_states_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_obs_ptr, int(n_obs),
+                                                             d_out_ptr, 1 if sync else 0))
+
+    def fix(self, eph, obs):
+        """gpsacq_fix_batch: obs is an OBS_DTYPE array [n_fix][sats_per_fix] (1 .. FIX_MAX_SATS per row, unusable entries are
+        skipped); returns FIX_DTYPE [n_fix]."""
+        ep, ob = self._nav_arrays(eph, obs)
+        if ob.ndim != 2:
+            raise ValueError("obs must be [n_fix][sats_per_fix]")
+        out = np.zeros(ob.shape[0], dtype=FIX_DTYPE)
+        _check(self._lib, self._lib.gpsacq_fix_batch(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), ob.ctypes.data_as(ctypes.c_void_p),
+                                                     int(ob.shape[0]), int(ob.shape[1]), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def fix_device(self, eph, d_obs_ptr, n_fix, sats_per_fix, d_out_ptr, sync=True):
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        _check(self._lib, self._lib.gpsacq_fix_batch_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_obs_ptr, int(n_fix),
+                                                            int(sats_per_fix), d_out_ptr, 1 if sync else 0))
+
+    def fix_last_ms(self):
+        """Device milliseconds of the last fix* call: (satellite-state kernel, fix kernel)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(self._lib, self._lib.gpsacq_fix_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     # ---- tracking channels on an 8-bit IQ capture -----------------------------------------
     def iq8_power(self, iq, signed=False):

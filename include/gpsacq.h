@@ -51,6 +51,10 @@
  *   gpsacq_nav_bits          the FPGA's NAV bit decision (sign of the I arm over a 20-epoch bit)
  *   gpsacq_nav_subframes     CHANNEL::ParityCheck(), c/channel.cpp:329-353, with the IS-GPS-200 Table 20-XIV parity
  *   gpsacq_generate_nav_range  gpsacq_generate_range with navigation data on every satellite
+ *   gpsacq_ephemeris_load    EPHEM::Subframe1/2/3(), c/ephemeris.cpp:36-68, with the fields of IS-GPS-200 Tables 20-I and 20-III
+ *   gpsacq_ephemeris_valid   EPHEM::Valid(), c/ephemeris.cpp:177-179 (IODC's eight low bits compared)
+ *   gpsacq_sat_states        EPHEM::GetClockCorrection() + GetXYZ(), c/ephemeris.cpp:114-173, for a batch of transmit times
+ *   gpsacq_fix_batch         Solve() + LatLonAlt(), c/solve.cpp:137-293, for a batch of receive instants
  *   gpsacq_sample_spectrum   Sample()'s fwd_buf      c/search_offline.cpp:161 (parity probe)
  *   gpsacq_code_spectrum     SearchInit()'s code[sv] c/search_offline.cpp:105-106 (parity probe)
  *
@@ -693,6 +697,86 @@ GPSACQ_API int gpsacq_generate_iq8_range(gpsacq_engine* e, void* iq_out, size_t 
 GPSACQ_API int gpsacq_generate_iq8_range_device(gpsacq_engine* e, void* d_iq_out, size_t n_samples, uint64_t first_sample, int format,
                                                 double if_hz, float scale, const gpsacq_sat* sats, int n_sats, const int8_t* nav,
                                                 int n_nav_bits, float noise_sigma, uint64_t seed, int sync);
+
+/*
+ * ---- Navigation solver: ephemeris, satellite state, batched position fixes ------------------------------------------------------
+ *
+ * Everything downstream of "the transmit time of every satellite at one receive instant": the work of the reference's
+ * c/ephemeris.cpp (subframe fields, satellite position, clock correction) and of Solve() / LatLonAlt(), c/solve.cpp:137-293.
+ * Taking those transmit times out of tracking channels (SNAPSHOT::GetClock(), c/solve.cpp:118-133) is not part of it.
+ *
+ * EPHEMERIS (host only).  gpsacq_ephemeris_load folds the subframes 1, 2, 3 among sf[0..n-1] into *eph in the order given (IDs 4,
+ * 5 and anything else are ignored; eph->prn and fields of subframes not seen are left as they are: zero the record first).  Field
+ * positions, widths, signedness and scale factors are IS-GPS-200 Tables 20-I and 20-III over gpsacq_subframe.words[] (word w of
+ * the ICD is words[w - 1], its bit b is bit 24 - b).  Each value is (integer field * its power of two), exact, and the semicircle
+ * fields are then multiplied once by the GPS pi, 3.1415926535898.  iodc is the whole 10-bit field.
+ * gpsacq_ephemeris_valid: 1 when subframes 1, 2, 3 are all loaded and (iodc & 0xff) == iode2 == iode3 != 0 (IS-GPS-200
+ * 20.3.3.4.1; EPHEM::Valid()), else 0 (also for NULL).
+ *
+ * TIME.  A time of week is a pair (ms, frac): whole milliseconds 0 .. 604 799 999 and seconds in [0, 1e-3) -- a double of
+ * seconds of week resolves 1.2e-10 s = 3.5 cm.  Times that feed the orbit (t - t_oe, t - t_oc) are formed from the integer
+ * millisecond difference, folded into +-302 400 s, plus frac.  Inside a fix every time is an offset from the fix's earliest
+ * transmit millisecond (differences folded the same way, so a fix may straddle the end of the week).
+ *
+ * SATELLITE STATE.  (tx_ms, tx_frac) is the UNCORRECTED satellite time, what a code replica shows.  With t_k from t_oe and t from
+ * t_oc at that time, Kepler's equation E = M + e sin E is iterated from E = M until the step is below 1e-12 (30 passes at most) and
+ *     clock_corr = a_f0 + a_f1 t + a_f2 t^2 + F e sqrt_a sin E - t_gd,      F = -4.442807633e-10.
+ * The position is IS-GPS-200 Table 20-IV at the corrected time (t_k - clock_corr), ECEF metres at that time, with
+ * mu = 3.986005e14, Omega_e-dot = 7.2921151467e-5.  An observation that is not usable (valid == 0, eph index outside
+ * [0, n_eph), an ephemeris that is not valid, a negative or non-finite weight) gives an all-zero gpsacq_sat_state.
+ *
+ * FIX.  Unknowns x, y, z and the receive time; start at the origin and at the mean corrected transmit time + 75 ms.  Per pass and
+ * satellite: turn the satellite by theta = Omega_e-dot (t_tx - t_rx) about z, residual = c (t_rx - t_tx) - range, Jacobian row
+ * (unit vector satellite -> receiver, c); weighted normal equations, solved by Cholesky with the time unknown in metres (c dt).
+ * Every step is applied and counted in `iterations`; one whose position part is below 1e-4 m is the last (the iteration converges
+ * quadratically, so what is left after it is far below the rounding; rms is that of the residuals the last step was made from).
+ * 20 steps without that, a pivot that is not positive (below 1e-13 of its diagonal entry) or a non-finite step:
+ * GPSACQ_FIX_NO_CONVERGE.  c = 2.99792458e8.
+ * lat / lon / alt: LatLonAlt()'s iteration on WGS-84 (a = 6378137, e^2 = 0.00669437999014132), until alt moves less than 1e-9 m,
+ * 10 passes at most.  A fix that is not GPSACQ_FIX_OK has every double field 0 and rx_ms = 0.
+ *
+ * gpsacq_sat_states: one state per observation.  gpsacq_fix_batch: obs[n_fix][sats_per_fix], one fix per row; unusable
+ * observations are skipped.  A negative or non-finite weight is GPSACQ_ERR_ARG in the host forms; the _device forms (device
+ * pointers for obs and out, eph stays a host pointer; work on the engine's stream, sync != 0 waits) cannot read the weights and
+ * skip such an observation instead.  Two kernels (csrc/nav_kernels.hip): one lane per observation, then one lane per fix.
+ */
+typedef struct {
+    int32_t prn;            /* 1..32 */
+    int32_t have;           /* bit s-1 set: subframe s (1..3) has been loaded */
+    uint32_t week, iodc, iode2, iode3, t_oc, t_oe;   /* t_oc, t_oe in seconds (field * 16) */
+    int32_t tow;            /* TOW count of the last subframe loaded */
+    int32_t reserved;
+    double t_gd, a_f0, a_f1, a_f2;
+    double c_rs, dn, m_0, c_uc, e, c_us, sqrt_a;
+    double c_ic, omega_0, c_is, i_0, c_rc, omega, omega_dot, idot;
+} gpsacq_ephemeris;         /* 192 bytes */
+GPSACQ_API int gpsacq_ephemeris_load(gpsacq_ephemeris* eph, const gpsacq_subframe* sf, int n);
+GPSACQ_API int gpsacq_ephemeris_valid(const gpsacq_ephemeris* eph);
+
+typedef struct { int32_t eph; int32_t valid; int32_t tx_ms; int32_t reserved; double tx_frac; double weight; } gpsacq_obs;   /* 32 bytes */
+typedef struct { double x, y, z; double clock_corr; } gpsacq_sat_state;                                                   /* 32 bytes */
+#define GPSACQ_FIX_OK 0
+#define GPSACQ_FIX_TOO_FEW 1      /* fewer than 4 usable observations */
+#define GPSACQ_FIX_NO_CONVERGE 2  /* 20 iterations, singular normal matrix, or a non-finite step */
+typedef struct {
+    int32_t status, n_used, iterations, rx_ms;
+    double rx_frac;               /* receive time = rx_ms, rx_frac, GPS time of week */
+    double x, y, z;               /* ECEF, metres */
+    double lat, lon, alt;         /* WGS-84, radians / metres */
+    double rms;                   /* weighted rms of the last residuals, metres */
+} gpsacq_fix;                     /* 80 bytes */
+#define GPSACQ_FIX_MAX_SATS 12
+GPSACQ_API int gpsacq_sat_states(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs, size_t n_obs,
+                                 gpsacq_sat_state* out);
+GPSACQ_API int gpsacq_sat_states_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, size_t n_obs,
+                                        void* d_out, int sync);
+GPSACQ_API int gpsacq_fix_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs /* [n_fix][sats_per_fix] */,
+                                size_t n_fix, int sats_per_fix, gpsacq_fix* out);
+GPSACQ_API int gpsacq_fix_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, size_t n_fix,
+                                       int sats_per_fix, void* d_out, int sync);
+/* device time of the two kernels of the last gpsacq_fix_batch* call on this engine, milliseconds (HIP events on its stream; waits
+ * for them).  Either pointer may be NULL. */
+GPSACQ_API int gpsacq_fix_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* fix_ms);
 
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);
