@@ -12,6 +12,7 @@
 #include "acq_launch.hpp"
 #include "gen_launch.hpp"
 #include "nav_launch.hpp"
+#include "obs_launch.hpp"
 
 // sets this thread's gpsacq_last_error() text from a printf format and returns `code` (gpsacq_engine.cpp)
 int fail(int code, const char* fmt, ...);
@@ -100,6 +101,15 @@ struct gpsacq_engine {
     size_t nav_fix_cap = 0;
     hipEvent_t nav_ev[3] = {};  // gpsacq_fix_batch*: before k_sat_state, between the kernels, after k_fix
     bool nav_timed = false;
+    // observables (gpsacq_observables*, gpsacq_fix_track_device)
+    acq::ObsChan* d_obs_chan = nullptr;  // the call's channels as the kernels read them
+    size_t obs_chan_cap = 0;
+    uint64_t* d_obs_pos = nullptr;  // k_code_pos's output, k_observe's input: [n_chans][max_epochs]
+    size_t obs_pos_cap = 0;
+    gpsacq_track_record* d_obs_rec = nullptr;  // host-buffer form: the records
+    size_t obs_rec_cap = 0;
+    hipEvent_t obs_ev[3] = {};  // before k_code_pos, between the kernels, after k_observe
+    bool obs_timed = false;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;

@@ -1,6 +1,7 @@
 // gpsacq_nav.cpp -- host side of "Navigation solver" of include/gpsacq.h.  First the ephemeris, host only: the fields of
 // subframes 1-3 by IS-GPS-200 Tables 20-I and 20-III, read from gpsacq_subframe.words[].  Then the gpsacq_sat_states* and
-// gpsacq_fix_batch* entry points that run nav_kernels.hip on the engine of gpsacq_engine.hpp.
+// gpsacq_fix_batch* entry points that run nav_kernels.hip on the engine of gpsacq_engine.hpp.  Last "Observables": the time tag
+// (host only) and the gpsacq_observables* / gpsacq_fix_track_device entry points that run obs_kernels.hip.
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 
 #include "gpsacq_engine.hpp"
 #include "nav_launch.hpp"
+#include "obs_launch.hpp"
 
 using namespace acq;
 
@@ -184,5 +186,114 @@ extern "C" int gpsacq_fix_last_ms(const gpsacq_engine* e, float* sat_state_ms, f
     HIPCHK(hipEventSynchronize(e->nav_ev[2]));
     if (sat_state_ms) HIPCHK(hipEventElapsedTime(sat_state_ms, e->nav_ev[0], e->nav_ev[1]));
     if (fix_ms) HIPCHK(hipEventElapsedTime(fix_ms, e->nav_ev[1], e->nav_ev[2]));
+    return GPSACQ_OK;
+}
+
+// ---- observables (obs_kernels.hip) ------------------------------------------------------------------------------------------
+extern "C" int gpsacq_time_tag_from_subframe(const gpsacq_subframe* sf, int bit_epoch0, int eph_index, gpsacq_time_tag* tag) {
+    if (!sf || !tag) return fail(GPSACQ_ERR_ARG, "gpsacq_time_tag_from_subframe: null argument");
+    if (sf->tow < 0 || sf->tow > 100799) return fail(GPSACQ_ERR_ARG, "gpsacq_time_tag_from_subframe: TOW count %d outside 0 .. 100799", sf->tow);
+    tag->epoch = bit_epoch0 + 20 * sf->bit_offset;
+    tag->ms = (sf->tow + 100799) % 100800 * 6000;  // the count names the start of the NEXT subframe
+    tag->eph = eph_index;
+    tag->valid = 1;
+    return GPSACQ_OK;
+}
+
+static int obs_check(const char* who, const gpsacq_engine* e, const void* records, int max_epochs, const int32_t* n_epochs,
+                     const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans, uint64_t first_rx_sample, uint64_t rx_step,
+                     size_t n_fix) {
+    if (!e || !records || !n_epochs || !chans || !tags || max_epochs < 0 || n_fix == 0 || n_fix > ((size_t)1 << 31))
+        return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (n_chans < 1 || n_chans > GPSACQ_FIX_MAX_SATS) return fail(GPSACQ_ERR_ARG, "%s: n_chans %d outside 1 .. %d", who, n_chans, GPSACQ_FIX_MAX_SATS);
+    if (rx_step == 0) return fail(GPSACQ_ERR_ARG, "%s: rx_step must be at least 1", who);
+    if ((uint64_t)(n_fix - 1) > (UINT64_MAX - first_rx_sample) / rx_step)
+        return fail(GPSACQ_ERR_ARG, "%s: the last receive instant does not fit 64 bits", who);
+    for (int c = 0; c < n_chans; ++c)
+        if (n_epochs[c] < 0 || n_epochs[c] > max_epochs)
+            return fail(GPSACQ_ERR_ARG, "%s: channel %d has %d epochs, max_epochs is %d", who, c, n_epochs[c], max_epochs);
+    return GPSACQ_OK;
+}
+
+// both kernels on the engine's stream; every argument has been checked
+static int obs_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
+                       const gpsacq_time_tag* tags, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, void* d_obs) {
+    ObsChan tab[GPSACQ_FIX_MAX_SATS];
+    for (int c = 0; c < n_chans; ++c) {
+        ObsChan& d = tab[c];
+        d.ca_pos = chans[c].ca_pos, d.next_sample = chans[c].next_sample;
+        d.n = n_epochs[c];
+        d.first_epoch = (int32_t)((uint32_t)chans[c].epoch - (uint32_t)n_epochs[c]);
+        d.tag_epoch = tags[c].epoch, d.tag_ms = tags[c].ms, d.tag_eph = tags[c].eph, d.tag_valid = tags[c].valid;
+    }
+    if (int rc = grow(e->d_obs_chan, e->obs_chan_cap, (size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
+    if (int rc = grow(e->d_obs_pos, e->obs_pos_cap, (size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
+    // pageable source: the copy has left `tab` when the call returns
+    HIPCHK(hipMemcpyAsync(e->d_obs_chan, tab, (size_t)n_chans * sizeof(ObsChan), hipMemcpyHostToDevice, e->stream));
+    for (auto& ev : e->obs_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    e->obs_timed = false;
+    HIPCHK(hipEventRecord(e->obs_ev[0], e->stream));
+    launch_code_pos(CodePosArgs{e->d_obs_chan, (const gpsacq_track_record*)d_records, max_epochs, e->d_obs_pos}, n_chans, e->stream);
+    HIPCHK(hipEventRecord(e->obs_ev[1], e->stream));
+    launch_observe(ObserveArgs{e->d_obs_chan, (const gpsacq_track_record*)d_records, e->d_obs_pos, max_epochs, n_chans, first_rx_sample, rx_step,
+                               n_fix, (gpsacq_obs*)d_obs},
+                   e->stream);
+    HIPCHK(hipEventRecord(e->obs_ev[2], e->stream));
+    HIPCHK(hipGetLastError());
+    e->obs_timed = true;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_observables_device(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs,
+                                         const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans,
+                                         uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, void* d_obs, int sync) {
+    if (int rc = obs_check("gpsacq_observables", e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix)) return rc;
+    if (!d_obs) return fail(GPSACQ_ERR_ARG, "gpsacq_observables: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = obs_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, d_obs)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_observables(gpsacq_engine* e, const gpsacq_track_record* records, int max_epochs, const int32_t* n_epochs,
+                                  const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans,
+                                  uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, gpsacq_obs* obs) {
+    if (int rc = obs_check("gpsacq_observables", e, records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix)) return rc;
+    if (!obs) return fail(GPSACQ_ERR_ARG, "gpsacq_observables: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_obs = n_fix * (size_t)n_chans;
+    if (int rc = grow(e->d_obs_rec, e->obs_rec_cap, (size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
+    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    for (int c = 0; c < n_chans; ++c)  // the rows keep their stride; only the records that exist travel
+        if (n_epochs[c] > 0)
+            HIPCHK(hipMemcpyAsync(e->d_obs_rec + (size_t)c * max_epochs, records + (size_t)c * max_epochs,
+                                  (size_t)n_epochs[c] * sizeof(gpsacq_track_record), hipMemcpyHostToDevice, e->stream));
+    if (int rc = obs_enqueue(e, e->d_obs_rec, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, e->d_nav_obs)) return rc;
+    HIPCHK(hipMemcpyAsync(obs, e->d_nav_obs, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_track_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_records, int max_epochs,
+                                       const int32_t* n_epochs, const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans,
+                                       uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, void* d_obs, void* d_fix, int sync) {
+    if (int rc = obs_check("gpsacq_fix_track", e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix)) return rc;
+    if (!eph || n_eph <= 0 || !d_fix) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_track: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (!d_obs) {
+        if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_fix * (size_t)n_chans, e->stream)) return rc;
+        d_obs = e->d_nav_obs;
+    }
+    if (int rc = obs_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, d_obs)) return rc;
+    return gpsacq_fix_batch_device(e, eph, n_eph, d_obs, n_fix, n_chans, d_fix, sync);
+}
+
+extern "C" int gpsacq_observables_last_ms(const gpsacq_engine* e, float* code_pos_ms, float* observe_ms) {
+    if (!e || !e->obs_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_observables_last_ms: no gpsacq_observables call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    HIPCHK(hipEventSynchronize(e->obs_ev[2]));
+    if (code_pos_ms) HIPCHK(hipEventElapsedTime(code_pos_ms, e->obs_ev[0], e->obs_ev[1]));
+    if (observe_ms) HIPCHK(hipEventElapsedTime(observe_ms, e->obs_ev[1], e->obs_ev[2]));
     return GPSACQ_OK;
 }

@@ -8,6 +8,9 @@
 //     chan K PRN P status ok|lost epochs E dop_hz D code_hz C bits B
 //     subframe PRN P id I tow T
 //     parity PRN P failures F
+// and, when at least four channels have a valid ephemeris (subframes 1-3) and a time tag, one position fix per second of capture
+// (gpsacq_observables + gpsacq_fix_batch), from the first whole second at which every such channel has records to the last:
+//     fix tow T lat LAT lon LON alt ALT n_used N rms R          (T seconds of week, degrees, metres)
 //
 // With GPSACQ_INPUT=iq_u8|iq_s8 in the environment FILE is an 8-bit IQ capture (rtl-sdr / HackRF, README.md:83-115), read the way
 // gps_test reads it (host/search_api.cpp: GPSACQ_MIX_HZ, GPSACQ_IQ_KEEP_DC, GPSACQ_IQ_MULTIBIT, GPSACQ_IQ_COMPLEX; the mean of the
@@ -127,15 +130,20 @@ int main(int argc, char** argv) {
     gpsacq_get_info(e, &info);
     const int max_epochs = (int)(n_samples / (size_t)info.num_lags) + 2;
     std::vector<int32_t> prompt(chans.size() * (size_t)max_epochs * 2), n_ep(chans.size());
+    std::vector<gpsacq_track_record> records(chans.size() * (size_t)max_epochs);
     if (rc == 0 && !chans.empty())
-        rc = iq ? gpsacq_track_iq8(e, &iqin, bits.data(), n_samples, 0, chans.data(), (int)chans.size(), params, prompt.data(), nullptr, max_epochs, n_ep.data())
-                : gpsacq_track(e, bits.data(), n_bytes, 0, chans.data(), (int)chans.size(), nullptr, prompt.data(), nullptr, max_epochs, n_ep.data());
+        rc = iq ? gpsacq_track_iq8(e, &iqin, bits.data(), n_samples, 0, chans.data(), (int)chans.size(), params, prompt.data(), records.data(), max_epochs, n_ep.data())
+                : gpsacq_track(e, bits.data(), n_bytes, 0, chans.data(), (int)chans.size(), nullptr, prompt.data(), records.data(), max_epochs, n_ep.data());
     if (rc) {
         std::fprintf(stderr, "gps_track: %d: %s\n", rc, gpsacq_last_error());
         gpsacq_destroy(e);
         return rc;
     }
     const double two32 = 4294967296.0;
+    // the channels a fix can use: their ephemerides, time tags and rows of `records`
+    std::vector<gpsacq_ephemeris> ephs;
+    std::vector<gpsacq_time_tag> tags;
+    std::vector<size_t> fix_chan;
     for (size_t c = 0; c < chans.size(); ++c) {
         const gpsacq_track_chan& ch = chans[c];
         const int n = n_ep[c];
@@ -159,6 +167,52 @@ int main(int argc, char** argv) {
         gpsacq_nav_subframes(nb.data(), n_bits, sf.data(), (int)sf.size(), &n_sf, &n_fail);
         for (int k = 0; k < n_sf && k < (int)sf.size(); ++k) std::printf("subframe PRN %d id %d tow %d\n", ch.prn, sf[k].id, sf[k].tow);
         std::printf("parity PRN %d failures %d\n", ch.prn, n_fail);
+        if (n_sf > (int)sf.size()) n_sf = (int)sf.size();
+        gpsacq_ephemeris eph;
+        std::memset(&eph, 0, sizeof eph);
+        eph.prn = ch.prn;
+        gpsacq_time_tag tag;
+        if (n_sf > 0 && fix_chan.size() < GPSACQ_FIX_MAX_SATS && gpsacq_ephemeris_load(&eph, sf.data(), n_sf) == GPSACQ_OK &&
+            gpsacq_ephemeris_valid(&eph) && gpsacq_time_tag_from_subframe(&sf[0], e0, (int)ephs.size(), &tag) == GPSACQ_OK) {
+            ephs.push_back(eph);
+            tags.push_back(tag);
+            fix_chan.push_back(c);
+        }
+    }
+    if (fix_chan.size() >= 4) {
+        const size_t m = fix_chan.size();
+        std::vector<gpsacq_track_record> rec(m * (size_t)max_epochs);
+        std::vector<gpsacq_track_chan> fch(m);
+        std::vector<int32_t> fn(m);
+        uint64_t from = 0, to = UINT64_MAX;  // every channel has records over [from, to)
+        for (size_t k = 0; k < m; ++k) {
+            const size_t c = fix_chan[k];
+            std::memcpy(&rec[k * max_epochs], &records[c * max_epochs], (size_t)n_ep[c] * sizeof(gpsacq_track_record));
+            fch[k] = chans[c];
+            fn[k] = n_ep[c];
+            const uint64_t first = n_ep[c] > 0 ? records[c * max_epochs].sample : chans[c].next_sample;
+            if (first > from) from = first;
+            if (chans[c].next_sample < to) to = chans[c].next_sample;
+        }
+        const uint64_t step = (uint64_t)std::llround(prm.fs);  // one second of samples
+        const uint64_t first_rx = (from + step - 1) / step * step;
+        if (step > 0 && first_rx < to) {
+            const size_t n_fix = (size_t)((to - 1 - first_rx) / step) + 1;
+            std::vector<gpsacq_obs> obs(n_fix * m);
+            std::vector<gpsacq_fix> fix(n_fix);
+            rc = gpsacq_observables(e, rec.data(), max_epochs, fn.data(), fch.data(), tags.data(), (int)m, first_rx, step, n_fix, obs.data());
+            if (rc == 0) rc = gpsacq_fix_batch(e, ephs.data(), (int)ephs.size(), obs.data(), n_fix, (int)m, fix.data());
+            if (rc) {
+                std::fprintf(stderr, "gps_track: %d: %s\n", rc, gpsacq_last_error());
+                gpsacq_destroy(e);
+                return rc;
+            }
+            const double deg = 180.0 / 3.14159265358979323846;
+            for (size_t k = 0; k < n_fix; ++k)
+                if (fix[k].status == GPSACQ_FIX_OK)
+                    std::printf("fix tow %.6f lat %.7f lon %.7f alt %.2f n_used %d rms %.2f\n", fix[k].rx_ms * 1e-3 + fix[k].rx_frac,
+                                fix[k].lat * deg, fix[k].lon * deg, fix[k].alt, fix[k].n_used, fix[k].rms);
+        }
     }
     gpsacq_destroy(e);
     return 0;

@@ -85,6 +85,8 @@ OBS_DTYPE = np.dtype([("eph", "<i4"), ("valid", "<i4"), ("tx_ms", "<i4"), ("rese
 SAT_STATE_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("clock_corr", "<f8")])
 FIX_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("iterations", "<i4"), ("rx_ms", "<i4"), ("rx_frac", "<f8"),
                       ("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("lat", "<f8"), ("lon", "<f8"), ("alt", "<f8"), ("rms", "<f8")])
+# observables (include/gpsacq.h, "Observables")
+TIME_TAG_DTYPE = np.dtype([("epoch", "<i4"), ("ms", "<i4"), ("eph", "<i4"), ("valid", "<i4")])
 
 
 class TrackParams(ctypes.Structure):
@@ -107,7 +109,9 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_track_default_params_iq8", "gpsacq_iq8_accumulate_power", "gpsacq_generate_iq8_range",
            "gpsacq_generate_iq8_range_device",
            "gpsacq_ephemeris_load", "gpsacq_ephemeris_valid", "gpsacq_sat_states", "gpsacq_sat_states_device", "gpsacq_fix_batch",
-           "gpsacq_fix_batch_device", "gpsacq_fix_last_ms"]
+           "gpsacq_fix_batch_device", "gpsacq_fix_last_ms",
+           "gpsacq_time_tag_from_subframe", "gpsacq_observables", "gpsacq_observables_device", "gpsacq_fix_track_device",
+           "gpsacq_observables_last_ms"]
 
 _lib = None
 
@@ -291,6 +295,17 @@ def load_library(path=None):
     lib.gpsacq_fix_batch_device.restype = ctypes.c_int
     lib.gpsacq_fix_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     lib.gpsacq_fix_last_ms.restype = ctypes.c_int
+    lib.gpsacq_time_tag_from_subframe.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]
+    lib.gpsacq_time_tag_from_subframe.restype = ctypes.c_int
+    obs_args = [vp, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, sz, vp]
+    lib.gpsacq_observables.argtypes = obs_args
+    lib.gpsacq_observables.restype = ctypes.c_int
+    lib.gpsacq_observables_device.argtypes = obs_args + [ctypes.c_int]
+    lib.gpsacq_observables_device.restype = ctypes.c_int
+    lib.gpsacq_fix_track_device.argtypes = [vp, vp, ctypes.c_int] + obs_args[1:] + [vp, ctypes.c_int]
+    lib.gpsacq_fix_track_device.restype = ctypes.c_int
+    lib.gpsacq_observables_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    lib.gpsacq_observables_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -360,6 +375,19 @@ def ephemeris_valid(eph):
     """gpsacq_ephemeris_valid of one EPHEMERIS_DTYPE record: subframes 1-3 loaded and IODC's low byte == both IODEs != 0."""
     rec = np.array(eph, dtype=EPHEMERIS_DTYPE).reshape(1).copy()
     return bool(load_library().gpsacq_ephemeris_valid(rec.ctypes.data_as(ctypes.c_void_p)))
+
+
+def time_tag(subframe, bit_epoch0, eph_index):
+    """gpsacq_time_tag_from_subframe: the TIME_TAG_DTYPE record (shape (1,)) of a channel from one of its subframes (a
+    SUBFRAME_DTYPE record of nav_subframes), bit_epoch0 being nav_bits' second result for the bit stream the subframe was found in,
+    and eph_index the row of the ephemeris table the channel's observations will name."""
+    lib = load_library()
+    sf = np.zeros(1, dtype=SUBFRAME_DTYPE)
+    sf[0] = subframe
+    tag = np.zeros(1, dtype=TIME_TAG_DTYPE)
+    _check(lib, lib.gpsacq_time_tag_from_subframe(sf.ctypes.data_as(ctypes.c_void_p), int(bit_epoch0), int(eph_index),
+                                                  tag.ctypes.data_as(ctypes.c_void_p)))
+    return tag
 
 
 def search_code(sv, g1):
@@ -698,6 +726,55 @@ class Engine:
         _check(self._lib, self._lib.gpsacq_fix_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
+    # ---- observables ----------------------------------------------------------------------
+    @staticmethod
+    def _obs_arrays(n_epochs, chans, tags):
+        ne = np.ascontiguousarray(np.asarray(n_epochs, dtype=np.int32).ravel())
+        ch = np.ascontiguousarray(np.asarray(chans, dtype=TRACK_CHAN_DTYPE).ravel())
+        tg = np.ascontiguousarray(np.asarray(tags, dtype=TIME_TAG_DTYPE).ravel())
+        if not (ne.size == ch.size == tg.size):
+            raise ValueError("n_epochs, chans and tags must hold one entry per channel")
+        return ne, ch, tg
+
+    def observables(self, records, n_epochs, chans, tags, first_rx_sample, rx_step, n_fix):
+        """gpsacq_observables: the uncorrected transmit time of every channel at the receive samples first_rx_sample + i * rx_step,
+        i < n_fix.  records: TRACK_RECORD_DTYPE [n_chans][max_epochs] of ONE track() call, n_epochs its third result, chans the
+        channels after it, tags a TIME_TAG_DTYPE array (time_tag).  Returns OBS_DTYPE [n_fix][n_chans], the layout fix() takes."""
+        ne, ch, tg = self._obs_arrays(n_epochs, chans, tags)
+        if not isinstance(records, np.ndarray) or records.dtype != TRACK_RECORD_DTYPE or records.ndim != 2 or records.shape[0] != ne.size:
+            raise TypeError("records must be a TRACK_RECORD_DTYPE array [n_chans][max_epochs]")
+        rec = np.ascontiguousarray(records)
+        out = np.zeros((int(n_fix), ne.size), dtype=OBS_DTYPE)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_observables(self._h, p(rec), int(rec.shape[1]), p(ne), p(ch), p(tg), int(ne.size), int(first_rx_sample),
+                                                       int(rx_step), int(n_fix), p(out)))
+        return out
+
+    def observables_device(self, d_records_ptr, max_epochs, n_epochs, chans, tags, first_rx_sample, rx_step, n_fix, d_obs_ptr, sync=True):
+        """gpsacq_observables_device: the records as track_device / track_iq8_device left them in device memory (row stride
+        max_epochs), the observations [n_fix][n_chans] into device memory; n_epochs, chans and tags are host arrays."""
+        ne, ch, tg = self._obs_arrays(n_epochs, chans, tags)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_observables_device(self._h, d_records_ptr, int(max_epochs), p(ne), p(ch), p(tg), int(ne.size),
+                                                              int(first_rx_sample), int(rx_step), int(n_fix), d_obs_ptr, 1 if sync else 0))
+
+    def fix_track_device(self, eph, d_records_ptr, max_epochs, n_epochs, chans, tags, first_rx_sample, rx_step, n_fix, d_fix_ptr,
+                         d_obs_ptr=None, sync=True):
+        """gpsacq_fix_track_device: observables_device, then fix_device on them, on the engine's stream with no host copy in
+        between.  d_fix: FIX_DTYPE [n_fix] in device memory; d_obs_ptr None keeps the observations in engine scratch."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        ne, ch, tg = self._obs_arrays(n_epochs, chans, tags)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_fix_track_device(self._h, p(ep), int(ep.size), d_records_ptr, int(max_epochs), p(ne), p(ch), p(tg),
+                                                            int(ne.size), int(first_rx_sample), int(rx_step), int(n_fix), d_obs_ptr, d_fix_ptr,
+                                                            1 if sync else 0))
+
+    def observables_last_ms(self):
+        """Device milliseconds of the last observables* / fix_track_device call: (code-position kernel, observation kernel)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(self._lib, self._lib.gpsacq_observables_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     # ---- tracking channels on an 8-bit IQ capture -----------------------------------------
     def iq8_power(self, iq, signed=False):
         """gpsacq_iq8_accumulate_power over a whole buffer: (mean of (I - off)^2, mean of (Q - off)^2), from exact integer sums."""
@@ -817,9 +894,16 @@ class Engine:
                                                            int(first_sample), n, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
-    def generate_device(self, d_bits_ptr, n_bytes, sats=(), noise_sigma=1.0, seed=1, sync=True, first_sample=0):
-        _check(self._lib, self._lib.gpsacq_generate_range_device(self._h, d_bits_ptr, int(n_bytes), int(first_sample), self._sats(sats),
-                                                                 len(sats), float(noise_sigma), int(seed), 1 if sync else 0))
+    def generate_device(self, d_bits_ptr, n_bytes, sats=(), noise_sigma=1.0, seed=1, sync=True, first_sample=0, nav=None):
+        """generate() into device memory; nav as there (gpsacq_generate_nav_range_device)."""
+        if nav is None:
+            _check(self._lib, self._lib.gpsacq_generate_range_device(self._h, d_bits_ptr, int(n_bytes), int(first_sample), self._sats(sats),
+                                                                     len(sats), float(noise_sigma), int(seed), 1 if sync else 0))
+            return
+        nv = np.ascontiguousarray(np.asarray(nav, dtype=np.int8).reshape(len(sats), -1))
+        _check(self._lib, self._lib.gpsacq_generate_nav_range_device(self._h, d_bits_ptr, int(n_bytes), int(first_sample), self._sats(sats),
+                                                                     len(sats), nv.ctypes.data_as(ctypes.c_void_p), int(nv.shape[1]),
+                                                                     float(noise_sigma), int(seed), 1 if sync else 0))
 
     # ---- 8-bit IQ ingestion --------------------------------------------------------------
     def iq8_to_bits(self, iq, signed=False, remove_dc=True, mix_hz=0.0, fs=0.0):

@@ -55,6 +55,10 @@
  *   gpsacq_ephemeris_valid   EPHEM::Valid(), c/ephemeris.cpp:177-179 (IODC's eight low bits compared)
  *   gpsacq_sat_states        EPHEM::GetClockCorrection() + GetXYZ(), c/ephemeris.cpp:114-173, for a batch of transmit times
  *   gpsacq_fix_batch         Solve() + LatLonAlt(), c/solve.cpp:137-293, for a batch of receive instants
+ *   gpsacq_observables       SNAPSHOT::GetClock(), c/solve.cpp:118-133, for every channel at a batch of receive instants: the
+ *                            uncorrected transmit times, read off the records of the tracking channels
+ *   gpsacq_time_tag_from_subframe  the TOW term of GetClock() (c/solve.cpp:125): which millisecond of the week a channel epoch is
+ *   gpsacq_fix_track_device  GetClock() + Solve() + LatLonAlt() in one go: records -> observations -> fixes without a host copy
  *   gpsacq_sample_spectrum   Sample()'s fwd_buf      c/search_offline.cpp:161 (parity probe)
  *   gpsacq_code_spectrum     SearchInit()'s code[sv] c/search_offline.cpp:105-106 (parity probe)
  *
@@ -703,7 +707,7 @@ GPSACQ_API int gpsacq_generate_iq8_range_device(gpsacq_engine* e, void* d_iq_out
  *
  * Everything downstream of "the transmit time of every satellite at one receive instant": the work of the reference's
  * c/ephemeris.cpp (subframe fields, satellite position, clock correction) and of Solve() / LatLonAlt(), c/solve.cpp:137-293.
- * Taking those transmit times out of tracking channels (SNAPSHOT::GetClock(), c/solve.cpp:118-133) is not part of it.
+ * Taking those transmit times out of tracking channels (SNAPSHOT::GetClock(), c/solve.cpp:118-133) is the section after this one.
  *
  * EPHEMERIS (host only).  gpsacq_ephemeris_load folds the subframes 1, 2, 3 among sf[0..n-1] into *eph in the order given (IDs 4,
  * 5 and anything else are ignored; eph->prn and fields of subframes not seen are left as they are: zero the record first).  Field
@@ -777,6 +781,71 @@ GPSACQ_API int gpsacq_fix_batch_device(gpsacq_engine* e, const gpsacq_ephemeris*
 /* device time of the two kernels of the last gpsacq_fix_batch* call on this engine, milliseconds (HIP events on its stream; waits
  * for them).  Either pointer may be NULL. */
 GPSACQ_API int gpsacq_fix_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* fix_ms);
+
+/*
+ * ---- Observables: transmit times from tracking channels -----------------------------------------------------------------------
+ *
+ * The step between the tracking channels and the solver: SNAPSHOT::GetClock(), c/solve.cpp:118-133, adds TOW x 6 s + buffered bits
+ * x 20 ms + ms since the last bit + code chips + code NCO phase.  An offline channel has the same five terms: a TIME TAG gives
+ * the first, the epoch count the second and third, the prompt code position P the last two.  THE MODEL; the kernels
+ * (csrc/obs_kernels.hip) and the reference of the tests (tests/obs_ref.py) are both written from this text.  Integer arithmetic
+ * up to one final division; "mod 2^64" is unsigned wrap-around.
+ *
+ * TIME TAG (host arithmetic, no device needed).  gpsacq_time_tag_from_subframe: bit_epoch0 is gpsacq_nav_bits's output -- the channel
+ * epoch where bit 0 of the stream that sf->bit_offset indexes starts.
+ *     epoch = bit_epoch0 + 20 * sf->bit_offset     the channel epoch whose start is the leading edge of the subframe's first bit
+ *     ms    = ((tow - 1) mod 100800) * 6000        non-negative modulus: the HOW's TOW count names the start of the NEXT subframe
+ *                                                  (IS-GPS-200 20.3.3.2), so tow = 0 gives 604 794 000
+ *     eph   = eph_index                            the row of the caller's ephemeris table this channel's observations will name
+ *     valid = 1
+ * tow outside 0..100799 or a NULL pointer: GPSACQ_ERR_ARG.
+ *
+ * CODE POSITION PER EPOCH.  gpsacq_track_record holds `sample` and `ca_rate` but not ca_pos.  Inputs: records[c][0..n-1] of ONE
+ * tracking call on channel c, chans[c] = the channel state AFTER that call (next_sample, ca_pos, epoch), n = n_epochs[c].  With
+ *     end_t = records[c][t+1].sample for t < n-1,  end_{n-1} = chans[c].next_sample,      n_t = end_t - records[c][t].sample
+ * the backward recursion, mod 2^64,
+ *     pos_n = chans[c].ca_pos
+ *     pos_t = pos_{t+1} + (1023 << 32) - n_t * ca_rate_t
+ * is the channel loop's own update (THE CHANNEL MODEL: ca_pos += n * ca_rate - 1023 * 2^32) run in reverse, exact in integers:
+ * pos_t is the prompt code position at records[c][t].sample.  first_epoch = chans[c].epoch - n is the epoch number of record 0.
+ *
+ * OBSERVATION of channel c at receive sample R (an absolute sample index).  With t such that records[c][t].sample <= R < end_t:
+ *     P       = pos_t + (R - sample_t) * ca_rate_t          ( < 1023 * 2^32 by the channel model's n = ceil(...) )
+ *     tx_ms   = (tag.ms + (first_epoch + t - tag.epoch)) mod 604800000      (non-negative; the difference may be negative)
+ *     tx_frac = (double)P / 4393751543808000.0
+ *     eph = tag.eph, valid = 1, weight = 1.0, reserved = 0
+ * The divisor is 1023 * 2^32 * 1000, a double without rounding, and P < 2^42 is one too: tx_frac is ONE IEEE division, in
+ * [0, 1e-3).  (No fast-math flag in the build.)  An observation that cannot be made is 32 zero bytes: tag.valid == 0, n == 0, R
+ * before record 0's sample, R at or past next_sample.  A LOST channel stays usable up to its last epoch.
+ *
+ * RECEIVE INSTANTS are an arithmetic sequence R_i = first_rx_sample + i * rx_step, i < n_fix, rx_step >= 1 (the last one must
+ * fit 64 bits).  Row i of the output is obs[i][0..n_chans-1], channel c in column c: the [n_fix][sats_per_fix] layout of
+ * gpsacq_fix_batch with sats_per_fix = n_chans, 1 <= n_chans <= GPSACQ_FIX_MAX_SATS.
+ *
+ * gpsacq_observables: records[n_chans][max_epochs] (row stride max_epochs, as gpsacq_track writes them), n_epochs[n_chans],
+ * chans[n_chans], tags[n_chans], obs[n_fix][n_chans]; host pointers, returns after completion.  gpsacq_observables_device: records
+ * and obs are device pointers (the records straight from gpsacq_track_device / gpsacq_track_iq8_device: 1-bit and multi-bit
+ * channels write the same layout); n_epochs, chans and tags stay host pointers; work on the engine's stream, sync != 0 waits.
+ * gpsacq_fix_track_device: the same followed by gpsacq_fix_batch_device on the same stream, no host copy in between; d_obs may
+ * be NULL (engine scratch), d_fix[n_fix].  Argument errors -- a NULL pointer, n_chans outside 1..GPSACQ_FIX_MAX_SATS, rx_step == 0,
+ * n_fix == 0, n_epochs[c] < 0 or > max_epochs, instants past 2^64 -- return GPSACQ_ERR_ARG, launch nothing and write nothing.
+ * Two kernels: k_code_pos, one wave64 per channel, the suffix sum as a scan (pos[n_chans][max_epochs] in engine scratch);
+ * k_observe, one lane per (instant, channel).
+ */
+typedef struct { int32_t epoch; int32_t ms; int32_t eph; int32_t valid; } gpsacq_time_tag;   /* 16 bytes */
+GPSACQ_API int gpsacq_time_tag_from_subframe(const gpsacq_subframe* sf, int bit_epoch0, int eph_index, gpsacq_time_tag* tag);
+GPSACQ_API int gpsacq_observables(gpsacq_engine* e, const gpsacq_track_record* records, int max_epochs, const int32_t* n_epochs,
+                                  const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans,
+                                  uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, gpsacq_obs* obs);
+GPSACQ_API int gpsacq_observables_device(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs,
+                                         const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans,
+                                         uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, void* d_obs, int sync);
+GPSACQ_API int gpsacq_fix_track_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_records, int max_epochs,
+                                       const int32_t* n_epochs, const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans,
+                                       uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, void* d_obs, void* d_fix, int sync);
+/* device time of the two kernels of the last gpsacq_observables* / gpsacq_fix_track_device call on this engine, milliseconds (HIP
+ * events on its stream; waits for them).  Either pointer may be NULL. */
+GPSACQ_API int gpsacq_observables_last_ms(const gpsacq_engine* e, float* code_pos_ms, float* observe_ms);
 
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);

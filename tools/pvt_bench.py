@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Capture-to-position benchmark: a synthetic 1-bit capture of five satellites with real navigation data (the constellation of
+the tests, tests/nav_ref.py; device generator), searched, tracked, decoded on the host (NAV bits, subframes, ephemerides, time
+tags), and then gpsacq_fix_track_device at every millisecond of the capture at which every channel has records -- records,
+observations and fixes resident in device memory.  Prints one JSON line: the device time of the two observables kernels and of
+the solver's two (HIP events on the engine's stream, best of --reps calls), fixes per second over the four, and the position
+error against the generator's truth.
+
+The generator runs every satellite at the Doppler it has at sample 19.5 s x fs, where its transmit times are the truth maker's;
+away from that instant the truth is off by the range acceleration (metres over the capture), so the error is given at that
+instant, and as median and maximum over the instants after the loops' first two seconds.
+
+    python tools/pvt_bench.py [--seconds 20] [--reps 5]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gnss-gps-sdr_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+FS, FC, SPM, L1 = 5.456e6, 4.092e6, 5456, 1575.42e6
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seconds", type=float, default=20.0)
+    ap.add_argument("--reps", type=int, default=5)
+    a = ap.parse_args()
+    if a.seconds < 20.0:
+        ap.error("subframes 1-3 are complete 19 s into the capture: --seconds must be at least 20")
+
+    import numpy as np
+    import torch
+
+    import gpsacq
+    import nav_ref
+    from nav_helpers import geometry
+
+    geo = geometry("north")
+    ephs = [geo["ephs"][k] for k in geo["subsets"][5]]
+    n_bytes = int(a.seconds * FS) // 8
+    r_star = int(19.5 * FS)
+    tow0 = 64898
+    bit0_ms = (tow0 - 1) * 6000
+    ref_ms, ref_frac = bit0_ms + 18_275, 0.3217e-3  # the receive time at r_star: bit 0 lies 1.3 s into the capture, past the 1000 epochs bit sync skips on a channel started from block 8
+    sats, nav = [], []
+    for j, eph in enumerate(ephs):
+        t = nav_ref.truth_tx(eph, geo["rx"], ref_ms, np.array([ref_frac - 0.5, ref_frac, ref_frac + 0.5]))
+        dop = L1 * ((t[2] - t[0]) - 1.0)
+        cp = ((ref_ms - bit0_ms) + t[1] * 1e3) * FS / (1000.0 * (1.0 + dop / L1)) - r_star
+        sats.append((int(eph["prn"]), 0.15 + 0.0125 * j, float(dop), float(cp), 0.1 + 0.17 * j))
+        nav.append(1 - 2 * nav_ref.encode_stream(eph, tow0, ids=(1, 2, 3, 4, 5)).astype(np.int8))
+    prns = [s[0] for s in sats]
+
+    with gpsacq.Engine(FC, FS, 5000.0, device=0) as eng:
+        d_bits = torch.zeros(n_bytes, dtype=torch.uint8, device="cuda:0")
+        d_peaks = torch.zeros(32 * gpsacq.PEAK_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        eng.generate_device(d_bits.data_ptr(), n_bytes, sats, noise_sigma=1.0, seed=77, nav=np.array(nav))
+        eng.search_device(d_bits.data_ptr(), 32, d_peaks.data_ptr())
+        peaks = d_peaks.cpu().numpy().view(gpsacq.PEAK_DTYPE)
+        chans = np.concatenate([eng.track_start(p, peaks[p - 1], (p - 1) * gpsacq.BLOCK_BYTES * 8) for p in prns])
+        max_epochs = int(a.seconds * 1000) + 100
+        d_prompt = torch.zeros(len(prns) * max_epochs * 2, dtype=torch.int32, device="cuda:0")
+        d_rec = torch.zeros(len(prns) * max_epochs * gpsacq.TRACK_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        ne = eng.track_device(d_bits.data_ptr(), n_bytes, chans, 0, max_epochs, d_prompt.data_ptr(), d_rec.data_ptr())
+        prompt = d_prompt.cpu().numpy().reshape(len(prns), max_epochs, 2)
+        tags, recs = [], []
+        for c, prn in enumerate(prns):
+            n = int(ne[c])
+            bits, e0 = gpsacq.nav_bits(prompt[c, 1000:n, 0], first_epoch=int(chans["epoch"][c]) - n + 1000)
+            sf, _ = gpsacq.nav_subframes(bits)
+            if not len(sf):
+                raise SystemExit("PRN %d: no subframe decoded" % prn)
+            recs.append(gpsacq.ephemeris(sf, prn))
+            tags.append(gpsacq.time_tag(sf[0], e0, c))
+        tags, recs = np.concatenate(tags), np.concatenate(recs)
+        # every millisecond (on r_star's grid) at which every channel has records
+        records0 = d_rec.cpu().numpy().view(gpsacq.TRACK_RECORD_DTYPE).reshape(len(prns), max_epochs)[:, 0]
+        lo, hi = int(records0["sample"].max()), int(chans["next_sample"].min())
+        first = r_star - (r_star - lo) // SPM * SPM
+        n_fix = (hi - 1 - first) // SPM + 1
+        d_fix = torch.zeros(n_fix * gpsacq.FIX_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        best = None
+        for _ in range(1 + a.reps):  # the first call also allocates the engine's scratch
+            eng.fix_track_device(recs, d_rec.data_ptr(), max_epochs, ne, chans, tags, first, SPM, n_fix, d_fix.data_ptr(), sync=True)
+            ms = eng.observables_last_ms() + eng.fix_last_ms()
+            if best is None or sum(ms) < sum(best):
+                best = ms
+        fix = d_fix.cpu().numpy().view(gpsacq.FIX_DTYPE)
+        name = eng.device_name
+    off = np.linalg.norm(np.stack([fix["x"], fix["y"], fix["z"]], 1) - geo["rx"], axis=1)
+    ok = fix["status"] == 0
+    row = (r_star - first) // SPM
+    late = ok & (np.arange(n_fix) * SPM + first >= 2 * FS)
+    print(json.dumps({"bench": "pvt", "device": name, "seconds": a.seconds, "sats": len(prns), "epochs": int(ne.min()), "n_fix": int(n_fix),
+                      "code_pos_ms": round(best[0], 4), "observe_ms": round(best[1], 4), "sat_state_ms": round(best[2], 4),
+                      "fix_ms": round(best[3], 4), "kernel_ms": round(sum(best), 4), "fixes_per_s": round(n_fix / (sum(best) * 1e-3)),
+                      "ok": int(ok.sum()), "valid_ephemerides": int(sum(gpsacq.ephemeris_valid(r) for r in recs)),
+                      "position_error_at_19p5s_m": round(float(off[row]), 2), "position_error_median_m": round(float(np.median(off[late])), 2),
+                      "position_error_max_m": round(float(off[late].max()), 2)}))
+
+
+if __name__ == "__main__":
+    main()
