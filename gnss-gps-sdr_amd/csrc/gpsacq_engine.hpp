@@ -110,6 +110,20 @@ struct gpsacq_engine {
     size_t obs_rec_cap = 0;
     hipEvent_t obs_ev[3] = {};  // before k_code_pos, between the kernels, after k_observe
     bool obs_timed = false;
+    // carrier observables and velocity (gpsacq_rate_observables*, gpsacq_vel_batch*, gpsacq_pvt_track_device)
+    acq::RateChan* d_rate_chan = nullptr;
+    size_t rate_chan_cap = 0;
+    int64_t* d_rate_acc = nullptr;  // k_carrier_acc's output, k_observe_rate's input: [n_chans][max_epochs + 1]
+    size_t rate_acc_cap = 0;
+    gpsacq_rate_obs* d_rate_obs = nullptr;  // host-buffer forms and gpsacq_pvt_track_device's scratch
+    size_t rate_obs_cap = 0;
+    gpsacq_sat_rate* d_sat_rate = nullptr;  // k_sat_state_rate's output
+    size_t sat_rate_cap = 0;
+    gpsacq_vel* d_vel = nullptr;
+    size_t vel_cap = 0;
+    hipEvent_t rate_ev[3] = {};  // before k_carrier_acc, between the kernels, after k_observe_rate
+    hipEvent_t vel_ev[3] = {};   // before k_sat_state_rate, between it and k_vel, after k_vel
+    bool rate_timed = false, vel_timed = false;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;

@@ -1,7 +1,8 @@
 // gpsacq_nav.cpp -- host side of "Navigation solver" of include/gpsacq.h.  First the ephemeris, host only: the fields of
 // subframes 1-3 by IS-GPS-200 Tables 20-I and 20-III, read from gpsacq_subframe.words[].  Then the gpsacq_sat_states* and
 // gpsacq_fix_batch* entry points that run nav_kernels.hip on the engine of gpsacq_engine.hpp.  Last "Observables": the time tag
-// (host only) and the gpsacq_observables* / gpsacq_fix_track_device entry points that run obs_kernels.hip.
+// (host only) and the gpsacq_observables* / gpsacq_fix_track_device entry points that run obs_kernels.hip, then "Carrier observables"
+// and "Velocity and clock drift": gpsacq_rate_observables*, gpsacq_sat_rates*, gpsacq_vel_batch*, gpsacq_pvt_track_device.
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -200,10 +201,10 @@ extern "C" int gpsacq_time_tag_from_subframe(const gpsacq_subframe* sf, int bit_
     return GPSACQ_OK;
 }
 
-static int obs_check(const char* who, const gpsacq_engine* e, const void* records, int max_epochs, const int32_t* n_epochs,
-                     const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans, uint64_t first_rx_sample, uint64_t rx_step,
-                     size_t n_fix) {
-    if (!e || !records || !n_epochs || !chans || !tags || max_epochs < 0 || n_fix == 0 || n_fix > ((size_t)1 << 31))
+// what the code and the carrier observables share: the records of one tracking call and the receive instants
+static int records_check(const char* who, const gpsacq_engine* e, const void* records, int max_epochs, const int32_t* n_epochs,
+                         const gpsacq_track_chan* chans, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix) {
+    if (!e || !records || !n_epochs || !chans || max_epochs < 0 || n_fix == 0 || n_fix > ((size_t)1 << 31))
         return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
     if (n_chans < 1 || n_chans > GPSACQ_FIX_MAX_SATS) return fail(GPSACQ_ERR_ARG, "%s: n_chans %d outside 1 .. %d", who, n_chans, GPSACQ_FIX_MAX_SATS);
     if (rx_step == 0) return fail(GPSACQ_ERR_ARG, "%s: rx_step must be at least 1", who);
@@ -213,6 +214,13 @@ static int obs_check(const char* who, const gpsacq_engine* e, const void* record
         if (n_epochs[c] < 0 || n_epochs[c] > max_epochs)
             return fail(GPSACQ_ERR_ARG, "%s: channel %d has %d epochs, max_epochs is %d", who, c, n_epochs[c], max_epochs);
     return GPSACQ_OK;
+}
+
+static int obs_check(const char* who, const gpsacq_engine* e, const void* records, int max_epochs, const int32_t* n_epochs,
+                     const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans, uint64_t first_rx_sample, uint64_t rx_step,
+                     size_t n_fix) {
+    if (!tags) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    return records_check(who, e, records, max_epochs, n_epochs, chans, n_chans, first_rx_sample, rx_step, n_fix);
 }
 
 // both kernels on the engine's stream; every argument has been checked
@@ -295,5 +303,207 @@ extern "C" int gpsacq_observables_last_ms(const gpsacq_engine* e, float* code_po
     HIPCHK(hipEventSynchronize(e->obs_ev[2]));
     if (code_pos_ms) HIPCHK(hipEventElapsedTime(code_pos_ms, e->obs_ev[0], e->obs_ev[1]));
     if (observe_ms) HIPCHK(hipEventElapsedTime(observe_ms, e->obs_ev[1], e->obs_ev[2]));
+    return GPSACQ_OK;
+}
+
+// ---- carrier observables (obs_kernels.hip) ---------------------------------------------------------------------------------
+static int rate_check(const char* who, const gpsacq_engine* e, const void* records, int max_epochs, const int32_t* n_epochs,
+                      const gpsacq_track_chan* chans, const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample, uint64_t rx_step,
+                      size_t n_fix, uint64_t avg_samples) {
+    if (!nom_words) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (int rc = records_check(who, e, records, max_epochs, n_epochs, chans, n_chans, first_rx_sample, rx_step, n_fix)) return rc;
+    if (avg_samples == 0) return fail(GPSACQ_ERR_ARG, "%s: avg_samples must be at least 1", who);
+    return GPSACQ_OK;
+}
+
+// both kernels on the engine's stream; every argument has been checked
+static int rate_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
+                        const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, uint64_t avg_samples,
+                        void* d_rate_obs) {
+    RateChan tab[GPSACQ_FIX_MAX_SATS];
+    for (int c = 0; c < n_chans; ++c) tab[c] = RateChan{chans[c].next_sample, n_epochs[c], nom_words[c]};
+    if (int rc = grow(e->d_rate_chan, e->rate_chan_cap, (size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
+    if (int rc = grow(e->d_rate_acc, e->rate_acc_cap, (size_t)n_chans * ((size_t)max_epochs + 1), e->stream)) return rc;
+    // pageable source: the copy has left `tab` when the call returns
+    HIPCHK(hipMemcpyAsync(e->d_rate_chan, tab, (size_t)n_chans * sizeof(RateChan), hipMemcpyHostToDevice, e->stream));
+    for (auto& ev : e->rate_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    e->rate_timed = false;
+    HIPCHK(hipEventRecord(e->rate_ev[0], e->stream));
+    launch_carrier_acc(CarrierAccArgs{e->d_rate_chan, (const gpsacq_track_record*)d_records, max_epochs, e->d_rate_acc}, n_chans, e->stream);
+    HIPCHK(hipEventRecord(e->rate_ev[1], e->stream));
+    launch_observe_rate(ObserveRateArgs{e->d_rate_chan, (const gpsacq_track_record*)d_records, e->d_rate_acc, max_epochs, n_chans, first_rx_sample,
+                                        rx_step, avg_samples, e->p.fs, n_fix, (gpsacq_rate_obs*)d_rate_obs},
+                        e->stream);
+    HIPCHK(hipEventRecord(e->rate_ev[2], e->stream));
+    HIPCHK(hipGetLastError());
+    e->rate_timed = true;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_rate_observables_device(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs,
+                                              const gpsacq_track_chan* chans, const uint32_t* nom_words, int n_chans,
+                                              uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, uint64_t avg_samples,
+                                              void* d_rate_obs, int sync) {
+    if (int rc = rate_check("gpsacq_rate_observables", e, d_records, max_epochs, n_epochs, chans, nom_words, n_chans, first_rx_sample, rx_step, n_fix, avg_samples)) return rc;
+    if (!d_rate_obs) return fail(GPSACQ_ERR_ARG, "gpsacq_rate_observables: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = rate_enqueue(e, d_records, max_epochs, n_epochs, chans, nom_words, n_chans, first_rx_sample, rx_step, n_fix, avg_samples, d_rate_obs)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_rate_observables(gpsacq_engine* e, const gpsacq_track_record* records, int max_epochs, const int32_t* n_epochs,
+                                       const gpsacq_track_chan* chans, const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample,
+                                       uint64_t rx_step, size_t n_fix, uint64_t avg_samples, gpsacq_rate_obs* rate_obs) {
+    if (int rc = rate_check("gpsacq_rate_observables", e, records, max_epochs, n_epochs, chans, nom_words, n_chans, first_rx_sample, rx_step, n_fix, avg_samples)) return rc;
+    if (!rate_obs) return fail(GPSACQ_ERR_ARG, "gpsacq_rate_observables: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_obs = n_fix * (size_t)n_chans;
+    if (int rc = grow(e->d_obs_rec, e->obs_rec_cap, (size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
+    if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_obs, e->stream)) return rc;
+    for (int c = 0; c < n_chans; ++c)  // the rows keep their stride; only the records that exist travel
+        if (n_epochs[c] > 0)
+            HIPCHK(hipMemcpyAsync(e->d_obs_rec + (size_t)c * max_epochs, records + (size_t)c * max_epochs,
+                                  (size_t)n_epochs[c] * sizeof(gpsacq_track_record), hipMemcpyHostToDevice, e->stream));
+    if (int rc = rate_enqueue(e, e->d_obs_rec, max_epochs, n_epochs, chans, nom_words, n_chans, first_rx_sample, rx_step, n_fix, avg_samples, e->d_rate_obs)) return rc;
+    HIPCHK(hipMemcpyAsync(rate_obs, e->d_rate_obs, n_obs * sizeof(gpsacq_rate_obs), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+// ---- velocity and clock drift (nav_kernels.hip) ----------------------------------------------------------------------------
+extern "C" int gpsacq_sat_rates_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, size_t n_obs,
+                                       void* d_out, int sync) {
+    if (int rc = nav_check("gpsacq_sat_rates", e, eph, n_eph, d_obs, n_obs, d_out)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    launch_sat_state_rate(SatRateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, (gpsacq_sat_rate*)d_out}, e->stream);
+    HIPCHK(hipGetLastError());
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_sat_rates(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs, size_t n_obs,
+                                gpsacq_sat_rate* out) {
+    if (int rc = nav_check("gpsacq_sat_rates", e, eph, n_eph, obs, n_obs, out)) return rc;
+    if (int rc = nav_check_weights("gpsacq_sat_rates", obs, n_obs)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_sat_rate, e->sat_rate_cap, n_obs, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    if (int rc = gpsacq_sat_rates_device(e, eph, n_eph, e->d_nav_obs, n_obs, e->d_sat_rate, 0)) return rc;
+    HIPCHK(hipMemcpyAsync(out, e->d_sat_rate, n_obs * sizeof(gpsacq_sat_rate), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+static int vel_check(const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* obs, const void* rate_obs, const void* fixes,
+                     size_t n_fix, int sats_per_fix, const void* out) {
+    if (int rc = nav_check("gpsacq_vel_batch", e, eph, n_eph, obs, n_fix, out)) return rc;
+    if (!rate_obs || !fixes) return fail(GPSACQ_ERR_ARG, "gpsacq_vel_batch: bad argument");
+    if (sats_per_fix < 1 || sats_per_fix > GPSACQ_FIX_MAX_SATS)
+        return fail(GPSACQ_ERR_ARG, "gpsacq_vel_batch: sats_per_fix %d outside 1 .. %d", sats_per_fix, GPSACQ_FIX_MAX_SATS);
+    return GPSACQ_OK;
+}
+
+// k_sat_state_rate and k_vel on the engine's stream; e->d_nav_eph holds the call's ephemerides and e->d_nav_state the satellite
+// states of d_obs (enqueued before), every argument has been checked
+static int vel_enqueue(gpsacq_engine* e, int n_eph, const void* d_obs, const void* d_rate_obs, const void* d_fixes, size_t n_fix,
+                       int sats_per_fix, void* d_out) {
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    if (int rc = grow(e->d_sat_rate, e->sat_rate_cap, n_obs, e->stream)) return rc;
+    for (auto& ev : e->vel_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    e->vel_timed = false;
+    HIPCHK(hipEventRecord(e->vel_ev[0], e->stream));
+    launch_sat_state_rate(SatRateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_sat_rate}, e->stream);
+    HIPCHK(hipEventRecord(e->vel_ev[1], e->stream));
+    launch_vel(VelArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, (const gpsacq_rate_obs*)d_rate_obs, e->d_nav_state, e->d_sat_rate,
+                       (const gpsacq_fix*)d_fixes, n_fix, sats_per_fix, (gpsacq_vel*)d_out},
+               e->stream);
+    HIPCHK(hipEventRecord(e->vel_ev[2], e->stream));
+    HIPCHK(hipGetLastError());
+    e->vel_timed = true;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_vel_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_rate_obs,
+                                       const void* d_fixes, size_t n_fix, int sats_per_fix, void* d_out, int sync) {
+    if (int rc = vel_check(e, eph, n_eph, d_obs, d_rate_obs, d_fixes, n_fix, sats_per_fix, d_out)) return rc;
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
+    launch_sat_state(SatStateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_nav_state}, e->stream);
+    if (int rc = vel_enqueue(e, n_eph, d_obs, d_rate_obs, d_fixes, n_fix, sats_per_fix, d_out)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_vel_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs,
+                                const gpsacq_rate_obs* rate_obs, const gpsacq_fix* fixes, size_t n_fix, int sats_per_fix, gpsacq_vel* out) {
+    if (int rc = vel_check(e, eph, n_eph, obs, rate_obs, fixes, n_fix, sats_per_fix, out)) return rc;
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    if (int rc = nav_check_weights("gpsacq_vel_batch", obs, n_obs)) return rc;
+    for (size_t k = 0; k < n_obs; ++k)
+        if (!(rate_obs[k].weight >= 0.0) || !std::isfinite(rate_obs[k].weight))
+            return fail(GPSACQ_ERR_ARG, "gpsacq_vel_batch: rate observation %zu has weight %g (must be finite and >= 0)", k, rate_obs[k].weight);
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
+    if (int rc = grow(e->d_vel, e->vel_cap, n_fix, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_rate_obs, rate_obs, n_obs * sizeof(gpsacq_rate_obs), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_nav_fix, fixes, n_fix * sizeof(gpsacq_fix), hipMemcpyHostToDevice, e->stream));
+    if (int rc = gpsacq_vel_batch_device(e, eph, n_eph, e->d_nav_obs, e->d_rate_obs, e->d_nav_fix, n_fix, sats_per_fix, e->d_vel, 0)) return rc;
+    HIPCHK(hipMemcpyAsync(out, e->d_vel, n_fix * sizeof(gpsacq_vel), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_pvt_track_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_records, int max_epochs,
+                                       const int32_t* n_epochs, const gpsacq_track_chan* chans, const gpsacq_time_tag* tags,
+                                       const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix,
+                                       uint64_t avg_samples, void* d_obs, void* d_rate_obs, void* d_fix, void* d_vel, int sync) {
+    if (int rc = rate_check("gpsacq_pvt_track", e, d_records, max_epochs, n_epochs, chans, nom_words, n_chans, first_rx_sample, rx_step, n_fix, avg_samples)) return rc;
+    if (!tags || !eph || n_eph <= 0 || !d_fix || !d_vel) return fail(GPSACQ_ERR_ARG, "gpsacq_pvt_track: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (!d_obs) {
+        if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_fix * (size_t)n_chans, e->stream)) return rc;
+        d_obs = e->d_nav_obs;
+    }
+    if (!d_rate_obs) {
+        if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_fix * (size_t)n_chans, e->stream)) return rc;
+        d_rate_obs = e->d_rate_obs;
+    }
+    if (int rc = obs_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, d_obs)) return rc;
+    if (int rc = rate_enqueue(e, d_records, max_epochs, n_epochs, chans, nom_words, n_chans, first_rx_sample, rx_step, n_fix, avg_samples, d_rate_obs)) return rc;
+    if (int rc = gpsacq_fix_batch_device(e, eph, n_eph, d_obs, n_fix, n_chans, d_fix, 0)) return rc;
+    // the ephemerides and the satellite states of d_obs are on the device from the fixes: only the rates and the solve remain
+    if (int rc = vel_enqueue(e, n_eph, d_obs, d_rate_obs, d_fix, n_fix, n_chans, d_vel)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_velocity_last_ms(const gpsacq_engine* e, float* carrier_acc_ms, float* observe_rate_ms, float* sat_rate_ms, float* vel_ms) {
+    if (!e || (!e->rate_timed && !e->vel_timed)) return fail(GPSACQ_ERR_ARG, "gpsacq_velocity_last_ms: no rate or velocity call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    float t[4] = {0.f, 0.f, 0.f, 0.f};
+    if (e->rate_timed) {
+        HIPCHK(hipEventSynchronize(e->rate_ev[2]));
+        HIPCHK(hipEventElapsedTime(&t[0], e->rate_ev[0], e->rate_ev[1]));
+        HIPCHK(hipEventElapsedTime(&t[1], e->rate_ev[1], e->rate_ev[2]));
+    }
+    if (e->vel_timed) {
+        HIPCHK(hipEventSynchronize(e->vel_ev[2]));
+        HIPCHK(hipEventElapsedTime(&t[2], e->vel_ev[0], e->vel_ev[1]));
+        HIPCHK(hipEventElapsedTime(&t[3], e->vel_ev[1], e->vel_ev[2]));
+    }
+    if (carrier_acc_ms) *carrier_acc_ms = t[0];
+    if (observe_rate_ms) *observe_rate_ms = t[1];
+    if (sat_rate_ms) *sat_rate_ms = t[2];
+    if (vel_ms) *vel_ms = t[3];
     return GPSACQ_OK;
 }

@@ -250,6 +250,22 @@ extern "C" int gpsacq_track_start_iq8(const gpsacq_engine* e, const gpsacq_iq8_i
     return GPSACQ_OK;
 }
 
+extern "C" int gpsacq_track_nominal_word_iq8(const gpsacq_engine* e, const gpsacq_iq8_input* in, uint32_t* word) {
+    if (!e || !in || !word) return fail(GPSACQ_ERR_ARG, "gpsacq_track_nominal_word_iq8: null argument");
+    Capture cap;
+    if (int rc = iq8_capture(e, in, nullptr, 0, &cap)) return rc;
+    if (in->multibit == GPSACQ_SAMPLES_SIGN) {  // gpsacq_track_start's lo_nom >> 32; cycles per sample mod 1, so that the cast is defined at fc >= fs
+        const double cycles = e->p.fc / e->p.fs;
+        *word = (uint32_t)((cycles - std::floor(cycles)) * 4294967296.0);
+        return GPSACQ_OK;
+    }
+    // gpsacq_track_start_iq8's carrier at zero Doppler, folded into [-fs / 2, fs / 2)
+    double f = -in->mix_hz + (in->multibit == GPSACQ_SAMPLES_COMPLEX ? 0.0 : e->p.fc);
+    f -= e->p.fs * std::floor(f / e->p.fs + 0.5);
+    *word = (uint32_t)(int64_t)std::llround(f / e->p.fs * 4294967296.0);
+    return GPSACQ_OK;
+}
+
 extern "C" int gpsacq_track_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, uint64_t first_sample,
                                        gpsacq_track_chan* chans, int n_chans, const gpsacq_track_params* params, void* d_prompt,
                                        void* d_records, int max_epochs, int32_t* n_epochs_out) {

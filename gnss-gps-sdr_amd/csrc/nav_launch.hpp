@@ -1,5 +1,6 @@
 // nav_launch.hpp -- argument blocks and launchers of the navigation solver of include/gpsacq.h ("Navigation solver"):
-// nav_kernels.hip's k_sat_state (one lane per observation) and k_fix (one lane per fix).
+// nav_kernels.hip's k_sat_state (one lane per observation) and k_fix (one lane per fix), and of "Velocity and clock drift":
+// k_sat_state_rate (one lane per observation) and k_vel (one lane per fix).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -40,5 +41,28 @@ struct FixArgs {
     gpsacq_fix* out;  // [n_fix] (device)
 };
 void launch_fix(const FixArgs& a, hipStream_t s);
+
+struct SatRateArgs {
+    const NavEph* eph;  // [n_eph] (device)
+    int n_eph;
+    const gpsacq_obs* obs;  // [n_obs] (device)
+    size_t n_obs;
+    gpsacq_sat_rate* out;  // [n_obs] (device)
+};
+void launch_sat_state_rate(const SatRateArgs& a, hipStream_t s);
+
+struct VelArgs {
+    const NavEph* eph;
+    int n_eph;
+    const gpsacq_obs* obs;            // [n_fix][sats] (device)
+    const gpsacq_rate_obs* rate_obs;  // [n_fix][sats]
+    const gpsacq_sat_state* state;    // [n_fix][sats], k_sat_state's output for obs
+    const gpsacq_sat_rate* rate;      // [n_fix][sats], k_sat_state_rate's output for obs
+    const gpsacq_fix* fix;            // [n_fix]
+    size_t n_fix;
+    int sats;  // 1 .. GPSACQ_FIX_MAX_SATS
+    gpsacq_vel* out;  // [n_fix] (device)
+};
+void launch_vel(const VelArgs& a, hipStream_t s);
 
 }  // namespace acq

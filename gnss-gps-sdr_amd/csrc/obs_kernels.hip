@@ -8,6 +8,12 @@
 // carry, so they overlap the scan of the pass before.  k_observe: one lane per (instant, channel); the epoch that holds the
 // instant is found by bisection over the records' `sample` fields (at most 31 steps, the lanes of a wave are neighbouring instants
 // of one channel and walk the same path).  No LDS, no barrier, no atomics; every loop is bounded.
+//
+// "Carrier observables" of the same header: k_carrier_acc is k_code_pos turned round -- a forward prefix sum A_{t+1} = A_t + n_t d_t
+// of the Doppler part of the carrier NCO word, the same chunks of 64 x OBS_RUN epochs, the scan with __shfl_up, the carry running
+// forward.  n_t d_t is a full 64 x 64 -> 64-bit product (a few v_mad_u64_u32 / v_mul_lo_u32; four per lane and pass, next to
+// eight 40-byte-strided loads it does not show).  k_observe_rate: one lane per (instant, channel), three bisections (R_a, R,
+// R_b); the Doppler is one fp64 product and one fp64 quotient in separate statements, nothing for the compiler to contract.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -86,6 +92,96 @@ __global__ __launch_bounds__(OBS_BLOCK) void k_observe(ObserveArgs a) {
         o.weight = 1.0;
     }
     a.out[i * (size_t)a.n_chans + c] = o;
+}
+
+__global__ __launch_bounds__(OBS_BLOCK) void k_carrier_acc(CarrierAccArgs a) {
+    const int c = blockIdx.x;
+    const int lane = threadIdx.x;
+    const RateChan ch = a.chan[c];
+    const int n = ch.n;
+    const gpsacq_track_record* rec = a.records + (size_t)c * (size_t)a.max_epochs;
+    int64_t* acc = a.acc + (size_t)c * ((size_t)a.max_epochs + 1);
+    constexpr int CHUNK = OBS_BLOCK * OBS_RUN;
+    if (lane == 0) acc[0] = 0;
+    uint64_t carry = 0;  // A at the first epoch of the chunk, mod 2^64
+    for (int base = 0; base < n; base += CHUNK) {
+        const int t0 = base + lane * OBS_RUN;
+        uint64_t smp[OBS_RUN + 1];
+#pragma unroll
+        for (int j = 0; j <= OBS_RUN; ++j) smp[j] = t0 + j < n ? rec[t0 + j].sample : ch.next_sample;
+        // inclusive prefix sums inside this lane's run
+        uint64_t pre[OBS_RUN];
+        uint64_t run = 0;
+#pragma unroll
+        for (int j = 0; j < OBS_RUN; ++j) {
+            if (t0 + j < n) {
+                const uint64_t d = (uint64_t)(int64_t)(int32_t)(rec[t0 + j].lo_rate - ch.nom_word);
+                run += (smp[j + 1] - smp[j]) * d;
+            }
+            pre[j] = run;
+        }
+        // inclusive prefix scan of the run totals over the wave
+        uint64_t incl = run;
+#pragma unroll
+        for (int off = 1; off < OBS_BLOCK; off <<= 1) {
+            const uint64_t v = __shfl_up((unsigned long long)incl, off, OBS_BLOCK);
+            if (lane >= off) incl += v;
+        }
+        const uint64_t left = carry + (incl - run);  // everything before this lane's run
+#pragma unroll
+        for (int j = 0; j < OBS_RUN; ++j)
+            if (t0 + j < n) acc[t0 + j + 1] = (int64_t)(left + pre[j]);
+        carry += __shfl((unsigned long long)incl, OBS_BLOCK - 1, OBS_BLOCK);
+    }
+}
+
+namespace {
+// A(X) of the model for rec[0].sample <= X < next_sample: the last record whose sample is <= X, then the interpolation
+__device__ __forceinline__ uint64_t acc_at(const gpsacq_track_record* rec, const int64_t* acc, int n, uint32_t nom_word, uint64_t X) {
+    int lo = 0, hi = n;
+    for (int k = 0; k < 32 && hi - lo > 1; ++k) {
+        const int mid = lo + (hi - lo) / 2;
+        if (rec[mid].sample <= X) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t d = (uint64_t)(int64_t)(int32_t)(rec[lo].lo_rate - nom_word);
+    return (uint64_t)acc[lo] + (X - rec[lo].sample) * d;
+}
+}  // namespace
+
+__global__ __launch_bounds__(OBS_BLOCK) void k_observe_rate(ObserveRateArgs a) {
+    const size_t i = (size_t)blockIdx.x * OBS_BLOCK + threadIdx.x;
+    const int c = blockIdx.y;
+    if (i >= a.n_fix) return;
+    const RateChan ch = a.chan[c];
+    const uint64_t R = a.first_rx_sample + (uint64_t)i * a.rx_step;
+    const uint64_t W = a.avg_samples, half = W / 2;
+    const gpsacq_track_record* rec = a.records + (size_t)c * (size_t)a.max_epochs;
+    const int64_t* acc = a.acc + (size_t)c * ((size_t)a.max_epochs + 1);
+    gpsacq_rate_obs o;
+    o.valid = o.reserved = 0;
+    o.adr = 0;
+    o.doppler_hz = o.weight = 0.0;
+    // R_a <= R <= R_b: R_a at or past record 0 and R_b before next_sample put all three inside the records
+    if (ch.n > 0 && R >= half && R - half >= rec[0].sample && R - half < ch.next_sample && W < ch.next_sample - (R - half)) {
+        const uint64_t Ra = R - half, Rb = Ra + W;
+        const int64_t D = (int64_t)(acc_at(rec, acc, ch.n, ch.nom_word, Rb) - acc_at(rec, acc, ch.n, ch.nom_word, Ra));
+        const double num = __dmul_rn((double)D, a.fs);
+        const double den = __dmul_rn((double)W, 4294967296.0);
+        o.valid = 1;
+        o.adr = (int64_t)acc_at(rec, acc, ch.n, ch.nom_word, R);
+        o.doppler_hz = __ddiv_rn(num, den);
+        o.weight = 1.0;
+    }
+    a.out[i * (size_t)a.n_chans + c] = o;
+}
+
+void launch_carrier_acc(const CarrierAccArgs& a, int n_chans, hipStream_t s) {
+    hipLaunchKernelGGL(k_carrier_acc, dim3((unsigned)n_chans), dim3(OBS_BLOCK), 0, s, a);
+}
+
+void launch_observe_rate(const ObserveRateArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_observe_rate, dim3((unsigned)((a.n_fix + OBS_BLOCK - 1) / OBS_BLOCK), (unsigned)a.n_chans), dim3(OBS_BLOCK), 0, s, a);
 }
 
 void launch_code_pos(const CodePosArgs& a, int n_chans, hipStream_t s) {

@@ -1,5 +1,6 @@
 // obs_launch.hpp -- argument blocks and launchers of the observables of include/gpsacq.h ("Observables"): obs_kernels.hip's
-// k_code_pos (one wave64 per channel) and k_observe (one lane per (instant, channel)).
+// k_code_pos (one wave64 per channel) and k_observe (one lane per (instant, channel)), and of "Carrier observables":
+// k_carrier_acc (one wave64 per channel) and k_observe_rate (one lane per (instant, channel)).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -40,5 +41,33 @@ struct ObserveArgs {
     gpsacq_obs* out;  // [n_fix][n_chans] (device)
 };
 void launch_observe(const ObserveArgs& a, hipStream_t s);
+
+// what the carrier kernels read of one channel
+struct RateChan {
+    uint64_t next_sample;  // end of the last record
+    int32_t n;             // records of this channel, 0 .. max_epochs
+    uint32_t nom_word;     // carrier NCO word of zero Doppler
+};  // 16 bytes
+
+struct CarrierAccArgs {
+    const RateChan* chan;                // [n_chans] (device)
+    const gpsacq_track_record* records;  // [n_chans][max_epochs] (device)
+    int max_epochs;
+    int64_t* acc;  // [n_chans][max_epochs + 1] (device): A_t of the model, written for t <= n
+};
+void launch_carrier_acc(const CarrierAccArgs& a, int n_chans, hipStream_t s);
+
+struct ObserveRateArgs {
+    const RateChan* chan;
+    const gpsacq_track_record* records;
+    const int64_t* acc;
+    int max_epochs;
+    int n_chans;  // 1 .. GPSACQ_FIX_MAX_SATS
+    uint64_t first_rx_sample, rx_step, avg_samples;
+    double fs;
+    size_t n_fix;
+    gpsacq_rate_obs* out;  // [n_fix][n_chans] (device)
+};
+void launch_observe_rate(const ObserveRateArgs& a, hipStream_t s);
 
 }  // namespace acq

@@ -11,6 +11,9 @@
 // and, when at least four channels have a valid ephemeris (subframes 1-3) and a time tag, one position fix per second of capture
 // (gpsacq_observables + gpsacq_fix_batch), from the first whole second at which every such channel has records to the last:
 //     fix tow T lat LAT lon LON alt ALT n_used N rms R          (T seconds of week, degrees, metres)
+// With GPSACQ_VELOCITY=1 in the environment every fix whose velocity could be solved (gpsacq_rate_observables over half a second of
+// samples centred on the instant + gpsacq_vel_batch) is followed by a second line; without it the output is unchanged:
+//     vel tow T ve E vn N vu U drift D n_used N rms R           (m/s east, north, up; drift of the sampling clock, parts in 1)
 //
 // With GPSACQ_INPUT=iq_u8|iq_s8 in the environment FILE is an 8-bit IQ capture (rtl-sdr / HackRF, README.md:83-115), read the way
 // gps_test reads it (host/search_api.cpp: GPSACQ_MIX_HZ, GPSACQ_IQ_KEEP_DC, GPSACQ_IQ_MULTIBIT, GPSACQ_IQ_COMPLEX; the mean of the
@@ -207,11 +210,35 @@ int main(int argc, char** argv) {
                 gpsacq_destroy(e);
                 return rc;
             }
+            const bool want_vel = env_int("GPSACQ_VELOCITY", 0) != 0;
+            std::vector<gpsacq_vel> vel;
+            if (want_vel) {
+                // the word of zero Doppler: what lo_nom holds, except for multi-bit channels, which keep their start word there
+                std::vector<uint32_t> nom(m);
+                uint32_t iq_word = 0;
+                if (iq && iqin.multibit) rc = gpsacq_track_nominal_word_iq8(e, &iqin, &iq_word);
+                for (size_t k = 0; k < m; ++k) nom[k] = iq && iqin.multibit ? iq_word : (uint32_t)((uint64_t)fch[k].lo_nom >> 32);
+                std::vector<gpsacq_rate_obs> robs(n_fix * m);
+                vel.resize(n_fix);
+                if (rc == 0)
+                    rc = gpsacq_rate_observables(e, rec.data(), max_epochs, fn.data(), fch.data(), nom.data(), (int)m, first_rx, step, n_fix,
+                                                 step / 2 > 0 ? step / 2 : 1, robs.data());
+                if (rc == 0) rc = gpsacq_vel_batch(e, ephs.data(), (int)ephs.size(), obs.data(), robs.data(), fix.data(), n_fix, (int)m, vel.data());
+                if (rc) {
+                    std::fprintf(stderr, "gps_track: %d: %s\n", rc, gpsacq_last_error());
+                    gpsacq_destroy(e);
+                    return rc;
+                }
+            }
             const double deg = 180.0 / 3.14159265358979323846;
             for (size_t k = 0; k < n_fix; ++k)
-                if (fix[k].status == GPSACQ_FIX_OK)
+                if (fix[k].status == GPSACQ_FIX_OK) {
                     std::printf("fix tow %.6f lat %.7f lon %.7f alt %.2f n_used %d rms %.2f\n", fix[k].rx_ms * 1e-3 + fix[k].rx_frac,
                                 fix[k].lat * deg, fix[k].lon * deg, fix[k].alt, fix[k].n_used, fix[k].rms);
+                    if (want_vel && vel[k].status == GPSACQ_VEL_OK)
+                        std::printf("vel tow %.6f ve %.3f vn %.3f vu %.3f drift %.4e n_used %d rms %.3f\n", fix[k].rx_ms * 1e-3 + fix[k].rx_frac,
+                                    vel[k].ve, vel[k].vn, vel[k].vu, vel[k].drift, vel[k].n_used, vel[k].rms);
+                }
         }
     }
     gpsacq_destroy(e);

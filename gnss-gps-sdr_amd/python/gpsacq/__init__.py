@@ -87,6 +87,12 @@ FIX_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("iterations", "<i4"
                       ("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("lat", "<f8"), ("lon", "<f8"), ("alt", "<f8"), ("rms", "<f8")])
 # observables (include/gpsacq.h, "Observables")
 TIME_TAG_DTYPE = np.dtype([("epoch", "<i4"), ("ms", "<i4"), ("eph", "<i4"), ("valid", "<i4")])
+# carrier observables and velocity (include/gpsacq.h, "Carrier observables", "Velocity and clock drift")
+RATE_OBS_DTYPE = np.dtype([("valid", "<i4"), ("reserved", "<i4"), ("adr", "<i8"), ("doppler_hz", "<f8"), ("weight", "<f8")])
+SAT_RATE_DTYPE = np.dtype([("vx", "<f8"), ("vy", "<f8"), ("vz", "<f8"), ("clock_drift", "<f8")])
+VEL_OK, VEL_TOO_FEW, VEL_NO_FIX, VEL_SINGULAR = 0, 1, 2, 3
+VEL_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("vx", "<f8"), ("vy", "<f8"), ("vz", "<f8"), ("ve", "<f8"), ("vn", "<f8"),
+                      ("vu", "<f8"), ("drift", "<f8"), ("rms", "<f8")])
 
 
 class TrackParams(ctypes.Structure):
@@ -111,7 +117,9 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_ephemeris_load", "gpsacq_ephemeris_valid", "gpsacq_sat_states", "gpsacq_sat_states_device", "gpsacq_fix_batch",
            "gpsacq_fix_batch_device", "gpsacq_fix_last_ms",
            "gpsacq_time_tag_from_subframe", "gpsacq_observables", "gpsacq_observables_device", "gpsacq_fix_track_device",
-           "gpsacq_observables_last_ms"]
+           "gpsacq_observables_last_ms",
+           "gpsacq_track_nominal_word_iq8", "gpsacq_rate_observables", "gpsacq_rate_observables_device", "gpsacq_sat_rates",
+           "gpsacq_sat_rates_device", "gpsacq_vel_batch", "gpsacq_vel_batch_device", "gpsacq_pvt_track_device", "gpsacq_velocity_last_ms"]
 
 _lib = None
 
@@ -306,6 +314,27 @@ def load_library(path=None):
     lib.gpsacq_fix_track_device.restype = ctypes.c_int
     lib.gpsacq_observables_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     lib.gpsacq_observables_last_ms.restype = ctypes.c_int
+    u64 = ctypes.c_uint64
+    lib.gpsacq_track_nominal_word_iq8.argtypes = [vp, ctypes.POINTER(Iq8Input), ctypes.POINTER(ctypes.c_uint32)]
+    lib.gpsacq_track_nominal_word_iq8.restype = ctypes.c_int
+    rate_args = [vp, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, u64, u64, sz, u64, vp]
+    lib.gpsacq_rate_observables.argtypes = rate_args
+    lib.gpsacq_rate_observables.restype = ctypes.c_int
+    lib.gpsacq_rate_observables_device.argtypes = rate_args + [ctypes.c_int]
+    lib.gpsacq_rate_observables_device.restype = ctypes.c_int
+    lib.gpsacq_sat_rates.argtypes = [vp, vp, ctypes.c_int, vp, sz, vp]
+    lib.gpsacq_sat_rates.restype = ctypes.c_int
+    lib.gpsacq_sat_rates_device.argtypes = [vp, vp, ctypes.c_int, vp, sz, vp, ctypes.c_int]
+    lib.gpsacq_sat_rates_device.restype = ctypes.c_int
+    lib.gpsacq_vel_batch.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, sz, ctypes.c_int, vp]
+    lib.gpsacq_vel_batch.restype = ctypes.c_int
+    lib.gpsacq_vel_batch_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, sz, ctypes.c_int, vp, ctypes.c_int]
+    lib.gpsacq_vel_batch_device.restype = ctypes.c_int
+    lib.gpsacq_pvt_track_device.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, u64, u64, sz, u64, vp, vp, vp, vp,
+                                            ctypes.c_int]
+    lib.gpsacq_pvt_track_device.restype = ctypes.c_int
+    lib.gpsacq_velocity_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 4
+    lib.gpsacq_velocity_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -774,6 +803,104 @@ class Engine:
         a, b = ctypes.c_float(), ctypes.c_float()
         _check(self._lib, self._lib.gpsacq_observables_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    # ---- carrier observables, velocity ----------------------------------------------------
+    @staticmethod
+    def _rate_arrays(n_epochs, chans, nom_words):
+        ne = np.ascontiguousarray(np.asarray(n_epochs, dtype=np.int32).ravel())
+        ch = np.ascontiguousarray(np.asarray(chans, dtype=TRACK_CHAN_DTYPE).ravel())
+        if nom_words is None:  # 1-bit and sign-mode channels: the word lo_nom holds
+            nom_words = (ch["lo_nom"].view(np.uint64) >> np.uint64(32)).astype(np.uint32)
+        nw = np.ascontiguousarray(np.asarray(nom_words, dtype=np.uint32).ravel())
+        if not (ne.size == ch.size == nw.size):
+            raise ValueError("n_epochs, chans and nom_words must hold one entry per channel")
+        return ne, ch, nw
+
+    def nominal_word_iq8(self, inp):
+        """gpsacq_track_nominal_word_iq8: the carrier NCO word of zero Doppler of channels started with track_start_iq8 on the
+        capture inp describes (multi-bit channels keep their START word in lo_nom, so the default of rate_observables is not
+        theirs)."""
+        w = ctypes.c_uint32()
+        _check(self._lib, self._lib.gpsacq_track_nominal_word_iq8(self._h, ctypes.byref(inp), ctypes.byref(w)))
+        return int(w.value)
+
+    def rate_observables(self, records, n_epochs, chans, first_rx_sample, rx_step, n_fix, avg_samples, nom_words=None):
+        """gpsacq_rate_observables: accumulated Doppler (adr, cycles * 2^32 from record 0) and Doppler (Hz, averaged over avg_samples
+        samples centred on the instant) of every channel at the receive samples first_rx_sample + i * rx_step.  Arguments as
+        observables() without the tags; nom_words None: the 1-bit rule, lo_nom >> 32 of chans.  Returns RATE_OBS_DTYPE
+        [n_fix][n_chans], index-parallel to observables()."""
+        ne, ch, nw = self._rate_arrays(n_epochs, chans, nom_words)
+        if not isinstance(records, np.ndarray) or records.dtype != TRACK_RECORD_DTYPE or records.ndim != 2 or records.shape[0] != ne.size:
+            raise TypeError("records must be a TRACK_RECORD_DTYPE array [n_chans][max_epochs]")
+        rec = np.ascontiguousarray(records)
+        out = np.zeros((int(n_fix), ne.size), dtype=RATE_OBS_DTYPE)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_rate_observables(self._h, p(rec), int(rec.shape[1]), p(ne), p(ch), p(nw), int(ne.size),
+                                                            int(first_rx_sample), int(rx_step), int(n_fix), int(avg_samples), p(out)))
+        return out
+
+    def rate_observables_device(self, d_records_ptr, max_epochs, n_epochs, chans, first_rx_sample, rx_step, n_fix, avg_samples, d_rate_obs_ptr,
+                                nom_words=None, sync=True):
+        """gpsacq_rate_observables_device: records and rate observations in device memory, the rest host arrays."""
+        ne, ch, nw = self._rate_arrays(n_epochs, chans, nom_words)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_rate_observables_device(self._h, d_records_ptr, int(max_epochs), p(ne), p(ch), p(nw), int(ne.size),
+                                                                   int(first_rx_sample), int(rx_step), int(n_fix), int(avg_samples),
+                                                                   d_rate_obs_ptr, 1 if sync else 0))
+
+    def sat_rates(self, eph, obs):
+        """gpsacq_sat_rates: ECEF velocity and clock drift (SAT_RATE_DTYPE, obs's shape) of every observation."""
+        ep, ob = self._nav_arrays(eph, obs)
+        out = np.zeros(ob.shape, dtype=SAT_RATE_DTYPE)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_sat_rates(self._h, p(ep), int(ep.size), p(ob), int(ob.size), p(out)))
+        return out
+
+    def sat_rates_device(self, eph, d_obs_ptr, n_obs, d_out_ptr, sync=True):
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        _check(self._lib, self._lib.gpsacq_sat_rates_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_obs_ptr, int(n_obs),
+                                                            d_out_ptr, 1 if sync else 0))
+
+    def velocity(self, eph, obs, rate_obs, fixes):
+        """gpsacq_vel_batch: receiver velocity and clock drift (VEL_DTYPE [n_fix]) from obs (OBS_DTYPE [n_fix][sats_per_fix]), the
+        index-parallel rate_obs (RATE_OBS_DTYPE) and the fixes made from obs (FIX_DTYPE [n_fix])."""
+        ep, ob = self._nav_arrays(eph, obs)
+        if ob.ndim != 2:
+            raise ValueError("obs must be [n_fix][sats_per_fix]")
+        if not isinstance(rate_obs, np.ndarray) or rate_obs.dtype != RATE_OBS_DTYPE or rate_obs.shape != ob.shape:
+            raise TypeError("rate_obs must be a RATE_OBS_DTYPE array of obs's shape")
+        if not isinstance(fixes, np.ndarray) or fixes.dtype != FIX_DTYPE or fixes.shape != (ob.shape[0],):
+            raise TypeError("fixes must be a FIX_DTYPE array [n_fix]")
+        ro, fx = np.ascontiguousarray(rate_obs), np.ascontiguousarray(fixes)
+        out = np.zeros(ob.shape[0], dtype=VEL_DTYPE)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_vel_batch(self._h, p(ep), int(ep.size), p(ob), p(ro), p(fx), int(ob.shape[0]), int(ob.shape[1]), p(out)))
+        return out
+
+    def velocity_device(self, eph, d_obs_ptr, d_rate_obs_ptr, d_fix_ptr, n_fix, sats_per_fix, d_out_ptr, sync=True):
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        _check(self._lib, self._lib.gpsacq_vel_batch_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_obs_ptr, d_rate_obs_ptr,
+                                                            d_fix_ptr, int(n_fix), int(sats_per_fix), d_out_ptr, 1 if sync else 0))
+
+    def pvt_track_device(self, eph, d_records_ptr, max_epochs, n_epochs, chans, tags, first_rx_sample, rx_step, n_fix, avg_samples, d_fix_ptr,
+                         d_vel_ptr, d_obs_ptr=None, d_rate_obs_ptr=None, nom_words=None, sync=True):
+        """gpsacq_pvt_track_device: fix_track_device extended by the rate observations and the velocities, all on the engine's
+        stream.  d_fix: FIX_DTYPE [n_fix], d_vel: VEL_DTYPE [n_fix] in device memory; d_obs_ptr / d_rate_obs_ptr None keep the
+        observations in engine scratch."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        ne, ch, tg = self._obs_arrays(n_epochs, chans, tags)
+        _, _, nw = self._rate_arrays(n_epochs, chans, nom_words)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_pvt_track_device(self._h, p(ep), int(ep.size), d_records_ptr, int(max_epochs), p(ne), p(ch), p(tg), p(nw),
+                                                            int(ne.size), int(first_rx_sample), int(rx_step), int(n_fix), int(avg_samples),
+                                                            d_obs_ptr, d_rate_obs_ptr, d_fix_ptr, d_vel_ptr, 1 if sync else 0))
+
+    def velocity_last_ms(self):
+        """Device milliseconds of the last rate_observables* / velocity* / pvt_track_device calls: (accumulation kernel, rate
+        observation kernel, satellite-rate kernel, velocity kernel); a pair whose call has not been made reads 0."""
+        t = [ctypes.c_float() for _ in range(4)]
+        _check(self._lib, self._lib.gpsacq_velocity_last_ms(self._h, *[ctypes.byref(x) for x in t]))
+        return tuple(x.value for x in t)
 
     # ---- tracking channels on an 8-bit IQ capture -----------------------------------------
     def iq8_power(self, iq, signed=False):

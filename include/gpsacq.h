@@ -847,6 +847,136 @@ GPSACQ_API int gpsacq_fix_track_device(gpsacq_engine* e, const gpsacq_ephemeris*
  * events on its stream; waits for them).  Either pointer may be NULL. */
 GPSACQ_API int gpsacq_observables_last_ms(const gpsacq_engine* e, float* code_pos_ms, float* observe_ms);
 
+/*
+ * ---- Carrier observables: accumulated Doppler and Doppler per channel ----------------------------------------------------------
+ *
+ * Every gpsacq_track_record carries lo_rate, the carrier NCO word its epoch ran at.  A phase-locked Costas channel follows the
+ * carrier to a fraction of a cycle (19 cm), so the sum of the NCO's advance is the carrier-phase observable.  THE MODEL; the
+ * kernels (csrc/obs_kernels.hip: k_carrier_acc, k_observe_rate) and the reference of the tests (tests/rate_ref.py) are both
+ * written from this text.  Integers up to the three fp64 operations of doppler_hz; n_t and end_t are those of CODE POSITION PER
+ * EPOCH above.
+ *
+ * NOMINAL WORD.  nom_word[c] (uint32, cycles per sample * 2^32) is the carrier NCO word of zero Doppler.  For 1-bit and
+ * sign-mode channels it is (uint32_t)((uint64_t)chan.lo_nom >> 32).  For multi-bit IQ channels chan.lo_nom is NOT it --
+ * gpsacq_track_start_iq8 stores the word the channel STARTED at there -- and gpsacq_track_nominal_word_iq8(e, in, &word) gives it
+ * (host arithmetic): gpsacq_track_start_iq8's formula at zero Doppler, f = -mix_hz + fc (GPSACQ_SAMPLES_COMPLEX: f = -mix_hz),
+ * reduced into [-fs / 2, fs / 2) by whole multiples of fs, word = (uint32)(int64)llround(f / fs * 2^32) (two's complement when
+ * negative).  In sign mode it returns (uint32)((fc / fs - floor(fc / fs)) * 2^32), cycles per sample mod 1: for fc < fs that
+ * is gpsacq_track_start's lo_nom >> 32 to the bit.
+ *
+ * ACCUMULATED DOPPLER PER EPOCH.
+ *     d_t     = (int64)(int32)(lo_rate_t - nom_word)       the difference wraps in 32 bits and is then sign-extended
+ *     A_0     = 0
+ *     A_{t+1} = A_t + n_t * d_t                            signed 64-bit (two's complement, mod 2^64)
+ * A_t is the accumulated Doppler at records[c][t].sample in cycles * 2^32, counted from record 0 of this call; A_n is the value
+ * at next_sample.  Over a run of epochs at constant lo_rate the low 32 bits of A plus n * nom_word advance as lo_phase does.
+ *
+ * RATE OBSERVATION of channel c at receive sample R, averaged over W = avg_samples >= 1 samples centred on R:
+ *     R_a = R - floor(W / 2),   R_b = R_a + W
+ *     A(X)       = A_t + (X - sample_t) * d_t               t the epoch that holds X: sample_t <= X < end_t
+ *     D          = A(R_b) - A(R_a)
+ *     doppler_hz = ((double)D * fs) / ((double)W * 4294967296.0)      product first, then the quotient; fs = the engine's
+ *     adr        = A(R)
+ *     valid = 1, weight = 1.0, reserved = 0
+ * Under the tracking windows |D| < 2^53, so (double)D is exact and W * 2^32 is exact: one rounding in the product, one in the
+ * quotient (no fast-math flag in the build).  The window is centred so that the average equals the instantaneous Doppler at R up to
+ * the third derivative of the phase (the second cancels).  A rate observation that cannot be made is 32 zero bytes: no epochs; R,
+ * R_a or R_b before record 0's sample (R < floor(W / 2) included); R or R_b at or past next_sample.  It needs no time tag.
+ * SIGN: doppler_hz > 0 for an approaching satellite, for a capture whose spectrum is not inverted (an inverted one is the caller's
+ * to negate).  adr carries no cycle-slip or half-cycle flag.
+ *
+ * gpsacq_rate_observables: gpsacq_observables's arguments without the tags, plus nom_words[n_chans] and avg_samples; the output
+ * rate_obs[n_fix][n_chans] is index-parallel to gpsacq_obs.  The _device form takes device pointers for records and rate_obs.
+ * Argument errors as for gpsacq_observables, avg_samples == 0 and nom_words == NULL included: GPSACQ_ERR_ARG, nothing launched,
+ * nothing written.  Two kernels: k_carrier_acc, one wave64 per channel, the prefix sum as a scan (acc[n_chans][max_epochs + 1]
+ * in engine scratch); k_observe_rate, one lane per (instant, channel).
+ */
+typedef struct { int32_t valid; int32_t reserved; int64_t adr; double doppler_hz; double weight; } gpsacq_rate_obs;   /* 32 bytes */
+GPSACQ_API int gpsacq_track_nominal_word_iq8(const gpsacq_engine* e, const gpsacq_iq8_input* in, uint32_t* word);
+GPSACQ_API int gpsacq_rate_observables(gpsacq_engine* e, const gpsacq_track_record* records, int max_epochs, const int32_t* n_epochs,
+                                       const gpsacq_track_chan* chans, const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample,
+                                       uint64_t rx_step, size_t n_fix, uint64_t avg_samples, gpsacq_rate_obs* rate_obs);
+GPSACQ_API int gpsacq_rate_observables_device(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs,
+                                              const gpsacq_track_chan* chans, const uint32_t* nom_words, int n_chans,
+                                              uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, uint64_t avg_samples,
+                                              void* d_rate_obs, int sync);
+
+/*
+ * ---- Velocity and clock drift -------------------------------------------------------------------------------------------------
+ *
+ * The reference stops at position; this is our own.  THE MODEL; the kernels (csrc/nav_kernels.hip: k_sat_state_rate, k_vel) and
+ * tests/rate_ref.py are both written from this text.
+ *
+ * SATELLITE VELOCITY: the time derivative of IS-GPS-200 Table 20-IV at the corrected time t_k of SATELLITE STATE, with n the
+ * corrected mean motion, phi = nu + omega, and E, r, u, i, Omega_k, x' = r cos u, y' = r sin u of that table:
+ *     E'      = n / (1 - e cos E)
+ *     nu'     = E' sqrt(1 - e^2) / (1 - e cos E)
+ *     u'      = nu' (1 + 2 (c_us cos 2phi - c_uc sin 2phi))
+ *     r'      = A e sin E E' + 2 nu' (c_rs cos 2phi - c_rc sin 2phi)
+ *     i'      = idot + 2 nu' (c_is cos 2phi - c_ic sin 2phi)
+ *     Omega_k' = omega_dot - Omega_e-dot
+ *     x''     = r' cos u - y' u',      y'' = r' sin u + x' u'
+ *     vx = x'' cos Omega_k - y'' cos i sin Omega_k + y' sin i sin Omega_k i' - Omega_k' y
+ *     vy = x'' sin Omega_k + y'' cos i cos Omega_k - y' sin i cos Omega_k i' + Omega_k' x
+ *     vz = y'' sin i + y' cos i i'
+ * ECEF metres per second.  clock_drift = a_f1 + 2 a_f2 t + F e sqrt_a cos E E', with E, E' and t at the UNCORRECTED time, the
+ * derivative of clock_corr as it is computed.  An observation that is not usable (SATELLITE STATE's rule) gives an all-zero
+ * gpsacq_sat_rate.
+ *
+ * VELOCITY.  First order, in the ECEF frame frozen at the receive instant.  Per fix: its gpsacq_fix (anything but GPSACQ_FIX_OK:
+ * GPSACQ_VEL_NO_FIX, n_used 0), its rows of gpsacq_obs and gpsacq_rate_obs.  A satellite is used where its gpsacq_obs is usable
+ * and its rate observation has valid != 0, a finite weight >= 0 and a finite doppler_hz.  For satellite i, with r_s, v_s its state
+ * and rate, t_tx its corrected transmit time, (r_r, t_rx) the fix, Omega_e = (0, 0, Omega_e-dot) and R(theta) the turn about z of FIX:
+ *     theta_i  = Omega_e-dot (t_tx,i - t_rx)                        the millisecond difference folded, as everywhere
+ *     r_i      = R(theta_i) r_s,i
+ *     v_i      = R(theta_i) (v_s,i + Omega_e x r_s,i)               inertial velocity expressed in that frame
+ *     e_i      = (r_i - r_r) / |r_i - r_r|
+ *     rho'_i   = -(c / L1) doppler_hz_i                             L1 = 1575.42e6
+ *     rho'_i   = e_i . (v_i - (v_r + Omega_e x r_r)) + c drift_r - c clock_drift_i
+ * Unknowns v_r (ECEF, m/s) and c drift_r: linear, so ONE weighted least-squares solve with the rows (-e_i, 1), weights
+ * gpsacq_rate_obs.weight, FIX's Cholesky and pivot test (a pivot below 1e-13 of its diagonal entry or a non-finite solution:
+ * GPSACQ_VEL_SINGULAR).  Fewer than 4 satellites: GPSACQ_VEL_TOO_FEW.  rms = sqrt(sum w res^2 / sum w) of the residuals AFTER the
+ * solve, m/s.  ve, vn, vu: v_r turned by the fix's lat / lon (east, north, up).  drift = drift_r is the fractional frequency
+ * error of the SAMPLING clock as seen through the carrier: > 0 when the receiver's clock runs fast.  Terms of order rho'^2 / c
+ * (below 3 mm/s) are left out.  Every double is 0 unless GPSACQ_VEL_OK.
+ *
+ * gpsacq_sat_rates: one rate per observation.  gpsacq_vel_batch: obs[n_fix][sats_per_fix], rate_obs[n_fix][sats_per_fix],
+ * fixes[n_fix], out[n_fix]; it runs k_sat_state and k_sat_state_rate into engine scratch, then k_vel.  Host forms refuse a negative
+ * or non-finite weight (GPSACQ_ERR_ARG); the _device forms (device pointers for obs, rate_obs, fixes and out) skip such a
+ * satellite.  gpsacq_pvt_track_device: gpsacq_fix_track_device extended -- records -> observations and rate observations -> fixes
+ * -> velocities on the engine's stream, no host copy in between; d_obs and d_rate_obs may be NULL (engine scratch); d_fix[n_fix]
+ * is byte for byte what gpsacq_fix_track_device writes.  Argument errors: GPSACQ_ERR_ARG, nothing launched, nothing written.
+ */
+typedef struct { double vx, vy, vz; double clock_drift; } gpsacq_sat_rate;                                                   /* 32 bytes */
+#define GPSACQ_VEL_OK 0
+#define GPSACQ_VEL_TOO_FEW 1      /* fewer than 4 usable satellites */
+#define GPSACQ_VEL_NO_FIX 2       /* the fix is not GPSACQ_FIX_OK */
+#define GPSACQ_VEL_SINGULAR 3     /* singular normal matrix or a non-finite solution */
+typedef struct {
+    int32_t status, n_used;
+    double vx, vy, vz;            /* ECEF, m/s */
+    double ve, vn, vu;            /* east, north, up at the fix, m/s */
+    double drift;                 /* fractional frequency error of the sampling clock */
+    double rms;                   /* weighted rms of the residuals after the solve, m/s */
+} gpsacq_vel;                     /* 72 bytes */
+GPSACQ_API int gpsacq_sat_rates(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs, size_t n_obs,
+                                gpsacq_sat_rate* out);
+GPSACQ_API int gpsacq_sat_rates_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, size_t n_obs,
+                                       void* d_out, int sync);
+GPSACQ_API int gpsacq_vel_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs,
+                                const gpsacq_rate_obs* rate_obs, const gpsacq_fix* fixes, size_t n_fix, int sats_per_fix, gpsacq_vel* out);
+GPSACQ_API int gpsacq_vel_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_rate_obs,
+                                       const void* d_fixes, size_t n_fix, int sats_per_fix, void* d_out, int sync);
+GPSACQ_API int gpsacq_pvt_track_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_records, int max_epochs,
+                                       const int32_t* n_epochs, const gpsacq_track_chan* chans, const gpsacq_time_tag* tags,
+                                       const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix,
+                                       uint64_t avg_samples, void* d_obs, void* d_rate_obs, void* d_fix, void* d_vel, int sync);
+/* device time of the new kernels of the last calls on this engine, milliseconds (HIP events on its stream; waits for them):
+ * k_carrier_acc and k_observe_rate of the last gpsacq_rate_observables* / gpsacq_pvt_track_device, k_sat_state_rate and k_vel of the
+ * last gpsacq_vel_batch* / gpsacq_pvt_track_device.  A pair whose call has not been made reads 0; neither made: GPSACQ_ERR_ARG.
+ * Any pointer may be NULL. */
+GPSACQ_API int gpsacq_velocity_last_ms(const gpsacq_engine* e, float* carrier_acc_ms, float* observe_rate_ms, float* sat_rate_ms, float* vel_ms);
+
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);
 

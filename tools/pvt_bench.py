@@ -10,7 +10,11 @@ The generator runs every satellite at the Doppler it has at sample 19.5 s x fs, 
 away from that instant the truth is off by the range acceleration (metres over the capture), so the error is given at that
 instant, and as median and maximum over the instants after the loops' first two seconds.
 
-    python tools/pvt_bench.py [--seconds 20] [--reps 5]
+With --velocity the line also carries the velocity leg: gpsacq_pvt_track_device over the same instants (Doppler averaged over half
+a second of samples), the device time of its four kernels from the same call as the others, and the speed of the stationary
+receiver at 19.5 s and over the instants whose window lies inside the records.  Without the flag the line is unchanged.
+
+    python tools/pvt_bench.py [--seconds 20] [--reps 5] [--velocity]
 """
 import argparse
 import json
@@ -28,6 +32,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=20.0)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--velocity", action="store_true")
     a = ap.parse_args()
     if a.seconds < 20.0:
         ap.error("subframes 1-3 are complete 19 s into the capture: --seconds must be at least 20")
@@ -93,17 +98,40 @@ def main():
             if best is None or sum(ms) < sum(best):
                 best = ms
         fix = d_fix.cpu().numpy().view(gpsacq.FIX_DTYPE)
+        vbest = None
+        if a.velocity:
+            d_fix2 = torch.zeros_like(d_fix)
+            d_vel = torch.zeros(n_fix * gpsacq.VEL_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+            torch.cuda.synchronize()
+            for _ in range(1 + a.reps):
+                eng.pvt_track_device(recs, d_rec.data_ptr(), max_epochs, ne, chans, tags, first, SPM, n_fix, int(0.5 * FS), d_fix2.data_ptr(),
+                                     d_vel.data_ptr(), sync=True)
+                ms = eng.observables_last_ms() + eng.fix_last_ms() + eng.velocity_last_ms()
+                if vbest is None or sum(ms) < sum(vbest):
+                    vbest = ms
+            vel = d_vel.cpu().numpy().view(gpsacq.VEL_DTYPE)
+            assert d_fix2.cpu().numpy().tobytes() == fix.tobytes()
         name = eng.device_name
     off = np.linalg.norm(np.stack([fix["x"], fix["y"], fix["z"]], 1) - geo["rx"], axis=1)
     ok = fix["status"] == 0
     row = (r_star - first) // SPM
     late = ok & (np.arange(n_fix) * SPM + first >= 2 * FS)
-    print(json.dumps({"bench": "pvt", "device": name, "seconds": a.seconds, "sats": len(prns), "epochs": int(ne.min()), "n_fix": int(n_fix),
+    out = {"bench": "pvt", "device": name, "seconds": a.seconds, "sats": len(prns), "epochs": int(ne.min()), "n_fix": int(n_fix),
                       "code_pos_ms": round(best[0], 4), "observe_ms": round(best[1], 4), "sat_state_ms": round(best[2], 4),
                       "fix_ms": round(best[3], 4), "kernel_ms": round(sum(best), 4), "fixes_per_s": round(n_fix / (sum(best) * 1e-3)),
                       "ok": int(ok.sum()), "valid_ephemerides": int(sum(gpsacq.ephemeris_valid(r) for r in recs)),
                       "position_error_at_19p5s_m": round(float(off[row]), 2), "position_error_median_m": round(float(np.median(off[late])), 2),
-                      "position_error_max_m": round(float(off[late].max()), 2)}))
+                      "position_error_max_m": round(float(off[late].max()), 2)}
+    if a.velocity:
+        vok = vel["status"] == 0
+        speed = np.sqrt(vel["vx"] ** 2 + vel["vy"] ** 2 + vel["vz"] ** 2)
+        vlate = vok & late
+        names = ("code_pos_ms", "observe_ms", "sat_state_ms", "fix_ms", "carrier_acc_ms", "observe_rate_ms", "sat_state_rate_ms", "vel_ms")
+        out["velocity"] = dict({k: round(v, 4) for k, v in zip(names, vbest)}, kernel_ms=round(sum(vbest), 4),
+                               pvt_per_s=round(n_fix / (sum(vbest) * 1e-3)), ok=int(vok.sum()), avg_samples=int(0.5 * FS),
+                               speed_at_19p5s_mps=round(float(speed[row]), 4), speed_median_mps=round(float(np.median(speed[vlate])), 4),
+                               speed_max_mps=round(float(speed[vlate].max()), 4), drift_at_19p5s=float(vel["drift"][row]))
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
