@@ -124,6 +124,13 @@ struct gpsacq_engine {
     hipEvent_t rate_ev[3] = {};  // before k_carrier_acc, between the kernels, after k_observe_rate
     hipEvent_t vel_ev[3] = {};   // before k_sat_state_rate, between it and k_vel, after k_vel
     bool rate_timed = false, vel_timed = false;
+    // atmosphere-corrected fixes (gpsacq_sat_views*, gpsacq_fix_atm_batch*)
+    gpsacq_fix_dop* d_atm_dop = nullptr;  // host-buffer form, and where the caller wants no DOP
+    size_t atm_dop_cap = 0;
+    gpsacq_sat_view* d_atm_view = nullptr;  // host-buffer forms
+    size_t atm_view_cap = 0;
+    hipEvent_t atm_ev[4] = {};  // before k_sat_state, between it and k_fix_atm, after k_fix_atm, after k_sat_view
+    bool atm_timed = false, atm_views = false;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;

@@ -2,7 +2,8 @@
 // subframes 1-3 by IS-GPS-200 Tables 20-I and 20-III, read from gpsacq_subframe.words[].  Then the gpsacq_sat_states* and
 // gpsacq_fix_batch* entry points that run nav_kernels.hip on the engine of gpsacq_engine.hpp.  Last "Observables": the time tag
 // (host only) and the gpsacq_observables* / gpsacq_fix_track_device entry points that run obs_kernels.hip, then "Carrier observables"
-// and "Velocity and clock drift": gpsacq_rate_observables*, gpsacq_sat_rates*, gpsacq_vel_batch*, gpsacq_pvt_track_device.
+// and "Velocity and clock drift": gpsacq_rate_observables*, gpsacq_sat_rates*, gpsacq_vel_batch*, gpsacq_pvt_track_device.  At the
+// end "Atmosphere, elevation mask and DOP": page 18 and the parameters (host only), gpsacq_sat_views*, gpsacq_fix_atm_batch*.
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "gpsacq_engine.hpp"
+#include "atm_launch.hpp"
 #include "nav_launch.hpp"
 #include "obs_launch.hpp"
 
@@ -505,5 +507,163 @@ extern "C" int gpsacq_velocity_last_ms(const gpsacq_engine* e, float* carrier_ac
     if (observe_rate_ms) *observe_rate_ms = t[1];
     if (sat_rate_ms) *sat_rate_ms = t[2];
     if (vel_ms) *vel_ms = t[3];
+    return GPSACQ_OK;
+}
+
+// ---- atmosphere, elevation mask and DOP (atm_kernels.hip) --------------------------------------------------------------------
+extern "C" int gpsacq_iono_load(gpsacq_iono* io, const gpsacq_subframe* sf, int n) {
+    if (!io || n < 0 || (n > 0 && !sf)) return fail(GPSACQ_ERR_ARG, "gpsacq_iono_load: bad argument");
+    for (int k = 0; k < n; ++k) {
+        const uint32_t* w = sf[k].words;
+        if (ubits(w, 2, 20, 3) != 4 || ubits(w, 3, 1, 8) != 0x78) continue;  // subframe 4, data ID 01, SV/page ID 56: page 18
+        io->valid = 1;
+        io->tow = (int32_t)ubits(w, 2, 1, 17);
+        // IS-GPS-200 Figure 20-1 sheet 8, Table 20-X
+        io->alpha[0] = scaled(sbits(w, 3, 9, 8), -30);
+        io->alpha[1] = scaled(sbits(w, 3, 17, 8), -27);
+        io->alpha[2] = scaled(sbits(w, 4, 1, 8), -24);
+        io->alpha[3] = scaled(sbits(w, 4, 9, 8), -24);
+        io->beta[0] = scaled(sbits(w, 4, 17, 8), 11);
+        io->beta[1] = scaled(sbits(w, 5, 1, 8), 14);
+        io->beta[2] = scaled(sbits(w, 5, 9, 8), 16);
+        io->beta[3] = scaled(sbits(w, 5, 17, 8), 16);
+    }
+    return GPSACQ_OK;
+}
+
+namespace {
+constexpr double ATM_HALF_PI = 1.5707963267948966;
+}
+
+extern "C" int gpsacq_atm_default_params(const gpsacq_iono* io, gpsacq_atm_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_atm_default_params: null argument");
+    std::memset(p, 0, sizeof *p);
+    if (io && io->valid)
+        for (int k = 0; k < 4; ++k) p->alpha[k] = io->alpha[k], p->beta[k] = io->beta[k];
+    p->elev_mask = 5.0 * (2.0 * ATM_HALF_PI) / 180.0;
+    p->flags = GPSACQ_ATM_IONO | GPSACQ_ATM_TROPO;
+    return GPSACQ_OK;
+}
+
+static int atm_check_params(const char* who, const gpsacq_atm_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "%s: params is NULL", who);
+    if (!std::isfinite(p->elev_mask) || p->elev_mask < -ATM_HALF_PI || !(p->elev_mask < ATM_HALF_PI))
+        return fail(GPSACQ_ERR_ARG, "%s: elev_mask %g outside [-pi/2, pi/2)", who, p->elev_mask);
+    if (p->flags & ~(GPSACQ_ATM_IONO | GPSACQ_ATM_TROPO)) return fail(GPSACQ_ERR_ARG, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(p->alpha[k]) || !std::isfinite(p->beta[k])) return fail(GPSACQ_ERR_ARG, "%s: coefficient %d is not finite", who, k);
+    return GPSACQ_OK;
+}
+
+static int atm_check(const char* who, const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* obs, size_t n_fix,
+                     int sats_per_fix, const gpsacq_atm_params* params, const void* out) {
+    if (int rc = nav_check(who, e, eph, n_eph, obs, n_fix, out)) return rc;
+    if (sats_per_fix < 1 || sats_per_fix > GPSACQ_FIX_MAX_SATS)
+        return fail(GPSACQ_ERR_ARG, "%s: sats_per_fix %d outside 1 .. %d", who, sats_per_fix, GPSACQ_FIX_MAX_SATS);
+    return atm_check_params(who, params);
+}
+
+extern "C" int gpsacq_sat_views_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_fix,
+                                       size_t n_fix, int sats_per_fix, const gpsacq_atm_params* params, void* d_out, int sync) {
+    if (int rc = atm_check("gpsacq_sat_views", e, eph, n_eph, d_obs, n_fix, sats_per_fix, params, d_out)) return rc;
+    if (!d_fix) return fail(GPSACQ_ERR_ARG, "gpsacq_sat_views: bad argument");
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
+    launch_sat_state(SatStateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_nav_state}, e->stream);
+    launch_sat_view(SatViewArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, e->d_nav_state, (const gpsacq_fix*)d_fix, n_obs, sats_per_fix, *params,
+                                (gpsacq_sat_view*)d_out},
+                    e->stream);
+    HIPCHK(hipGetLastError());
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_sat_views(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs, const gpsacq_fix* fix,
+                                size_t n_fix, int sats_per_fix, const gpsacq_atm_params* params, gpsacq_sat_view* out) {
+    if (int rc = atm_check("gpsacq_sat_views", e, eph, n_eph, obs, n_fix, sats_per_fix, params, out)) return rc;
+    if (!fix) return fail(GPSACQ_ERR_ARG, "gpsacq_sat_views: bad argument");
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    if (int rc = nav_check_weights("gpsacq_sat_views", obs, n_obs)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
+    if (int rc = grow(e->d_atm_view, e->atm_view_cap, n_obs, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_nav_fix, fix, n_fix * sizeof(gpsacq_fix), hipMemcpyHostToDevice, e->stream));
+    if (int rc = gpsacq_sat_views_device(e, eph, n_eph, e->d_nav_obs, e->d_nav_fix, n_fix, sats_per_fix, params, e->d_atm_view, 0)) return rc;
+    HIPCHK(hipMemcpyAsync(out, e->d_atm_view, n_obs * sizeof(gpsacq_sat_view), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_atm_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, size_t n_fix,
+                                           int sats_per_fix, const gpsacq_atm_params* params, void* d_fix, void* d_dop, void* d_views,
+                                           int sync) {
+    if (int rc = atm_check("gpsacq_fix_atm_batch", e, eph, n_eph, d_obs, n_fix, sats_per_fix, params, d_fix)) return rc;
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
+    if (!d_dop) {  // the kernel always writes it
+        if (int rc = grow(e->d_atm_dop, e->atm_dop_cap, n_fix, e->stream)) return rc;
+        d_dop = e->d_atm_dop;
+    }
+    for (auto& ev : e->atm_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    e->atm_timed = false;
+    HIPCHK(hipEventRecord(e->atm_ev[0], e->stream));
+    launch_sat_state(SatStateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_nav_state}, e->stream);
+    HIPCHK(hipEventRecord(e->atm_ev[1], e->stream));
+    launch_fix_atm(FixAtmArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, e->d_nav_state, n_fix, sats_per_fix, *params, (gpsacq_fix*)d_fix,
+                              (gpsacq_fix_dop*)d_dop},
+                   e->stream);
+    HIPCHK(hipEventRecord(e->atm_ev[2], e->stream));
+    if (d_views)
+        launch_sat_view(SatViewArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, e->d_nav_state, (const gpsacq_fix*)d_fix, n_obs, sats_per_fix,
+                                    *params, (gpsacq_sat_view*)d_views},
+                        e->stream);
+    HIPCHK(hipEventRecord(e->atm_ev[3], e->stream));
+    HIPCHK(hipGetLastError());
+    e->atm_views = d_views != nullptr;
+    e->atm_timed = true;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_atm_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs, size_t n_fix,
+                                    int sats_per_fix, const gpsacq_atm_params* params, gpsacq_fix* fix_out, gpsacq_fix_dop* dop_out,
+                                    gpsacq_sat_view* views_out) {
+    if (int rc = atm_check("gpsacq_fix_atm_batch", e, eph, n_eph, obs, n_fix, sats_per_fix, params, fix_out)) return rc;
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    if (int rc = nav_check_weights("gpsacq_fix_atm_batch", obs, n_obs)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
+    if (int rc = grow(e->d_atm_dop, e->atm_dop_cap, n_fix, e->stream)) return rc;
+    if (views_out)
+        if (int rc = grow(e->d_atm_view, e->atm_view_cap, n_obs, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    if (int rc = gpsacq_fix_atm_batch_device(e, eph, n_eph, e->d_nav_obs, n_fix, sats_per_fix, params, e->d_nav_fix, e->d_atm_dop,
+                                             views_out ? e->d_atm_view : nullptr, 0))
+        return rc;
+    HIPCHK(hipMemcpyAsync(fix_out, e->d_nav_fix, n_fix * sizeof(gpsacq_fix), hipMemcpyDeviceToHost, e->stream));
+    if (dop_out) HIPCHK(hipMemcpyAsync(dop_out, e->d_atm_dop, n_fix * sizeof(gpsacq_fix_dop), hipMemcpyDeviceToHost, e->stream));
+    if (views_out) HIPCHK(hipMemcpyAsync(views_out, e->d_atm_view, n_obs * sizeof(gpsacq_sat_view), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_atm_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* fix_atm_ms, float* sat_view_ms) {
+    if (!e || !e->atm_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_atm_last_ms: no gpsacq_fix_atm_batch call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    HIPCHK(hipEventSynchronize(e->atm_ev[3]));
+    if (sat_state_ms) HIPCHK(hipEventElapsedTime(sat_state_ms, e->atm_ev[0], e->atm_ev[1]));
+    if (fix_atm_ms) HIPCHK(hipEventElapsedTime(fix_atm_ms, e->atm_ev[1], e->atm_ev[2]));
+    if (sat_view_ms) {
+        *sat_view_ms = 0.f;
+        if (e->atm_views) HIPCHK(hipEventElapsedTime(sat_view_ms, e->atm_ev[2], e->atm_ev[3]));
+    }
     return GPSACQ_OK;
 }

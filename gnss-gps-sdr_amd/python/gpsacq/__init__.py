@@ -93,6 +93,13 @@ SAT_RATE_DTYPE = np.dtype([("vx", "<f8"), ("vy", "<f8"), ("vz", "<f8"), ("clock_
 VEL_OK, VEL_TOO_FEW, VEL_NO_FIX, VEL_SINGULAR = 0, 1, 2, 3
 VEL_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("vx", "<f8"), ("vy", "<f8"), ("vz", "<f8"), ("ve", "<f8"), ("vn", "<f8"),
                       ("vu", "<f8"), ("drift", "<f8"), ("rms", "<f8")])
+# atmosphere, elevation mask and DOP (include/gpsacq.h, "Atmosphere, elevation mask and DOP")
+ATM_IONO, ATM_TROPO, ATM_ROUNDS = 1, 2, 3
+IONO_DTYPE = np.dtype([("valid", "<i4"), ("tow", "<i4"), ("alpha", "<f8", (4,)), ("beta", "<f8", (4,))])
+ATM_PARAMS_DTYPE = np.dtype([("alpha", "<f8", (4,)), ("beta", "<f8", (4,)), ("elev_mask", "<f8"), ("flags", "<i4"), ("reserved", "<i4")])
+SAT_VIEW_DTYPE = np.dtype([("az", "<f8"), ("el", "<f8"), ("iono_m", "<f8"), ("tropo_m", "<f8")])
+FIX_DOP_DTYPE = np.dtype([("used_mask", "<u4"), ("n_masked", "<i4"), ("gdop", "<f8"), ("pdop", "<f8"), ("hdop", "<f8"), ("vdop", "<f8"),
+                          ("tdop", "<f8")])
 
 
 class TrackParams(ctypes.Structure):
@@ -119,7 +126,9 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_time_tag_from_subframe", "gpsacq_observables", "gpsacq_observables_device", "gpsacq_fix_track_device",
            "gpsacq_observables_last_ms",
            "gpsacq_track_nominal_word_iq8", "gpsacq_rate_observables", "gpsacq_rate_observables_device", "gpsacq_sat_rates",
-           "gpsacq_sat_rates_device", "gpsacq_vel_batch", "gpsacq_vel_batch_device", "gpsacq_pvt_track_device", "gpsacq_velocity_last_ms"]
+           "gpsacq_sat_rates_device", "gpsacq_vel_batch", "gpsacq_vel_batch_device", "gpsacq_pvt_track_device", "gpsacq_velocity_last_ms",
+           "gpsacq_iono_load", "gpsacq_atm_default_params", "gpsacq_sat_views", "gpsacq_sat_views_device", "gpsacq_fix_atm_batch",
+           "gpsacq_fix_atm_batch_device", "gpsacq_fix_atm_last_ms"]
 
 _lib = None
 
@@ -335,6 +344,20 @@ def load_library(path=None):
     lib.gpsacq_pvt_track_device.restype = ctypes.c_int
     lib.gpsacq_velocity_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 4
     lib.gpsacq_velocity_last_ms.restype = ctypes.c_int
+    lib.gpsacq_iono_load.argtypes = [vp, vp, ctypes.c_int]
+    lib.gpsacq_iono_load.restype = ctypes.c_int
+    lib.gpsacq_atm_default_params.argtypes = [vp, vp]
+    lib.gpsacq_atm_default_params.restype = ctypes.c_int
+    lib.gpsacq_sat_views.argtypes = [vp, vp, ctypes.c_int, vp, vp, sz, ctypes.c_int, vp, vp]
+    lib.gpsacq_sat_views.restype = ctypes.c_int
+    lib.gpsacq_sat_views_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, sz, ctypes.c_int, vp, vp, ctypes.c_int]
+    lib.gpsacq_sat_views_device.restype = ctypes.c_int
+    lib.gpsacq_fix_atm_batch.argtypes = [vp, vp, ctypes.c_int, vp, sz, ctypes.c_int, vp, vp, vp, vp]
+    lib.gpsacq_fix_atm_batch.restype = ctypes.c_int
+    lib.gpsacq_fix_atm_batch_device.argtypes = [vp, vp, ctypes.c_int, vp, sz, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_fix_atm_batch_device.restype = ctypes.c_int
+    lib.gpsacq_fix_atm_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
+    lib.gpsacq_fix_atm_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -404,6 +427,31 @@ def ephemeris_valid(eph):
     """gpsacq_ephemeris_valid of one EPHEMERIS_DTYPE record: subframes 1-3 loaded and IODC's low byte == both IODEs != 0."""
     rec = np.array(eph, dtype=EPHEMERIS_DTYPE).reshape(1).copy()
     return bool(load_library().gpsacq_ephemeris_valid(rec.ctypes.data_as(ctypes.c_void_p)))
+
+
+def iono(subframes, io=None):
+    """gpsacq_iono_load: every page 18 (subframe 4, SV/page ID 56) of a SUBFRAME_DTYPE array folded, in order, into an IONO_DTYPE
+    record of shape (1,) -- a fresh one (valid == 0 until a page 18 is seen), or a copy of `io` to carry on from."""
+    lib = load_library()
+    sf = np.ascontiguousarray(np.asarray(subframes, dtype=SUBFRAME_DTYPE).ravel())
+    out = np.zeros(1, dtype=IONO_DTYPE) if io is None else np.array(io, dtype=IONO_DTYPE).reshape(1).copy()
+    _check(lib, lib.gpsacq_iono_load(out.ctypes.data_as(ctypes.c_void_p), sf.ctypes.data_as(ctypes.c_void_p) if sf.size else None, int(sf.size)))
+    return out
+
+
+def atm_params(iono=None, elev_mask=None, flags=None):
+    """gpsacq_atm_default_params: an ATM_PARAMS_DTYPE record of shape (1,) -- the coefficients of `iono` (an IONO_DTYPE record;
+    zeros when None or not valid), a 5-degree mask, ionosphere and troposphere on -- with elev_mask (radians) and flags replaced
+    where given.  The entry points that take it check it."""
+    lib = load_library()
+    io = None if iono is None else np.array(iono, dtype=IONO_DTYPE).reshape(1).copy()
+    out = np.zeros(1, dtype=ATM_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_atm_default_params(None if io is None else io.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p)))
+    if elev_mask is not None:
+        out["elev_mask"] = float(elev_mask)
+    if flags is not None:
+        out["flags"] = int(flags)
+    return out
 
 
 def time_tag(subframe, bit_epoch0, eph_index):
@@ -754,6 +802,64 @@ class Engine:
         a, b = ctypes.c_float(), ctypes.c_float()
         _check(self._lib, self._lib.gpsacq_fix_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    # ---- atmosphere, elevation mask and DOP -----------------------------------------------
+    @staticmethod
+    def _atm_params(params):
+        if params is None:
+            return None, None
+        pr = np.array(params, dtype=ATM_PARAMS_DTYPE).reshape(1).copy()
+        return pr, pr.ctypes.data_as(ctypes.c_void_p)
+
+    def fix_atm(self, eph, obs, params, dop=True, views=False):
+        """gpsacq_fix_atm_batch: fix() with the ionosphere, the troposphere and the elevation mask of params (atm_params()).
+        Returns FIX_DTYPE [n_fix], then FIX_DOP_DTYPE [n_fix] if dop, then SAT_VIEW_DTYPE [n_fix][sats_per_fix] if views (a tuple
+        when more than the fixes is asked for)."""
+        ep, ob = self._nav_arrays(eph, obs)
+        if ob.ndim != 2:
+            raise ValueError("obs must be [n_fix][sats_per_fix]")
+        pr, pp = self._atm_params(params)
+        out = np.zeros(ob.shape[0], dtype=FIX_DTYPE)
+        dp = np.zeros(ob.shape[0], dtype=FIX_DOP_DTYPE) if dop else None
+        vw = np.zeros(ob.shape, dtype=SAT_VIEW_DTYPE) if views else None
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_fix_atm_batch(self._h, p(ep), int(ep.size), p(ob), int(ob.shape[0]), int(ob.shape[1]), pp, p(out),
+                                                         p(dp), p(vw)))
+        res = (out,) + ((dp,) if dop else ()) + ((vw,) if views else ())
+        return res if len(res) > 1 else out
+
+    def fix_atm_device(self, eph, d_obs_ptr, n_fix, sats_per_fix, params, d_fix_ptr, d_dop_ptr=None, d_views_ptr=None, sync=True):
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        pr, pp = self._atm_params(params)
+        _check(self._lib, self._lib.gpsacq_fix_atm_batch_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_obs_ptr, int(n_fix),
+                                                                int(sats_per_fix), pp, d_fix_ptr, d_dop_ptr, d_views_ptr, 1 if sync else 0))
+
+    def sat_views(self, eph, obs, fixes, params):
+        """gpsacq_sat_views: azimuth, elevation and the two delays (SAT_VIEW_DTYPE [n_fix][sats_per_fix]) of every observation of
+        obs (OBS_DTYPE [n_fix][sats_per_fix]) seen from its row's fix (FIX_DTYPE [n_fix])."""
+        ep, ob = self._nav_arrays(eph, obs)
+        if ob.ndim != 2:
+            raise ValueError("obs must be [n_fix][sats_per_fix]")
+        if not isinstance(fixes, np.ndarray) or fixes.dtype != FIX_DTYPE or fixes.shape != (ob.shape[0],):
+            raise TypeError("fixes must be a FIX_DTYPE array [n_fix]")
+        fx = np.ascontiguousarray(fixes)
+        pr, pp = self._atm_params(params)
+        out = np.zeros(ob.shape, dtype=SAT_VIEW_DTYPE)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_sat_views(self._h, p(ep), int(ep.size), p(ob), p(fx), int(ob.shape[0]), int(ob.shape[1]), pp, p(out)))
+        return out
+
+    def sat_views_device(self, eph, d_obs_ptr, d_fix_ptr, n_fix, sats_per_fix, params, d_out_ptr, sync=True):
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        pr, pp = self._atm_params(params)
+        _check(self._lib, self._lib.gpsacq_sat_views_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_obs_ptr, d_fix_ptr,
+                                                            int(n_fix), int(sats_per_fix), pp, d_out_ptr, 1 if sync else 0))
+
+    def fix_atm_last_ms(self):
+        """Device milliseconds of the last fix_atm* call: (satellite-state kernel, corrected-fix kernel, view kernel or 0)."""
+        t = [ctypes.c_float() for _ in range(3)]
+        _check(self._lib, self._lib.gpsacq_fix_atm_last_ms(self._h, *[ctypes.byref(x) for x in t]))
+        return tuple(x.value for x in t)
 
     # ---- observables ----------------------------------------------------------------------
     @staticmethod

@@ -977,6 +977,117 @@ GPSACQ_API int gpsacq_pvt_track_device(gpsacq_engine* e, const gpsacq_ephemeris*
  * Any pointer may be NULL. */
 GPSACQ_API int gpsacq_velocity_last_ms(const gpsacq_engine* e, float* carrier_acc_ms, float* observe_rate_ms, float* sat_rate_ms, float* vel_ms);
 
+/*
+ * ---- Atmosphere, elevation mask and DOP ---------------------------------------------------------------------------------------
+ *
+ * gpsacq_fix_batch is the reference's bare Solve(): signals as if in vacuum, every satellite with an ephemeris used, no figure of
+ * the geometry.  This section adds the Klobuchar ionosphere, a Saastamoinen troposphere, an elevation mask and the dilutions of
+ * precision.  The reference decodes the ionospheric coefficients (EPHEM::LoadPage18, c/ephemeris.cpp:70-83) and never uses them;
+ * the rest is our own.  THE MODEL; the kernels (csrc/atm_kernels.hip: k_sat_view, k_fix_atm) and tests/atm_ref.py are both
+ * written from this text.  Nothing of the sections above changes: k_sat_state, k_fix, k_vel and their entry points are what they were.
+ *
+ * PAGE 18 (host only).  gpsacq_iono_load folds, in the order given, every subframe of sf[0..n-1] whose ID (word 2, bits 20-22)
+ * is 4 and whose word 3 starts with the eight bits 0x78 (data ID 01, SV/page ID 56: the test EPHEM::Subframe4 makes).  Such a
+ * page sets valid = 1, tow = its TOW count (word 2, bits 1-17) and the eight coefficients; everything else is ignored and *io is
+ * left as it was (zero the record first).  The fields are eight signed 8-bit integers, IS-GPS-200 Figure 20-1 sheet 8 and Table
+ * 20-X, in the convention of EPHEMERIS above (ICD word w is words[w - 1], its bit b is bit 24 - b):
+ *     alpha0, alpha1        word 3, bits 9-16 and 17-24       * 2^-30, 2^-27     seconds, seconds / semicircle
+ *     alpha2, alpha3, beta0 word 4, bits 1-8, 9-16, 17-24     * 2^-24, 2^-24, 2^11
+ *     beta1, beta2, beta3   word 5, bits 1-8, 9-16, 17-24     * 2^14, 2^16, 2^16
+ * (LoadPage18's bytes nav[7..14]).  Each value is integer * power of two, exact.  The UTC parameters of the same page are not read.
+ *
+ * PARAMETERS.  gpsacq_atm_default_params: alpha / beta from *io when it is given and valid, else zeros; elev_mask = 5 degrees
+ * (5 pi / 180 radians); flags = GPSACQ_ATM_IONO | GPSACQ_ATM_TROPO; reserved = 0.  Every entry point below checks its parameters:
+ * elev_mask finite and in [-pi/2, pi/2) (-pi/2 masks nothing), no flag bit besides the two, finite alpha and beta; else
+ * GPSACQ_ERR_ARG.  pi is the true one, 3.141592653589793, everywhere in this section.
+ *
+ * VIEW of a satellite from a receiver at ECEF r, with (lat, lon, alt) = FIX's LatLonAlt() iteration of r (on the axis, where
+ * sqrt(x^2 + y^2) <= 1e-6: lon = 0, lat = +-pi/2, alt = |z| - a sqrt(1 - e^2)).  alt is the height above the WGS-84 ellipsoid, not
+ * above the geoid.  s is the satellite's state turned by theta = Omega_e-dot (t_tx - t_rx) about z exactly as FIX and VELOCITY turn
+ * it, t_tx the corrected transmit time (tx - clock_corr).  d = s - r, and in the local frame (VELOCITY's rotation for ve, vn, vu)
+ *     e = -sin lon dx + cos lon dy
+ *     n = -sin lat cos lon dx - sin lat sin lon dy + cos lat dz
+ *     u =  cos lat cos lon dx + cos lat sin lon dy + sin lat dz
+ *     az = atan2(e, n)  in (-pi, pi],       el = atan2(u, hypot(e, n)).
+ *
+ * IONOSPHERE: IS-GPS-200 Figure 20-4, angles in semicircles.  With E = el / pi, phi_u = lat / pi, lambda_u = lon / pi and tow the
+ * receive time of week in seconds (rx_ms * 1e-3 + rx_frac):
+ *     psi      = 0.0137 / (E + 0.11) - 0.022
+ *     phi_i    = phi_u + psi cos az,                      clamped to +-0.416
+ *     lambda_i = lambda_u + psi sin az / cos(phi_i pi)
+ *     phi_m    = phi_i + 0.064 cos((lambda_i - 1.617) pi)
+ *     t        = 4.32e4 lambda_i + tow,   t = t - 86400 floor(t / 86400)             in [0, 86400)
+ *     F        = 1 + 16 (0.53 - E)^3
+ *     AMP      = ((alpha3 phi_m + alpha2) phi_m + alpha1) phi_m + alpha0,            0 where that is negative
+ *     PER      = ((beta3 phi_m + beta2) phi_m + beta1) phi_m + beta0,                72000 where that is less
+ *     x        = 2 pi (t - 50400) / PER
+ *     iono_m   = c F (5e-9 + AMP (1 - x^2 / 2 + x^4 / 24))   where |x| < 1.57,   else c F 5e-9.
+ * iono_m = 0 where el <= 0 or GPSACQ_ATM_IONO is off.  (The branch at |x| = 1.57 is the ICD's, and discontinuous.)
+ *
+ * TROPOSPHERE: Saastamoinen's zenith delay in a standard atmosphere (1013.25 hPa, 288.16 K - 6.5 K / km, 70 % humidity) over
+ * sin el.  tropo_m = 0 where el <= 0, alt < -100, alt > 1e4 or GPSACQ_ATM_TROPO is off.  Else, with h = max(alt, 0):
+ *     P = 1013.25 (1 - 2.2557e-5 h)^5.2568
+ *     T = 288.16 - 6.5e-3 h
+ *     e = 6.108 * 0.7 * exp((17.15 T - 4684) / (T - 38.45))
+ *     tropo_m = (0.0022768 P / (1 - 0.00266 cos(2 lat) - 0.00028 h / 1000) + 0.002277 (1255 / T + 0.05) e) / sin el.
+ *
+ * CORRECTED FIX, per row of observations:
+ *   0. FIX's iteration unchanged -- same start, same step rule, same failure tests -- over all usable observations.  A failure
+ *      ends the fix with FIX's status (fewer than 4 usable: GPSACQ_FIX_TOO_FEW before any step).
+ *   1. MASK.  At the position and receive time of stage 0, every used satellite with el < elev_mask is dropped, once and for all
+ *      (the position is within tens of metres, 1e-6 rad of elevation: the mask is not evaluated again).  Fewer than 4 left:
+ *      GPSACQ_FIX_TOO_FEW with n_used the number left.
+ *   2. ROUNDS.  If nothing was dropped and flags == 0 the fix is done.  Else GPSACQ_ATM_ROUNDS = 3 rounds: at the current position
+ *      and receive time compute every remaining satellite's D = iono_m + tropo_m, hold it, and run FIX's iteration FROM THE
+ *      CURRENT STATE (not from the origin) with the residual  c (t_rx - t_tx) - D - range.  theta keeps the unmodified t_tx: the
+ *      signal was under way for t_rx - t_tx.  Each round ends by its own step below 1e-4 m and has FIX's failure tests, 20 steps
+ *      included; a failure is GPSACQ_FIX_NO_CONVERGE.  Why three: the altitude error of a round feeds the next round's tropospheric
+ *      delay at 3e-4 m per metre, every round shrinks the distance to the model's fixed point about a thousandfold (2e-2, 2e-5,
+ *      3e-8 m measured on the tests' constellation), and the solver is tested to 1e-4 m.
+ *   3. OUTPUT.  gpsacq_fix as FIX writes it: n_used the satellites in the final solution, `iterations` every step of every stage,
+ *      rms that of the residuals the last step was made from; not GPSACQ_FIX_OK: every double 0 and rx_ms = 0 (n_used and
+ *      iterations stay).  gpsacq_fix_dop: used_mask has bit s set where observation s of the row is usable and was not dropped
+ *      (whatever the status), n_masked is the number the mask dropped.
+ * DOP.  At the final position and receive time, H has the rows (ux, uy, uz, 1), u the unit vector satellite -> receiver, over the
+ * satellites of used_mask WITH WEIGHT > 0.  Q = (H^T H)^-1, unweighted, by FIX's Cholesky and pivot test.  With the local frame
+ * of VIEW at the final position: pdop = sqrt(Qee + Qnn + Quu), hdop = sqrt(Qee + Qnn), vdop = sqrt(Quu), tdop = sqrt(Qtt) (the time
+ * unknown in metres), gdop = sqrt(Qee + Qnn + Quu + Qtt) = sqrt(trace Q).  A failed pivot or a fix that is not OK: all five 0.
+ *
+ * gpsacq_sat_views: obs[n_fix][sats_per_fix] and one gpsacq_fix per row (its x, y, z, rx_ms, rx_frac and status are read; lat /
+ * lon / alt are recomputed from x, y, z); out[n_fix][sats_per_fix].  An unusable observation or a fix that is not OK gives 32
+ * zero bytes.  gpsacq_fix_atm_batch: k_sat_state, then k_fix_atm, then -- if views are wanted -- k_sat_view on the fixes just
+ * written, so its views are exactly gpsacq_sat_views of its own fixes.  dop_out / views_out (d_dop / d_views) may be NULL.
+ * Arguments, scratch, stream and events as gpsacq_fix_batch*: the host forms refuse a negative or non-finite weight, the _device
+ * forms skip such an observation; params == NULL is GPSACQ_ERR_ARG.  A corrected gpsacq_fix goes into gpsacq_vel_batch* as it is.
+ *
+ * OUT OF SCOPE.  gps_track and the *_track_device chains stay on the plain fix: the signal generator puts no atmosphere on its
+ * captures, where a corrected fix would only be worse, and a real capture needs up to 12.5 minutes for a page 18.  The UTC
+ * parameters.  Dropping masked satellites from k_vel (the caller can clear `valid` from used_mask).  RAIM.
+ */
+typedef struct { int32_t valid; int32_t tow; double alpha[4]; double beta[4]; } gpsacq_iono;   /* 72 bytes */
+GPSACQ_API int gpsacq_iono_load(gpsacq_iono* io, const gpsacq_subframe* sf, int n);
+#define GPSACQ_ATM_IONO 1
+#define GPSACQ_ATM_TROPO 2
+#define GPSACQ_ATM_ROUNDS 3
+typedef struct { double alpha[4], beta[4]; double elev_mask; int32_t flags; int32_t reserved; } gpsacq_atm_params;   /* 80 bytes */
+GPSACQ_API int gpsacq_atm_default_params(const gpsacq_iono* io /* may be NULL or not valid: zeros */, gpsacq_atm_params* p);
+typedef struct { double az, el, iono_m, tropo_m; } gpsacq_sat_view;                                                          /* 32 bytes */
+typedef struct { uint32_t used_mask; int32_t n_masked; double gdop, pdop, hdop, vdop, tdop; } gpsacq_fix_dop;               /* 48 bytes */
+GPSACQ_API int gpsacq_sat_views(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs /* [n_fix][sats_per_fix] */,
+                                const gpsacq_fix* fix /* [n_fix] */, size_t n_fix, int sats_per_fix, const gpsacq_atm_params* params,
+                                gpsacq_sat_view* out /* [n_fix][sats_per_fix] */);
+GPSACQ_API int gpsacq_sat_views_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_fix,
+                                       size_t n_fix, int sats_per_fix, const gpsacq_atm_params* params, void* d_out, int sync);
+GPSACQ_API int gpsacq_fix_atm_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs, size_t n_fix,
+                                    int sats_per_fix, const gpsacq_atm_params* params, gpsacq_fix* fix_out, gpsacq_fix_dop* dop_out,
+                                    gpsacq_sat_view* views_out);
+GPSACQ_API int gpsacq_fix_atm_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, size_t n_fix,
+                                           int sats_per_fix, const gpsacq_atm_params* params, void* d_fix, void* d_dop, void* d_views,
+                                           int sync);
+/* device time of the kernels of the last gpsacq_fix_atm_batch* call on this engine, milliseconds (HIP events on its stream; waits
+ * for them); sat_view_ms reads 0 when that call asked for no views.  Any pointer may be NULL. */
+GPSACQ_API int gpsacq_fix_atm_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* fix_atm_ms, float* sat_view_ms);
+
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);
 

@@ -5,7 +5,11 @@ satellites each, from the synthetic constellation of the tests (tests/nav_ref.py
 line: n_fix, sats, the device time of the two kernels (HIP events on the engine's stream, best of --reps calls), fixes per
 second, and how far the worst fix lies from the receiver.
 
-    python tools/fix_bench.py [--n-fix 81800] [--sats 10] [--reps 5]
+    python tools/fix_bench.py [--n-fix 81800] [--sats 10] [--reps 5] [--atm]
+
+--atm: the same batch seen through the model's atmosphere (tests/atm_ref.py's truth maker: Klobuchar with coefficients that give
+metres, Saastamoinen) through gpsacq_fix_atm_batch_device (default parameters: both delays, 5-degree mask, DOP written, no
+views), and the plain solver on the SAME observations in the same run: fix_atm_ms beside fix_ms, and both worst position errors.
 """
 import argparse
 import json
@@ -22,6 +26,7 @@ def main():
     ap.add_argument("--n-fix", type=int, default=81800)
     ap.add_argument("--sats", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--atm", action="store_true")
     a = ap.parse_args()
 
     import numpy as np
@@ -36,8 +41,10 @@ def main():
     sel = (up + [k for k in range(12) if k not in up])[:a.sats]  # the satellites above the horizon first
     ref_ms = (geo["ref_ms"] + np.arange(a.n_fix, dtype=np.int64)) % nav_ref.WEEK_MS  # 1 kHz
     t_rx = (0.137e-3 + np.arange(a.n_fix) * 0.0131e-3) % 1e-3
-    obs = np.ascontiguousarray(truth_obs(geo, ref_ms, t_rx)[:, sel])
     rec = to_records(geo["ephs"])
+    if a.atm:
+        return atm(a, geo, sel, ref_ms, t_rx, rec)
+    obs = np.ascontiguousarray(truth_obs(geo, ref_ms, t_rx)[:, sel])
 
     with gpsacq.Engine(4.092e6, 5.456e6, 5000.0, device=0) as eng:
         d_obs = torch.from_numpy(obs.view(np.uint8).reshape(-1)).to("cuda:0")
@@ -56,6 +63,48 @@ def main():
                       "fix_ms": round(best[1], 4), "kernel_ms": round(sum(best), 4), "fixes_per_s": round(a.n_fix / (sum(best) * 1e-3)),
                       "ok": int((fix["status"] == 0).sum()), "iterations_max": int(fix["iterations"].max()),
                       "max_position_error_m": float(err)}))
+
+
+def atm(a, geo, sel, ref_ms, t_rx, rec):
+    import numpy as np
+    import torch
+
+    import atm_ref
+    import gpsacq
+
+    p = atm_ref.params()
+    tx_ms, tx_frac = atm_ref.truth_times([geo["ephs"][k] for k in sel], geo["rx"], ref_ms, t_rx, p)
+    obs = np.zeros(tx_ms.shape, gpsacq.OBS_DTYPE)
+    obs["tx_ms"], obs["tx_frac"], obs["eph"], obs["valid"], obs["weight"] = tx_ms, tx_frac, sel, 1, 1.0
+    par = gpsacq.atm_params()
+    par["alpha"][0], par["beta"][0] = p["alpha"], p["beta"]
+    with gpsacq.Engine(4.092e6, 5.456e6, 5000.0, device=0) as eng:
+        d_obs = torch.from_numpy(obs.view(np.uint8).reshape(-1)).to("cuda:0")
+        d_fix = torch.zeros(a.n_fix * gpsacq.FIX_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+        d_dop = torch.zeros(a.n_fix * gpsacq.FIX_DOP_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+        d_plain = torch.zeros_like(d_fix)
+        torch.cuda.synchronize()
+        best = plain = None
+        for _ in range(1 + a.reps):  # the first call also allocates the engine's scratch
+            eng.fix_atm_device(rec, d_obs.data_ptr(), a.n_fix, a.sats, par, d_fix.data_ptr(), d_dop.data_ptr(), sync=True)
+            ms = eng.fix_atm_last_ms()
+            if best is None or ms[1] < best[1]:
+                best = ms
+            eng.fix_device(rec, d_obs.data_ptr(), a.n_fix, a.sats, d_plain.data_ptr(), sync=True)
+            ms = eng.fix_last_ms()
+            if plain is None or ms[1] < plain[1]:
+                plain = ms
+        fix = d_fix.cpu().numpy().view(gpsacq.FIX_DTYPE)
+        dop = d_dop.cpu().numpy().view(gpsacq.FIX_DOP_DTYPE)
+        pfix = d_plain.cpu().numpy().view(gpsacq.FIX_DTYPE)
+        name = eng.device_name
+    xyz = lambda f: np.stack([f["x"], f["y"], f["z"]], 1)
+    print(json.dumps({"bench": "fix_atm", "device": name, "n_fix": a.n_fix, "sats": a.sats, "sat_state_ms": round(best[0], 4),
+                      "fix_atm_ms": round(best[1], 4), "fix_ms": round(plain[1], 4), "ratio": round(best[1] / plain[1], 3),
+                      "fixes_per_s": round(a.n_fix / ((best[0] + best[1]) * 1e-3)), "ok": int((fix["status"] == 0).sum()),
+                      "iterations_max": int(fix["iterations"].max()), "n_masked_max": int(dop["n_masked"].max()),
+                      "pdop_max": float(dop["pdop"].max()), "max_position_error_m": float(np.abs(xyz(fix) - geo["rx"]).max()),
+                      "plain_max_position_error_m": float(np.abs(xyz(pfix) - geo["rx"]).max())}))
 
 
 if __name__ == "__main__":
