@@ -13,6 +13,7 @@
 #include "gen_launch.hpp"
 #include "nav_launch.hpp"
 #include "obs_launch.hpp"
+#include "raim_launch.hpp"
 
 // sets this thread's gpsacq_last_error() text from a printf format and returns `code` (gpsacq_engine.cpp)
 int fail(int code, const char* fmt, ...);
@@ -131,6 +132,13 @@ struct gpsacq_engine {
     size_t atm_view_cap = 0;
     hipEvent_t atm_ev[4] = {};  // before k_sat_state, between it and k_fix_atm, after k_fix_atm, after k_sat_view
     bool atm_timed = false, atm_views = false;
+    // fix integrity (gpsacq_fix_raim_batch*)
+    acq::RaimRow* d_raim_rows = nullptr;  // k_raim_detect's hand-over to k_raim_exclude: [n_fix]
+    size_t raim_rows_cap = 0;
+    gpsacq_fix_raim* d_raim = nullptr;  // host-buffer form
+    size_t raim_cap = 0;
+    hipEvent_t raim_ev[4] = {};  // before k_sat_state, between it and k_raim_detect, after k_raim_detect, after k_raim_exclude
+    bool raim_timed = false;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;

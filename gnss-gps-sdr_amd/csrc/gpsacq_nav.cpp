@@ -3,7 +3,8 @@
 // gpsacq_fix_batch* entry points that run nav_kernels.hip on the engine of gpsacq_engine.hpp.  Last "Observables": the time tag
 // (host only) and the gpsacq_observables* / gpsacq_fix_track_device entry points that run obs_kernels.hip, then "Carrier observables"
 // and "Velocity and clock drift": gpsacq_rate_observables*, gpsacq_sat_rates*, gpsacq_vel_batch*, gpsacq_pvt_track_device.  At the
-// end "Atmosphere, elevation mask and DOP": page 18 and the parameters (host only), gpsacq_sat_views*, gpsacq_fix_atm_batch*.
+// end "Atmosphere, elevation mask and DOP": page 18 and the parameters (host only), gpsacq_sat_views*, gpsacq_fix_atm_batch*, and
+// "Fix integrity": the chi-square thresholds (host only) and gpsacq_fix_raim_batch*, which run raim_kernels.hip.
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,7 @@
 #include "atm_launch.hpp"
 #include "nav_launch.hpp"
 #include "obs_launch.hpp"
+#include "raim_launch.hpp"
 
 using namespace acq;
 
@@ -665,5 +667,120 @@ extern "C" int gpsacq_fix_atm_last_ms(const gpsacq_engine* e, float* sat_state_m
         *sat_view_ms = 0.f;
         if (e->atm_views) HIPCHK(hipEventElapsedTime(sat_view_ms, e->atm_ev[2], e->atm_ev[3]));
     }
+    return GPSACQ_OK;
+}
+
+// ---- fix integrity: residual test and single-satellite exclusion (raim_kernels.hip) -----------------------------------------------
+namespace {
+// upper tail of the chi-square distribution at d degrees of freedom, the closed form for integer d
+double chi2_tail(int d, double x) {
+    const double h = 0.5 * x;
+    double sum = 0.0;
+    if (d % 2 == 0) {
+        double term = 1.0;  // h^j / j!
+        for (int j = 0; j < d / 2; ++j) {
+            sum += term;
+            term *= h / (double)(j + 1);
+        }
+        return std::exp(-h) * sum;
+    }
+    for (int j = 0; j < (d - 1) / 2; ++j) sum += std::pow(h, j + 0.5) / std::tgamma(j + 1.5);
+    return std::erfc(std::sqrt(h)) + std::exp(-h) * sum;
+}
+}  // namespace
+
+extern "C" int gpsacq_raim_default_params(double sigma_m, double p_fa, gpsacq_raim_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_raim_default_params: null argument");
+    if (!std::isfinite(sigma_m) || !(sigma_m > 0.0)) return fail(GPSACQ_ERR_ARG, "gpsacq_raim_default_params: sigma_m %g (must be finite and > 0)", sigma_m);
+    if (!(p_fa >= 1e-15) || !(p_fa <= 0.5)) return fail(GPSACQ_ERR_ARG, "gpsacq_raim_default_params: p_fa %g outside [1e-15, 0.5]", p_fa);
+    std::memset(p, 0, sizeof *p);
+    p->sigma_m = sigma_m;
+    p->p_fa = p_fa;
+    for (int d = 1; d <= GPSACQ_RAIM_MAX_DOF; ++d) {
+        double lo = 0.0, hi = 4000.0;  // the tail falls from 1 to 0 in between
+        for (int k = 0; k < 200; ++k) {
+            const double mid = 0.5 * (lo + hi);
+            if (chi2_tail(d, mid) > p_fa) lo = mid;
+            else hi = mid;
+        }
+        p->threshold[d - 1] = 0.5 * (lo + hi);
+    }
+    p->exclude = 1;
+    return GPSACQ_OK;
+}
+
+static int raim_check(const char* who, const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* obs, size_t n_fix,
+                      int sats_per_fix, const gpsacq_atm_params* atm_params, const gpsacq_raim_params* rp, const void* fix, const void* raim) {
+    if (int rc = atm_check(who, e, eph, n_eph, obs, n_fix, sats_per_fix, atm_params, fix)) return rc;
+    if (!raim) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (!rp) return fail(GPSACQ_ERR_ARG, "%s: raim params is NULL", who);
+    if (!std::isfinite(rp->sigma_m) || !(rp->sigma_m > 0.0)) return fail(GPSACQ_ERR_ARG, "%s: sigma_m %g (must be finite and > 0)", who, rp->sigma_m);
+    for (int k = 0; k < GPSACQ_RAIM_MAX_DOF; ++k)
+        if (!std::isfinite(rp->threshold[k]) || !(rp->threshold[k] > 0.0))
+            return fail(GPSACQ_ERR_ARG, "%s: threshold %d is %g (must be finite and > 0)", who, k, rp->threshold[k]);
+    if (rp->exclude != 0 && rp->exclude != 1) return fail(GPSACQ_ERR_ARG, "%s: exclude %d (must be 0 or 1)", who, (int)rp->exclude);
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_raim_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, size_t n_fix,
+                                            int sats_per_fix, const gpsacq_atm_params* atm_params, const gpsacq_raim_params* raim_params,
+                                            void* d_fix, void* d_dop, void* d_raim, int sync) {
+    if (int rc = raim_check("gpsacq_fix_raim_batch", e, eph, n_eph, d_obs, n_fix, sats_per_fix, atm_params, raim_params, d_fix, d_raim)) return rc;
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_raim_rows, e->raim_rows_cap, n_fix, e->stream)) return rc;
+    if (!d_dop) {  // the kernels always write it
+        if (int rc = grow(e->d_atm_dop, e->atm_dop_cap, n_fix, e->stream)) return rc;
+        d_dop = e->d_atm_dop;
+    }
+    for (auto& ev : e->raim_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    e->raim_timed = false;
+    const RaimArgs args{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, e->d_nav_state, n_fix, sats_per_fix, *atm_params, *raim_params,
+                        (gpsacq_fix*)d_fix, (gpsacq_fix_dop*)d_dop, (gpsacq_fix_raim*)d_raim, e->d_raim_rows};
+    HIPCHK(hipEventRecord(e->raim_ev[0], e->stream));
+    launch_sat_state(SatStateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_nav_state}, e->stream);
+    HIPCHK(hipEventRecord(e->raim_ev[1], e->stream));
+    launch_raim_detect(args, e->stream);
+    HIPCHK(hipEventRecord(e->raim_ev[2], e->stream));
+    launch_raim_exclude(args, e->stream);  // always: which rows were flagged is known on the device only
+    HIPCHK(hipEventRecord(e->raim_ev[3], e->stream));
+    HIPCHK(hipGetLastError());
+    e->raim_timed = true;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_raim_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs, size_t n_fix,
+                                     int sats_per_fix, const gpsacq_atm_params* atm_params, const gpsacq_raim_params* raim_params,
+                                     gpsacq_fix* fix_out, gpsacq_fix_dop* dop_out, gpsacq_fix_raim* raim_out) {
+    if (int rc = raim_check("gpsacq_fix_raim_batch", e, eph, n_eph, obs, n_fix, sats_per_fix, atm_params, raim_params, fix_out, raim_out)) return rc;
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    if (int rc = nav_check_weights("gpsacq_fix_raim_batch", obs, n_obs)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
+    if (int rc = grow(e->d_atm_dop, e->atm_dop_cap, n_fix, e->stream)) return rc;
+    if (int rc = grow(e->d_raim, e->raim_cap, n_fix, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    if (int rc = gpsacq_fix_raim_batch_device(e, eph, n_eph, e->d_nav_obs, n_fix, sats_per_fix, atm_params, raim_params, e->d_nav_fix,
+                                              e->d_atm_dop, e->d_raim, 0))
+        return rc;
+    HIPCHK(hipMemcpyAsync(fix_out, e->d_nav_fix, n_fix * sizeof(gpsacq_fix), hipMemcpyDeviceToHost, e->stream));
+    if (dop_out) HIPCHK(hipMemcpyAsync(dop_out, e->d_atm_dop, n_fix * sizeof(gpsacq_fix_dop), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(raim_out, e->d_raim, n_fix * sizeof(gpsacq_fix_raim), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_raim_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* detect_ms, float* exclude_ms) {
+    if (!e || !e->raim_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_raim_last_ms: no gpsacq_fix_raim_batch call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    HIPCHK(hipEventSynchronize(e->raim_ev[3]));
+    if (sat_state_ms) HIPCHK(hipEventElapsedTime(sat_state_ms, e->raim_ev[0], e->raim_ev[1]));
+    if (detect_ms) HIPCHK(hipEventElapsedTime(detect_ms, e->raim_ev[1], e->raim_ev[2]));
+    if (exclude_ms) HIPCHK(hipEventElapsedTime(exclude_ms, e->raim_ev[2], e->raim_ev[3]));
     return GPSACQ_OK;
 }

@@ -100,6 +100,12 @@ ATM_PARAMS_DTYPE = np.dtype([("alpha", "<f8", (4,)), ("beta", "<f8", (4,)), ("el
 SAT_VIEW_DTYPE = np.dtype([("az", "<f8"), ("el", "<f8"), ("iono_m", "<f8"), ("tropo_m", "<f8")])
 FIX_DOP_DTYPE = np.dtype([("used_mask", "<u4"), ("n_masked", "<i4"), ("gdop", "<f8"), ("pdop", "<f8"), ("hdop", "<f8"), ("vdop", "<f8"),
                           ("tdop", "<f8")])
+# fix integrity (include/gpsacq.h, "Fix integrity: residual test and single-satellite exclusion")
+RAIM_MAX_DOF = 8
+RAIM_NONE, RAIM_UNCHECKED, RAIM_PASS, RAIM_EXCLUDED, RAIM_FAILED = 0, 1, 2, 3, 4
+RAIM_PARAMS_DTYPE = np.dtype([("sigma_m", "<f8"), ("p_fa", "<f8"), ("threshold", "<f8", (RAIM_MAX_DOF,)), ("exclude", "<i4"), ("reserved", "<i4")])
+FIX_RAIM_DTYPE = np.dtype([("status", "<i4"), ("dof", "<i4"), ("excluded", "<i4"), ("n_candidates", "<i4"), ("stat_full", "<f8"), ("stat", "<f8"),
+                           ("threshold", "<f8")])
 
 
 class TrackParams(ctypes.Structure):
@@ -128,7 +134,8 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_track_nominal_word_iq8", "gpsacq_rate_observables", "gpsacq_rate_observables_device", "gpsacq_sat_rates",
            "gpsacq_sat_rates_device", "gpsacq_vel_batch", "gpsacq_vel_batch_device", "gpsacq_pvt_track_device", "gpsacq_velocity_last_ms",
            "gpsacq_iono_load", "gpsacq_atm_default_params", "gpsacq_sat_views", "gpsacq_sat_views_device", "gpsacq_fix_atm_batch",
-           "gpsacq_fix_atm_batch_device", "gpsacq_fix_atm_last_ms"]
+           "gpsacq_fix_atm_batch_device", "gpsacq_fix_atm_last_ms",
+           "gpsacq_raim_default_params", "gpsacq_fix_raim_batch", "gpsacq_fix_raim_batch_device", "gpsacq_fix_raim_last_ms"]
 
 _lib = None
 
@@ -358,6 +365,14 @@ def load_library(path=None):
     lib.gpsacq_fix_atm_batch_device.restype = ctypes.c_int
     lib.gpsacq_fix_atm_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
     lib.gpsacq_fix_atm_last_ms.restype = ctypes.c_int
+    lib.gpsacq_raim_default_params.argtypes = [ctypes.c_double, ctypes.c_double, vp]
+    lib.gpsacq_raim_default_params.restype = ctypes.c_int
+    lib.gpsacq_fix_raim_batch.argtypes = [vp, vp, ctypes.c_int, vp, sz, ctypes.c_int, vp, vp, vp, vp, vp]
+    lib.gpsacq_fix_raim_batch.restype = ctypes.c_int
+    lib.gpsacq_fix_raim_batch_device.argtypes = [vp, vp, ctypes.c_int, vp, sz, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_fix_raim_batch_device.restype = ctypes.c_int
+    lib.gpsacq_fix_raim_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
+    lib.gpsacq_fix_raim_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -451,6 +466,16 @@ def atm_params(iono=None, elev_mask=None, flags=None):
         out["elev_mask"] = float(elev_mask)
     if flags is not None:
         out["flags"] = int(flags)
+    return out
+
+
+def raim_params(sigma_m, p_fa=1e-3):
+    """gpsacq_raim_default_params: a RAIM_PARAMS_DTYPE record of shape (1,) -- sigma_m the standard deviation (metres) of a
+    pseudorange of weight 1, threshold[d - 1] the chi-square quantile with upper tail p_fa at d degrees of freedom, exclude = 1.
+    The caller may overwrite thresholds and exclude; the entry points that take the record check it."""
+    lib = load_library()
+    out = np.zeros(1, dtype=RAIM_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_raim_default_params(float(sigma_m), float(p_fa), out.ctypes.data_as(ctypes.c_void_p)))
     return out
 
 
@@ -859,6 +884,45 @@ class Engine:
         """Device milliseconds of the last fix_atm* call: (satellite-state kernel, corrected-fix kernel, view kernel or 0)."""
         t = [ctypes.c_float() for _ in range(3)]
         _check(self._lib, self._lib.gpsacq_fix_atm_last_ms(self._h, *[ctypes.byref(x) for x in t]))
+        return tuple(x.value for x in t)
+
+    # ---- fix integrity ---------------------------------------------------------------------
+    @staticmethod
+    def _raim_params(params):
+        if params is None:
+            return None, None
+        pr = np.array(params, dtype=RAIM_PARAMS_DTYPE).reshape(1).copy()
+        return pr, pr.ctypes.data_as(ctypes.c_void_p)
+
+    def fix_raim(self, eph, obs, atm_params, raim_params):
+        """gpsacq_fix_raim_batch: fix_atm() followed by the chi-square test of its residuals against raim_params (raim_params())
+        and, where the test fails, the exclusion of the one observation whose removal mends the fix.  Returns (FIX_DTYPE [n_fix],
+        FIX_DOP_DTYPE [n_fix], FIX_RAIM_DTYPE [n_fix])."""
+        ep, ob = self._nav_arrays(eph, obs)
+        if ob.ndim != 2:
+            raise ValueError("obs must be [n_fix][sats_per_fix]")
+        ar, ap = self._atm_params(atm_params)
+        rr, rp = self._raim_params(raim_params)
+        out = np.zeros(ob.shape[0], dtype=FIX_DTYPE)
+        dp = np.zeros(ob.shape[0], dtype=FIX_DOP_DTYPE)
+        rm = np.zeros(ob.shape[0], dtype=FIX_RAIM_DTYPE)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_fix_raim_batch(self._h, p(ep), int(ep.size), p(ob), int(ob.shape[0]), int(ob.shape[1]), ap, rp, p(out),
+                                                          p(dp), p(rm)))
+        return out, dp, rm
+
+    def fix_raim_device(self, eph, d_obs_ptr, n_fix, sats_per_fix, atm_params, raim_params, d_fix_ptr, d_dop_ptr, d_raim_ptr, sync=True):
+        """gpsacq_fix_raim_batch_device: device pointers for the observations and the three outputs; d_dop_ptr may be None."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        ar, ap = self._atm_params(atm_params)
+        rr, rp = self._raim_params(raim_params)
+        _check(self._lib, self._lib.gpsacq_fix_raim_batch_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_obs_ptr, int(n_fix),
+                                                                 int(sats_per_fix), ap, rp, d_fix_ptr, d_dop_ptr, d_raim_ptr, 1 if sync else 0))
+
+    def fix_raim_last_ms(self):
+        """Device milliseconds of the last fix_raim* call: (satellite-state kernel, detect kernel, exclude kernel)."""
+        t = [ctypes.c_float() for _ in range(3)]
+        _check(self._lib, self._lib.gpsacq_fix_raim_last_ms(self._h, *[ctypes.byref(x) for x in t]))
         return tuple(x.value for x in t)
 
     # ---- observables ----------------------------------------------------------------------

@@ -1062,7 +1062,7 @@ GPSACQ_API int gpsacq_velocity_last_ms(const gpsacq_engine* e, float* carrier_ac
  *
  * OUT OF SCOPE.  gps_track and the *_track_device chains stay on the plain fix: the signal generator puts no atmosphere on its
  * captures, where a corrected fix would only be worse, and a real capture needs up to 12.5 minutes for a page 18.  The UTC
- * parameters.  Dropping masked satellites from k_vel (the caller can clear `valid` from used_mask).  RAIM.
+ * parameters.  Dropping masked satellites from k_vel (the caller can clear `valid` from used_mask).
  */
 typedef struct { int32_t valid; int32_t tow; double alpha[4]; double beta[4]; } gpsacq_iono;   /* 72 bytes */
 GPSACQ_API int gpsacq_iono_load(gpsacq_iono* io, const gpsacq_subframe* sf, int n);
@@ -1087,6 +1087,90 @@ GPSACQ_API int gpsacq_fix_atm_batch_device(gpsacq_engine* e, const gpsacq_epheme
 /* device time of the kernels of the last gpsacq_fix_atm_batch* call on this engine, milliseconds (HIP events on its stream; waits
  * for them); sat_view_ms reads 0 when that call asked for no views.  Any pointer may be NULL. */
 GPSACQ_API int gpsacq_fix_atm_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* fix_atm_ms, float* sat_view_ms);
+
+/*
+ * ---- Fix integrity: residual test and single-satellite exclusion ----------------------------------------------------------------
+ *
+ * Every solver above trusts every observation it is given: one transmit time that is off (a slipped code chip, a wrong time tag, a
+ * cross-correlation lock) moves a fix by tens to hundreds of metres and nothing in the output says so.  The reference's answer is
+ * LoadReplicas() (c/solve.cpp), which strips channels whose glitch counters moved; this section is our own: receiver autonomous
+ * integrity monitoring (RAIM) on top of CORRECTED FIX -- a chi-square test of the residuals against an expected noise level and,
+ * where it fails, the exclusion of the one observation whose removal explains the failure best.  THE MODEL; the kernels
+ * (csrc/raim_kernels.hip: k_raim_detect, k_raim_exclude) and tests/raim_ref.py are both written from this text.  Nothing of the
+ * sections above changes: k_sat_state, k_fix, k_vel, k_sat_view, k_fix_atm and their entry points are what they were.
+ *
+ * PARAMETERS.  sigma_m is the standard deviation, in metres, of a pseudorange whose observation has weight 1; an observation of
+ * weight w has variance sigma_m^2 / w.  threshold[d - 1] is the chi-square quantile with upper tail p_fa at d degrees of freedom.
+ * gpsacq_raim_default_params (host only) computes the table from the closed-form tail for integer d; with h = x / 2
+ *     even d:  Q_d(x) = e^-h sum_{j < d/2} h^j / j!
+ *     odd d:   Q_d(x) = erfc(sqrt h) + e^-h sum_{j < (d-1)/2} h^(j + 1/2) / Gamma(j + 3/2)
+ * and Q_d(x) = p_fa bisected on [0, 4000], 200 halvings; it sets exclude = 1 and reserved = 0 and keeps sigma_m and p_fa.  sigma_m
+ * must be finite and > 0 and p_fa in [1e-15, 0.5]; anything else, or NULL: GPSACQ_ERR_ARG.  The kernels read only sigma_m,
+ * threshold[] and exclude, so a caller may write thresholds of their own.  Every entry point below checks its parameters: sigma_m
+ * and all eight thresholds finite and > 0, exclude 0 or 1; else GPSACQ_ERR_ARG and nothing is launched.  For p_fa = 1e-3 the
+ * table is 10.827566170662733, 13.815510557964274, 16.26623619623813, 18.46682695290317, 20.515005652432876, 22.457744484825323,
+ * 24.321886347856854, 26.12448155837614.
+ *
+ * STATISTIC, at a converged state (x, y, z, t_rx) over a satellite set S with held delays D_s:
+ *     T(S) = sum_{s in S} w_s r_s^2 / sigma_m^2,       r_s = c (t_rx - t_tx,s) - D_s - range_s
+ * with the residuals recomputed AT the state after the last step (not gpsacq_fix.rms's "residuals the last step was made from").
+ * dof(S) = (number of s in S with w_s > 0) - 4.  Weight-0 observations stay in the solution as they do in FIX: they add nothing
+ * to T, do not count, and are never exclusion candidates.
+ *
+ * PER ROW:
+ *   1. FULL.  CORRECTED FIX, stages 0-2 of the section above, unchanged: status, the set S after the mask, the state, and the
+ *      delays of the last round (with flags == 0 and nothing masked: zeros).  Not GPSACQ_FIX_OK: gpsacq_fix and gpsacq_fix_dop as
+ *      gpsacq_fix_atm_batch writes them, raim status GPSACQ_RAIM_NONE.
+ *   2. TEST.  d = dof(S).  d < 1: GPSACQ_RAIM_UNCHECKED, the outputs are the full solution.  T(S) <= threshold[d - 1]:
+ *      GPSACQ_RAIM_PASS.
+ *   3. EXCLUDE.  If exclude == 0 or d < 2: GPSACQ_RAIM_FAILED, the outputs are the full solution.  Otherwise, for every k in S
+ *      with w_k > 0, FIX's Newton iteration over S \ {k}: from the full solution's state, with the full solution's delays held,
+ *      with FIX's step rule and failure tests.  A candidate that fails is not a candidate.  T_k is the statistic at its converged
+ *      state.  The winner is the smallest T_k, on a tie the lowest k.  No candidate, or T_k > threshold[d - 2]:
+ *      GPSACQ_RAIM_FAILED, the outputs are the full solution.
+ *   4. FINAL.  From the winner's state GPSACQ_ATM_ROUNDS rounds over S \ {k}, stage 2 of CORRECTED FIX: delays at the current
+ *      state, then Newton from the current state.  A failure here: fix status GPSACQ_FIX_NO_CONVERGE (every double 0, n_used and
+ *      iterations stay), raim status GPSACQ_RAIM_NONE with excluded = k.  If flags == 0 and the elevation mask dropped nothing,
+ *      the winner's state is final and no round runs.  The mask is not evaluated again.  Status GPSACQ_RAIM_EXCLUDED;
+ *      gpsacq_fix holds the final state with n_used one less; `iterations` counts the steps of FULL, of the winning candidate and
+ *      of FINAL (not the losing candidates'); gpsacq_fix_dop has bit k cleared in used_mask and its DOP over the final set.
+ *
+ * gpsacq_fix_raim: dof, stat and threshold describe the solution that was output -- PASS and FAILED: d, T(S), threshold[d - 1];
+ * UNCHECKED: d (0 or less), T(S), 0; EXCLUDED: d - 1, T_k recomputed at the FINAL state with FINAL's delays, threshold[d - 2].
+ * stat_full is T(S) of step 2.  excluded is the observation's column in the row, or -1.  n_candidates is the number of subset
+ * solves that converged, 0 if step 3 did not run.  GPSACQ_RAIM_NONE: every other field 0, excluded -1 unless FINAL failed.
+ *
+ * gpsacq_fix_raim_batch: k_sat_state as it is; k_raim_detect, one lane per fix (k_fix_atm's algorithm plus the statistic and the
+ * test; it writes fix, dop and raim of every row, and for the rows that go on to step 3 a record in engine scratch: state, t0,
+ * set and the twelve delays); k_raim_exclude, sixteen lanes per fix, lane k < 12 solving the subset without observation k, the
+ * minimum found by a reduction across the sixteen lanes, the winning lane running FINAL and overwriting the row's three records.
+ * k_raim_exclude is always launched (whether a row was flagged is known on the device only); a group whose row needs no exclusion
+ * returns at once, so exclude_ms is small but never 0.  Arguments, scratch, stream, events and weights as gpsacq_fix_atm_batch*:
+ * the host form refuses a negative or non-finite weight, the _device form skips such an observation; dop_out (d_dop) may be NULL,
+ * fix and raim may not; either params pointer NULL is GPSACQ_ERR_ARG.  Argument errors launch nothing and write nothing.
+ *
+ * OUT OF SCOPE.  More than one exclusion per fix.  Protection levels.  k_vel: the caller clears `valid` from used_mask, as before.
+ * gps_track and the *_track_device chains: nobody has measured the pseudorange sigma of our tracked channels, and a threshold
+ * without it is a guess.
+ */
+#define GPSACQ_RAIM_MAX_DOF 8     /* GPSACQ_FIX_MAX_SATS - 4 */
+typedef struct { double sigma_m; double p_fa; double threshold[GPSACQ_RAIM_MAX_DOF]; int32_t exclude; int32_t reserved; } gpsacq_raim_params; /* 88 bytes */
+GPSACQ_API int gpsacq_raim_default_params(double sigma_m, double p_fa, gpsacq_raim_params* p);   /* host only */
+#define GPSACQ_RAIM_NONE 0        /* no fix to judge */
+#define GPSACQ_RAIM_UNCHECKED 1   /* no redundancy: dof < 1 */
+#define GPSACQ_RAIM_PASS 2
+#define GPSACQ_RAIM_EXCLUDED 3    /* the test failed, one observation was dropped and the rest pass */
+#define GPSACQ_RAIM_FAILED 4      /* the test failed and no single exclusion mends it (or none was tried) */
+typedef struct { int32_t status, dof, excluded, n_candidates; double stat_full, stat, threshold; } gpsacq_fix_raim;   /* 40 bytes */
+GPSACQ_API int gpsacq_fix_raim_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs, size_t n_fix,
+                                     int sats_per_fix, const gpsacq_atm_params* atm_params, const gpsacq_raim_params* raim_params,
+                                     gpsacq_fix* fix_out, gpsacq_fix_dop* dop_out, gpsacq_fix_raim* raim_out);
+GPSACQ_API int gpsacq_fix_raim_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, size_t n_fix,
+                                            int sats_per_fix, const gpsacq_atm_params* atm_params, const gpsacq_raim_params* raim_params,
+                                            void* d_fix, void* d_dop, void* d_raim, int sync);
+/* device time of the kernels of the last gpsacq_fix_raim_batch* call on this engine, milliseconds (HIP events on its stream; waits
+ * for them): k_sat_state, k_raim_detect, k_raim_exclude.  Any pointer may be NULL. */
+GPSACQ_API int gpsacq_fix_raim_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* detect_ms, float* exclude_ms);
 
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);
