@@ -14,6 +14,7 @@
 #include "nav_launch.hpp"
 #include "obs_launch.hpp"
 #include "raim_launch.hpp"
+#include "smooth_launch.hpp"
 
 // sets this thread's gpsacq_last_error() text from a printf format and returns `code` (gpsacq_engine.cpp)
 int fail(int code, const char* fmt, ...);
@@ -139,6 +140,19 @@ struct gpsacq_engine {
     size_t raim_cap = 0;
     hipEvent_t raim_ev[4] = {};  // before k_sat_state, between it and k_raim_detect, after k_raim_detect, after k_raim_exclude
     bool raim_timed = false;
+    // carrier-smoothed observables (gpsacq_smooth_observables*, gpsacq_fix_smooth_track_device)
+    acq::SmoothChan* d_smooth_chan = nullptr;
+    size_t smooth_chan_cap = 0;
+    int64_t* d_smooth_lock = nullptr;  // k_lock_acc's two outputs: [2][n_chans][max_epochs + 1]
+    size_t smooth_lock_cap = 0;
+    uint64_t* d_smooth_q = nullptr;  // channel-major 64-bit rows: Z and P [n_chans][n_fix] each, then S [n_chans][n_fix + 1]
+    size_t smooth_q_cap = 0;
+    int32_t* d_smooth_w = nullptr;  // channel-major 32-bit rows, [n_chans][n_fix] each: t, the state, s_i
+    size_t smooth_w_cap = 0;
+    gpsacq_smooth_info* d_smooth_info = nullptr;  // host-buffer form
+    size_t smooth_info_cap = 0;
+    hipEvent_t smooth_ev[5] = {};  // before k_lock_acc, then after each of k_lock_acc, k_cmc, k_smooth_scan, k_smooth_out
+    bool smooth_timed = false;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;

@@ -5,6 +5,8 @@
 // and "Velocity and clock drift": gpsacq_rate_observables*, gpsacq_sat_rates*, gpsacq_vel_batch*, gpsacq_pvt_track_device.  At the
 // end "Atmosphere, elevation mask and DOP": page 18 and the parameters (host only), gpsacq_sat_views*, gpsacq_fix_atm_batch*, and
 // "Fix integrity": the chi-square thresholds (host only) and gpsacq_fix_raim_batch*, which run raim_kernels.hip.
+// Between the velocity and the atmosphere: "Carrier-smoothed observables", gpsacq_smooth_observables* and
+// gpsacq_fix_smooth_track_device, which run smooth_kernels.hip after k_code_pos and k_carrier_acc.
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -17,6 +19,7 @@
 #include "nav_launch.hpp"
 #include "obs_launch.hpp"
 #include "raim_launch.hpp"
+#include "smooth_launch.hpp"
 
 using namespace acq;
 
@@ -227,9 +230,9 @@ static int obs_check(const char* who, const gpsacq_engine* e, const void* record
     return records_check(who, e, records, max_epochs, n_epochs, chans, n_chans, first_rx_sample, rx_step, n_fix);
 }
 
-// both kernels on the engine's stream; every argument has been checked
-static int obs_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
-                       const gpsacq_time_tag* tags, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, void* d_obs) {
+// the call's channels as the kernels read them into e->d_obs_chan, then k_code_pos between obs_ev[0] and obs_ev[1]
+static int code_pos_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
+                            const gpsacq_time_tag* tags, int n_chans) {
     ObsChan tab[GPSACQ_FIX_MAX_SATS];
     for (int c = 0; c < n_chans; ++c) {
         ObsChan& d = tab[c];
@@ -248,6 +251,13 @@ static int obs_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, 
     HIPCHK(hipEventRecord(e->obs_ev[0], e->stream));
     launch_code_pos(CodePosArgs{e->d_obs_chan, (const gpsacq_track_record*)d_records, max_epochs, e->d_obs_pos}, n_chans, e->stream);
     HIPCHK(hipEventRecord(e->obs_ev[1], e->stream));
+    return GPSACQ_OK;
+}
+
+// both kernels on the engine's stream; every argument has been checked
+static int obs_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
+                       const gpsacq_time_tag* tags, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, void* d_obs) {
+    if (int rc = code_pos_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, n_chans)) return rc;
     launch_observe(ObserveArgs{e->d_obs_chan, (const gpsacq_track_record*)d_records, e->d_obs_pos, max_epochs, n_chans, first_rx_sample, rx_step,
                                n_fix, (gpsacq_obs*)d_obs},
                    e->stream);
@@ -320,10 +330,9 @@ static int rate_check(const char* who, const gpsacq_engine* e, const void* recor
     return GPSACQ_OK;
 }
 
-// both kernels on the engine's stream; every argument has been checked
-static int rate_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
-                        const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, uint64_t avg_samples,
-                        void* d_rate_obs) {
+// the call's channels as the carrier kernels read them into e->d_rate_chan, then k_carrier_acc between rate_ev[0] and rate_ev[1]
+static int carrier_acc_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
+                               const uint32_t* nom_words, int n_chans) {
     RateChan tab[GPSACQ_FIX_MAX_SATS];
     for (int c = 0; c < n_chans; ++c) tab[c] = RateChan{chans[c].next_sample, n_epochs[c], nom_words[c]};
     if (int rc = grow(e->d_rate_chan, e->rate_chan_cap, (size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
@@ -336,6 +345,14 @@ static int rate_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs,
     HIPCHK(hipEventRecord(e->rate_ev[0], e->stream));
     launch_carrier_acc(CarrierAccArgs{e->d_rate_chan, (const gpsacq_track_record*)d_records, max_epochs, e->d_rate_acc}, n_chans, e->stream);
     HIPCHK(hipEventRecord(e->rate_ev[1], e->stream));
+    return GPSACQ_OK;
+}
+
+// both kernels on the engine's stream; every argument has been checked
+static int rate_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
+                        const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, uint64_t avg_samples,
+                        void* d_rate_obs) {
+    if (int rc = carrier_acc_enqueue(e, d_records, max_epochs, n_epochs, chans, nom_words, n_chans)) return rc;
     launch_observe_rate(ObserveRateArgs{e->d_rate_chan, (const gpsacq_track_record*)d_records, e->d_rate_acc, max_epochs, n_chans, first_rx_sample,
                                         rx_step, avg_samples, e->p.fs, n_fix, (gpsacq_rate_obs*)d_rate_obs},
                         e->stream);
@@ -509,6 +526,155 @@ extern "C" int gpsacq_velocity_last_ms(const gpsacq_engine* e, float* carrier_ac
     if (observe_rate_ms) *observe_rate_ms = t[1];
     if (sat_rate_ms) *sat_rate_ms = t[2];
     if (vel_ms) *vel_ms = t[3];
+    return GPSACQ_OK;
+}
+
+// ---- carrier-smoothed observables (smooth_kernels.hip) --------------------------------------------------------------------
+extern "C" int gpsacq_smooth_default_params(gpsacq_smooth_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_smooth_default_params: null argument");
+    std::memset(p, 0, sizeof *p);
+    p->window = 1000;
+    p->lock_epochs = 20;
+    p->lock_num = 1, p->lock_den = 2;
+    p->jump = (int64_t)385 << 32;  // a quarter chip in carrier cycles
+    return GPSACQ_OK;
+}
+
+// the caller's parameters or the defaults into *out, checked
+static int smooth_params(const char* who, const gpsacq_smooth_params* params, gpsacq_smooth_params* out) {
+    if (!params) return gpsacq_smooth_default_params(out);
+    *out = *params;
+    if (out->window < 1 || out->window > 65536) return fail(GPSACQ_ERR_ARG, "%s: window %d outside 1 .. 65536", who, out->window);
+    if (out->lock_epochs < 0 || out->lock_epochs > 1024) return fail(GPSACQ_ERR_ARG, "%s: lock_epochs %d outside 0 .. 1024", who, out->lock_epochs);
+    if (out->lock_num < 1 || out->lock_num > out->lock_den || out->lock_den > 1024)
+        return fail(GPSACQ_ERR_ARG, "%s: lock_num / lock_den %d / %d outside 1 <= num <= den <= 1024", who, out->lock_num, out->lock_den);
+    if (out->jump < 0) return fail(GPSACQ_ERR_ARG, "%s: jump must not be negative", who);
+    return GPSACQ_OK;
+}
+
+static int smooth_check(const char* who, const gpsacq_engine* e, const void* records, int max_epochs, const int32_t* n_epochs,
+                        const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, const uint32_t* nom_words, int n_chans,
+                        uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, const gpsacq_smooth_params* params, gpsacq_smooth_params* checked) {
+    if (!tags || !nom_words) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (int rc = records_check(who, e, records, max_epochs, n_epochs, chans, n_chans, first_rx_sample, rx_step, n_fix)) return rc;
+    return smooth_params(who, params, checked);
+}
+
+// k_code_pos, k_carrier_acc and the four smoothing kernels on the engine's stream; every argument has been checked
+static int smooth_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
+                          const gpsacq_time_tag* tags, const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample, uint64_t rx_step,
+                          size_t n_fix, const gpsacq_smooth_params& sp, void* d_obs, void* d_info) {
+    SmoothChan tab[GPSACQ_FIX_MAX_SATS];
+    for (int c = 0; c < n_chans; ++c) {
+        SmoothChan& d = tab[c];
+        d.next_sample = chans[c].next_sample;
+        d.n = n_epochs[c];
+        d.first_epoch = (int32_t)((uint32_t)chans[c].epoch - (uint32_t)n_epochs[c]);
+        d.tag_epoch = tags[c].epoch, d.tag_ms = tags[c].ms, d.tag_eph = tags[c].eph, d.tag_valid = tags[c].valid;
+        d.cw = (uint32_t)((uint64_t)chans[c].ca_nom >> 32);
+        d.nom_word = nom_words[c];
+    }
+    const size_t row = (size_t)max_epochs + 1, nc = (size_t)n_chans;
+    if (int rc = grow(e->d_smooth_chan, e->smooth_chan_cap, (size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
+    if (int rc = grow(e->d_smooth_lock, e->smooth_lock_cap, 2 * nc * row, e->stream)) return rc;
+    if (int rc = grow(e->d_smooth_q, e->smooth_q_cap, nc * (3 * n_fix + 1), e->stream)) return rc;
+    if (int rc = grow(e->d_smooth_w, e->smooth_w_cap, nc * 3 * n_fix, e->stream)) return rc;
+    for (auto& ev : e->smooth_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    // pageable source: the copy has left `tab` when the call returns
+    HIPCHK(hipMemcpyAsync(e->d_smooth_chan, tab, nc * sizeof(SmoothChan), hipMemcpyHostToDevice, e->stream));
+    // pos_t and A_t into the scratch the observables use; their second kernels do not run, so those times read 0
+    if (int rc = code_pos_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, n_chans)) return rc;
+    HIPCHK(hipEventRecord(e->obs_ev[2], e->stream));
+    e->obs_timed = true;
+    if (int rc = carrier_acc_enqueue(e, d_records, max_epochs, n_epochs, chans, nom_words, n_chans)) return rc;
+    HIPCHK(hipEventRecord(e->rate_ev[2], e->stream));
+    e->rate_timed = true;
+    const gpsacq_track_record* rec = (const gpsacq_track_record*)d_records;
+    int64_t *lock_n = e->d_smooth_lock, *lock_d = e->d_smooth_lock + nc * row;
+    uint64_t *z = e->d_smooth_q, *p = z + nc * n_fix, *sum = p + nc * n_fix;
+    int32_t *t = e->d_smooth_w, *state = t + nc * n_fix, *seg = state + nc * n_fix;
+    e->smooth_timed = false;
+    HIPCHK(hipEventRecord(e->smooth_ev[0], e->stream));
+    if (sp.lock_epochs > 0) launch_lock_acc(LockAccArgs{e->d_smooth_chan, rec, max_epochs, lock_n, lock_d}, n_chans, e->stream);
+    HIPCHK(hipEventRecord(e->smooth_ev[1], e->stream));
+    launch_cmc(CmcArgs{e->d_smooth_chan, rec, e->d_obs_pos, e->d_rate_acc, lock_n, lock_d, max_epochs, n_chans, first_rx_sample, rx_step, n_fix,
+                       sp.lock_epochs, sp.lock_num, sp.lock_den, sp.invert, z, p, t, state},
+               e->stream);
+    HIPCHK(hipEventRecord(e->smooth_ev[2], e->stream));
+    launch_smooth_scan(SmoothScanArgs{z, state, n_fix, sp.jump, sum, seg}, n_chans, e->stream);
+    HIPCHK(hipEventRecord(e->smooth_ev[3], e->stream));
+    launch_smooth_out(SmoothOutArgs{e->d_smooth_chan, z, p, t, state, sum, seg, n_chans, n_fix, sp.window, (gpsacq_obs*)d_obs,
+                                    (gpsacq_smooth_info*)d_info},
+                      e->stream);
+    HIPCHK(hipEventRecord(e->smooth_ev[4], e->stream));
+    HIPCHK(hipGetLastError());
+    e->smooth_timed = true;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_smooth_observables_device(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs,
+                                                const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, const uint32_t* nom_words,
+                                                int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix,
+                                                const gpsacq_smooth_params* params, void* d_obs, void* d_info, int sync) {
+    gpsacq_smooth_params sp;
+    if (int rc = smooth_check("gpsacq_smooth_observables", e, d_records, max_epochs, n_epochs, chans, tags, nom_words, n_chans, first_rx_sample, rx_step, n_fix, params, &sp)) return rc;
+    if (!d_obs) return fail(GPSACQ_ERR_ARG, "gpsacq_smooth_observables: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = smooth_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, nom_words, n_chans, first_rx_sample, rx_step, n_fix, sp, d_obs, d_info)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_smooth_observables(gpsacq_engine* e, const gpsacq_track_record* records, int max_epochs, const int32_t* n_epochs,
+                                         const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, const uint32_t* nom_words, int n_chans,
+                                         uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, const gpsacq_smooth_params* params,
+                                         gpsacq_obs* obs, gpsacq_smooth_info* info) {
+    gpsacq_smooth_params sp;
+    if (int rc = smooth_check("gpsacq_smooth_observables", e, records, max_epochs, n_epochs, chans, tags, nom_words, n_chans, first_rx_sample, rx_step, n_fix, params, &sp)) return rc;
+    if (!obs) return fail(GPSACQ_ERR_ARG, "gpsacq_smooth_observables: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_obs = n_fix * (size_t)n_chans;
+    if (int rc = grow(e->d_obs_rec, e->obs_rec_cap, (size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
+    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    if (info)
+        if (int rc = grow(e->d_smooth_info, e->smooth_info_cap, n_obs, e->stream)) return rc;
+    for (int c = 0; c < n_chans; ++c)  // the rows keep their stride; only the records that exist travel
+        if (n_epochs[c] > 0)
+            HIPCHK(hipMemcpyAsync(e->d_obs_rec + (size_t)c * max_epochs, records + (size_t)c * max_epochs,
+                                  (size_t)n_epochs[c] * sizeof(gpsacq_track_record), hipMemcpyHostToDevice, e->stream));
+    if (int rc = smooth_enqueue(e, e->d_obs_rec, max_epochs, n_epochs, chans, tags, nom_words, n_chans, first_rx_sample, rx_step, n_fix, sp, e->d_nav_obs,
+                                info ? e->d_smooth_info : nullptr))
+        return rc;
+    HIPCHK(hipMemcpyAsync(obs, e->d_nav_obs, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
+    if (info) HIPCHK(hipMemcpyAsync(info, e->d_smooth_info, n_obs * sizeof(gpsacq_smooth_info), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_smooth_track_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_records, int max_epochs,
+                                              const int32_t* n_epochs, const gpsacq_track_chan* chans, const gpsacq_time_tag* tags,
+                                              const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix,
+                                              const gpsacq_smooth_params* params, void* d_obs, void* d_info, void* d_fix, int sync) {
+    gpsacq_smooth_params sp;
+    if (int rc = smooth_check("gpsacq_fix_smooth_track", e, d_records, max_epochs, n_epochs, chans, tags, nom_words, n_chans, first_rx_sample, rx_step, n_fix, params, &sp)) return rc;
+    if (!eph || n_eph <= 0 || !d_fix) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_smooth_track: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (!d_obs) {
+        if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_fix * (size_t)n_chans, e->stream)) return rc;
+        d_obs = e->d_nav_obs;
+    }
+    if (int rc = smooth_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, nom_words, n_chans, first_rx_sample, rx_step, n_fix, sp, d_obs, d_info)) return rc;
+    return gpsacq_fix_batch_device(e, eph, n_eph, d_obs, n_fix, n_chans, d_fix, sync);
+}
+
+extern "C" int gpsacq_smooth_last_ms(const gpsacq_engine* e, float* lock_acc_ms, float* cmc_ms, float* scan_ms, float* out_ms) {
+    if (!e || !e->smooth_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_smooth_last_ms: no gpsacq_smooth_observables call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    HIPCHK(hipEventSynchronize(e->smooth_ev[4]));
+    float* out[4] = {lock_acc_ms, cmc_ms, scan_ms, out_ms};
+    for (int k = 0; k < 4; ++k)
+        if (out[k]) HIPCHK(hipEventElapsedTime(out[k], e->smooth_ev[k], e->smooth_ev[k + 1]));
     return GPSACQ_OK;
 }
 

@@ -14,6 +14,11 @@
 // With GPSACQ_VELOCITY=1 in the environment every fix whose velocity could be solved (gpsacq_rate_observables over half a second of
 // samples centred on the instant + gpsacq_vel_batch) is followed by a second line; without it the output is unchanged:
 //     vel tow T ve E vn N vu U drift D n_used N rms R           (m/s east, north, up; drift of the sampling clock, parts in 1)
+// With GPSACQ_SMOOTH_MS=W (1 .. 65536) the fixes are made from carrier-smoothed observations (gpsacq_smooth_observables): instants
+// a thousandth of a second of samples apart from the first record every channel has, a window of W instants, the fix of every
+// 1000th instant -- the same once-a-second instants -- in the same format, and after the fixes one line per channel with the
+// scatter of the code against the carrier over the full windows (the measured pseudorange sigma, metres):
+//     sigma PRN P code_sigma_m S full N
 //
 // With GPSACQ_INPUT=iq_u8|iq_s8 in the environment FILE is an 8-bit IQ capture (rtl-sdr / HackRF, README.md:83-115), read the way
 // gps_test reads it (host/search_api.cpp: GPSACQ_MIX_HZ, GPSACQ_IQ_KEEP_DC, GPSACQ_IQ_MULTIBIT, GPSACQ_IQ_COMPLEX; the mean of the
@@ -203,21 +208,44 @@ int main(int argc, char** argv) {
             const size_t n_fix = (size_t)((to - 1 - first_rx) / step) + 1;
             std::vector<gpsacq_obs> obs(n_fix * m);
             std::vector<gpsacq_fix> fix(n_fix);
-            rc = gpsacq_observables(e, rec.data(), max_epochs, fn.data(), fch.data(), tags.data(), (int)m, first_rx, step, n_fix, obs.data());
+            // the word of zero Doppler: what lo_nom holds, except for multi-bit channels, which keep their start word there
+            std::vector<uint32_t> nom(m);
+            uint32_t iq_word = 0;
+            const bool want_vel = env_int("GPSACQ_VELOCITY", 0) != 0;
+            const int smooth_ms = env_int("GPSACQ_SMOOTH_MS", 0);
+            if (iq && iqin.multibit && (want_vel || smooth_ms > 0)) rc = gpsacq_track_nominal_word_iq8(e, &iqin, &iq_word);
+            for (size_t k = 0; k < m; ++k) nom[k] = iq && iqin.multibit ? iq_word : (uint32_t)((uint64_t)fch[k].lo_nom >> 32);
+            const uint64_t ms_step = step / 1000;
+            std::vector<gpsacq_smooth_info> sinfo;
+            size_t n_ms = 0;
+            if (rc == 0 && smooth_ms > 0 && ms_step > 0) {
+                // instants a millisecond apart that hit every whole second: back from the first one to the start of the records
+                const uint64_t back = (first_rx - from) / ms_step;
+                const uint64_t start = first_rx - back * ms_step;
+                n_ms = (size_t)((to - 1 - start) / ms_step) + 1;
+                gpsacq_smooth_params sp;
+                gpsacq_smooth_default_params(&sp);
+                sp.window = smooth_ms;
+                std::vector<gpsacq_obs> sobs(n_ms * m);
+                sinfo.resize(n_ms * m);
+                rc = gpsacq_smooth_observables(e, rec.data(), max_epochs, fn.data(), fch.data(), tags.data(), nom.data(), (int)m, start, ms_step, n_ms,
+                                               &sp, sobs.data(), sinfo.data());
+                for (size_t k = 0; rc == 0 && k < n_fix; ++k) {
+                    const size_t i = (size_t)back + k * 1000;
+                    if (i < n_ms) std::memcpy(&obs[k * m], &sobs[i * m], m * sizeof(gpsacq_obs));
+                    else std::memset(&obs[k * m], 0, m * sizeof(gpsacq_obs));
+                }
+            } else if (rc == 0) {
+                rc = gpsacq_observables(e, rec.data(), max_epochs, fn.data(), fch.data(), tags.data(), (int)m, first_rx, step, n_fix, obs.data());
+            }
             if (rc == 0) rc = gpsacq_fix_batch(e, ephs.data(), (int)ephs.size(), obs.data(), n_fix, (int)m, fix.data());
             if (rc) {
                 std::fprintf(stderr, "gps_track: %d: %s\n", rc, gpsacq_last_error());
                 gpsacq_destroy(e);
                 return rc;
             }
-            const bool want_vel = env_int("GPSACQ_VELOCITY", 0) != 0;
             std::vector<gpsacq_vel> vel;
             if (want_vel) {
-                // the word of zero Doppler: what lo_nom holds, except for multi-bit channels, which keep their start word there
-                std::vector<uint32_t> nom(m);
-                uint32_t iq_word = 0;
-                if (iq && iqin.multibit) rc = gpsacq_track_nominal_word_iq8(e, &iqin, &iq_word);
-                for (size_t k = 0; k < m; ++k) nom[k] = iq && iqin.multibit ? iq_word : (uint32_t)((uint64_t)fch[k].lo_nom >> 32);
                 std::vector<gpsacq_rate_obs> robs(n_fix * m);
                 vel.resize(n_fix);
                 if (rc == 0)
@@ -239,6 +267,19 @@ int main(int argc, char** argv) {
                         std::printf("vel tow %.6f ve %.3f vn %.3f vu %.3f drift %.4e n_used %d rms %.3f\n", fix[k].rx_ms * 1e-3 + fix[k].rx_frac,
                                     vel[k].ve, vel[k].vn, vel[k].vu, vel[k].drift, vel[k].n_used, vel[k].rms);
                 }
+            for (size_t k = 0; n_ms > 0 && k < m; ++k) {
+                // corr is in cycles * 2^32: times the L1 wavelength it is the code's distance from its carrier-held mean
+                const double unit = 299792458.0 / 1575.42e6 / two32;
+                double sum = 0.0, sq = 0.0;
+                size_t full = 0;
+                for (size_t i = 0; i < n_ms; ++i)
+                    if (sinfo[i * m + k].flags & GPSACQ_SMOOTH_FULL) {
+                        const double v = (double)sinfo[i * m + k].corr * unit;
+                        sum += v, sq += v * v, ++full;
+                    }
+                const double var = full ? sq / (double)full - (sum / (double)full) * (sum / (double)full) : 0.0;
+                std::printf("sigma PRN %d code_sigma_m %.3f full %zu\n", fch[k].prn, std::sqrt(var > 0 ? var : 0.0), full);
+            }
         }
     }
     gpsacq_destroy(e);

@@ -108,6 +108,15 @@ FIX_RAIM_DTYPE = np.dtype([("status", "<i4"), ("dof", "<i4"), ("excluded", "<i4"
                            ("threshold", "<f8")])
 
 
+# carrier-smoothed observables (include/gpsacq.h "Carrier-smoothed observables")
+SMOOTH_RESET, SMOOTH_UNLOCKED, SMOOTH_FULL = 1, 2, 4
+SMOOTH_PARAMS_DTYPE = np.dtype([("window", "<i4"), ("lock_epochs", "<i4"), ("lock_num", "<i4"), ("lock_den", "<i4"), ("jump", "<i8"),
+                                ("invert", "<i4"), ("reserved", "<i4")])
+SMOOTH_INFO_DTYPE = np.dtype([("window", "<i4"), ("flags", "<i4"), ("cmc", "<i8"), ("corr", "<i8")])
+L1_HZ = 1575.42e6
+C_MPS = 299792458.0
+
+
 class TrackParams(ctypes.Structure):
     _fields_ = [("lo_ki", ctypes.c_int32), ("lo_kp", ctypes.c_int32), ("ca_ki", ctypes.c_int32), ("ca_kp", ctypes.c_int32),
                 ("fll_k", ctypes.c_int32), ("fll_epochs", ctypes.c_int32), ("aid_epoch", ctypes.c_int32), ("agc_period", ctypes.c_int32),
@@ -135,7 +144,9 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_sat_rates_device", "gpsacq_vel_batch", "gpsacq_vel_batch_device", "gpsacq_pvt_track_device", "gpsacq_velocity_last_ms",
            "gpsacq_iono_load", "gpsacq_atm_default_params", "gpsacq_sat_views", "gpsacq_sat_views_device", "gpsacq_fix_atm_batch",
            "gpsacq_fix_atm_batch_device", "gpsacq_fix_atm_last_ms",
-           "gpsacq_raim_default_params", "gpsacq_fix_raim_batch", "gpsacq_fix_raim_batch_device", "gpsacq_fix_raim_last_ms"]
+           "gpsacq_raim_default_params", "gpsacq_fix_raim_batch", "gpsacq_fix_raim_batch_device", "gpsacq_fix_raim_last_ms",
+           "gpsacq_smooth_default_params", "gpsacq_smooth_observables", "gpsacq_smooth_observables_device", "gpsacq_fix_smooth_track_device",
+           "gpsacq_smooth_last_ms"]
 
 _lib = None
 
@@ -373,6 +384,17 @@ def load_library(path=None):
     lib.gpsacq_fix_raim_batch_device.restype = ctypes.c_int
     lib.gpsacq_fix_raim_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
     lib.gpsacq_fix_raim_last_ms.restype = ctypes.c_int
+    lib.gpsacq_smooth_default_params.argtypes = [vp]
+    lib.gpsacq_smooth_default_params.restype = ctypes.c_int
+    smooth_args = [vp, vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, u64, u64, sz, vp, vp, vp]
+    lib.gpsacq_smooth_observables.argtypes = smooth_args
+    lib.gpsacq_smooth_observables.restype = ctypes.c_int
+    lib.gpsacq_smooth_observables_device.argtypes = smooth_args + [ctypes.c_int]
+    lib.gpsacq_smooth_observables_device.restype = ctypes.c_int
+    lib.gpsacq_fix_smooth_track_device.argtypes = [vp, vp, ctypes.c_int] + smooth_args[1:] + [vp, ctypes.c_int]
+    lib.gpsacq_fix_smooth_track_device.restype = ctypes.c_int
+    lib.gpsacq_smooth_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 4
+    lib.gpsacq_smooth_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -476,6 +498,35 @@ def raim_params(sigma_m, p_fa=1e-3):
     lib = load_library()
     out = np.zeros(1, dtype=RAIM_PARAMS_DTYPE)
     _check(lib, lib.gpsacq_raim_default_params(float(sigma_m), float(p_fa), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def smooth_params(**overrides):
+    """gpsacq_smooth_default_params: a SMOOTH_PARAMS_DTYPE record of shape (1,) -- window 1000 instants, phase lock over 20 epochs
+    at a ratio of 1 / 2, a jump test at a quarter chip (385 << 32), spectrum not inverted -- with the named fields replaced.  The
+    entry points that take it check it."""
+    lib = load_library()
+    out = np.zeros(1, dtype=SMOOTH_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_smooth_default_params(out.ctypes.data_as(ctypes.c_void_p)))
+    for k, v in overrides.items():
+        if k not in SMOOTH_PARAMS_DTYPE.names:
+            raise TypeError("smooth_params: no field %r" % k)
+        out[k] = int(v)
+    return out
+
+
+def code_sigma_m(info):
+    """The measured pseudorange sigma per channel, metres: the standard deviation of corr * (c / L1) / 2^32 over the observations of
+    info (SMOOTH_INFO_DTYPE [n_fix][n_chans]) flagged SMOOTH_FULL; NaN where a channel has none.  The number raim_params(sigma_m=...)
+    asks for."""
+    info = np.asarray(info)
+    if info.dtype != SMOOTH_INFO_DTYPE or info.ndim != 2:
+        raise TypeError("info must be a SMOOTH_INFO_DTYPE array [n_fix][n_chans]")
+    out = np.full(info.shape[1], np.nan)
+    for c in range(info.shape[1]):
+        full = (info["flags"][:, c] & SMOOTH_FULL) != 0
+        if full.any():
+            out[c] = float(np.std(info["corr"][full, c].astype(np.float64) * (C_MPS / L1_HZ / 4294967296.0)))
     return out
 
 
@@ -1070,6 +1121,65 @@ class Engine:
         observation kernel, satellite-rate kernel, velocity kernel); a pair whose call has not been made reads 0."""
         t = [ctypes.c_float() for _ in range(4)]
         _check(self._lib, self._lib.gpsacq_velocity_last_ms(self._h, *[ctypes.byref(x) for x in t]))
+        return tuple(x.value for x in t)
+
+    # ---- carrier-smoothed observables -----------------------------------------------------
+    @staticmethod
+    def _smooth_params(params):
+        if params is None:
+            return None
+        pr = np.ascontiguousarray(np.asarray(params, dtype=SMOOTH_PARAMS_DTYPE).ravel())
+        if pr.size != 1:
+            raise ValueError("params must be one SMOOTH_PARAMS_DTYPE record")
+        return pr
+
+    def smooth_observables(self, records, n_epochs, chans, tags, first_rx_sample, rx_step, n_fix, params=None, nom_words=None, info=True):
+        """gpsacq_smooth_observables: observables() with the code position of every phase-locked instant replaced by its mean over
+        a window of instants carried by the carrier (a box-window Hatch filter that restarts on loss of lock and on a jump of
+        code-minus-carrier).  params: smooth_params() (None: the defaults); nom_words as in rate_observables().  Returns (obs
+        OBS_DTYPE [n_fix][n_chans], info SMOOTH_INFO_DTYPE of the same shape), or obs alone with info=False."""
+        ne, ch, tg = self._obs_arrays(n_epochs, chans, tags)
+        _, _, nw = self._rate_arrays(n_epochs, chans, nom_words)
+        pr = self._smooth_params(params)
+        if not isinstance(records, np.ndarray) or records.dtype != TRACK_RECORD_DTYPE or records.ndim != 2 or records.shape[0] != ne.size:
+            raise TypeError("records must be a TRACK_RECORD_DTYPE array [n_chans][max_epochs]")
+        rec = np.ascontiguousarray(records)
+        out = np.zeros((int(n_fix), ne.size), dtype=OBS_DTYPE)
+        inf = np.zeros((int(n_fix), ne.size), dtype=SMOOTH_INFO_DTYPE) if info else None
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_smooth_observables(self._h, p(rec), int(rec.shape[1]), p(ne), p(ch), p(tg), p(nw), int(ne.size),
+                                                              int(first_rx_sample), int(rx_step), int(n_fix), p(pr), p(out), p(inf)))
+        return (out, inf) if info else out
+
+    def smooth_observables_device(self, d_records_ptr, max_epochs, n_epochs, chans, tags, first_rx_sample, rx_step, n_fix, d_obs_ptr,
+                                  d_info_ptr=None, params=None, nom_words=None, sync=True):
+        """gpsacq_smooth_observables_device: records, observations and info (may be None) in device memory, the rest host arrays."""
+        ne, ch, tg = self._obs_arrays(n_epochs, chans, tags)
+        _, _, nw = self._rate_arrays(n_epochs, chans, nom_words)
+        pr = self._smooth_params(params)
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_smooth_observables_device(self._h, d_records_ptr, int(max_epochs), p(ne), p(ch), p(tg), p(nw), int(ne.size),
+                                                                     int(first_rx_sample), int(rx_step), int(n_fix), p(pr), d_obs_ptr, d_info_ptr,
+                                                                     1 if sync else 0))
+
+    def fix_smooth_track_device(self, eph, d_records_ptr, max_epochs, n_epochs, chans, tags, first_rx_sample, rx_step, n_fix, d_fix_ptr,
+                                d_obs_ptr=None, d_info_ptr=None, params=None, nom_words=None, sync=True):
+        """gpsacq_fix_smooth_track_device: smooth_observables_device, then fix_device on them, on the engine's stream with no host
+        copy in between.  d_fix: FIX_DTYPE [n_fix] in device memory; d_obs_ptr / d_info_ptr None keep those in engine scratch."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        ne, ch, tg = self._obs_arrays(n_epochs, chans, tags)
+        _, _, nw = self._rate_arrays(n_epochs, chans, nom_words)
+        pr = self._smooth_params(params)
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_fix_smooth_track_device(self._h, p(ep), int(ep.size), d_records_ptr, int(max_epochs), p(ne), p(ch), p(tg),
+                                                                   p(nw), int(ne.size), int(first_rx_sample), int(rx_step), int(n_fix), p(pr),
+                                                                   d_obs_ptr, d_info_ptr, d_fix_ptr, 1 if sync else 0))
+
+    def smooth_last_ms(self):
+        """Device milliseconds of the last smooth_observables* / fix_smooth_track_device call: (lock sums, code-minus-carrier, scan,
+        output kernel); the first reads 0 when lock_epochs was 0."""
+        t = [ctypes.c_float() for _ in range(4)]
+        _check(self._lib, self._lib.gpsacq_smooth_last_ms(self._h, *[ctypes.byref(x) for x in t]))
         return tuple(x.value for x in t)
 
     # ---- tracking channels on an 8-bit IQ capture -----------------------------------------

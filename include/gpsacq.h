@@ -978,6 +978,103 @@ GPSACQ_API int gpsacq_pvt_track_device(gpsacq_engine* e, const gpsacq_ephemeris*
 GPSACQ_API int gpsacq_velocity_last_ms(const gpsacq_engine* e, float* carrier_acc_ms, float* observe_rate_ms, float* sat_rate_ms, float* vel_ms);
 
 /*
+ * ---- Carrier-smoothed observables: code-minus-carrier, phase lock and slip resets ---------------------------------------------
+ *
+ * A fix made from gpsacq_observables carries the code loop's noise of one instant (metres); the carrier observable of the same
+ * channel is clean to centimetres but has an unknown constant.  Their difference, code-minus-carrier, is that constant plus the
+ * code's noise, so its mean over a window is the code's noise to take out: a box-window Hatch filter.  THE MODEL; the kernels
+ * (csrc/smooth_kernels.hip) and the reference of the tests (tests/smooth_ref.py) are both written from this text.  Integer
+ * arithmetic up to the one fp64 division of tx_frac; "mod 2^64" is unsigned wrap-around, "(int64)" reads such a value as two's
+ * complement, floor(a / b) is the signed division rounded toward minus infinity.
+ *
+ * INPUTS: those of gpsacq_rate_observables plus the tags -- records[c][0..n-1] of ONE tracking call, n = n_epochs[c], chans[c]
+ * after that call, tags[c], nom_words[c], the RECEIVE INSTANTS R_i = first_rx_sample + i * rx_step, i < n_fix -- and a
+ * gpsacq_smooth_params.  Per channel, with FULL = 1023 * 2^32:
+ *     cw  = (uint32)((uint64)chans[c].ca_nom >> 32)         the nominal code word
+ *     S   = records[c][0].sample
+ *     t, pos_t, P, first_epoch as in OBSERVATION;   A(R) as in RATE OBSERVATION
+ *     sgn = -1 if params.invert != 0, else +1               (SIGN of Carrier observables: an inverted spectrum is the caller's to declare)
+ *
+ * USABLE INSTANT: tag.valid != 0, n > 0 and records[c][0].sample <= R_i < next_sample -- exactly the instants at which an
+ * OBSERVATION can be made.  Any other instant is INVALID: its obs and its info are all-zero bytes.
+ *
+ * CODE-MINUS-CARRIER of a usable instant, in cycles * 2^32 (1540 carrier cycles per chip):
+ *     Z_i = 1540 * ((first_epoch + t) * FULL + P - (R_i - S) * cw) - sgn * A(R_i)          mod 2^64
+ * (first_epoch sign-extended to 64 bits).  The bracket is the code's advance over the nominal one, the same quantity A counts
+ * for the carrier.  Only differences of Z are ever used, each read as int64.
+ *
+ * PHASE LOCK of a usable instant, when lock_epochs = L > 0: over the epochs u = t-L+1 .. t of this call's records,
+ *     N = sum (ip_u^2 - qp_u^2),   D = sum (ip_u^2 + qp_u^2)        squares and sums in int64 (mod 2^64)
+ *     locked iff t >= L-1 and D > 0 and N * lock_den >= D * lock_num       the two products in int64 (mod 2^64)
+ * With |ip|, |qp| < 2^21 (1-bit channels: at most 65535) nothing wraps.  L = 0: every usable instant is locked.  A usable instant
+ * that is not locked is UNLOCKED: its obs is the raw OBSERVATION, byte for byte what gpsacq_observables writes, its info has
+ * flags = GPSACQ_SMOOTH_UNLOCKED and every other field 0.  (During FLL pull-in the ratio N / D swings to -0.8; a Costas loop
+ * in lock keeps it above 0.85.)
+ *
+ * SEGMENTS.  A locked instant i starts a segment (flag GPSACQ_SMOOTH_RESET) iff i = 0, or instant i-1 is INVALID or UNLOCKED, or
+ * jump > 0 and |(int64)(Z_i - Z_{i-1})| > jump (the difference INT64_MIN counts as greater).  s_i = the latest segment start
+ * <= i, m_i = min(i - s_i + 1, window).
+ *
+ * SMOOTHING of a locked instant:
+ *     D_i  = sum over j = i-m_i+1 .. i of (Z_j - Z_i)          mod 2^64, read as int64
+ *          = (S_{i+1} - S_{i+1-m_i}) - m_i * Z_i  mod 2^64,    S_k = sum over j < k of Z_j mod 2^64, Z_j = 0 where j is not locked
+ *     q_i  = floor(D_i / m_i)                                  cycles * 2^32: mean code-minus-carrier of the window minus Z_i
+ *     c_i  = floor(q_i / 1540)                                 chips * 2^32
+ *     P'   = (int64)P + c_i;   k = floor(P' / FULL);   P~ = P' - k * FULL          0 <= P~ < FULL
+ *     tx_ms   = (tag.ms + (first_epoch + t + k - tag.epoch)) mod 604800000         non-negative, as in OBSERVATION
+ *     tx_frac = (double)P~ / 4393751543808000.0                                    the same single IEEE division
+ *     eph = tag.eph, valid = 1, weight = 1.0, reserved = 0
+ * Every j of the window is locked and inside i's segment, so the two forms of D_i are the same number mod 2^64 always; the sum of
+ * the int64 differences (int64)(Z_j - Z_i) equals it without wrap-around while every |Z_j - Z_i| < 2^63 / m_i, which jump > 0
+ * guarantees for jump * window^2 < 2^63 (the defaults: 2^41 * 10^6).  Z constant over the window gives q = c = 0 and the raw bytes.
+ *
+ * INFO per observation, index-parallel to obs: window = m_i; cmc = (int64)(Z_i - Z_{s_i}), code-minus-carrier since the segment
+ * began; corr = q_i; flags = GPSACQ_SMOOTH_RESET (i = s_i) | GPSACQ_SMOOTH_FULL (m_i == window).
+ *
+ * PARAMETERS.  gpsacq_smooth_default_params: window 1000, lock_epochs 20, lock_num / lock_den 1 / 2, jump (int64)385 << 32 (a
+ * quarter chip in cycles, half the early-late spacing), invert 0, reserved 0.  Valid: 1 <= window <= 65536, 0 <= lock_epochs
+ * <= 1024, 1 <= lock_num <= lock_den <= 1024, jump >= 0 (0: no jump test); anything else is GPSACQ_ERR_ARG.
+ *
+ * NOTES.  A nominal word that is off by delta Hz (nom_words[c] and cw are truncated) drifts every channel's Z by delta cycles/s;
+ * that is common to all channels and goes into the receiver clock only while the channels' windows are equal -- cmc shows it.
+ * Half-cycle slips are invisible to the jump test: 9.5 cm against metres of code noise.  adr still carries no flag.  The standard
+ * deviation of corr * (c / L1) / 2^32 over FULL windows is the measured pseudorange sigma of the channel (metres), the number
+ * gpsacq_raim_default_params asks for.
+ *
+ * gpsacq_smooth_observables: host pointers; obs[n_fix][n_chans] in gpsacq_observables's layout, info[n_fix][n_chans] index-parallel
+ * (may be NULL), params NULL = the defaults.  gpsacq_smooth_observables_device: records, obs and info are device pointers (d_info
+ * may be NULL), the rest host pointers; work on the engine's stream, sync != 0 waits.  gpsacq_fix_smooth_track_device: the same
+ * followed by gpsacq_fix_batch_device on the same stream, no host copy in between; d_obs and d_info may be NULL (engine scratch).
+ * Argument errors are those of gpsacq_observables and gpsacq_rate_observables plus the parameter ranges: GPSACQ_ERR_ARG, nothing
+ * launched, nothing written.  Kernels: k_code_pos and k_carrier_acc as they are, into the scratch they already use (their times stay
+ * with gpsacq_observables_last_ms and gpsacq_velocity_last_ms, whose second kernels then read 0), then k_lock_acc (one wave64 per
+ * channel: the prefix sums of ip^2 - qp^2 and ip^2 + qp^2; skipped when lock_epochs = 0), k_cmc (one lane per (instant,
+ * channel): t, P, Z and the state), k_smooth_scan (one wave64 per channel: S and s_i over the instants, in chunks with a
+ * carry) and k_smooth_out (one lane per (instant, channel): the two records).
+ */
+#define GPSACQ_SMOOTH_RESET 1      /* this instant starts a segment */
+#define GPSACQ_SMOOTH_UNLOCKED 2   /* not phase-locked: obs is the raw observation */
+#define GPSACQ_SMOOTH_FULL 4       /* the window has its full length */
+typedef struct { int32_t window, lock_epochs, lock_num, lock_den; int64_t jump; int32_t invert, reserved; } gpsacq_smooth_params;   /* 32 bytes */
+typedef struct { int32_t window; int32_t flags; int64_t cmc; int64_t corr; } gpsacq_smooth_info;                                   /* 24 bytes */
+GPSACQ_API int gpsacq_smooth_default_params(gpsacq_smooth_params* p);   /* host only */
+GPSACQ_API int gpsacq_smooth_observables(gpsacq_engine* e, const gpsacq_track_record* records, int max_epochs, const int32_t* n_epochs,
+                                         const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, const uint32_t* nom_words, int n_chans,
+                                         uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, const gpsacq_smooth_params* params,
+                                         gpsacq_obs* obs, gpsacq_smooth_info* info);
+GPSACQ_API int gpsacq_smooth_observables_device(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs,
+                                                const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, const uint32_t* nom_words,
+                                                int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix,
+                                                const gpsacq_smooth_params* params, void* d_obs, void* d_info, int sync);
+GPSACQ_API int gpsacq_fix_smooth_track_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_records, int max_epochs,
+                                              const int32_t* n_epochs, const gpsacq_track_chan* chans, const gpsacq_time_tag* tags,
+                                              const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix,
+                                              const gpsacq_smooth_params* params, void* d_obs, void* d_info, void* d_fix, int sync);
+/* device time of the four new kernels of the last gpsacq_smooth_observables* / gpsacq_fix_smooth_track_device call on this engine,
+ * milliseconds (HIP events on its stream; waits for them); lock_acc_ms reads 0 when lock_epochs was 0.  Any pointer may be NULL. */
+GPSACQ_API int gpsacq_smooth_last_ms(const gpsacq_engine* e, float* lock_acc_ms, float* cmc_ms, float* scan_ms, float* out_ms);
+
+/*
  * ---- Atmosphere, elevation mask and DOP ---------------------------------------------------------------------------------------
  *
  * gpsacq_fix_batch is the reference's bare Solve(): signals as if in vacuum, every satellite with an ephemeris used, no figure of
