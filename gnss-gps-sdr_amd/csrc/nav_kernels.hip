@@ -136,6 +136,7 @@ __device__ __forceinline__ gpsacq_sat_rate sat_state_rate(const NavEph& p, int32
 
 // LatLonAlt(), c/solve.cpp:273-293, bounded
 __device__ __forceinline__ void geodetic(double x, double y, double z, double& lat, double& lon, double& alt) {
+#pragma clang fp contract(off)  // the three copies of this function give the same bits whatever kernel they are inlined into
     const double p = sqrt(x * x + y * y);
     if (!(p > 1e-6)) {  // on the axis: p / cos(lat) is 0 / 0
         lon = 0.0;
@@ -143,7 +144,14 @@ __device__ __forceinline__ void geodetic(double x, double y, double z, double& l
         alt = fabs(z) - WGS84_A * sqrt(1.0 - WGS84_E2);
         return;
     }
-    lon = 2.0 * atan2(y, x + p);
+    // tan(lon / 2) = y / (x + p) = (p - x) / y: the form whose sum does not cancel.  With x < 0 the first one loses x + p to rounding
+    // next to the antimeridian and is 0 / 0 on it (y == 0: lon = pi, in (-pi, pi])
+    if (x >= 0.0) {
+        lon = 2.0 * atan2(y, x + p);
+    } else {
+        const double half = 2.0 * atan2(p - x, fabs(y));
+        lon = y < 0.0 ? -half : half;
+    }
     lat = atan(z / (p * (1.0 - WGS84_E2)));
     alt = 0.0;
     for (int k = 0; k < GEODETIC_PASSES; ++k) {

@@ -49,6 +49,7 @@ __device__ __forceinline__ bool raim_usable(const gpsacq_obs& o, const NavEph* e
 
 // LatLonAlt(), c/solve.cpp:273-293, bounded: k_fix's
 __device__ __forceinline__ void raim_geodetic(double x, double y, double z, double& lat, double& lon, double& alt) {
+#pragma clang fp contract(off)  // the three copies of this function give the same bits whatever kernel they are inlined into
     const double p = sqrt(x * x + y * y);
     if (!(p > 1e-6)) {  // on the axis: p / cos(lat) is 0 / 0
         lon = 0.0;
@@ -56,7 +57,14 @@ __device__ __forceinline__ void raim_geodetic(double x, double y, double z, doub
         alt = fabs(z) - RAIM_WGS84_A * sqrt(1.0 - RAIM_WGS84_E2);
         return;
     }
-    lon = 2.0 * atan2(y, x + p);
+    // tan(lon / 2) = y / (x + p) = (p - x) / y: the form whose sum does not cancel.  With x < 0 the first one loses x + p to rounding
+    // next to the antimeridian and is 0 / 0 on it (y == 0: lon = pi, in (-pi, pi])
+    if (x >= 0.0) {
+        lon = 2.0 * atan2(y, x + p);
+    } else {
+        const double half = 2.0 * atan2(p - x, fabs(y));
+        lon = y < 0.0 ? -half : half;
+    }
     lat = atan(z / (p * (1.0 - RAIM_WGS84_E2)));
     alt = 0.0;
     for (int k = 0; k < RAIM_GEODETIC_PASSES; ++k) {

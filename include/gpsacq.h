@@ -727,7 +727,10 @@ GPSACQ_API int gpsacq_generate_iq8_range_device(gpsacq_engine* e, void* d_iq_out
  *     clock_corr = a_f0 + a_f1 t + a_f2 t^2 + F e sqrt_a sin E - t_gd,      F = -4.442807633e-10.
  * The position is IS-GPS-200 Table 20-IV at the corrected time (t_k - clock_corr), ECEF metres at that time, with
  * mu = 3.986005e14, Omega_e-dot = 7.2921151467e-5.  An observation that is not usable (valid == 0, eph index outside
- * [0, n_eph), an ephemeris that is not valid, a negative or non-finite weight) gives an all-zero gpsacq_sat_state.
+ * [0, n_eph), an ephemeris that is not valid, a negative or non-finite weight) gives an all-zero gpsacq_sat_state.  An ephemeris
+ * whose t_oe or t_oc is 604 800 s or more -- the 16-bit fields reach 1 048 560 s -- names no instant of the week and counts as not
+ * valid here, whatever gpsacq_ephemeris_valid says of its issue numbers.  An observation whose tx_frac is NaN or infinite is not
+ * usable either, in the host forms and in the _device forms alike (it is no argument error: the host forms check the weights only).
  *
  * FIX.  Unknowns x, y, z and the receive time; start at the origin and at the mean corrected transmit time + 75 ms.  Per pass and
  * satellite: turn the satellite by theta = Omega_e-dot (t_tx - t_rx) about z, residual = c (t_rx - t_tx) - range, Jacobian row
@@ -737,7 +740,10 @@ GPSACQ_API int gpsacq_generate_iq8_range_device(gpsacq_engine* e, void* d_iq_out
  * 20 steps without that, a pivot that is not positive (below 1e-13 of its diagonal entry) or a non-finite step:
  * GPSACQ_FIX_NO_CONVERGE.  c = 2.99792458e8.
  * lat / lon / alt: LatLonAlt()'s iteration on WGS-84 (a = 6378137, e^2 = 0.00669437999014132), until alt moves less than 1e-9 m,
- * 10 passes at most.  A fix that is not GPSACQ_FIX_OK has every double field 0 and rx_ms = 0.
+ * 10 passes at most.  lon = atan2(y, x) in (-pi, pi], taken as 2 atan2(y, x + p) where x >= 0 and as +-2 atan2(p - x, |y|) with the
+ * sign of y where x < 0 (p = sqrt(x^2 + y^2); tan(lon / 2) = y / (x + p) = (p - x) / y, each used where its sum does not cancel): a
+ * point with y == 0 and x < 0 lies on the antimeridian, lon = pi.  A fix that is not GPSACQ_FIX_OK has every double field 0 and
+ * rx_ms = 0.
  *
  * gpsacq_sat_states: one state per observation.  gpsacq_fix_batch: obs[n_fix][sats_per_fix], one fix per row; unusable
  * observations are skipped.  A negative or non-finite weight is GPSACQ_ERR_ARG in the host forms; the _device forms (device
@@ -1099,7 +1105,8 @@ GPSACQ_API int gpsacq_smooth_last_ms(const gpsacq_engine* e, float* lock_acc_ms,
  * GPSACQ_ERR_ARG.  pi is the true one, 3.141592653589793, everywhere in this section.
  *
  * VIEW of a satellite from a receiver at ECEF r, with (lat, lon, alt) = FIX's LatLonAlt() iteration of r (on the axis, where
- * sqrt(x^2 + y^2) <= 1e-6: lon = 0, lat = +-pi/2, alt = |z| - a sqrt(1 - e^2)).  alt is the height above the WGS-84 ellipsoid, not
+ * sqrt(x^2 + y^2) <= 1e-6: lon = 0, lat = +-pi/2, alt = |z| - a sqrt(1 - e^2); off it lon = atan2(y, x) in (-pi, pi] as FIX takes it, so
+ * y == 0 with x < 0 is lon = pi, the antimeridian, and not 0).  alt is the height above the WGS-84 ellipsoid, not
  * above the geoid.  s is the satellite's state turned by theta = Omega_e-dot (t_tx - t_rx) about z exactly as FIX and VELOCITY turn
  * it, t_tx the corrected transmit time (tx - clock_corr).  d = s - r, and in the local frame (VELOCITY's rotation for ve, vn, vu)
  *     e = -sin lon dx + cos lon dy

@@ -76,7 +76,8 @@ def geodetic(xyz):
     p = math.sqrt(x * x + y * y)
     if not p > 1e-6:
         return (-PI / 2 if z < 0 else PI / 2), 0.0, abs(z) - WGS84_A * math.sqrt(1 - WGS84_E2)
-    lon = 2 * math.atan2(y, x + p)
+    # tan(lon / 2) = y / (x + p) = (p - x) / y, each where its sum does not cancel; y == 0 with x < 0 is the antimeridian, pi
+    lon = 2 * math.atan2(y, x + p) if x >= 0 else math.copysign(2 * math.atan2(p - x, abs(y)), 1.0 if y >= 0 else -1.0)
     lat = math.atan(z / (p * (1 - WGS84_E2)))
     alt = 0.0
     for _ in range(10):
