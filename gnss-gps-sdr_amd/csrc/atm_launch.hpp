@@ -1,4 +1,4 @@
-// atm_launch.hpp -- argument blocks and launchers of "Atmosphere, elevation mask and DOP" of include/gpsacq.h: atm_kernels.hip's
+// atm_launch.hpp -- argument blocks and launchers of "Atmosphere, elevation mask and DOP" of include/gpsacq.h: fix_kernels.hip's
 // k_sat_view (one lane per observation) and k_fix_atm (one lane per fix).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -4,7 +4,7 @@
 // (host only) and the gpsacq_observables* / gpsacq_fix_track_device entry points that run obs_kernels.hip, then "Carrier observables"
 // and "Velocity and clock drift": gpsacq_rate_observables*, gpsacq_sat_rates*, gpsacq_vel_batch*, gpsacq_pvt_track_device.  At the
 // end "Atmosphere, elevation mask and DOP": page 18 and the parameters (host only), gpsacq_sat_views*, gpsacq_fix_atm_batch*, and
-// "Fix integrity": the chi-square thresholds (host only) and gpsacq_fix_raim_batch*, which run raim_kernels.hip.
+// "Fix integrity": the chi-square thresholds (host only) and gpsacq_fix_raim_batch*, which run fix_kernels.hip's k_raim_*.
 // Between the velocity and the atmosphere: "Carrier-smoothed observables", gpsacq_smooth_observables* and
 // gpsacq_fix_smooth_track_device, which run smooth_kernels.hip after k_code_pos and k_carrier_acc.
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
@@ -678,7 +678,7 @@ extern "C" int gpsacq_smooth_last_ms(const gpsacq_engine* e, float* lock_acc_ms,
     return GPSACQ_OK;
 }
 
-// ---- atmosphere, elevation mask and DOP (atm_kernels.hip) --------------------------------------------------------------------
+// ---- atmosphere, elevation mask and DOP (fix_kernels.hip) --------------------------------------------------------------------
 extern "C" int gpsacq_iono_load(gpsacq_iono* io, const gpsacq_subframe* sf, int n) {
     if (!io || n < 0 || (n > 0 && !sf)) return fail(GPSACQ_ERR_ARG, "gpsacq_iono_load: bad argument");
     for (int k = 0; k < n; ++k) {
@@ -836,7 +836,7 @@ extern "C" int gpsacq_fix_atm_last_ms(const gpsacq_engine* e, float* sat_state_m
     return GPSACQ_OK;
 }
 
-// ---- fix integrity: residual test and single-satellite exclusion (raim_kernels.hip) -----------------------------------------------
+// ---- fix integrity: residual test and single-satellite exclusion (fix_kernels.hip) -----------------------------------------------
 namespace {
 // upper tail of the chi-square distribution at d degrees of freedom, the closed form for integer d
 double chi2_tail(int d, double x) {

@@ -1,5 +1,5 @@
 // raim_launch.hpp -- argument block and launchers of "Fix integrity: residual test and single-satellite exclusion" of
-// include/gpsacq.h: raim_kernels.hip's k_raim_detect (one lane per fix) and k_raim_exclude (sixteen lanes per fix).
+// include/gpsacq.h: fix_kernels.hip's k_raim_detect (one lane per fix) and k_raim_exclude (sixteen lanes per fix).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1086,8 +1086,8 @@ GPSACQ_API int gpsacq_smooth_last_ms(const gpsacq_engine* e, float* lock_acc_ms,
  * gpsacq_fix_batch is the reference's bare Solve(): signals as if in vacuum, every satellite with an ephemeris used, no figure of
  * the geometry.  This section adds the Klobuchar ionosphere, a Saastamoinen troposphere, an elevation mask and the dilutions of
  * precision.  The reference decodes the ionospheric coefficients (EPHEM::LoadPage18, c/ephemeris.cpp:70-83) and never uses them;
- * the rest is our own.  THE MODEL; the kernels (csrc/atm_kernels.hip: k_sat_view, k_fix_atm) and tests/atm_ref.py are both
- * written from this text.  Nothing of the sections above changes: k_sat_state, k_fix, k_vel and their entry points are what they were.
+ * the rest is our own.  THE MODEL; the kernels (csrc/fix_kernels.hip: k_sat_view, k_fix_atm) and tests/atm_ref.py are both
+ * written from this text.  Nothing of the sections above changes: gpsacq_sat_states*, gpsacq_fix_batch*, gpsacq_vel_batch* compute what they did.
  *
  * PAGE 18 (host only).  gpsacq_iono_load folds, in the order given, every subframe of sf[0..n-1] whose ID (word 2, bits 20-22)
  * is 4 and whose word 3 starts with the eight bits 0x78 (data ID 01, SV/page ID 56: the test EPHEM::Subframe4 makes).  Such a
@@ -1200,8 +1200,8 @@ GPSACQ_API int gpsacq_fix_atm_last_ms(const gpsacq_engine* e, float* sat_state_m
  * LoadReplicas() (c/solve.cpp), which strips channels whose glitch counters moved; this section is our own: receiver autonomous
  * integrity monitoring (RAIM) on top of CORRECTED FIX -- a chi-square test of the residuals against an expected noise level and,
  * where it fails, the exclusion of the one observation whose removal explains the failure best.  THE MODEL; the kernels
- * (csrc/raim_kernels.hip: k_raim_detect, k_raim_exclude) and tests/raim_ref.py are both written from this text.  Nothing of the
- * sections above changes: k_sat_state, k_fix, k_vel, k_sat_view, k_fix_atm and their entry points are what they were.
+ * (csrc/fix_kernels.hip: k_raim_detect, k_raim_exclude) and tests/raim_ref.py are both written from this text.  Nothing of the
+ * sections above changes: their entry points compute what they did.
  *
  * PARAMETERS.  sigma_m is the standard deviation, in metres, of a pseudorange whose observation has weight 1; an observation of
  * weight w has variance sigma_m^2 / w.  threshold[d - 1] is the chi-square quantile with upper tail p_fa at d degrees of freedom.
