@@ -194,9 +194,11 @@ extern "C" int gpsacq_track(gpsacq_engine* e, const uint8_t* bits, size_t n_byte
 }
 
 // ---- tracking channels on an 8-bit IQ capture (track_iq_kernels.hip; include/gpsacq.h) -------------------------------------
-extern "C" int gpsacq_track_default_params_iq8(const gpsacq_engine* e, double sample_rms, gpsacq_track_params* p) {
-    if (!e || !p) return fail(GPSACQ_ERR_ARG, "gpsacq_track_default_params_iq8: null argument");
+extern "C" int gpsacq_track_default_params_iq8(const gpsacq_engine* e, double sample_rms, gpsacq_track_params* params) {
+    if (!e || !params) return fail(GPSACQ_ERR_ARG, "gpsacq_track_default_params_iq8: null argument");
     if (!(sample_rms > 0) || !std::isfinite(sample_rms)) return fail(GPSACQ_ERR_UNSUPPORTED, "gpsacq_track_default_params_iq8: sample_rms %g", sample_rms);
+    gpsacq_track_params q;  // *params is written only on success
+    gpsacq_track_params* p = &q;
     if (int rc = gpsacq_track_default_params(e, p)) return rc;
     int g = (int)std::lround(std::log2((double)GPSACQ_TRACK_IQ8_GAIN * sample_rms * sample_rms));
     // every shift stays in [0, 62], the carrier's in [1, 62] (gain_adj = -1)
@@ -208,6 +210,7 @@ extern "C" int gpsacq_track_default_params_iq8(const gpsacq_engine* e, double sa
     const double s = std::ldexp(1.0, g);
     p->agc_lo = (int64_t)std::floor((double)p->agc_lo * s);
     p->agc_hi = (int64_t)std::floor((double)p->agc_hi * s);
+    *params = q;
     return GPSACQ_OK;
 }
 

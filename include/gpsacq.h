@@ -677,7 +677,9 @@ GPSACQ_API int gpsacq_track_start_iq8(const gpsacq_engine* e, const gpsacq_iq8_i
  * synthetic captures gives 6.0 r^2).  A plain g = round(log2(sample_rms^2)) would leave every loop gain about six times a 1-bit
  * channel's and trip the AGC on the stronger satellites; the constant is therefore two bits more, 4, the power of two nearest
  * to 6.2, which puts the loops at the 1-bit channels' bandwidths.  g is clamped so that every shift stays in [0, 62] (lo_ki, lo_kp >= 1);
- * GPSACQ_ERR_UNSUPPORTED if it cannot be (sample_rms <= 0, not finite, or so large that a shift would go negative).
+ * GPSACQ_ERR_UNSUPPORTED if it cannot be (sample_rms <= 0, not finite, or so large that a shift would go negative); *params is written only on success.  The smallest
+ * shift is ca_ki, so that is g > ca_ki of gpsacq_track_default_params, log2(4 sample_rms^2) >= ca_ki + 1/2: a sample RMS above 152 /
+ * 107 / 76 / 53 / 38 / 38 / 26.9 / 13.4 / 9.5 / 3.36 at fs = 2.046 / 2.8 / 4 / 5.456 / 6.5 / 8.184 / 10 / 16.368 / 20 / 40 MHz.
  */
 #define GPSACQ_TRACK_IQ8_GAIN 4
 GPSACQ_API int gpsacq_track_default_params_iq8(const gpsacq_engine* e, double sample_rms, gpsacq_track_params* params);

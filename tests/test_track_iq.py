@@ -1,6 +1,9 @@
 """Tracking channels on an 8-bit IQ capture, CPU side: the model of the multi-bit complex channel (tests/c/track_model_iq.c,
 written from include/gpsacq.h) against a numpy restatement of its sums and against the 1-bit model on degenerate captures; the
-host-only entry points; the ABI.  The kernel itself is checked against this model in tests/test_gpu_track_iq.py."""
+host-only entry points; the ABI; and the model under the independent reference of tests/track_ref.py (complex integer samples)
+over the scenarios of test_track_ref.sweep at 2.046 .. 40 MHz, with bytes on the rails (-128 included), means up to (-128, 127)
+and carriers on both sides of zero; the supported-RMS boundary of gpsacq_track_default_params_iq8; lock from 60 Hz off at 10, 20
+and 40 MHz.  The kernel itself is checked against this model in tests/test_gpu_track_iq.py and tests/test_gpu_track_iq_sweep.py."""
 import ctypes
 import math
 import os
@@ -9,6 +12,8 @@ import re
 import numpy as np
 import pytest
 
+import track_iq_helpers as iqh
+from test_track_ref import FS_FC
 from track_helpers import ROOT, run_model
 from track_iq_helpers import host_capture, host_chan, numpy_epoch_sums, run_model_iq
 
@@ -134,3 +139,102 @@ def test_iq8_tracking_abi():
     assert lib.gpsacq_track_default_params_iq8(None, 16.0, ctypes.byref(p)) == 1
     ch = np.zeros(1, gpsacq.TRACK_CHAN_DTYPE)
     assert lib.gpsacq_track_start_iq8(None, None, 1, None, 0, None, ch.ctypes.data_as(ctypes.c_void_p)) == 1
+
+
+# ---- the model under the independent reference ---------------------------------------------------------------------------------
+_IDS = [f"{fs / 1e6:g}MHz" for fs, _ in FS_FC]
+
+
+@pytest.mark.parametrize("fs", [fs for fs, _ in FS_FC], ids=_IDS)
+def test_model_equals_reference_iq(fs):
+    """tests/c/track_model_iq.c against track_ref.audit (every epoch's geometry and loop arithmetic, the final state; the six sums
+    of every epoch below 10 MHz, of 30 seeded ones per channel from there on) over every scenario of the sweep.  First, on the
+    inputs alone: at 2.046 .. 5.456 MHz at least 0.5 % of the bytes lie on a rail and both rails occur (measured 4.4 % at scale
+    60 with no mean, half the bytes under the mean (-128, 127)), the window starts off the 8-sample grid and its byte count is
+    2 .. 14 mod 16; then, on the model's reports, what each scenario aims at."""
+    reps, sats, first, buf, case = iqh.sweep_iq(fs)
+    lo, hi = iqh.rail_share(buf, case["signed"])
+    print("fs %g scale %d dc %s signed %d if %.1f rms %.2f rails %.4f %.4f" % (fs, case["scale"], case["dc"], case["signed"], case["if_hz"], case["rms"], lo, hi))
+    if fs <= 5.456e6:
+        assert lo + hi >= 0.005 and lo > 0 and hi > 0, (lo, hi)
+    assert first % 8 != 0 and np.asarray(buf).size % 16 == 2 * (1 + case["i"] % 7)
+    assert case["rms"] < iqh.iq8_rms_bound(fs)
+    iqh.check_sweep_reports(reps)
+    r = {k: v[0] for k, v in reps.items()}
+    assert sum(x["short_first"] for x in r["wrap"]) >= 2  # (a start past 1022.97 chips may land on the next period)
+
+
+def test_branch_coverage_iq():
+    """the census of test_track_ref.test_branch_coverage over the IQ sweep: every branch it aims at was taken somewhere, by
+    channels of all 32 PRNs; and the rotation put every mean, both byte formats and carriers of both signs to work"""
+    tot = dict(agc_down=0, agc_up=0, ring_wraps=0, fll_epochs=0, costas_epochs=0, costas_adj_epochs=0, aid=0, late_wrap=0, early_wrap=0,
+               short_first=0)
+    lost, stops, prns, dcs, fmts, signs = set(), set(), set(), set(), set(), set()
+    for fs, _ in FS_FC:
+        reps, sats, _, _, case = iqh.sweep_iq(fs)
+        prns |= {s[0] for s in sats}
+        dcs.add(case["dc"])
+        fmts.add(case["signed"])
+        signs |= {np.sign(case["if_hz"] + s[2]) for s in sats}
+        for v in reps.values():
+            for x in v[0]:
+                for k in tot:
+                    tot[k] += len(x[k]) if k == "aid" else int(x[k])
+                lost |= x["lost"]
+                stops.add(x["stop"])
+    assert all(v > 0 for v in tot.values()), tot
+    assert lost == {"lo_int", "lo_rate", "ca_int", "ca_rate", "min_epoch", "max_epoch"}
+    assert stops == {"window", "max_epochs", "lost", "entered_lost"}
+    assert prns == set(range(1, 33))
+    assert dcs == set(iqh.IQ_DC) and fmts == {True, False} and signs == {-1.0, 1.0}
+
+
+_ALL_FS = sorted(iqh.IQ_SCALE)
+
+
+def test_default_params_iq8_boundary():
+    """gpsacq_track_default_params_iq8, restated from the header, answers up to the sample RMS at which log2(4 rms^2) = ca_ki + 1/2
+    (ca_ki of the 1-bit defaults, the smallest shift) and not beyond:
+
+        fs, MHz    2.046  2.8  4   5.456  6.5  8.184  10    16.368  20   40
+        RMS up to  152    107  76  53     38   38     26.9  13.4    9.5  3.36
+
+    (at 40 MHz an 8-bit capture may use less than two bits).  Just below the boundary every shift is in range, ca_ki is 0 and
+    the AGC levels are the 1-bit ones times 2^g; just above there is no answer.  The scales of the sweep keep inside it."""
+    from test_track_ref import default_params
+    table = dict(zip(_ALL_FS, (152, 107, 76, 53, 38, 38, 26.9, 13.4, 9.5, 3.36)))
+    for fs in _ALL_FS:
+        b = iqh.iq8_rms_bound(fs)
+        digits = 0 if table[fs] >= 30 else (1 if table[fs] >= 9 else 2)
+        assert math.floor(b * 10 ** digits) == round(table[fs] * 10 ** digits), (fs, b)
+        base = default_params(fs)
+        ok, bad = iqh.default_params_iq8(fs, b * (1 - 1e-9)), iqh.default_params_iq8(fs, b * (1 + 1e-9))
+        assert bad is None and ok is not None, fs
+        g = base.ca_ki
+        assert ok.ca_ki == 0 and [base.lo_ki - ok.lo_ki, base.lo_kp - ok.lo_kp, base.ca_kp - ok.ca_kp, base.fll_k - ok.fll_k] == [g] * 4
+        assert min(ok.lo_ki, ok.lo_kp) >= 1 and (ok.agc_lo, ok.agc_hi) == (base.agc_lo * 2 ** g, base.agc_hi * 2 ** g)
+        # one step of g further down the RMS scale, and the clamp at the top of the shifts
+        low = iqh.default_params_iq8(fs, b / math.sqrt(2) * (1 - 1e-9))
+        assert low.ca_ki == 1
+        tiny = iqh.default_params_iq8(fs, 1e-9)
+        assert max(tiny.lo_ki, tiny.lo_kp, tiny.ca_ki, tiny.ca_kp, tiny.fll_k) == 62
+        for x in (0.0, -1.0, float("nan"), float("inf")):
+            assert iqh.default_params_iq8(fs, x) is None
+    for fs, _ in FS_FC:
+        assert iqh.IQ_SCALE[fs] * 1.05 < iqh.iq8_rms_bound(fs)  # room for the satellites' sum a^2 / 2 <= 0.1; the sweep asserts its RMS
+
+
+@pytest.mark.parametrize("fs", sorted(iqh.LOCK_CASES), ids=lambda v: f"{v / 1e6:g}MHz")
+def test_iq8_defaults_lock_at_high_fs(fs):
+    """1.1 s at 10 (the HackRF flow: IF 2.6 MHz, int8), 20 and 40 MHz, amplitudes inside the supported RMS (scale 25 / 9 / 3), two
+    satellites of amplitude 0.25 started 60 Hz off: through the 500-epoch FLL and on under the Costas loop.  Both end TRACK_OK,
+    after epoch 700 the carrier deviates less than the 60 Hz it started with (measured here: at most 56.1 / 50.7 / 30.0 Hz; the
+    word of an epoch carries the Costas loop's proportional term, 19 / 15 / 9 Hz rms), the prompt power on I is at least 10 times
+    that on Q (measured: 136 and up).  Satellites, window and seeds are those of test_track_ref.test_defaults_lock_at_high_fs.  The
+    run is audited by the reference."""
+    sats, n, case = iqh.lock_setup(fs)
+    buf = iqh.host_lock_capture(fs, sats, n, case)
+    p, ch, rms = iqh.lock_params_and_chans(fs, buf, sats, case)
+    assert rms < iqh.iq8_rms_bound(fs)
+    reps, prompt, rec, ne = iqh.run_and_audit_iq(buf, 0, ch, p, sum_epochs=30, fmt=(case["signed"],) + case["dc"])
+    print("fs %g rms %.2f (dev Hz, I/Q power)" % (fs, rms), iqh.assert_locked(fs, case, sats, reps, prompt, rec, ne))

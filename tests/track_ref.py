@@ -8,7 +8,10 @@ include/gpsacq.h.  It shares no bit tricks with tests/c/track_model.c or csrc/tr
 * the loops run in Python integers, reduced mod 2^64 explicitly, with shifts written as multiplications by 2**k and ">> 32"
   as a floor division of the reduced value.
 
-audit() checks what a call of gpsacq_track (or the CPU model) wrote for one channel: every epoch's geometry, its six sums,
+The samples are either 1-bit (v_i = 1 - 2 x, v_q = 0) or the complex integers of "Tracking channels on an 8-bit IQ capture"
+(v = byte - off - dc on both arms): one sum routine, I_X = sum h_X (v_i C - v_q S), Q_X = sum h_X (v_i S + v_q C), serves both.
+
+audit() checks what a call of gpsacq_track or gpsacq_track_iq8 (or their CPU models) wrote for one channel: every epoch's geometry, its six sums,
 the loop arithmetic that took each record to the next, the final state field by field and why the call stopped.  It returns
 the branches the channel went through, so that tests can assert they reached what they aim at."""
 import numpy as np
@@ -54,9 +57,11 @@ def code_chips(P, prn):
     return [c[i] for i in idx]
 
 
-def epoch_sums(samples01, first_sample, prn, starts, ns, lo_phase, lo_rate, ca_pos, ca_rate, chunk_samples=1 << 21):
-    """The six sums (IE, QE, IP, QP, IL, QL) of epochs given by their start sample, length and NCO state (int arrays);
-    samples01: the window's samples, 0/1 (1 = negative).  Returns int64 [n_epochs][6]."""
+def _sums(samples, base, prn, starts, ns, lo_phase, lo_rate, ca_pos, ca_rate, chunk_samples):
+    """I_X = sum h_X (v_i C - v_q S), Q_X = sum h_X (v_i S + v_q C), X in E, P, L, of epochs given by their start sample, length and
+    NCO state (int arrays); samples(at) gives (v_i, v_q) of the samples base + at as integer arrays (v_q None: 0, the 1-bit
+    channel).  |v| <= 256 and an epoch has at most 65535 samples, so every sum is below 2^26 and exact as a float64 bincount.
+    Returns int64 [n_epochs][6]."""
     starts, ns = np.asarray(starts, np.int64), np.asarray(ns, np.int64)
     out = np.zeros((starts.size, 6), np.int64)
     a = 0
@@ -69,19 +74,44 @@ def epoch_sums(samples01, first_sample, prn, starts, ns, lo_phase, lo_rate, ca_p
         n = ns[a:b]
         ep = np.repeat(np.arange(b - a), n)
         j = np.arange(tot, dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)
-        x = samples01[np.repeat(starts[a:b] - first_sample, n) + j].astype(np.int8)
+        at = np.repeat(starts[a:b] - base, n) + j
         ph = (np.asarray(lo_phase[a:b], np.int64)[ep] + j * np.asarray(lo_rate[a:b], np.int64)[ep]) % TWO32
         P = np.asarray(ca_pos[a:b], np.int64)[ep] + j * np.asarray(ca_rate[a:b], np.int64)[ep]
         assert (P < FULL).all()
         cb, sb = carrier_signs(ph)
-        sv = 1 - 2 * x
-        cv, sn = 1 - 2 * cb, 1 - 2 * sb
+        C, S = 1 - 2 * cb, 1 - 2 * sb  # int8; the products below stay within +-512: int8 for 1-bit samples, int16 for 8-bit ones
+        xi, xq = samples(at)
+        if xq is None:
+            re_, im_ = xi * C, xi * S
+        else:
+            re_, im_ = xi * C - xq * S, xi * S + xq * C
         for k, ch in enumerate(code_chips(P, prn)):
-            prod = sv * (1 - 2 * ch)
-            out[a:b, 2 * k] = np.bincount(ep, weights=prod * cv, minlength=b - a).astype(np.int64)
-            out[a:b, 2 * k + 1] = np.bincount(ep, weights=prod * sn, minlength=b - a).astype(np.int64)
+            h = 1 - 2 * ch
+            out[a:b, 2 * k] = np.bincount(ep, weights=h * re_, minlength=b - a).astype(np.int64)
+            out[a:b, 2 * k + 1] = np.bincount(ep, weights=h * im_, minlength=b - a).astype(np.int64)
         a = b
     return out
+
+
+def epoch_sums(samples01, first_sample, prn, starts, ns, lo_phase, lo_rate, ca_pos, ca_rate, chunk_samples=1 << 21):
+    """The six sums (IE, QE, IP, QP, IL, QL) of epochs given by their start sample, length and NCO state (int arrays);
+    samples01: the window's samples, 0/1 (1 = negative): v_i = 1 - 2 x, v_q = 0.  Returns int64 [n_epochs][6]."""
+    return _sums(lambda at: (1 - 2 * samples01[at].astype(np.int8), None), first_sample, prn, starts, ns, lo_phase, lo_rate, ca_pos, ca_rate, chunk_samples)
+
+
+def iq_samples(iq, signed, dc_i, dc_q):
+    """(v_i, v_q) of interleaved I, Q bytes, "Tracking channels on an 8-bit IQ capture": v = byte - off - dc, off = 128 for unsigned
+    bytes and 0 for two's-complement ones.  int16 arrays (|v| <= 256)."""
+    raw = np.asarray(iq).view(np.uint8).astype(np.int16).reshape(-1, 2)
+    a = np.where(raw >= 128, raw - 256, raw) if signed else raw - 128
+    return a[:, 0] - np.int16(dc_i), a[:, 1] - np.int16(dc_q)
+
+
+def epoch_sums_iq(iq, first_sample, signed, dc_i, dc_q, prn, starts, ns, lo_phase, lo_rate, ca_pos, ca_rate, chunk_samples=1 << 21):
+    """epoch_sums for a window of complex integer samples: iq holds samples first_sample .. as interleaved I, Q bytes."""
+    pairs = np.asarray(iq).view(np.uint8).ravel()
+    pairs = pairs[:pairs.size // 2 * 2].reshape(-1, 2)
+    return _sums(lambda at: iq_samples(pairs[at], signed, dc_i, dc_q), first_sample, prn, starts, ns, lo_phase, lo_rate, ca_pos, ca_rate, chunk_samples)
 
 
 def _signed(v):
@@ -97,8 +127,10 @@ def _p(params, name):
     return int(params[name] if isinstance(params, dict) else getattr(params, name))
 
 
-def audit(bits, first_sample, chan0, params, records, n_epochs, chan_out, max_epochs=None, prompt=None, sum_epochs=None, seed=0):
-    """Check one channel's call of gpsacq_track over the window bits (uint8, samples first_sample ..): chan0 / chan_out are its
+def audit(bits, first_sample, chan0, params, records, n_epochs, chan_out, max_epochs=None, prompt=None, sum_epochs=None, seed=0, iq=None):
+    """Check one channel's call of gpsacq_track over the window bits (uint8, samples first_sample ..), or, with iq = (signed, dc_i,
+    dc_q), of gpsacq_track_iq8 in multi-bit mode over the window of interleaved I, Q bytes passed as `bits` (it ends at
+    first_sample + len(bits) // 2, any sample): chan0 / chan_out are its
     TRACK_CHAN_DTYPE record before and after, records its TRACK_RECORD_DTYPE rows (at least n_epochs), prompt its [epochs][2]
     rows if that output was written.  sum_epochs: recompute the sums of every epoch (None) or of that many seeded ones.
     Raises AssertionError on the first disagreement; returns the branches taken:
@@ -108,7 +140,7 @@ def audit(bits, first_sample, chan0, params, records, n_epochs, chan_out, max_ep
       period: it started away from chip 0), late_wrap / early_wrap (epochs whose late / early position wrapped)."""
     c0 = chan0
     prn = int(c0["prn"])
-    end = first_sample + 8 * len(bits)
+    end = first_sample + (8 * len(bits) if iq is None else len(bits) // 2)
     rep = dict(agc_down=0, agc_up=0, agc_polls=0, ring_wraps=0, fll_epochs=0, costas_epochs=0, costas_adj_epochs=0, aid=[], lost=set(),
                stop=None, short_first=False, late_wrap=0, early_wrap=0, epochs=int(n_epochs))
     lo_ki, lo_kp, ca_ki, ca_kp, fll_k = (_p(params, k) for k in ("lo_ki", "lo_kp", "ca_ki", "ca_kp", "fll_k"))
@@ -227,10 +259,14 @@ def audit(bits, first_sample, chan0, params, records, n_epochs, chan_out, max_ep
             sel = np.sort(np.random.default_rng(seed).choice(n_epochs, sum_epochs, replace=False))
         lo = int(geo[sel, 0].min()) - first_sample
         hi = int((geo[sel, 0] + geo[sel, 1]).max()) - first_sample
-        b0, b1 = lo // 8, (hi + 7) // 8
-        s01 = np.unpackbits(np.asarray(bits[b0:b1], np.uint8), bitorder="little")
         g = geo[sel]
-        got = epoch_sums(s01, first_sample + 8 * b0, prn, g[:, 0], g[:, 1], g[:, 2], g[:, 3], g[:, 4], g[:, 5])
+        if iq is None:
+            b0, b1 = lo // 8, (hi + 7) // 8
+            s01 = np.unpackbits(np.asarray(bits[b0:b1], np.uint8), bitorder="little")
+            got = epoch_sums(s01, first_sample + 8 * b0, prn, g[:, 0], g[:, 1], g[:, 2], g[:, 3], g[:, 4], g[:, 5])
+        else:
+            got = epoch_sums_iq(np.asarray(bits).view(np.uint8).ravel()[2 * lo:2 * hi], first_sample + lo, iq[0], iq[1], iq[2], prn,
+                                g[:, 0], g[:, 1], g[:, 2], g[:, 3], g[:, 4], g[:, 5])
         bad = np.nonzero((got != sums[sel]).any(axis=1))[0]
         assert bad.size == 0, ("sums", int(sel[bad[0]]), got[bad[0]].tolist(), sums[sel[bad[0]]].tolist())
     return rep
