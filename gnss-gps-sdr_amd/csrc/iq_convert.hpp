@@ -74,6 +74,10 @@ __device__ __forceinline__ void iq8_complex(unsigned pair, size_t n, const IqCon
 // r_fast = yi cs - yq sn is within 512 x 1e-6 + 1e-4 (float products of |y| <= 256) < 7e-4 of the double result.  Only when
 // |r_fast| < 5e-3 -- one sample in a few thousand -- is the bit taken from the double-precision path; elsewhere both agree on the
 // sign by construction, so the stream is the same bit for bit (tests/test_iq.py, the IQ modes of tools/fuzz_gpu.py).
+// That budget is probed by tests/test_gpu_iq_edges.py against an independent reference (tests/iq_ref.py): every byte pair at 16 phases,
+// samples built to put r next to zero and next to the threshold, fc = fs / 4, the rails, capture indices up to 2^40 -- no decided
+// sign differs.  With the threshold at 5e-6 a handful of samples per 65 536 adversarial ones flip (the fast path's real error is
+// some 1e-5, well inside the budget); without the second term of 2 pi the 2^40 case fails (k ~ 2.4e11 turns the phase by 6e-5).
 __device__ __forceinline__ unsigned iq8_bit(unsigned pair, size_t n, const IqConv& c) {
     if (!c.mix) return iq8_value(pair, n, c) > 0.0 ? 0u : 1u;  // no trigonometry on this path
     double yi, yq;
