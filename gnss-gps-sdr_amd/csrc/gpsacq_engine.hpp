@@ -13,6 +13,7 @@
 #include "gen_launch.hpp"
 #include "nav_launch.hpp"
 #include "obs_launch.hpp"
+#include "quality_launch.hpp"
 #include "raim_launch.hpp"
 #include "smooth_launch.hpp"
 
@@ -153,6 +154,15 @@ struct gpsacq_engine {
     size_t smooth_info_cap = 0;
     hipEvent_t smooth_ev[5] = {};  // before k_lock_acc, then after each of k_lock_acc, k_cmc, k_smooth_scan, k_smooth_out
     bool smooth_timed = false;
+    // signal quality (gpsacq_quality_observables*, gpsacq_fix_quality_track_device)
+    acq::QualityChan* d_quality_chan = nullptr;
+    size_t quality_chan_cap = 0;
+    uint64_t* d_quality_sums = nullptr;  // k_quality_acc's three outputs: [3][n_chans][max_epochs + 1]
+    size_t quality_sums_cap = 0;
+    gpsacq_quality_info* d_quality_info = nullptr;  // host-buffer form, and where the caller of the chain wants no info
+    size_t quality_info_cap = 0;
+    hipEvent_t quality_ev[3] = {};  // before k_quality_acc, between the kernels, after k_quality_out
+    bool quality_timed = false;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;

@@ -678,6 +678,153 @@ extern "C" int gpsacq_smooth_last_ms(const gpsacq_engine* e, float* lock_acc_ms,
     return GPSACQ_OK;
 }
 
+// ---- signal quality per observation (quality_kernels.hip) -----------------------------------------------------------------
+extern "C" int gpsacq_quality_default_params(gpsacq_quality_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_quality_default_params: null argument");
+    std::memset(p, 0, sizeof *p);
+    p->epochs = 200;
+    p->min_epochs = 20;
+    p->lock_num = 1, p->lock_den = 2;
+    p->require_lock = 1;
+    p->cn0_min_lin = std::pow(10.0, 30.0 / 10.0);
+    p->cn0_ref_lin = std::pow(10.0, 45.0 / 10.0);
+    p->cn0_cap_dbhz = 99.0;
+    return GPSACQ_OK;
+}
+
+// the caller's parameters or the defaults into *out, checked
+static int quality_params(const char* who, const gpsacq_quality_params* params, gpsacq_quality_params* out) {
+    if (!params) return gpsacq_quality_default_params(out);
+    *out = *params;
+    if (out->min_epochs < 1 || out->min_epochs > out->epochs || out->epochs > 1024)
+        return fail(GPSACQ_ERR_ARG, "%s: min_epochs / epochs %d / %d outside 1 <= min_epochs <= epochs <= 1024", who, out->min_epochs, out->epochs);
+    if (out->lock_num < 1 || out->lock_num > out->lock_den || out->lock_den > 1024)
+        return fail(GPSACQ_ERR_ARG, "%s: lock_num / lock_den %d / %d outside 1 <= num <= den <= 1024", who, out->lock_num, out->lock_den);
+    if (!(out->cn0_min_lin >= 0.0) || !std::isfinite(out->cn0_min_lin)) return fail(GPSACQ_ERR_ARG, "%s: cn0_min_lin %g must be finite and >= 0", who, out->cn0_min_lin);
+    if (!(out->cn0_ref_lin > 0.0) || !std::isfinite(out->cn0_ref_lin)) return fail(GPSACQ_ERR_ARG, "%s: cn0_ref_lin %g must be finite and > 0", who, out->cn0_ref_lin);
+    if (!std::isfinite(out->cn0_cap_dbhz)) return fail(GPSACQ_ERR_ARG, "%s: cn0_cap_dbhz must be finite", who);
+    return GPSACQ_OK;
+}
+
+static int quality_check(const char* who, const gpsacq_engine* e, const void* records, int max_epochs, const int32_t* n_epochs,
+                         const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans, uint64_t first_rx_sample, uint64_t rx_step,
+                         size_t n_fix, const gpsacq_quality_params* params, gpsacq_quality_params* checked) {
+    if (int rc = obs_check(who, e, records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix)) return rc;
+    return quality_params(who, params, checked);
+}
+
+// both kernels on the engine's stream, into scratch of their own; every argument has been checked
+static int quality_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
+                           const gpsacq_time_tag* tags, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix,
+                           const gpsacq_quality_params& qp, void* d_obs, void* d_info) {
+    QualityChan tab[GPSACQ_FIX_MAX_SATS];
+    for (int c = 0; c < n_chans; ++c) {
+        tab[c].next_sample = chans[c].next_sample;
+        tab[c].n = n_epochs[c];
+        tab[c].tag_valid = tags[c].valid;
+    }
+    const size_t row = (size_t)max_epochs + 1, nc = (size_t)n_chans;
+    if (int rc = grow(e->d_quality_chan, e->quality_chan_cap, (size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
+    if (int rc = grow(e->d_quality_sums, e->quality_sums_cap, 3 * nc * row, e->stream)) return rc;
+    for (auto& ev : e->quality_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    // pageable source: the copy has left `tab` when the call returns
+    HIPCHK(hipMemcpyAsync(e->d_quality_chan, tab, nc * sizeof(QualityChan), hipMemcpyHostToDevice, e->stream));
+    const gpsacq_track_record* rec = (const gpsacq_track_record*)d_records;
+    uint64_t *sum_a = e->d_quality_sums, *sum_d = sum_a + nc * row, *sum_n = sum_d + nc * row;
+    e->quality_timed = false;
+    HIPCHK(hipEventRecord(e->quality_ev[0], e->stream));
+    launch_quality_acc(QualityAccArgs{e->d_quality_chan, rec, max_epochs, sum_a, sum_d, sum_n}, n_chans, e->stream);
+    HIPCHK(hipEventRecord(e->quality_ev[1], e->stream));
+    launch_quality_out(QualityOutArgs{e->d_quality_chan, rec, sum_a, sum_d, sum_n, max_epochs, n_chans, first_rx_sample, rx_step, n_fix, qp,
+                                      (gpsacq_obs*)d_obs, (gpsacq_quality_info*)d_info},
+                       e->stream);
+    HIPCHK(hipEventRecord(e->quality_ev[2], e->stream));
+    HIPCHK(hipGetLastError());
+    e->quality_timed = true;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_quality_observables_device(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs,
+                                                 const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans,
+                                                 uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, const gpsacq_quality_params* params,
+                                                 void* d_obs, void* d_info, int sync) {
+    gpsacq_quality_params qp;
+    if (int rc = quality_check("gpsacq_quality_observables", e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, params, &qp)) return rc;
+    if (!d_info) return fail(GPSACQ_ERR_ARG, "gpsacq_quality_observables: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = quality_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, qp, d_obs, d_info)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_quality_observables(gpsacq_engine* e, const gpsacq_track_record* records, int max_epochs, const int32_t* n_epochs,
+                                          const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans, uint64_t first_rx_sample,
+                                          uint64_t rx_step, size_t n_fix, const gpsacq_quality_params* params, gpsacq_obs* obs,
+                                          gpsacq_quality_info* info) {
+    gpsacq_quality_params qp;
+    if (int rc = quality_check("gpsacq_quality_observables", e, records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, params, &qp)) return rc;
+    if (!info) return fail(GPSACQ_ERR_ARG, "gpsacq_quality_observables: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_obs = n_fix * (size_t)n_chans;
+    if (int rc = grow(e->d_obs_rec, e->obs_rec_cap, (size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
+    if (int rc = grow(e->d_quality_info, e->quality_info_cap, n_obs, e->stream)) return rc;
+    if (obs) {
+        if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+        HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    }
+    for (int c = 0; c < n_chans; ++c)  // the rows keep their stride; only the records that exist travel
+        if (n_epochs[c] > 0)
+            HIPCHK(hipMemcpyAsync(e->d_obs_rec + (size_t)c * max_epochs, records + (size_t)c * max_epochs,
+                                  (size_t)n_epochs[c] * sizeof(gpsacq_track_record), hipMemcpyHostToDevice, e->stream));
+    if (int rc = quality_enqueue(e, e->d_obs_rec, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, qp,
+                                 obs ? e->d_nav_obs : nullptr, e->d_quality_info))
+        return rc;
+    if (obs) HIPCHK(hipMemcpyAsync(obs, e->d_nav_obs, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(info, e->d_quality_info, n_obs * sizeof(gpsacq_quality_info), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fix_quality_track_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_records, int max_epochs,
+                                               const int32_t* n_epochs, const gpsacq_track_chan* chans, const gpsacq_time_tag* tags,
+                                               const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix,
+                                               const gpsacq_smooth_params* smooth, const gpsacq_quality_params* quality, void* d_obs,
+                                               void* d_info, void* d_fix, int sync) {
+    gpsacq_quality_params qp;
+    gpsacq_smooth_params sp;
+    if (int rc = quality_check("gpsacq_fix_quality_track", e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, quality, &qp)) return rc;
+    if (!eph || n_eph <= 0 || !d_fix || (smooth && !nom_words)) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_quality_track: bad argument");
+    if (smooth)
+        if (int rc = smooth_params("gpsacq_fix_quality_track", smooth, &sp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_obs = n_fix * (size_t)n_chans;
+    if (!d_obs) {
+        if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+        d_obs = e->d_nav_obs;
+    }
+    if (!d_info) {
+        if (int rc = grow(e->d_quality_info, e->quality_info_cap, n_obs, e->stream)) return rc;
+        d_info = e->d_quality_info;
+    }
+    if (smooth) {
+        if (int rc = smooth_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, nom_words, n_chans, first_rx_sample, rx_step, n_fix, sp, d_obs, nullptr)) return rc;
+    } else {
+        if (int rc = obs_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, d_obs)) return rc;
+    }
+    if (int rc = quality_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, qp, d_obs, d_info)) return rc;
+    return gpsacq_fix_batch_device(e, eph, n_eph, d_obs, n_fix, n_chans, d_fix, sync);
+}
+
+extern "C" int gpsacq_quality_last_ms(const gpsacq_engine* e, float* acc_ms, float* out_ms) {
+    if (!e || !e->quality_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_quality_last_ms: no gpsacq_quality_observables call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    HIPCHK(hipEventSynchronize(e->quality_ev[2]));
+    if (acc_ms) HIPCHK(hipEventElapsedTime(acc_ms, e->quality_ev[0], e->quality_ev[1]));
+    if (out_ms) HIPCHK(hipEventElapsedTime(out_ms, e->quality_ev[1], e->quality_ev[2]));
+    return GPSACQ_OK;
+}
+
 // ---- atmosphere, elevation mask and DOP (fix_kernels.hip) --------------------------------------------------------------------
 extern "C" int gpsacq_iono_load(gpsacq_iono* io, const gpsacq_subframe* sf, int n) {
     if (!io || n < 0 || (n > 0 && !sf)) return fail(GPSACQ_ERR_ARG, "gpsacq_iono_load: bad argument");

@@ -19,6 +19,11 @@
 // 1000th instant -- the same once-a-second instants -- in the same format, and after the fixes one line per channel with the
 // scatter of the code against the carrier over the full windows (the measured pseudorange sigma, metres):
 //     sigma PRN P code_sigma_m S full N
+// With GPSACQ_QUALITY=1 every whole second of the capture at which a channel has records gets one line with the C/N0 estimate of
+// every such channel (gpsacq_quality_observables at its default parameters: dB-Hz over the last 200 epochs, the flags
+// GPSACQ_QUALITY_* as a number), printed after the channels' own lines, and the fixes are made from observations that carry the
+// weights of that estimate (a channel below 30 dB-Hz or out of phase lock has none); without it the output is unchanged:
+//     cn0 sec K PRN P dbhz X flags F [PRN P dbhz X flags F ...]
 //
 // With GPSACQ_INPUT=iq_u8|iq_s8 in the environment FILE is an 8-bit IQ capture (rtl-sdr / HackRF, README.md:83-115), read the way
 // gps_test reads it (host/search_api.cpp: GPSACQ_MIX_HZ, GPSACQ_IQ_KEEP_DC, GPSACQ_IQ_MULTIBIT, GPSACQ_IQ_COMPLEX; the mean of the
@@ -187,6 +192,39 @@ int main(int argc, char** argv) {
             fix_chan.push_back(c);
         }
     }
+    const bool want_quality = env_int("GPSACQ_QUALITY", 0) != 0;
+    const uint64_t second = (uint64_t)std::llround(prm.fs);
+    if (want_quality && !chans.empty() && second > 0 && n_samples > second) {
+        // the estimate needs no time tag beyond `valid`: every channel, twelve to a call, at the whole seconds inside the capture
+        const size_t n_sec = (size_t)((n_samples - 1) / second);
+        std::vector<gpsacq_quality_info> qi(n_sec * chans.size()), part(n_sec * GPSACQ_FIX_MAX_SATS);
+        gpsacq_time_tag any[GPSACQ_FIX_MAX_SATS];
+        std::memset(any, 0, sizeof any);
+        for (auto& t : any) t.valid = 1;
+        for (size_t g0 = 0; rc == 0 && g0 < chans.size(); g0 += GPSACQ_FIX_MAX_SATS) {
+            const size_t ng = chans.size() - g0 < GPSACQ_FIX_MAX_SATS ? chans.size() - g0 : GPSACQ_FIX_MAX_SATS;
+            rc = gpsacq_quality_observables(e, records.data() + g0 * (size_t)max_epochs, max_epochs, n_ep.data() + g0, chans.data() + g0, any, (int)ng,
+                                            second, second, n_sec, nullptr, nullptr, part.data());
+            for (size_t k = 0; rc == 0 && k < n_sec; ++k)
+                for (size_t c = 0; c < ng; ++c) qi[k * chans.size() + g0 + c] = part[k * ng + c];
+        }
+        if (rc) {
+            std::fprintf(stderr, "gps_track: %d: %s\n", rc, gpsacq_last_error());
+            gpsacq_destroy(e);
+            return rc;
+        }
+        for (size_t k = 0; k < n_sec; ++k) {
+            bool head = false;
+            for (size_t c = 0; c < chans.size(); ++c) {
+                const gpsacq_quality_info& q = qi[k * chans.size() + c];
+                if (q.epochs == 0) continue;
+                if (!head) std::printf("cn0 sec %zu", k + 1);
+                head = true;
+                std::printf(" PRN %d dbhz %.2f flags %d", chans[c].prn, q.cn0_dbhz, q.flags);
+            }
+            if (head) std::printf("\n");
+        }
+    }
     if (fix_chan.size() >= 4) {
         const size_t m = fix_chan.size();
         std::vector<gpsacq_track_record> rec(m * (size_t)max_epochs);
@@ -237,6 +275,12 @@ int main(int argc, char** argv) {
                 }
             } else if (rc == 0) {
                 rc = gpsacq_observables(e, rec.data(), max_epochs, fn.data(), fch.data(), tags.data(), (int)m, first_rx, step, n_fix, obs.data());
+            }
+            if (rc == 0 && want_quality) {
+                // the weights of the same instants into the observations: smoothed ones lie 1000 millisecond steps apart
+                std::vector<gpsacq_quality_info> qinfo(n_fix * m);
+                rc = gpsacq_quality_observables(e, rec.data(), max_epochs, fn.data(), fch.data(), tags.data(), (int)m, first_rx,
+                                                n_ms > 0 ? 1000 * ms_step : step, n_fix, nullptr, obs.data(), qinfo.data());
             }
             if (rc == 0) rc = gpsacq_fix_batch(e, ephs.data(), (int)ephs.size(), obs.data(), n_fix, (int)m, fix.data());
             if (rc) {

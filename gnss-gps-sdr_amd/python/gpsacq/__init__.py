@@ -116,6 +116,13 @@ SMOOTH_INFO_DTYPE = np.dtype([("window", "<i4"), ("flags", "<i4"), ("cmc", "<i8"
 L1_HZ = 1575.42e6
 C_MPS = 299792458.0
 
+# signal quality per observation (include/gpsacq.h "Signal quality per observation")
+QUALITY_NO_POWER, QUALITY_SATURATED, QUALITY_UNLOCKED, QUALITY_FULL, QUALITY_SHORT = 1, 2, 4, 8, 16
+QUALITY_PARAMS_DTYPE = np.dtype([("epochs", "<i4"), ("min_epochs", "<i4"), ("lock_num", "<i4"), ("lock_den", "<i4"), ("require_lock", "<i4"),
+                                 ("reserved", "<i4"), ("cn0_min_lin", "<f8"), ("cn0_ref_lin", "<f8"), ("cn0_cap_dbhz", "<f8")])
+QUALITY_INFO_DTYPE = np.dtype([("epochs", "<i4"), ("flags", "<i4"), ("sig", "<u8"), ("noise", "<u8"), ("lin", "<f8"), ("cn0_dbhz", "<f8"),
+                               ("weight", "<f8")])
+
 
 class TrackParams(ctypes.Structure):
     _fields_ = [("lo_ki", ctypes.c_int32), ("lo_kp", ctypes.c_int32), ("ca_ki", ctypes.c_int32), ("ca_kp", ctypes.c_int32),
@@ -146,7 +153,9 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_fix_atm_batch_device", "gpsacq_fix_atm_last_ms",
            "gpsacq_raim_default_params", "gpsacq_fix_raim_batch", "gpsacq_fix_raim_batch_device", "gpsacq_fix_raim_last_ms",
            "gpsacq_smooth_default_params", "gpsacq_smooth_observables", "gpsacq_smooth_observables_device", "gpsacq_fix_smooth_track_device",
-           "gpsacq_smooth_last_ms"]
+           "gpsacq_smooth_last_ms",
+           "gpsacq_quality_default_params", "gpsacq_quality_observables", "gpsacq_quality_observables_device",
+           "gpsacq_fix_quality_track_device", "gpsacq_quality_last_ms"]
 
 _lib = None
 
@@ -395,6 +404,18 @@ def load_library(path=None):
     lib.gpsacq_fix_smooth_track_device.restype = ctypes.c_int
     lib.gpsacq_smooth_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 4
     lib.gpsacq_smooth_last_ms.restype = ctypes.c_int
+    lib.gpsacq_quality_default_params.argtypes = [vp]
+    lib.gpsacq_quality_default_params.restype = ctypes.c_int
+    quality_args = [vp, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, u64, u64, sz, vp, vp, vp]
+    lib.gpsacq_quality_observables.argtypes = quality_args
+    lib.gpsacq_quality_observables.restype = ctypes.c_int
+    lib.gpsacq_quality_observables_device.argtypes = quality_args + [ctypes.c_int]
+    lib.gpsacq_quality_observables_device.restype = ctypes.c_int
+    lib.gpsacq_fix_quality_track_device.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, u64, u64, sz, vp, vp, vp, vp,
+                                                    vp, ctypes.c_int]
+    lib.gpsacq_fix_quality_track_device.restype = ctypes.c_int
+    lib.gpsacq_quality_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
+    lib.gpsacq_quality_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -512,6 +533,23 @@ def smooth_params(**overrides):
         if k not in SMOOTH_PARAMS_DTYPE.names:
             raise TypeError("smooth_params: no field %r" % k)
         out[k] = int(v)
+    return out
+
+
+def quality_params(cn0_min_dbhz=30, cn0_ref_dbhz=45, **overrides):
+    """gpsacq_quality_default_params: a QUALITY_PARAMS_DTYPE record of shape (1,) -- a window of 200 epochs, at least 20 of them,
+    phase lock at a ratio of 1 / 2 and required, cn0_cap_dbhz 99 -- with the gate cn0_min_lin = 10^(cn0_min_dbhz / 10), the
+    reference level cn0_ref_lin = 10^(cn0_ref_dbhz / 10) (weight 1 from there up), and then the named fields replaced.  The entry
+    points that take it check it."""
+    lib = load_library()
+    out = np.zeros(1, dtype=QUALITY_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_quality_default_params(out.ctypes.data_as(ctypes.c_void_p)))
+    out["cn0_min_lin"] = 10.0 ** (float(cn0_min_dbhz) / 10.0)
+    out["cn0_ref_lin"] = 10.0 ** (float(cn0_ref_dbhz) / 10.0)
+    for k, v in overrides.items():
+        if k not in QUALITY_PARAMS_DTYPE.names:
+            raise TypeError("quality_params: no field %r" % k)
+        out[k] = v
     return out
 
 
@@ -1181,6 +1219,68 @@ class Engine:
         t = [ctypes.c_float() for _ in range(4)]
         _check(self._lib, self._lib.gpsacq_smooth_last_ms(self._h, *[ctypes.byref(x) for x in t]))
         return tuple(x.value for x in t)
+
+    # ---- signal quality per observation ---------------------------------------------------
+    @staticmethod
+    def _quality_params(params):
+        if params is None:
+            return None
+        pr = np.ascontiguousarray(np.asarray(params, dtype=QUALITY_PARAMS_DTYPE).ravel())
+        if pr.size != 1:
+            raise ValueError("params must be one QUALITY_PARAMS_DTYPE record")
+        return pr
+
+    def quality(self, records, n_epochs, chans, tags, first_rx_sample, rx_step, n_fix, params=None, obs=None):
+        """gpsacq_quality_observables: C/N0 (dB-Hz), phase lock and the weight of every channel at the receive samples
+        first_rx_sample + i * rx_step, from the prompt sums of the records; arguments as observables().  params: quality_params()
+        (None: the defaults).  Returns info, QUALITY_INFO_DTYPE [n_fix][n_chans]; with obs (OBS_DTYPE [n_fix][n_chans] made for the
+        same instants by observables() or smooth_observables()) returns (a copy of obs with the weights set, info)."""
+        ne, ch, tg = self._obs_arrays(n_epochs, chans, tags)
+        pr = self._quality_params(params)
+        if not isinstance(records, np.ndarray) or records.dtype != TRACK_RECORD_DTYPE or records.ndim != 2 or records.shape[0] != ne.size:
+            raise TypeError("records must be a TRACK_RECORD_DTYPE array [n_chans][max_epochs]")
+        rec = np.ascontiguousarray(records)
+        ob = None
+        if obs is not None:
+            if not isinstance(obs, np.ndarray) or obs.dtype != OBS_DTYPE or obs.shape != (int(n_fix), ne.size):
+                raise TypeError("obs must be an OBS_DTYPE array [n_fix][n_chans]")
+            ob = np.array(obs, order="C")
+        inf = np.zeros((int(n_fix), ne.size), dtype=QUALITY_INFO_DTYPE)
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_quality_observables(self._h, p(rec), int(rec.shape[1]), p(ne), p(ch), p(tg), int(ne.size),
+                                                               int(first_rx_sample), int(rx_step), int(n_fix), p(pr), p(ob), p(inf)))
+        return inf if obs is None else (ob, inf)
+
+    def quality_device(self, d_records_ptr, max_epochs, n_epochs, chans, tags, first_rx_sample, rx_step, n_fix, d_info_ptr, d_obs_ptr=None,
+                       params=None, sync=True):
+        """gpsacq_quality_observables_device: records, info and the in-out observations (may be None) in device memory, the rest host
+        arrays."""
+        ne, ch, tg = self._obs_arrays(n_epochs, chans, tags)
+        pr = self._quality_params(params)
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_quality_observables_device(self._h, d_records_ptr, int(max_epochs), p(ne), p(ch), p(tg), int(ne.size),
+                                                                      int(first_rx_sample), int(rx_step), int(n_fix), p(pr), d_obs_ptr, d_info_ptr,
+                                                                      1 if sync else 0))
+
+    def fix_quality_track_device(self, eph, d_records_ptr, max_epochs, n_epochs, chans, tags, first_rx_sample, rx_step, n_fix, d_fix_ptr,
+                                 d_obs_ptr=None, d_info_ptr=None, quality_params=None, smooth_params=None, nom_words=None, sync=True):
+        """gpsacq_fix_quality_track_device: observables_device (smooth_params None) or smooth_observables_device, then the quality
+        weights, then fix_device, on the engine's stream with no host copy in between.  d_fix: FIX_DTYPE [n_fix] in device memory;
+        d_obs_ptr / d_info_ptr None keep those in engine scratch; nom_words as in rate_observables(), read only when smoothing."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        ne, ch, tg = self._obs_arrays(n_epochs, chans, tags)
+        nw = None if smooth_params is None else self._rate_arrays(n_epochs, chans, nom_words)[2]
+        qp, sp = self._quality_params(quality_params), self._smooth_params(smooth_params)
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_fix_quality_track_device(self._h, p(ep), int(ep.size), d_records_ptr, int(max_epochs), p(ne), p(ch), p(tg),
+                                                                    p(nw), int(ne.size), int(first_rx_sample), int(rx_step), int(n_fix), p(sp), p(qp),
+                                                                    d_obs_ptr, d_info_ptr, d_fix_ptr, 1 if sync else 0))
+
+    def quality_last_ms(self):
+        """Device milliseconds of the last quality* / fix_quality_track_device call: (prefix-sum kernel, output kernel)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(self._lib, self._lib.gpsacq_quality_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     # ---- tracking channels on an 8-bit IQ capture -----------------------------------------
     def iq8_power(self, iq, signed=False):

@@ -1083,6 +1083,113 @@ GPSACQ_API int gpsacq_fix_smooth_track_device(gpsacq_engine* e, const gpsacq_eph
 GPSACQ_API int gpsacq_smooth_last_ms(const gpsacq_engine* e, float* lock_acc_ms, float* cmc_ms, float* scan_ms, float* out_ms);
 
 /*
+ * ---- Signal quality per observation: C/N0, phase lock and the weight of an observation ----------------------------------------
+ *
+ * Every solver here is a weighted least-squares solver and every observation maker above writes weight = 1.0.  This section makes
+ * the weight: per channel and receive instant a carrier-to-noise density estimate from the prompt correlator sums, the phase-lock
+ * ratio over the same window, and from the two a weight in [0, 1].  THE MODEL; the kernels (csrc/quality_kernels.hip) and the
+ * reference of the tests (tests/quality_ref.py) are both written from this text.  Integers are uint64, "mod 2^64" is unsigned
+ * wrap-around, "(int64)" reads such a value as two's complement; every floating-point step is ONE named IEEE double operation
+ * (no fast-math flag and no contraction in the build).
+ *
+ * INPUTS: those of gpsacq_observables -- records[c][0..n-1] of ONE tracking call (1-bit or multi-bit: the layout is the same),
+ * n = n_epochs[c], chans[c] after that call, tags[c], the RECEIVE INSTANTS R_i = first_rx_sample + i * rx_step, i < n_fix -- and
+ * a gpsacq_quality_params.
+ *
+ * USABLE INSTANT: exactly OBSERVATION's: tag.valid != 0, n > 0 and records[c][0].sample <= R_i < next_sample; t is found by the
+ * same rule, sample_t <= R_i < end_t.  Any other instant is INVALID: its info is 48 zero bytes (and its weight is 0).
+ *
+ * WINDOW of a usable instant: the epochs u = t-m+1 .. t, m = min(t + 1, params.epochs).  With ip_u, qp_u sign-extended to 64 bits,
+ * products and sums mod 2^64:
+ *     A     = sum |ip_u|
+ *     D     = sum (ip_u^2 + qp_u^2)
+ *     N     = sum (ip_u^2 - qp_u^2)
+ *     sig   = A * A
+ *     tot   = m * D
+ *     noise = tot - sig
+ * This is the signal-to-noise-variance estimator (Pauluzzi and Beaulieu, IEEE Trans. Commun. 48 (2000)): the squared mean of
+ * |I_P| is the signal power (times m^2), the total prompt power less that is the noise power (times m^2).  The absolute value
+ * takes the navigation bit out, so no bit synchronisation and nothing of the tag beyond `valid` is needed.  By Cauchy-Schwarz
+ * A^2 <= m * sum ip^2 <= m * D, so noise >= 0 whenever nothing wraps, and nothing wraps while |ip|, |qp| < 2^21 and
+ * epochs <= 1024 (the bound the smoothing text states; tot < 2^10 * 2^10 * 2^43 = 2^63) -- for 1-bit channels, |ip| <= 65535,
+ * always.  Beyond that bound the arithmetic mod 2^64 still defines ONE answer, and that is the answer.
+ *
+ * VALUES.
+ *     D == 0 or sig == 0:   flag GPSACQ_QUALITY_NO_POWER, lin = cn0_dbhz = weight = 0
+ *     else noise == 0:      flag GPSACQ_QUALITY_SATURATED, lin = +infinity, cn0_dbhz = params.cn0_cap_dbhz
+ *     else:                 snr      = (double)sig / (double)noise      both conversions uint64 -> double, round to nearest even;
+ *                                                                       one division
+ *                           lin      = snr * 1000.0                     one epoch is one code period, nominally 1000 per second;
+ *                                                                       the Doppler stretch of a few ppm is ignored
+ *                           cn0_dbhz = 10.0 * log10(lin)
+ * D, sig and noise are compared as uint64 ("D == 0" is all 64 bits zero).  info.sig and info.noise hold sig and noise as computed,
+ * in every one of the three cases.
+ *
+ * LOCK.  locked iff D != 0 and (int64)(N * lock_den) >= (int64)(D * lock_num): the products of the smoothing section's PHASE
+ * LOCK, taken over this window (which may be shorter than params.epochs).  Not locked: flag GPSACQ_QUALITY_UNLOCKED.
+ *
+ * WINDOW LENGTH.  Flag GPSACQ_QUALITY_FULL when m == params.epochs, flag GPSACQ_QUALITY_SHORT when m < params.min_epochs.
+ *
+ * WEIGHT.  weight = 0 if NO_POWER, or SHORT, or UNLOCKED with params.require_lock != 0, or lin < params.cn0_min_lin.  Otherwise
+ *     w      = lin / params.cn0_ref_lin            one division (+infinity stays +infinity)
+ *     weight = w < 1.0 ? w : 1.0                   SATURATED gives 1.0
+ * The gate and the weight read lin, never cn0_dbhz, so every field but cn0_dbhz is reproducible byte for byte; log10 is the only
+ * libm call.  The weight is proportional to C/N0 up to the reference level -- the thermal-noise law of a delay-locked loop's range
+ * variance -- and sigma_m of gpsacq_raim_default_params is then the pseudorange sigma at cn0_ref.
+ *
+ * INFO per (instant, channel), gpsacq_quality_info, 48 bytes: epochs = m, flags, sig, noise, lin, cn0_dbhz, weight.
+ *
+ * THE OBSERVATION.  When a gpsacq_obs array made for the SAME instants is given (raw or smoothed; valid and usable then coincide),
+ * every observation with valid != 0 has its weight replaced by this weight.  No other byte of it is written, and an observation
+ * with valid == 0 is not written at all.
+ *
+ * PARAMETERS.  gpsacq_quality_default_params (host only): epochs 200, min_epochs 20, lock_num / lock_den 1 / 2, require_lock 1,
+ * reserved 0, cn0_min_lin 10^(30/10) = 1000.0, cn0_ref_lin 10^(45/10) (pow(10.0, 4.5)), cn0_cap_dbhz 99.0.  Valid:
+ * 1 <= min_epochs <= epochs <= 1024, 1 <= lock_num <= lock_den <= 1024, cn0_min_lin finite and >= 0, cn0_ref_lin finite and > 0,
+ * cn0_cap_dbhz finite; anything else is GPSACQ_ERR_ARG.  params NULL = the defaults.
+ *
+ * NOTES.  Noise alone (ip, qp independent, zero mean, equal variance) reads snr = (2/pi) / (2 - 2/pi) = 0.467: 26.7 dB-Hz is
+ * the estimator's floor, no channel reads lower for long, and that is why the default gate sits at 30.  During FLL pull-in the
+ * power is shared between the two arms, so the estimate reads LOW; that is what require_lock is for.  On 1-bit channels (and
+ * sign-mode IQ channels) the samples have been through a hard limiter: this is the C/N0 AFTER the limiter, not the antenna's.
+ *
+ * gpsacq_quality_observables: host pointers, returns after completion; obs[n_fix][n_chans] in-out and may be NULL,
+ * info[n_fix][n_chans] index-parallel.  gpsacq_quality_observables_device: records, obs (may be NULL) and info are device pointers,
+ * the rest host pointers; work on the engine's stream, sync != 0 waits.  gpsacq_fix_quality_track_device: observations by
+ * gpsacq_observables_device -- or, when smooth_params != NULL, by gpsacq_smooth_observables_device with those parameters; nom_words
+ * is then required, otherwise it is not read -- then the weights, then gpsacq_fix_batch_device, all on the engine's stream with no
+ * host copy in between; d_obs and d_info may be NULL (engine scratch), d_fix[n_fix].  Argument errors are those of
+ * gpsacq_observables plus the parameter ranges (and info == NULL): GPSACQ_ERR_ARG, nothing launched, nothing written.  Two kernels:
+ * k_quality_acc, one wave64 per channel, k_lock_acc's idiom: the prefix sums of |ip|, ip^2 + qp^2 and ip^2 - qp^2 over the epochs
+ * ([3][n_chans][max_epochs + 1] in engine scratch of its own); k_quality_out, one lane per (instant, channel): the bisection for t,
+ * the window sums as differences of prefix sums, the info record and the weight.
+ */
+#define GPSACQ_QUALITY_NO_POWER 1    /* D == 0 or sig == 0: nothing to estimate from */
+#define GPSACQ_QUALITY_SATURATED 2   /* noise == 0: lin = +infinity, cn0_dbhz = cn0_cap_dbhz */
+#define GPSACQ_QUALITY_UNLOCKED 4    /* the phase-lock ratio over the window is below lock_num / lock_den */
+#define GPSACQ_QUALITY_FULL 8        /* the window has its full length */
+#define GPSACQ_QUALITY_SHORT 16      /* the window is shorter than min_epochs */
+typedef struct { int32_t epochs, min_epochs, lock_num, lock_den, require_lock, reserved; double cn0_min_lin, cn0_ref_lin, cn0_cap_dbhz; } gpsacq_quality_params;   /* 48 bytes */
+typedef struct { int32_t epochs; int32_t flags; uint64_t sig; uint64_t noise; double lin; double cn0_dbhz; double weight; } gpsacq_quality_info;                     /* 48 bytes */
+GPSACQ_API int gpsacq_quality_default_params(gpsacq_quality_params* p);   /* host only */
+GPSACQ_API int gpsacq_quality_observables(gpsacq_engine* e, const gpsacq_track_record* records, int max_epochs, const int32_t* n_epochs,
+                                          const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans, uint64_t first_rx_sample,
+                                          uint64_t rx_step, size_t n_fix, const gpsacq_quality_params* params, gpsacq_obs* obs,
+                                          gpsacq_quality_info* info);
+GPSACQ_API int gpsacq_quality_observables_device(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs,
+                                                 const gpsacq_track_chan* chans, const gpsacq_time_tag* tags, int n_chans,
+                                                 uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix, const gpsacq_quality_params* params,
+                                                 void* d_obs, void* d_info, int sync);
+GPSACQ_API int gpsacq_fix_quality_track_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_records, int max_epochs,
+                                               const int32_t* n_epochs, const gpsacq_track_chan* chans, const gpsacq_time_tag* tags,
+                                               const uint32_t* nom_words, int n_chans, uint64_t first_rx_sample, uint64_t rx_step, size_t n_fix,
+                                               const gpsacq_smooth_params* smooth_params, const gpsacq_quality_params* quality_params,
+                                               void* d_obs, void* d_info, void* d_fix, int sync);
+/* device time of the two kernels of the last gpsacq_quality_observables* / gpsacq_fix_quality_track_device call on this engine,
+ * milliseconds (HIP events on its stream; waits for them).  Either pointer may be NULL. */
+GPSACQ_API int gpsacq_quality_last_ms(const gpsacq_engine* e, float* acc_ms, float* out_ms);
+
+/*
  * ---- Atmosphere, elevation mask and DOP ---------------------------------------------------------------------------------------
  *
  * gpsacq_fix_batch is the reference's bare Solve(): signals as if in vacuum, every satellite with an ephemeris used, no figure of
