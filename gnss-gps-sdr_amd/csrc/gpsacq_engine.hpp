@@ -163,6 +163,19 @@ struct gpsacq_engine {
     size_t quality_info_cap = 0;
     hipEvent_t quality_ev[3] = {};  // before k_quality_acc, between the kernels, after k_quality_out
     bool quality_timed = false;
+    // coarse-time fixes (gpsacq_coarse_obs*, gpsacq_coarse_fix_batch*, gpsacq_coarse_fix_peaks_device)
+    gpsacq_peak* d_coarse_peaks = nullptr;  // host-buffer form of gpsacq_coarse_obs
+    size_t coarse_peaks_cap = 0;
+    gpsacq_obs* d_coarse_obs = nullptr;  // k_coarse_obs's output where the caller of the chain wants no observations
+    size_t coarse_obs_cap = 0;
+    gpsacq_obs* d_coarse_work = nullptr;  // k_coarse_fix's whole milliseconds where the caller wants no obs_out, and the host-buffer form
+    size_t coarse_work_cap = 0;
+    gpsacq_coarse_prior* d_coarse_prior = nullptr;  // host-buffer form
+    size_t coarse_prior_cap = 0;
+    gpsacq_coarse_info* d_coarse_info = nullptr;  // host-buffer form
+    size_t coarse_info_cap = 0;
+    hipEvent_t coarse_ev[4] = {};  // before and after k_coarse_obs, before and after k_coarse_fix
+    bool coarse_obs_timed = false, coarse_fix_timed = false;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;

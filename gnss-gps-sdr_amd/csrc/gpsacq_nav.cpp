@@ -6,7 +6,8 @@
 // end "Atmosphere, elevation mask and DOP": page 18 and the parameters (host only), gpsacq_sat_views*, gpsacq_fix_atm_batch*, and
 // "Fix integrity": the chi-square thresholds (host only) and gpsacq_fix_raim_batch*, which run fix_kernels.hip's k_raim_*.
 // Between the velocity and the atmosphere: "Carrier-smoothed observables", gpsacq_smooth_observables* and
-// gpsacq_fix_smooth_track_device, which run smooth_kernels.hip after k_code_pos and k_carrier_acc.
+// gpsacq_fix_smooth_track_device, which run smooth_kernels.hip after k_code_pos and k_carrier_acc.  Last of all "Coarse-time
+// fixes": gpsacq_coarse_obs*, gpsacq_coarse_fix_batch* and gpsacq_coarse_fix_peaks_device, which run coarse_kernels.hip.
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@
 
 #include "gpsacq_engine.hpp"
 #include "atm_launch.hpp"
+#include "coarse_launch.hpp"
 #include "nav_launch.hpp"
 #include "obs_launch.hpp"
 #include "raim_launch.hpp"
@@ -1095,5 +1097,175 @@ extern "C" int gpsacq_fix_raim_last_ms(const gpsacq_engine* e, float* sat_state_
     if (sat_state_ms) HIPCHK(hipEventElapsedTime(sat_state_ms, e->raim_ev[0], e->raim_ev[1]));
     if (detect_ms) HIPCHK(hipEventElapsedTime(detect_ms, e->raim_ev[1], e->raim_ev[2]));
     if (exclude_ms) HIPCHK(hipEventElapsedTime(exclude_ms, e->raim_ev[2], e->raim_ev[3]));
+    return GPSACQ_OK;
+}
+
+// ---- coarse-time fixes: positions from code phases alone (coarse_kernels.hip) ----------------------------------------------------
+extern "C" int gpsacq_coarse_default_params(gpsacq_coarse_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_default_params: null argument");
+    std::memset(p, 0, sizeof *p);
+    p->rms_max_m = 2.99792458e8 / 1.023e6;  // one C/A chip
+    return GPSACQ_OK;
+}
+
+// the caller's parameters or the defaults into *out, checked
+static int coarse_params(const char* who, const gpsacq_coarse_params* params, gpsacq_coarse_params* out) {
+    if (!params) return gpsacq_coarse_default_params(out);
+    *out = *params;
+    if (!std::isfinite(out->rms_max_m) || !(out->rms_max_m > 0.0)) return fail(GPSACQ_ERR_ARG, "%s: rms_max_m %g (must be finite and > 0)", who, out->rms_max_m);
+    return GPSACQ_OK;
+}
+
+static int coarse_fix_check(const char* who, const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* obs, const void* prior,
+                            size_t n_fix, int sats_per_fix, const gpsacq_coarse_params* params, const void* fix, const void* info,
+                            const void* obs_out, gpsacq_coarse_params* checked) {
+    if (int rc = nav_check(who, e, eph, n_eph, obs, n_fix, fix)) return rc;
+    if (!prior || !info) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (sats_per_fix < 1 || sats_per_fix > GPSACQ_FIX_MAX_SATS)
+        return fail(GPSACQ_ERR_ARG, "%s: sats_per_fix %d outside 1 .. %d", who, sats_per_fix, GPSACQ_FIX_MAX_SATS);
+    if (obs_out == obs) return fail(GPSACQ_ERR_ARG, "%s: obs_out must not be obs", who);
+    return coarse_params(who, params, checked);
+}
+
+static int coarse_obs_check(const char* who, const gpsacq_engine* e, const void* peaks, size_t n_fix, int n_chans, double snr_min, const void* obs) {
+    if (!e || !peaks || !obs || n_fix == 0 || n_fix > ((size_t)1 << 31)) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (n_chans < 1 || n_chans > GPSACQ_FIX_MAX_SATS) return fail(GPSACQ_ERR_ARG, "%s: n_chans %d outside 1 .. %d", who, n_chans, GPSACQ_FIX_MAX_SATS);
+    if (!std::isfinite(snr_min)) return fail(GPSACQ_ERR_ARG, "%s: snr_min %g (must be finite)", who, snr_min);
+    return GPSACQ_OK;
+}
+
+static int coarse_events(gpsacq_engine* e) {
+    for (auto& ev : e->coarse_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    return GPSACQ_OK;
+}
+
+// k_coarse_obs on the engine's stream between coarse_ev[0] and coarse_ev[1]; every argument has been checked
+static int coarse_obs_enqueue(gpsacq_engine* e, const void* d_peaks, size_t n_fix, int n_chans, double snr_min, void* d_obs) {
+    if (int rc = coarse_events(e)) return rc;
+    e->coarse_obs_timed = false;
+    HIPCHK(hipEventRecord(e->coarse_ev[0], e->stream));
+    launch_coarse_obs(CoarseObsArgs{(const gpsacq_peak*)d_peaks, n_fix * (size_t)n_chans, n_chans, e->p.fs, snr_min, (gpsacq_obs*)d_obs}, e->stream);
+    HIPCHK(hipEventRecord(e->coarse_ev[1], e->stream));
+    HIPCHK(hipGetLastError());
+    e->coarse_obs_timed = true;
+    return GPSACQ_OK;
+}
+
+// the ephemerides up, then k_coarse_fix between coarse_ev[2] and coarse_ev[3]; every argument has been checked
+static int coarse_fix_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_prior, size_t n_fix,
+                              int sats_per_fix, const gpsacq_coarse_params& cp, void* d_fix, void* d_info, void* d_obs_out) {
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    if (!d_obs_out) {  // the whole milliseconds live somewhere
+        if (int rc = grow(e->d_coarse_work, e->coarse_work_cap, n_fix * (size_t)sats_per_fix, e->stream)) return rc;
+        d_obs_out = e->d_coarse_work;
+    }
+    if (int rc = coarse_events(e)) return rc;
+    e->coarse_fix_timed = false;
+    HIPCHK(hipEventRecord(e->coarse_ev[2], e->stream));
+    launch_coarse_fix(CoarseFixArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, (const gpsacq_coarse_prior*)d_prior, n_fix, sats_per_fix, cp,
+                                    (gpsacq_fix*)d_fix, (gpsacq_coarse_info*)d_info, (gpsacq_obs*)d_obs_out},
+                      e->stream);
+    HIPCHK(hipEventRecord(e->coarse_ev[3], e->stream));
+    HIPCHK(hipGetLastError());
+    e->coarse_fix_timed = true;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_obs_device(gpsacq_engine* e, const void* d_peaks, size_t n_fix, int n_chans, double snr_min, void* d_obs, int sync) {
+    if (int rc = coarse_obs_check("gpsacq_coarse_obs", e, d_peaks, n_fix, n_chans, snr_min, d_obs)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = coarse_obs_enqueue(e, d_peaks, n_fix, n_chans, snr_min, d_obs)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_obs(gpsacq_engine* e, const gpsacq_peak* peaks, size_t n_fix, int n_chans, double snr_min, gpsacq_obs* obs) {
+    if (int rc = coarse_obs_check("gpsacq_coarse_obs", e, peaks, n_fix, n_chans, snr_min, obs)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_obs = n_fix * (size_t)n_chans;
+    if (int rc = grow(e->d_coarse_peaks, e->coarse_peaks_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_coarse_obs, e->coarse_obs_cap, n_obs, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_coarse_peaks, peaks, n_obs * sizeof(gpsacq_peak), hipMemcpyHostToDevice, e->stream));
+    if (int rc = coarse_obs_enqueue(e, e->d_coarse_peaks, n_fix, n_chans, snr_min, e->d_coarse_obs)) return rc;
+    HIPCHK(hipMemcpyAsync(obs, e->d_coarse_obs, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_fix_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_prior,
+                                              size_t n_fix, int sats_per_fix, const gpsacq_coarse_params* params, void* d_fix, void* d_info,
+                                              void* d_obs_out, int sync) {
+    gpsacq_coarse_params cp;
+    if (int rc = coarse_fix_check("gpsacq_coarse_fix_batch", e, eph, n_eph, d_obs, d_prior, n_fix, sats_per_fix, params, d_fix, d_info, d_obs_out, &cp))
+        return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = coarse_fix_enqueue(e, eph, n_eph, d_obs, d_prior, n_fix, sats_per_fix, cp, d_fix, d_info, d_obs_out)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_fix_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs,
+                                       const gpsacq_coarse_prior* prior, size_t n_fix, int sats_per_fix, const gpsacq_coarse_params* params,
+                                       gpsacq_fix* fix_out, gpsacq_coarse_info* info_out, gpsacq_obs* obs_out) {
+    gpsacq_coarse_params cp;
+    if (int rc = coarse_fix_check("gpsacq_coarse_fix_batch", e, eph, n_eph, obs, prior, n_fix, sats_per_fix, params, fix_out, info_out, obs_out, &cp))
+        return rc;
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    if (int rc = nav_check_weights("gpsacq_coarse_fix_batch", obs, n_obs)) return rc;
+    for (size_t k = 0; k < n_fix; ++k)
+        if (prior[k].rx_ms < 0 || prior[k].rx_ms >= 604800000 || !std::isfinite(prior[k].x) || !std::isfinite(prior[k].y) || !std::isfinite(prior[k].z))
+            return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_fix_batch: prior %zu is (%g, %g, %g) at rx_ms %d (must be finite, 0 <= rx_ms < 604800000)", k,
+                        prior[k].x, prior[k].y, prior[k].z, (int)prior[k].rx_ms);
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_coarse_work, e->coarse_work_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_coarse_prior, e->coarse_prior_cap, n_fix, e->stream)) return rc;
+    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
+    if (int rc = grow(e->d_coarse_info, e->coarse_info_cap, n_fix, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_coarse_prior, prior, n_fix * sizeof(gpsacq_coarse_prior), hipMemcpyHostToDevice, e->stream));
+    if (int rc = coarse_fix_enqueue(e, eph, n_eph, e->d_nav_obs, e->d_coarse_prior, n_fix, sats_per_fix, cp, e->d_nav_fix, e->d_coarse_info, nullptr))
+        return rc;
+    HIPCHK(hipMemcpyAsync(fix_out, e->d_nav_fix, n_fix * sizeof(gpsacq_fix), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(info_out, e->d_coarse_info, n_fix * sizeof(gpsacq_coarse_info), hipMemcpyDeviceToHost, e->stream));
+    if (obs_out) HIPCHK(hipMemcpyAsync(obs_out, e->d_coarse_work, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_fix_peaks_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_peaks, size_t n_fix,
+                                              int n_chans, double snr_min, const void* d_prior, const gpsacq_coarse_params* params, void* d_obs,
+                                              void* d_fix, void* d_info, void* d_obs_out, int sync) {
+    if (int rc = coarse_obs_check("gpsacq_coarse_fix_peaks", e, d_peaks, n_fix, n_chans, snr_min, d_fix)) return rc;
+    if (!eph || n_eph <= 0 || !d_prior || !d_info) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_fix_peaks: bad argument");
+    if (d_obs && d_obs_out == d_obs) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_fix_peaks: obs_out must not be obs");
+    gpsacq_coarse_params cp;
+    if (int rc = coarse_params("gpsacq_coarse_fix_peaks", params, &cp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (!d_obs) {
+        if (int rc = grow(e->d_coarse_obs, e->coarse_obs_cap, n_fix * (size_t)n_chans, e->stream)) return rc;
+        d_obs = e->d_coarse_obs;
+    }
+    if (int rc = coarse_obs_enqueue(e, d_peaks, n_fix, n_chans, snr_min, d_obs)) return rc;
+    if (int rc = coarse_fix_enqueue(e, eph, n_eph, d_obs, d_prior, n_fix, n_chans, cp, d_fix, d_info, d_obs_out)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_last_ms(const gpsacq_engine* e, float* obs_ms, float* fix_ms) {
+    if (!e || (!e->coarse_obs_timed && !e->coarse_fix_timed)) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_last_ms: no gpsacq_coarse call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    float t[2] = {0.f, 0.f};
+    if (e->coarse_obs_timed) {
+        HIPCHK(hipEventSynchronize(e->coarse_ev[1]));
+        HIPCHK(hipEventElapsedTime(&t[0], e->coarse_ev[0], e->coarse_ev[1]));
+    }
+    if (e->coarse_fix_timed) {
+        HIPCHK(hipEventSynchronize(e->coarse_ev[3]));
+        HIPCHK(hipEventElapsedTime(&t[1], e->coarse_ev[2], e->coarse_ev[3]));
+    }
+    if (obs_ms) *obs_ms = t[0];
+    if (fix_ms) *fix_ms = t[1];
     return GPSACQ_OK;
 }

@@ -106,6 +106,11 @@ RAIM_NONE, RAIM_UNCHECKED, RAIM_PASS, RAIM_EXCLUDED, RAIM_FAILED = 0, 1, 2, 3, 4
 RAIM_PARAMS_DTYPE = np.dtype([("sigma_m", "<f8"), ("p_fa", "<f8"), ("threshold", "<f8", (RAIM_MAX_DOF,)), ("exclude", "<i4"), ("reserved", "<i4")])
 FIX_RAIM_DTYPE = np.dtype([("status", "<i4"), ("dof", "<i4"), ("excluded", "<i4"), ("n_candidates", "<i4"), ("stat_full", "<f8"), ("stat", "<f8"),
                            ("threshold", "<f8")])
+# coarse-time fixes (include/gpsacq.h, "Coarse-time fixes: positions from code phases alone")
+COARSE_INCONSISTENT = 1
+COARSE_PRIOR_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("rx_ms", "<i4"), ("reserved", "<i4")])
+COARSE_PARAMS_DTYPE = np.dtype([("rms_max_m", "<f8"), ("reserved", "<f8")])
+COARSE_INFO_DTYPE = np.dtype([("ref", "<i4"), ("flags", "<i4"), ("coarse_s", "<f8"), ("bias_m", "<f8"), ("pdop", "<f8"), ("cdop", "<f8")])
 
 
 # carrier-smoothed observables (include/gpsacq.h "Carrier-smoothed observables")
@@ -155,7 +160,9 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_smooth_default_params", "gpsacq_smooth_observables", "gpsacq_smooth_observables_device", "gpsacq_fix_smooth_track_device",
            "gpsacq_smooth_last_ms",
            "gpsacq_quality_default_params", "gpsacq_quality_observables", "gpsacq_quality_observables_device",
-           "gpsacq_fix_quality_track_device", "gpsacq_quality_last_ms"]
+           "gpsacq_fix_quality_track_device", "gpsacq_quality_last_ms",
+           "gpsacq_coarse_default_params", "gpsacq_coarse_fix_batch", "gpsacq_coarse_fix_batch_device", "gpsacq_coarse_obs",
+           "gpsacq_coarse_obs_device", "gpsacq_coarse_fix_peaks_device", "gpsacq_coarse_last_ms"]
 
 _lib = None
 
@@ -416,6 +423,20 @@ def load_library(path=None):
     lib.gpsacq_fix_quality_track_device.restype = ctypes.c_int
     lib.gpsacq_quality_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
     lib.gpsacq_quality_last_ms.restype = ctypes.c_int
+    lib.gpsacq_coarse_default_params.argtypes = [vp]
+    lib.gpsacq_coarse_default_params.restype = ctypes.c_int
+    lib.gpsacq_coarse_fix_batch.argtypes = [vp, vp, ctypes.c_int, vp, vp, sz, ctypes.c_int, vp, vp, vp, vp]
+    lib.gpsacq_coarse_fix_batch.restype = ctypes.c_int
+    lib.gpsacq_coarse_fix_batch_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, sz, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_coarse_fix_batch_device.restype = ctypes.c_int
+    lib.gpsacq_coarse_obs.argtypes = [vp, vp, sz, ctypes.c_int, ctypes.c_double, vp]
+    lib.gpsacq_coarse_obs.restype = ctypes.c_int
+    lib.gpsacq_coarse_obs_device.argtypes = [vp, vp, sz, ctypes.c_int, ctypes.c_double, vp, ctypes.c_int]
+    lib.gpsacq_coarse_obs_device.restype = ctypes.c_int
+    lib.gpsacq_coarse_fix_peaks_device.argtypes = [vp, vp, ctypes.c_int, vp, sz, ctypes.c_int, ctypes.c_double, vp, vp, vp, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_coarse_fix_peaks_device.restype = ctypes.c_int
+    lib.gpsacq_coarse_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
+    lib.gpsacq_coarse_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -519,6 +540,29 @@ def raim_params(sigma_m, p_fa=1e-3):
     lib = load_library()
     out = np.zeros(1, dtype=RAIM_PARAMS_DTYPE)
     _check(lib, lib.gpsacq_raim_default_params(float(sigma_m), float(p_fa), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def coarse_params(rms_max_m=None):
+    """gpsacq_coarse_default_params: a COARSE_PARAMS_DTYPE record of shape (1,) -- rms_max_m one C/A chip, 293.05 m -- with
+    rms_max_m replaced where given.  The entry points that take it check it."""
+    lib = load_library()
+    out = np.zeros(1, dtype=COARSE_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_coarse_default_params(out.ctypes.data_as(ctypes.c_void_p)))
+    if rms_max_m is not None:
+        out["rms_max_m"] = float(rms_max_m)
+    return out
+
+
+def coarse_prior(xyz, rx_ms, n_fix=None):
+    """COARSE_PRIOR_DTYPE records: the prior place xyz (ECEF metres, (3,) or (n, 3)) and receive time rx_ms (millisecond of week,
+    one or n of them), each broadcast to n_fix rows (n_fix None: as many as the longer of the two)."""
+    xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+    ms = np.asarray(rx_ms, dtype=np.int64).reshape(-1)
+    n = max(xyz.shape[0], ms.size) if n_fix is None else int(n_fix)
+    out = np.zeros(n, dtype=COARSE_PRIOR_DTYPE)
+    out["x"], out["y"], out["z"] = np.broadcast_to(xyz, (n, 3)).T
+    out["rx_ms"] = np.broadcast_to(ms, (n,))
     return out
 
 
@@ -1013,6 +1057,73 @@ class Engine:
         t = [ctypes.c_float() for _ in range(3)]
         _check(self._lib, self._lib.gpsacq_fix_raim_last_ms(self._h, *[ctypes.byref(x) for x in t]))
         return tuple(x.value for x in t)
+
+    # ---- coarse-time fixes ------------------------------------------------------------------
+    @staticmethod
+    def _coarse_params(params):
+        if params is None:
+            return None, None
+        pr = np.array(params, dtype=COARSE_PARAMS_DTYPE).reshape(1).copy()
+        return pr, pr.ctypes.data_as(ctypes.c_void_p)
+
+    def coarse_fix(self, eph, obs, prior, params=None):
+        """gpsacq_coarse_fix_batch: one position per row of obs (OBS_DTYPE [n_fix][sats_per_fix], of which only eph, valid, tx_frac
+        and weight are read: the code phases) from the prior place and time of prior (COARSE_PRIOR_DTYPE, one record or n_fix;
+        coarse_prior()).  Returns (FIX_DTYPE [n_fix], COARSE_INFO_DTYPE [n_fix], OBS_DTYPE [n_fix][sats_per_fix]): the fixes, the
+        fifth unknown and the five-state dilutions, and the observations with their whole milliseconds, ready for fix(), fix_atm()
+        or fix_raim().  params: coarse_params(), None for the defaults."""
+        ep, ob = self._nav_arrays(eph, obs)
+        if ob.ndim != 2:
+            raise ValueError("obs must be [n_fix][sats_per_fix]")
+        pr = np.ascontiguousarray(np.broadcast_to(np.asarray(prior, dtype=COARSE_PRIOR_DTYPE).ravel(), (ob.shape[0],)))
+        cr, cp = self._coarse_params(params)
+        out = np.zeros(ob.shape[0], dtype=FIX_DTYPE)
+        info = np.zeros(ob.shape[0], dtype=COARSE_INFO_DTYPE)
+        oo = np.zeros(ob.shape, dtype=OBS_DTYPE)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_coarse_fix_batch(self._h, p(ep), int(ep.size), p(ob), p(pr), int(ob.shape[0]), int(ob.shape[1]), cp,
+                                                            p(out), p(info), p(oo)))
+        return out, info, oo
+
+    def coarse_fix_device(self, eph, d_obs_ptr, d_prior_ptr, n_fix, sats_per_fix, d_fix_ptr, d_info_ptr, d_obs_out_ptr=None, params=None, sync=True):
+        """gpsacq_coarse_fix_batch_device: device pointers for the observations, the priors and the outputs; d_obs_out_ptr may be
+        None."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        cr, cp = self._coarse_params(params)
+        _check(self._lib, self._lib.gpsacq_coarse_fix_batch_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_obs_ptr, d_prior_ptr,
+                                                                   int(n_fix), int(sats_per_fix), cp, d_fix_ptr, d_info_ptr, d_obs_out_ptr,
+                                                                   1 if sync else 0))
+
+    def coarse_obs(self, peaks, snr_min=THRESHOLD):
+        """gpsacq_coarse_obs: search peaks (PEAK_DTYPE [n_fix][n_chans], block outer and channel inner) into code-phase observations
+        (OBS_DTYPE, the same shape): valid where snr >= snr_min, eph = the channel, tx_frac = ca_shift / fs, weight 1."""
+        if not isinstance(peaks, np.ndarray) or peaks.dtype != PEAK_DTYPE or peaks.ndim != 2:
+            raise TypeError("peaks must be a PEAK_DTYPE array [n_fix][n_chans]")
+        pk = np.ascontiguousarray(peaks)
+        out = np.zeros(pk.shape, dtype=OBS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_coarse_obs(self._h, pk.ctypes.data_as(ctypes.c_void_p), int(pk.shape[0]), int(pk.shape[1]), float(snr_min),
+                                                      out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def coarse_obs_device(self, d_peaks_ptr, n_fix, n_chans, d_obs_ptr, snr_min=THRESHOLD, sync=True):
+        _check(self._lib, self._lib.gpsacq_coarse_obs_device(self._h, d_peaks_ptr, int(n_fix), int(n_chans), float(snr_min), d_obs_ptr,
+                                                             1 if sync else 0))
+
+    def coarse_fix_peaks_device(self, eph, d_peaks_ptr, n_fix, n_chans, d_prior_ptr, d_fix_ptr, d_info_ptr, d_obs_ptr=None, d_obs_out_ptr=None,
+                                snr_min=THRESHOLD, params=None, sync=True):
+        """gpsacq_coarse_fix_peaks_device: peaks -> observations -> coarse-time fixes in device memory, no host copy in between;
+        d_obs_ptr (the code-phase observations) and d_obs_out_ptr (with their whole milliseconds) may be None."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        cr, cp = self._coarse_params(params)
+        _check(self._lib, self._lib.gpsacq_coarse_fix_peaks_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_peaks_ptr, int(n_fix),
+                                                                   int(n_chans), float(snr_min), d_prior_ptr, cp, d_obs_ptr, d_fix_ptr, d_info_ptr,
+                                                                   d_obs_out_ptr, 1 if sync else 0))
+
+    def coarse_last_ms(self):
+        """Device milliseconds of the last coarse* calls: (k_coarse_obs or 0, k_coarse_fix or 0)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(self._lib, self._lib.gpsacq_coarse_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     # ---- observables ----------------------------------------------------------------------
     @staticmethod

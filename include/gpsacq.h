@@ -1385,6 +1385,118 @@ GPSACQ_API int gpsacq_fix_raim_batch_device(gpsacq_engine* e, const gpsacq_ephem
  * for them): k_sat_state, k_raim_detect, k_raim_exclude.  Any pointer may be NULL. */
 GPSACQ_API int gpsacq_fix_raim_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* detect_ms, float* exclude_ms);
 
+/*
+ * ---- Coarse-time fixes: positions from code phases alone -----------------------------------------------------------------------
+ *
+ * Everything above starts from tracking records: a channel runs for 19 s and decodes subframes 1-3 before the first transmit
+ * time exists.  A search peak gives only the code phase, the transmit time modulo one millisecond.  With ephemerides from
+ * elsewhere and a rough idea of place and time (the PRIOR) that is enough: the whole milliseconds follow from the prior, and the
+ * unknown error of the prior's time becomes a fifth unknown of the solve.  Every block of a capture is its own fix.  THE MODEL;
+ * the kernels (csrc/coarse_kernels.hip) and the reference of the tests (tests/coarse_ref.py) are both written from this text.
+ *
+ * INPUTS.  eph[n_eph] as for gpsacq_fix_batch.  obs[n_fix][sats_per_fix] of gpsacq_obs, of which only eph, valid, tx_frac and
+ * weight are read: tx_frac in [0, 1e-3) is the sub-millisecond part of the uncorrected satellite time that the replica shows at
+ * the receive instant; tx_ms is ignored.  USABLE here: usable as in "Navigation solver" and also 0 <= tx_frac < 1e-3.
+ * prior[n_fix] of gpsacq_coarse_prior: a place (ECEF metres) and a receive time t0 = (rx_ms, 0), rx_ms in 0 .. 604 799 999.  A
+ * prior whose rx_ms is outside the week or whose place is not finite is GPSACQ_ERR_ARG in the host form; the _device form cannot
+ * read it and treats every observation of that row as not usable.  gpsacq_coarse_params: rms_max_m, finite and > 0;
+ * gpsacq_coarse_default_params (host only) sets it to c / 1.023e6 = 293.05 m, one C/A chip.  Times below are seconds from t0; an
+ * absolute time is (rx_ms + whole milliseconds, fraction), split by FIX's rule (k = floor(1e3 t), frac = t - 1e-3 k, moved by one
+ * millisecond where rounding left frac outside [0, 1e-3)), and the orbit folds it against t_oe and t_oc as everywhere else.
+ * R(a) turns a vector about z by the angle a: (x cos a - y sin a, x sin a + y cos a, z).
+ *
+ * A. WHOLE MILLISECONDS.  Per fix, over the usable observations in column order, f_k = tx_frac:
+ *      pass 1: the satellite position at the uncorrected time -75e-3, turned by R(-Omega_e 75e-3); tau = its distance to the
+ *              prior's place / c.
+ *      pass 2: position and clock correction cc at the uncorrected time -tau, turned by R(-Omega_e tau); tau' = distance / c.
+ *      P_k = cc - tau'                                    the uncorrected satellite time the prior predicts, from t0
+ *    The reference r is the first usable column:
+ *      N_r = nearbyint((P_r - f_r) 1e3),   delta = N_r 1e-3 + f_r - P_r
+ *    every other column
+ *      N_k = nearbyint((delta + P_k - f_k) 1e3)
+ *    and T_k = N_k 1e-3 + f_k for all of them.  (nearbyint: to nearest, ties to even.)  delta absorbs what is common to all
+ *    satellites -- the receiver's clock and the mean of the prior's errors -- so only the DIFFERENCES between satellites have to
+ *    stay below half a millisecond.  An error dp of the prior's place moves P_k - P_r by at most 2 |dp| / c, an error dt of its
+ *    time by at most 1600 m/s |dt| / c (twice the largest range rate): every N_k is right up to one common integer while
+ *        2 |dp| + 1600 m/s |dt| < 150 km       (c x 0.5 ms).
+ *    Beyond that it depends on the geometry.  A common integer is one millisecond of receive time and is found by the solve.
+ *
+ * B. FIVE UNKNOWNS: x, y, z, b (metres) and s (seconds, the correction of the prior's time).  Start at the prior's place with
+ *    b = s = 0.  Per pass and satellite: position p, clock correction cc, ECEF velocity v and clock drift d at the uncorrected
+ *    time T_k + s (v and d as in "Velocity and clock drift", SATELLITE RATE), then
+ *      rho   = c (cc - T_k) - b
+ *      theta = -Omega_e rho / c
+ *      range = |x - R(theta) p|,   u = (x - R(theta) p) / range
+ *      res   = rho - range
+ *      h     = (u, 1, -(c d + u . R(theta) v))            so that res ~ h . (dx, db, ds)
+ *    Weighted normal equations A = sum w h h^T, g = sum w h res, solved by a 5x5 Cholesky with FIX's pivot rule (a pivot below
+ *    1e-13 of its diagonal entry: singular).  Every step is applied and counted in `iterations`; one with |dx| < 1e-4 m and
+ *    |ds| < 1e-7 s is the last.  20 steps without such a one, a bad pivot, a non-finite step or |s| reaching half a week
+ *    (302 400 s: no correction of a prior): GPSACQ_FIX_NO_CONVERGE.  Fewer than 5 usable observations: GPSACQ_FIX_TOO_FEW before
+ *    any step.  (In A, an N_k that is not finite or beyond 1e6 -- an ephemeris that describes no orbit -- is taken as 0.)
+ *    The receive time is t0 + s - b / c as (rx_ms, rx_frac); lat / lon / alt as in FIX; rms = sqrt(sum w res^2 / sum w) over the
+ *    residuals the last step was made from.
+ *
+ * C. RECORDS.  Three per fix.
+ *    gpsacq_fix as everywhere: not GPSACQ_FIX_OK means every double 0 and rx_ms = 0 (n_used and iterations stay).
+ *    gpsacq_coarse_info: ref the reference column (-1: no usable observation); coarse_s = s; bias_m = b; pdop = sqrt of the trace
+ *    of the position block of (H^T H)^-1 and cdop = sqrt of its s-s entry (seconds per metre), H the five-column rows h at the
+ *    final state, unweighted, over the usable observations with weight > 0; both 0 where the Cholesky factor of H^T H fails or
+ *    either is not finite.  flags: GPSACQ_COARSE_INCONSISTENT when n_used >= 6 and rms > rms_max_m -- with one satellite to spare
+ *    a wrong millisecond or a false peak shows as kilometres of residual.  Not GPSACQ_FIX_OK: ref stays, everything else 0.
+ *    Five satellites have no residual to judge, and the five-state normal matrix of even the best five of a constellation has a
+ *    condition of 1e9 - 1e10: read pdop and cdop before trusting such a fix.
+ *    obs_out[n_fix][sats_per_fix], optional: the usable observations of a GPSACQ_FIX_OK fix as ordinary observations -- eph and
+ *    weight kept, valid = 1, (tx_ms, tx_frac) the split of t0 + T_k + s folded into the week -- everything else 32 zero bytes.
+ *    They drop into gpsacq_fix_batch, gpsacq_fix_atm_batch, gpsacq_fix_raim_batch and gpsacq_sat_views unchanged.  At the optimum
+ *    of the five-state problem the four-state normal equations hold, so gpsacq_fix_batch on obs_out returns the same place and
+ *    receive time.  obs_out must not overlap obs.
+ *
+ * FROM PEAKS.  gpsacq_coarse_obs: peaks[n_fix][n_chans] of gpsacq_peak, task order with the block outer and the channel inner
+ * (task b * n_chans + c = block b against the PRN of eph[c]), 1 <= n_chans <= GPSACQ_FIX_MAX_SATS.  ca_shift is the code position,
+ * in samples, at the block's first sample, and THAT SAMPLE is the receive instant of the row.  Per (fix, channel)
+ *      valid = snr >= snr_min and 0 <= ca_shift < fs / 1000,   eph = channel,   tx_frac = (double)ca_shift / fs,   weight = 1.0,
+ *      tx_ms = reserved = 0;
+ * an observation that is not valid is 32 zero bytes.  fs is the engine's.  A whole-sample code phase is off by up to one sample,
+ * c / fs = 55 m of range at 5.456 MHz, so such fixes are good to 100-200 m with eight satellites; interpolating the correlation
+ * peak below a sample is the next step and is not done here.
+ *
+ * gpsacq_coarse_fix_batch: host pointers, returns after completion; a negative or non-finite weight is GPSACQ_ERR_ARG; params
+ * NULL means the defaults; obs_out may be NULL, fix_out and info_out may not.  gpsacq_coarse_fix_batch_device: obs, prior and the
+ * three outputs are device pointers (d_obs_out may be NULL: the whole milliseconds then live in engine scratch, and the fixes are
+ * the same byte for byte), eph stays a host pointer; work on the engine's stream, sync != 0 waits; a bad weight skips the
+ * observation.  gpsacq_coarse_obs / _device likewise.  gpsacq_coarse_fix_peaks_device: k_coarse_obs then k_coarse_fix on the same
+ * stream, no host copy in between; d_obs may be NULL (engine scratch).  Argument errors -- a NULL pointer, n_fix == 0,
+ * sats_per_fix or n_chans outside 1..GPSACQ_FIX_MAX_SATS, a non-finite snr_min, rms_max_m not finite or <= 0 -- return
+ * GPSACQ_ERR_ARG, launch nothing and write nothing.
+ * Kernels (csrc/coarse_kernels.hip): k_coarse_obs, one lane per (fix, channel).  k_coarse_fix, one lane per fix: nothing of the
+ * row is held in registers -- the satellite loop of every pass reads the observation back from memory, evaluates the orbit
+ * (csrc/orbit_device.hpp, the one copy k_sat_state and k_sat_state_rate use) and adds into the 15 + 5 sums.
+ *
+ * OUT OF SCOPE.  Sub-sample code phases (no change to the correlator or to gpsacq_peak).  Doppler-aided time.  gps_test and
+ * gps_track.
+ */
+typedef struct { double x, y, z; int32_t rx_ms; int32_t reserved; } gpsacq_coarse_prior;                                    /* 32 bytes */
+typedef struct { double rms_max_m; double reserved; } gpsacq_coarse_params;                                                  /* 16 bytes */
+#define GPSACQ_COARSE_INCONSISTENT 1   /* n_used >= 6 and rms > rms_max_m */
+typedef struct { int32_t ref; int32_t flags; double coarse_s, bias_m, pdop, cdop; } gpsacq_coarse_info;                     /* 40 bytes */
+GPSACQ_API int gpsacq_coarse_default_params(gpsacq_coarse_params* p);   /* host only */
+GPSACQ_API int gpsacq_coarse_fix_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs /* [n_fix][sats_per_fix] */,
+                                       const gpsacq_coarse_prior* prior, size_t n_fix, int sats_per_fix, const gpsacq_coarse_params* params,
+                                       gpsacq_fix* fix_out, gpsacq_coarse_info* info_out, gpsacq_obs* obs_out);
+GPSACQ_API int gpsacq_coarse_fix_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_prior,
+                                              size_t n_fix, int sats_per_fix, const gpsacq_coarse_params* params, void* d_fix, void* d_info,
+                                              void* d_obs_out, int sync);
+GPSACQ_API int gpsacq_coarse_obs(gpsacq_engine* e, const gpsacq_peak* peaks /* [n_fix][n_chans] */, size_t n_fix, int n_chans, double snr_min,
+                                 gpsacq_obs* obs);
+GPSACQ_API int gpsacq_coarse_obs_device(gpsacq_engine* e, const void* d_peaks, size_t n_fix, int n_chans, double snr_min, void* d_obs, int sync);
+GPSACQ_API int gpsacq_coarse_fix_peaks_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_peaks, size_t n_fix,
+                                              int n_chans, double snr_min, const void* d_prior, const gpsacq_coarse_params* params, void* d_obs,
+                                              void* d_fix, void* d_info, void* d_obs_out, int sync);
+/* device time of k_coarse_obs and k_coarse_fix as last run on this engine, milliseconds (HIP events on its stream; waits for
+ * them); a kernel that has not run reads 0.  Either pointer may be NULL. */
+GPSACQ_API int gpsacq_coarse_last_ms(const gpsacq_engine* e, float* obs_ms, float* fix_ms);
+
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);
 
