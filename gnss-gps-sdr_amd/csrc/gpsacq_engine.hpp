@@ -176,6 +176,17 @@ struct gpsacq_engine {
     size_t coarse_info_cap = 0;
     hipEvent_t coarse_ev[4] = {};  // before and after k_coarse_obs, before and after k_coarse_fix
     bool coarse_obs_timed = false, coarse_fix_timed = false;
+    // fine code phases (gpsacq_refine*, gpsacq_coarse_obs_fine*, gpsacq_coarse_fix_fine_device)
+    uint8_t* d_refine_bits = nullptr;  // host-buffer form of gpsacq_refine: the capture, its tasks and peaks
+    size_t refine_bits_cap = 0;
+    gpsacq_task* d_refine_tasks = nullptr;
+    size_t refine_tasks_cap = 0;
+    gpsacq_peak* d_refine_peaks = nullptr;  // also the peaks of the host-buffer form of gpsacq_coarse_obs_fine
+    size_t refine_peaks_cap = 0;
+    gpsacq_fine* d_fine = nullptr;  // host-buffer forms, and k_refine's output where the caller of the chain wants no records
+    size_t fine_cap = 0;
+    hipEvent_t refine_ev[4] = {};  // before and after k_refine, before and after k_coarse_obs_fine
+    bool refine_timed = false, refine_obs_timed = false;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;

@@ -6,8 +6,9 @@
 // end "Atmosphere, elevation mask and DOP": page 18 and the parameters (host only), gpsacq_sat_views*, gpsacq_fix_atm_batch*, and
 // "Fix integrity": the chi-square thresholds (host only) and gpsacq_fix_raim_batch*, which run fix_kernels.hip's k_raim_*.
 // Between the velocity and the atmosphere: "Carrier-smoothed observables", gpsacq_smooth_observables* and
-// gpsacq_fix_smooth_track_device, which run smooth_kernels.hip after k_code_pos and k_carrier_acc.  Last of all "Coarse-time
-// fixes": gpsacq_coarse_obs*, gpsacq_coarse_fix_batch* and gpsacq_coarse_fix_peaks_device, which run coarse_kernels.hip.
+// gpsacq_fix_smooth_track_device, which run smooth_kernels.hip after k_code_pos and k_carrier_acc.  Then "Coarse-time
+// fixes": gpsacq_coarse_obs*, gpsacq_coarse_fix_batch* and gpsacq_coarse_fix_peaks_device, which run coarse_kernels.hip.  Last of
+// all "Fine code phases": gpsacq_refine*, gpsacq_coarse_obs_fine* and gpsacq_coarse_fix_fine_device, which run refine_kernels.hip.
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,7 @@
 #include "nav_launch.hpp"
 #include "obs_launch.hpp"
 #include "raim_launch.hpp"
+#include "refine_launch.hpp"
 #include "smooth_launch.hpp"
 
 using namespace acq;
@@ -1267,5 +1269,193 @@ extern "C" int gpsacq_coarse_last_ms(const gpsacq_engine* e, float* obs_ms, floa
     }
     if (obs_ms) *obs_ms = t[0];
     if (fix_ms) *fix_ms = t[1];
+    return GPSACQ_OK;
+}
+
+// ---- fine code phases: search peaks refined below a sample (refine_kernels.hip) --------------------------------------------------
+extern "C" int gpsacq_refine_default_params(gpsacq_refine_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_refine_default_params: null argument");
+    std::memset(p, 0, sizeof *p);
+    p->blocks = 16;
+    p->min_segments = 1;
+    p->half_spacing_chips = 0.25;
+    p->snr_min = 25.0;  // the threshold of the search, c/search_offline.cpp:248
+    return GPSACQ_OK;
+}
+
+// the caller's parameters or the defaults into *out, checked
+static int refine_params(const char* who, const gpsacq_refine_params* params, gpsacq_refine_params* out) {
+    if (!params) return gpsacq_refine_default_params(out);
+    *out = *params;
+    if (out->blocks < 1 || out->blocks > 64) return fail(GPSACQ_ERR_ARG, "%s: blocks %d outside 1 .. 64", who, (int)out->blocks);
+    if (out->min_segments < 1) return fail(GPSACQ_ERR_ARG, "%s: min_segments %d (must be >= 1)", who, (int)out->min_segments);
+    if (!(out->half_spacing_chips >= 1.0 / 64 && out->half_spacing_chips <= 0.5))
+        return fail(GPSACQ_ERR_ARG, "%s: half_spacing_chips %g outside [1/64, 0.5]", who, out->half_spacing_chips);
+    if (!std::isfinite(out->snr_min)) return fail(GPSACQ_ERR_ARG, "%s: snr_min %g (must be finite)", who, out->snr_min);
+    return GPSACQ_OK;
+}
+
+static int refine_check(const char* who, const gpsacq_engine* e, const void* bits, size_t n_bytes, size_t stride, const void* peaks, size_t n_tasks,
+                        const gpsacq_refine_params* params, const void* fine, gpsacq_refine_params* checked) {
+    if (!e || !bits || !peaks || !fine || n_bytes == 0 || n_tasks == 0 || n_tasks > 0x7fffffffu) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (stride < 5000 || stride > ((size_t)1 << 31)) return fail(GPSACQ_ERR_ARG, "%s: stride %zu outside 5000 .. 2^31", who, stride);
+    if (n_bytes > ((size_t)1 << 56)) return fail(GPSACQ_ERR_ARG, "%s: n_bytes %zu", who, n_bytes);
+    if (e->nlags > 65535) return fail(GPSACQ_ERR_UNSUPPORTED, "%s: %d samples per millisecond (the packed counts hold 65535)", who, e->nlags);
+    if (1.023e6 / e->p.fs + 1.0 / 1540.0 > REFINE_MAX_CHIPS_PER_SAMPLE)
+        return fail(GPSACQ_ERR_UNSUPPORTED, "%s: fs = %g Hz is fewer than %.2f samples per chip (a word's chips leave the kernel's window)", who, e->p.fs,
+                    1.0 / REFINE_MAX_CHIPS_PER_SAMPLE);
+    return refine_params(who, params, checked);
+}
+
+static int refine_events(gpsacq_engine* e) {
+    for (auto& ev : e->refine_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    return GPSACQ_OK;
+}
+
+// k_refine on the engine's stream between refine_ev[0] and refine_ev[1]; every argument has been checked
+static int refine_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
+                          size_t n_tasks, const gpsacq_refine_params& rp, void* d_fine) {
+    if (int rc = ensure_track_chips(e)) return rc;
+    if (int rc = refine_events(e)) return rc;
+    const uint32_t lead = (uint32_t)((uintptr_t)d_bits & 3u);  // the kernel loads whole words from the aligned address below
+    const bool ref_grid = e->sub == 1 && e->dstride == 1;       // as gpsacq_handoff_engine
+    RefineArgs a{};
+    a.words = (const uint32_t*)((uintptr_t)d_bits - lead);
+    a.n_bytes = n_bytes + lead;
+    a.lead = lead;
+    a.stride = stride;
+    a.tasks = (const gpsacq_task*)d_tasks;
+    a.peaks = (const gpsacq_peak*)d_peaks;
+    a.n_tasks = n_tasks;
+    a.chips = e->d_track_chips;
+    a.fc = e->p.fc, a.fs = e->p.fs;
+    a.step_hz = ref_grid ? 0.0 : e->p.fs / N_FFT * e->dstride / e->sub;
+    a.spm = e->nlags;
+    a.p = rp;
+    a.out = (gpsacq_fine*)d_fine;
+    e->refine_timed = false;
+    HIPCHK(hipEventRecord(e->refine_ev[0], e->stream));
+    launch_refine(a, e->stream);
+    HIPCHK(hipEventRecord(e->refine_ev[1], e->stream));
+    HIPCHK(hipGetLastError());
+    e->refine_timed = true;
+    return GPSACQ_OK;
+}
+
+// k_coarse_obs_fine between refine_ev[2] and refine_ev[3]; every argument has been checked
+static int coarse_obs_fine_enqueue(gpsacq_engine* e, const void* d_peaks, const void* d_fine, size_t n_fix, int n_chans, double snr_min, void* d_obs) {
+    if (int rc = refine_events(e)) return rc;
+    e->refine_obs_timed = false;
+    HIPCHK(hipEventRecord(e->refine_ev[2], e->stream));
+    launch_coarse_obs_fine(CoarseObsFineArgs{(const gpsacq_peak*)d_peaks, (const gpsacq_fine*)d_fine, n_fix * (size_t)n_chans, n_chans, e->p.fs, snr_min,
+                                             (gpsacq_obs*)d_obs},
+                           e->stream);
+    HIPCHK(hipEventRecord(e->refine_ev[3], e->stream));
+    HIPCHK(hipGetLastError());
+    e->refine_obs_timed = true;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_refine_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
+                                    size_t n_tasks, const gpsacq_refine_params* params, void* d_fine, int sync) {
+    gpsacq_refine_params rp;
+    if (int rc = refine_check("gpsacq_refine", e, d_bits, n_bytes, stride, d_peaks, n_tasks, params, d_fine, &rp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = refine_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, rp, d_fine)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_refine(gpsacq_engine* e, const uint8_t* bits, size_t n_bytes, size_t stride, const gpsacq_task* tasks, const gpsacq_peak* peaks,
+                             size_t n_tasks, const gpsacq_refine_params* params, gpsacq_fine* fine_out) {
+    gpsacq_refine_params rp;
+    if (int rc = refine_check("gpsacq_refine", e, bits, n_bytes, stride, peaks, n_tasks, params, fine_out, &rp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_refine_bits, e->refine_bits_cap, n_bytes, e->stream)) return rc;
+    if (int rc = grow(e->d_refine_peaks, e->refine_peaks_cap, n_tasks, e->stream)) return rc;
+    if (int rc = grow(e->d_fine, e->fine_cap, n_tasks, e->stream)) return rc;
+    if (tasks) {
+        if (int rc = grow(e->d_refine_tasks, e->refine_tasks_cap, n_tasks, e->stream)) return rc;
+        HIPCHK(hipMemcpyAsync(e->d_refine_tasks, tasks, n_tasks * sizeof(gpsacq_task), hipMemcpyHostToDevice, e->stream));
+    }
+    HIPCHK(hipMemcpyAsync(e->d_refine_bits, bits, n_bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_refine_peaks, peaks, n_tasks * sizeof(gpsacq_peak), hipMemcpyHostToDevice, e->stream));
+    if (int rc = refine_enqueue(e, e->d_refine_bits, n_bytes, stride, tasks ? e->d_refine_tasks : nullptr, e->d_refine_peaks, n_tasks, rp, e->d_fine))
+        return rc;
+    HIPCHK(hipMemcpyAsync(fine_out, e->d_fine, n_tasks * sizeof(gpsacq_fine), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_obs_fine_device(gpsacq_engine* e, const void* d_peaks, const void* d_fine, size_t n_fix, int n_chans, double snr_min,
+                                             void* d_obs, int sync) {
+    if (int rc = coarse_obs_check("gpsacq_coarse_obs_fine", e, d_peaks, n_fix, n_chans, snr_min, d_obs)) return rc;
+    if (!d_fine) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_obs_fine: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = coarse_obs_fine_enqueue(e, d_peaks, d_fine, n_fix, n_chans, snr_min, d_obs)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_obs_fine(gpsacq_engine* e, const gpsacq_peak* peaks, const gpsacq_fine* fine, size_t n_fix, int n_chans, double snr_min,
+                                      gpsacq_obs* obs) {
+    if (int rc = coarse_obs_check("gpsacq_coarse_obs_fine", e, peaks, n_fix, n_chans, snr_min, obs)) return rc;
+    if (!fine) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_obs_fine: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_obs = n_fix * (size_t)n_chans;
+    if (int rc = grow(e->d_refine_peaks, e->refine_peaks_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_fine, e->fine_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_coarse_obs, e->coarse_obs_cap, n_obs, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_refine_peaks, peaks, n_obs * sizeof(gpsacq_peak), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_fine, fine, n_obs * sizeof(gpsacq_fine), hipMemcpyHostToDevice, e->stream));
+    if (int rc = coarse_obs_fine_enqueue(e, e->d_refine_peaks, e->d_fine, n_fix, n_chans, snr_min, e->d_coarse_obs)) return rc;
+    HIPCHK(hipMemcpyAsync(obs, e->d_coarse_obs, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_fix_fine_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_bits, size_t n_bytes, size_t stride,
+                                             const void* d_tasks, const void* d_peaks, size_t n_fix, int n_chans,
+                                             const gpsacq_refine_params* refine_par, const void* d_prior, const gpsacq_coarse_params* params,
+                                             void* d_fine, void* d_obs, void* d_fix, void* d_info, void* d_obs_out, int sync) {
+    if (int rc = coarse_obs_check("gpsacq_coarse_fix_fine", e, d_peaks, n_fix, n_chans, 0.0, d_fix)) return rc;
+    if (!eph || n_eph <= 0 || !d_prior || !d_info) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_fix_fine: bad argument");
+    if (d_obs && d_obs_out == d_obs) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_fix_fine: obs_out must not be obs");
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    gpsacq_refine_params rp;
+    if (int rc = refine_check("gpsacq_coarse_fix_fine", e, d_bits, n_bytes, stride, d_peaks, n_tasks, refine_par, d_fix, &rp)) return rc;
+    gpsacq_coarse_params cp;
+    if (int rc = coarse_params("gpsacq_coarse_fix_fine", params, &cp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (!d_fine) {
+        if (int rc = grow(e->d_fine, e->fine_cap, n_tasks, e->stream)) return rc;
+        d_fine = e->d_fine;
+    }
+    if (!d_obs) {
+        if (int rc = grow(e->d_coarse_obs, e->coarse_obs_cap, n_tasks, e->stream)) return rc;
+        d_obs = e->d_coarse_obs;
+    }
+    if (int rc = refine_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, rp, d_fine)) return rc;
+    if (int rc = coarse_obs_fine_enqueue(e, d_peaks, d_fine, n_fix, n_chans, rp.snr_min, d_obs)) return rc;
+    if (int rc = coarse_fix_enqueue(e, eph, n_eph, d_obs, d_prior, n_fix, n_chans, cp, d_fix, d_info, d_obs_out)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_refine_last_ms(const gpsacq_engine* e, float* refine_ms, float* obs_ms) {
+    if (!e || (!e->refine_timed && !e->refine_obs_timed)) return fail(GPSACQ_ERR_ARG, "gpsacq_refine_last_ms: no gpsacq_refine call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    float t[2] = {0.f, 0.f};
+    if (e->refine_timed) {
+        HIPCHK(hipEventSynchronize(e->refine_ev[1]));
+        HIPCHK(hipEventElapsedTime(&t[0], e->refine_ev[0], e->refine_ev[1]));
+    }
+    if (e->refine_obs_timed) {
+        HIPCHK(hipEventSynchronize(e->refine_ev[3]));
+        HIPCHK(hipEventElapsedTime(&t[1], e->refine_ev[2], e->refine_ev[3]));
+    }
+    if (refine_ms) *refine_ms = t[0];
+    if (obs_ms) *obs_ms = t[1];
     return GPSACQ_OK;
 }

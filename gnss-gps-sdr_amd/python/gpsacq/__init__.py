@@ -111,6 +111,11 @@ COARSE_INCONSISTENT = 1
 COARSE_PRIOR_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("rx_ms", "<i4"), ("reserved", "<i4")])
 COARSE_PARAMS_DTYPE = np.dtype([("rms_max_m", "<f8"), ("reserved", "<f8")])
 COARSE_INFO_DTYPE = np.dtype([("ref", "<i4"), ("flags", "<i4"), ("coarse_s", "<f8"), ("bias_m", "<f8"), ("pdop", "<f8"), ("cdop", "<f8")])
+# fine code phases (include/gpsacq.h, "Fine code phases: search peaks refined below a sample")
+FINE_NO_HIT, FINE_SHORT, FINE_NO_POWER, FINE_FEW = 1, 2, 4, 8
+REFINE_PARAMS_DTYPE = np.dtype([("blocks", "<i4"), ("min_segments", "<i4"), ("half_spacing_chips", "<f8"), ("snr_min", "<f8")])
+FINE_DTYPE = np.dtype([("flags", "<i4"), ("segments", "<i4"), ("lo_rate", "<u4"), ("ca_rate", "<u4"), ("early", "<u8"), ("prompt", "<u8"),
+                       ("late", "<u8"), ("offset_chips", "<f8"), ("tx_frac", "<f8")])
 
 
 # carrier-smoothed observables (include/gpsacq.h "Carrier-smoothed observables")
@@ -162,7 +167,9 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_quality_default_params", "gpsacq_quality_observables", "gpsacq_quality_observables_device",
            "gpsacq_fix_quality_track_device", "gpsacq_quality_last_ms",
            "gpsacq_coarse_default_params", "gpsacq_coarse_fix_batch", "gpsacq_coarse_fix_batch_device", "gpsacq_coarse_obs",
-           "gpsacq_coarse_obs_device", "gpsacq_coarse_fix_peaks_device", "gpsacq_coarse_last_ms"]
+           "gpsacq_coarse_obs_device", "gpsacq_coarse_fix_peaks_device", "gpsacq_coarse_last_ms",
+           "gpsacq_refine_default_params", "gpsacq_refine", "gpsacq_refine_device", "gpsacq_coarse_obs_fine", "gpsacq_coarse_obs_fine_device",
+           "gpsacq_coarse_fix_fine_device", "gpsacq_refine_last_ms"]
 
 _lib = None
 
@@ -437,6 +444,20 @@ def load_library(path=None):
     lib.gpsacq_coarse_fix_peaks_device.restype = ctypes.c_int
     lib.gpsacq_coarse_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
     lib.gpsacq_coarse_last_ms.restype = ctypes.c_int
+    lib.gpsacq_refine_default_params.argtypes = [vp]
+    lib.gpsacq_refine_default_params.restype = ctypes.c_int
+    lib.gpsacq_refine.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp]
+    lib.gpsacq_refine.restype = ctypes.c_int
+    lib.gpsacq_refine_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp, ctypes.c_int]
+    lib.gpsacq_refine_device.restype = ctypes.c_int
+    lib.gpsacq_coarse_obs_fine.argtypes = [vp, vp, vp, sz, ctypes.c_int, ctypes.c_double, vp]
+    lib.gpsacq_coarse_obs_fine.restype = ctypes.c_int
+    lib.gpsacq_coarse_obs_fine_device.argtypes = [vp, vp, vp, sz, ctypes.c_int, ctypes.c_double, vp, ctypes.c_int]
+    lib.gpsacq_coarse_obs_fine_device.restype = ctypes.c_int
+    lib.gpsacq_coarse_fix_fine_device.argtypes = [vp, vp, ctypes.c_int, vp, sz, sz, vp, vp, sz, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_coarse_fix_fine_device.restype = ctypes.c_int
+    lib.gpsacq_refine_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
+    lib.gpsacq_refine_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -551,6 +572,31 @@ def coarse_params(rms_max_m=None):
     _check(lib, lib.gpsacq_coarse_default_params(out.ctypes.data_as(ctypes.c_void_p)))
     if rms_max_m is not None:
         out["rms_max_m"] = float(rms_max_m)
+    return out
+
+
+def refine_params(**overrides):
+    """gpsacq_refine_default_params: a REFINE_PARAMS_DTYPE record of shape (1,) -- a window of 16 blocks, min_segments 1, early
+    and late a quarter chip from the prompt, snr_min the search threshold -- with the named fields replaced.  Values outside the
+    bounds of include/gpsacq.h ("Fine code phases", INPUTS) raise ValueError here; the entry points check them again."""
+    lib = load_library()
+    out = np.zeros(1, dtype=REFINE_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_refine_default_params(out.ctypes.data_as(ctypes.c_void_p)))
+    for k, v in overrides.items():
+        if k not in REFINE_PARAMS_DTYPE.names:
+            raise TypeError("refine_params: no field %r" % k)
+        if k in ("blocks", "min_segments") and int(v) != v:
+            raise ValueError("refine_params: %s = %r is no whole number" % (k, v))
+        out[k] = v
+    r = out[0]
+    if not 1 <= r["blocks"] <= 64:
+        raise ValueError("refine_params: blocks %d outside 1 .. 64" % r["blocks"])
+    if r["min_segments"] < 1:
+        raise ValueError("refine_params: min_segments %d (must be >= 1)" % r["min_segments"])
+    if not 1.0 / 64 <= r["half_spacing_chips"] <= 0.5:
+        raise ValueError("refine_params: half_spacing_chips %g outside [1/64, 0.5]" % r["half_spacing_chips"])
+    if not np.isfinite(r["snr_min"]):
+        raise ValueError("refine_params: snr_min %g (must be finite)" % r["snr_min"])
     return out
 
 
@@ -1094,16 +1140,81 @@ class Engine:
                                                                    int(n_fix), int(sats_per_fix), cp, d_fix_ptr, d_info_ptr, d_obs_out_ptr,
                                                                    1 if sync else 0))
 
-    def coarse_obs(self, peaks, snr_min=THRESHOLD):
+    def coarse_obs(self, peaks, snr_min=THRESHOLD, fine=None):
         """gpsacq_coarse_obs: search peaks (PEAK_DTYPE [n_fix][n_chans], block outer and channel inner) into code-phase observations
-        (OBS_DTYPE, the same shape): valid where snr >= snr_min, eph = the channel, tx_frac = ca_shift / fs, weight 1."""
+        (OBS_DTYPE, the same shape): valid where snr >= snr_min, eph = the channel, tx_frac = ca_shift / fs, weight 1.
+        fine: refine()'s records of those peaks (FINE_DTYPE, as many) -- gpsacq_coarse_obs_fine: valid also needs a usable record,
+        and tx_frac is the record's."""
         if not isinstance(peaks, np.ndarray) or peaks.dtype != PEAK_DTYPE or peaks.ndim != 2:
             raise TypeError("peaks must be a PEAK_DTYPE array [n_fix][n_chans]")
         pk = np.ascontiguousarray(peaks)
         out = np.zeros(pk.shape, dtype=OBS_DTYPE)
+        if fine is not None:
+            if not isinstance(fine, np.ndarray) or fine.dtype != FINE_DTYPE or fine.size != pk.size:
+                raise TypeError("fine must be a FINE_DTYPE array with one record per peak")
+            fn = np.ascontiguousarray(fine)
+            _check(self._lib, self._lib.gpsacq_coarse_obs_fine(self._h, pk.ctypes.data_as(ctypes.c_void_p), fn.ctypes.data_as(ctypes.c_void_p),
+                                                               int(pk.shape[0]), int(pk.shape[1]), float(snr_min), out.ctypes.data_as(ctypes.c_void_p)))
+            return out
         _check(self._lib, self._lib.gpsacq_coarse_obs(self._h, pk.ctypes.data_as(ctypes.c_void_p), int(pk.shape[0]), int(pk.shape[1]), float(snr_min),
                                                       out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+    # ---- fine code phases -------------------------------------------------------------------
+    @staticmethod
+    def _refine_params(params):
+        if params is None:
+            return None, None
+        pr = np.array(params, dtype=REFINE_PARAMS_DTYPE).reshape(1).copy()
+        return pr, pr.ctypes.data_as(ctypes.c_void_p)
+
+    def refine(self, bits, peaks, tasks=None, stride=BLOCK_BYTES, params=None):
+        """gpsacq_refine: the peaks of a search of `bits` (PEAK_DTYPE, any shape; tasks as given to search(), None for the reference
+        schedule) refined below a sample on a window of consecutive blocks of the capture.  Returns FINE_DTYPE records in the shape
+        of peaks.  params: refine_params(), None for the defaults."""
+        buf = np.ascontiguousarray(np.frombuffer(bits, dtype=np.uint8) if not isinstance(bits, np.ndarray) else bits.view(np.uint8))
+        if not isinstance(peaks, np.ndarray) or peaks.dtype != PEAK_DTYPE:
+            raise TypeError("peaks must be a PEAK_DTYPE array")
+        pk = np.ascontiguousarray(peaks)
+        tptr = None
+        if tasks is not None:
+            t = np.ascontiguousarray(np.asarray(tasks, dtype=np.int32).reshape(-1, 2))
+            if t.shape[0] != pk.size:
+                raise ValueError("one task per peak")
+            tptr = t.ctypes.data_as(ctypes.c_void_p)
+        rr, rp = self._refine_params(params)
+        out = np.zeros(pk.shape, dtype=FINE_DTYPE)
+        _check(self._lib, self._lib.gpsacq_refine(self._h, buf.ctypes.data_as(ctypes.c_void_p), int(buf.size), int(stride), tptr,
+                                                  pk.ctypes.data_as(ctypes.c_void_p), int(pk.size), rp, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def refine_device(self, d_bits_ptr, n_bytes, d_peaks_ptr, n_tasks, d_fine_ptr, stride=BLOCK_BYTES, d_tasks_ptr=None, params=None, sync=True):
+        """gpsacq_refine_device: device pointers for the capture (any byte address), the peaks, the tasks (None: the reference
+        schedule) and the records."""
+        rr, rp = self._refine_params(params)
+        _check(self._lib, self._lib.gpsacq_refine_device(self._h, d_bits_ptr, int(n_bytes), int(stride), d_tasks_ptr, d_peaks_ptr, int(n_tasks), rp,
+                                                         d_fine_ptr, 1 if sync else 0))
+
+    def coarse_obs_fine_device(self, d_peaks_ptr, d_fine_ptr, n_fix, n_chans, d_obs_ptr, snr_min=THRESHOLD, sync=True):
+        _check(self._lib, self._lib.gpsacq_coarse_obs_fine_device(self._h, d_peaks_ptr, d_fine_ptr, int(n_fix), int(n_chans), float(snr_min), d_obs_ptr,
+                                                                  1 if sync else 0))
+
+    def coarse_fix_fine_device(self, eph, d_bits_ptr, n_bytes, d_tasks_ptr, d_peaks_ptr, n_fix, n_chans, d_prior_ptr, d_fix_ptr, d_info_ptr,
+                               d_fine_ptr=None, d_obs_ptr=None, d_obs_out_ptr=None, stride=BLOCK_BYTES, refine_params=None, params=None, sync=True):
+        """gpsacq_coarse_fix_fine_device: capture, tasks (block outer, channel inner) and peaks -> fine records -> observations ->
+        coarse-time fixes in device memory, no host copy in between; d_fine_ptr, d_obs_ptr and d_obs_out_ptr may be None."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        rr, rp = self._refine_params(refine_params)
+        cr, cp = self._coarse_params(params)
+        _check(self._lib, self._lib.gpsacq_coarse_fix_fine_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_bits_ptr, int(n_bytes),
+                                                                  int(stride), d_tasks_ptr, d_peaks_ptr, int(n_fix), int(n_chans), rp, d_prior_ptr, cp,
+                                                                  d_fine_ptr, d_obs_ptr, d_fix_ptr, d_info_ptr, d_obs_out_ptr, 1 if sync else 0))
+
+    def refine_last_ms(self):
+        """Device milliseconds of the last refine* calls: (k_refine or 0, k_coarse_obs_fine or 0)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(self._lib, self._lib.gpsacq_refine_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def coarse_obs_device(self, d_peaks_ptr, n_fix, n_chans, d_obs_ptr, snr_min=THRESHOLD, sync=True):
         _check(self._lib, self._lib.gpsacq_coarse_obs_device(self._h, d_peaks_ptr, int(n_fix), int(n_chans), float(snr_min), d_obs_ptr,

@@ -1458,8 +1458,8 @@ GPSACQ_API int gpsacq_fix_raim_last_ms(const gpsacq_engine* e, float* sat_state_
  *      valid = snr >= snr_min and 0 <= ca_shift < fs / 1000,   eph = channel,   tx_frac = (double)ca_shift / fs,   weight = 1.0,
  *      tx_ms = reserved = 0;
  * an observation that is not valid is 32 zero bytes.  fs is the engine's.  A whole-sample code phase is off by up to one sample,
- * c / fs = 55 m of range at 5.456 MHz, so such fixes are good to 100-200 m with eight satellites; interpolating the correlation
- * peak below a sample is the next step and is not done here.
+ * c / fs = 55 m of range at 5.456 MHz, so such fixes are good to 100-200 m with eight satellites; the code phase below a sample
+ * is the business of "Fine code phases" further down, whose observations (gpsacq_coarse_obs_fine) enter here unchanged.
  *
  * gpsacq_coarse_fix_batch: host pointers, returns after completion; a negative or non-finite weight is GPSACQ_ERR_ARG; params
  * NULL means the defaults; obs_out may be NULL, fix_out and info_out may not.  gpsacq_coarse_fix_batch_device: obs, prior and the
@@ -1473,8 +1473,8 @@ GPSACQ_API int gpsacq_fix_raim_last_ms(const gpsacq_engine* e, float* sat_state_
  * row is held in registers -- the satellite loop of every pass reads the observation back from memory, evaluates the orbit
  * (csrc/orbit_device.hpp, the one copy k_sat_state and k_sat_state_rate use) and adds into the 15 + 5 sums.
  *
- * OUT OF SCOPE.  Sub-sample code phases (no change to the correlator or to gpsacq_peak).  Doppler-aided time.  gps_test and
- * gps_track.
+ * OUT OF SCOPE.  Doppler-aided time.  gps_test and gps_track.  (Sub-sample code phases: "Fine code phases" below; the correlator
+ * and gpsacq_peak stay as they are.)
  */
 typedef struct { double x, y, z; int32_t rx_ms; int32_t reserved; } gpsacq_coarse_prior;                                    /* 32 bytes */
 typedef struct { double rms_max_m; double reserved; } gpsacq_coarse_params;                                                  /* 16 bytes */
@@ -1496,6 +1496,109 @@ GPSACQ_API int gpsacq_coarse_fix_peaks_device(gpsacq_engine* e, const gpsacq_eph
 /* device time of k_coarse_obs and k_coarse_fix as last run on this engine, milliseconds (HIP events on its stream; waits for
  * them); a kernel that has not run reads 0.  Either pointer may be NULL. */
 GPSACQ_API int gpsacq_coarse_last_ms(const gpsacq_engine* e, float* obs_ms, float* fix_ms);
+
+/*
+ * ---- Fine code phases: search peaks refined below a sample --------------------------------------------------------------------
+ *
+ * A search peak carries its code phase in whole samples: tx_frac = ca_shift / fs is off by up to half a sample, 27 m of range at
+ * 5.456 MHz (15.8 m rms).  gpsacq_refine goes back to the 1-bit capture for every hit: in the time domain it correlates a window
+ * of consecutive blocks against early, prompt and late replicas at the hit's Doppler and reads the code phase below a sample off
+ * the early and late amplitudes, as the DLL of THE CHANNEL MODEL does.  One 7.3 ms block does not beat the sample grid: thermal
+ * noise and the 16-samples-per-3-chips staircase of fs = 5.456 MHz leave about 12 m.  Over ~100 ms the code Doppler slides the
+ * replica across the staircase and averages it out: sixteen blocks leave about a fifth of the whole-sample error (simulated with
+ * eight satellites at amplitude 0.2, noise sigma 1: 2.9 m rms against 15.8 m).  THE MODEL; the kernels (csrc/refine_kernels.hip)
+ * and the reference of the tests (tests/refine_ref.py) are both written from this text.  Integer arithmetic "mod 2^N" is unsigned
+ * wrap-around as in THE CHANNEL MODEL, whose carrier bits, chip table and sums are used.
+ *
+ * INPUTS.  bits[n_bytes]: the capture as gpsacq_search reads it, sample m is bit m % 8 of byte m / 8, 1 = negative.  stride: bytes
+ * between blocks, 5000 <= stride <= 2^31, any value, odd ones included.  tasks[n_tasks] and peaks[n_tasks]: the task list given
+ * to the search and the peaks it returned; tasks == NULL is the reference schedule, task t = (block t, PRN t % 32).
+ * gpsacq_refine_params: blocks, 1 .. 64, the length of the window; min_segments >= 1; half_spacing_chips in [1/64, 0.5], the
+ * distance d of the early and of the late replica from the prompt one; snr_min, finite.  gpsacq_refine_default_params (host only)
+ * sets 16, 1, 0.25 and 25.0, the threshold of the search.
+ *
+ * PER TASK.  spm = gpsacq_info.num_lags, o = 8 block stride (the first sample of the block), FULL = 1023 * 2^32.
+ * 1. NCO WORDS.  lo_rate and ca_rate are those of gpsacq_handoff_engine(e, peak, 0, .), the step of the engine's current Doppler
+ *    grid included: lo_dop = lo_shift * step (on the reference grid lo_shift * fs / 40000), ca_dop = lo_dop / L1 * 1.023e6,
+ *    lo_rate = (uint32)((fc + lo_dop) / fs * 2^32), ca_rate = (uint32)((1.023e6 + ca_dop) / fs * 2^32), every operation rounded
+ *    by itself (no fused multiply-add).
+ * 2. NOT A HIT (GPSACQ_FINE_NO_HIT): not snr >= snr_min; ca_shift outside [0, spm); block < 0 or prn outside 0 .. 31; o at or
+ *    beyond sample 8 n_bytes; fc + lo_dop or 1.023e6 + ca_dop outside [0, fs); ca_rate == 0.  The record is then that flag and
+ *    zeros.
+ * 3. WINDOW AND SEGMENTS.  The window is the blocks * 40000 samples that start at o: contiguous in the stream, whatever the stride.
+ *    It is cut into segments of spm samples, one nominal code period each:
+ *      segments = min(floor(blocks * 40000 / spm), floor((8 n_bytes - o) / spm));
+ *    the tail of the window is not used.  Fewer segments than the first term: GPSACQ_FINE_SHORT.  Fewer than min_segments:
+ *    GPSACQ_FINE_FEW.  Nothing is read at or beyond byte n_bytes.
+ * 4. SUMS.  D = (uint32)(half_spacing_chips * 2^32), P0 = (ca_shift * ca_rate) mod FULL.  For sample j of the window (the first is
+ *    j = 0), which is sample o + j of the capture:
+ *      carrier phase  ph = j * lo_rate (mod 2^32); cos bit and sin bit as in THE CHANNEL MODEL
+ *      prompt         P = (P0 + j * ca_rate) mod FULL;  early E = (P + D) mod FULL;  late L = (P - D) mod FULL
+ *      the chip at position X is chip[X >> 32]
+ *    and per segment s (samples j = s spm .. (s + 1) spm - 1) the six sums I_X, Q_X, X in E, P, L, as in THE CHANNEL MODEL.
+ *      early = sum over the segments of I_E^2 + Q_E^2,   prompt and late likewise,
+ *    as uint64: a segment adds at most 2 spm^2, so nothing overflows.
+ * 5. ESTIMATE, in fp64.  d = D / 2^32, a_E = sqrt((double)early), a_L = sqrt((double)late).  early + late == 0:
+ *    GPSACQ_FINE_NO_POWER, offset_chips = tx_frac = 0.  Otherwise
+ *      offset_chips = ((1 - d) * (a_E - a_L)) / (a_E + a_L)
+ *    (early stronger = the signal's code is ahead, as in the DLL; the triangle's early and late arms are 1 - d -+ x at an offset
+ *    x, so the ratio is x / (1 - d)),
+ *      pos = P0 / 2^32 + offset_chips, moved once by +-1023 into [0, 1023),     tx_frac = pos / 1.023e6,
+ *    and a tx_frac that is not < 1e-3 is 0.0.
+ * 6. USABLE: the record carries none of GPSACQ_FINE_NO_HIT, GPSACQ_FINE_NO_POWER and GPSACQ_FINE_FEW.
+ * The record is gpsacq_fine; a hit's record keeps lo_rate, ca_rate, the segment count and the three sums whatever its flags.
+ *
+ * OBSERVATIONS.  gpsacq_coarse_obs_fine: gpsacq_coarse_obs (FROM PEAKS, above) with fine[n_fix][n_chans] beside the peaks; valid
+ * additionally needs a usable record whose tx_frac lies in [0, 1e-3), and tx_frac is the record's.  The observations drop into
+ * gpsacq_coarse_fix_batch*, and its obs_out into gpsacq_fix_batch, gpsacq_fix_atm_batch and gpsacq_fix_raim_batch, all unchanged.
+ *
+ * gpsacq_refine: host pointers, returns after completion.  gpsacq_refine_device: bits, tasks, peaks and fine are device pointers
+ * (bits at any byte address), params stays a host pointer (NULL: the defaults); work on the engine's stream, sync != 0 waits.
+ * Neither form reads the task list on the host, so both report a task out of range as GPSACQ_FINE_NO_HIT, and they agree byte
+ * for byte.  gpsacq_coarse_obs_fine / _device likewise.  gpsacq_coarse_fix_fine_device: k_refine, k_coarse_obs_fine and
+ * k_coarse_fix on the same stream, capture, tasks and peaks to records, observations and fixes with no host copy in between;
+ * tasks are block outer and channel inner (task b * n_chans + c, eph = c) as FROM PEAKS has them, n_tasks = n_fix * n_chans, the
+ * observations' snr_min is refine_params' and d_fine and d_obs may be NULL (engine scratch).  Argument errors -- a NULL pointer,
+ * n_tasks or n_fix == 0, n_bytes == 0, a parameter or the stride outside the bounds above, n_chans outside
+ * 1..GPSACQ_FIX_MAX_SATS -- return GPSACQ_ERR_ARG, launch nothing and write nothing; an engine whose num_lags exceeds 65535, or
+ * whose fs is below 1.138 MHz (1.023e6 / fs + 1 / 1540 > 0.9 chips per sample), is GPSACQ_ERR_UNSUPPORTED.
+ * Kernel (csrc/refine_kernels.hip): k_refine, one workgroup of four wave64 per task; wave w takes segments w, w + 4, ..., lane l
+ * the 32-sample words l, l + 64, ... of a segment, five masks and six popcounts per word as the tracking channels'; the 96 chips
+ * of a word are bits of one 32-chip window cut out of the chip sequence in LDS; the squares are added as integers, so the record
+ * does not depend on the order of anything.
+ *
+ * LIMITS OF THE MODEL.  The estimate is the mean offset over the window, carried to its first sample at the replica's rate: a
+ * Doppler half a bin off (68 Hz at 5.456 MHz) moves it by at most 0.044 chips/s * T / 2, which is 0.75 m at 16 blocks.  The
+ * triangle is linear only for |offset| <= d, and a 1-bit front end rounds its corners.  The segments are added non-coherently, so
+ * data-bit flips and the half-bin carrier error cost little.  Subtracting the analytic noise floor from the three powers did not
+ * help consistently in simulation and is left out.  For the peaks of plain 1-bit searches only.
+ *
+ * OUT OF SCOPE.  Accumulated or re-aligned searches (gpsacq_set_noncoherent, creep compensation, block alignment), fs above
+ * 10 MHz where ca_shift refers to block 0 of several passes, 8-bit IQ input, multi-GPU, gps_test and gps_track.  The correlator
+ * and gpsacq_peak do not change.
+ */
+#define GPSACQ_FINE_NO_HIT 1     /* the peak is no hit, or its task or NCO words are out of range: the record is this flag and zeros */
+#define GPSACQ_FINE_SHORT 2      /* the capture ends before the window does */
+#define GPSACQ_FINE_NO_POWER 4   /* early + late == 0 */
+#define GPSACQ_FINE_FEW 8        /* segments < min_segments */
+typedef struct { int32_t blocks; int32_t min_segments; double half_spacing_chips; double snr_min; } gpsacq_refine_params;          /* 24 bytes */
+typedef struct { int32_t flags, segments; uint32_t lo_rate, ca_rate; uint64_t early, prompt, late; double offset_chips, tx_frac; } gpsacq_fine; /* 56 bytes */
+GPSACQ_API int gpsacq_refine_default_params(gpsacq_refine_params* p);   /* host only */
+GPSACQ_API int gpsacq_refine(gpsacq_engine* e, const uint8_t* bits, size_t n_bytes, size_t stride, const gpsacq_task* tasks, const gpsacq_peak* peaks,
+                             size_t n_tasks, const gpsacq_refine_params* params, gpsacq_fine* fine_out);
+GPSACQ_API int gpsacq_refine_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
+                                    size_t n_tasks, const gpsacq_refine_params* params, void* d_fine, int sync);
+GPSACQ_API int gpsacq_coarse_obs_fine(gpsacq_engine* e, const gpsacq_peak* peaks /* [n_fix][n_chans] */, const gpsacq_fine* fine, size_t n_fix,
+                                      int n_chans, double snr_min, gpsacq_obs* obs);
+GPSACQ_API int gpsacq_coarse_obs_fine_device(gpsacq_engine* e, const void* d_peaks, const void* d_fine, size_t n_fix, int n_chans, double snr_min,
+                                             void* d_obs, int sync);
+GPSACQ_API int gpsacq_coarse_fix_fine_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_bits, size_t n_bytes, size_t stride,
+                                             const void* d_tasks, const void* d_peaks, size_t n_fix, int n_chans,
+                                             const gpsacq_refine_params* refine_params, const void* d_prior, const gpsacq_coarse_params* params,
+                                             void* d_fine, void* d_obs, void* d_fix, void* d_info, void* d_obs_out, int sync);
+/* device time of k_refine and k_coarse_obs_fine as last run on this engine, milliseconds (HIP events on its stream; waits for
+ * them); a kernel that has not run reads 0.  Either pointer may be NULL. */
+GPSACQ_API int gpsacq_refine_last_ms(const gpsacq_engine* e, float* refine_ms, float* obs_ms);
 
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);

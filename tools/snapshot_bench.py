@@ -12,7 +12,14 @@ The generator runs every satellite at the Doppler it has in the middle of the ca
 away from that instant the truth is off by the range acceleration (metres over 15 s), well below the 55 m a whole-sample code phase
 is worth at 5.456 MHz.
 
-    python tools/snapshot_bench.py [--blocks 2048] [--reps 5]
+    python tools/snapshot_bench.py [--blocks 2048] [--reps 5] [--refine [--refine-blocks 16]]
+
+--refine: the capture is made K - 1 blocks longer (K = --refine-blocks) so that every searched block has its whole window, and
+each repetition also runs gpsacq_coarse_fix_fine_device on the same capture, tasks and peaks: k_refine (the fine code phases of
+include/gpsacq.h), k_coarse_obs_fine and k_coarse_fix.  The line gains refine_ms (the best k_refine time, beside search_ms of the
+same run), the position error of the fine fixes beside the whole-sample ones of the same blocks, and the rms code-phase error of
+both kinds of phase against the generator's own law (the code position (m + code_phase) * chips_per_sample at a block's first
+sample m), in metres of range.  The generator's constant Doppler (above) is part of the fine fixes' position error.
 """
 import argparse
 import json
@@ -30,6 +37,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=2048)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--refine", action="store_true", help="also refine the peaks below a sample and fix from the fine code phases")
+    ap.add_argument("--refine-blocks", type=int, default=16, help="window of the refinement, in blocks (1 .. 64)")
     a = ap.parse_args()
 
     import numpy as np
@@ -49,7 +58,7 @@ def main():
     blk_ms, blk_frac = block_times(ref_ms, ref_frac - mid * spb / FS, a.blocks, spb, FS)
     prior = priors(geo, blk_ms, seed=3, km=30.0, secs=30.0)
     tasks = np.array([(b, s[0] - 1) for b in range(a.blocks) for s in sats], dtype=np.int32)
-    n_bytes, n_tasks = a.blocks * gpsacq.BLOCK_BYTES, len(tasks)
+    n_bytes, n_tasks = (a.blocks + (a.refine_blocks - 1 if a.refine else 0)) * gpsacq.BLOCK_BYTES, len(tasks)
 
     with gpsacq.Engine(FC, FS, 5000.0, device=0) as eng:
         dev = lambda arr: torch.from_numpy(arr.view(np.uint8).reshape(-1).copy()).to("cuda:0")
@@ -58,9 +67,13 @@ def main():
         d_peaks = zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize)
         d_fix, d_info = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
         d_out, d_fix4 = zeros(n_tasks * gpsacq.OBS_DTYPE.itemsize), zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize)
+        if a.refine:
+            rp = gpsacq.refine_params(blocks=a.refine_blocks)
+            d_fine = zeros(n_tasks * gpsacq.FINE_DTYPE.itemsize)
+            d_fix_f, d_info_f = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
         torch.cuda.synchronize()
         eng.generate_device(d_bits.data_ptr(), n_bytes, sats, noise_sigma=1.0, seed=77)
-        best, search_best = None, float("inf")
+        best, search_best, refine_best = None, float("inf"), float("inf")
         for _ in range(1 + a.reps):  # the first call also allocates the engine's scratch
             eng.search_device(d_bits.data_ptr(), a.blocks, d_peaks.data_ptr(), d_tasks_ptr=d_tasks.data_ptr(), n_tasks=n_tasks, sync=True)
             search_ms = eng.last_timing()["ms_total"]
@@ -71,6 +84,15 @@ def main():
             ms = eng.coarse_last_ms() + eng.fix_last_ms()
             if best is None or sum(ms) < sum(best):
                 best = ms
+            if a.refine:
+                eng.coarse_fix_fine_device(ephs, d_bits.data_ptr(), n_bytes, d_tasks.data_ptr(), d_peaks.data_ptr(), a.blocks, len(sats),
+                                           d_prior.data_ptr(), d_fix_f.data_ptr(), d_info_f.data_ptr(), d_fine_ptr=d_fine.data_ptr(), refine_params=rp,
+                                           sync=True)
+                refine_best = min(refine_best, eng.refine_last_ms()[0])
+        if a.refine:
+            fine = d_fine.cpu().numpy().view(gpsacq.FINE_DTYPE).reshape(a.blocks, len(sats))
+            fix_f = d_fix_f.cpu().numpy().view(gpsacq.FIX_DTYPE)
+            info_f = d_info_f.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
         fix = d_fix.cpu().numpy().view(gpsacq.FIX_DTYPE)
         info = d_info.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
         four = d_fix4.cpu().numpy().view(gpsacq.FIX_DTYPE)
@@ -81,6 +103,29 @@ def main():
     off = np.linalg.norm(np.stack([fix["x"], fix["y"], fix["z"]], 1) - geo["rx"], axis=1)
     both = ok & (four["status"] == 0)
     apart = np.linalg.norm(np.stack([fix[k] - four[k] for k in "xyz"], 1), axis=1)
+    extra = {}
+    if a.refine:
+        # the generator's law: at sample m satellite s shows the code position (m + code_phase) * chips_per_sample
+        C, L1, CPS = 2.99792458e8, 1575.42e6, 1.023e6
+        m0 = np.arange(a.blocks, dtype=np.float64)[:, None] * spb
+        cps = np.array([CPS * (1.0 + s[2] / L1) / FS for s in sats])[None, :]
+        want = ((m0 + np.array([s[3] for s in sats])[None, :]) * cps % 1023.0) / CPS
+        wrap = lambda t: (t + 0.5e-3) % 1e-3 - 0.5e-3
+        pk = peaks.reshape(a.blocks, len(sats))
+        hit = (pk["snr"] >= gpsacq.THRESHOLD) & ((fine["flags"] & (gpsacq.FINE_NO_HIT | gpsacq.FINE_NO_POWER | gpsacq.FINE_FEW)) == 0)
+        hit &= np.abs(wrap(pk["ca_shift"] / FS - want)) * FS <= 1.5  # true peaks only: a false one is no code-phase error
+        e_whole, e_fine = C * wrap(pk["ca_shift"] / FS - want)[hit], C * wrap(fine["tx_frac"] - want)[hit]
+        ok_f = (fix_f["status"] == 0) & (info_f["flags"] == 0) & clean  # the same blocks on both sides
+        off_f = np.linalg.norm(np.stack([fix_f["x"], fix_f["y"], fix_f["z"]], 1) - geo["rx"], axis=1)
+        extra = {
+            "refine_blocks": a.refine_blocks, "refine_ms": round(refine_best, 4), "refine_over_search": round(refine_best / search_best, 4),
+            "fine_hits": int(hit.sum()), "code_phase_rms_whole_m": round(float(np.sqrt((e_whole ** 2).mean())), 2),
+            "code_phase_rms_fine_m": round(float(np.sqrt((e_fine ** 2).mean())), 2),
+            "fine_blocks_compared": int(ok_f.sum()),
+            "position_error_median_whole_same_blocks_m": round(float(np.median(off[ok_f])), 2) if ok_f.any() else None,
+            "position_error_max_whole_same_blocks_m": round(float(off[ok_f].max()), 2) if ok_f.any() else None,
+            "position_error_median_fine_m": round(float(np.median(off_f[ok_f])), 2) if ok_f.any() else None,
+            "position_error_max_fine_m": round(float(off_f[ok_f].max()), 2) if ok_f.any() else None}
     print(json.dumps({
         "bench": "snapshot", "device": name, "blocks": a.blocks, "sats": len(sats), "tasks": n_tasks, "prior_off_km": 30.0, "prior_off_s": 30.0,
         "search_ms": round(search_best, 4), "coarse_obs_ms": round(best[0], 4), "coarse_fix_ms": round(best[1], 4),
@@ -91,7 +136,7 @@ def main():
         "rms_median_m": round(float(np.median(fix["rms"][clean])), 2) if clean.any() else None,
         "passes_max": int(fix["iterations"].max()), "pdop_median": round(float(np.median(info["pdop"][ok])), 3) if ok.any() else None,
         "cdop_median_s_per_m": float(np.median(info["cdop"][ok])) if ok.any() else None,
-        "fix_batch_on_obs_out_max_m": float(apart[both].max()) if both.any() else None}))
+        "fix_batch_on_obs_out_max_m": float(apart[both].max()) if both.any() else None, **extra}))
 
 
 if __name__ == "__main__":
