@@ -260,6 +260,9 @@ __global__ __launch_bounds__(WG, WPS) void k_corr(CorrArgs a) {
     // pass 2's 500 twiddles; with FOLD followed by the accumulate factors [alpha][column], in whole 1 KB chunks (the DMA's unit)
     constexpr int TQS = TqStride<MC>::value;
     constexpr int NTAB = NT2 + RA * TQS, NCHUNK = (NTAB + 127) / 128;
+    // pass 2 reads its output twiddles one pair of rows ahead of its stores (acq_math.hpp pass2_inplace) in the three-per-CU instances
+    // that stay inside their 168 VGPRs with it: the 40-column one would spill 36 bytes instead of 28 and keeps the plain loop
+    constexpr bool P2_AHEAD = WPS == 3 && MC <= 33;
     __shared__ __attribute__((aligned(16))) cf tabs[FOLD ? NCHUNK * 128 : NT2];
     cf* const t2s = tabs;
     const cf* const tqs = tabs + NT2;
@@ -382,7 +385,13 @@ __global__ __launch_bounds__(WG, WPS) void k_corr(CorrArgs a) {
 #pragma unroll
         for (int m = 0; m < MC; ++m) pw[m] = 0.f;
     }
-    const int t3 = tid < NBF3 ? tid : 0;
+    int t3 = tid < NBF3 ? tid : 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // PERSIST: formed anew for every cell (the empty asm hides that it is the same each time), or hipcc hoists the 64-bit address of
+    // the thread's rho_map entry out of the cell loop and holds it in two VGPRs across the sub-transforms -- the two that the
+    // 22-column instance needs to keep pass 2's read-ahead out of scratch
+    if constexpr (PERSIST && L::REMAP) asm volatile("" : "+v"(t3));
+#endif
     const int rho = corr_rho<L>(a, t3);  // the radix-20 butterfly (output residue) this thread owns
     const int n_acc = NC ? KA(n_acc) : 1;
     // FOLD: which 16 bytes of the global table fold[q] (acq_tables.hpp TablesFold: [t2q (500)][tq (10 x 160)] per q) each lane copies
@@ -445,7 +454,7 @@ __global__ __launch_bounds__(WG, WPS) void k_corr(CorrArgs a) {
             if constexpr (FOLD) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
             __syncthreads();  // also orders the t2s fill before its first use
-            corr_phase2<L>(tid, t2s, lds);
+            corr_phase2<L, P2_AHEAD>(tid, t2s, lds);
             __syncthreads();
             constexpr bool FIRST = decltype(first)::value;
             if constexpr (FOLD) corr_phase3_fold<MC, L, FIRST>(tid, rho, tqs, lds, acc);

@@ -37,6 +37,12 @@
 #else
 #define ACQ_PK_ASM 0
 #endif
+// scheduling fence: hipcc moves nothing across it (used where it otherwise undoes an issue order written on purpose)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define ACQ_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+#else
+#define ACQ_SCHED_FENCE() ((void)0)
+#endif
 
 namespace acq {
 
@@ -505,7 +511,12 @@ template <int DIR, bool W1H = false> ACQ_HD void pass1_store_pair(const cf* x0, 
 
 // pass 2 for butterfly e (0..199), in place; t2 may live in LDS (its own allocation, so the
 // compiler knows the in-place stores do not alias it) or in global memory.
-template <int DIR, class L = LayA> ACQ_HD void pass2_inplace(int e, const cf* __restrict__ t2, cf* lds) {
+// AHEAD (the correlator's three-per-CU instances): the output twiddles are read one pair of rows ahead of the pair being multiplied
+// and stored.  hipcc otherwise emits read pair, wait for everything (the previous store included), multiply, store -- twelve exposed
+// LDS round trips per sub-transform; reading ahead costs four registers from the second store on, when the outputs already stored
+// have freed more than that.  The same calls on the same operands in the same order: the same bits.  (The fences pin the order:
+// without them the scheduler folds the loop back into the serial chain.)
+template <int DIR, class L = LayA, bool AHEAD = false> ACQ_HD void pass2_inplace(int e, const cf* __restrict__ t2, cf* lds) {
     int al, jpp;
     pass2_owner<L>(e, al, jpp);
     cf* p = lds + L::SA * al + L::SJ * jpp;
@@ -514,8 +525,32 @@ template <int DIR, class L = LayA> ACQ_HD void pass2_inplace(int e, const cf* __
     for (int b = 0; b < RB; ++b) x[b] = p[L::SB * b];
     radix25<DIR>(x, y);
     p[0] = y[0];
+    if constexpr (AHEAD) {
+        static_assert(RB % 2 == 1, "rows 1 .. RB - 1 in pairs");
+        const cf* tw2 = t2 + jpp;
+        cf wa = tw2[1 * RC], wb = tw2[2 * RC];
 #pragma unroll
-    for (int be = 1; be < RB; ++be) p[L::SB * be] = tw<DIR>(y[be], t2[be * RC + jpp]);
+        for (int be = 1; be < RB; be += 2) {
+            cf na = wa, nb = wb;
+            if (be > 1 && be + 2 < RB) {  // (not ahead of the first store: all 25 outputs are still live there)
+                na = tw2[(be + 2) * RC];
+                nb = tw2[(be + 3) * RC];
+                ACQ_SCHED_FENCE();
+            }
+            p[L::SB * be] = tw<DIR>(y[be], wa);
+            p[L::SB * (be + 1)] = tw<DIR>(y[be + 1], wb);
+            if (be + 2 < RB) ACQ_SCHED_FENCE();
+            if (be == 1) {
+                na = tw2[(be + 2) * RC];
+                nb = tw2[(be + 3) * RC];
+            }
+            wa = na;
+            wb = nb;
+        }
+    } else {
+#pragma unroll
+        for (int be = 1; be < RB; ++be) p[L::SB * be] = tw<DIR>(y[be], t2[be * RC + jpp]);
+    }
 }
 
 // pass 3 for the butterfly rho = 10 beta + alpha (0..249): y[n''] = F[250 n'' + rho].

@@ -60,12 +60,7 @@ ACQ_HD void load_tw1(int tid, const cf* __restrict__ t1, cf (&w)[2][RA - 1]) {
 // ---------------------------------------------------------------------------------------
 // Correlate(): prod = conj(data) * shifted code (:181-185) fused into pass 1 of IDFT_5000.
 // The 20 loads are issued in NB batches; a scheduling barrier after each batch keeps hipcc from
-// sinking them next to their first use (it otherwise emits load, s_waitcnt vmcnt(0), use, load ...).
-#if defined(__HIP_DEVICE_COMPILE__)
-#define ACQ_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define ACQ_SCHED_FENCE() ((void)0)
-#endif
+// sinking them next to their first use (it otherwise emits load, s_waitcnt vmcnt(0), use, load ...): ACQ_SCHED_FENCE, acq_math.hpp.
 template <int NB, bool W1H = false, class L = LayB>
 ACQ_HD void corr_phase1(int tid, int q, int dop, const cf* __restrict__ dpp, const cf* __restrict__ cpp,
                         int crow, int halo, const cf (&w)[2][RA - 1], cf* lds) {
@@ -119,9 +114,10 @@ ACQ_HD void corr_phase1(int tid, int q, int dop, const cf* __restrict__ dpp, con
     }
 }
 
-template <class L = LayB>
+// AHEAD: output twiddles read one pair of rows ahead of the stores (acq_math.hpp pass2_inplace)
+template <class L = LayB, bool AHEAD = false>
 ACQ_HD void corr_phase2(int tid, const cf* t2, cf* lds) {
-    if (tid < NBF2) pass2_inplace<+1, L>(tid, t2, lds);
+    if (tid < NBF2) pass2_inplace<+1, L, AHEAD>(tid, t2, lds);
 }
 // acc[m] accumulates y[n] for n = 250 (m0 + m) + rho over the 8 polyphase components (m0, the first
 // column of this pass, is a multiple of 20 so that column m0 + m reads radix-20 output m % 20):
