@@ -360,6 +360,33 @@ GPSACQ_API int gpsacq_iq8_accumulate_sums(gpsacq_engine* e, const void* iq, size
  * bit = (sum < 0), sample m in bit m % 8 of byte m / 8.  Uses the engine's fc and fs.  Deterministic
  * in (seed, arguments).  A search of the result reports lo_shift = round(doppler * 40000 / fs) and
  * ca_shift = (code_phase + 8 * stride * block) mod (fs / 1000) for block-sized strides.
+ *
+ * THE GENERATOR'S LAW (gpsacq_generate*, gpsacq_generate_nav_range*, gpsacq_generate_iq8_range*; tests/gen_ref.py restates it from
+ * this text).  m is the absolute sample index, a 64-bit unsigned integer, first_sample included; every quantity below is a
+ * function of m and the arguments alone.
+ *   Rates (host, IEEE double, in this order of operations):
+ *       chips_per_sample  = 1.023e6 * (1.0 + doppler_hz / 1575.42e6) / fs
+ *       cycles_per_sample = (fc + doppler_hz) / fs          (8-bit generator: if_hz in the place of fc)
+ *     amplitude, noise_sigma and scale are floats.
+ *   Noise.  h = mix(seed ^ (m * 0x9e3779b97f4a7c15)) in 64-bit unsigned arithmetic, mix being the splitmix64 finaliser
+ *       z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;  z = (z ^ (z >> 27)) * 0x94d049bb133111eb;  z ^ (z >> 31).
+ *     u1 = (float(h >> 32) + 1) * 2^-32, a float in (0, 1] (1 where the float sum rounds up to 2^32); u2 = float(h & 0xffffffff) * 2^-32.
+ *     n_I = sqrt(-2 ln u1) cos(2 pi u2), n_Q = sqrt(-2 ln u1) sin(2 pi u2), in float with the fast intrinsics (__logf, __cosf,
+ *     __sinf; 2 pi as the float 6.2831853).  The 1-bit generator uses n_I, the 8-bit one both.
+ *   Chip count.  q = floor((m + code_phase_samples) * chips_per_sample), a signed 64-bit integer, floor also below zero.  The chip
+ *     is chip[q mod 1023] of the PRN (+1 for a C/A bit of 0, -1 for 1), the modulo a true one for q < 0 (q = -1: chip 1022).  The
+ *     navigation bit is nav[s * n_nav_bits + (floor(q / 20460) mod n_nav_bits)], floor and modulo true ones for q < 0 as well
+ *     (q = -1: bit n_nav_bits - 1).
+ *   Carrier.  p = cycles_per_sample * m + carrier_phase_cycles in double, reduced to [0, 1) by p - floor(p), cast to float, and
+ *     the carrier is cospif(2 p) (and sinpif(2 p) for Q): exact zeros at the quarter points, exact +-1 at 0 and 1/2.
+ *   Sum.  y = noise_sigma * n_I + sum over the satellites in their order of amplitude * nav * chip * cos, in float.
+ *   1-bit decision.  bit = (y < 0); a sum of +0 or -0 gives bit 0.
+ *   8-bit value.  rintf(scale * y) per arm, ties to even, clamped to [-127, 127] (never -128), plus 128 for GPSACQ_IQ_U8.  The Q
+ *     arm is noise_sigma * n_Q + sum amplitude * nav * chip * (+sin).
+ *   Precision.  Code position and carrier phase are evaluated in double from the absolute sample index, as a product and a sum,
+ *     or fused; their resolution is 2^-52 of their size, e.g. 2e-4 cycle and 2e-4 chip at sample 2^40.  The float cast of the
+ *     phase resolves 2^-24 cycle.  Where the exact code position lies within rounding of an integer, or the exact sum within
+ *     rounding of zero or of a half-integer, either neighbour may come out.
  */
 typedef struct {
     int32_t prn;                 /* 1..32 */
@@ -603,7 +630,8 @@ GPSACQ_API int gpsacq_nav_subframes(const uint8_t* bits, int n_bits, gpsacq_subf
 /*
  * gpsacq_generate_range with navigation data: satellite s is multiplied by nav[s * n_nav_bits + (floor(q / 20460) mod n_nav_bits)]
  * (+1 / -1), q being the chip count of gpsacq_generate's law (floor((m + code_phase) * 1.023e6 (1 + doppler / L1) / fs)), so a bit
- * lasts 20 code periods and bit 0 starts at q = 0.  nav == NULL: exactly gpsacq_generate_range.
+ * lasts 20 code periods and bit 0 starts at q = 0; q < 0 counts backwards from the last bit (THE GENERATOR'S LAW, at gpsacq_sat).
+ * nav == NULL: exactly gpsacq_generate_range.
  */
 GPSACQ_API int gpsacq_generate_nav_range(gpsacq_engine* e, uint8_t* bits_out, size_t n_bytes, uint64_t first_sample, const gpsacq_sat* sats,
                                          int n_sats, const int8_t* nav, int n_nav_bits, float noise_sigma, uint64_t seed);
@@ -695,7 +723,8 @@ GPSACQ_API int gpsacq_iq8_accumulate_power(const gpsacq_engine* e, const void* i
  * interleaved bytes, GPSACQ_IQ_S8 as they are, GPSACQ_IQ_U8 plus 128.  iq_out[2 * n_samples] holds samples first_sample ..
  * first_sample + n_samples - 1 (any first_sample); deterministic in (seed, arguments).  The engine's fc plays no part.  A search
  * with mix_hz = fc - if_hz (GPSACQ_SAMPLES_SIGN / _REAL) or mix_hz = -if_hz (GPSACQ_SAMPLES_COMPLEX) reports lo_shift =
- * round(doppler * 40000 / fs) and the code phase of gpsacq_generate.  nav == NULL: no data.
+ * round(doppler * 40000 / fs) and the code phase of gpsacq_generate.  nav == NULL: no data.  Noise, chip count, carrier, rounding
+ * and clamp sample by sample: THE GENERATOR'S LAW, at gpsacq_sat.
  */
 GPSACQ_API int gpsacq_generate_iq8_range(gpsacq_engine* e, void* iq_out, size_t n_samples, uint64_t first_sample, int format, double if_hz,
                                          float scale, const gpsacq_sat* sats, int n_sats, const int8_t* nav, int n_nav_bits,
