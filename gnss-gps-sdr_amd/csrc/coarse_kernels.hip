@@ -90,24 +90,7 @@ __device__ __forceinline__ void inverse_diagonal5(const double (&l)[15], double 
     }
 }
 
-// ---- time ---------------------------------------------------------------------------------------------------------------------
-// t seconds into whole milliseconds and a fraction in [0, 1e-3): fill_fix's rule
-__device__ __forceinline__ void split(double t, double& k, double& frac) {
-    k = floor(t * 1e3);
-    frac = t - k * 1e-3;
-    if (frac < 0.0) k -= 1.0, frac += 1e-3;
-    if (frac >= 1e-3) k += 1.0, frac -= 1e-3;
-}
-
-// millisecond of week base + k.  A k that is no count of milliseconds (a diverged or non-finite time) is taken as 0: the row
-// fails its own tests, the conversion must not overflow on the way there
-__device__ __forceinline__ int32_t week_ms(int32_t base, double k) {
-    if (!(fabs(k) < 1e12)) k = 0.0;
-    int64_t ms = ((int64_t)base + (int64_t)k) % WEEK_MS;
-    if (ms < 0) ms += WEEK_MS;
-    return (int32_t)ms;
-}
-
+// ---- time (split() and week_ms() are nav_device.hpp's) ---------------------------------------------------------------------------
 // nearbyint as an int32; what is no count of milliseconds near t0 (beyond 1e6, or not finite) is 0, as in week_ms
 __device__ __forceinline__ int32_t whole(double x) {
     const double n = nearbyint(x);

@@ -114,7 +114,7 @@ extern "C" void gpsacq_destroy(gpsacq_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->p.device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    void* bufs[] = {e->d_t1, e->d_t2, e->d_bq, e->d_fold, e->d_tn, e->d_rho, e->d_cos, e->d_sin, e->d_cos_t, e->d_sin_t, e->d_code, e->d_patch_blocks, e->d_bits, e->d_iq, e->d_iqbits, e->d_fsamp, e->d_pdump, e->d_sums, e->d_sats, e->d_gen, e->d_nav, e->d_track_chips, e->d_chans, e->d_track_n, e->d_prompt, e->d_records, e->d_nav_eph, e->d_nav_obs, e->d_nav_state, e->d_nav_fix, e->d_obs_chan, e->d_obs_pos, e->d_obs_rec, e->d_rate_chan, e->d_rate_acc, e->d_rate_obs, e->d_sat_rate, e->d_vel, e->d_atm_dop, e->d_atm_view, e->d_raim_rows, e->d_raim, e->d_smooth_chan, e->d_smooth_lock, e->d_smooth_q, e->d_smooth_w, e->d_smooth_info, e->d_quality_chan, e->d_quality_sums, e->d_quality_info, e->d_coarse_peaks, e->d_coarse_obs, e->d_coarse_work, e->d_coarse_prior, e->d_coarse_info, e->d_refine_bits, e->d_refine_tasks, e->d_refine_peaks, e->d_fine, e->d_persist, e->d_lutc,
+    void* bufs[] = {e->d_t1, e->d_t2, e->d_bq, e->d_fold, e->d_tn, e->d_rho, e->d_cos, e->d_sin, e->d_cos_t, e->d_sin_t, e->d_code, e->d_patch_blocks, e->d_bits, e->d_iq, e->d_iqbits, e->d_fsamp, e->d_pdump, e->d_sums, e->d_sats, e->d_gen, e->d_nav, e->d_track_chips, e->d_chans, e->d_track_n, e->d_prompt, e->d_records, e->d_nav_eph, e->d_nav_obs, e->d_nav_state, e->d_nav_fix, e->d_obs_chan, e->d_obs_pos, e->d_obs_rec, e->d_rate_chan, e->d_rate_acc, e->d_rate_obs, e->d_sat_rate, e->d_vel, e->d_atm_dop, e->d_atm_view, e->d_raim_rows, e->d_raim, e->d_smooth_chan, e->d_smooth_lock, e->d_smooth_q, e->d_smooth_w, e->d_smooth_info, e->d_quality_chan, e->d_quality_sums, e->d_quality_info, e->d_coarse_peaks, e->d_coarse_obs, e->d_coarse_work, e->d_coarse_prior, e->d_coarse_info, e->d_refine_bits, e->d_refine_tasks, e->d_refine_peaks, e->d_fine, e->d_dopfine, e->d_dop_tau, e->d_dop_rx_ms, e->d_dop_fix, e->d_dop_prior, e->d_persist, e->d_lutc,
                     e->d_dpp, e->d_parts, e->d_tasks, e->d_cells, e->d_peaks};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -142,6 +142,8 @@ extern "C" void gpsacq_destroy(gpsacq_engine* e) {
     for (auto& ev : e->coarse_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : e->refine_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : e->dop_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (e->copy_stream) (void)hipStreamSynchronize(e->copy_stream);
     for (auto& sl : e->pipe) {

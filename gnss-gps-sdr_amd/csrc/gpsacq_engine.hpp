@@ -187,6 +187,20 @@ struct gpsacq_engine {
     size_t fine_cap = 0;
     hipEvent_t refine_ev[4] = {};  // before and after k_refine, before and after k_coarse_obs_fine
     bool refine_timed = false, refine_obs_timed = false;
+    // cold snapshot fixes (gpsacq_fine_doppler*, gpsacq_rate_obs_fine*, gpsacq_doppler_fix_batch*, gpsacq_cold_fix_device); the
+    // host-buffer forms stage the capture, tasks and peaks in the d_refine_* buffers above and the observations in d_nav_obs / d_rate_obs
+    gpsacq_dopfine* d_dopfine = nullptr;  // host-buffer forms, and k_fine_dop's output where the caller of the chain wants no records
+    size_t dopfine_cap = 0;
+    double* d_dop_tau = nullptr;  // k_doppler_fix's light times between its passes: [n_fix][sats]
+    size_t dop_tau_cap = 0;
+    int32_t* d_dop_rx_ms = nullptr;  // host-buffer form
+    size_t dop_rx_ms_cap = 0;
+    gpsacq_doppler_fix* d_dop_fix = nullptr;  // host-buffer form
+    size_t dop_fix_cap = 0;
+    gpsacq_coarse_prior* d_dop_prior = nullptr;  // host-buffer form, and the chain's priors where the caller wants none
+    size_t dop_prior_cap = 0;
+    hipEvent_t dop_ev[6] = {};  // before and after k_fine_dop, k_rate_obs_fine, k_doppler_fix
+    bool dop_fine_timed = false, dop_obs_timed = false, dop_fix_timed = false;
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     int* d_persist = nullptr;
     size_t persist_cap = 0;

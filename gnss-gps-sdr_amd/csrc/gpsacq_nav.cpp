@@ -8,7 +8,9 @@
 // Between the velocity and the atmosphere: "Carrier-smoothed observables", gpsacq_smooth_observables* and
 // gpsacq_fix_smooth_track_device, which run smooth_kernels.hip after k_code_pos and k_carrier_acc.  Then "Coarse-time
 // fixes": gpsacq_coarse_obs*, gpsacq_coarse_fix_batch* and gpsacq_coarse_fix_peaks_device, which run coarse_kernels.hip.  Last of
-// all "Fine code phases": gpsacq_refine*, gpsacq_coarse_obs_fine* and gpsacq_coarse_fix_fine_device, which run refine_kernels.hip.
+// all "Fine code phases": gpsacq_refine*, gpsacq_coarse_obs_fine* and gpsacq_coarse_fix_fine_device, which run refine_kernels.hip, and
+// "Cold snapshot fixes": gpsacq_fine_doppler*, gpsacq_rate_obs_fine*, gpsacq_doppler_fix_batch* and gpsacq_cold_fix_device, which run
+// doppler_kernels.hip.
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -19,6 +21,7 @@
 #include "gpsacq_engine.hpp"
 #include "atm_launch.hpp"
 #include "coarse_launch.hpp"
+#include "doppler_launch.hpp"
 #include "nav_launch.hpp"
 #include "obs_launch.hpp"
 #include "raim_launch.hpp"
@@ -1295,15 +1298,22 @@ static int refine_params(const char* who, const gpsacq_refine_params* params, gp
     return GPSACQ_OK;
 }
 
-static int refine_check(const char* who, const gpsacq_engine* e, const void* bits, size_t n_bytes, size_t stride, const void* peaks, size_t n_tasks,
-                        const gpsacq_refine_params* params, const void* fine, gpsacq_refine_params* checked) {
-    if (!e || !bits || !peaks || !fine || n_bytes == 0 || n_tasks == 0 || n_tasks > 0x7fffffffu) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+// the capture, the peaks, the output and the engine of a kernel that goes back to the capture (k_refine, k_fine_dop)
+static int capture_check(const char* who, const gpsacq_engine* e, const void* bits, size_t n_bytes, size_t stride, const void* peaks, size_t n_tasks,
+                         const void* out) {
+    if (!e || !bits || !peaks || !out || n_bytes == 0 || n_tasks == 0 || n_tasks > 0x7fffffffu) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
     if (stride < 5000 || stride > ((size_t)1 << 31)) return fail(GPSACQ_ERR_ARG, "%s: stride %zu outside 5000 .. 2^31", who, stride);
     if (n_bytes > ((size_t)1 << 56)) return fail(GPSACQ_ERR_ARG, "%s: n_bytes %zu", who, n_bytes);
     if (e->nlags > 65535) return fail(GPSACQ_ERR_UNSUPPORTED, "%s: %d samples per millisecond (the packed counts hold 65535)", who, e->nlags);
     if (1.023e6 / e->p.fs + 1.0 / 1540.0 > REFINE_MAX_CHIPS_PER_SAMPLE)
         return fail(GPSACQ_ERR_UNSUPPORTED, "%s: fs = %g Hz is fewer than %.2f samples per chip (a word's chips leave the kernel's window)", who, e->p.fs,
                     1.0 / REFINE_MAX_CHIPS_PER_SAMPLE);
+    return GPSACQ_OK;
+}
+
+static int refine_check(const char* who, const gpsacq_engine* e, const void* bits, size_t n_bytes, size_t stride, const void* peaks, size_t n_tasks,
+                        const gpsacq_refine_params* params, const void* fine, gpsacq_refine_params* checked) {
+    if (int rc = capture_check(who, e, bits, n_bytes, stride, peaks, n_tasks, fine)) return rc;
     return refine_params(who, params, checked);
 }
 
@@ -1457,5 +1467,299 @@ extern "C" int gpsacq_refine_last_ms(const gpsacq_engine* e, float* refine_ms, f
     }
     if (refine_ms) *refine_ms = t[0];
     if (obs_ms) *obs_ms = t[1];
+    return GPSACQ_OK;
+}
+
+// ---- cold snapshot fixes: fine Doppler and a Doppler-only position solver (doppler_kernels.hip) ----------------------------------
+extern "C" int gpsacq_dopfine_default_params(gpsacq_dopfine_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_dopfine_default_params: null argument");
+    std::memset(p, 0, sizeof *p);
+    p->blocks = 16;
+    p->min_segments = 2;
+    p->snr_min = 25.0;  // the threshold of the search, as gpsacq_refine_default_params
+    p->coherence_min = 0.0;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_doppler_fix_default_params(gpsacq_doppler_fix_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_doppler_fix_default_params: null argument");
+    std::memset(p, 0, sizeof *p);
+    p->rms_max_mps = 3.0;  // three times the largest rms of 2048 measured blocks (0.72 m/s), rounded up: include/gpsacq.h
+    return GPSACQ_OK;
+}
+
+// the caller's parameters or the defaults into *out, checked against the bounds and the engine (OVERFLOW, and the LDS of k_fine_dop)
+static int dopfine_params(const char* who, const gpsacq_engine* e, const gpsacq_dopfine_params* params, gpsacq_dopfine_params* out) {
+    if (!params) {
+        if (int rc = gpsacq_dopfine_default_params(out)) return rc;
+    } else {
+        *out = *params;
+    }
+    if (out->blocks < 1 || out->blocks > 64) return fail(GPSACQ_ERR_ARG, "%s: blocks %d outside 1 .. 64", who, (int)out->blocks);
+    if (out->min_segments < 2) return fail(GPSACQ_ERR_ARG, "%s: min_segments %d (must be >= 2)", who, (int)out->min_segments);
+    if (!std::isfinite(out->snr_min)) return fail(GPSACQ_ERR_ARG, "%s: snr_min %g (must be finite)", who, out->snr_min);
+    if (!std::isfinite(out->coherence_min) || out->coherence_min < 0.0)
+        return fail(GPSACQ_ERR_ARG, "%s: coherence_min %g (must be finite and >= 0)", who, out->coherence_min);
+    const unsigned __int128 spm = (unsigned __int128)e->nlags;  // 1137 .. 65535 after capture_check
+    if ((unsigned __int128)out->blocks * 160000u * spm * spm * spm >= (unsigned __int128)1 << 63)
+        return fail(GPSACQ_ERR_UNSUPPORTED, "%s: %d blocks of %d samples per millisecond (the lag sums could leave 63 bits)", who, (int)out->blocks, e->nlags);
+    if ((uint64_t)out->blocks * 40000u / (uint64_t)e->nlags > (uint64_t)DOP_MAX_SEGMENTS)
+        return fail(GPSACQ_ERR_UNSUPPORTED, "%s: a window of more than %d segments", who, DOP_MAX_SEGMENTS);
+    return GPSACQ_OK;
+}
+
+static int doppler_fix_params(const char* who, const gpsacq_doppler_fix_params* params, gpsacq_doppler_fix_params* out) {
+    if (!params) return gpsacq_doppler_fix_default_params(out);
+    *out = *params;
+    if (!std::isfinite(out->rms_max_mps) || !(out->rms_max_mps > 0.0))
+        return fail(GPSACQ_ERR_ARG, "%s: rms_max_mps %g (must be finite and > 0)", who, out->rms_max_mps);
+    return GPSACQ_OK;
+}
+
+static int doppler_fix_check(const char* who, const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* obs, const void* rate_obs,
+                             const void* rx_ms, size_t n_fix, int sats_per_fix, const gpsacq_doppler_fix_params* params, const void* fix,
+                             gpsacq_doppler_fix_params* checked) {
+    if (int rc = nav_check(who, e, eph, n_eph, obs, n_fix, fix)) return rc;
+    if (!rate_obs || !rx_ms) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (sats_per_fix < 1 || sats_per_fix > GPSACQ_FIX_MAX_SATS)
+        return fail(GPSACQ_ERR_ARG, "%s: sats_per_fix %d outside 1 .. %d", who, sats_per_fix, GPSACQ_FIX_MAX_SATS);
+    return doppler_fix_params(who, params, checked);
+}
+
+static int doppler_events(gpsacq_engine* e) {
+    for (auto& ev : e->dop_ev)
+        if (!ev) HIPCHK(hipEventCreate(&ev));
+    return GPSACQ_OK;
+}
+
+// k_fine_dop on the engine's stream between dop_ev[0] and dop_ev[1]; every argument has been checked
+static int fine_dop_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
+                            size_t n_tasks, const gpsacq_dopfine_params& dp, void* d_dopfine) {
+    if (int rc = ensure_track_chips(e)) return rc;
+    if (int rc = doppler_events(e)) return rc;
+    const uint32_t lead = (uint32_t)((uintptr_t)d_bits & 3u);  // the kernel loads whole words from the aligned address below
+    const bool ref_grid = e->sub == 1 && e->dstride == 1;       // as gpsacq_handoff_engine
+    FineDopArgs a{};
+    a.words = (const uint32_t*)((uintptr_t)d_bits - lead);
+    a.n_bytes = n_bytes + lead;
+    a.lead = lead;
+    a.stride = stride;
+    a.tasks = (const gpsacq_task*)d_tasks;
+    a.peaks = (const gpsacq_peak*)d_peaks;
+    a.n_tasks = n_tasks;
+    a.chips = e->d_track_chips;
+    a.fc = e->p.fc, a.fs = e->p.fs;
+    a.step_hz = ref_grid ? 0.0 : e->p.fs / N_FFT * e->dstride / e->sub;
+    a.spm = e->nlags;
+    a.p = dp;
+    a.out = (gpsacq_dopfine*)d_dopfine;
+    e->dop_fine_timed = false;
+    HIPCHK(hipEventRecord(e->dop_ev[0], e->stream));
+    launch_fine_dop(a, e->stream);
+    HIPCHK(hipEventRecord(e->dop_ev[1], e->stream));
+    HIPCHK(hipGetLastError());
+    e->dop_fine_timed = true;
+    return GPSACQ_OK;
+}
+
+// k_rate_obs_fine between dop_ev[2] and dop_ev[3]; every argument has been checked
+static int rate_obs_fine_enqueue(gpsacq_engine* e, const void* d_peaks, const void* d_dopfine, size_t n_fix, int n_chans, double snr_min,
+                                 void* d_rate_obs) {
+    if (int rc = doppler_events(e)) return rc;
+    e->dop_obs_timed = false;
+    HIPCHK(hipEventRecord(e->dop_ev[2], e->stream));
+    launch_rate_obs_fine(RateObsFineArgs{(const gpsacq_peak*)d_peaks, (const gpsacq_dopfine*)d_dopfine, n_fix * (size_t)n_chans, snr_min,
+                                         (gpsacq_rate_obs*)d_rate_obs},
+                         e->stream);
+    HIPCHK(hipEventRecord(e->dop_ev[3], e->stream));
+    HIPCHK(hipGetLastError());
+    e->dop_obs_timed = true;
+    return GPSACQ_OK;
+}
+
+// the ephemerides up, then k_doppler_fix between dop_ev[4] and dop_ev[5]; every argument has been checked
+static int doppler_fix_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_rate_obs, const void* d_rx_ms,
+                               size_t n_fix, int sats_per_fix, const gpsacq_doppler_fix_params& fp, void* d_fix, void* d_prior) {
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    if (int rc = grow(e->d_dop_tau, e->dop_tau_cap, n_fix * (size_t)sats_per_fix, e->stream)) return rc;
+    if (int rc = doppler_events(e)) return rc;
+    e->dop_fix_timed = false;
+    HIPCHK(hipEventRecord(e->dop_ev[4], e->stream));
+    launch_doppler_fix(DopplerFixArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, (const gpsacq_rate_obs*)d_rate_obs, (const int32_t*)d_rx_ms, n_fix,
+                                      sats_per_fix, fp, e->d_dop_tau, (gpsacq_doppler_fix*)d_fix, (gpsacq_coarse_prior*)d_prior},
+                       e->stream);
+    HIPCHK(hipEventRecord(e->dop_ev[5], e->stream));
+    HIPCHK(hipGetLastError());
+    e->dop_fix_timed = true;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fine_doppler_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
+                                          size_t n_tasks, const gpsacq_dopfine_params* params, void* d_dopfine, int sync) {
+    gpsacq_dopfine_params dp;
+    if (int rc = capture_check("gpsacq_fine_doppler", e, d_bits, n_bytes, stride, d_peaks, n_tasks, d_dopfine)) return rc;
+    if (int rc = dopfine_params("gpsacq_fine_doppler", e, params, &dp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = fine_dop_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, dp, d_dopfine)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fine_doppler(gpsacq_engine* e, const uint8_t* bits, size_t n_bytes, size_t stride, const gpsacq_task* tasks,
+                                   const gpsacq_peak* peaks, size_t n_tasks, const gpsacq_dopfine_params* params, gpsacq_dopfine* dopfine_out) {
+    gpsacq_dopfine_params dp;
+    if (int rc = capture_check("gpsacq_fine_doppler", e, bits, n_bytes, stride, peaks, n_tasks, dopfine_out)) return rc;
+    if (int rc = dopfine_params("gpsacq_fine_doppler", e, params, &dp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_refine_bits, e->refine_bits_cap, n_bytes, e->stream)) return rc;
+    if (int rc = grow(e->d_refine_peaks, e->refine_peaks_cap, n_tasks, e->stream)) return rc;
+    if (int rc = grow(e->d_dopfine, e->dopfine_cap, n_tasks, e->stream)) return rc;
+    if (tasks) {
+        if (int rc = grow(e->d_refine_tasks, e->refine_tasks_cap, n_tasks, e->stream)) return rc;
+        HIPCHK(hipMemcpyAsync(e->d_refine_tasks, tasks, n_tasks * sizeof(gpsacq_task), hipMemcpyHostToDevice, e->stream));
+    }
+    HIPCHK(hipMemcpyAsync(e->d_refine_bits, bits, n_bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_refine_peaks, peaks, n_tasks * sizeof(gpsacq_peak), hipMemcpyHostToDevice, e->stream));
+    if (int rc = fine_dop_enqueue(e, e->d_refine_bits, n_bytes, stride, tasks ? e->d_refine_tasks : nullptr, e->d_refine_peaks, n_tasks, dp, e->d_dopfine))
+        return rc;
+    HIPCHK(hipMemcpyAsync(dopfine_out, e->d_dopfine, n_tasks * sizeof(gpsacq_dopfine), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_rate_obs_fine_device(gpsacq_engine* e, const void* d_peaks, const void* d_dopfine, size_t n_fix, int n_chans, double snr_min,
+                                           void* d_rate_obs, int sync) {
+    if (int rc = coarse_obs_check("gpsacq_rate_obs_fine", e, d_peaks, n_fix, n_chans, snr_min, d_rate_obs)) return rc;
+    if (!d_dopfine) return fail(GPSACQ_ERR_ARG, "gpsacq_rate_obs_fine: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = rate_obs_fine_enqueue(e, d_peaks, d_dopfine, n_fix, n_chans, snr_min, d_rate_obs)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_rate_obs_fine(gpsacq_engine* e, const gpsacq_peak* peaks, const gpsacq_dopfine* dopfine, size_t n_fix, int n_chans,
+                                    double snr_min, gpsacq_rate_obs* rate_obs) {
+    if (int rc = coarse_obs_check("gpsacq_rate_obs_fine", e, peaks, n_fix, n_chans, snr_min, rate_obs)) return rc;
+    if (!dopfine) return fail(GPSACQ_ERR_ARG, "gpsacq_rate_obs_fine: bad argument");
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_obs = n_fix * (size_t)n_chans;
+    if (int rc = grow(e->d_refine_peaks, e->refine_peaks_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_dopfine, e->dopfine_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_obs, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_refine_peaks, peaks, n_obs * sizeof(gpsacq_peak), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_dopfine, dopfine, n_obs * sizeof(gpsacq_dopfine), hipMemcpyHostToDevice, e->stream));
+    if (int rc = rate_obs_fine_enqueue(e, e->d_refine_peaks, e->d_dopfine, n_fix, n_chans, snr_min, e->d_rate_obs)) return rc;
+    HIPCHK(hipMemcpyAsync(rate_obs, e->d_rate_obs, n_obs * sizeof(gpsacq_rate_obs), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_doppler_fix_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_rate_obs,
+                                               const void* d_rx_ms, size_t n_fix, int sats_per_fix, const gpsacq_doppler_fix_params* params,
+                                               void* d_doppler_fix, void* d_prior, int sync) {
+    gpsacq_doppler_fix_params fp;
+    if (int rc = doppler_fix_check("gpsacq_doppler_fix_batch", e, eph, n_eph, d_obs, d_rate_obs, d_rx_ms, n_fix, sats_per_fix, params, d_doppler_fix, &fp))
+        return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = doppler_fix_enqueue(e, eph, n_eph, d_obs, d_rate_obs, d_rx_ms, n_fix, sats_per_fix, fp, d_doppler_fix, d_prior)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_doppler_fix_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs, const gpsacq_rate_obs* rate_obs,
+                                        const int32_t* rx_ms, size_t n_fix, int sats_per_fix, const gpsacq_doppler_fix_params* params,
+                                        gpsacq_doppler_fix* fix_out, gpsacq_coarse_prior* prior_out) {
+    gpsacq_doppler_fix_params fp;
+    if (int rc = doppler_fix_check("gpsacq_doppler_fix_batch", e, eph, n_eph, obs, rate_obs, rx_ms, n_fix, sats_per_fix, params, fix_out, &fp)) return rc;
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    for (size_t k = 0; k < n_obs; ++k)
+        if (!(rate_obs[k].weight >= 0.0) || !std::isfinite(rate_obs[k].weight))
+            return fail(GPSACQ_ERR_ARG, "gpsacq_doppler_fix_batch: rate observation %zu has weight %g (must be finite and >= 0)", k, rate_obs[k].weight);
+    for (size_t k = 0; k < n_fix; ++k)
+        if (rx_ms[k] < 0 || rx_ms[k] >= 604800000)
+            return fail(GPSACQ_ERR_ARG, "gpsacq_doppler_fix_batch: rx_ms[%zu] = %d (0 <= rx_ms < 604800000)", k, (int)rx_ms[k]);
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = grow(e->d_dop_rx_ms, e->dop_rx_ms_cap, n_fix, e->stream)) return rc;
+    if (int rc = grow(e->d_dop_fix, e->dop_fix_cap, n_fix, e->stream)) return rc;
+    if (int rc = grow(e->d_dop_prior, e->dop_prior_cap, n_fix, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_rate_obs, rate_obs, n_obs * sizeof(gpsacq_rate_obs), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_dop_rx_ms, rx_ms, n_fix * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    if (int rc = doppler_fix_enqueue(e, eph, n_eph, e->d_nav_obs, e->d_rate_obs, e->d_dop_rx_ms, n_fix, sats_per_fix, fp, e->d_dop_fix,
+                                     prior_out ? e->d_dop_prior : nullptr))
+        return rc;
+    HIPCHK(hipMemcpyAsync(fix_out, e->d_dop_fix, n_fix * sizeof(gpsacq_doppler_fix), hipMemcpyDeviceToHost, e->stream));
+    if (prior_out) HIPCHK(hipMemcpyAsync(prior_out, e->d_dop_prior, n_fix * sizeof(gpsacq_coarse_prior), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_cold_fix_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_bits, size_t n_bytes, size_t stride,
+                                      const void* d_tasks, const void* d_peaks, const void* d_rx_ms, size_t n_fix, int n_chans,
+                                      const gpsacq_dopfine_params* dopfine_par, const gpsacq_doppler_fix_params* doppler_par,
+                                      const gpsacq_refine_params* refine_par, const gpsacq_coarse_params* coarse_par, void* d_dopfine, void* d_rate_obs,
+                                      void* d_doppler_fix, void* d_prior, void* d_fine, void* d_obs, void* d_fix, void* d_info, void* d_obs_out,
+                                      int sync) {
+    const char* who = "gpsacq_cold_fix";
+    if (int rc = coarse_obs_check(who, e, d_peaks, n_fix, n_chans, 0.0, d_fix)) return rc;
+    if (!eph || n_eph <= 0 || !d_rx_ms || !d_info || !d_doppler_fix) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (d_obs && d_obs_out == d_obs) return fail(GPSACQ_ERR_ARG, "%s: obs_out must not be obs", who);
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    gpsacq_dopfine_params dp;
+    gpsacq_doppler_fix_params fp;
+    gpsacq_refine_params rp;
+    gpsacq_coarse_params cp;
+    if (int rc = refine_check(who, e, d_bits, n_bytes, stride, d_peaks, n_tasks, refine_par, d_fix, &rp)) return rc;
+    if (int rc = dopfine_params(who, e, dopfine_par, &dp)) return rc;
+    if (int rc = doppler_fix_params(who, doppler_par, &fp)) return rc;
+    if (int rc = coarse_params(who, coarse_par, &cp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (!d_dopfine) {
+        if (int rc = grow(e->d_dopfine, e->dopfine_cap, n_tasks, e->stream)) return rc;
+        d_dopfine = e->d_dopfine;
+    }
+    if (!d_rate_obs) {
+        if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_tasks, e->stream)) return rc;
+        d_rate_obs = e->d_rate_obs;
+    }
+    if (!d_prior) {
+        if (int rc = grow(e->d_dop_prior, e->dop_prior_cap, n_fix, e->stream)) return rc;
+        d_prior = e->d_dop_prior;
+    }
+    if (!d_fine) {
+        if (int rc = grow(e->d_fine, e->fine_cap, n_tasks, e->stream)) return rc;
+        d_fine = e->d_fine;
+    }
+    if (!d_obs) {
+        if (int rc = grow(e->d_coarse_obs, e->coarse_obs_cap, n_tasks, e->stream)) return rc;
+        d_obs = e->d_coarse_obs;
+    }
+    if (int rc = fine_dop_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, dp, d_dopfine)) return rc;
+    if (int rc = coarse_obs_enqueue(e, d_peaks, n_fix, n_chans, dp.snr_min, d_obs)) return rc;
+    if (int rc = rate_obs_fine_enqueue(e, d_peaks, d_dopfine, n_fix, n_chans, dp.snr_min, d_rate_obs)) return rc;
+    if (int rc = doppler_fix_enqueue(e, eph, n_eph, d_obs, d_rate_obs, d_rx_ms, n_fix, n_chans, fp, d_doppler_fix, d_prior)) return rc;
+    if (int rc = refine_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, rp, d_fine)) return rc;
+    if (int rc = coarse_obs_fine_enqueue(e, d_peaks, d_fine, n_fix, n_chans, rp.snr_min, d_obs)) return rc;
+    if (int rc = coarse_fix_enqueue(e, eph, n_eph, d_obs, d_prior, n_fix, n_chans, cp, d_fix, d_info, d_obs_out)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_doppler_last_ms(const gpsacq_engine* e, float* fine_dop_ms, float* rate_obs_ms, float* doppler_fix_ms) {
+    if (!e || (!e->dop_fine_timed && !e->dop_obs_timed && !e->dop_fix_timed))
+        return fail(GPSACQ_ERR_ARG, "gpsacq_doppler_last_ms: no gpsacq_fine_doppler, gpsacq_rate_obs_fine or gpsacq_doppler_fix call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    const bool timed[3] = {e->dop_fine_timed, e->dop_obs_timed, e->dop_fix_timed};
+    float t[3] = {0.f, 0.f, 0.f};
+    for (int k = 0; k < 3; ++k)
+        if (timed[k]) {
+            HIPCHK(hipEventSynchronize(e->dop_ev[2 * k + 1]));
+            HIPCHK(hipEventElapsedTime(&t[k], e->dop_ev[2 * k], e->dop_ev[2 * k + 1]));
+        }
+    if (fine_dop_ms) *fine_dop_ms = t[0];
+    if (rate_obs_ms) *rate_obs_ms = t[1];
+    if (doppler_fix_ms) *doppler_fix_ms = t[2];
     return GPSACQ_OK;
 }

@@ -31,6 +31,23 @@ __device__ __forceinline__ int32_t fold_ms(int32_t d) {
     return d;
 }
 
+// t seconds into whole milliseconds and a fraction in [0, 1e-3): fill_fix's rule (k_coarse_fix, k_doppler_fix)
+__device__ __forceinline__ void split(double t, double& k, double& frac) {
+    k = floor(t * 1e3);
+    frac = t - k * 1e-3;
+    if (frac < 0.0) k -= 1.0, frac += 1e-3;
+    if (frac >= 1e-3) k += 1.0, frac -= 1e-3;
+}
+
+// millisecond of week base + k.  A k that is no count of milliseconds (a diverged or non-finite time) is taken as 0: the row
+// fails its own tests, the conversion must not overflow on the way there
+__device__ __forceinline__ int32_t week_ms(int32_t base, double k) {
+    if (!(fabs(k) < 1e12)) k = 0.0;
+    int64_t ms = ((int64_t)base + (int64_t)k) % WEEK_MS;
+    if (ms < 0) ms += WEEK_MS;
+    return (int32_t)ms;
+}
+
 __device__ __forceinline__ bool usable(const gpsacq_obs& o, const NavEph* eph, int n_eph) {
     if (!o.valid || o.eph < 0 || o.eph >= n_eph) return false;
     if (!(o.weight >= 0.0) || !isfinite(o.weight) || !isfinite(o.tx_frac)) return false;

@@ -17,37 +17,22 @@
 // The six counts of ones pack in pairs (a segment has spm <= 65535 samples) and are summed over the wave with xor shuffles; every
 // lane then adds the three squares I^2 + Q^2 into 64-bit partials, the four waves' partials meet in LDS and thread 0 writes the
 // record.  Integer sums, no atomics: the record does not depend on the order of anything.  Two barriers; every loop is bounded by
-// kernel arguments.
+// kernel arguments.  The word loop's pieces (word_at, mod_full, the chips in LDS, the per-word window and masks) live in
+// capture_words.hpp, which k_fine_dop of doppler_kernels.hip shares.
 // k_coarse_obs_fine: one lane per (fix, channel), k_coarse_obs of coarse_kernels.hip with the code phase of a usable record.
 // Built with -ffp-contract=off (Makefile): the NCO words must be gpsacq_handoff_engine's to the bit, and `lo_shift * step + fc`
 // or `lo_dop / L1 * CPS + CPS` fused into an FMA round differently from the host's two operations.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "capture_words.hpp"
 #include "nav_launch.hpp"
 #include "refine_launch.hpp"
 
 namespace acq {
 
 namespace {
-constexpr uint64_t FULL = 1023ull << 32;  // one code period, chips * 2^32
 constexpr int FINE_UNUSABLE = GPSACQ_FINE_NO_HIT | GPSACQ_FINE_NO_POWER | GPSACQ_FINE_FEW;
-
-// 32 samples from byte 4 wi of the aligned capture; the capture's last bytes one at a time, nothing at or beyond n_bytes
-__device__ __forceinline__ uint32_t word_at(const uint32_t* words, size_t n_bytes, uint64_t wi) {
-    const size_t off = (size_t)wi * 4;
-    if (off + 4 <= n_bytes) return words[wi];
-    const uint8_t* b = reinterpret_cast<const uint8_t*>(words);
-    uint32_t v = 0;
-    for (int k = 0; k < 4; ++k)
-        if (off + k < n_bytes) v |= (uint32_t)b[off + k] << (8 * k);
-    return v;
-}
-
-// x mod 1023 * 2^32 for x < 2^64: the low word stays, the high word is reduced mod 1023
-__device__ __forceinline__ uint64_t mod_full(uint64_t x) { return (uint64_t)((uint32_t)(x >> 32) % 1023u) << 32 | (uint32_t)x; }
-
-constexpr int CHIP_WORDS = 34;  // the chip sequence twice over, bits 0 .. 1087: a window starts at bit b <= 1022 and ends at b + 31
 }  // namespace
 
 __global__ __launch_bounds__(64 * REFINE_WAVES) void k_refine(RefineArgs a) {
@@ -56,44 +41,17 @@ __global__ __launch_bounds__(64 * REFINE_WAVES) void k_refine(RefineArgs a) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t t = blockIdx.x;
     const gpsacq_peak pk = a.peaks[t];
-    int32_t block = (int32_t)t, prn = (int32_t)(t % 32);
-    if (a.tasks) block = a.tasks[t].block, prn = a.tasks[t].prn;
 
-    // 1. the NCO words of gpsacq_handoff_engine, 2. what is no hit.  Every lane of the workgroup decides the same.
-    const double L1 = 1575.42e6, CPS = 1.023e6;
-    const double lo_dop = a.step_hz > 0 ? pk.lo_shift * a.step_hz : pk.lo_shift * a.fs / 40000.0;
-    const double ca_dop = lo_dop / L1 * CPS;
-    const double lo_f = a.fc + lo_dop, ca_f = CPS + ca_dop;
-    bool hit = (double)pk.snr >= a.p.snr_min && pk.ca_shift >= 0 && pk.ca_shift < a.spm && block >= 0 && prn >= 0 && prn < GPSACQ_NUM_SATS &&
-               lo_f >= 0 && lo_f < a.fs && ca_f >= 0 && ca_f < a.fs;
-    const uint64_t total = (uint64_t)a.n_bytes * 8;  // samples from the aligned base, the `lead` bytes in front included
-    uint64_t o = 0;
-    uint32_t lo_rate = 0, ca_rate = 0;
-    if (hit) {
-        o = 8ull * a.lead + 8ull * (uint64_t)block * a.stride;  // stride <= 2^31: no overflow
-        lo_rate = (uint32_t)(lo_f / a.fs * 4294967296.0);
-        ca_rate = (uint32_t)(ca_f / a.fs * 4294967296.0);
-        hit = o < total && ca_rate != 0;
-    }
-    if (!hit) {
+    // 1. the NCO words of gpsacq_handoff_engine, 2. what is no hit, 3. window and segments
+    const Window win = window_of(pk, a.tasks, t, a.fc, a.fs, a.step_hz, a.spm, a.p.snr_min, a.p.blocks, a.n_bytes, a.lead, a.stride);
+    const uint64_t o = win.o, spm = (uint64_t)a.spm, fit = win.fit, segments = win.segments;
+    const uint32_t lo_rate = win.lo_rate, ca_rate = win.ca_rate;
+    if (!win.hit) {
         if (threadIdx.x == 0) a.out[t] = gpsacq_fine{GPSACQ_FINE_NO_HIT, 0, 0, 0, 0, 0, 0, 0.0, 0.0};
         return;
     }
-    if (threadIdx.x < CHIP_WORDS) {  // bit i of word k: chip (32 k + i) mod 1023
-        const uint32_t* c = a.chips + prn * 32;
-        uint32_t w = 0;
-        for (uint32_t i = 0; i < 32; ++i) {
-            const uint32_t q = (32u * threadIdx.x + i) % 1023u;
-            w |= ((c[q >> 5] >> (q & 31)) & 1u) << i;
-        }
-        s_chips[threadIdx.x] = w;
-    }
+    chips_to_lds(a.chips, win.prn, s_chips);
     __syncthreads();
-
-    // 3. window and segments
-    const uint64_t spm = (uint64_t)a.spm;
-    const uint64_t fit = (uint64_t)a.p.blocks * 40000ull / spm, have = (total - o) / spm;
-    const uint64_t segments = have < fit ? have : fit;
 
     // 4. sums
     const uint32_t D = (uint32_t)(a.p.half_spacing_chips * 4294967296.0);
@@ -104,34 +62,10 @@ __global__ __launch_bounds__(64 * REFINE_WAVES) void k_refine(RefineArgs a) {
         const uint64_t w1 = (a1 - 1) >> 5;
         uint32_t ones[6] = {0, 0, 0, 0, 0, 0};  // IE QE IP QP IL QL: samples whose product is -1
         for (uint64_t wi = (a0 >> 5) + lane; wi <= w1; wi += 64) {
-            const uint32_t x = word_at(a.words, a.n_bytes, wi);
-            const uint64_t ws = wi << 5;
-            const uint32_t b_lo = ws < a0 ? (uint32_t)(a0 - ws) : 0u;        // 0 .. 31
-            const uint32_t b_hi = ws + 32 > a1 ? (uint32_t)(a1 - ws) : 32u;  // 1 .. 32
-            const uint32_t valid = (b_hi == 32 ? ~0u : (1u << b_hi) - 1u) & ~((1u << b_lo) - 1u);
-            // the prompt position of the word's first sample of the segment (window sample j >= 0, j ca_rate < 2^54), carried back
-            // to bit 0 of the word modulo the period: bits below b_lo are masked out, the ones from b_lo on get their own position
-            uint64_t P = mod_full(P0 + (ws + b_lo - o) * ca_rate);
-            const uint64_t back = (uint64_t)b_lo * ca_rate;  // < 2^37 < FULL
-            P = P >= back ? P - back : P + FULL - back;
-            uint32_t ph = (uint32_t)(ws - o) * lo_rate;  // modulo 2^32 also where the word starts before the window
-            // the window of 32 chips from late's chip at bit 0, and the prompt position relative to it: rel - D >= 0 and
-            // rel + D + 31 ca_rate < 32 * 2^32, so every chip index below is the high word of a sum that does not wrap
-            const uint64_t L0 = P >= D ? P - D : P + FULL - D;
-            const uint32_t cb = (uint32_t)(L0 >> 32);  // 0 .. 1022
-            const uint32_t win = __funnelshift_r(s_chips[cb >> 5], s_chips[(cb >> 5) + 1], cb & 31);
-            uint64_t rel = (uint64_t)(uint32_t)L0 + D;
-            uint32_t cm = 0, sp = 0, em = 0, pm = 0, lm = 0;  // sp: the samples where -sin is POSITIVE (bit 31 of the phase)
-#pragma unroll
-            for (int b = 0; b < 32; ++b) {
-                cm |= ((ph + 0x40000000u) >> 31) << b;  // bit31 ^ bit30
-                sp |= (ph >> 31) << b;
-                em |= ((win >> (uint32_t)((rel + D) >> 32)) & 1u) << b;
-                pm |= ((win >> (uint32_t)(rel >> 32)) & 1u) << b;
-                lm |= ((win >> (uint32_t)((rel - D) >> 32)) & 1u) << b;
-                ph += lo_rate;
-                rel += ca_rate;
-            }
+            const WordPos w = word_pos(a.words, a.n_bytes, wi, a0, a1, o, P0, D, lo_rate, ca_rate, s_chips);
+            const uint32_t x = w.x, valid = w.valid;
+            uint32_t cm, sp, em, pm, lm;
+            word_masks<true>(w, D, lo_rate, ca_rate, cm, sp, em, pm, lm);
             const uint32_t sm = ~sp;
             ones[0] += __popc((x ^ em ^ cm) & valid);
             ones[1] += __popc((x ^ em ^ sm) & valid);

@@ -116,6 +116,15 @@ FINE_NO_HIT, FINE_SHORT, FINE_NO_POWER, FINE_FEW = 1, 2, 4, 8
 REFINE_PARAMS_DTYPE = np.dtype([("blocks", "<i4"), ("min_segments", "<i4"), ("half_spacing_chips", "<f8"), ("snr_min", "<f8")])
 FINE_DTYPE = np.dtype([("flags", "<i4"), ("segments", "<i4"), ("lo_rate", "<u4"), ("ca_rate", "<u4"), ("early", "<u8"), ("prompt", "<u8"),
                        ("late", "<u8"), ("offset_chips", "<f8"), ("tx_frac", "<f8")])
+# cold snapshot fixes (include/gpsacq.h, "Cold snapshot fixes: fine Doppler and a Doppler-only position solver")
+DOPFINE_NO_HIT, DOPFINE_SHORT, DOPFINE_NO_POWER, DOPFINE_FEW, DOPFINE_WEAK = 1, 2, 4, 8, 16
+DOPPLER_INCONSISTENT = 1
+DOPFINE_PARAMS_DTYPE = np.dtype([("blocks", "<i4"), ("min_segments", "<i4"), ("snr_min", "<f8"), ("coherence_min", "<f8")])
+DOPFINE_DTYPE = np.dtype([("flags", "<i4"), ("segments", "<i4"), ("lo_rate", "<u4"), ("ca_rate", "<u4"), ("re", "<i8"), ("im", "<i8"),
+                          ("mag", "<u8"), ("power", "<u8"), ("coherence", "<f8"), ("df_hz", "<f8"), ("doppler_hz", "<f8")])
+DOPPLER_FIX_PARAMS_DTYPE = np.dtype([("rms_max_mps", "<f8"), ("reserved", "<f8")])
+DOPPLER_FIX_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("iterations", "<i4"), ("flags", "<i4"), ("x", "<f8"), ("y", "<f8"),
+                              ("z", "<f8"), ("lat", "<f8"), ("lon", "<f8"), ("alt", "<f8"), ("drift", "<f8"), ("rms", "<f8"), ("pdop", "<f8")])
 
 
 # carrier-smoothed observables (include/gpsacq.h "Carrier-smoothed observables")
@@ -169,7 +178,10 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_coarse_default_params", "gpsacq_coarse_fix_batch", "gpsacq_coarse_fix_batch_device", "gpsacq_coarse_obs",
            "gpsacq_coarse_obs_device", "gpsacq_coarse_fix_peaks_device", "gpsacq_coarse_last_ms",
            "gpsacq_refine_default_params", "gpsacq_refine", "gpsacq_refine_device", "gpsacq_coarse_obs_fine", "gpsacq_coarse_obs_fine_device",
-           "gpsacq_coarse_fix_fine_device", "gpsacq_refine_last_ms"]
+           "gpsacq_coarse_fix_fine_device", "gpsacq_refine_last_ms",
+           "gpsacq_dopfine_default_params", "gpsacq_doppler_fix_default_params", "gpsacq_fine_doppler", "gpsacq_fine_doppler_device",
+           "gpsacq_rate_obs_fine", "gpsacq_rate_obs_fine_device", "gpsacq_doppler_fix_batch", "gpsacq_doppler_fix_batch_device",
+           "gpsacq_cold_fix_device", "gpsacq_doppler_last_ms"]
 
 _lib = None
 
@@ -458,6 +470,26 @@ def load_library(path=None):
     lib.gpsacq_coarse_fix_fine_device.restype = ctypes.c_int
     lib.gpsacq_refine_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
     lib.gpsacq_refine_last_ms.restype = ctypes.c_int
+    lib.gpsacq_dopfine_default_params.argtypes = [vp]
+    lib.gpsacq_dopfine_default_params.restype = ctypes.c_int
+    lib.gpsacq_doppler_fix_default_params.argtypes = [vp]
+    lib.gpsacq_doppler_fix_default_params.restype = ctypes.c_int
+    lib.gpsacq_fine_doppler.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp]
+    lib.gpsacq_fine_doppler.restype = ctypes.c_int
+    lib.gpsacq_fine_doppler_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp, ctypes.c_int]
+    lib.gpsacq_fine_doppler_device.restype = ctypes.c_int
+    lib.gpsacq_rate_obs_fine.argtypes = [vp, vp, vp, sz, ctypes.c_int, ctypes.c_double, vp]
+    lib.gpsacq_rate_obs_fine.restype = ctypes.c_int
+    lib.gpsacq_rate_obs_fine_device.argtypes = [vp, vp, vp, sz, ctypes.c_int, ctypes.c_double, vp, ctypes.c_int]
+    lib.gpsacq_rate_obs_fine_device.restype = ctypes.c_int
+    lib.gpsacq_doppler_fix_batch.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, sz, ctypes.c_int, vp, vp, vp]
+    lib.gpsacq_doppler_fix_batch.restype = ctypes.c_int
+    lib.gpsacq_doppler_fix_batch_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, sz, ctypes.c_int, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_doppler_fix_batch_device.restype = ctypes.c_int
+    lib.gpsacq_cold_fix_device.argtypes = [vp, vp, ctypes.c_int, vp, sz, sz, vp, vp, vp, sz, ctypes.c_int] + [vp] * 13 + [ctypes.c_int]
+    lib.gpsacq_cold_fix_device.restype = ctypes.c_int
+    lib.gpsacq_doppler_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
+    lib.gpsacq_doppler_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -597,6 +629,42 @@ def refine_params(**overrides):
         raise ValueError("refine_params: half_spacing_chips %g outside [1/64, 0.5]" % r["half_spacing_chips"])
     if not np.isfinite(r["snr_min"]):
         raise ValueError("refine_params: snr_min %g (must be finite)" % r["snr_min"])
+    return out
+
+
+def dopfine_params(**overrides):
+    """gpsacq_dopfine_default_params: a DOPFINE_PARAMS_DTYPE record of shape (1,) -- a window of 16 blocks, min_segments 2, snr_min
+    the search threshold, coherence_min 0 (no gate) -- with the named fields replaced.  Values outside the bounds of
+    include/gpsacq.h ("Cold snapshot fixes", 1.) raise ValueError here; the entry points check them again."""
+    lib = load_library()
+    out = np.zeros(1, dtype=DOPFINE_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_dopfine_default_params(out.ctypes.data_as(ctypes.c_void_p)))
+    for k, v in overrides.items():
+        if k not in DOPFINE_PARAMS_DTYPE.names:
+            raise TypeError("dopfine_params: no field %r" % k)
+        if k in ("blocks", "min_segments") and int(v) != v:
+            raise ValueError("dopfine_params: %s = %r is no whole number" % (k, v))
+        out[k] = v
+    r = out[0]
+    if not 1 <= r["blocks"] <= 64:
+        raise ValueError("dopfine_params: blocks %d outside 1 .. 64" % r["blocks"])
+    if r["min_segments"] < 2:
+        raise ValueError("dopfine_params: min_segments %d (must be >= 2)" % r["min_segments"])
+    if not np.isfinite(r["snr_min"]):
+        raise ValueError("dopfine_params: snr_min %g (must be finite)" % r["snr_min"])
+    if not (np.isfinite(r["coherence_min"]) and r["coherence_min"] >= 0):
+        raise ValueError("dopfine_params: coherence_min %g (must be finite and >= 0)" % r["coherence_min"])
+    return out
+
+
+def doppler_fix_params(rms_max_mps=None):
+    """gpsacq_doppler_fix_default_params: a DOPPLER_FIX_PARAMS_DTYPE record of shape (1,) -- rms_max_mps 3.0 m/s -- with rms_max_mps
+    replaced where given.  The entry points that take it check it."""
+    lib = load_library()
+    out = np.zeros(1, dtype=DOPPLER_FIX_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_doppler_fix_default_params(out.ctypes.data_as(ctypes.c_void_p)))
+    if rms_max_mps is not None:
+        out["rms_max_mps"] = float(rms_max_mps)
     return out
 
 
@@ -1215,6 +1283,110 @@ class Engine:
         a, b = ctypes.c_float(), ctypes.c_float()
         _check(self._lib, self._lib.gpsacq_refine_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    # ---- cold snapshot fixes ----------------------------------------------------------------
+    @staticmethod
+    def _record(params, dtype):
+        if params is None:
+            return None, None
+        pr = np.array(params, dtype=dtype).reshape(1).copy()
+        return pr, pr.ctypes.data_as(ctypes.c_void_p)
+
+    def fine_doppler(self, bits, peaks, tasks=None, stride=BLOCK_BYTES, params=None):
+        """gpsacq_fine_doppler: the Doppler of the peaks of a search of `bits` (PEAK_DTYPE, any shape; tasks as given to search(),
+        None for the reference schedule) below a bin, from the turn of the 1 ms prompt sums over a window of consecutive blocks.
+        Returns DOPFINE_DTYPE records in the shape of peaks.  params: dopfine_params(), None for the defaults."""
+        buf = np.ascontiguousarray(np.frombuffer(bits, dtype=np.uint8) if not isinstance(bits, np.ndarray) else bits.view(np.uint8))
+        if not isinstance(peaks, np.ndarray) or peaks.dtype != PEAK_DTYPE:
+            raise TypeError("peaks must be a PEAK_DTYPE array")
+        pk = np.ascontiguousarray(peaks)
+        tptr = None
+        if tasks is not None:
+            t = np.ascontiguousarray(np.asarray(tasks, dtype=np.int32).reshape(-1, 2))
+            if t.shape[0] != pk.size:
+                raise ValueError("one task per peak")
+            tptr = t.ctypes.data_as(ctypes.c_void_p)
+        dr, dp = self._record(params, DOPFINE_PARAMS_DTYPE)
+        out = np.zeros(pk.shape, dtype=DOPFINE_DTYPE)
+        _check(self._lib, self._lib.gpsacq_fine_doppler(self._h, buf.ctypes.data_as(ctypes.c_void_p), int(buf.size), int(stride), tptr,
+                                                        pk.ctypes.data_as(ctypes.c_void_p), int(pk.size), dp, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def fine_doppler_device(self, d_bits_ptr, n_bytes, d_peaks_ptr, n_tasks, d_dopfine_ptr, stride=BLOCK_BYTES, d_tasks_ptr=None, params=None,
+                            sync=True):
+        """gpsacq_fine_doppler_device: device pointers for the capture (any byte address), the peaks, the tasks (None: the reference
+        schedule) and the records."""
+        dr, dp = self._record(params, DOPFINE_PARAMS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_fine_doppler_device(self._h, d_bits_ptr, int(n_bytes), int(stride), d_tasks_ptr, d_peaks_ptr, int(n_tasks),
+                                                               dp, d_dopfine_ptr, 1 if sync else 0))
+
+    def rate_obs_fine(self, peaks, dopfine, snr_min=THRESHOLD):
+        """gpsacq_rate_obs_fine: search peaks (PEAK_DTYPE [n_fix][n_chans]) and their fine_doppler() records into rate observations
+        (RATE_OBS_DTYPE, the same shape): valid where snr >= snr_min and the record is usable, doppler_hz the record's, weight 1."""
+        if not isinstance(peaks, np.ndarray) or peaks.dtype != PEAK_DTYPE or peaks.ndim != 2:
+            raise TypeError("peaks must be a PEAK_DTYPE array [n_fix][n_chans]")
+        if not isinstance(dopfine, np.ndarray) or dopfine.dtype != DOPFINE_DTYPE or dopfine.size != peaks.size:
+            raise TypeError("dopfine must be a DOPFINE_DTYPE array with one record per peak")
+        pk, df = np.ascontiguousarray(peaks), np.ascontiguousarray(dopfine)
+        out = np.zeros(pk.shape, dtype=RATE_OBS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_rate_obs_fine(self._h, pk.ctypes.data_as(ctypes.c_void_p), df.ctypes.data_as(ctypes.c_void_p),
+                                                         int(pk.shape[0]), int(pk.shape[1]), float(snr_min), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def rate_obs_fine_device(self, d_peaks_ptr, d_dopfine_ptr, n_fix, n_chans, d_rate_obs_ptr, snr_min=THRESHOLD, sync=True):
+        _check(self._lib, self._lib.gpsacq_rate_obs_fine_device(self._h, d_peaks_ptr, d_dopfine_ptr, int(n_fix), int(n_chans), float(snr_min),
+                                                                d_rate_obs_ptr, 1 if sync else 0))
+
+    def doppler_fix(self, eph, obs, rate_obs, rx_ms, params=None):
+        """gpsacq_doppler_fix_batch: one place per row from Dopplers alone, with no prior of place: obs (OBS_DTYPE
+        [n_fix][sats_per_fix], of which only eph and valid are read), rate_obs (RATE_OBS_DTYPE, the same shape) and rx_ms (int32,
+        one value or n_fix), the receive time to about 30 s.  Returns (DOPPLER_FIX_DTYPE [n_fix], COARSE_PRIOR_DTYPE [n_fix]): the
+        fixes, and the priors coarse_fix() takes (NaN where a row failed).  params: doppler_fix_params(), None for the defaults."""
+        ep, ob = self._nav_arrays(eph, obs)
+        if ob.ndim != 2:
+            raise ValueError("obs must be [n_fix][sats_per_fix]")
+        ro = np.ascontiguousarray(np.asarray(rate_obs, dtype=RATE_OBS_DTYPE))
+        if ro.shape != ob.shape:
+            raise ValueError("rate_obs must have the shape of obs")
+        rx = np.ascontiguousarray(np.broadcast_to(np.asarray(rx_ms, dtype=np.int32).ravel(), (ob.shape[0],)))
+        fr, fp = self._record(params, DOPPLER_FIX_PARAMS_DTYPE)
+        out = np.zeros(ob.shape[0], dtype=DOPPLER_FIX_DTYPE)
+        pr = np.zeros(ob.shape[0], dtype=COARSE_PRIOR_DTYPE)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_doppler_fix_batch(self._h, p(ep), int(ep.size), p(ob), p(ro), p(rx), int(ob.shape[0]), int(ob.shape[1]), fp,
+                                                             p(out), p(pr)))
+        return out, pr
+
+    def doppler_fix_device(self, eph, d_obs_ptr, d_rate_obs_ptr, d_rx_ms_ptr, n_fix, sats_per_fix, d_doppler_fix_ptr, d_prior_ptr=None, params=None,
+                           sync=True):
+        """gpsacq_doppler_fix_batch_device: device pointers for the observations, the times and the outputs; d_prior_ptr may be None."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        fr, fp = self._record(params, DOPPLER_FIX_PARAMS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_doppler_fix_batch_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_obs_ptr, d_rate_obs_ptr,
+                                                                    d_rx_ms_ptr, int(n_fix), int(sats_per_fix), fp, d_doppler_fix_ptr, d_prior_ptr,
+                                                                    1 if sync else 0))
+
+    def cold_fix_device(self, eph, d_bits_ptr, n_bytes, d_tasks_ptr, d_peaks_ptr, d_rx_ms_ptr, n_fix, n_chans, d_fix_ptr, d_info_ptr,
+                        d_doppler_fix_ptr, d_dopfine_ptr=None, d_rate_obs_ptr=None, d_prior_ptr=None, d_fine_ptr=None, d_obs_ptr=None,
+                        d_obs_out_ptr=None, stride=BLOCK_BYTES, dopfine_params=None, doppler_params=None, refine_params=None, params=None, sync=True):
+        """gpsacq_cold_fix_device: capture, tasks (block outer, channel inner), peaks and rx_ms (int32 [n_fix]) -> fine Dopplers ->
+        Doppler fixes -> fine code phases -> coarse-time fixes in device memory, no host copy in between and no prior of place; the
+        six optional buffers may be None.  d_obs_out_ptr, d_rate_obs_ptr and d_fix_ptr go into velocity_device() unchanged."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        dr, dp = self._record(dopfine_params, DOPFINE_PARAMS_DTYPE)
+        fr, fp = self._record(doppler_params, DOPPLER_FIX_PARAMS_DTYPE)
+        rr, rp = self._refine_params(refine_params)
+        cr, cp = self._coarse_params(params)
+        _check(self._lib, self._lib.gpsacq_cold_fix_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_bits_ptr, int(n_bytes),
+                                                           int(stride), d_tasks_ptr, d_peaks_ptr, d_rx_ms_ptr, int(n_fix), int(n_chans), dp, fp, rp, cp,
+                                                           d_dopfine_ptr, d_rate_obs_ptr, d_doppler_fix_ptr, d_prior_ptr, d_fine_ptr, d_obs_ptr,
+                                                           d_fix_ptr, d_info_ptr, d_obs_out_ptr, 1 if sync else 0))
+
+    def doppler_last_ms(self):
+        """Device milliseconds of the last cold-fix calls: (k_fine_dop or 0, k_rate_obs_fine or 0, k_doppler_fix or 0)."""
+        t = [ctypes.c_float() for _ in range(3)]
+        _check(self._lib, self._lib.gpsacq_doppler_last_ms(self._h, *[ctypes.byref(x) for x in t]))
+        return tuple(x.value for x in t)
 
     def coarse_obs_device(self, d_peaks_ptr, n_fix, n_chans, d_obs_ptr, snr_min=THRESHOLD, sync=True):
         _check(self._lib, self._lib.gpsacq_coarse_obs_device(self._h, d_peaks_ptr, int(n_fix), int(n_chans), float(snr_min), d_obs_ptr,

@@ -1502,8 +1502,8 @@ GPSACQ_API int gpsacq_fix_raim_last_ms(const gpsacq_engine* e, float* sat_state_
  * row is held in registers -- the satellite loop of every pass reads the observation back from memory, evaluates the orbit
  * (csrc/orbit_device.hpp, the one copy k_sat_state and k_sat_state_rate use) and adds into the 15 + 5 sums.
  *
- * OUT OF SCOPE.  Doppler-aided time.  gps_test and gps_track.  (Sub-sample code phases: "Fine code phases" below; the correlator
- * and gpsacq_peak stay as they are.)
+ * OUT OF SCOPE.  Doppler-aided time.  gps_test and gps_track.  (Sub-sample code phases: "Fine code phases" below; a prior of place
+ * from the capture's own Dopplers: "Cold snapshot fixes" further down; the correlator and gpsacq_peak stay as they are.)
  */
 typedef struct { double x, y, z; int32_t rx_ms; int32_t reserved; } gpsacq_coarse_prior;                                    /* 32 bytes */
 typedef struct { double rms_max_m; double reserved; } gpsacq_coarse_params;                                                  /* 16 bytes */
@@ -1628,6 +1628,169 @@ GPSACQ_API int gpsacq_coarse_fix_fine_device(gpsacq_engine* e, const gpsacq_ephe
 /* device time of k_refine and k_coarse_obs_fine as last run on this engine, milliseconds (HIP events on its stream; waits for
  * them); a kernel that has not run reads 0.  Either pointer may be NULL. */
 GPSACQ_API int gpsacq_refine_last_ms(const gpsacq_engine* e, float* refine_ms, float* obs_ms);
+
+/*
+ * ---- Cold snapshot fixes: fine Doppler and a Doppler-only position solver ------------------------------------------------------
+ *
+ * The coarse-time solver wants a PRIOR: a place good to tens of kilometres (2 |dp| + 1600 m/s |dt| < 150 km, above).  A capture of
+ * unknown origin has none, but its hits carry one: the Doppler of a satellite is the projection of a known velocity on the line
+ * of sight, and a handful of them fix the receiver to a few kilometres once each is known to about 1 Hz.  A search peak knows its
+ * Doppler to half a bin only (lo_shift in steps of fs / 40000, +-68 Hz at 5.456 MHz, some +-70 km of place per satellite), so
+ * gpsacq_fine_doppler goes back to the capture as gpsacq_refine does and reads the carrier's turn from one code period to the next
+ * off the prompt sums; gpsacq_doppler_fix_batch then solves place and clock drift from the Dopplers alone, from no place at all,
+ * and hands gpsacq_coarse_fix_batch its prior.  Only the TIME has to be known, to about +-30 s.  THE MODEL; the kernels
+ * (csrc/doppler_kernels.hip) and the reference of the tests (tests/dop_ref.py) are both written from this text.  Integer arithmetic
+ * is exact (int64 / uint64, the bound is under OVERFLOW); every fp64 expression is evaluated as written, left to right, every
+ * operation rounded by itself (no fused multiply-add).
+ *
+ * 1. FINE DOPPLER.  INPUTS are those of gpsacq_refine: bits, n_bytes, stride, tasks or NULL, peaks, n_tasks.  gpsacq_dopfine_params:
+ * blocks, 1 .. 64, the length of the window; min_segments >= 2; snr_min, finite; coherence_min, finite and >= 0.
+ * gpsacq_dopfine_default_params (host only) sets 16, 2, 25.0 and 0.0 (the coherence gate is off).
+ * PER TASK.  spm, o and FULL as in "Fine code phases", PER TASK, whose steps 1 (NCO WORDS), 2 (NOT A HIT, here
+ * GPSACQ_DOPFINE_NO_HIT) and 3 (WINDOW AND SEGMENTS, here GPSACQ_DOPFINE_SHORT and GPSACQ_DOPFINE_FEW) apply word for word, with
+ * this section's blocks, min_segments and snr_min.  Then
+ *   PROMPT SUMS.  P0 = (ca_shift * ca_rate) mod FULL.  For sample j of the window: carrier phase ph = j * lo_rate (mod 2^32), cos
+ *     bit and sin bit as in THE CHANNEL MODEL; prompt position P = (P0 + j * ca_rate) mod FULL, chip[P >> 32].  Per segment s
+ *     (samples j = s spm .. (s + 1) spm - 1) the two sums I_s, Q_s as in THE CHANNEL MODEL: exactly step 4's I_P and Q_P.  Q is
+ *     the -sin arm, so with z = I + iQ a signal whose carrier lies df above the replica's turns z by +2 pi df T per segment.
+ *   SQUARES, blind to the data bits (a bit flip negates z and leaves z^2):  A_s = I_s^2 - Q_s^2,  B_s = 2 I_s Q_s,  int64.
+ *   LAG-1 SUMS over s = 1 .. segments - 1 (z_s^2 times the conjugate of z_(s-1)^2, and what bounds it):
+ *       re    = sum (A_s A_(s-1) + B_s B_(s-1))                        int64
+ *       im    = sum (B_s A_(s-1) - A_s B_(s-1))                        int64
+ *       mag   = sum (I_s^2 + Q_s^2) (I_(s-1)^2 + Q_(s-1)^2)            uint64
+ *     and over s = 0 .. segments - 1
+ *       power = sum (I_s^2 + Q_s^2)                                    uint64
+ *     With fewer than 2 segments re = im = mag = 0.
+ *   OVERFLOW.  |I|, |Q| <= spm, so a term of re, im or mag is at most 4 spm^4 and there are fewer than blocks * 40000 / spm of
+ *     them: an engine and parameters with blocks * 160000 * spm^3 >= 2^63 are GPSACQ_ERR_UNSUPPORTED (at spm = 10000: more than 57
+ *     blocks).  So are the engines gpsacq_refine refuses (num_lags > 65535, fs below 1.138 MHz).
+ *   ESTIMATE, in fp64.  mag == 0, or re == 0 and im == 0: GPSACQ_DOPFINE_NO_POWER and coherence = df_hz = doppler_hz = 0.  Otherwise
+ *       T          = (double)spm / fs
+ *       df_hz      = atan2((double)im, (double)re) / ((4 pi) T)        4 pi = 4.0 * 3.141592653589793
+ *       coherence  = hypot((double)re, (double)im) / (double)mag       in (0, 1]: 1 for a noise-free steady turn
+ *       doppler_hz = (((double)lo_rate * fs) / 2^32 - fc) + df_hz      the Doppler the replica really had, plus the rest
+ *     unambiguous while |df| < 1 / (4 T) = 250 Hz; a bin is +-68 Hz.  Then GPSACQ_DOPFINE_WEAK where coherence < coherence_min
+ *     (a NO_POWER record has coherence 0, so any coherence_min > 0 marks it).
+ *   USABLE: the record carries none of GPSACQ_DOPFINE_NO_HIT, _NO_POWER, _FEW and _WEAK.
+ * The record is gpsacq_dopfine; a NO_HIT record is that flag and zeros, every other keeps segments, lo_rate, ca_rate and the four
+ * sums whatever its flags.
+ * LIMITS.  Squaring a 1 ms sum costs 6 dB and more below about 12 dB of SNR per millisecond: for hits of the plain 1-bit search
+ * (38 dB-Hz and up).  The estimate is the mean over the window; the Doppler's own rate (below 1 Hz/s) is not modelled.  Measured
+ * with 116 lag-1 products at amplitude 0.2, noise sigma 1, over 16 384 hits: 1.26 Hz rms, 6.6 Hz worst, coherence 0.78 .. 0.95
+ * (1.5 Hz had been expected).  WITHOUT noise |df| reads some 7 % low (4 Hz at 60 Hz): the hard-limited signal keeps its third
+ * harmonic, which meets the third harmonic of the two-bit replica in a term that turns the other way; noise at the usual level
+ * linearises the limiter and takes the term away (tests/test_doppler.py measures both).
+ *
+ * RATE OBSERVATIONS.  gpsacq_rate_obs_fine: peaks[n_fix][n_chans] and dopfine[n_fix][n_chans], block outer and channel inner as
+ * FROM PEAKS of "Coarse-time fixes" has them.  Per (fix, channel): valid where snr >= snr_min and the record is usable and its
+ * doppler_hz is finite; then valid = 1, reserved = 0, adr = 0, doppler_hz the record's, weight = 1.0.  Anything else is 32 zero
+ * bytes.  The output is gpsacq_rate_obs, what gpsacq_vel_batch reads.
+ *
+ * 2. DOPPLER FIX.  INPUTS.  eph[n_eph] as for gpsacq_fix_batch.  obs[n_fix][sats_per_fix] of gpsacq_obs, of which ONLY eph and
+ * valid are read (gpsacq_coarse_obs's output serves).  rate_obs[n_fix][sats_per_fix].  rx_ms[n_fix], int32 in 0 .. 604 799 999:
+ * the prior of TIME only, the receive instant t0 = (rx_ms, 0).  gpsacq_doppler_fix_params: rms_max_mps, finite and > 0.
+ * A column is USABLE where its eph is in 0 .. n_eph - 1, that ephemeris passes SATELLITE STATE's rule (gpsacq_ephemeris_valid),
+ * valid != 0 in both records, doppler_hz is finite and the rate observation's weight is finite and >= 0.  A row whose rx_ms is
+ * outside the week has no usable column.  n_used counts the usable columns; fewer than 4: GPSACQ_FIX_TOO_FEW, no step.
+ * UNKNOWNS x, y, z (ECEF metres) and g = c drift_r (m/s).  Every usable column k carries a light time tau_k, 75e-3 s at first.
+ * Omega = Omega_e-dot, c, L1 and R(a) as in "Coarse-time fixes" and VELOCITY.  SATELLITE of column k at light time tau: position p,
+ * clock drift d and ECEF velocity v (SATELLITE STATE, SATELLITE RATE) at the uncorrected time -tau from t0, split by FIX's rule
+ * into (rx_ms + whole milliseconds folded into the week, fraction); a = -Omega tau;
+ *       r  = R(a) p,     vi = R(a) (v + (-Omega p_y, Omega p_x, 0))          the inertial velocity in the frame of t0
+ *   START.  u = sum over the usable columns of r / |r|, each at tau = 75e-3.  |u| not >= 1e-6: GPSACQ_FIX_NO_CONVERGE.  Otherwise
+ *     (x, y, z) = (6371000 u_x / |u|, 6371000 u_y / |u|, 6371000 u_z / |u|) and g = 0: the foot of the mean satellite direction.
+ *   PASS.  Per usable column, in column order, with its satellite at tau_k:
+ *       D     = r - (x, y, z),   range = |D|,   e = D / range  (every division by range is a product with 1 / range)
+ *       w     = vi - (-Omega y, Omega x, 0)
+ *       ew    = e . w
+ *       pred  = (ew + g) - c d
+ *       res   = -(c / L1) doppler_hz - pred
+ *       h     = ( -(w - ew e) / range + (-Omega e_y, Omega e_x, 0),  1 )     so that res ~ h . (dx, dy, dz, dg)
+ *       tau_k = range / c                                                    for the next pass
+ *     (VELOCITY's equation with v_r = 0, differentiated by the place.)  Weighted normal equations A = sum w h h^T, b = sum w h res
+ *     with w the rate observation's weight, FIX's 4x4 Cholesky and pivot rule.  rms = sqrt(sum w res^2 / sum w) of this pass.
+ *     The step is applied and counted in `iterations`; one with |(dx, dy, dz)| < 1e-3 m is the last.  A bad pivot, a step that is
+ *     not finite, |(x, y, z)| not <= 1e8 m after a step, or 20 steps without a last one: GPSACQ_FIX_NO_CONVERGE.
+ *   RECORD gpsacq_doppler_fix.  GPSACQ_FIX_OK: x, y, z; lat, lon, alt as in FIX; drift = g / c; rms that of the last pass, m/s;
+ *     pdop = sqrt of the trace of the position block of (H^T H)^-1, H the rows h of the last pass, unweighted, over the usable
+ *     columns with weight > 0 -- metres of place per m/s of range rate -- and 0 where its Cholesky factor fails or it is not
+ *     finite; flags = GPSACQ_DOPPLER_INCONSISTENT when n_used >= 5 and rms > rms_max_mps.  Any other status: every double and
+ *     flags 0; n_used and iterations stay.
+ *   PRIOR.  prior_out[n_fix] of gpsacq_coarse_prior: rx_ms the row's as given, reserved 0, and the place of a GPSACQ_FIX_OK row that
+ *     is not INCONSISTENT; for every other row x = y = z = NaN, which gpsacq_coarse_fix_batch_device treats as a row with no
+ *     usable observation.
+ * gpsacq_doppler_fix_default_params (host only) sets rms_max_mps = 3.0 m/s, about 16 Hz.  Measured (tools/snapshot_bench.py --cold,
+ * 2048 blocks x 8 satellites at amplitude 0.2, the time 20 s off): rms 0.08 .. 0.72 m/s, median 0.40; three times the largest is
+ * 2.15 m/s, rounded up to one digit.  (2.0 m/s, the value first proposed from an expected 1.5 Hz per Doppler, is below that.)  One
+ * Doppler 200 Hz off among eight leaves 3.3 m/s and more.
+ * WHAT TO EXPECT (simulated, three geometries, drift 2e-6): 5-6 steps; exact Dopplers land 4-35 m from the truth; 1.5 Hz of noise
+ * on eight satellites 2.4-3.0 km median and 6.3 km worst, on five 7 km median and 21 km worst; a time 30 s off moves the place by
+ * up to 26 km with eight satellites and 64 km with five.  Eight satellites and +-30 s stay inside the coarse-time condition, five
+ * do not always.  The receiver is taken to be at rest: 1 m/s of its own speed is some 5 Hz, kilometres of place.
+ *
+ * 3. THE CHAIN.  gpsacq_cold_fix_device: on the engine's stream, no host copy in between,
+ *       k_fine_dop -> k_coarse_obs and k_rate_obs_fine -> k_doppler_fix -> k_refine -> k_coarse_obs_fine -> k_coarse_fix
+ * from the capture, tasks, peaks (task b * n_chans + c = block b against the PRN of eph[c], n_tasks = n_fix * n_chans) and
+ * d_rx_ms[n_fix] to d_fix, d_info (gpsacq_coarse_fix_batch's records) and d_doppler_fix.  Both snr_min of the observations are
+ * their kernel's params' (dopfine_params for k_coarse_obs and k_rate_obs_fine, refine_params for k_coarse_obs_fine).  d_dopfine,
+ * d_rate_obs, d_prior, d_fine, d_obs and d_obs_out may be NULL (engine scratch); d_obs holds k_coarse_obs's observations first and
+ * k_coarse_obs_fine's in the end.  d_obs_out, d_rate_obs and d_fix go into gpsacq_vel_batch_device unchanged: a snapshot velocity
+ * (and a second reading of the clock drift) comes for free.
+ *
+ * gpsacq_fine_doppler, gpsacq_rate_obs_fine, gpsacq_doppler_fix_batch: host pointers, return after completion; a negative or
+ * non-finite weight or an rx_ms outside the week is GPSACQ_ERR_ARG in gpsacq_doppler_fix_batch.  The _device forms: device pointers
+ * for everything but eph and the params (NULL: the defaults), bits at any byte address; work on the engine's stream, sync != 0
+ * waits; a bad weight skips the column, a bad rx_ms the row; host and device form agree byte for byte.  Argument errors -- a NULL
+ * pointer (prior_out and d_prior may be NULL), n_tasks or n_fix == 0, n_bytes == 0, a parameter or the stride outside its bounds,
+ * n_chans or sats_per_fix outside 1..GPSACQ_FIX_MAX_SATS, d_obs_out == d_obs -- return GPSACQ_ERR_ARG, launch nothing and write
+ * nothing.
+ * Kernels (csrc/doppler_kernels.hip).  k_fine_dop: one workgroup of four wave64 per task with k_refine's word loop
+ * (csrc/capture_words.hpp holds the one copy): three masks and two popcounts per word; every segment's (I, Q) goes into LDS as two
+ * int32 (at most 64 * 40000 / 1137 = 2251 segments, 18 KB); after one barrier thread i takes s = i, i + 256, ...; the four sums
+ * meet through integer shuffles and one LDS step.  No atomics, no float before the estimate: the record depends on the order of
+ * nothing.  k_rate_obs_fine: one lane per (fix, channel).  k_doppler_fix: one lane per fix, nothing of the row in registers (the
+ * light times live in engine scratch), the orbit from csrc/orbit_device.hpp.  Every loop is bounded by kernel arguments.
+ *
+ * OUT OF SCOPE.  Coherent sums longer than one code period and signals below about 38 dB-Hz.  Doppler rate over the window.  A
+ * height constraint for five-satellite rows.  Solving the time error from the Dopplers.  Fusing k_fine_dop into k_refine.  8-bit
+ * IQ input, accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.
+ */
+#define GPSACQ_DOPFINE_NO_HIT 1     /* the peak is no hit, or its task or NCO words are out of range: the record is this flag and zeros */
+#define GPSACQ_DOPFINE_SHORT 2      /* the capture ends before the window does */
+#define GPSACQ_DOPFINE_NO_POWER 4   /* mag == 0, or re == 0 and im == 0 */
+#define GPSACQ_DOPFINE_FEW 8        /* segments < min_segments */
+#define GPSACQ_DOPFINE_WEAK 16      /* coherence < coherence_min */
+typedef struct { int32_t blocks; int32_t min_segments; double snr_min; double coherence_min; } gpsacq_dopfine_params;             /* 24 bytes */
+typedef struct { int32_t flags, segments; uint32_t lo_rate, ca_rate; int64_t re, im; uint64_t mag, power;
+                 double coherence, df_hz, doppler_hz; } gpsacq_dopfine;                                                          /* 72 bytes */
+typedef struct { double rms_max_mps; double reserved; } gpsacq_doppler_fix_params;                                               /* 16 bytes */
+#define GPSACQ_DOPPLER_INCONSISTENT 1   /* n_used >= 5 and rms > rms_max_mps */
+typedef struct { int32_t status, n_used, iterations, flags; double x, y, z, lat, lon, alt, drift, rms, pdop; } gpsacq_doppler_fix; /* 88 bytes */
+GPSACQ_API int gpsacq_dopfine_default_params(gpsacq_dopfine_params* p);            /* host only */
+GPSACQ_API int gpsacq_doppler_fix_default_params(gpsacq_doppler_fix_params* p);    /* host only */
+GPSACQ_API int gpsacq_fine_doppler(gpsacq_engine* e, const uint8_t* bits, size_t n_bytes, size_t stride, const gpsacq_task* tasks,
+                                   const gpsacq_peak* peaks, size_t n_tasks, const gpsacq_dopfine_params* params, gpsacq_dopfine* dopfine_out);
+GPSACQ_API int gpsacq_fine_doppler_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks,
+                                          const void* d_peaks, size_t n_tasks, const gpsacq_dopfine_params* params, void* d_dopfine, int sync);
+GPSACQ_API int gpsacq_rate_obs_fine(gpsacq_engine* e, const gpsacq_peak* peaks /* [n_fix][n_chans] */, const gpsacq_dopfine* dopfine, size_t n_fix,
+                                    int n_chans, double snr_min, gpsacq_rate_obs* rate_obs);
+GPSACQ_API int gpsacq_rate_obs_fine_device(gpsacq_engine* e, const void* d_peaks, const void* d_dopfine, size_t n_fix, int n_chans, double snr_min,
+                                           void* d_rate_obs, int sync);
+GPSACQ_API int gpsacq_doppler_fix_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs /* [n_fix][sats_per_fix] */,
+                                        const gpsacq_rate_obs* rate_obs, const int32_t* rx_ms, size_t n_fix, int sats_per_fix,
+                                        const gpsacq_doppler_fix_params* params, gpsacq_doppler_fix* fix_out, gpsacq_coarse_prior* prior_out);
+GPSACQ_API int gpsacq_doppler_fix_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_rate_obs,
+                                               const void* d_rx_ms, size_t n_fix, int sats_per_fix, const gpsacq_doppler_fix_params* params,
+                                               void* d_doppler_fix, void* d_prior, int sync);
+GPSACQ_API int gpsacq_cold_fix_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_bits, size_t n_bytes, size_t stride,
+                                      const void* d_tasks, const void* d_peaks, const void* d_rx_ms, size_t n_fix, int n_chans,
+                                      const gpsacq_dopfine_params* dopfine_params, const gpsacq_doppler_fix_params* doppler_params,
+                                      const gpsacq_refine_params* refine_params, const gpsacq_coarse_params* coarse_params, void* d_dopfine,
+                                      void* d_rate_obs, void* d_doppler_fix, void* d_prior, void* d_fine, void* d_obs, void* d_fix, void* d_info,
+                                      void* d_obs_out, int sync);
+/* device time of k_fine_dop, k_rate_obs_fine and k_doppler_fix as last run on this engine, milliseconds (HIP events on its
+ * stream; waits for them); a kernel that has not run reads 0.  Any pointer may be NULL. */
+GPSACQ_API int gpsacq_doppler_last_ms(const gpsacq_engine* e, float* fine_dop_ms, float* rate_obs_ms, float* doppler_fix_ms);
 
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);

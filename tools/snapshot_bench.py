@@ -12,7 +12,7 @@ The generator runs every satellite at the Doppler it has in the middle of the ca
 away from that instant the truth is off by the range acceleration (metres over 15 s), well below the 55 m a whole-sample code phase
 is worth at 5.456 MHz.
 
-    python tools/snapshot_bench.py [--blocks 2048] [--reps 5] [--refine [--refine-blocks 16]]
+    python tools/snapshot_bench.py [--blocks 2048] [--reps 5] [--refine [--refine-blocks 16]] [--cold]
 
 --refine: the capture is made K - 1 blocks longer (K = --refine-blocks) so that every searched block has its whole window, and
 each repetition also runs gpsacq_coarse_fix_fine_device on the same capture, tasks and peaks: k_refine (the fine code phases of
@@ -20,6 +20,14 @@ include/gpsacq.h), k_coarse_obs_fine and k_coarse_fix.  The line gains refine_ms
 same run), the position error of the fine fixes beside the whole-sample ones of the same blocks, and the rms code-phase error of
 both kinds of phase against the generator's own law (the code position (m + code_phase) * chips_per_sample at a block's first
 sample m), in metres of range.  The generator's constant Doppler (above) is part of the fine fixes' position error.
+
+--cold: the --refine scene (it implies --refine) fixed once more with NO prior of place and a time 20 s off, early and late in
+turn: each repetition also runs gpsacq_cold_fix_device -- k_fine_dop, k_coarse_obs, k_rate_obs_fine, k_doppler_fix, k_refine,
+k_coarse_obs_fine, k_coarse_fix ("Cold snapshot fixes" of include/gpsacq.h).  The line gains fine_dop_ms and doppler_fix_ms (best
+of the repetitions, beside refine_ms and search_ms of the same run), the error of the fine Dopplers against the generator's (rms
+and worst over the true hits, beside the bin centres'), their coherence (min, median), the Doppler fixes' place error (median,
+worst), the distribution of their rms in m/s (the default rms_max_mps must stay at or above three times its maximum), and the cold
+fixes' position error beside the warm fine fixes' of the same blocks.
 """
 import argparse
 import json
@@ -39,7 +47,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--refine", action="store_true", help="also refine the peaks below a sample and fix from the fine code phases")
     ap.add_argument("--refine-blocks", type=int, default=16, help="window of the refinement, in blocks (1 .. 64)")
+    ap.add_argument("--cold", action="store_true", help="also fix every block with no prior of place: fine Doppler, Doppler fix, fine fix")
     a = ap.parse_args()
+    a.refine = a.refine or a.cold
 
     import numpy as np
     import torch
@@ -71,6 +81,13 @@ def main():
             rp = gpsacq.refine_params(blocks=a.refine_blocks)
             d_fine = zeros(n_tasks * gpsacq.FINE_DTYPE.itemsize)
             d_fix_f, d_info_f = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
+        if a.cold:
+            rx_cold = np.ascontiguousarray(priors(geo, blk_ms, seed=3, km=30.0, secs=20.0)["rx_ms"].astype(np.int32))
+            d_rx = dev(rx_cold)
+            d_dopfine, d_rate = zeros(n_tasks * gpsacq.DOPFINE_DTYPE.itemsize), zeros(n_tasks * gpsacq.RATE_OBS_DTYPE.itemsize)
+            d_dfix = zeros(a.blocks * gpsacq.DOPPLER_FIX_DTYPE.itemsize)
+            d_fix_c, d_info_c = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
+            cold_best = [float("inf")] * 3
         torch.cuda.synchronize()
         eng.generate_device(d_bits.data_ptr(), n_bytes, sats, noise_sigma=1.0, seed=77)
         best, search_best, refine_best = None, float("inf"), float("inf")
@@ -89,10 +106,21 @@ def main():
                                            d_prior.data_ptr(), d_fix_f.data_ptr(), d_info_f.data_ptr(), d_fine_ptr=d_fine.data_ptr(), refine_params=rp,
                                            sync=True)
                 refine_best = min(refine_best, eng.refine_last_ms()[0])
+            if a.cold:
+                eng.cold_fix_device(ephs, d_bits.data_ptr(), n_bytes, d_tasks.data_ptr(), d_peaks.data_ptr(), d_rx.data_ptr(), a.blocks, len(sats),
+                                    d_fix_c.data_ptr(), d_info_c.data_ptr(), d_dfix.data_ptr(), d_dopfine_ptr=d_dopfine.data_ptr(),
+                                    d_rate_obs_ptr=d_rate.data_ptr(), refine_params=rp, sync=True)
+                cold_best = [min(x, y) for x, y in zip(cold_best, eng.doppler_last_ms())]
+                refine_best = min(refine_best, eng.refine_last_ms()[0])
         if a.refine:
             fine = d_fine.cpu().numpy().view(gpsacq.FINE_DTYPE).reshape(a.blocks, len(sats))
             fix_f = d_fix_f.cpu().numpy().view(gpsacq.FIX_DTYPE)
             info_f = d_info_f.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
+        if a.cold:
+            dopfine = d_dopfine.cpu().numpy().view(gpsacq.DOPFINE_DTYPE).reshape(a.blocks, len(sats))
+            dfix = d_dfix.cpu().numpy().view(gpsacq.DOPPLER_FIX_DTYPE)
+            fix_c = d_fix_c.cpu().numpy().view(gpsacq.FIX_DTYPE)
+            info_c = d_info_c.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
         fix = d_fix.cpu().numpy().view(gpsacq.FIX_DTYPE)
         info = d_info.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
         four = d_fix4.cpu().numpy().view(gpsacq.FIX_DTYPE)
@@ -126,6 +154,37 @@ def main():
             "position_error_max_whole_same_blocks_m": round(float(off[ok_f].max()), 2) if ok_f.any() else None,
             "position_error_median_fine_m": round(float(np.median(off_f[ok_f])), 2) if ok_f.any() else None,
             "position_error_max_fine_m": round(float(off_f[ok_f].max()), 2) if ok_f.any() else None}
+    if a.cold:
+        dops = np.array([s[2] for s in sats])[None, :]
+        usable = hit & ((dopfine["flags"] & (gpsacq.DOPFINE_NO_HIT | gpsacq.DOPFINE_NO_POWER | gpsacq.DOPFINE_FEW | gpsacq.DOPFINE_WEAK)) == 0)
+        e_fine_hz, e_bin_hz = (dopfine["doppler_hz"] - dops)[usable], (pk["lo_shift"] * (FS / 40000.0) - dops)[usable]
+        d_ok = dfix["status"] == 0
+        d_clean = d_ok & (dfix["flags"] == 0)
+        d_off = np.linalg.norm(np.stack([dfix["x"], dfix["y"], dfix["z"]], 1) - geo["rx"], axis=1)
+        ok_c = (fix_c["status"] == 0) & (info_c["flags"] == 0) & ok_f  # the same blocks as the warm fine fixes
+        off_c = np.linalg.norm(np.stack([fix_c["x"], fix_c["y"], fix_c["z"]], 1) - geo["rx"], axis=1)
+        gap = np.linalg.norm(np.stack([fix_c[k] - fix_f[k] for k in "xyz"], 1), axis=1)
+        rms = dfix["rms"][d_ok]
+        r4 = lambda v: round(float(v), 4)
+        extra.update({
+            "time_off_s": 20.0, "fine_dop_ms": r4(cold_best[0]), "rate_obs_fine_ms": r4(cold_best[1]), "doppler_fix_ms": r4(cold_best[2]),
+            "fine_dop_over_refine": r4(cold_best[0] / refine_best), "doppler_hits": int(usable.sum()),
+            "doppler_error_rms_hz": r4(np.sqrt((e_fine_hz ** 2).mean())), "doppler_error_max_hz": r4(np.abs(e_fine_hz).max()),
+            "bin_centre_error_rms_hz": r4(np.sqrt((e_bin_hz ** 2).mean())), "bin_centre_error_max_hz": r4(np.abs(e_bin_hz).max()),
+            "coherence_min": r4(dopfine["coherence"][usable].min()), "coherence_median": r4(np.median(dopfine["coherence"][usable])),
+            "doppler_fix_ok": int(d_ok.sum()), "doppler_fix_inconsistent": int((d_ok & ~d_clean).sum()),
+            "doppler_fix_passes_max": int(dfix["iterations"].max()),
+            "doppler_fix_error_median_km": r4(np.median(d_off[d_clean]) / 1e3) if d_clean.any() else None,
+            "doppler_fix_error_max_km": r4(d_off[d_clean].max() / 1e3) if d_clean.any() else None,
+            "doppler_fix_rms_mps": {k: r4(v) for k, v in zip(("min", "median", "p99", "max"),
+                                                             (rms.min(), np.median(rms), np.percentile(rms, 99), rms.max()))} if d_ok.any() else None,
+            "rms_max_mps_default_over_3x_max": r4(float(gpsacq.doppler_fix_params()["rms_max_mps"][0]) / (3.0 * rms.max())) if d_ok.any() else None,
+            "cold_blocks_compared": int(ok_c.sum()), "cold_ok": int((fix_c["status"] == 0).sum()),
+            "position_error_median_cold_m": round(float(np.median(off_c[ok_c])), 2) if ok_c.any() else None,
+            "position_error_max_cold_m": round(float(off_c[ok_c].max()), 2) if ok_c.any() else None,
+            "position_error_median_warm_fine_same_blocks_m": round(float(np.median(off_f[ok_c])), 2) if ok_c.any() else None,
+            "position_error_max_warm_fine_same_blocks_m": round(float(off_f[ok_c].max()), 2) if ok_c.any() else None,
+            "cold_against_warm_max_m": float(gap[ok_c].max()) if ok_c.any() else None})
     print(json.dumps({
         "bench": "snapshot", "device": name, "blocks": a.blocks, "sats": len(sats), "tasks": n_tasks, "prior_off_km": 30.0, "prior_off_s": 30.0,
         "search_ms": round(search_best, 4), "coarse_obs_ms": round(best[0], 4), "coarse_fix_ms": round(best[1], 4),
