@@ -46,20 +46,15 @@ static const size_t kFwdChunk = 32768;  // blocks per forward-transform launch (
 static const size_t kPdumpBytes = (size_t)1 << 30;  // per-lag power sums of the multi-pass re-alignment path, per chunk of tasks
 
 static int ensure_code_slots(gpsacq_engine* e, size_t n_patch) {
-    if (n_patch <= e->patch_cap) return GPSACQ_OK;
+    if (n_patch <= e->d_patch_blocks.cap) return GPSACQ_OK;
     const size_t slot = (size_t)NPOLY * e->crow;
-    cf* nd = nullptr;
-    HIPCHK(hipMalloc((void**)&nd, (GPSACQ_NUM_SATS + n_patch) * slot * sizeof(cf)));
+    Scratch<cf> nd;  // leaves with the old spectra
+    HIPCHK(nd.alloc((GPSACQ_NUM_SATS + n_patch) * slot));
     HIPCHK(hipMemcpyAsync(nd, e->d_code, GPSACQ_NUM_SATS * slot * sizeof(cf), hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipFree(e->d_code));
-    e->d_code = nd;
-    e->patch_cap = 0;
+    e->d_code.swap(nd);
     e->sched_valid = false;  // the cached default schedule's patch list lived in the buffer freed below
-    if (e->d_patch_blocks) HIPCHK(hipFree(e->d_patch_blocks));
-    e->d_patch_blocks = nullptr;
-    HIPCHK(hipMalloc((void**)&e->d_patch_blocks, n_patch * sizeof(int32_t)));
-    e->patch_cap = n_patch;
+    HIPCHK(e->d_patch_blocks.alloc(n_patch));
     return GPSACQ_OK;
 }
 
@@ -114,49 +109,14 @@ extern "C" void gpsacq_destroy(gpsacq_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->p.device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    void* bufs[] = {e->d_t1, e->d_t2, e->d_bq, e->d_fold, e->d_tn, e->d_rho, e->d_cos, e->d_sin, e->d_cos_t, e->d_sin_t, e->d_code, e->d_patch_blocks, e->d_bits, e->d_iq, e->d_iqbits, e->d_fsamp, e->d_pdump, e->d_sums, e->d_sats, e->d_gen, e->d_nav, e->d_track_chips, e->d_chans, e->d_track_n, e->d_prompt, e->d_records, e->d_nav_eph, e->d_nav_obs, e->d_nav_state, e->d_nav_fix, e->d_obs_chan, e->d_obs_pos, e->d_obs_rec, e->d_rate_chan, e->d_rate_acc, e->d_rate_obs, e->d_sat_rate, e->d_vel, e->d_atm_dop, e->d_atm_view, e->d_raim_rows, e->d_raim, e->d_smooth_chan, e->d_smooth_lock, e->d_smooth_q, e->d_smooth_w, e->d_smooth_info, e->d_quality_chan, e->d_quality_sums, e->d_quality_info, e->d_coarse_peaks, e->d_coarse_obs, e->d_coarse_work, e->d_coarse_prior, e->d_coarse_info, e->d_refine_bits, e->d_refine_tasks, e->d_refine_peaks, e->d_fine, e->d_dopfine, e->d_dop_tau, e->d_dop_rx_ms, e->d_dop_fix, e->d_dop_prior, e->d_persist, e->d_lutc,
-                    e->d_dpp, e->d_parts, e->d_tasks, e->d_cells, e->d_peaks};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (auto& set : e->ev)
-        for (auto& ev : set)
-            if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->tiq_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->nav_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->obs_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->rate_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->vel_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->atm_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->raim_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->smooth_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->quality_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->coarse_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->refine_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : e->dop_ev)
-        if (ev) (void)hipEventDestroy(ev);
     if (e->copy_stream) (void)hipStreamSynchronize(e->copy_stream);
-    for (auto& sl : e->pipe) {
+    for (auto& sl : e->pipe) {  // the pinned staging of the pipelined searches
         if (sl.h_in) (void)hipHostFree(sl.h_in);
         if (sl.h_peaks) (void)hipHostFree(sl.h_peaks);
-        if (sl.d_in) (void)hipFree(sl.d_in);
-        if (sl.d_peaks) (void)hipFree(sl.d_peaks);
-        if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
-        if (sl.done) (void)hipEventDestroy(sl.done);
     }
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
     if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    delete e;  // every Scratch and Stages member frees itself here, with the engine's device still current on this thread
 }
 
 extern "C" int gpsacq_create(const gpsacq_params* params, gpsacq_engine** out) {
@@ -249,8 +209,8 @@ extern "C" int gpsacq_create(const gpsacq_params* params, gpsacq_engine** out) {
     } while (0)
     const double ms_runtime = lap();  // HIP runtime + device initialisation happen inside the first calls above
     HCK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    for (auto& set : e->ev)
-        for (auto& ev : set) HCK(hipEventCreate(&ev));
+    for (auto& st : e->ring)
+        for (auto& ev : st.ev) HCK(hipEventCreate(&ev));
 
     const double ms_before_prep = lap();
     std::unique_ptr<HostPrep> hp;
@@ -263,49 +223,48 @@ extern "C" int gpsacq_create(const gpsacq_params* params, gpsacq_engine** out) {
     }
     const Tables& T = hp->T;
     const double ms_prep_wait = lap() - ms_before_prep;
-    HCK(hipMalloc((void**)&e->d_t1, T.t1.size() * sizeof(cf)));
-    HCK(hipMalloc((void**)&e->d_t2, T.t2.size() * sizeof(cf)));
-    HCK(hipMalloc((void**)&e->d_tn, hp->tn.size() * sizeof(cf)));
+    HCK(e->d_t1.alloc(T.t1.size()));
+    HCK(e->d_t2.alloc(T.t2.size()));
+    HCK(e->d_tn.alloc(hp->tn.size()));
     HCK(hipMemcpy(e->d_tn, hp->tn.data(), hp->tn.size() * sizeof(cf), hipMemcpyHostToDevice));
-    HCK(hipMalloc((void**)&e->d_lutc, hp->lutc.size() * sizeof(cf)));
+    HCK(e->d_lutc.alloc(hp->lutc.size()));
     HCK(hipMemcpy(e->d_lutc, hp->lutc.data(), hp->lutc.size() * sizeof(cf), hipMemcpyHostToDevice));
     HCK(upload_wq(T.wq.data()));
     HCK(upload_chips(hp->chips.data()));
     {
         unsigned char rho[256] = {0};
         memcpy(rho, kRhoC, sizeof kRhoC);
-        HCK(hipMalloc((void**)&e->d_rho, sizeof rho));
+        HCK(e->d_rho.alloc(sizeof rho));
         HCK(hipMemcpy(e->d_rho, rho, sizeof rho, hipMemcpyHostToDevice));
     }
-    HCK(hipMalloc((void**)&e->d_fold, hp->TF.fold.size() * sizeof(cf)));
+    HCK(e->d_fold.alloc(hp->TF.fold.size()));
     HCK(hipMemcpy(e->d_fold, hp->TF.fold.data(), hp->TF.fold.size() * sizeof(cf), hipMemcpyHostToDevice));
-    HCK(hipMalloc((void**)&e->d_bq, T.bq.size() * sizeof(cf)));
+    HCK(e->d_bq.alloc(T.bq.size()));
     HCK(hipMemcpy(e->d_bq, T.bq.data(), T.bq.size() * sizeof(cf), hipMemcpyHostToDevice));
     HCK(hipMemcpy(e->d_t1, T.t1.data(), T.t1.size() * sizeof(cf), hipMemcpyHostToDevice));
     HCK(hipMemcpy(e->d_t2, T.t2.data(), T.t2.size() * sizeof(cf), hipMemcpyHostToDevice));
 
-    HCK(hipMalloc((void**)&e->d_cos, BLOCK_BYTES));
-    HCK(hipMalloc((void**)&e->d_sin, BLOCK_BYTES));
+    HCK(e->d_cos.alloc(BLOCK_BYTES));
+    HCK(e->d_sin.alloc(BLOCK_BYTES));
     HCK(hipMemcpy(e->d_cos, hp->cosm.data(), BLOCK_BYTES, hipMemcpyHostToDevice));
     HCK(hipMemcpy(e->d_sin, hp->sinm.data(), BLOCK_BYTES, hipMemcpyHostToDevice));
-    HCK(hipMalloc((void**)&e->d_cos_t, 625 * sizeof(uint64_t)));
-    HCK(hipMalloc((void**)&e->d_sin_t, 625 * sizeof(uint64_t)));
+    HCK(e->d_cos_t.alloc(625));
+    HCK(e->d_sin_t.alloc(625));
     HCK(hipMemcpy(e->d_cos_t, hp->cos_t.data(), 625 * sizeof(uint64_t), hipMemcpyHostToDevice));
     HCK(hipMemcpy(e->d_sin_t, hp->sin_t.data(), 625 * sizeof(uint64_t), hipMemcpyHostToDevice));
 
     const double ms_tables = lap();
     // SearchInit(): 32 resampled replicas (host, float-sequential NCO) -> code spectra (device)
     const std::vector<float>& rep = hp->rep;
-    float* d_rep = nullptr;
-    HCK(hipMalloc((void**)&d_rep, rep.size() * sizeof(float)));
+    Scratch<float> d_rep;
+    HCK(d_rep.alloc(rep.size()));
     HCK(hipMemcpy(d_rep, rep.data(), rep.size() * sizeof(float), hipMemcpyHostToDevice));
     const size_t slot = (size_t)NPOLY * e->crow;
-    HCK(hipMalloc((void**)&e->d_code, GPSACQ_NUM_SATS * slot * sizeof(cf)));
+    HCK(e->d_code.alloc(GPSACQ_NUM_SATS * slot));
     HCK(hipMemsetAsync(e->d_code, 0, GPSACQ_NUM_SATS * slot * sizeof(cf), e->stream));
     {
         int rc = run_forward(e, FWD_REAL, d_rep, N_FFT, GPSACQ_NUM_SATS, e->d_code, slot, e->crow, e->halo, false);
         if (rc != GPSACQ_OK) {
-            (void)hipFree(d_rep);
             gpsacq_destroy(e);
             return rc;
         }
@@ -313,7 +272,6 @@ extern "C" int gpsacq_create(const gpsacq_params* params, gpsacq_engine** out) {
     launch_code_halo(e->d_code, GPSACQ_NUM_SATS * NPOLY, e->crow, e->halo, e->stream);
     HCK(hipGetLastError());
     HCK(hipStreamSynchronize(e->stream));
-    HCK(hipFree(d_rep));
 #undef HCK
     if (trace)
         fprintf(stderr, "gpsacq trace: gpsacq_create %.1f ms = HIP runtime/device start-up %.1f (host tables and code replicas computed meanwhile; "
@@ -366,7 +324,7 @@ static void launch_patches(gpsacq_engine* e, size_t n_patch, const uint8_t* d_bi
 static int build_default_schedule(gpsacq_engine* e, size_t n_tasks) {
     const bool quirks = e->p.ref_quirks != 0;
     e->sched_valid = false;
-    if (int rc = grow(e->d_tasks, e->task_cap, n_tasks, e->stream)) return rc;
+    if (int rc = e->d_tasks.grow(n_tasks, e->stream)) return rc;
     std::vector<Task> tk(n_tasks);
     std::vector<int32_t> patch_blocks;
     for (size_t t = 0; t < n_tasks; ++t) {
@@ -399,7 +357,7 @@ static int prepare_tasks(gpsacq_engine* e, const gpsacq_task* h_tasks, const voi
         return GPSACQ_OK;
     }
     e->sched_valid = false;  // before grow(): a failed reallocation must not leave a cached schedule pointing at freed memory
-    if (int rc = grow(e->d_tasks, e->task_cap, n_tasks, e->stream)) return rc;
+    if (int rc = e->d_tasks.grow(n_tasks, e->stream)) return rc;
     std::vector<gpsacq_task> tmp;
     if (!h_tasks && d_user_tasks) {
         if (!quirks) {  // same layout: {block, prn} == {spec, code}
@@ -460,7 +418,7 @@ static int arm_persist(gpsacq_engine* e, CorrArgs& ca, int mc) {
     const size_t slots = (size_t)handout_slots((long)ca.n_tasks, units, wgs);
     if (slots > 0x7fffffffu / 8) return GPSACQ_OK;  // (a batch too large for the slot table: one workgroup per cell)
     const size_t ints = 9 * 16 + 8 * slots;
-    if (int rc = grow(e->d_persist, e->persist_cap, ints, e->stream)) return rc;
+    if (int rc = e->d_persist.grow(ints, e->stream)) return rc;
     HIPCHK(hipMemsetAsync(e->d_persist, 0, ints * sizeof(int), e->stream));
     ca.persist_queue = e->d_persist;
     ca.persist_tasks = e->d_persist + 9 * 16;
@@ -488,7 +446,7 @@ static int search_core(gpsacq_engine* e, const Capture& cap_in, size_t n_blocks,
             if (cap.stride < (size_t)BLOCK_BYTES * 16)
                 return fail(GPSACQ_ERR_ARG, "ref_quirks needs all 40960 samples of a block: 8-bit IQ stride %zu < 81920 bytes", cap.stride);
             const size_t n_samples = (n_blocks - 1) * (cap.stride / 2) + (size_t)BLOCK_BYTES * 8;
-            if (int rc = grow(e->d_iqbits, e->iqbits_cap, (n_samples + 7) / 8, e->stream)) return rc;
+            if (int rc = e->d_iqbits.grow((n_samples + 7) / 8, e->stream)) return rc;
             IqConv cv = cap.iq;
             const size_t avail = cap.iq_total > cap.iq_first ? cap.iq_total - cap.iq_first : 0;
             if (int rc = iq8_to_bits_enqueue(e, cap.d_src, std::min(n_samples, avail), cv, cap.iq_first, e->d_iqbits)) return rc;
@@ -505,14 +463,14 @@ static int search_core(gpsacq_engine* e, const Capture& cap_in, size_t n_blocks,
     if (n_blocks > 0x7fffffffu) return fail(GPSACQ_ERR_ARG, "batch too large: %zu blocks", n_blocks);
     if (n_tasks * (size_t)e->ndop > 0x7fffff00u) return fail(GPSACQ_ERR_ARG, "batch too large: %zu tasks x %d bins", n_tasks, e->ndop);
     if (n_blocks * (size_t)e->sub > 0x7fffffffu) return fail(GPSACQ_ERR_ARG, "batch too large: %zu blocks x %d sub-bin spectra", n_blocks, e->sub);
-    if (int rc = grow(e->d_dpp, e->dpp_cap, n_blocks * (size_t)e->sub, e->stream, (size_t)NPOLY * M_SUB * sizeof(cf))) return rc;
+    if (int rc = e->d_dpp.grow(n_blocks * (size_t)e->sub, e->stream, (size_t)NPOLY * M_SUB * sizeof(cf))) return rc;
     if (!d_cells) {
-        if (int rc = grow(e->d_cells, e->cell_cap, n_tasks * (size_t)e->ndop, e->stream)) return rc;
+        if (int rc = e->d_cells.grow(n_tasks * (size_t)e->ndop, e->stream)) return rc;
         d_cells = e->d_cells;
     }
     if (int rc = prepare_tasks(e, h_tasks, d_user_tasks, n_blocks, n_tasks, cap.d_src, stride)) return rc;
 
-    hipEvent_t* ev = e->ev[e->searches % gpsacq_engine::kTimingRing];
+    hipEvent_t* ev = e->ring[e->searches % gpsacq_engine::kTimingRing].ev;
     HIPCHK(hipEventRecord(ev[0], e->stream));
     if (cap.iq8 && cap.multibit) {
         // multi-bit path: the real-IF value of every sample as a float (same arithmetic as the 1-bit converter, iq_convert.hpp),
@@ -522,7 +480,7 @@ static int search_core(gpsacq_engine* e, const Capture& cap_in, size_t n_blocks,
         const size_t avail = cap.iq_total > cap.iq_first ? cap.iq_total - cap.iq_first : 0;
         const size_t n_samples = std::min(want, avail);
         if (n_samples < want) return fail(GPSACQ_ERR_ARG, "multi-bit path: the capture ends inside the batch (%zu of %zu samples)", n_samples, want);
-        if (int rc = grow(e->d_fsamp, e->fsamp_cap, n_blocks * (size_t)e->sub * N_FFT * 2, e->stream)) return rc;  // [block][sub-bin copy][40000] complex
+        if (int rc = e->d_fsamp.grow(n_blocks * (size_t)e->sub * N_FFT * 2, e->stream)) return rc;  // [block][sub-bin copy][40000] complex
         IqArgs ia{};
         ia.iq = cap.d_src;
         ia.bits = nullptr;
@@ -558,7 +516,7 @@ static int search_core(gpsacq_engine* e, const Capture& cap_in, size_t n_blocks,
     ca.acc_step = e->acc_step;
     ca.n_spec = (int)n_blocks;
     ca.creep = 0.f;
-    ca.n_code = GPSACQ_NUM_SATS + (int)e->patch_cap;
+    ca.n_code = GPSACQ_NUM_SATS + (int)e->d_patch_blocks.cap;
     ca.sub = e->sub;
     ca.dstride = e->dstride;
     if (e->block_align && e->n_acc > 1) {
@@ -583,7 +541,7 @@ static int search_core(gpsacq_engine* e, const Capture& cap_in, size_t n_blocks,
         // 0.4 GB, a 2048-task batch would otherwise ask for 27 GB); a single task's points always go together.
         const size_t per_task = (size_t)e->ndop * (size_t)e->nlags;
         const size_t chunk_tasks = std::max<size_t>(1, std::min(n_tasks, kPdumpBytes / sizeof(float) / per_task));
-        if (int rc = grow(e->d_pdump, e->pdump_cap, chunk_tasks * per_task, e->stream)) return rc;
+        if (int rc = e->d_pdump.grow(chunk_tasks * per_task, e->stream)) return rc;
         if (e->creep_comp) ca.creep = (float)((double)e->acc_step * block_samples * (e->p.fs / N_FFT * e->dstride / e->sub) / 1575.42e6);
         ca.pdump = e->d_pdump;
         // cells start as zeros: a task the kernel rejects (device task list out of range) leaves max_i = -1 there, which the
@@ -604,7 +562,7 @@ static int search_core(gpsacq_engine* e, const Capture& cap_in, size_t n_blocks,
         }
     } else {
         const size_t n_cells = n_tasks * (size_t)e->ndop;
-        if (int rc = grow(e->d_parts, e->parts_cap, n_cells * (size_t)n_pass, e->stream)) return rc;
+        if (int rc = e->d_parts.grow(n_cells * (size_t)n_pass, e->stream)) return rc;
         for (int p = 0; p < n_pass; ++p) {
             ca.m0 = p * MC_MAX;
             ca.cells = e->d_parts + (size_t)p * n_cells;
@@ -682,13 +640,12 @@ extern "C" int gpsacq_search_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input
 static int search_host(gpsacq_engine* e, Capture cap, const void* host, size_t nbytes, size_t n_blocks, const gpsacq_task* tasks,
                        size_t n_tasks, gpsacq_cell* cells, gpsacq_peak* peaks) {
     HIPCHK(hipSetDevice(e->p.device));
-    uint8_t*& dbuf = cap.iq8 ? e->d_iq : e->d_bits;
-    size_t& dcap = cap.iq8 ? e->iq_cap : e->bits_cap;
-    if (int rc = grow(dbuf, dcap, nbytes + 16, e->stream)) return rc;
+    Scratch<uint8_t>& dbuf = cap.iq8 ? e->d_iq : e->d_bits;
+    if (int rc = dbuf.grow(nbytes + 16, e->stream)) return rc;
     HIPCHK(hipMemcpyAsync(dbuf, host, nbytes, hipMemcpyHostToDevice, e->stream));
     cap.d_src = dbuf;
-    if (int rc = grow(e->d_cells, e->cell_cap, n_tasks * (size_t)e->ndop, e->stream)) return rc;
-    if (int rc = grow(e->d_peaks, e->peak_cap, n_tasks, e->stream)) return rc;
+    if (int rc = e->d_cells.grow(n_tasks * (size_t)e->ndop, e->stream)) return rc;
+    if (int rc = e->d_peaks.grow(n_tasks, e->stream)) return rc;
     if (int rc = search_core(e, cap, n_blocks, tasks, nullptr, n_tasks, e->d_cells, e->d_peaks)) return rc;
     if (cells) HIPCHK(hipMemcpyAsync(cells, e->d_cells, n_tasks * (size_t)e->ndop * sizeof(Cell), hipMemcpyDeviceToHost, e->stream));
     if (peaks) HIPCHK(hipMemcpyAsync(peaks, e->d_peaks, n_tasks * sizeof(Peak), hipMemcpyDeviceToHost, e->stream));
@@ -750,30 +707,24 @@ extern "C" uint8_t* gpsacq_pipe_buffer(gpsacq_engine* e, int slot, size_t nbytes
         fail(GPSACQ_ERR_ARG, "gpsacq_pipe_buffer: slot %d has a search in flight (collect it first)", slot);
         return nullptr;
     }
-    if (nbytes > sl->h_cap) {
+    if (nbytes > sl->h_bytes) {
         // everything a batch of this size needs, once: pinned staging, its device copy, and peak arrays for the most blocks
         // nbytes can hold (a block is at least 5000 bytes) -- submits then allocate nothing
         if (sl->h_in) (void)hipHostFree(sl->h_in);
-        if (sl->d_in) (void)hipFree(sl->d_in);
-        if (sl->d_peaks) (void)hipFree(sl->d_peaks);
         if (sl->h_peaks) (void)hipHostFree(sl->h_peaks);
         sl->h_in = nullptr;
-        sl->d_in = nullptr;
-        sl->d_peaks = nullptr;
         sl->h_peaks = nullptr;
-        sl->h_cap = sl->d_cap = sl->peak_cap = 0;
+        sl->h_bytes = 0;
         const size_t max_blocks = nbytes / (size_t)USED_BYTES + 1;
         hipError_t he = hipHostMalloc((void**)&sl->h_in, nbytes, hipHostMallocDefault);
-        if (he == hipSuccess) he = hipMalloc((void**)&sl->d_in, nbytes + 16);
-        if (he == hipSuccess) he = hipMalloc((void**)&sl->d_peaks, max_blocks * sizeof(Peak));
+        if (he == hipSuccess) he = sl->d_in.alloc(nbytes + 16);
+        if (he == hipSuccess) he = sl->d_peaks.alloc(max_blocks);
         if (he == hipSuccess) he = hipHostMalloc((void**)&sl->h_peaks, max_blocks * sizeof(Peak), hipHostMallocDefault);
         if (he != hipSuccess) {
             fail(he == hipErrorOutOfMemory ? GPSACQ_ERR_NOMEM : GPSACQ_ERR_DEVICE, "gpsacq_pipe_buffer(%zu bytes): %s", nbytes, hipGetErrorString(he));
             return nullptr;
         }
-        sl->h_cap = nbytes;
-        sl->d_cap = nbytes + 16;
-        sl->peak_cap = max_blocks;
+        sl->h_bytes = nbytes;
     }
     return sl->h_in;
 }
@@ -792,9 +743,9 @@ extern "C" int gpsacq_pipe_submit(gpsacq_engine* e, int slot, size_t n_blocks, s
     } else {
         nbytes = (n_blocks - 1) * stride + (stride < (size_t)BLOCK_BYTES ? stride : (size_t)BLOCK_BYTES);
     }
-    if (!sl->h_in || nbytes > sl->h_cap) return fail(GPSACQ_ERR_ARG, "gpsacq_pipe_submit: slot %d holds %zu bytes, the batch needs %zu", slot, sl->h_cap, nbytes);
-    if (nbytes + 16 > sl->d_cap || n_blocks > sl->peak_cap)
-        return fail(GPSACQ_ERR_ARG, "gpsacq_pipe_submit: slot %d was sized for %zu bytes / %zu blocks", slot, sl->h_cap, sl->peak_cap);
+    if (!sl->h_in || nbytes > sl->h_bytes) return fail(GPSACQ_ERR_ARG, "gpsacq_pipe_submit: slot %d holds %zu bytes, the batch needs %zu", slot, sl->h_bytes, nbytes);
+    if (nbytes + 16 > sl->d_in.cap || n_blocks > sl->d_peaks.cap)
+        return fail(GPSACQ_ERR_ARG, "gpsacq_pipe_submit: slot %d was sized for %zu bytes / %zu blocks", slot, sl->h_bytes, sl->d_peaks.cap);
     HIPCHK(hipMemcpyAsync(sl->d_in, sl->h_in, nbytes, hipMemcpyHostToDevice, e->copy_stream));
     HIPCHK(hipEventRecord(sl->uploaded, e->copy_stream));
     HIPCHK(hipStreamWaitEvent(e->stream, sl->uploaded, 0));
@@ -823,8 +774,8 @@ extern "C" int gpsacq_pipe_collect(gpsacq_engine* e, int slot, const gpsacq_peak
 extern "C" int gpsacq_reserve(gpsacq_engine* e, size_t n_blocks) {
     if (!e || n_blocks == 0) return fail(GPSACQ_ERR_ARG, "gpsacq_reserve: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_dpp, e->dpp_cap, n_blocks * (size_t)e->sub, e->stream, (size_t)NPOLY * M_SUB * sizeof(cf))) return rc;
-    if (int rc = grow(e->d_cells, e->cell_cap, n_blocks * (size_t)e->ndop, e->stream)) return rc;
+    if (int rc = e->d_dpp.grow(n_blocks * (size_t)e->sub, e->stream, (size_t)NPOLY * M_SUB * sizeof(cf))) return rc;
+    if (int rc = e->d_cells.grow(n_blocks * (size_t)e->ndop, e->stream)) return rc;
     if (e->n_acc == 1) {
         // the reference schedule for the largest batch, built once: every shorter batch (the front end's 1, 2, 4, ... run ramp)
         // is a prefix of it and enqueues without waiting for the stream
@@ -832,7 +783,7 @@ extern "C" int gpsacq_reserve(gpsacq_engine* e, size_t n_blocks) {
             if (int rc = build_default_schedule(e, n_blocks)) return rc;
     } else {
         e->sched_valid = false;  // (never valid in the non-coherent mode; the buffer may be about to move)
-        if (int rc = grow(e->d_tasks, e->task_cap, n_blocks, e->stream)) return rc;
+        if (int rc = e->d_tasks.grow(n_blocks, e->stream)) return rc;
     }
     return GPSACQ_OK;
 }
@@ -899,15 +850,13 @@ extern "C" int gpsacq_set_doppler_step(gpsacq_engine* e, double step_hz) {
         HIPCHK(hipStreamSynchronize(e->stream));
         std::vector<cf> tn, lutc;
         forward_tables(sub, tn, &lutc);
-        cf *ntn = nullptr, *nlut = nullptr;
-        HIPCHK(hipMalloc((void**)&ntn, tn.size() * sizeof(cf)));
-        HIPCHK(hipMalloc((void**)&nlut, lutc.size() * sizeof(cf)));
+        Scratch<cf> ntn, nlut;  // leave with the old tables
+        HIPCHK(ntn.alloc(tn.size()));
+        HIPCHK(nlut.alloc(lutc.size()));
         HIPCHK(hipMemcpy(ntn, tn.data(), tn.size() * sizeof(cf), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(nlut, lutc.data(), lutc.size() * sizeof(cf), hipMemcpyHostToDevice));
-        HIPCHK(hipFree(e->d_tn));
-        HIPCHK(hipFree(e->d_lutc));
-        e->d_tn = ntn;
-        e->d_lutc = nlut;
+        e->d_tn.swap(ntn);
+        e->d_lutc.swap(nlut);
     }
     e->sub = sub;
     e->dstride = dstride;
@@ -951,7 +900,7 @@ extern "C" int gpsacq_timing_ago(const gpsacq_engine* e, int n_back, gpsacq_timi
     if (n_back < 0 || n_back >= gpsacq_engine::kTimingRing || (long)n_back >= e->searches)
         return fail(GPSACQ_ERR_ARG, "no timing %d searches back (%ld searches so far, %d kept)", n_back, e->searches, gpsacq_engine::kTimingRing);
     const int slot = (int)((e->searches - 1 - n_back) % gpsacq_engine::kTimingRing);
-    const hipEvent_t* ev = e->ev[slot];
+    const hipEvent_t* ev = e->ring[slot].ev;
     HIPCHK(hipEventSynchronize(ev[3]));
     memset(t, 0, sizeof *t);
     HIPCHK(hipEventElapsedTime(&t->ms_total, ev[0], ev[3]));
@@ -988,11 +937,11 @@ extern "C" int gpsacq_generate_nav_range_device(gpsacq_engine* e, void* d_bits, 
         gs[i].carrier_phase = sats[i].carrier_phase_cycles;
     }
     if (n_sats > 0) {
-        if (int rc = grow(e->d_sats, e->sats_cap, (size_t)n_sats, e->stream)) return rc;
+        if (int rc = e->d_sats.grow((size_t)n_sats, e->stream)) return rc;
         HIPCHK(hipMemcpyAsync(e->d_sats, gs.data(), gs.size() * sizeof(GenSat), hipMemcpyHostToDevice, e->stream));
         if (nav) {
             const size_t nn = (size_t)n_sats * n_nav;
-            if (int rc = grow(e->d_nav, e->nav_cap, nn, e->stream)) return rc;
+            if (int rc = e->d_nav.grow(nn, e->stream)) return rc;
             HIPCHK(hipMemcpyAsync(e->d_nav, nav, nn, hipMemcpyHostToDevice, e->stream));
         }
         HIPCHK(hipStreamSynchronize(e->stream));  // gs goes out of scope
@@ -1025,7 +974,7 @@ extern "C" int gpsacq_generate_nav_range(gpsacq_engine* e, uint8_t* bits_out, si
                                          int n_sats, const int8_t* nav, int n_nav, float noise_sigma, uint64_t seed) {
     if (!e || !bits_out || n_bytes == 0) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_range: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_gen, e->gen_cap, n_bytes, e->stream)) return rc;
+    if (int rc = e->d_gen.grow(n_bytes, e->stream)) return rc;
     if (int rc = gpsacq_generate_nav_range_device(e, e->d_gen, n_bytes, first_sample, sats, n_sats, nav, n_nav, noise_sigma, seed, 0)) return rc;
     HIPCHK(hipMemcpyAsync(bits_out, e->d_gen, n_bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -1053,7 +1002,7 @@ extern "C" int gpsacq_generate_sig(gpsacq_engine* e, int prn, const int8_t* data
     for (int i = 0; i < n_data_bits; ++i)
         if (data_bits[i] != 1 && data_bits[i] != -1) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_sig: navigation bit %d is %d, not +-1", i, data_bits[i]);
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_gen, e->gen_cap, n_bytes + (size_t)n_data_bits, e->stream)) return rc;
+    if (int rc = e->d_gen.grow(n_bytes + (size_t)n_data_bits, e->stream)) return rc;
     int8_t* d_data = (int8_t*)(e->d_gen + n_bytes);
     HIPCHK(hipMemcpyAsync(d_data, data_bits, (size_t)n_data_bits, hipMemcpyHostToDevice, e->stream));
     const double ca_rate = 1.023e6 * 8, fc = ca_rate / 4;  // gps_sig_gen.m:8-9,14,34
@@ -1091,11 +1040,11 @@ extern "C" int gpsacq_generate_sig_tx(gpsacq_engine* e, int prn, const int8_t* d
         if (data_bits[i] != 1 && data_bits[i] != -1) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_sig_tx: navigation bit %d is %d, not +-1", i, data_bits[i]);
     HIPCHK(hipSetDevice(e->p.device));
     const size_t out_bytes = 2 * n_samples, data_off = (out_bytes + 15) & ~(size_t)15;
-    if (int rc = grow(e->d_gen, e->gen_cap, data_off + (size_t)n_data_bits, e->stream)) return rc;
+    if (int rc = e->d_gen.grow(data_off + (size_t)n_data_bits, e->stream)) return rc;
     int8_t* d_data = (int8_t*)(e->d_gen + data_off);
     HIPCHK(hipMemcpyAsync(d_data, data_bits, (size_t)n_data_bits, hipMemcpyHostToDevice, e->stream));
     SigTxArgs a{};
-    a.iq = (int8_t*)e->d_gen;
+    a.iq = (int8_t*)e->d_gen.p;
     a.n_samples = n_samples;
     a.first_sample = (long long)first_sample;
     a.data = d_data;
@@ -1125,7 +1074,7 @@ int iq8_to_bits_enqueue(gpsacq_engine* e, const uint8_t* d_iq, size_t n_samples,
 
 // exact integer sums of I and Q over n_samples of a device buffer, added to sums[0..1]
 static int iq8_sums_device(gpsacq_engine* e, const uint8_t* d_iq, size_t n_samples, bool is_signed, long long sums[2]) {
-    if (!e->d_sums) HIPCHK(hipMalloc((void**)&e->d_sums, 2 * sizeof(unsigned long long)));
+    if (!e->d_sums) HIPCHK(e->d_sums.alloc(2));
     HIPCHK(hipMemsetAsync(e->d_sums, 0, 2 * sizeof(unsigned long long), e->stream));
     launch_iq_sums(d_iq, n_samples, is_signed, e->d_sums, e->stream);
     HIPCHK(hipGetLastError());
@@ -1167,7 +1116,7 @@ extern "C" int gpsacq_iq8_accumulate_sums(gpsacq_engine* e, const void* iq, size
     if (!e || !iq || !sums || n_samples == 0) return fail(GPSACQ_ERR_ARG, "gpsacq_iq8_accumulate_sums: bad argument");
     if (format != GPSACQ_IQ_U8 && format != GPSACQ_IQ_S8) return fail(GPSACQ_ERR_ARG, "unknown IQ format %d", format);
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_iq, e->iq_cap, 2 * n_samples + 16, e->stream)) return rc;
+    if (int rc = e->d_iq.grow(2 * n_samples + 16, e->stream)) return rc;
     HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * n_samples, hipMemcpyHostToDevice, e->stream));
     long long h[2] = {0, 0};
     if (int rc = iq8_sums_device(e, e->d_iq, n_samples, format == GPSACQ_IQ_S8, h)) return rc;
@@ -1181,8 +1130,8 @@ extern "C" int gpsacq_iq8_to_bits(gpsacq_engine* e, const void* iq, size_t n_sam
     if (!e || !iq || !bits_out || n_samples == 0) return fail(GPSACQ_ERR_ARG, "gpsacq_iq8_to_bits: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
     const size_t n_bytes = (n_samples + 7) / 8;
-    if (int rc = grow(e->d_iq, e->iq_cap, 2 * n_samples + 16, e->stream)) return rc;
-    if (int rc = grow(e->d_iqbits, e->iqbits_cap, n_bytes, e->stream)) return rc;
+    if (int rc = e->d_iq.grow(2 * n_samples + 16, e->stream)) return rc;
+    if (int rc = e->d_iqbits.grow(n_bytes, e->stream)) return rc;
     HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * n_samples, hipMemcpyHostToDevice, e->stream));
     if (int rc = gpsacq_iq8_to_bits_device(e, e->d_iq, n_samples, format, remove_dc, mix_hz, fs, e->d_iqbits, 0)) return rc;
     HIPCHK(hipMemcpyAsync(bits_out, e->d_iqbits, n_bytes, hipMemcpyDeviceToHost, e->stream));
@@ -1245,11 +1194,11 @@ extern "C" int gpsacq_generate_iq8_range_device(gpsacq_engine* e, void* d_iq, si
         gs[i].carrier_phase = sats[i].carrier_phase_cycles;
     }
     if (n_sats > 0) {
-        if (int rc = grow(e->d_sats, e->sats_cap, (size_t)n_sats, e->stream)) return rc;
+        if (int rc = e->d_sats.grow((size_t)n_sats, e->stream)) return rc;
         HIPCHK(hipMemcpyAsync(e->d_sats, gs.data(), gs.size() * sizeof(GenSat), hipMemcpyHostToDevice, e->stream));
         if (nav) {
             const size_t nn = (size_t)n_sats * n_nav;
-            if (int rc = grow(e->d_nav, e->nav_cap, nn, e->stream)) return rc;
+            if (int rc = e->d_nav.grow(nn, e->stream)) return rc;
             HIPCHK(hipMemcpyAsync(e->d_nav, nav, nn, hipMemcpyHostToDevice, e->stream));
         }
         HIPCHK(hipStreamSynchronize(e->stream));  // gs goes out of scope
@@ -1278,7 +1227,7 @@ extern "C" int gpsacq_generate_iq8_range(gpsacq_engine* e, void* iq_out, size_t 
                                          uint64_t seed) {
     if (!e || !iq_out || n_samples == 0) return fail(GPSACQ_ERR_ARG, "gpsacq_generate_iq8_range: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_gen, e->gen_cap, 2 * n_samples, e->stream)) return rc;
+    if (int rc = e->d_gen.grow(2 * n_samples, e->stream)) return rc;
     if (int rc = gpsacq_generate_iq8_range_device(e, e->d_gen, n_samples, first_sample, format, if_hz, scale, sats, n_sats, nav, n_nav, noise_sigma, seed, 0))
         return rc;
     HIPCHK(hipMemcpyAsync(iq_out, e->d_gen, 2 * n_samples, hipMemcpyDeviceToHost, e->stream));
@@ -1302,8 +1251,8 @@ static void pp_to_natural(const std::vector<cf>& pp, long row, int off, bool con
 extern "C" int gpsacq_sample_spectrum(gpsacq_engine* e, const uint8_t* block, float* out) {
     if (!e || !block || !out) return fail(GPSACQ_ERR_ARG, "gpsacq_sample_spectrum: null argument");
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_bits, e->bits_cap, (size_t)BLOCK_BYTES, e->stream)) return rc;
-    if (int rc = grow(e->d_dpp, e->dpp_cap, (size_t)1, e->stream, (size_t)NPOLY * M_SUB * sizeof(cf))) return rc;
+    if (int rc = e->d_bits.grow((size_t)BLOCK_BYTES, e->stream)) return rc;
+    if (int rc = e->d_dpp.grow((size_t)1, e->stream, (size_t)NPOLY * M_SUB * sizeof(cf))) return rc;
     HIPCHK(hipMemcpyAsync(e->d_bits, block, BLOCK_BYTES, hipMemcpyHostToDevice, e->stream));
     // one spectrum (sub-bin offset 0) even when a finer Doppler grid is active: d_dpp is grown for exactly that
     if (int rc = run_forward(e, FWD_BITS, e->d_bits, BLOCK_BYTES, 1, e->d_dpp, (size_t)NPOLY * M_SUB, M_SUB, 0, true, 1)) return rc;

@@ -30,6 +30,45 @@
 
 using namespace acq;
 
+// ---- the shapes the entry points below are made of --------------------------------------------------------------------------
+// n elements of a host array into a buffer of the engine, grown to hold them, on the engine's stream
+template <class T> static int upload(gpsacq_engine* e, Scratch<T>& d, const T* src, size_t n) {
+    if (int rc = d.grow(n, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, e->stream));
+    return GPSACQ_OK;
+}
+// ... and back, where the caller wants them (dst may be NULL); the caller waits for the stream after its last one
+template <class T> static int download(gpsacq_engine* e, T* dst, const Scratch<T>& d, size_t n) {
+    if (dst) HIPCHK(hipMemcpyAsync(dst, d, n * sizeof(T), hipMemcpyDeviceToHost, e->stream));
+    return GPSACQ_OK;
+}
+// an optional output of a chain: the caller's buffer, or the engine's grown to n elements
+template <class T> static int or_own(gpsacq_engine* e, void*& d, Scratch<T>& own, size_t n) {
+    if (d) return GPSACQ_OK;
+    if (int rc = own.grow(n, e->stream)) return rc;
+    d = own.p;
+    return GPSACQ_OK;
+}
+// the time of a one-kernel stage: waited for where it ran, exactly 0 where it did not
+static int stage_ms(const Stages<2>& t, float* ms) {
+    float v = 0.f;
+    if (t.ran()) {
+        if (int rc = t.wait()) return rc;
+        if (int rc = t.elapsed(0, 1, &v)) return rc;
+    }
+    if (ms) *ms = v;
+    return GPSACQ_OK;
+}
+// the records of a host-buffer form into e->d_obs_rec: the rows keep their stride; only the records that exist travel
+static int upload_records(gpsacq_engine* e, const gpsacq_track_record* records, int max_epochs, const int32_t* n_epochs, int n_chans) {
+    if (int rc = e->d_obs_rec.grow((size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
+    for (int c = 0; c < n_chans; ++c)
+        if (n_epochs[c] > 0)
+            HIPCHK(hipMemcpyAsync(e->d_obs_rec + (size_t)c * max_epochs, records + (size_t)c * max_epochs,
+                                  (size_t)n_epochs[c] * sizeof(gpsacq_track_record), hipMemcpyHostToDevice, e->stream));
+    return GPSACQ_OK;
+}
+
 // ---- ephemeris ---------------------------------------------------------------------------------------------------------------
 namespace {
 constexpr double GPS_PI = 3.1415926535898;
@@ -113,10 +152,7 @@ static int nav_upload_eph(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_e
         d.valid = in_week && gpsacq_ephemeris_valid(&s);
         d.reserved = 0;
     }
-    if (int rc = grow(e->d_nav_eph, e->nav_eph_cap, (size_t)n_eph, e->stream)) return rc;
-    // pageable source: the copy has left `tab` when the call returns
-    HIPCHK(hipMemcpyAsync(e->d_nav_eph, tab.data(), tab.size() * sizeof(NavEph), hipMemcpyHostToDevice, e->stream));
-    return GPSACQ_OK;
+    return upload(e, e->d_nav_eph, tab.data(), tab.size());  // pageable source: the copy has left `tab` when the call returns
 }
 
 static int nav_check(const char* who, const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* obs, size_t n, const void* out) {
@@ -146,11 +182,10 @@ extern "C" int gpsacq_sat_states(gpsacq_engine* e, const gpsacq_ephemeris* eph, 
     if (int rc = nav_check("gpsacq_sat_states", e, eph, n_eph, obs, n_obs, out)) return rc;
     if (int rc = nav_check_weights("gpsacq_sat_states", obs, n_obs)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_nav_state.grow(n_obs, e->stream)) return rc;
+    if (int rc = upload(e, e->d_nav_obs, obs, n_obs)) return rc;
     if (int rc = gpsacq_sat_states_device(e, eph, n_eph, e->d_nav_obs, n_obs, e->d_nav_state, 0)) return rc;
-    HIPCHK(hipMemcpyAsync(out, e->d_nav_state, n_obs * sizeof(gpsacq_sat_state), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, out, e->d_nav_state, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -163,17 +198,13 @@ extern "C" int gpsacq_fix_batch_device(gpsacq_engine* e, const gpsacq_ephemeris*
     const size_t n_obs = n_fix * (size_t)sats_per_fix;
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
-    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
-    for (auto& ev : e->nav_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
-    e->nav_timed = false;
-    HIPCHK(hipEventRecord(e->nav_ev[0], e->stream));
+    if (int rc = e->d_nav_state.grow(n_obs, e->stream)) return rc;
+    if (int rc = e->nav_t.begin(e->stream)) return rc;
     launch_sat_state(SatStateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_nav_state}, e->stream);
-    HIPCHK(hipEventRecord(e->nav_ev[1], e->stream));
+    if (int rc = e->nav_t.mark(1, e->stream)) return rc;
     launch_fix(FixArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, e->d_nav_state, n_fix, sats_per_fix, (gpsacq_fix*)d_out}, e->stream);
-    HIPCHK(hipEventRecord(e->nav_ev[2], e->stream));
-    HIPCHK(hipGetLastError());
-    e->nav_timed = true;
+    if (int rc = e->nav_t.mark(2, e->stream)) return rc;
+    if (int rc = e->nav_t.finish()) return rc;
     if (sync) HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -186,22 +217,20 @@ extern "C" int gpsacq_fix_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, i
     const size_t n_obs = n_fix * (size_t)sats_per_fix;
     if (int rc = nav_check_weights("gpsacq_fix_batch", obs, n_obs)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_nav_fix.grow(n_fix, e->stream)) return rc;
+    if (int rc = upload(e, e->d_nav_obs, obs, n_obs)) return rc;
     if (int rc = gpsacq_fix_batch_device(e, eph, n_eph, e->d_nav_obs, n_fix, sats_per_fix, e->d_nav_fix, 0)) return rc;
-    HIPCHK(hipMemcpyAsync(out, e->d_nav_fix, n_fix * sizeof(gpsacq_fix), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, out, e->d_nav_fix, n_fix)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
 
 extern "C" int gpsacq_fix_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* fix_ms) {
-    if (!e || !e->nav_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_last_ms: no gpsacq_fix_batch call on this engine");
+    if (!e || !e->nav_t.ran()) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_last_ms: no gpsacq_fix_batch call on this engine");
     HIPCHK(hipSetDevice(e->p.device));
-    HIPCHK(hipEventSynchronize(e->nav_ev[2]));
-    if (sat_state_ms) HIPCHK(hipEventElapsedTime(sat_state_ms, e->nav_ev[0], e->nav_ev[1]));
-    if (fix_ms) HIPCHK(hipEventElapsedTime(fix_ms, e->nav_ev[1], e->nav_ev[2]));
-    return GPSACQ_OK;
+    if (int rc = e->nav_t.wait()) return rc;
+    if (int rc = e->nav_t.elapsed(0, 1, sat_state_ms)) return rc;
+    return e->nav_t.elapsed(1, 2, fix_ms);
 }
 
 // ---- observables (obs_kernels.hip) ------------------------------------------------------------------------------------------
@@ -237,7 +266,7 @@ static int obs_check(const char* who, const gpsacq_engine* e, const void* record
     return records_check(who, e, records, max_epochs, n_epochs, chans, n_chans, first_rx_sample, rx_step, n_fix);
 }
 
-// the call's channels as the kernels read them into e->d_obs_chan, then k_code_pos between obs_ev[0] and obs_ev[1]
+// the call's channels as the kernels read them into e->d_obs_chan, then k_code_pos as the first stage of obs_t
 static int code_pos_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
                             const gpsacq_time_tag* tags, int n_chans) {
     ObsChan tab[GPSACQ_FIX_MAX_SATS];
@@ -248,16 +277,13 @@ static int code_pos_enqueue(gpsacq_engine* e, const void* d_records, int max_epo
         d.first_epoch = (int32_t)((uint32_t)chans[c].epoch - (uint32_t)n_epochs[c]);
         d.tag_epoch = tags[c].epoch, d.tag_ms = tags[c].ms, d.tag_eph = tags[c].eph, d.tag_valid = tags[c].valid;
     }
-    if (int rc = grow(e->d_obs_chan, e->obs_chan_cap, (size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
-    if (int rc = grow(e->d_obs_pos, e->obs_pos_cap, (size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
+    if (int rc = e->d_obs_chan.grow((size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
+    if (int rc = e->d_obs_pos.grow((size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
     // pageable source: the copy has left `tab` when the call returns
     HIPCHK(hipMemcpyAsync(e->d_obs_chan, tab, (size_t)n_chans * sizeof(ObsChan), hipMemcpyHostToDevice, e->stream));
-    for (auto& ev : e->obs_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
-    e->obs_timed = false;
-    HIPCHK(hipEventRecord(e->obs_ev[0], e->stream));
+    if (int rc = e->obs_t.begin(e->stream)) return rc;
     launch_code_pos(CodePosArgs{e->d_obs_chan, (const gpsacq_track_record*)d_records, max_epochs, e->d_obs_pos}, n_chans, e->stream);
-    HIPCHK(hipEventRecord(e->obs_ev[1], e->stream));
+    if (int rc = e->obs_t.mark(1, e->stream)) return rc;
     return GPSACQ_OK;
 }
 
@@ -268,9 +294,8 @@ static int obs_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, 
     launch_observe(ObserveArgs{e->d_obs_chan, (const gpsacq_track_record*)d_records, e->d_obs_pos, max_epochs, n_chans, first_rx_sample, rx_step,
                                n_fix, (gpsacq_obs*)d_obs},
                    e->stream);
-    HIPCHK(hipEventRecord(e->obs_ev[2], e->stream));
-    HIPCHK(hipGetLastError());
-    e->obs_timed = true;
+    if (int rc = e->obs_t.mark(2, e->stream)) return rc;
+    if (int rc = e->obs_t.finish()) return rc;
     return GPSACQ_OK;
 }
 
@@ -292,14 +317,10 @@ extern "C" int gpsacq_observables(gpsacq_engine* e, const gpsacq_track_record* r
     if (!obs) return fail(GPSACQ_ERR_ARG, "gpsacq_observables: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
     const size_t n_obs = n_fix * (size_t)n_chans;
-    if (int rc = grow(e->d_obs_rec, e->obs_rec_cap, (size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
-    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-    for (int c = 0; c < n_chans; ++c)  // the rows keep their stride; only the records that exist travel
-        if (n_epochs[c] > 0)
-            HIPCHK(hipMemcpyAsync(e->d_obs_rec + (size_t)c * max_epochs, records + (size_t)c * max_epochs,
-                                  (size_t)n_epochs[c] * sizeof(gpsacq_track_record), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_nav_obs.grow(n_obs, e->stream)) return rc;
+    if (int rc = upload_records(e, records, max_epochs, n_epochs, n_chans)) return rc;
     if (int rc = obs_enqueue(e, e->d_obs_rec, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, e->d_nav_obs)) return rc;
-    HIPCHK(hipMemcpyAsync(obs, e->d_nav_obs, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, obs, e->d_nav_obs, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -310,21 +331,17 @@ extern "C" int gpsacq_fix_track_device(gpsacq_engine* e, const gpsacq_ephemeris*
     if (int rc = obs_check("gpsacq_fix_track", e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix)) return rc;
     if (!eph || n_eph <= 0 || !d_fix) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_track: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
-    if (!d_obs) {
-        if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_fix * (size_t)n_chans, e->stream)) return rc;
-        d_obs = e->d_nav_obs;
-    }
+    if (int rc = or_own(e, d_obs, e->d_nav_obs, n_fix * (size_t)n_chans)) return rc;
     if (int rc = obs_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, d_obs)) return rc;
     return gpsacq_fix_batch_device(e, eph, n_eph, d_obs, n_fix, n_chans, d_fix, sync);
 }
 
 extern "C" int gpsacq_observables_last_ms(const gpsacq_engine* e, float* code_pos_ms, float* observe_ms) {
-    if (!e || !e->obs_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_observables_last_ms: no gpsacq_observables call on this engine");
+    if (!e || !e->obs_t.ran()) return fail(GPSACQ_ERR_ARG, "gpsacq_observables_last_ms: no gpsacq_observables call on this engine");
     HIPCHK(hipSetDevice(e->p.device));
-    HIPCHK(hipEventSynchronize(e->obs_ev[2]));
-    if (code_pos_ms) HIPCHK(hipEventElapsedTime(code_pos_ms, e->obs_ev[0], e->obs_ev[1]));
-    if (observe_ms) HIPCHK(hipEventElapsedTime(observe_ms, e->obs_ev[1], e->obs_ev[2]));
-    return GPSACQ_OK;
+    if (int rc = e->obs_t.wait()) return rc;
+    if (int rc = e->obs_t.elapsed(0, 1, code_pos_ms)) return rc;
+    return e->obs_t.elapsed(1, 2, observe_ms);
 }
 
 // ---- carrier observables (obs_kernels.hip) ---------------------------------------------------------------------------------
@@ -337,21 +354,18 @@ static int rate_check(const char* who, const gpsacq_engine* e, const void* recor
     return GPSACQ_OK;
 }
 
-// the call's channels as the carrier kernels read them into e->d_rate_chan, then k_carrier_acc between rate_ev[0] and rate_ev[1]
+// the call's channels as the carrier kernels read them into e->d_rate_chan, then k_carrier_acc as the first stage of rate_t
 static int carrier_acc_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs, const int32_t* n_epochs, const gpsacq_track_chan* chans,
                                const uint32_t* nom_words, int n_chans) {
     RateChan tab[GPSACQ_FIX_MAX_SATS];
     for (int c = 0; c < n_chans; ++c) tab[c] = RateChan{chans[c].next_sample, n_epochs[c], nom_words[c]};
-    if (int rc = grow(e->d_rate_chan, e->rate_chan_cap, (size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
-    if (int rc = grow(e->d_rate_acc, e->rate_acc_cap, (size_t)n_chans * ((size_t)max_epochs + 1), e->stream)) return rc;
+    if (int rc = e->d_rate_chan.grow((size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
+    if (int rc = e->d_rate_acc.grow((size_t)n_chans * ((size_t)max_epochs + 1), e->stream)) return rc;
     // pageable source: the copy has left `tab` when the call returns
     HIPCHK(hipMemcpyAsync(e->d_rate_chan, tab, (size_t)n_chans * sizeof(RateChan), hipMemcpyHostToDevice, e->stream));
-    for (auto& ev : e->rate_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
-    e->rate_timed = false;
-    HIPCHK(hipEventRecord(e->rate_ev[0], e->stream));
+    if (int rc = e->rate_t.begin(e->stream)) return rc;
     launch_carrier_acc(CarrierAccArgs{e->d_rate_chan, (const gpsacq_track_record*)d_records, max_epochs, e->d_rate_acc}, n_chans, e->stream);
-    HIPCHK(hipEventRecord(e->rate_ev[1], e->stream));
+    if (int rc = e->rate_t.mark(1, e->stream)) return rc;
     return GPSACQ_OK;
 }
 
@@ -363,9 +377,8 @@ static int rate_enqueue(gpsacq_engine* e, const void* d_records, int max_epochs,
     launch_observe_rate(ObserveRateArgs{e->d_rate_chan, (const gpsacq_track_record*)d_records, e->d_rate_acc, max_epochs, n_chans, first_rx_sample,
                                         rx_step, avg_samples, e->p.fs, n_fix, (gpsacq_rate_obs*)d_rate_obs},
                         e->stream);
-    HIPCHK(hipEventRecord(e->rate_ev[2], e->stream));
-    HIPCHK(hipGetLastError());
-    e->rate_timed = true;
+    if (int rc = e->rate_t.mark(2, e->stream)) return rc;
+    if (int rc = e->rate_t.finish()) return rc;
     return GPSACQ_OK;
 }
 
@@ -388,14 +401,10 @@ extern "C" int gpsacq_rate_observables(gpsacq_engine* e, const gpsacq_track_reco
     if (!rate_obs) return fail(GPSACQ_ERR_ARG, "gpsacq_rate_observables: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
     const size_t n_obs = n_fix * (size_t)n_chans;
-    if (int rc = grow(e->d_obs_rec, e->obs_rec_cap, (size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
-    if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_obs, e->stream)) return rc;
-    for (int c = 0; c < n_chans; ++c)  // the rows keep their stride; only the records that exist travel
-        if (n_epochs[c] > 0)
-            HIPCHK(hipMemcpyAsync(e->d_obs_rec + (size_t)c * max_epochs, records + (size_t)c * max_epochs,
-                                  (size_t)n_epochs[c] * sizeof(gpsacq_track_record), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_rate_obs.grow(n_obs, e->stream)) return rc;
+    if (int rc = upload_records(e, records, max_epochs, n_epochs, n_chans)) return rc;
     if (int rc = rate_enqueue(e, e->d_obs_rec, max_epochs, n_epochs, chans, nom_words, n_chans, first_rx_sample, rx_step, n_fix, avg_samples, e->d_rate_obs)) return rc;
-    HIPCHK(hipMemcpyAsync(rate_obs, e->d_rate_obs, n_obs * sizeof(gpsacq_rate_obs), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, rate_obs, e->d_rate_obs, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -417,11 +426,10 @@ extern "C" int gpsacq_sat_rates(gpsacq_engine* e, const gpsacq_ephemeris* eph, i
     if (int rc = nav_check("gpsacq_sat_rates", e, eph, n_eph, obs, n_obs, out)) return rc;
     if (int rc = nav_check_weights("gpsacq_sat_rates", obs, n_obs)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_sat_rate, e->sat_rate_cap, n_obs, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_sat_rate.grow(n_obs, e->stream)) return rc;
+    if (int rc = upload(e, e->d_nav_obs, obs, n_obs)) return rc;
     if (int rc = gpsacq_sat_rates_device(e, eph, n_eph, e->d_nav_obs, n_obs, e->d_sat_rate, 0)) return rc;
-    HIPCHK(hipMemcpyAsync(out, e->d_sat_rate, n_obs * sizeof(gpsacq_sat_rate), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, out, e->d_sat_rate, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -440,19 +448,15 @@ static int vel_check(const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_
 static int vel_enqueue(gpsacq_engine* e, int n_eph, const void* d_obs, const void* d_rate_obs, const void* d_fixes, size_t n_fix,
                        int sats_per_fix, void* d_out) {
     const size_t n_obs = n_fix * (size_t)sats_per_fix;
-    if (int rc = grow(e->d_sat_rate, e->sat_rate_cap, n_obs, e->stream)) return rc;
-    for (auto& ev : e->vel_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
-    e->vel_timed = false;
-    HIPCHK(hipEventRecord(e->vel_ev[0], e->stream));
+    if (int rc = e->d_sat_rate.grow(n_obs, e->stream)) return rc;
+    if (int rc = e->vel_t.begin(e->stream)) return rc;
     launch_sat_state_rate(SatRateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_sat_rate}, e->stream);
-    HIPCHK(hipEventRecord(e->vel_ev[1], e->stream));
+    if (int rc = e->vel_t.mark(1, e->stream)) return rc;
     launch_vel(VelArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, (const gpsacq_rate_obs*)d_rate_obs, e->d_nav_state, e->d_sat_rate,
                        (const gpsacq_fix*)d_fixes, n_fix, sats_per_fix, (gpsacq_vel*)d_out},
                e->stream);
-    HIPCHK(hipEventRecord(e->vel_ev[2], e->stream));
-    HIPCHK(hipGetLastError());
-    e->vel_timed = true;
+    if (int rc = e->vel_t.mark(2, e->stream)) return rc;
+    if (int rc = e->vel_t.finish()) return rc;
     return GPSACQ_OK;
 }
 
@@ -462,7 +466,7 @@ extern "C" int gpsacq_vel_batch_device(gpsacq_engine* e, const gpsacq_ephemeris*
     const size_t n_obs = n_fix * (size_t)sats_per_fix;
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
-    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
+    if (int rc = e->d_nav_state.grow(n_obs, e->stream)) return rc;
     launch_sat_state(SatStateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_nav_state}, e->stream);
     if (int rc = vel_enqueue(e, n_eph, d_obs, d_rate_obs, d_fixes, n_fix, sats_per_fix, d_out)) return rc;
     if (sync) HIPCHK(hipStreamSynchronize(e->stream));
@@ -478,15 +482,12 @@ extern "C" int gpsacq_vel_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, i
         if (!(rate_obs[k].weight >= 0.0) || !std::isfinite(rate_obs[k].weight))
             return fail(GPSACQ_ERR_ARG, "gpsacq_vel_batch: rate observation %zu has weight %g (must be finite and >= 0)", k, rate_obs[k].weight);
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
-    if (int rc = grow(e->d_vel, e->vel_cap, n_fix, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_rate_obs, rate_obs, n_obs * sizeof(gpsacq_rate_obs), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_nav_fix, fixes, n_fix * sizeof(gpsacq_fix), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_vel.grow(n_fix, e->stream)) return rc;
+    if (int rc = upload(e, e->d_nav_obs, obs, n_obs)) return rc;
+    if (int rc = upload(e, e->d_rate_obs, rate_obs, n_obs)) return rc;
+    if (int rc = upload(e, e->d_nav_fix, fixes, n_fix)) return rc;
     if (int rc = gpsacq_vel_batch_device(e, eph, n_eph, e->d_nav_obs, e->d_rate_obs, e->d_nav_fix, n_fix, sats_per_fix, e->d_vel, 0)) return rc;
-    HIPCHK(hipMemcpyAsync(out, e->d_vel, n_fix * sizeof(gpsacq_vel), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, out, e->d_vel, n_fix)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -498,14 +499,8 @@ extern "C" int gpsacq_pvt_track_device(gpsacq_engine* e, const gpsacq_ephemeris*
     if (int rc = rate_check("gpsacq_pvt_track", e, d_records, max_epochs, n_epochs, chans, nom_words, n_chans, first_rx_sample, rx_step, n_fix, avg_samples)) return rc;
     if (!tags || !eph || n_eph <= 0 || !d_fix || !d_vel) return fail(GPSACQ_ERR_ARG, "gpsacq_pvt_track: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
-    if (!d_obs) {
-        if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_fix * (size_t)n_chans, e->stream)) return rc;
-        d_obs = e->d_nav_obs;
-    }
-    if (!d_rate_obs) {
-        if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_fix * (size_t)n_chans, e->stream)) return rc;
-        d_rate_obs = e->d_rate_obs;
-    }
+    if (int rc = or_own(e, d_obs, e->d_nav_obs, n_fix * (size_t)n_chans)) return rc;
+    if (int rc = or_own(e, d_rate_obs, e->d_rate_obs, n_fix * (size_t)n_chans)) return rc;
     if (int rc = obs_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, d_obs)) return rc;
     if (int rc = rate_enqueue(e, d_records, max_epochs, n_epochs, chans, nom_words, n_chans, first_rx_sample, rx_step, n_fix, avg_samples, d_rate_obs)) return rc;
     if (int rc = gpsacq_fix_batch_device(e, eph, n_eph, d_obs, n_fix, n_chans, d_fix, 0)) return rc;
@@ -516,19 +511,16 @@ extern "C" int gpsacq_pvt_track_device(gpsacq_engine* e, const gpsacq_ephemeris*
 }
 
 extern "C" int gpsacq_velocity_last_ms(const gpsacq_engine* e, float* carrier_acc_ms, float* observe_rate_ms, float* sat_rate_ms, float* vel_ms) {
-    if (!e || (!e->rate_timed && !e->vel_timed)) return fail(GPSACQ_ERR_ARG, "gpsacq_velocity_last_ms: no rate or velocity call on this engine");
+    if (!e || (!e->rate_t.ran() && !e->vel_t.ran())) return fail(GPSACQ_ERR_ARG, "gpsacq_velocity_last_ms: no rate or velocity call on this engine");
     HIPCHK(hipSetDevice(e->p.device));
-    float t[4] = {0.f, 0.f, 0.f, 0.f};
-    if (e->rate_timed) {
-        HIPCHK(hipEventSynchronize(e->rate_ev[2]));
-        HIPCHK(hipEventElapsedTime(&t[0], e->rate_ev[0], e->rate_ev[1]));
-        HIPCHK(hipEventElapsedTime(&t[1], e->rate_ev[1], e->rate_ev[2]));
-    }
-    if (e->vel_timed) {
-        HIPCHK(hipEventSynchronize(e->vel_ev[2]));
-        HIPCHK(hipEventElapsedTime(&t[2], e->vel_ev[0], e->vel_ev[1]));
-        HIPCHK(hipEventElapsedTime(&t[3], e->vel_ev[1], e->vel_ev[2]));
-    }
+    float t[4] = {0.f, 0.f, 0.f, 0.f};  // the half that did not run reads 0
+    const Stages<3>* half[2] = {&e->rate_t, &e->vel_t};
+    for (int h = 0; h < 2; ++h)
+        if (half[h]->ran()) {
+            if (int rc = half[h]->wait()) return rc;
+            if (int rc = half[h]->elapsed(0, 1, &t[2 * h])) return rc;
+            if (int rc = half[h]->elapsed(1, 2, &t[2 * h + 1])) return rc;
+        }
     if (carrier_acc_ms) *carrier_acc_ms = t[0];
     if (observe_rate_ms) *observe_rate_ms = t[1];
     if (sat_rate_ms) *sat_rate_ms = t[2];
@@ -582,41 +574,37 @@ static int smooth_enqueue(gpsacq_engine* e, const void* d_records, int max_epoch
         d.nom_word = nom_words[c];
     }
     const size_t row = (size_t)max_epochs + 1, nc = (size_t)n_chans;
-    if (int rc = grow(e->d_smooth_chan, e->smooth_chan_cap, (size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
-    if (int rc = grow(e->d_smooth_lock, e->smooth_lock_cap, 2 * nc * row, e->stream)) return rc;
-    if (int rc = grow(e->d_smooth_q, e->smooth_q_cap, nc * (3 * n_fix + 1), e->stream)) return rc;
-    if (int rc = grow(e->d_smooth_w, e->smooth_w_cap, nc * 3 * n_fix, e->stream)) return rc;
-    for (auto& ev : e->smooth_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
+    if (int rc = e->d_smooth_chan.grow((size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
+    if (int rc = e->d_smooth_lock.grow(2 * nc * row, e->stream)) return rc;
+    if (int rc = e->d_smooth_q.grow(nc * (3 * n_fix + 1), e->stream)) return rc;
+    if (int rc = e->d_smooth_w.grow(nc * 3 * n_fix, e->stream)) return rc;
     // pageable source: the copy has left `tab` when the call returns
     HIPCHK(hipMemcpyAsync(e->d_smooth_chan, tab, nc * sizeof(SmoothChan), hipMemcpyHostToDevice, e->stream));
     // pos_t and A_t into the scratch the observables use; their second kernels do not run, so those times read 0
     if (int rc = code_pos_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, n_chans)) return rc;
-    HIPCHK(hipEventRecord(e->obs_ev[2], e->stream));
-    e->obs_timed = true;
+    if (int rc = e->obs_t.mark(2, e->stream)) return rc;
+    if (int rc = e->obs_t.finish()) return rc;
     if (int rc = carrier_acc_enqueue(e, d_records, max_epochs, n_epochs, chans, nom_words, n_chans)) return rc;
-    HIPCHK(hipEventRecord(e->rate_ev[2], e->stream));
-    e->rate_timed = true;
+    if (int rc = e->rate_t.mark(2, e->stream)) return rc;
+    if (int rc = e->rate_t.finish()) return rc;
     const gpsacq_track_record* rec = (const gpsacq_track_record*)d_records;
     int64_t *lock_n = e->d_smooth_lock, *lock_d = e->d_smooth_lock + nc * row;
     uint64_t *z = e->d_smooth_q, *p = z + nc * n_fix, *sum = p + nc * n_fix;
     int32_t *t = e->d_smooth_w, *state = t + nc * n_fix, *seg = state + nc * n_fix;
-    e->smooth_timed = false;
-    HIPCHK(hipEventRecord(e->smooth_ev[0], e->stream));
+    if (int rc = e->smooth_t.begin(e->stream)) return rc;
     if (sp.lock_epochs > 0) launch_lock_acc(LockAccArgs{e->d_smooth_chan, rec, max_epochs, lock_n, lock_d}, n_chans, e->stream);
-    HIPCHK(hipEventRecord(e->smooth_ev[1], e->stream));
+    if (int rc = e->smooth_t.mark(1, e->stream)) return rc;
     launch_cmc(CmcArgs{e->d_smooth_chan, rec, e->d_obs_pos, e->d_rate_acc, lock_n, lock_d, max_epochs, n_chans, first_rx_sample, rx_step, n_fix,
                        sp.lock_epochs, sp.lock_num, sp.lock_den, sp.invert, z, p, t, state},
                e->stream);
-    HIPCHK(hipEventRecord(e->smooth_ev[2], e->stream));
+    if (int rc = e->smooth_t.mark(2, e->stream)) return rc;
     launch_smooth_scan(SmoothScanArgs{z, state, n_fix, sp.jump, sum, seg}, n_chans, e->stream);
-    HIPCHK(hipEventRecord(e->smooth_ev[3], e->stream));
+    if (int rc = e->smooth_t.mark(3, e->stream)) return rc;
     launch_smooth_out(SmoothOutArgs{e->d_smooth_chan, z, p, t, state, sum, seg, n_chans, n_fix, sp.window, (gpsacq_obs*)d_obs,
                                     (gpsacq_smooth_info*)d_info},
                       e->stream);
-    HIPCHK(hipEventRecord(e->smooth_ev[4], e->stream));
-    HIPCHK(hipGetLastError());
-    e->smooth_timed = true;
+    if (int rc = e->smooth_t.mark(4, e->stream)) return rc;
+    if (int rc = e->smooth_t.finish()) return rc;
     return GPSACQ_OK;
 }
 
@@ -642,19 +630,15 @@ extern "C" int gpsacq_smooth_observables(gpsacq_engine* e, const gpsacq_track_re
     if (!obs) return fail(GPSACQ_ERR_ARG, "gpsacq_smooth_observables: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
     const size_t n_obs = n_fix * (size_t)n_chans;
-    if (int rc = grow(e->d_obs_rec, e->obs_rec_cap, (size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
-    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
+    if (int rc = e->d_nav_obs.grow(n_obs, e->stream)) return rc;
     if (info)
-        if (int rc = grow(e->d_smooth_info, e->smooth_info_cap, n_obs, e->stream)) return rc;
-    for (int c = 0; c < n_chans; ++c)  // the rows keep their stride; only the records that exist travel
-        if (n_epochs[c] > 0)
-            HIPCHK(hipMemcpyAsync(e->d_obs_rec + (size_t)c * max_epochs, records + (size_t)c * max_epochs,
-                                  (size_t)n_epochs[c] * sizeof(gpsacq_track_record), hipMemcpyHostToDevice, e->stream));
+        if (int rc = e->d_smooth_info.grow(n_obs, e->stream)) return rc;
+    if (int rc = upload_records(e, records, max_epochs, n_epochs, n_chans)) return rc;
     if (int rc = smooth_enqueue(e, e->d_obs_rec, max_epochs, n_epochs, chans, tags, nom_words, n_chans, first_rx_sample, rx_step, n_fix, sp, e->d_nav_obs,
-                                info ? e->d_smooth_info : nullptr))
+                                info ? e->d_smooth_info.p : nullptr))
         return rc;
-    HIPCHK(hipMemcpyAsync(obs, e->d_nav_obs, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
-    if (info) HIPCHK(hipMemcpyAsync(info, e->d_smooth_info, n_obs * sizeof(gpsacq_smooth_info), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, obs, e->d_nav_obs, n_obs)) return rc;
+    if (int rc = download(e, info, e->d_smooth_info, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -667,21 +651,18 @@ extern "C" int gpsacq_fix_smooth_track_device(gpsacq_engine* e, const gpsacq_eph
     if (int rc = smooth_check("gpsacq_fix_smooth_track", e, d_records, max_epochs, n_epochs, chans, tags, nom_words, n_chans, first_rx_sample, rx_step, n_fix, params, &sp)) return rc;
     if (!eph || n_eph <= 0 || !d_fix) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_smooth_track: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
-    if (!d_obs) {
-        if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_fix * (size_t)n_chans, e->stream)) return rc;
-        d_obs = e->d_nav_obs;
-    }
+    if (int rc = or_own(e, d_obs, e->d_nav_obs, n_fix * (size_t)n_chans)) return rc;
     if (int rc = smooth_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, nom_words, n_chans, first_rx_sample, rx_step, n_fix, sp, d_obs, d_info)) return rc;
     return gpsacq_fix_batch_device(e, eph, n_eph, d_obs, n_fix, n_chans, d_fix, sync);
 }
 
 extern "C" int gpsacq_smooth_last_ms(const gpsacq_engine* e, float* lock_acc_ms, float* cmc_ms, float* scan_ms, float* out_ms) {
-    if (!e || !e->smooth_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_smooth_last_ms: no gpsacq_smooth_observables call on this engine");
+    if (!e || !e->smooth_t.ran()) return fail(GPSACQ_ERR_ARG, "gpsacq_smooth_last_ms: no gpsacq_smooth_observables call on this engine");
     HIPCHK(hipSetDevice(e->p.device));
-    HIPCHK(hipEventSynchronize(e->smooth_ev[4]));
+    if (int rc = e->smooth_t.wait()) return rc;
     float* out[4] = {lock_acc_ms, cmc_ms, scan_ms, out_ms};
     for (int k = 0; k < 4; ++k)
-        if (out[k]) HIPCHK(hipEventElapsedTime(out[k], e->smooth_ev[k], e->smooth_ev[k + 1]));
+        if (int rc = e->smooth_t.elapsed(k, k + 1, out[k])) return rc;
     return GPSACQ_OK;
 }
 
@@ -731,24 +712,20 @@ static int quality_enqueue(gpsacq_engine* e, const void* d_records, int max_epoc
         tab[c].tag_valid = tags[c].valid;
     }
     const size_t row = (size_t)max_epochs + 1, nc = (size_t)n_chans;
-    if (int rc = grow(e->d_quality_chan, e->quality_chan_cap, (size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
-    if (int rc = grow(e->d_quality_sums, e->quality_sums_cap, 3 * nc * row, e->stream)) return rc;
-    for (auto& ev : e->quality_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
+    if (int rc = e->d_quality_chan.grow((size_t)GPSACQ_FIX_MAX_SATS, e->stream)) return rc;
+    if (int rc = e->d_quality_sums.grow(3 * nc * row, e->stream)) return rc;
     // pageable source: the copy has left `tab` when the call returns
     HIPCHK(hipMemcpyAsync(e->d_quality_chan, tab, nc * sizeof(QualityChan), hipMemcpyHostToDevice, e->stream));
     const gpsacq_track_record* rec = (const gpsacq_track_record*)d_records;
     uint64_t *sum_a = e->d_quality_sums, *sum_d = sum_a + nc * row, *sum_n = sum_d + nc * row;
-    e->quality_timed = false;
-    HIPCHK(hipEventRecord(e->quality_ev[0], e->stream));
+    if (int rc = e->quality_t.begin(e->stream)) return rc;
     launch_quality_acc(QualityAccArgs{e->d_quality_chan, rec, max_epochs, sum_a, sum_d, sum_n}, n_chans, e->stream);
-    HIPCHK(hipEventRecord(e->quality_ev[1], e->stream));
+    if (int rc = e->quality_t.mark(1, e->stream)) return rc;
     launch_quality_out(QualityOutArgs{e->d_quality_chan, rec, sum_a, sum_d, sum_n, max_epochs, n_chans, first_rx_sample, rx_step, n_fix, qp,
                                       (gpsacq_obs*)d_obs, (gpsacq_quality_info*)d_info},
                        e->stream);
-    HIPCHK(hipEventRecord(e->quality_ev[2], e->stream));
-    HIPCHK(hipGetLastError());
-    e->quality_timed = true;
+    if (int rc = e->quality_t.mark(2, e->stream)) return rc;
+    if (int rc = e->quality_t.finish()) return rc;
     return GPSACQ_OK;
 }
 
@@ -774,21 +751,15 @@ extern "C" int gpsacq_quality_observables(gpsacq_engine* e, const gpsacq_track_r
     if (!info) return fail(GPSACQ_ERR_ARG, "gpsacq_quality_observables: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
     const size_t n_obs = n_fix * (size_t)n_chans;
-    if (int rc = grow(e->d_obs_rec, e->obs_rec_cap, (size_t)n_chans * (size_t)std::max(max_epochs, 1), e->stream)) return rc;
-    if (int rc = grow(e->d_quality_info, e->quality_info_cap, n_obs, e->stream)) return rc;
-    if (obs) {
-        if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-        HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
-    }
-    for (int c = 0; c < n_chans; ++c)  // the rows keep their stride; only the records that exist travel
-        if (n_epochs[c] > 0)
-            HIPCHK(hipMemcpyAsync(e->d_obs_rec + (size_t)c * max_epochs, records + (size_t)c * max_epochs,
-                                  (size_t)n_epochs[c] * sizeof(gpsacq_track_record), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_quality_info.grow(n_obs, e->stream)) return rc;
+    if (obs)
+        if (int rc = upload(e, e->d_nav_obs, obs, n_obs)) return rc;
+    if (int rc = upload_records(e, records, max_epochs, n_epochs, n_chans)) return rc;
     if (int rc = quality_enqueue(e, e->d_obs_rec, max_epochs, n_epochs, chans, tags, n_chans, first_rx_sample, rx_step, n_fix, qp,
-                                 obs ? e->d_nav_obs : nullptr, e->d_quality_info))
+                                 obs ? e->d_nav_obs.p : nullptr, e->d_quality_info))
         return rc;
-    if (obs) HIPCHK(hipMemcpyAsync(obs, e->d_nav_obs, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(info, e->d_quality_info, n_obs * sizeof(gpsacq_quality_info), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, obs, e->d_nav_obs, n_obs)) return rc;
+    if (int rc = download(e, info, e->d_quality_info, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -806,14 +777,8 @@ extern "C" int gpsacq_fix_quality_track_device(gpsacq_engine* e, const gpsacq_ep
         if (int rc = smooth_params("gpsacq_fix_quality_track", smooth, &sp)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
     const size_t n_obs = n_fix * (size_t)n_chans;
-    if (!d_obs) {
-        if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-        d_obs = e->d_nav_obs;
-    }
-    if (!d_info) {
-        if (int rc = grow(e->d_quality_info, e->quality_info_cap, n_obs, e->stream)) return rc;
-        d_info = e->d_quality_info;
-    }
+    if (int rc = or_own(e, d_obs, e->d_nav_obs, n_obs)) return rc;
+    if (int rc = or_own(e, d_info, e->d_quality_info, n_obs)) return rc;
     if (smooth) {
         if (int rc = smooth_enqueue(e, d_records, max_epochs, n_epochs, chans, tags, nom_words, n_chans, first_rx_sample, rx_step, n_fix, sp, d_obs, nullptr)) return rc;
     } else {
@@ -824,12 +789,11 @@ extern "C" int gpsacq_fix_quality_track_device(gpsacq_engine* e, const gpsacq_ep
 }
 
 extern "C" int gpsacq_quality_last_ms(const gpsacq_engine* e, float* acc_ms, float* out_ms) {
-    if (!e || !e->quality_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_quality_last_ms: no gpsacq_quality_observables call on this engine");
+    if (!e || !e->quality_t.ran()) return fail(GPSACQ_ERR_ARG, "gpsacq_quality_last_ms: no gpsacq_quality_observables call on this engine");
     HIPCHK(hipSetDevice(e->p.device));
-    HIPCHK(hipEventSynchronize(e->quality_ev[2]));
-    if (acc_ms) HIPCHK(hipEventElapsedTime(acc_ms, e->quality_ev[0], e->quality_ev[1]));
-    if (out_ms) HIPCHK(hipEventElapsedTime(out_ms, e->quality_ev[1], e->quality_ev[2]));
-    return GPSACQ_OK;
+    if (int rc = e->quality_t.wait()) return rc;
+    if (int rc = e->quality_t.elapsed(0, 1, acc_ms)) return rc;
+    return e->quality_t.elapsed(1, 2, out_ms);
 }
 
 // ---- atmosphere, elevation mask and DOP (fix_kernels.hip) --------------------------------------------------------------------
@@ -892,7 +856,7 @@ extern "C" int gpsacq_sat_views_device(gpsacq_engine* e, const gpsacq_ephemeris*
     const size_t n_obs = n_fix * (size_t)sats_per_fix;
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
-    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
+    if (int rc = e->d_nav_state.grow(n_obs, e->stream)) return rc;
     launch_sat_state(SatStateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_nav_state}, e->stream);
     launch_sat_view(SatViewArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, e->d_nav_state, (const gpsacq_fix*)d_fix, n_obs, sats_per_fix, *params,
                                 (gpsacq_sat_view*)d_out},
@@ -909,13 +873,11 @@ extern "C" int gpsacq_sat_views(gpsacq_engine* e, const gpsacq_ephemeris* eph, i
     const size_t n_obs = n_fix * (size_t)sats_per_fix;
     if (int rc = nav_check_weights("gpsacq_sat_views", obs, n_obs)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
-    if (int rc = grow(e->d_atm_view, e->atm_view_cap, n_obs, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_nav_fix, fix, n_fix * sizeof(gpsacq_fix), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_atm_view.grow(n_obs, e->stream)) return rc;
+    if (int rc = upload(e, e->d_nav_obs, obs, n_obs)) return rc;
+    if (int rc = upload(e, e->d_nav_fix, fix, n_fix)) return rc;
     if (int rc = gpsacq_sat_views_device(e, eph, n_eph, e->d_nav_obs, e->d_nav_fix, n_fix, sats_per_fix, params, e->d_atm_view, 0)) return rc;
-    HIPCHK(hipMemcpyAsync(out, e->d_atm_view, n_obs * sizeof(gpsacq_sat_view), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, out, e->d_atm_view, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -927,29 +889,22 @@ extern "C" int gpsacq_fix_atm_batch_device(gpsacq_engine* e, const gpsacq_epheme
     const size_t n_obs = n_fix * (size_t)sats_per_fix;
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
-    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
-    if (!d_dop) {  // the kernel always writes it
-        if (int rc = grow(e->d_atm_dop, e->atm_dop_cap, n_fix, e->stream)) return rc;
-        d_dop = e->d_atm_dop;
-    }
-    for (auto& ev : e->atm_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
-    e->atm_timed = false;
-    HIPCHK(hipEventRecord(e->atm_ev[0], e->stream));
+    if (int rc = e->d_nav_state.grow(n_obs, e->stream)) return rc;
+    if (int rc = or_own(e, d_dop, e->d_atm_dop, n_fix)) return rc;  // the kernel always writes it
+    if (int rc = e->atm_t.begin(e->stream)) return rc;
     launch_sat_state(SatStateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_nav_state}, e->stream);
-    HIPCHK(hipEventRecord(e->atm_ev[1], e->stream));
+    if (int rc = e->atm_t.mark(1, e->stream)) return rc;
     launch_fix_atm(FixAtmArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, e->d_nav_state, n_fix, sats_per_fix, *params, (gpsacq_fix*)d_fix,
                               (gpsacq_fix_dop*)d_dop},
                    e->stream);
-    HIPCHK(hipEventRecord(e->atm_ev[2], e->stream));
+    if (int rc = e->atm_t.mark(2, e->stream)) return rc;
     if (d_views)
         launch_sat_view(SatViewArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, e->d_nav_state, (const gpsacq_fix*)d_fix, n_obs, sats_per_fix,
                                     *params, (gpsacq_sat_view*)d_views},
                         e->stream);
-    HIPCHK(hipEventRecord(e->atm_ev[3], e->stream));
-    HIPCHK(hipGetLastError());
+    if (int rc = e->atm_t.mark(3, e->stream)) return rc;
+    if (int rc = e->atm_t.finish()) return rc;
     e->atm_views = d_views != nullptr;
-    e->atm_timed = true;
     if (sync) HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -961,33 +916,29 @@ extern "C" int gpsacq_fix_atm_batch(gpsacq_engine* e, const gpsacq_ephemeris* ep
     const size_t n_obs = n_fix * (size_t)sats_per_fix;
     if (int rc = nav_check_weights("gpsacq_fix_atm_batch", obs, n_obs)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
-    if (int rc = grow(e->d_atm_dop, e->atm_dop_cap, n_fix, e->stream)) return rc;
+    if (int rc = e->d_nav_fix.grow(n_fix, e->stream)) return rc;
+    if (int rc = e->d_atm_dop.grow(n_fix, e->stream)) return rc;
     if (views_out)
-        if (int rc = grow(e->d_atm_view, e->atm_view_cap, n_obs, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+        if (int rc = e->d_atm_view.grow(n_obs, e->stream)) return rc;
+    if (int rc = upload(e, e->d_nav_obs, obs, n_obs)) return rc;
     if (int rc = gpsacq_fix_atm_batch_device(e, eph, n_eph, e->d_nav_obs, n_fix, sats_per_fix, params, e->d_nav_fix, e->d_atm_dop,
-                                             views_out ? e->d_atm_view : nullptr, 0))
+                                             views_out ? e->d_atm_view.p : nullptr, 0))
         return rc;
-    HIPCHK(hipMemcpyAsync(fix_out, e->d_nav_fix, n_fix * sizeof(gpsacq_fix), hipMemcpyDeviceToHost, e->stream));
-    if (dop_out) HIPCHK(hipMemcpyAsync(dop_out, e->d_atm_dop, n_fix * sizeof(gpsacq_fix_dop), hipMemcpyDeviceToHost, e->stream));
-    if (views_out) HIPCHK(hipMemcpyAsync(views_out, e->d_atm_view, n_obs * sizeof(gpsacq_sat_view), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, fix_out, e->d_nav_fix, n_fix)) return rc;
+    if (int rc = download(e, dop_out, e->d_atm_dop, n_fix)) return rc;
+    if (int rc = download(e, views_out, e->d_atm_view, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
 
 extern "C" int gpsacq_fix_atm_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* fix_atm_ms, float* sat_view_ms) {
-    if (!e || !e->atm_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_atm_last_ms: no gpsacq_fix_atm_batch call on this engine");
+    if (!e || !e->atm_t.ran()) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_atm_last_ms: no gpsacq_fix_atm_batch call on this engine");
     HIPCHK(hipSetDevice(e->p.device));
-    HIPCHK(hipEventSynchronize(e->atm_ev[3]));
-    if (sat_state_ms) HIPCHK(hipEventElapsedTime(sat_state_ms, e->atm_ev[0], e->atm_ev[1]));
-    if (fix_atm_ms) HIPCHK(hipEventElapsedTime(fix_atm_ms, e->atm_ev[1], e->atm_ev[2]));
-    if (sat_view_ms) {
-        *sat_view_ms = 0.f;
-        if (e->atm_views) HIPCHK(hipEventElapsedTime(sat_view_ms, e->atm_ev[2], e->atm_ev[3]));
-    }
-    return GPSACQ_OK;
+    if (int rc = e->atm_t.wait()) return rc;
+    if (int rc = e->atm_t.elapsed(0, 1, sat_state_ms)) return rc;
+    if (int rc = e->atm_t.elapsed(1, 2, fix_atm_ms)) return rc;
+    if (sat_view_ms) *sat_view_ms = 0.f;  // k_sat_view ran only where the call asked for views
+    return e->atm_views ? e->atm_t.elapsed(2, 3, sat_view_ms) : GPSACQ_OK;
 }
 
 // ---- fix integrity: residual test and single-satellite exclusion (fix_kernels.hip) -----------------------------------------------
@@ -1049,26 +1000,19 @@ extern "C" int gpsacq_fix_raim_batch_device(gpsacq_engine* e, const gpsacq_ephem
     const size_t n_obs = n_fix * (size_t)sats_per_fix;
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
-    if (int rc = grow(e->d_nav_state, e->nav_state_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_raim_rows, e->raim_rows_cap, n_fix, e->stream)) return rc;
-    if (!d_dop) {  // the kernels always write it
-        if (int rc = grow(e->d_atm_dop, e->atm_dop_cap, n_fix, e->stream)) return rc;
-        d_dop = e->d_atm_dop;
-    }
-    for (auto& ev : e->raim_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
-    e->raim_timed = false;
+    if (int rc = e->d_nav_state.grow(n_obs, e->stream)) return rc;
+    if (int rc = e->d_raim_rows.grow(n_fix, e->stream)) return rc;
+    if (int rc = or_own(e, d_dop, e->d_atm_dop, n_fix)) return rc;  // the kernels always write it
     const RaimArgs args{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, e->d_nav_state, n_fix, sats_per_fix, *atm_params, *raim_params,
                         (gpsacq_fix*)d_fix, (gpsacq_fix_dop*)d_dop, (gpsacq_fix_raim*)d_raim, e->d_raim_rows};
-    HIPCHK(hipEventRecord(e->raim_ev[0], e->stream));
+    if (int rc = e->raim_t.begin(e->stream)) return rc;
     launch_sat_state(SatStateArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, n_obs, e->d_nav_state}, e->stream);
-    HIPCHK(hipEventRecord(e->raim_ev[1], e->stream));
+    if (int rc = e->raim_t.mark(1, e->stream)) return rc;
     launch_raim_detect(args, e->stream);
-    HIPCHK(hipEventRecord(e->raim_ev[2], e->stream));
+    if (int rc = e->raim_t.mark(2, e->stream)) return rc;
     launch_raim_exclude(args, e->stream);  // always: which rows were flagged is known on the device only
-    HIPCHK(hipEventRecord(e->raim_ev[3], e->stream));
-    HIPCHK(hipGetLastError());
-    e->raim_timed = true;
+    if (int rc = e->raim_t.mark(3, e->stream)) return rc;
+    if (int rc = e->raim_t.finish()) return rc;
     if (sync) HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -1080,29 +1024,27 @@ extern "C" int gpsacq_fix_raim_batch(gpsacq_engine* e, const gpsacq_ephemeris* e
     const size_t n_obs = n_fix * (size_t)sats_per_fix;
     if (int rc = nav_check_weights("gpsacq_fix_raim_batch", obs, n_obs)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
-    if (int rc = grow(e->d_atm_dop, e->atm_dop_cap, n_fix, e->stream)) return rc;
-    if (int rc = grow(e->d_raim, e->raim_cap, n_fix, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_nav_fix.grow(n_fix, e->stream)) return rc;
+    if (int rc = e->d_atm_dop.grow(n_fix, e->stream)) return rc;
+    if (int rc = e->d_raim.grow(n_fix, e->stream)) return rc;
+    if (int rc = upload(e, e->d_nav_obs, obs, n_obs)) return rc;
     if (int rc = gpsacq_fix_raim_batch_device(e, eph, n_eph, e->d_nav_obs, n_fix, sats_per_fix, atm_params, raim_params, e->d_nav_fix,
                                               e->d_atm_dop, e->d_raim, 0))
         return rc;
-    HIPCHK(hipMemcpyAsync(fix_out, e->d_nav_fix, n_fix * sizeof(gpsacq_fix), hipMemcpyDeviceToHost, e->stream));
-    if (dop_out) HIPCHK(hipMemcpyAsync(dop_out, e->d_atm_dop, n_fix * sizeof(gpsacq_fix_dop), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(raim_out, e->d_raim, n_fix * sizeof(gpsacq_fix_raim), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, fix_out, e->d_nav_fix, n_fix)) return rc;
+    if (int rc = download(e, dop_out, e->d_atm_dop, n_fix)) return rc;
+    if (int rc = download(e, raim_out, e->d_raim, n_fix)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
 
 extern "C" int gpsacq_fix_raim_last_ms(const gpsacq_engine* e, float* sat_state_ms, float* detect_ms, float* exclude_ms) {
-    if (!e || !e->raim_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_raim_last_ms: no gpsacq_fix_raim_batch call on this engine");
+    if (!e || !e->raim_t.ran()) return fail(GPSACQ_ERR_ARG, "gpsacq_fix_raim_last_ms: no gpsacq_fix_raim_batch call on this engine");
     HIPCHK(hipSetDevice(e->p.device));
-    HIPCHK(hipEventSynchronize(e->raim_ev[3]));
-    if (sat_state_ms) HIPCHK(hipEventElapsedTime(sat_state_ms, e->raim_ev[0], e->raim_ev[1]));
-    if (detect_ms) HIPCHK(hipEventElapsedTime(detect_ms, e->raim_ev[1], e->raim_ev[2]));
-    if (exclude_ms) HIPCHK(hipEventElapsedTime(exclude_ms, e->raim_ev[2], e->raim_ev[3]));
-    return GPSACQ_OK;
+    if (int rc = e->raim_t.wait()) return rc;
+    if (int rc = e->raim_t.elapsed(0, 1, sat_state_ms)) return rc;
+    if (int rc = e->raim_t.elapsed(1, 2, detect_ms)) return rc;
+    return e->raim_t.elapsed(2, 3, exclude_ms);
 }
 
 // ---- coarse-time fixes: positions from code phases alone (coarse_kernels.hip) ----------------------------------------------------
@@ -1139,42 +1081,25 @@ static int coarse_obs_check(const char* who, const gpsacq_engine* e, const void*
     return GPSACQ_OK;
 }
 
-static int coarse_events(gpsacq_engine* e) {
-    for (auto& ev : e->coarse_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
-    return GPSACQ_OK;
-}
-
-// k_coarse_obs on the engine's stream between coarse_ev[0] and coarse_ev[1]; every argument has been checked
+// k_coarse_obs on the engine's stream timed; every argument has been checked
 static int coarse_obs_enqueue(gpsacq_engine* e, const void* d_peaks, size_t n_fix, int n_chans, double snr_min, void* d_obs) {
-    if (int rc = coarse_events(e)) return rc;
-    e->coarse_obs_timed = false;
-    HIPCHK(hipEventRecord(e->coarse_ev[0], e->stream));
+    if (int rc = e->coarse_obs_t.begin(e->stream)) return rc;
     launch_coarse_obs(CoarseObsArgs{(const gpsacq_peak*)d_peaks, n_fix * (size_t)n_chans, n_chans, e->p.fs, snr_min, (gpsacq_obs*)d_obs}, e->stream);
-    HIPCHK(hipEventRecord(e->coarse_ev[1], e->stream));
-    HIPCHK(hipGetLastError());
-    e->coarse_obs_timed = true;
-    return GPSACQ_OK;
+    if (int rc = e->coarse_obs_t.mark(1, e->stream)) return rc;
+    return e->coarse_obs_t.finish();
 }
 
-// the ephemerides up, then k_coarse_fix between coarse_ev[2] and coarse_ev[3]; every argument has been checked
+// the ephemerides up, then k_coarse_fix timed; every argument has been checked
 static int coarse_fix_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_prior, size_t n_fix,
                               int sats_per_fix, const gpsacq_coarse_params& cp, void* d_fix, void* d_info, void* d_obs_out) {
     if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
-    if (!d_obs_out) {  // the whole milliseconds live somewhere
-        if (int rc = grow(e->d_coarse_work, e->coarse_work_cap, n_fix * (size_t)sats_per_fix, e->stream)) return rc;
-        d_obs_out = e->d_coarse_work;
-    }
-    if (int rc = coarse_events(e)) return rc;
-    e->coarse_fix_timed = false;
-    HIPCHK(hipEventRecord(e->coarse_ev[2], e->stream));
+    if (int rc = or_own(e, d_obs_out, e->d_coarse_work, n_fix * (size_t)sats_per_fix)) return rc;  // the whole milliseconds live somewhere
+    if (int rc = e->coarse_fix_t.begin(e->stream)) return rc;
     launch_coarse_fix(CoarseFixArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, (const gpsacq_coarse_prior*)d_prior, n_fix, sats_per_fix, cp,
                                     (gpsacq_fix*)d_fix, (gpsacq_coarse_info*)d_info, (gpsacq_obs*)d_obs_out},
                       e->stream);
-    HIPCHK(hipEventRecord(e->coarse_ev[3], e->stream));
-    HIPCHK(hipGetLastError());
-    e->coarse_fix_timed = true;
-    return GPSACQ_OK;
+    if (int rc = e->coarse_fix_t.mark(1, e->stream)) return rc;
+    return e->coarse_fix_t.finish();
 }
 
 extern "C" int gpsacq_coarse_obs_device(gpsacq_engine* e, const void* d_peaks, size_t n_fix, int n_chans, double snr_min, void* d_obs, int sync) {
@@ -1189,11 +1114,10 @@ extern "C" int gpsacq_coarse_obs(gpsacq_engine* e, const gpsacq_peak* peaks, siz
     if (int rc = coarse_obs_check("gpsacq_coarse_obs", e, peaks, n_fix, n_chans, snr_min, obs)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
     const size_t n_obs = n_fix * (size_t)n_chans;
-    if (int rc = grow(e->d_coarse_peaks, e->coarse_peaks_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_coarse_obs, e->coarse_obs_cap, n_obs, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_coarse_peaks, peaks, n_obs * sizeof(gpsacq_peak), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_coarse_obs.grow(n_obs, e->stream)) return rc;
+    if (int rc = upload(e, e->d_coarse_peaks, peaks, n_obs)) return rc;
     if (int rc = coarse_obs_enqueue(e, e->d_coarse_peaks, n_fix, n_chans, snr_min, e->d_coarse_obs)) return rc;
-    HIPCHK(hipMemcpyAsync(obs, e->d_coarse_obs, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, obs, e->d_coarse_obs, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -1223,18 +1147,16 @@ extern "C" int gpsacq_coarse_fix_batch(gpsacq_engine* e, const gpsacq_ephemeris*
             return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_fix_batch: prior %zu is (%g, %g, %g) at rx_ms %d (must be finite, 0 <= rx_ms < 604800000)", k,
                         prior[k].x, prior[k].y, prior[k].z, (int)prior[k].rx_ms);
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_coarse_work, e->coarse_work_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_coarse_prior, e->coarse_prior_cap, n_fix, e->stream)) return rc;
-    if (int rc = grow(e->d_nav_fix, e->nav_fix_cap, n_fix, e->stream)) return rc;
-    if (int rc = grow(e->d_coarse_info, e->coarse_info_cap, n_fix, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_coarse_prior, prior, n_fix * sizeof(gpsacq_coarse_prior), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_coarse_work.grow(n_obs, e->stream)) return rc;
+    if (int rc = e->d_nav_fix.grow(n_fix, e->stream)) return rc;
+    if (int rc = e->d_coarse_info.grow(n_fix, e->stream)) return rc;
+    if (int rc = upload(e, e->d_nav_obs, obs, n_obs)) return rc;
+    if (int rc = upload(e, e->d_coarse_prior, prior, n_fix)) return rc;
     if (int rc = coarse_fix_enqueue(e, eph, n_eph, e->d_nav_obs, e->d_coarse_prior, n_fix, sats_per_fix, cp, e->d_nav_fix, e->d_coarse_info, nullptr))
         return rc;
-    HIPCHK(hipMemcpyAsync(fix_out, e->d_nav_fix, n_fix * sizeof(gpsacq_fix), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(info_out, e->d_coarse_info, n_fix * sizeof(gpsacq_coarse_info), hipMemcpyDeviceToHost, e->stream));
-    if (obs_out) HIPCHK(hipMemcpyAsync(obs_out, e->d_coarse_work, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, fix_out, e->d_nav_fix, n_fix)) return rc;
+    if (int rc = download(e, info_out, e->d_coarse_info, n_fix)) return rc;
+    if (int rc = download(e, obs_out, e->d_coarse_work, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -1248,10 +1170,7 @@ extern "C" int gpsacq_coarse_fix_peaks_device(gpsacq_engine* e, const gpsacq_eph
     gpsacq_coarse_params cp;
     if (int rc = coarse_params("gpsacq_coarse_fix_peaks", params, &cp)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (!d_obs) {
-        if (int rc = grow(e->d_coarse_obs, e->coarse_obs_cap, n_fix * (size_t)n_chans, e->stream)) return rc;
-        d_obs = e->d_coarse_obs;
-    }
+    if (int rc = or_own(e, d_obs, e->d_coarse_obs, n_fix * (size_t)n_chans)) return rc;
     if (int rc = coarse_obs_enqueue(e, d_peaks, n_fix, n_chans, snr_min, d_obs)) return rc;
     if (int rc = coarse_fix_enqueue(e, eph, n_eph, d_obs, d_prior, n_fix, n_chans, cp, d_fix, d_info, d_obs_out)) return rc;
     if (sync) HIPCHK(hipStreamSynchronize(e->stream));
@@ -1259,20 +1178,10 @@ extern "C" int gpsacq_coarse_fix_peaks_device(gpsacq_engine* e, const gpsacq_eph
 }
 
 extern "C" int gpsacq_coarse_last_ms(const gpsacq_engine* e, float* obs_ms, float* fix_ms) {
-    if (!e || (!e->coarse_obs_timed && !e->coarse_fix_timed)) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_last_ms: no gpsacq_coarse call on this engine");
+    if (!e || (!e->coarse_obs_t.ran() && !e->coarse_fix_t.ran())) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_last_ms: no gpsacq_coarse call on this engine");
     HIPCHK(hipSetDevice(e->p.device));
-    float t[2] = {0.f, 0.f};
-    if (e->coarse_obs_timed) {
-        HIPCHK(hipEventSynchronize(e->coarse_ev[1]));
-        HIPCHK(hipEventElapsedTime(&t[0], e->coarse_ev[0], e->coarse_ev[1]));
-    }
-    if (e->coarse_fix_timed) {
-        HIPCHK(hipEventSynchronize(e->coarse_ev[3]));
-        HIPCHK(hipEventElapsedTime(&t[1], e->coarse_ev[2], e->coarse_ev[3]));
-    }
-    if (obs_ms) *obs_ms = t[0];
-    if (fix_ms) *fix_ms = t[1];
-    return GPSACQ_OK;
+    if (int rc = stage_ms(e->coarse_obs_t, obs_ms)) return rc;
+    return stage_ms(e->coarse_fix_t, fix_ms);
 }
 
 // ---- fine code phases: search peaks refined below a sample (refine_kernels.hip) --------------------------------------------------
@@ -1317,20 +1226,12 @@ static int refine_check(const char* who, const gpsacq_engine* e, const void* bit
     return refine_params(who, params, checked);
 }
 
-static int refine_events(gpsacq_engine* e) {
-    for (auto& ev : e->refine_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
-    return GPSACQ_OK;
-}
-
-// k_refine on the engine's stream between refine_ev[0] and refine_ev[1]; every argument has been checked
-static int refine_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
-                          size_t n_tasks, const gpsacq_refine_params& rp, void* d_fine) {
-    if (int rc = ensure_track_chips(e)) return rc;
-    if (int rc = refine_events(e)) return rc;
+// what k_refine and k_fine_dop are told alike (the twelve fields RefineArgs and FineDopArgs share): the capture, its tasks and
+// peaks, the chip table and the engine's grid
+template <class Args> static void capture_args(const gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks,
+                                               const void* d_peaks, size_t n_tasks, Args& a) {
     const uint32_t lead = (uint32_t)((uintptr_t)d_bits & 3u);  // the kernel loads whole words from the aligned address below
     const bool ref_grid = e->sub == 1 && e->dstride == 1;       // as gpsacq_handoff_engine
-    RefineArgs a{};
     a.words = (const uint32_t*)((uintptr_t)d_bits - lead);
     a.n_bytes = n_bytes + lead;
     a.lead = lead;
@@ -1342,29 +1243,30 @@ static int refine_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes, 
     a.fc = e->p.fc, a.fs = e->p.fs;
     a.step_hz = ref_grid ? 0.0 : e->p.fs / N_FFT * e->dstride / e->sub;
     a.spm = e->nlags;
-    a.p = rp;
-    a.out = (gpsacq_fine*)d_fine;
-    e->refine_timed = false;
-    HIPCHK(hipEventRecord(e->refine_ev[0], e->stream));
-    launch_refine(a, e->stream);
-    HIPCHK(hipEventRecord(e->refine_ev[1], e->stream));
-    HIPCHK(hipGetLastError());
-    e->refine_timed = true;
-    return GPSACQ_OK;
 }
 
-// k_coarse_obs_fine between refine_ev[2] and refine_ev[3]; every argument has been checked
+// k_refine on the engine's stream timed; every argument has been checked
+static int refine_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
+                          size_t n_tasks, const gpsacq_refine_params& rp, void* d_fine) {
+    if (int rc = ensure_track_chips(e)) return rc;
+    RefineArgs a{};
+    capture_args(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, a);
+    a.p = rp;
+    a.out = (gpsacq_fine*)d_fine;
+    if (int rc = e->refine_t.begin(e->stream)) return rc;
+    launch_refine(a, e->stream);
+    if (int rc = e->refine_t.mark(1, e->stream)) return rc;
+    return e->refine_t.finish();
+}
+
+// k_coarse_obs_fine timed; every argument has been checked
 static int coarse_obs_fine_enqueue(gpsacq_engine* e, const void* d_peaks, const void* d_fine, size_t n_fix, int n_chans, double snr_min, void* d_obs) {
-    if (int rc = refine_events(e)) return rc;
-    e->refine_obs_timed = false;
-    HIPCHK(hipEventRecord(e->refine_ev[2], e->stream));
+    if (int rc = e->refine_obs_t.begin(e->stream)) return rc;
     launch_coarse_obs_fine(CoarseObsFineArgs{(const gpsacq_peak*)d_peaks, (const gpsacq_fine*)d_fine, n_fix * (size_t)n_chans, n_chans, e->p.fs, snr_min,
                                              (gpsacq_obs*)d_obs},
                            e->stream);
-    HIPCHK(hipEventRecord(e->refine_ev[3], e->stream));
-    HIPCHK(hipGetLastError());
-    e->refine_obs_timed = true;
-    return GPSACQ_OK;
+    if (int rc = e->refine_obs_t.mark(1, e->stream)) return rc;
+    return e->refine_obs_t.finish();
 }
 
 extern "C" int gpsacq_refine_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
@@ -1382,18 +1284,14 @@ extern "C" int gpsacq_refine(gpsacq_engine* e, const uint8_t* bits, size_t n_byt
     gpsacq_refine_params rp;
     if (int rc = refine_check("gpsacq_refine", e, bits, n_bytes, stride, peaks, n_tasks, params, fine_out, &rp)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_refine_bits, e->refine_bits_cap, n_bytes, e->stream)) return rc;
-    if (int rc = grow(e->d_refine_peaks, e->refine_peaks_cap, n_tasks, e->stream)) return rc;
-    if (int rc = grow(e->d_fine, e->fine_cap, n_tasks, e->stream)) return rc;
-    if (tasks) {
-        if (int rc = grow(e->d_refine_tasks, e->refine_tasks_cap, n_tasks, e->stream)) return rc;
-        HIPCHK(hipMemcpyAsync(e->d_refine_tasks, tasks, n_tasks * sizeof(gpsacq_task), hipMemcpyHostToDevice, e->stream));
-    }
-    HIPCHK(hipMemcpyAsync(e->d_refine_bits, bits, n_bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_refine_peaks, peaks, n_tasks * sizeof(gpsacq_peak), hipMemcpyHostToDevice, e->stream));
-    if (int rc = refine_enqueue(e, e->d_refine_bits, n_bytes, stride, tasks ? e->d_refine_tasks : nullptr, e->d_refine_peaks, n_tasks, rp, e->d_fine))
+    if (int rc = e->d_fine.grow(n_tasks, e->stream)) return rc;
+    if (tasks)
+        if (int rc = upload(e, e->d_refine_tasks, tasks, n_tasks)) return rc;
+    if (int rc = upload(e, e->d_refine_bits, bits, n_bytes)) return rc;
+    if (int rc = upload(e, e->d_refine_peaks, peaks, n_tasks)) return rc;
+    if (int rc = refine_enqueue(e, e->d_refine_bits, n_bytes, stride, tasks ? e->d_refine_tasks.p : nullptr, e->d_refine_peaks, n_tasks, rp, e->d_fine))
         return rc;
-    HIPCHK(hipMemcpyAsync(fine_out, e->d_fine, n_tasks * sizeof(gpsacq_fine), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, fine_out, e->d_fine, n_tasks)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -1414,13 +1312,11 @@ extern "C" int gpsacq_coarse_obs_fine(gpsacq_engine* e, const gpsacq_peak* peaks
     if (!fine) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_obs_fine: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
     const size_t n_obs = n_fix * (size_t)n_chans;
-    if (int rc = grow(e->d_refine_peaks, e->refine_peaks_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_fine, e->fine_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_coarse_obs, e->coarse_obs_cap, n_obs, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_refine_peaks, peaks, n_obs * sizeof(gpsacq_peak), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_fine, fine, n_obs * sizeof(gpsacq_fine), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_coarse_obs.grow(n_obs, e->stream)) return rc;
+    if (int rc = upload(e, e->d_refine_peaks, peaks, n_obs)) return rc;
+    if (int rc = upload(e, e->d_fine, fine, n_obs)) return rc;
     if (int rc = coarse_obs_fine_enqueue(e, e->d_refine_peaks, e->d_fine, n_fix, n_chans, snr_min, e->d_coarse_obs)) return rc;
-    HIPCHK(hipMemcpyAsync(obs, e->d_coarse_obs, n_obs * sizeof(gpsacq_obs), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, obs, e->d_coarse_obs, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -1438,14 +1334,8 @@ extern "C" int gpsacq_coarse_fix_fine_device(gpsacq_engine* e, const gpsacq_ephe
     gpsacq_coarse_params cp;
     if (int rc = coarse_params("gpsacq_coarse_fix_fine", params, &cp)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (!d_fine) {
-        if (int rc = grow(e->d_fine, e->fine_cap, n_tasks, e->stream)) return rc;
-        d_fine = e->d_fine;
-    }
-    if (!d_obs) {
-        if (int rc = grow(e->d_coarse_obs, e->coarse_obs_cap, n_tasks, e->stream)) return rc;
-        d_obs = e->d_coarse_obs;
-    }
+    if (int rc = or_own(e, d_fine, e->d_fine, n_tasks)) return rc;
+    if (int rc = or_own(e, d_obs, e->d_coarse_obs, n_tasks)) return rc;
     if (int rc = refine_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, rp, d_fine)) return rc;
     if (int rc = coarse_obs_fine_enqueue(e, d_peaks, d_fine, n_fix, n_chans, rp.snr_min, d_obs)) return rc;
     if (int rc = coarse_fix_enqueue(e, eph, n_eph, d_obs, d_prior, n_fix, n_chans, cp, d_fix, d_info, d_obs_out)) return rc;
@@ -1454,20 +1344,10 @@ extern "C" int gpsacq_coarse_fix_fine_device(gpsacq_engine* e, const gpsacq_ephe
 }
 
 extern "C" int gpsacq_refine_last_ms(const gpsacq_engine* e, float* refine_ms, float* obs_ms) {
-    if (!e || (!e->refine_timed && !e->refine_obs_timed)) return fail(GPSACQ_ERR_ARG, "gpsacq_refine_last_ms: no gpsacq_refine call on this engine");
+    if (!e || (!e->refine_t.ran() && !e->refine_obs_t.ran())) return fail(GPSACQ_ERR_ARG, "gpsacq_refine_last_ms: no gpsacq_refine call on this engine");
     HIPCHK(hipSetDevice(e->p.device));
-    float t[2] = {0.f, 0.f};
-    if (e->refine_timed) {
-        HIPCHK(hipEventSynchronize(e->refine_ev[1]));
-        HIPCHK(hipEventElapsedTime(&t[0], e->refine_ev[0], e->refine_ev[1]));
-    }
-    if (e->refine_obs_timed) {
-        HIPCHK(hipEventSynchronize(e->refine_ev[3]));
-        HIPCHK(hipEventElapsedTime(&t[1], e->refine_ev[2], e->refine_ev[3]));
-    }
-    if (refine_ms) *refine_ms = t[0];
-    if (obs_ms) *obs_ms = t[1];
-    return GPSACQ_OK;
+    if (int rc = stage_ms(e->refine_t, refine_ms)) return rc;
+    return stage_ms(e->refine_obs_t, obs_ms);
 }
 
 // ---- cold snapshot fixes: fine Doppler and a Doppler-only position solver (doppler_kernels.hip) ----------------------------------
@@ -1526,72 +1406,42 @@ static int doppler_fix_check(const char* who, const gpsacq_engine* e, const gpsa
     return doppler_fix_params(who, params, checked);
 }
 
-static int doppler_events(gpsacq_engine* e) {
-    for (auto& ev : e->dop_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
-    return GPSACQ_OK;
-}
-
-// k_fine_dop on the engine's stream between dop_ev[0] and dop_ev[1]; every argument has been checked
+// k_fine_dop on the engine's stream timed; every argument has been checked
 static int fine_dop_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
                             size_t n_tasks, const gpsacq_dopfine_params& dp, void* d_dopfine) {
     if (int rc = ensure_track_chips(e)) return rc;
-    if (int rc = doppler_events(e)) return rc;
-    const uint32_t lead = (uint32_t)((uintptr_t)d_bits & 3u);  // the kernel loads whole words from the aligned address below
-    const bool ref_grid = e->sub == 1 && e->dstride == 1;       // as gpsacq_handoff_engine
     FineDopArgs a{};
-    a.words = (const uint32_t*)((uintptr_t)d_bits - lead);
-    a.n_bytes = n_bytes + lead;
-    a.lead = lead;
-    a.stride = stride;
-    a.tasks = (const gpsacq_task*)d_tasks;
-    a.peaks = (const gpsacq_peak*)d_peaks;
-    a.n_tasks = n_tasks;
-    a.chips = e->d_track_chips;
-    a.fc = e->p.fc, a.fs = e->p.fs;
-    a.step_hz = ref_grid ? 0.0 : e->p.fs / N_FFT * e->dstride / e->sub;
-    a.spm = e->nlags;
+    capture_args(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, a);
     a.p = dp;
     a.out = (gpsacq_dopfine*)d_dopfine;
-    e->dop_fine_timed = false;
-    HIPCHK(hipEventRecord(e->dop_ev[0], e->stream));
+    if (int rc = e->dop_fine_t.begin(e->stream)) return rc;
     launch_fine_dop(a, e->stream);
-    HIPCHK(hipEventRecord(e->dop_ev[1], e->stream));
-    HIPCHK(hipGetLastError());
-    e->dop_fine_timed = true;
-    return GPSACQ_OK;
+    if (int rc = e->dop_fine_t.mark(1, e->stream)) return rc;
+    return e->dop_fine_t.finish();
 }
 
-// k_rate_obs_fine between dop_ev[2] and dop_ev[3]; every argument has been checked
+// k_rate_obs_fine timed; every argument has been checked
 static int rate_obs_fine_enqueue(gpsacq_engine* e, const void* d_peaks, const void* d_dopfine, size_t n_fix, int n_chans, double snr_min,
                                  void* d_rate_obs) {
-    if (int rc = doppler_events(e)) return rc;
-    e->dop_obs_timed = false;
-    HIPCHK(hipEventRecord(e->dop_ev[2], e->stream));
+    if (int rc = e->dop_obs_t.begin(e->stream)) return rc;
     launch_rate_obs_fine(RateObsFineArgs{(const gpsacq_peak*)d_peaks, (const gpsacq_dopfine*)d_dopfine, n_fix * (size_t)n_chans, snr_min,
                                          (gpsacq_rate_obs*)d_rate_obs},
                          e->stream);
-    HIPCHK(hipEventRecord(e->dop_ev[3], e->stream));
-    HIPCHK(hipGetLastError());
-    e->dop_obs_timed = true;
-    return GPSACQ_OK;
+    if (int rc = e->dop_obs_t.mark(1, e->stream)) return rc;
+    return e->dop_obs_t.finish();
 }
 
-// the ephemerides up, then k_doppler_fix between dop_ev[4] and dop_ev[5]; every argument has been checked
+// the ephemerides up, then k_doppler_fix timed; every argument has been checked
 static int doppler_fix_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_rate_obs, const void* d_rx_ms,
                                size_t n_fix, int sats_per_fix, const gpsacq_doppler_fix_params& fp, void* d_fix, void* d_prior) {
     if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
-    if (int rc = grow(e->d_dop_tau, e->dop_tau_cap, n_fix * (size_t)sats_per_fix, e->stream)) return rc;
-    if (int rc = doppler_events(e)) return rc;
-    e->dop_fix_timed = false;
-    HIPCHK(hipEventRecord(e->dop_ev[4], e->stream));
+    if (int rc = e->d_dop_tau.grow(n_fix * (size_t)sats_per_fix, e->stream)) return rc;
+    if (int rc = e->dop_fix_t.begin(e->stream)) return rc;
     launch_doppler_fix(DopplerFixArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, (const gpsacq_rate_obs*)d_rate_obs, (const int32_t*)d_rx_ms, n_fix,
                                       sats_per_fix, fp, e->d_dop_tau, (gpsacq_doppler_fix*)d_fix, (gpsacq_coarse_prior*)d_prior},
                        e->stream);
-    HIPCHK(hipEventRecord(e->dop_ev[5], e->stream));
-    HIPCHK(hipGetLastError());
-    e->dop_fix_timed = true;
-    return GPSACQ_OK;
+    if (int rc = e->dop_fix_t.mark(1, e->stream)) return rc;
+    return e->dop_fix_t.finish();
 }
 
 extern "C" int gpsacq_fine_doppler_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
@@ -1611,18 +1461,14 @@ extern "C" int gpsacq_fine_doppler(gpsacq_engine* e, const uint8_t* bits, size_t
     if (int rc = capture_check("gpsacq_fine_doppler", e, bits, n_bytes, stride, peaks, n_tasks, dopfine_out)) return rc;
     if (int rc = dopfine_params("gpsacq_fine_doppler", e, params, &dp)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_refine_bits, e->refine_bits_cap, n_bytes, e->stream)) return rc;
-    if (int rc = grow(e->d_refine_peaks, e->refine_peaks_cap, n_tasks, e->stream)) return rc;
-    if (int rc = grow(e->d_dopfine, e->dopfine_cap, n_tasks, e->stream)) return rc;
-    if (tasks) {
-        if (int rc = grow(e->d_refine_tasks, e->refine_tasks_cap, n_tasks, e->stream)) return rc;
-        HIPCHK(hipMemcpyAsync(e->d_refine_tasks, tasks, n_tasks * sizeof(gpsacq_task), hipMemcpyHostToDevice, e->stream));
-    }
-    HIPCHK(hipMemcpyAsync(e->d_refine_bits, bits, n_bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_refine_peaks, peaks, n_tasks * sizeof(gpsacq_peak), hipMemcpyHostToDevice, e->stream));
-    if (int rc = fine_dop_enqueue(e, e->d_refine_bits, n_bytes, stride, tasks ? e->d_refine_tasks : nullptr, e->d_refine_peaks, n_tasks, dp, e->d_dopfine))
+    if (int rc = e->d_dopfine.grow(n_tasks, e->stream)) return rc;
+    if (tasks)
+        if (int rc = upload(e, e->d_refine_tasks, tasks, n_tasks)) return rc;
+    if (int rc = upload(e, e->d_refine_bits, bits, n_bytes)) return rc;
+    if (int rc = upload(e, e->d_refine_peaks, peaks, n_tasks)) return rc;
+    if (int rc = fine_dop_enqueue(e, e->d_refine_bits, n_bytes, stride, tasks ? e->d_refine_tasks.p : nullptr, e->d_refine_peaks, n_tasks, dp, e->d_dopfine))
         return rc;
-    HIPCHK(hipMemcpyAsync(dopfine_out, e->d_dopfine, n_tasks * sizeof(gpsacq_dopfine), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, dopfine_out, e->d_dopfine, n_tasks)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -1643,13 +1489,11 @@ extern "C" int gpsacq_rate_obs_fine(gpsacq_engine* e, const gpsacq_peak* peaks, 
     if (!dopfine) return fail(GPSACQ_ERR_ARG, "gpsacq_rate_obs_fine: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
     const size_t n_obs = n_fix * (size_t)n_chans;
-    if (int rc = grow(e->d_refine_peaks, e->refine_peaks_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_dopfine, e->dopfine_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_obs, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_refine_peaks, peaks, n_obs * sizeof(gpsacq_peak), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_dopfine, dopfine, n_obs * sizeof(gpsacq_dopfine), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_rate_obs.grow(n_obs, e->stream)) return rc;
+    if (int rc = upload(e, e->d_refine_peaks, peaks, n_obs)) return rc;
+    if (int rc = upload(e, e->d_dopfine, dopfine, n_obs)) return rc;
     if (int rc = rate_obs_fine_enqueue(e, e->d_refine_peaks, e->d_dopfine, n_fix, n_chans, snr_min, e->d_rate_obs)) return rc;
-    HIPCHK(hipMemcpyAsync(rate_obs, e->d_rate_obs, n_obs * sizeof(gpsacq_rate_obs), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, rate_obs, e->d_rate_obs, n_obs)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -1679,19 +1523,16 @@ extern "C" int gpsacq_doppler_fix_batch(gpsacq_engine* e, const gpsacq_ephemeris
         if (rx_ms[k] < 0 || rx_ms[k] >= 604800000)
             return fail(GPSACQ_ERR_ARG, "gpsacq_doppler_fix_batch: rx_ms[%zu] = %d (0 <= rx_ms < 604800000)", k, (int)rx_ms[k]);
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_nav_obs, e->nav_obs_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_obs, e->stream)) return rc;
-    if (int rc = grow(e->d_dop_rx_ms, e->dop_rx_ms_cap, n_fix, e->stream)) return rc;
-    if (int rc = grow(e->d_dop_fix, e->dop_fix_cap, n_fix, e->stream)) return rc;
-    if (int rc = grow(e->d_dop_prior, e->dop_prior_cap, n_fix, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_nav_obs, obs, n_obs * sizeof(gpsacq_obs), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_rate_obs, rate_obs, n_obs * sizeof(gpsacq_rate_obs), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_dop_rx_ms, rx_ms, n_fix * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    if (int rc = e->d_dop_fix.grow(n_fix, e->stream)) return rc;
+    if (int rc = e->d_dop_prior.grow(n_fix, e->stream)) return rc;
+    if (int rc = upload(e, e->d_nav_obs, obs, n_obs)) return rc;
+    if (int rc = upload(e, e->d_rate_obs, rate_obs, n_obs)) return rc;
+    if (int rc = upload(e, e->d_dop_rx_ms, rx_ms, n_fix)) return rc;
     if (int rc = doppler_fix_enqueue(e, eph, n_eph, e->d_nav_obs, e->d_rate_obs, e->d_dop_rx_ms, n_fix, sats_per_fix, fp, e->d_dop_fix,
-                                     prior_out ? e->d_dop_prior : nullptr))
+                                     prior_out ? e->d_dop_prior.p : nullptr))
         return rc;
-    HIPCHK(hipMemcpyAsync(fix_out, e->d_dop_fix, n_fix * sizeof(gpsacq_doppler_fix), hipMemcpyDeviceToHost, e->stream));
-    if (prior_out) HIPCHK(hipMemcpyAsync(prior_out, e->d_dop_prior, n_fix * sizeof(gpsacq_coarse_prior), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, fix_out, e->d_dop_fix, n_fix)) return rc;
+    if (int rc = download(e, prior_out, e->d_dop_prior, n_fix)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -1716,26 +1557,11 @@ extern "C" int gpsacq_cold_fix_device(gpsacq_engine* e, const gpsacq_ephemeris* 
     if (int rc = doppler_fix_params(who, doppler_par, &fp)) return rc;
     if (int rc = coarse_params(who, coarse_par, &cp)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (!d_dopfine) {
-        if (int rc = grow(e->d_dopfine, e->dopfine_cap, n_tasks, e->stream)) return rc;
-        d_dopfine = e->d_dopfine;
-    }
-    if (!d_rate_obs) {
-        if (int rc = grow(e->d_rate_obs, e->rate_obs_cap, n_tasks, e->stream)) return rc;
-        d_rate_obs = e->d_rate_obs;
-    }
-    if (!d_prior) {
-        if (int rc = grow(e->d_dop_prior, e->dop_prior_cap, n_fix, e->stream)) return rc;
-        d_prior = e->d_dop_prior;
-    }
-    if (!d_fine) {
-        if (int rc = grow(e->d_fine, e->fine_cap, n_tasks, e->stream)) return rc;
-        d_fine = e->d_fine;
-    }
-    if (!d_obs) {
-        if (int rc = grow(e->d_coarse_obs, e->coarse_obs_cap, n_tasks, e->stream)) return rc;
-        d_obs = e->d_coarse_obs;
-    }
+    if (int rc = or_own(e, d_dopfine, e->d_dopfine, n_tasks)) return rc;
+    if (int rc = or_own(e, d_rate_obs, e->d_rate_obs, n_tasks)) return rc;
+    if (int rc = or_own(e, d_prior, e->d_dop_prior, n_fix)) return rc;
+    if (int rc = or_own(e, d_fine, e->d_fine, n_tasks)) return rc;
+    if (int rc = or_own(e, d_obs, e->d_coarse_obs, n_tasks)) return rc;
     if (int rc = fine_dop_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, dp, d_dopfine)) return rc;
     if (int rc = coarse_obs_enqueue(e, d_peaks, n_fix, n_chans, dp.snr_min, d_obs)) return rc;
     if (int rc = rate_obs_fine_enqueue(e, d_peaks, d_dopfine, n_fix, n_chans, dp.snr_min, d_rate_obs)) return rc;
@@ -1748,18 +1574,10 @@ extern "C" int gpsacq_cold_fix_device(gpsacq_engine* e, const gpsacq_ephemeris* 
 }
 
 extern "C" int gpsacq_doppler_last_ms(const gpsacq_engine* e, float* fine_dop_ms, float* rate_obs_ms, float* doppler_fix_ms) {
-    if (!e || (!e->dop_fine_timed && !e->dop_obs_timed && !e->dop_fix_timed))
+    if (!e || (!e->dop_fine_t.ran() && !e->dop_obs_t.ran() && !e->dop_fix_t.ran()))
         return fail(GPSACQ_ERR_ARG, "gpsacq_doppler_last_ms: no gpsacq_fine_doppler, gpsacq_rate_obs_fine or gpsacq_doppler_fix call on this engine");
     HIPCHK(hipSetDevice(e->p.device));
-    const bool timed[3] = {e->dop_fine_timed, e->dop_obs_timed, e->dop_fix_timed};
-    float t[3] = {0.f, 0.f, 0.f};
-    for (int k = 0; k < 3; ++k)
-        if (timed[k]) {
-            HIPCHK(hipEventSynchronize(e->dop_ev[2 * k + 1]));
-            HIPCHK(hipEventElapsedTime(&t[k], e->dop_ev[2 * k], e->dop_ev[2 * k + 1]));
-        }
-    if (fine_dop_ms) *fine_dop_ms = t[0];
-    if (rate_obs_ms) *rate_obs_ms = t[1];
-    if (doppler_fix_ms) *doppler_fix_ms = t[2];
-    return GPSACQ_OK;
+    if (int rc = stage_ms(e->dop_fine_t, fine_dop_ms)) return rc;
+    if (int rc = stage_ms(e->dop_obs_t, rate_obs_ms)) return rc;
+    return stage_ms(e->dop_fix_t, doppler_fix_ms);
 }

@@ -88,7 +88,7 @@ static int track_check_params(const gpsacq_track_params& p) {
 int ensure_track_chips(gpsacq_engine* e) {
     if (e->d_track_chips) return GPSACQ_OK;
     const std::vector<uint32_t> chips = ca_chip_words();
-    HIPCHK(hipMalloc((void**)&e->d_track_chips, chips.size() * sizeof(uint32_t)));
+    HIPCHK(e->d_track_chips.alloc(chips.size()));
     HIPCHK(hipMemcpy(e->d_track_chips, chips.data(), chips.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     return GPSACQ_OK;
 }
@@ -105,8 +105,8 @@ static int track_prepare(gpsacq_engine* e, uint64_t first_sample, const gpsacq_t
     }
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = ensure_track_chips(e)) return rc;
-    if (int rc = grow(e->d_chans, e->chans_cap, (size_t)n_chans, e->stream)) return rc;
-    if (int rc = grow(e->d_track_n, e->track_n_cap, (size_t)n_chans, e->stream)) return rc;
+    if (int rc = e->d_chans.grow((size_t)n_chans, e->stream)) return rc;
+    if (int rc = e->d_track_n.grow((size_t)n_chans, e->stream)) return rc;
     HIPCHK(hipMemcpyAsync(e->d_chans, chans, n_chans * sizeof(gpsacq_track_chan), hipMemcpyHostToDevice, e->stream));
     return GPSACQ_OK;
 }
@@ -173,9 +173,9 @@ template <class Run> static int track_from_host(gpsacq_engine* e, int n_chans, i
                                                 const int32_t* n_epochs, Run run) {
     const size_t per = (size_t)n_chans * (size_t)max_epochs;
     if (prompt && per)
-        if (int rc = grow(e->d_prompt, e->prompt_cap, 2 * per, e->stream)) return rc;
+        if (int rc = e->d_prompt.grow(2 * per, e->stream)) return rc;
     if (records && per)
-        if (int rc = grow(e->d_records, e->records_cap, per, e->stream)) return rc;
+        if (int rc = e->d_records.grow(per, e->stream)) return rc;
     if (int rc = run(prompt && per ? (void*)e->d_prompt : nullptr, records && per ? (void*)e->d_records : nullptr)) return rc;
     return track_rows_to_host(e, n_chans, max_epochs, n_epochs, prompt, records);
 }
@@ -186,7 +186,7 @@ extern "C" int gpsacq_track(gpsacq_engine* e, const uint8_t* bits, size_t n_byte
     if (!e || !bits || n_bytes == 0 || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
         return fail(GPSACQ_ERR_ARG, "gpsacq_track: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_gen, e->gen_cap, n_bytes, e->stream)) return rc;
+    if (int rc = e->d_gen.grow(n_bytes, e->stream)) return rc;
     HIPCHK(hipMemcpyAsync(e->d_gen, bits, n_bytes, hipMemcpyHostToDevice, e->stream));
     return track_from_host(e, n_chans, max_epochs, prompt, records, n_epochs_out, [&](void* d_prompt, void* d_records) {
         return gpsacq_track_device(e, e->d_gen, n_bytes, first_sample, chans, n_chans, params, d_prompt, d_records, max_epochs, n_epochs_out);
@@ -287,21 +287,18 @@ extern "C" int gpsacq_track_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input*
     else if (int rc = gpsacq_track_default_params(e, &p)) return rc;
     if (int rc = track_check_params(p)) return rc;
     if (int rc = track_prepare(e, first_sample, chans, n_chans)) return rc;
-    for (auto& ev : e->tiq_ev)
-        if (!ev) HIPCHK(hipEventCreate(&ev));
-    e->tiq_timed = false;
-    HIPCHK(hipEventRecord(e->tiq_ev[0], e->stream));
+    if (int rc = e->tiq_t.begin(e->stream)) return rc;
     if (sign) {
         // the window as the 1-bit stream the scripts would have written, in engine scratch; then the 1-bit channels on it
         const size_t n_bytes = (n_samples + 7) / 8;
-        if (int rc = grow(e->d_iqbits, e->iqbits_cap, n_bytes, e->stream)) return rc;
+        if (int rc = e->d_iqbits.grow(n_bytes, e->stream)) return rc;
         const size_t left = cap.iq_total > cap.iq_first ? cap.iq_total - cap.iq_first : 0;  // samples of the capture from iq[0] on
         if (left < n_samples) HIPCHK(hipMemsetAsync(e->d_iqbits, 0, n_bytes, e->stream));
         if (int rc = iq8_to_bits_enqueue(e, (const uint8_t*)d_iq, std::min(n_samples, left), cap.iq, cap.iq_first, e->d_iqbits)) return rc;
-        HIPCHK(hipEventRecord(e->tiq_ev[1], e->stream));
+        if (int rc = e->tiq_t.mark(1, e->stream)) return rc;
         track_launch_bits(e, e->d_iqbits, n_bytes, first_sample, n_chans, p, d_prompt, d_records, max_epochs);
     } else {
-        HIPCHK(hipEventRecord(e->tiq_ev[1], e->stream));
+        if (int rc = e->tiq_t.mark(1, e->stream)) return rc;
         TrackIqArgs a{};
         track_common(e, first_sample, n_samples, n_chans, p, d_prompt, d_records, max_epochs, a);
         a.iq = (const uint8_t*)d_iq;
@@ -311,10 +308,9 @@ extern "C" int gpsacq_track_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input*
         if (std::abs(a.dc_i) > 128 || std::abs(a.dc_q) > 128) return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: mean (%g, %g) outside +-128", in->mean_i, in->mean_q);
         launch_track_iq(a, e->stream);
     }
-    HIPCHK(hipEventRecord(e->tiq_ev[2], e->stream));
+    if (int rc = e->tiq_t.mark(2, e->stream)) return rc;
     if (int rc = track_collect(e, chans, n_chans, n_epochs_out)) return rc;
-    e->tiq_timed = true;
-    return GPSACQ_OK;
+    return e->tiq_t.finish();
 }
 
 extern "C" int gpsacq_track_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, uint64_t first_sample,
@@ -323,7 +319,7 @@ extern "C" int gpsacq_track_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, co
     if (!e || !iq || n_samples == 0 || !chans || n_chans <= 0 || max_epochs < 0 || !n_epochs_out)
         return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8: bad argument");
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = grow(e->d_iq, e->iq_cap, 2 * n_samples + 16, e->stream)) return rc;
+    if (int rc = e->d_iq.grow(2 * n_samples + 16, e->stream)) return rc;
     HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * n_samples, hipMemcpyHostToDevice, e->stream));
     return track_from_host(e, n_chans, max_epochs, prompt, records, n_epochs_out, [&](void* d_prompt, void* d_records) {
         return gpsacq_track_iq8_device(e, in, e->d_iq, n_samples, first_sample, chans, n_chans, params, d_prompt, d_records, max_epochs, n_epochs_out);
@@ -331,11 +327,10 @@ extern "C" int gpsacq_track_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, co
 }
 
 extern "C" int gpsacq_track_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* track_ms) {
-    if (!e || !e->tiq_timed) return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8_last_ms: no finished gpsacq_track_iq8 call");
+    if (!e || !e->tiq_t.ran()) return fail(GPSACQ_ERR_ARG, "gpsacq_track_iq8_last_ms: no finished gpsacq_track_iq8 call");
     HIPCHK(hipSetDevice(e->p.device));
-    if (convert_ms) HIPCHK(hipEventElapsedTime(convert_ms, e->tiq_ev[0], e->tiq_ev[1]));
-    if (track_ms) HIPCHK(hipEventElapsedTime(track_ms, e->tiq_ev[1], e->tiq_ev[2]));
-    return GPSACQ_OK;
+    if (int rc = e->tiq_t.elapsed(0, 1, convert_ms)) return rc;  // (the call itself waited for the stream)
+    return e->tiq_t.elapsed(1, 2, track_ms);
 }
 
 // ---- NAV decoder ---------------------------------------------------------------------------------------------------------------
