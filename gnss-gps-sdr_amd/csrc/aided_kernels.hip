@@ -1,0 +1,287 @@
+// aided_kernels.hip -- "Aided acquisition: predicted code phase and Doppler, windowed search" of include/gpsacq.h.
+//
+// k_aid_predict: one lane per (fix, channel), in fp64 on nav_device.hpp (split, week_ms, earth_turn, geodetic, view_of) and
+// orbit_device.hpp (the one orbit evaluation): the two light-time passes of k_coarse_fix's step A from the fix's place (one loop
+// body), then the satellite's state and rate at the time its replica shows, k_vel's row read backwards and k_sat_view's elevation.
+// No LDS, no barrier, no atomics; every loop is bounded.
+//
+// k_aided: one workgroup of AIDED_WAVES wave64 per task.  The PRN's chips go into LDS as in k_refine; wave w takes the segments
+// w, w + 4, ... of the window, and per Doppler hypothesis d and segment it does two things.
+//   BUILD.  The segment's 32-sample words (and the 2 W / 32 + 1 words behind them, for the chip stream alone) are shared out over
+//     the lanes; each word is built ONCE with k_refine's word_pos / word_masks<false> (capture_words.hpp): the samples, the bits
+//     that belong to the segment, the cos and -sin masks and the prompt chips of hypothesis h = 0, which at sample j + h are the
+//     chips of hypothesis h at sample j.  Into the wave's own LDS go {x ^ cos, x ^ ~sin, valid} per word (one 16-byte entry) and
+//     the chip-mask stream, one word per 32 samples.
+//   WALK.  After a wave-local wait lane l owns code hypothesis h = l (l + 64, l + 128, l + 192 in further passes over the same
+//     masks).  It walks the segment's words: every lane reads the same 16-byte entry (a broadcast), lanes 0..31 and 32..63 read one
+//     stream word each (two broadcasts), the lane cuts its chip mask out of the stream word it kept from the last step and the
+//     new one with a funnel shift by h & 31 (word offset h >> 5), and takes two xor-popcounts over the WHOLE word: the bits that
+//     are not the segment's (only its first and last word have any) are counted once more by themselves and taken off.  Five
+//     vector instructions and two LDS reads per word serve 64 hypotheses; nothing crosses lanes.  At the segment's end the lane
+//     squares its own I and Q into its own uint64.
+// A segment of more than AIDED_CHUNK words (spm above 6100) is built and walked in chunks; the counts carry over.  Once per d the four
+// waves' sums meet in LDS (two barriers), thread h adds them, writes power(h, d), and keeps its total and the largest KEY
+// power << 13 | (31 - d) << 8 | (255 - h) (power < 2^39: include/gpsacq.h, step 4): the maximum of the keys over the workgroup is
+// the record's best, whatever the order.  No atomics.  Every loop is bounded by kernel arguments; s_x is indexed below
+// AIDED_CHUNK, s_stream below AIDED_CHUNK + 2 W / 32 + 1 <= AIDED_CHUNK + 8, s_pow below 2 W + 1 <= 255 (W <= 127 is checked by the
+// host); nothing is read at or beyond byte n_bytes (word_at).
+// Built with -ffp-contract=off (Makefile): the NCO words must be gpsacq_handoff_engine's to the bit, as in refine_kernels.hip.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "aided_launch.hpp"
+#include "capture_words.hpp"
+#include "nav_device.hpp"
+#include "orbit_device.hpp"
+
+namespace acq {
+
+namespace {
+constexpr double L1_HZ = 1575.42e6;
+constexpr int AIDED_CHUNK = 192;               // capture words built and walked at a time: 6144 samples
+constexpr int AIDED_STREAM = AIDED_CHUNK + 8;  // and the stream words that go with them
+static_assert((2 * AIDED_MAX_CODE_HALF >> 5) + 1 <= AIDED_STREAM - AIDED_CHUNK, "the stream's tail");
+static_assert(2 * AIDED_MAX_CODE_HALF + 1 <= 64 * AIDED_PASSES && 2 * AIDED_MAX_DOP_HALF + 1 <= 32, "passes and key");
+
+// the lanes of ONE wave hand LDS to each other: the wave's LDS operations execute in program order, so all that is needed is
+// that the compiler keeps them in it
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
+    return (uint64_t)hi << 32 | lo;
+}
+
+// the window of Doppler hypothesis lo_shift: refine's steps 1 to 3 on a peak that is a hit by itself
+__device__ __forceinline__ Window window_at(const AidedArgs& a, size_t t, int64_t lo_shift) {
+    Window w = {false, 0, 0, 0, 0, 0, 0, 0};
+    if (lo_shift < -(int64_t)a.kmax || lo_shift > (int64_t)a.kmax) return w;
+    const gpsacq_peak pk = {1.0f, (int32_t)lo_shift, 0, 0.0f};
+    return window_of(pk, a.tasks, t, a.fc, a.fs, a.step_hz, a.spm, 0.0, a.p.blocks, a.n_bytes, a.lead, a.stride);
+}
+}  // namespace
+
+__global__ __launch_bounds__(NAV_BLOCK) void k_aid_predict(AidPredictArgs a) {
+    const size_t i = (size_t)blockIdx.x * NAV_BLOCK + threadIdx.x;
+    if (i >= a.n_fix * (size_t)a.chans) return;
+    const size_t f = i / (size_t)a.chans;
+    const int c = (int)(i % (size_t)a.chans);
+    gpsacq_aid out = {0, 0, 0, 0, 0.0, 0.0, 0.0};
+    const gpsacq_fix fix = a.fix[f];
+    if (fix.status != GPSACQ_FIX_OK) {
+        out.flags = GPSACQ_AID_NO_FIX;
+    } else if (c >= a.n_eph || !a.eph[c].valid) {
+        out.flags = GPSACQ_AID_NO_EPH;
+    } else {
+        const NavEph& p = a.eph[c];
+        // light time
+        double tau = 75e-3, cc = 0.0, k, frac, sn, cs;
+#pragma unroll 1
+        for (int pass = 0; pass < 2; ++pass) {  // at -75 ms, then at -tau
+            split(fix.rx_frac + -tau, k, frac);
+            const gpsacq_sat_state st = sat_state(orbit_at(p, week_ms(fix.rx_ms, k), frac));
+            sincos(-OMEGA_E * tau, &sn, &cs);
+            const double dx = fix.x - (st.x * cs - st.y * sn), dy = fix.y - (st.x * sn + st.y * cs), dz = fix.z - st.z;
+            tau = sqrt(dx * dx + dy * dy + dz * dz) / C;
+            cc = st.clock_corr;
+        }
+        // code
+        split(fix.rx_frac + (cc - tau), k, frac);
+        const gpsacq_obs o = {c, 1, week_ms(fix.rx_ms, k), 0, frac, 1.0};
+        // Doppler
+        const Orbit orb = orbit_at(p, o.tx_ms, o.tx_frac);
+        const gpsacq_sat_state st = sat_state(orb);
+        const gpsacq_sat_rate sr = sat_state_rate(p, orb);
+        earth_turn(o, st, fix, sn, cs);
+        const double qx = sr.vx - OMEGA_E * st.y, qy = sr.vy + OMEGA_E * st.x;  // v + Omega x p
+        const double dx = (st.x * cs - st.y * sn) - fix.x, dy = (st.x * sn + st.y * cs) - fix.y, dz = st.z - fix.z;
+        const double range = sqrt(dx * dx + dy * dy + dz * dz);
+        const double ex = dx / range, ey = dy / range, ez = dz / range;
+        double vx = 0.0, vy = 0.0, vz = 0.0, drift = 0.0;
+        if (a.vel) {
+            const gpsacq_vel v = a.vel[f];
+            if (v.status == GPSACQ_VEL_OK) vx = v.vx, vy = v.vy, vz = v.vz, drift = v.drift;
+        }
+        const double wx = (qx * cs - qy * sn) - (vx - OMEGA_E * fix.y), wy = (qx * sn + qy * cs) - (vy + OMEGA_E * fix.x), wz = sr.vz - vz;
+        const double rho = (ex * wx + ey * wy + ez * wz) + C * drift - C * sr.clock_drift;
+        const double dop = -(L1_HZ / C) * rho;
+        // elevation
+        double lat, lon, alt;
+        geodetic(fix.x, fix.y, fix.z, lat, lon, alt);
+        const View v = view_of(make_site(lat, lon, alt, 0.0, 0), dx, dy, dz);
+        const double elev = v.el * 180.0 / PI;
+        if (!isfinite(range) || !isfinite(o.tx_frac) || !isfinite(dop) || !isfinite(elev)) {
+            out.flags = GPSACQ_AID_NO_EPH;
+        } else {
+            out.tx_frac = o.tx_frac, out.doppler_hz = dop, out.elev_deg = elev;
+            out.ca_center = (int32_t)nearbyint(o.tx_frac * a.fs) % a.spm;
+            const double n = nearbyint(dop / a.step_hz);
+            if (fabs(n) < 2147483648.0) out.lo_center = (int32_t)n;
+            else out.flags |= GPSACQ_AID_OFF_GRID;
+            if (out.lo_center < -a.kmax || out.lo_center > a.kmax) out.flags |= GPSACQ_AID_OFF_GRID;
+            if (elev < a.p.elev_min_deg) out.flags |= GPSACQ_AID_LOW;
+        }
+    }
+    a.out[i] = out;
+}
+
+__global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided(AidedArgs a) {
+    __shared__ uint32_t s_chips[CHIP_WORDS];
+    __shared__ uint4 s_x[AIDED_WAVES][AIDED_CHUNK];  // x ^ cos mask, x ^ ~sin mask, the bits of the segment, unused
+    __shared__ uint32_t s_stream[AIDED_WAVES][AIDED_STREAM];
+    __shared__ unsigned long long s_pow[AIDED_WAVES][64 * AIDED_PASSES];
+    __shared__ unsigned long long s_red[AIDED_WAVES][2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t t = blockIdx.x;
+    const int W = a.p.code_half, K = a.p.dop_half, n_code = 2 * W + 1, n_dop = 2 * K + 1;
+    unsigned long long* const powers = a.powers ? a.powers + t * (size_t)(n_dop * n_code) : nullptr;
+
+    // 1. kept, 2. no aid: the flag and zeros
+    int blank = 0;
+    gpsacq_peak pk_out = {0.0f, 0, 0, 0.0f};
+    const gpsacq_aid aid = a.aid[t];
+    if (a.peaks) {
+        const gpsacq_peak pk = a.peaks[t];
+        if ((double)pk.snr >= a.p.keep_snr) blank = GPSACQ_AIDED_KEPT, pk_out = pk;
+    }
+    Window win = {false, 0, 0, 0, 0, 0, 0, 0};
+    if (!blank) {
+        if (aid.flags == 0 && aid.ca_center >= 0 && aid.ca_center < a.spm)
+            for (int d = 0; d < n_dop && !win.hit; ++d) win = window_at(a, t, (int64_t)aid.lo_center - K + d);
+        if (!win.hit) blank = GPSACQ_AIDED_NO_AID;
+    }
+    if (blank) {
+        if (threadIdx.x == 0) {
+            a.out[t] = gpsacq_aided{blank, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0};
+            a.peaks_out[t] = pk_out;
+        }
+        if (powers)
+            for (int i = threadIdx.x; i < n_dop * n_code; i += 64 * AIDED_WAVES) powers[i] = 0;
+        return;
+    }
+    chips_to_lds(a.chips, win.prn, s_chips);
+    __syncthreads();
+
+    // 3. hypotheses, 4. sums
+    const uint64_t o = win.o, spm = (uint64_t)a.spm, segments = win.segments;
+    const uint32_t base = (uint32_t)(((aid.ca_center - W) % a.spm + a.spm) % a.spm);
+    const int extra = (2 * W >> 5) + 1;  // stream words behind a chunk's capture words
+    uint64_t total = 0, key = 0;         // of hypothesis h = threadIdx.x
+    for (int d = 0; d < n_dop; ++d) {
+        const Window wd = window_at(a, t, (int64_t)aid.lo_center - K + d);
+        if (!wd.hit) {  // every lane decides the same
+            if (powers && (int)threadIdx.x < n_code) powers[d * n_code + threadIdx.x] = 0;
+            continue;
+        }
+        const uint32_t lo_rate = wd.lo_rate, ca_rate = wd.ca_rate;
+        const uint64_t P0 = (uint64_t)base * ca_rate % FULL;
+        uint64_t acc[AIDED_PASSES] = {0, 0, 0, 0};
+        for (uint64_t s = wv; s < segments; s += AIDED_WAVES) {
+            const uint64_t a0 = o + s * spm, a1 = a0 + spm;  // the segment's samples [a0, a1), counted from the aligned base
+            const uint64_t w1 = (a1 - 1) >> 5;
+            uint32_t ones_i[AIDED_PASSES] = {0, 0, 0, 0}, ones_q[AIDED_PASSES] = {0, 0, 0, 0};  // samples whose product is -1
+            for (uint64_t c0 = a0 >> 5; c0 <= w1; c0 += AIDED_CHUNK) {
+                const int nw = w1 - c0 + 1 < (uint64_t)AIDED_CHUNK ? (int)(w1 - c0 + 1) : AIDED_CHUNK;
+                for (int i = lane; i < nw + extra; i += 64) {
+                    const uint64_t wi = c0 + i;
+                    const WordPos w = word_pos(a.words, a.n_bytes, wi, a0, i < nw ? a1 : (wi << 5) + 32, o, P0, 0u, lo_rate, ca_rate, s_chips);
+                    uint32_t cm, sp, em, pm, lm;
+                    word_masks<false>(w, 0u, lo_rate, ca_rate, cm, sp, em, pm, lm);
+                    s_stream[wv][i] = pm;
+                    if (i < nw) s_x[wv][i] = make_uint4(w.x ^ cm, w.x ^ ~sp, w.valid, 0u);
+                }
+                wave_sync();
+#pragma unroll
+                for (int p = 0; p < AIDED_PASSES; ++p) {
+                    const int h = lane + 64 * p;
+                    if (h < n_code) {
+                        const int off = h >> 5;
+                        const uint32_t sh = (uint32_t)h & 31u;
+                        const uint32_t* st = &s_stream[wv][off];
+                        // the bits outside the segment, which only its first and last word have, are taken off again: the loop
+                        // counts whole words
+                        uint32_t below = st[0], above = st[1];
+                        const uint4 first = s_x[wv][0];
+                        uint32_t m = __funnelshift_r(below, above, sh);
+                        uint32_t ci = 0u - __popc((first.x ^ m) & ~first.z), cq = 0u - __popc((first.y ^ m) & ~first.z);
+                        if (nw > 1) {
+                            const uint4 last = s_x[wv][nw - 1];
+                            m = __funnelshift_r(st[nw - 1], st[nw], sh);
+                            ci -= __popc((last.x ^ m) & ~last.z), cq -= __popc((last.y ^ m) & ~last.z);
+                        }
+#pragma unroll 4
+                        for (int i = 0; i < nw; ++i) {
+                            above = st[i + 1];
+                            m = __funnelshift_r(below, above, sh);
+                            const uint2 x = *reinterpret_cast<const uint2*>(&s_x[wv][i]);
+                            ci += __popc(x.x ^ m);
+                            cq += __popc(x.y ^ m);
+                            below = above;
+                        }
+                        ones_i[p] += ci, ones_q[p] += cq;
+                    }
+                }
+                wave_sync();
+            }
+#pragma unroll
+            for (int p = 0; p < AIDED_PASSES; ++p) {
+                const int64_t I = (int64_t)a.spm - 2 * (int64_t)ones_i[p], Q = (int64_t)a.spm - 2 * (int64_t)ones_q[p];
+                acc[p] += (uint64_t)(I * I + Q * Q);
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < AIDED_PASSES; ++p) s_pow[wv][lane + 64 * p] = acc[p];
+        __syncthreads();
+        if ((int)threadIdx.x < n_code) {
+            uint64_t pw = 0;
+            for (int w = 0; w < AIDED_WAVES; ++w) pw += s_pow[w][threadIdx.x];
+            if (powers) powers[d * n_code + threadIdx.x] = pw;
+            total += pw;
+            const uint64_t kd = pw << 13 | (uint64_t)(31 - d) << 8 | (uint64_t)(255 - threadIdx.x);
+            key = kd > key ? kd : key;
+        }
+        __syncthreads();
+    }
+
+    // 5. record, 6. peak
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint64_t other = shfl_xor64(key, m);
+        key = other > key ? other : key;
+        total += shfl_xor64(total, m);
+    }
+    if (lane == 0) s_red[wv][0] = key, s_red[wv][1] = total;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    key = total = 0;
+    for (int w = 0; w < AIDED_WAVES; ++w) {
+        key = s_red[w][0] > key ? s_red[w][0] : key;
+        total += s_red[w][1];
+    }
+    gpsacq_aided r = {0, (int32_t)segments, n_code, n_dop, 255 - (int32_t)(key & 255), 31 - (int32_t)(key >> 8 & 31), 0, 0, key >> 13, total, 2 * spm * segments, 0.0};
+    r.lo_shift = aid.lo_center - K + r.best_d;
+    r.ca_shift = (int32_t)((base + (uint32_t)r.best_h) % (uint32_t)a.spm);
+    if (r.floor) r.ratio = (double)r.best / (double)r.floor;
+    if (segments < win.fit) r.flags |= GPSACQ_AIDED_SHORT;
+    if (segments < (uint64_t)a.p.min_segments) r.flags |= GPSACQ_AIDED_FEW;
+    if (r.best == 0) r.flags |= GPSACQ_AIDED_NO_POWER;
+    if (r.ratio < a.p.ratio_min) r.flags |= GPSACQ_AIDED_BELOW;
+    if (!(r.flags & (GPSACQ_AIDED_FEW | GPSACQ_AIDED_NO_POWER | GPSACQ_AIDED_BELOW))) pk_out = gpsacq_peak{(float)r.ratio, r.lo_shift, r.ca_shift, (float)r.best};
+    a.out[t] = r;
+    a.peaks_out[t] = pk_out;
+}
+
+void launch_aid_predict(const AidPredictArgs& a, hipStream_t s) {
+    const size_t n = a.n_fix * (size_t)a.chans;
+    hipLaunchKernelGGL(k_aid_predict, dim3((unsigned)((n + NAV_BLOCK - 1) / NAV_BLOCK)), dim3(NAV_BLOCK), 0, s, a);
+}
+
+void launch_aided(const AidedArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_aided, dim3((unsigned)a.n_tasks), dim3(64 * AIDED_WAVES), 0, s, a);
+}
+
+}  // namespace acq

@@ -1,0 +1,53 @@
+// aided_launch.hpp -- argument blocks and launchers of "Aided acquisition: predicted code phase and Doppler, windowed search" of
+// include/gpsacq.h: aided_kernels.hip's k_aid_predict (one lane per (fix, channel)) and k_aided (one workgroup per task).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/gpsacq.h"
+#include "nav_launch.hpp"
+
+namespace acq {
+
+static constexpr int AIDED_WAVES = 4;        // wave64s of a k_aided workgroup; wave w takes segments w, w + 4, ...
+static constexpr int AIDED_MAX_CODE_HALF = 127;  // W: 2 W + 1 <= 255 hypotheses, at most AIDED_PASSES passes of 64 lanes
+static constexpr int AIDED_MAX_DOP_HALF = 8;     // K
+static constexpr int AIDED_PASSES = 4;
+
+struct AidPredictArgs {
+    const NavEph* eph;  // [n_eph] (device)
+    int n_eph;
+    const gpsacq_fix* fix;  // [n_fix] (device)
+    const gpsacq_vel* vel;  // [n_fix] (device), or NULL: at rest
+    size_t n_fix;
+    int chans;             // 1 .. GPSACQ_FIX_MAX_SATS
+    double fs, step_hz;    // step_hz: gpsacq_info.doppler_step_hz
+    int spm, kmax;         // samples per millisecond; the grid is -kmax .. +kmax
+    gpsacq_aid_params p;
+    gpsacq_aid* out;  // [n_fix][chans] (device)
+};
+void launch_aid_predict(const AidPredictArgs& a, hipStream_t s);
+
+// the first twelve fields are RefineArgs's (gpsacq_nav.cpp fills them alike); `peaks` is peaks_in and may be NULL
+struct AidedArgs {
+    const uint32_t* words;
+    size_t n_bytes;
+    uint32_t lead;
+    size_t stride;
+    const gpsacq_task* tasks;
+    const gpsacq_peak* peaks;
+    size_t n_tasks;
+    const uint32_t* chips;
+    double fc, fs, step_hz;
+    int spm;
+    int kmax;               // the grid is -kmax .. +kmax
+    const gpsacq_aid* aid;  // [n_tasks] (device)
+    gpsacq_aided_params p;
+    gpsacq_aided* out;             // [n_tasks] (device)
+    gpsacq_peak* peaks_out;        // [n_tasks]
+    unsigned long long* powers;    // [n_tasks][2 K + 1][2 W + 1], or NULL
+};
+void launch_aided(const AidedArgs& a, hipStream_t s);
+
+}  // namespace acq

@@ -1,5 +1,5 @@
 // capture_words.hpp -- the word loop of the kernels that go back to the 1-bit capture at a search peak, once: refine_kernels.hip
-// (k_refine) and doppler_kernels.hip (k_fine_dop) include it, nothing else does.  A segment of the window is walked in the 32-sample
+// (k_refine), doppler_kernels.hip (k_fine_dop) and aided_kernels.hip (k_aided, at a predicted peak) include it, nothing else does.  A segment of the window is walked in the 32-sample
 // words of the capture's 4-byte-aligned base; window_of() is steps 1 to 3 of the text (NCO words, no hit, segments); per word word_pos() reads the samples (the capture's last bytes one at a time, nothing
 // at or beyond n_bytes), masks the bits before and after the segment, carries the code position back to the word's bit 0 and cuts
 // the ONE 32-chip window that holds every chip of the word out of the chip sequence in LDS; word_masks() then builds the carrier

@@ -218,6 +218,13 @@ struct gpsacq_engine {
     Scratch<gpsacq_doppler_fix> d_dop_fix;     // host-buffer form
     Scratch<gpsacq_coarse_prior> d_dop_prior;  // host-buffer form, and the chain's priors where the caller wants none
     Stages<2> dop_fine_t, dop_obs_t, dop_fix_t;  // around k_fine_dop, k_rate_obs_fine, k_doppler_fix
+    // aided acquisition (gpsacq_aid_predict*, gpsacq_aided_search*, gpsacq_aided_peaks_device); the host-buffer forms stage fixes and
+    // velocities in d_nav_fix / d_vel and the capture, tasks and input peaks in the d_refine_* buffers above
+    Scratch<gpsacq_aid> d_aid;  // host-buffer forms, and k_aid_predict's output where the caller of the chain wants no records
+    Scratch<gpsacq_aided> d_aided;       // host-buffer form
+    Scratch<gpsacq_peak> d_aided_peaks;  // host-buffer form: the output peaks
+    Scratch<unsigned long long> d_aided_powers;  // host-buffer form: [n_tasks][2 K + 1][2 W + 1]
+    Stages<2> aid_predict_t, aided_t;  // around k_aid_predict, around k_aided
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     Scratch<int> d_persist;
     bool persist = false;

@@ -10,7 +10,8 @@
 // fixes": gpsacq_coarse_obs*, gpsacq_coarse_fix_batch* and gpsacq_coarse_fix_peaks_device, which run coarse_kernels.hip.  Last of
 // all "Fine code phases": gpsacq_refine*, gpsacq_coarse_obs_fine* and gpsacq_coarse_fix_fine_device, which run refine_kernels.hip, and
 // "Cold snapshot fixes": gpsacq_fine_doppler*, gpsacq_rate_obs_fine*, gpsacq_doppler_fix_batch* and gpsacq_cold_fix_device, which run
-// doppler_kernels.hip.
+// doppler_kernels.hip, and "Aided acquisition": gpsacq_aid_predict*, gpsacq_aided_search* and gpsacq_aided_peaks_device, which run
+// aided_kernels.hip.
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -26,6 +27,7 @@
 #include "obs_launch.hpp"
 #include "raim_launch.hpp"
 #include "refine_launch.hpp"
+#include "aided_launch.hpp"
 #include "smooth_launch.hpp"
 
 using namespace acq;
@@ -1580,4 +1582,200 @@ extern "C" int gpsacq_doppler_last_ms(const gpsacq_engine* e, float* fine_dop_ms
     if (int rc = stage_ms(e->dop_fine_t, fine_dop_ms)) return rc;
     if (int rc = stage_ms(e->dop_obs_t, rate_obs_ms)) return rc;
     return stage_ms(e->dop_fix_t, doppler_fix_ms);
+}
+
+// ---- aided acquisition: predicted code phase and Doppler, windowed search (aided_kernels.hip) ------------------------------------
+extern "C" int gpsacq_aid_default_params(gpsacq_aid_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_aid_default_params: null argument");
+    std::memset(p, 0, sizeof *p);
+    p->elev_min_deg = 5.0;
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_default_params(gpsacq_aided_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_aided_default_params: null argument");
+    std::memset(p, 0, sizeof *p);
+    p->blocks = 16;
+    p->min_segments = 1;
+    p->code_half = 16;
+    p->dop_half = 1;
+    p->keep_snr = 25.0;    // the threshold of the search, as gpsacq_refine_default_params
+    p->ratio_min = 1.922;  // the largest ratio of 2304 measured draws on absent PRNs (1.7376) plus a quarter of its excess over 1: include/gpsacq.h
+    return GPSACQ_OK;
+}
+
+// the caller's parameters or the defaults into *out, checked
+static int aid_params(const char* who, const gpsacq_aid_params* params, gpsacq_aid_params* out) {
+    if (!params) return gpsacq_aid_default_params(out);
+    *out = *params;
+    if (!(out->elev_min_deg >= -90.0 && out->elev_min_deg <= 90.0))
+        return fail(GPSACQ_ERR_ARG, "%s: elev_min_deg %g outside [-90, 90]", who, out->elev_min_deg);
+    return GPSACQ_OK;
+}
+
+static int aided_params(const char* who, const gpsacq_aided_params* params, gpsacq_aided_params* out) {
+    if (!params) return gpsacq_aided_default_params(out);
+    *out = *params;
+    if (out->blocks < 1 || out->blocks > 64) return fail(GPSACQ_ERR_ARG, "%s: blocks %d outside 1 .. 64", who, (int)out->blocks);
+    if (out->min_segments < 1) return fail(GPSACQ_ERR_ARG, "%s: min_segments %d (must be >= 1)", who, (int)out->min_segments);
+    if (out->code_half < 0 || out->code_half > AIDED_MAX_CODE_HALF)
+        return fail(GPSACQ_ERR_ARG, "%s: code_half %d outside 0 .. %d", who, (int)out->code_half, AIDED_MAX_CODE_HALF);
+    if (out->dop_half < 0 || out->dop_half > AIDED_MAX_DOP_HALF)
+        return fail(GPSACQ_ERR_ARG, "%s: dop_half %d outside 0 .. %d", who, (int)out->dop_half, AIDED_MAX_DOP_HALF);
+    if (!std::isfinite(out->keep_snr)) return fail(GPSACQ_ERR_ARG, "%s: keep_snr %g (must be finite)", who, out->keep_snr);
+    if (!std::isfinite(out->ratio_min)) return fail(GPSACQ_ERR_ARG, "%s: ratio_min %g (must be finite)", who, out->ratio_min);
+    return GPSACQ_OK;
+}
+
+// an engine the aided kernels serve: gpsacq_refine's, and coherent
+static int aided_engine_check(const char* who, const gpsacq_engine* e) {
+    if (e->nlags > 65535) return fail(GPSACQ_ERR_UNSUPPORTED, "%s: %d samples per millisecond (the packed counts hold 65535)", who, e->nlags);
+    if (1.023e6 / e->p.fs + 1.0 / 1540.0 > REFINE_MAX_CHIPS_PER_SAMPLE)
+        return fail(GPSACQ_ERR_UNSUPPORTED, "%s: fs = %g Hz is fewer than %.2f samples per chip (a word's chips leave the kernel's window)", who, e->p.fs,
+                    1.0 / REFINE_MAX_CHIPS_PER_SAMPLE);
+    if (e->n_acc > 1) return fail(GPSACQ_ERR_UNSUPPORTED, "%s: the engine accumulates %d blocks (gpsacq_set_noncoherent)", who, e->n_acc);
+    return GPSACQ_OK;
+}
+
+static int aid_predict_check(const char* who, const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* fix, size_t n_fix, int n_chans,
+                             const gpsacq_aid_params* params, const void* aid, gpsacq_aid_params* checked) {
+    if (int rc = nav_check(who, e, eph, n_eph, fix, n_fix, aid)) return rc;
+    if (n_chans < 1 || n_chans > GPSACQ_FIX_MAX_SATS) return fail(GPSACQ_ERR_ARG, "%s: n_chans %d outside 1 .. %d", who, n_chans, GPSACQ_FIX_MAX_SATS);
+    if (int rc = aid_params(who, params, checked)) return rc;
+    return aided_engine_check(who, e);
+}
+
+static int aided_check(const char* who, const gpsacq_engine* e, const void* bits, size_t n_bytes, size_t stride, const void* aid, const void* peaks_in,
+                       size_t n_tasks, const gpsacq_aided_params* params, const void* aided, const void* peaks_out, gpsacq_aided_params* checked) {
+    if (!aided || !peaks_out || (peaks_in && peaks_in == peaks_out)) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (int rc = capture_check(who, e, bits, n_bytes, stride, aid, n_tasks, aided)) return rc;
+    if (int rc = aided_params(who, params, checked)) return rc;
+    return aided_engine_check(who, e);
+}
+
+// the ephemerides up, then k_aid_predict timed; every argument has been checked
+static int aid_predict_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel, size_t n_fix, int n_chans,
+                               const gpsacq_aid_params& ap, void* d_aid) {
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    AidPredictArgs a{};
+    a.eph = e->d_nav_eph, a.n_eph = n_eph;
+    a.fix = (const gpsacq_fix*)d_fix, a.vel = (const gpsacq_vel*)d_vel;
+    a.n_fix = n_fix, a.chans = n_chans;
+    a.fs = e->p.fs, a.step_hz = e->p.fs / N_FFT * e->dstride / e->sub;  // gpsacq_info.doppler_step_hz
+    a.spm = e->nlags, a.kmax = e->kmax;
+    a.p = ap;
+    a.out = (gpsacq_aid*)d_aid;
+    if (int rc = e->aid_predict_t.begin(e->stream)) return rc;
+    launch_aid_predict(a, e->stream);
+    if (int rc = e->aid_predict_t.mark(1, e->stream)) return rc;
+    return e->aid_predict_t.finish();
+}
+
+// k_aided timed; every argument has been checked
+static int aided_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_aid,
+                         const void* d_peaks_in, size_t n_tasks, const gpsacq_aided_params& sp, void* d_aided, void* d_peaks_out, void* d_powers) {
+    if (int rc = ensure_track_chips(e)) return rc;
+    AidedArgs a{};
+    capture_args(e, d_bits, n_bytes, stride, d_tasks, d_peaks_in, n_tasks, a);
+    a.kmax = e->kmax;
+    a.aid = (const gpsacq_aid*)d_aid;
+    a.p = sp;
+    a.out = (gpsacq_aided*)d_aided;
+    a.peaks_out = (gpsacq_peak*)d_peaks_out;
+    a.powers = (unsigned long long*)d_powers;
+    if (int rc = e->aided_t.begin(e->stream)) return rc;
+    launch_aided(a, e->stream);
+    if (int rc = e->aided_t.mark(1, e->stream)) return rc;
+    return e->aided_t.finish();
+}
+
+extern "C" int gpsacq_aid_predict_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel, size_t n_fix,
+                                         int n_chans, const gpsacq_aid_params* params, void* d_aid, int sync) {
+    gpsacq_aid_params ap;
+    if (int rc = aid_predict_check("gpsacq_aid_predict", e, eph, n_eph, d_fix, n_fix, n_chans, params, d_aid, &ap)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = aid_predict_enqueue(e, eph, n_eph, d_fix, d_vel, n_fix, n_chans, ap, d_aid)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aid_predict(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_fix* fix, const gpsacq_vel* vel, size_t n_fix,
+                                  int n_chans, const gpsacq_aid_params* params, gpsacq_aid* aid_out) {
+    gpsacq_aid_params ap;
+    if (int rc = aid_predict_check("gpsacq_aid_predict", e, eph, n_eph, fix, n_fix, n_chans, params, aid_out, &ap)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n = n_fix * (size_t)n_chans;
+    if (int rc = e->d_aid.grow(n, e->stream)) return rc;
+    if (int rc = upload(e, e->d_nav_fix, fix, n_fix)) return rc;
+    if (vel)
+        if (int rc = upload(e, e->d_vel, vel, n_fix)) return rc;
+    if (int rc = aid_predict_enqueue(e, eph, n_eph, e->d_nav_fix, vel ? e->d_vel.p : nullptr, n_fix, n_chans, ap, e->d_aid)) return rc;
+    if (int rc = download(e, aid_out, e->d_aid, n)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_search_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_aid,
+                                          const void* d_peaks_in, size_t n_tasks, const gpsacq_aided_params* params, void* d_aided,
+                                          void* d_peaks_out, void* d_powers_out, int sync) {
+    gpsacq_aided_params sp;
+    if (int rc = aided_check("gpsacq_aided_search", e, d_bits, n_bytes, stride, d_aid, d_peaks_in, n_tasks, params, d_aided, d_peaks_out, &sp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = aided_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_aid, d_peaks_in, n_tasks, sp, d_aided, d_peaks_out, d_powers_out)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_search(gpsacq_engine* e, const uint8_t* bits, size_t n_bytes, size_t stride, const gpsacq_task* tasks, const gpsacq_aid* aid,
+                                   const gpsacq_peak* peaks_in, size_t n_tasks, const gpsacq_aided_params* params, gpsacq_aided* aided_out,
+                                   gpsacq_peak* peaks_out, uint64_t* powers_out) {
+    gpsacq_aided_params sp;
+    if (int rc = aided_check("gpsacq_aided_search", e, bits, n_bytes, stride, aid, peaks_in, n_tasks, params, aided_out, peaks_out, &sp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_pow = n_tasks * (size_t)(2 * sp.dop_half + 1) * (size_t)(2 * sp.code_half + 1);
+    if (int rc = e->d_aided.grow(n_tasks, e->stream)) return rc;
+    if (int rc = e->d_aided_peaks.grow(n_tasks, e->stream)) return rc;
+    if (powers_out)
+        if (int rc = e->d_aided_powers.grow(n_pow, e->stream)) return rc;
+    if (tasks)
+        if (int rc = upload(e, e->d_refine_tasks, tasks, n_tasks)) return rc;
+    if (peaks_in)
+        if (int rc = upload(e, e->d_refine_peaks, peaks_in, n_tasks)) return rc;
+    if (int rc = upload(e, e->d_refine_bits, bits, n_bytes)) return rc;
+    if (int rc = upload(e, e->d_aid, aid, n_tasks)) return rc;
+    if (int rc = aided_enqueue(e, e->d_refine_bits, n_bytes, stride, tasks ? e->d_refine_tasks.p : nullptr, e->d_aid,
+                               peaks_in ? e->d_refine_peaks.p : nullptr, n_tasks, sp, e->d_aided, e->d_aided_peaks,
+                               powers_out ? e->d_aided_powers.p : nullptr))
+        return rc;
+    if (int rc = download(e, aided_out, e->d_aided, n_tasks)) return rc;
+    if (int rc = download(e, peaks_out, e->d_aided_peaks, n_tasks)) return rc;
+    if (int rc = download(e, (unsigned long long*)powers_out, e->d_aided_powers, n_pow)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_peaks_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel,
+                                         const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks_in, size_t n_fix,
+                                         int n_chans, const gpsacq_aid_params* aid_par, const gpsacq_aided_params* aided_par, void* d_aid,
+                                         void* d_aided, void* d_peaks_out, int sync) {
+    const char* who = "gpsacq_aided_peaks";
+    gpsacq_aid_params ap;
+    gpsacq_aided_params sp;
+    if (int rc = aid_predict_check(who, e, eph, n_eph, d_fix, n_fix, n_chans, aid_par, d_aided, &ap)) return rc;
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    if (int rc = aided_check(who, e, d_bits, n_bytes, stride, d_aided, d_peaks_in, n_tasks, aided_par, d_aided, d_peaks_out, &sp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = or_own(e, d_aid, e->d_aid, n_tasks)) return rc;
+    if (int rc = aid_predict_enqueue(e, eph, n_eph, d_fix, d_vel, n_fix, n_chans, ap, d_aid)) return rc;
+    if (int rc = aided_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_aid, d_peaks_in, n_tasks, sp, d_aided, d_peaks_out, nullptr)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_last_ms(const gpsacq_engine* e, float* predict_ms, float* search_ms) {
+    if (!e || (!e->aid_predict_t.ran() && !e->aided_t.ran()))
+        return fail(GPSACQ_ERR_ARG, "gpsacq_aided_last_ms: no gpsacq_aid_predict or gpsacq_aided_search call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = stage_ms(e->aid_predict_t, predict_ms)) return rc;
+    return stage_ms(e->aided_t, search_ms);
 }

@@ -1,6 +1,6 @@
 // nav_device.hpp -- the device functions the navigation kernels are written on, all in fp64: nav_kernels.hip (k_sat_state,
-// k_sat_state_rate, k_fix, k_vel), fix_kernels.hip (k_sat_view, k_fix_atm, k_raim_detect, k_raim_exclude) and coarse_kernels.hip
-// (k_coarse_fix) include it, and orbit_device.hpp, the orbit evaluation, is written on its constants; nothing else does.  Constants, the 4x4 Cholesky piece, geodetic(), the view and the two delays, and the fix solver as functions over a
+// k_sat_state_rate, k_fix, k_vel), fix_kernels.hip (k_sat_view, k_fix_atm, k_raim_detect, k_raim_exclude), coarse_kernels.hip
+// (k_coarse_fix), doppler_kernels.hip (k_doppler_fix) and aided_kernels.hip (k_aid_predict) include it, and orbit_device.hpp, the orbit evaluation, is written on its constants; nothing else does.  Constants, the 4x4 Cholesky piece, geodetic(), the view and the two delays, and the fix solver as functions over a
 // row held in registers: load_row, newton, delays, full_fix, residuals, dop_of, fill_fix.
 // No LDS, no barrier, no atomics; every loop is bounded, so a bad fix ends, it never spins.  The row is only ever indexed by
 // compile-time constants (a subset of it is a bit mask, data and not an index), so it stays in registers: the loops over the

@@ -1,7 +1,8 @@
 // orbit_device.hpp -- the orbit evaluation of include/gpsacq.h ("Navigation solver", SATELLITE STATE; "Velocity and clock drift",
-// SATELLITE RATE), once, in fp64: nav_kernels.hip (k_sat_state, k_sat_state_rate) and coarse_kernels.hip (k_coarse_fix) include it,
-// nothing else does.  Clock correction at the uncorrected satellite time, IS-GPS-200 Table 20-IV at the corrected one, and the
-// analytic time derivative of both.  Every loop is bounded.
+// SATELLITE RATE), once, in fp64: nav_kernels.hip (k_sat_state, k_sat_state_rate), coarse_kernels.hip (k_coarse_fix),
+// doppler_kernels.hip (k_doppler_fix) and aided_kernels.hip (k_aid_predict) include it, nothing else does.  Clock correction at
+// the uncorrected satellite time, IS-GPS-200 Table 20-IV at the corrected one, and the analytic time derivative of both.  Every
+// loop is bounded.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -125,6 +125,16 @@ DOPFINE_DTYPE = np.dtype([("flags", "<i4"), ("segments", "<i4"), ("lo_rate", "<u
 DOPPLER_FIX_PARAMS_DTYPE = np.dtype([("rms_max_mps", "<f8"), ("reserved", "<f8")])
 DOPPLER_FIX_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("iterations", "<i4"), ("flags", "<i4"), ("x", "<f8"), ("y", "<f8"),
                               ("z", "<f8"), ("lat", "<f8"), ("lon", "<f8"), ("alt", "<f8"), ("drift", "<f8"), ("rms", "<f8"), ("pdop", "<f8")])
+# aided acquisition (include/gpsacq.h, "Aided acquisition: predicted code phase and Doppler, windowed search")
+AID_NO_FIX, AID_NO_EPH, AID_LOW, AID_OFF_GRID = 1, 2, 4, 8
+AIDED_KEPT, AIDED_NO_AID, AIDED_SHORT, AIDED_FEW, AIDED_NO_POWER, AIDED_BELOW = 1, 2, 4, 8, 16, 32
+AID_PARAMS_DTYPE = np.dtype([("elev_min_deg", "<f8"), ("reserved", "<f8")])
+AID_DTYPE = np.dtype([("flags", "<i4"), ("ca_center", "<i4"), ("lo_center", "<i4"), ("reserved", "<i4"), ("tx_frac", "<f8"), ("doppler_hz", "<f8"),
+                      ("elev_deg", "<f8")])
+AIDED_PARAMS_DTYPE = np.dtype([("blocks", "<i4"), ("min_segments", "<i4"), ("code_half", "<i4"), ("dop_half", "<i4"), ("keep_snr", "<f8"),
+                               ("ratio_min", "<f8")])
+AIDED_DTYPE = np.dtype([("flags", "<i4"), ("segments", "<i4"), ("n_code", "<i4"), ("n_dop", "<i4"), ("best_h", "<i4"), ("best_d", "<i4"),
+                        ("lo_shift", "<i4"), ("ca_shift", "<i4"), ("best", "<u8"), ("total", "<u8"), ("floor", "<u8"), ("ratio", "<f8")])
 
 
 # carrier-smoothed observables (include/gpsacq.h "Carrier-smoothed observables")
@@ -181,7 +191,9 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_coarse_fix_fine_device", "gpsacq_refine_last_ms",
            "gpsacq_dopfine_default_params", "gpsacq_doppler_fix_default_params", "gpsacq_fine_doppler", "gpsacq_fine_doppler_device",
            "gpsacq_rate_obs_fine", "gpsacq_rate_obs_fine_device", "gpsacq_doppler_fix_batch", "gpsacq_doppler_fix_batch_device",
-           "gpsacq_cold_fix_device", "gpsacq_doppler_last_ms"]
+           "gpsacq_cold_fix_device", "gpsacq_doppler_last_ms",
+           "gpsacq_aid_default_params", "gpsacq_aided_default_params", "gpsacq_aid_predict", "gpsacq_aid_predict_device", "gpsacq_aided_search",
+           "gpsacq_aided_search_device", "gpsacq_aided_peaks_device", "gpsacq_aided_last_ms"]
 
 _lib = None
 
@@ -490,6 +502,22 @@ def load_library(path=None):
     lib.gpsacq_cold_fix_device.restype = ctypes.c_int
     lib.gpsacq_doppler_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
     lib.gpsacq_doppler_last_ms.restype = ctypes.c_int
+    lib.gpsacq_aid_default_params.argtypes = [vp]
+    lib.gpsacq_aid_default_params.restype = ctypes.c_int
+    lib.gpsacq_aided_default_params.argtypes = [vp]
+    lib.gpsacq_aided_default_params.restype = ctypes.c_int
+    lib.gpsacq_aid_predict.argtypes = [vp, vp, ctypes.c_int, vp, vp, sz, ctypes.c_int, vp, vp]
+    lib.gpsacq_aid_predict.restype = ctypes.c_int
+    lib.gpsacq_aid_predict_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, sz, ctypes.c_int, vp, vp, ctypes.c_int]
+    lib.gpsacq_aid_predict_device.restype = ctypes.c_int
+    lib.gpsacq_aided_search.argtypes = [vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.gpsacq_aided_search.restype = ctypes.c_int
+    lib.gpsacq_aided_search_device.argtypes = [vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_aided_search_device.restype = ctypes.c_int
+    lib.gpsacq_aided_peaks_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, sz, sz, vp, vp, sz, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_aided_peaks_device.restype = ctypes.c_int
+    lib.gpsacq_aided_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
+    lib.gpsacq_aided_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -665,6 +693,46 @@ def doppler_fix_params(rms_max_mps=None):
     _check(lib, lib.gpsacq_doppler_fix_default_params(out.ctypes.data_as(ctypes.c_void_p)))
     if rms_max_mps is not None:
         out["rms_max_mps"] = float(rms_max_mps)
+    return out
+
+
+def aid_params(elev_min_deg=None):
+    """gpsacq_aid_default_params: an AID_PARAMS_DTYPE record of shape (1,) -- elev_min_deg 5.0 -- with elev_min_deg replaced where
+    given (finite, -90 .. 90: ValueError otherwise; the entry points check it again)."""
+    lib = load_library()
+    out = np.zeros(1, dtype=AID_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_aid_default_params(out.ctypes.data_as(ctypes.c_void_p)))
+    if elev_min_deg is not None:
+        if not -90.0 <= float(elev_min_deg) <= 90.0:
+            raise ValueError("aid_params: elev_min_deg %g outside [-90, 90]" % elev_min_deg)
+        out["elev_min_deg"] = float(elev_min_deg)
+    return out
+
+
+def aided_params(**overrides):
+    """gpsacq_aided_default_params: an AIDED_PARAMS_DTYPE record of shape (1,) -- a window of 16 blocks, min_segments 1, code_half 16,
+    dop_half 1, keep_snr the search threshold, ratio_min the measured default -- with the named fields replaced.  Values outside
+    the bounds of include/gpsacq.h ("Aided acquisition", B) raise ValueError here; the entry points check them again."""
+    lib = load_library()
+    out = np.zeros(1, dtype=AIDED_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_aided_default_params(out.ctypes.data_as(ctypes.c_void_p)))
+    for k, v in overrides.items():
+        if k not in AIDED_PARAMS_DTYPE.names:
+            raise TypeError("aided_params: no field %r" % k)
+        if k in ("blocks", "min_segments", "code_half", "dop_half") and int(v) != v:
+            raise ValueError("aided_params: %s = %r is no whole number" % (k, v))
+        out[k] = v
+    r = out[0]
+    if not 1 <= r["blocks"] <= 64:
+        raise ValueError("aided_params: blocks %d outside 1 .. 64" % r["blocks"])
+    if r["min_segments"] < 1:
+        raise ValueError("aided_params: min_segments %d (must be >= 1)" % r["min_segments"])
+    if not 0 <= r["code_half"] <= 127:
+        raise ValueError("aided_params: code_half %d outside 0 .. 127" % r["code_half"])
+    if not 0 <= r["dop_half"] <= 8:
+        raise ValueError("aided_params: dop_half %d outside 0 .. 8" % r["dop_half"])
+    if not (np.isfinite(r["keep_snr"]) and np.isfinite(r["ratio_min"])):
+        raise ValueError("aided_params: keep_snr %g, ratio_min %g (must be finite)" % (r["keep_snr"], r["ratio_min"]))
     return out
 
 
@@ -1387,6 +1455,90 @@ class Engine:
         t = [ctypes.c_float() for _ in range(3)]
         _check(self._lib, self._lib.gpsacq_doppler_last_ms(self._h, *[ctypes.byref(x) for x in t]))
         return tuple(x.value for x in t)
+
+    # ---- aided acquisition ------------------------------------------------------------------
+    def aid_predict(self, eph, fix, n_chans, vel=None, params=None):
+        """gpsacq_aid_predict: the code phase and Doppler the first n_chans ephemerides of eph should show at the receive instant
+        of each fix (FIX_DTYPE [n_fix]; vel: VEL_DTYPE [n_fix] or None, a receiver at rest).  Returns AID_DTYPE [n_fix][n_chans].
+        params: aid_params(), None for the defaults."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        fx = np.ascontiguousarray(np.asarray(fix, dtype=FIX_DTYPE).ravel())
+        vptr = None
+        if vel is not None:
+            vl = np.ascontiguousarray(np.asarray(vel, dtype=VEL_DTYPE).ravel())
+            if vl.size != fx.size:
+                raise ValueError("one velocity per fix")
+            vptr = vl.ctypes.data_as(ctypes.c_void_p)
+        ar, ap = self._record(params, AID_PARAMS_DTYPE)
+        out = np.zeros((fx.size, int(n_chans)), dtype=AID_DTYPE)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_aid_predict(self._h, p(ep), int(ep.size), p(fx), vptr, int(fx.size), int(n_chans), ap, p(out)))
+        return out
+
+    def aid_predict_device(self, eph, d_fix_ptr, n_fix, n_chans, d_aid_ptr, d_vel_ptr=None, params=None, sync=True):
+        """gpsacq_aid_predict_device: device pointers for the fixes, the velocities (None: at rest) and the records."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        ar, ap = self._record(params, AID_PARAMS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_aid_predict_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_fix_ptr, d_vel_ptr, int(n_fix),
+                                                              int(n_chans), ap, d_aid_ptr, 1 if sync else 0))
+
+    def aided_search(self, bits, aid, tasks=None, peaks_in=None, stride=BLOCK_BYTES, params=None, powers=False):
+        """gpsacq_aided_search: the capture searched once more around the predictions `aid` (AID_DTYPE, any shape; tasks as given to
+        search(), None for the reference schedule) over a window of consecutive blocks; peaks_in (PEAK_DTYPE, as many, or None):
+        what the plain search returned, kept where its snr reaches keep_snr.  Returns (AIDED_DTYPE, PEAK_DTYPE) in the shape of aid,
+        and with powers=True also the powers, uint64 [n_tasks][2 K + 1][2 W + 1].  The snr of an aided peak is its ratio to the
+        noise floor, not a search snr.  params: aided_params(), None for the defaults."""
+        buf = np.ascontiguousarray(np.frombuffer(bits, dtype=np.uint8) if not isinstance(bits, np.ndarray) else bits.view(np.uint8))
+        if not isinstance(aid, np.ndarray) or aid.dtype != AID_DTYPE:
+            raise TypeError("aid must be an AID_DTYPE array")
+        ad = np.ascontiguousarray(aid)
+        tptr = iptr = wptr = None
+        if tasks is not None:
+            t = np.ascontiguousarray(np.asarray(tasks, dtype=np.int32).reshape(-1, 2))
+            if t.shape[0] != ad.size:
+                raise ValueError("one task per prediction")
+            tptr = t.ctypes.data_as(ctypes.c_void_p)
+        if peaks_in is not None:
+            if not isinstance(peaks_in, np.ndarray) or peaks_in.dtype != PEAK_DTYPE or peaks_in.size != ad.size:
+                raise TypeError("peaks_in must be a PEAK_DTYPE array with one peak per prediction")
+            pi = np.ascontiguousarray(peaks_in)
+            iptr = pi.ctypes.data_as(ctypes.c_void_p)
+        sr, sp = self._record(params, AIDED_PARAMS_DTYPE)
+        prm = aided_params() if sr is None else sr
+        out = np.zeros(ad.shape, dtype=AIDED_DTYPE)
+        pk = np.zeros(ad.shape, dtype=PEAK_DTYPE)
+        if powers:
+            pw = np.zeros((ad.size, 2 * int(prm["dop_half"][0]) + 1, 2 * int(prm["code_half"][0]) + 1), dtype=np.uint64)
+            wptr = pw.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_aided_search(self._h, buf.ctypes.data_as(ctypes.c_void_p), int(buf.size), int(stride), tptr,
+                                                        ad.ctypes.data_as(ctypes.c_void_p), iptr, int(ad.size), sp, out.ctypes.data_as(ctypes.c_void_p),
+                                                        pk.ctypes.data_as(ctypes.c_void_p), wptr))
+        return (out, pk, pw) if powers else (out, pk)
+
+    def aided_search_device(self, d_bits_ptr, n_bytes, d_aid_ptr, n_tasks, d_aided_ptr, d_peaks_out_ptr, stride=BLOCK_BYTES, d_tasks_ptr=None,
+                            d_peaks_in_ptr=None, d_powers_ptr=None, params=None, sync=True):
+        """gpsacq_aided_search_device: device pointers for the capture (any byte address), the predictions, the tasks (None: the
+        reference schedule), the input peaks (None: nothing is kept), the records, the output peaks and the powers (None)."""
+        sr, sp = self._record(params, AIDED_PARAMS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_aided_search_device(self._h, d_bits_ptr, int(n_bytes), int(stride), d_tasks_ptr, d_aid_ptr, d_peaks_in_ptr,
+                                                               int(n_tasks), sp, d_aided_ptr, d_peaks_out_ptr, d_powers_ptr, 1 if sync else 0))
+
+    def aided_peaks_device(self, eph, d_fix_ptr, d_bits_ptr, n_bytes, d_tasks_ptr, n_fix, n_chans, d_aided_ptr, d_peaks_out_ptr, d_vel_ptr=None,
+                           d_peaks_in_ptr=None, d_aid_ptr=None, stride=BLOCK_BYTES, aid_params=None, params=None, sync=True):
+        """gpsacq_aided_peaks_device: fixes (and velocities) -> predictions -> aided peaks in device memory, no host copy in between;
+        tasks block outer and channel inner; d_vel_ptr, d_peaks_in_ptr and d_aid_ptr may be None."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        ar, ap = self._record(aid_params, AID_PARAMS_DTYPE)
+        sr, sp = self._record(params, AIDED_PARAMS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_aided_peaks_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_fix_ptr, d_vel_ptr, d_bits_ptr,
+                                                              int(n_bytes), int(stride), d_tasks_ptr, d_peaks_in_ptr, int(n_fix), int(n_chans), ap, sp,
+                                                              d_aid_ptr, d_aided_ptr, d_peaks_out_ptr, 1 if sync else 0))
+
+    def aided_last_ms(self):
+        """Device milliseconds of the last aided calls: (k_aid_predict or 0, k_aided or 0)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(self._lib, self._lib.gpsacq_aided_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def coarse_obs_device(self, d_peaks_ptr, n_fix, n_chans, d_obs_ptr, snr_min=THRESHOLD, sync=True):
         _check(self._lib, self._lib.gpsacq_coarse_obs_device(self._h, d_peaks_ptr, int(n_fix), int(n_chans), float(snr_min), d_obs_ptr,

@@ -1792,6 +1792,184 @@ GPSACQ_API int gpsacq_cold_fix_device(gpsacq_engine* e, const gpsacq_ephemeris* 
  * stream; waits for them); a kernel that has not run reads 0.  Any pointer may be NULL. */
 GPSACQ_API int gpsacq_doppler_last_ms(const gpsacq_engine* e, float* fine_dop_ms, float* rate_obs_ms, float* doppler_fix_ms);
 
+/*
+ * ---- Aided acquisition: predicted code phase and Doppler, windowed search -------------------------------------------------------
+ *
+ * The snapshot chain above uses the satellites the FFT search finds in ONE 7.3 ms block at its threshold of 25.  A satellite 8 to
+ * 10 dB below that never enters a fix, though the capture holds it over its 117 ms -- and after the first fix the receiver knows
+ * where to look to within a sample and a Doppler grid point.  gpsacq_aid_predict turns a fix (and a velocity, where there is one)
+ * into a predicted code phase and Doppler per satellite; gpsacq_aided_search goes back to the 1-bit capture as gpsacq_refine does
+ * and sums the 1 ms prompt powers of a window of blocks over the few hypotheses around the prediction; its peaks drop into
+ * gpsacq_refine, gpsacq_fine_doppler, gpsacq_coarse_obs[_fine], gpsacq_coarse_fix_fine_device and gpsacq_track_start unchanged.
+ * (Estimated from the generator's figure, amplitude 0.151 = 45 dB-Hz, not measured: amplitude 0.03 is about 32 dB-Hz, a search snr
+ * of about 12; the sum of 117 prompt powers at the right hypothesis then stands about 8 sigma over its floor.)  THE MODEL; the
+ * kernels (csrc/aided_kernels.hip) and the reference of the tests (tests/aided_ref.py) are both written from this text.  Integer
+ * arithmetic "mod 2^N" is unsigned wrap-around as in THE CHANNEL MODEL; every fp64 expression is evaluated as written, every
+ * operation rounded by itself (no fused multiply-add).
+ *
+ * A. PREDICTION.  gpsacq_aid_predict.  INPUTS.  eph[n_eph] as for gpsacq_fix_batch.  fix[n_fix] of gpsacq_fix: its place and its
+ * (rx_ms, rx_frac) are taken as the RECEIVE INSTANT of the first sample of the row's block (FROM PEAKS of "Coarse-time fixes"
+ * makes that sample the receive instant of a row).  vel[n_fix] of gpsacq_vel, optional: NULL, or a status other than
+ * GPSACQ_VEL_OK, means v_r = 0 and drift_r = 0.  n_chans in 1 .. GPSACQ_FIX_MAX_SATS: channel c is eph[c], as in FROM PEAKS, and
+ * the records are aid[n_fix][n_chans], block outer and channel inner.  gpsacq_aid_params: elev_min_deg, finite and in [-90, 90];
+ * gpsacq_aid_default_params (host only) sets 5.0.
+ * PER (fix, channel).  Times are seconds from the receive instant; the time t is the pair (rx_ms + k folded into the week, frac)
+ * with (k, frac) FIX's split of rx_frac + t (k = floor(1e3 u), frac = u - 1e-3 k, moved by one millisecond where rounding left
+ * frac outside [0, 1e-3)).  Omega_e, c, L1 and R(a) as in "Coarse-time fixes" and VELOCITY.
+ *   LIGHT TIME: the two passes of "Coarse-time fixes" A from the fix's place r_r.
+ *       pass 1: the satellite position at the uncorrected time -75e-3, turned by R(-Omega_e 75e-3); tau = its distance to r_r / c.
+ *       pass 2: position and clock correction cc at the uncorrected time -tau, turned by R(-Omega_e tau); tau' = distance / c.
+ *   CODE.  T = cc - tau' is the uncorrected satellite time the replica shows at the receive instant; (tx_ms, tx_frac) is the pair
+ *     of T, and
+ *       ca_center = (int)nearbyint(tx_frac * fs) mod spm,      spm = gpsacq_info.num_lags
+ *     -- FROM PEAKS read backwards (tx_frac = ca_shift / fs).
+ *   DOPPLER: VELOCITY's row read backwards.  Position p, clock correction cc3, velocity v and clock_drift of the satellite at the
+ *     uncorrected time (tx_ms, tx_frac) (SATELLITE STATE, SATELLITE VELOCITY); then, exactly as VELOCITY has them,
+ *       theta = Omega_e ((double)fold(tx_ms - rx_ms) 1e-3 + ((tx_frac - cc3) - rx_frac))
+ *       r_i = R(theta) p,     v_i = R(theta) (v + Omega_e x p),     e_i = (r_i - r_r) / |r_i - r_r|
+ *       rho' = e_i . (v_i - (v_r + Omega_e x r_r)) + c drift_r - c clock_drift
+ *       doppler_hz = -(L1 / c) rho'
+ *       lo_center  = (int)nearbyint(doppler_hz / gpsacq_info.doppler_step_hz)
+ *   ELEVATION by k_sat_view's rule: (lat, lon) = FIX's LatLonAlt() of r_r, d = r_i - r_r in VIEW's local frame,
+ *     elev_deg = atan2(u, hypot(e, n)) * 180 / pi.
+ *   (nearbyint: to nearest, ties to even.)
+ * RECORD gpsacq_aid.  flags: GPSACQ_AID_NO_FIX, the fix is not GPSACQ_FIX_OK; GPSACQ_AID_NO_EPH, c >= n_eph, or the ephemeris does
+ * not pass SATELLITE STATE's rule, or r_i, tx_frac, doppler_hz or elev_deg is not finite; for these two everything else in the
+ * record is 0.  GPSACQ_AID_LOW: elev_deg < elev_min_deg.  GPSACQ_AID_OFF_GRID: |lo_center| > (gpsacq_info.num_doppler_total - 1)
+ * / 2, beyond the engine's grid (a Doppler beyond +-2^31 steps counts so too, with lo_center 0).  A record with any flag is NOT
+ * USABLE; LOW and OFF_GRID keep the rest of the record.
+ * NOT MODELLED.  The atmosphere: ionosphere and troposphere delay the code by 2 to 30 m, at most about half a sample at 5.456 MHz
+ * (55 m per sample), well inside any window.  The Doppler's own rate over the window (below 1 Hz/s).  The fix's own error enters
+ * as it is: 150 m of place or 0.5 us of receive time is one chip.
+ * THE RECEIVE INSTANT OF A COARSE-TIME FIX.  gpsacq_coarse_fix_batch reports t0 + s - b / c, and its s is good to cdop times the
+ * range noise only -- milliseconds -- which lands in rx_frac and moves EVERY prediction by the same code offset.  The fix's place
+ * and b are good: take the receive instant as t0 + nearbyint(1e3 s) 1e-3 - bias_m / c from its gpsacq_coarse_info (any whole
+ * millisecond serves: a few milliseconds of satellite motion are metres) and put that into rx_ms and rx_frac before predicting.
+ * tools/snapshot_bench.py --aided does; with the fix's own time it found 8 of 2048 weak satellites, with this one 2022 of 2024.
+ *
+ * B. WINDOWED SEARCH.  gpsacq_aided_search.  INPUTS as gpsacq_refine's: bits[n_bytes], stride, tasks[n_tasks] (NULL: the reference
+ * schedule, task t = (block t, PRN t % 32)).  aid[n_tasks]: a prediction per task (of which flags, ca_center and lo_center are
+ * read).  peaks_in[n_tasks], optional: what the plain search returned for these tasks.  gpsacq_aided_params: blocks, 1 .. 64, the
+ * length of the window; min_segments >= 1; code_half = W, 0 .. 127, and dop_half = K, 0 .. 8: the search covers 2W + 1 code
+ * phases and 2K + 1 Doppler grid points around the prediction; keep_snr and ratio_min, finite.  gpsacq_aided_default_params (host
+ * only) sets 16, 1, 16, 1, 25.0 (the threshold of the search) and ratio_min = 1.922 (DEFAULT RATIO_MIN below).
+ * PER TASK.  spm, o, FULL, the window, its segments and the flags GPSACQ_AIDED_SHORT and GPSACQ_AIDED_FEW are exactly steps 2 and 3
+ * of "Fine code phases" with this section's blocks and min_segments.
+ * 1. KEPT.  peaks_in is given and peaks_in[t].snr >= keep_snr: the output peak is peaks_in[t] byte for byte, the record is the flag
+ *    GPSACQ_AIDED_KEPT and zeros, and nothing is read from the capture.  This comes before everything below.
+ * 2. NO_AID (the record is GPSACQ_AIDED_NO_AID and zeros, the output peak is 16 zero bytes): the aid record is not usable, or its
+ *    ca_center is outside [0, spm); or the task is out of range by refine's rule (block < 0, prn outside 0 .. 31, o at or beyond
+ *    sample 8 n_bytes); or no Doppler hypothesis of step 3 is valid.
+ * 3. HYPOTHESES.  Doppler index d = 0 .. 2K with lo_shift_d = lo_center - K + d.  d is VALID when |lo_shift_d| lies on the
+ *    engine's grid (at most (num_doppler_total - 1) / 2) and refine's NCO range test passes: fc + lo_dop and 1.023e6 + ca_dop in
+ *    [0, fs) and ca_rate != 0, with lo_rate_d and ca_rate_d from step 1 of "Fine code phases".  Code index h = 0 .. 2W, with
+ *      base = (ca_center - W) mod spm        in [0, spm)
+ *      P0(h, d) = ((base + h) * ca_rate_d) mod FULL              base + h is NOT reduced mod spm
+ *      ca_shift_h = (base + h) mod spm                           what is reported
+ *    and at window sample j (the first is j = 0, sample o + j of the capture) the replica of (h, d) shows
+ *      P = (P0(h, d) + j * ca_rate_d) mod FULL = ((base + h + j) * ca_rate_d) mod FULL,     chip[P >> 32]:
+ *    the replica of h at sample j is the replica of h = 0 at sample j + h, exactly -- ONE chip stream per (segment, d).  The
+ *    carrier is refine's, ph = j * lo_rate_d (mod 2^32), counted from the window's first sample and the same for every h.  The
+ *    segments are the window's, fixed, whatever h is.
+ * 4. SUMS.  I_P, Q_P: the prompt sums of THE CHANNEL MODEL over the spm samples of a segment, as step 4 of "Fine code phases" has
+ *    them.  power(h, d) = sum over the segments of I_P^2 + Q_P^2, uint64 (a segment adds at most 2 spm^2; 64 blocks stay below
+ *    2^39).  For base + h < spm this is bit for bit the `prompt` field gpsacq_refine returns for a peak (ca_shift_h, lo_shift_d).
+ *    Across the wrap (base + h >= spm) refine starts from ((base + h - spm) * ca_rate) mod FULL: the two differ by
+ *    (spm * ca_rate) mod FULL of code position, the code Doppler's creep over one millisecond: ca_dop * 1 ms, 3.2e-3 chip at 5 kHz
+ *    (far below the sample grid, but enough to move a sample across a chip boundary: the sums differ in a few units).
+ * 5. RECORD gpsacq_aided: flags, segments, n_code = 2W + 1, n_dop = 2K + 1, and
+ *      best   = the largest power over the valid d and all h; its place (best_d, best_h) is the hypothesis with the largest KEY
+ *               (power, -d, -h) in lexicographic order -- among equal powers the smaller d, then the smaller h -- so the result
+ *               does not depend on the order of any reduction
+ *      lo_shift = lo_center - K + best_d,     ca_shift = ca_shift_(best_h)
+ *      total  = the sum of power(h, d) over the valid d and all h
+ *      floor  = 2 * spm * segments           what a +-1 stream uncorrelated with the replica leaves: E[I^2 + Q^2] = 2 spm
+ *      ratio  = (double)best / (double)floor,   0.0 where floor == 0
+ *    GPSACQ_AIDED_NO_POWER: best == 0.  GPSACQ_AIDED_BELOW: ratio < ratio_min.  DETECTED: none of NO_AID, FEW, NO_POWER, BELOW.
+ *    Every record but KEPT and NO_AID keeps all its fields whatever its flags.
+ * 6. OUTPUT PEAK (gpsacq_peak).  Detected: { (float)ratio, lo_shift, ca_shift, (float)best }.  Otherwise 16 zero bytes.  AN AIDED
+ *    PEAK'S snr IS ON THE RATIO SCALE (1 = the floor), not on the search's: give the calls downstream snr_min <= ratio_min, which
+ *    passes every aided peak and, while ratio_min <= keep_snr, every KEPT peak too.
+ * 7. powers_out[n_tasks][2K + 1][2W + 1], optional, uint64: power(h, d) at [t][d][h]; the rows of invalid d are 0, KEPT and NO_AID
+ *    tasks are all 0.
+ * LIMITS.  A segment is one millisecond of coherent sum, 1 kHz wide: neighbouring Doppler grid points (136 Hz at 5.456 MHz) differ
+ * by a few per cent of power, so best_d picks among near equals and lo_shift is good to +-K grid points, no better;
+ * gpsacq_fine_doppler takes it from there.  ca_shift is a whole sample, as a search peak's; gpsacq_refine takes it from there.
+ * DEFAULT RATIO_MIN.  No closed form covers the floor: the C/A cross-correlation of the strong satellites is part of it.  Measured
+ * (tools/aided_floor.py, on the CPU with tests/aided_ref.py): the scene of tools/snapshot_bench.py (eight satellites at amplitude
+ * 0.2, noise sigma 1, fs = 5.456 MHz) made with tests/gen_ref.py and searched for its 24 ABSENT PRNs with the defaults, 2304 draws of
+ * (window start, lo_center, PRN, ca_center), 99 hypotheses each: the largest ratio was 1.7376 (median 1.348, 99.9 % below 1.688).  The default is that
+ * plus a quarter of its excess over 1: 1.7376 + 0.7376 / 4 = 1.922.  It belongs to 16 blocks, W = 16, K = 1: more hypotheses or fewer segments raise the
+ * floor's maximum, and a caller who changes them measures again.
+ * WHAT TO EXPECT.  Measured on the CPU (tests/test_aided.py, 16 blocks, five satellites at 0.2 beside the weak one): amplitude 0.03
+ * reads ratio 1.63, 0.04 reads 1.98, 0.045 reads 2.20, 0.05 reads 2.45, where the plain search gives all of them an snr of 15 to 16,
+ * a noise peak.  So the default detects from about amplitude 0.04 (some 33.5 dB-Hz on the generator's scale, estimated), not from the
+ * 0.03 first hoped for.  Measured on an MI355X (tools/snapshot_bench.py --aided, 1024 blocks, two satellites at 0.05 and two absent
+ * PRNs per block, shader clock not read): 2022 of 2024 weak tasks detected, all at the true code phase (17.3 m rms, whole samples),
+ * median ratio 2.49; no detection in 2048 absent tasks, largest ratio 1.696.
+ *
+ * C. THE CHAIN.  gpsacq_aided_peaks_device: k_aid_predict then k_aided on the engine's stream, no host copy in between, from eph,
+ * d_fix[n_fix], d_vel[n_fix] (may be NULL), the capture, d_tasks[n_fix * n_chans] (block outer, channel inner: task b * n_chans
+ * + c = block b against the PRN of eph[c]; NULL is the reference schedule) and d_peaks_in (may be NULL) to d_aid (may be NULL:
+ * engine scratch), d_aided and d_peaks_out, exactly what the two calls give.
+ *
+ * gpsacq_aid_predict, gpsacq_aided_search: host pointers, return after completion.  The _device forms: device pointers for
+ * everything but eph and the params (NULL: the defaults), bits at any byte address; work on the engine's stream, sync != 0
+ * waits; host and device form agree byte for byte.  peaks_out must not be peaks_in.  Argument errors -- a NULL pointer (vel,
+ * peaks_in, powers_out and d_aid of the chain may be NULL), n_fix or n_tasks == 0, n_bytes == 0, a parameter or the stride outside
+ * its bounds, n_chans outside 1..GPSACQ_FIX_MAX_SATS, n_eph <= 0 -- return GPSACQ_ERR_ARG, launch nothing and write nothing.
+ * GPSACQ_ERR_UNSUPPORTED: the engines gpsacq_refine refuses (num_lags > 65535, fs below 1.138 MHz) and an engine in non-coherent
+ * mode (gpsacq_set_noncoherent with more than one block); a finer Doppler grid (gpsacq_set_doppler_step) is supported, lo_center
+ * and lo_shift then count its points.
+ * Kernels (csrc/aided_kernels.hip).  k_aid_predict: one lane per (fix, channel), the orbit from csrc/orbit_device.hpp, the frame
+ * from csrc/nav_device.hpp.  k_aided: one workgroup of four wave64 per task; a wave owns whole segments.  Per (segment, d) its
+ * lanes build, once per 32-sample word and with k_refine's word loop (csrc/capture_words.hpp), the samples xor-ed with the two
+ * carrier masks and the ONE chip-mask stream of spm + 2W samples into LDS; then lane h (h + 64, ... in further passes over the
+ * same masks) walks the segment's words, cuts its own chip mask out of two neighbouring stream words with a funnel shift by
+ * h & 31 at word offset h >> 5, takes two xor-popcounts per word, squares its own I and Q and adds into its own uint64.  No
+ * cross-lane reduction inside a segment, no atomics; the four waves' sums meet in LDS once per d, and the best hypothesis is the
+ * maximum of a packed key.  Every loop is bounded by kernel arguments, every LDS index by the host-checked limits
+ * (spm <= 65535, W <= 127, K <= 8).
+ *
+ * OUT OF SCOPE.  8-bit IQ input, accumulated or re-aligned searches, fs above 10 MHz, multi-GPU, gps_test and gps_track.  The
+ * correlator, the search and every existing record stay as they are.
+ */
+#define GPSACQ_AID_NO_FIX 1      /* the fix is not GPSACQ_FIX_OK: the record is this flag and zeros */
+#define GPSACQ_AID_NO_EPH 2      /* no valid ephemeris, or a state that is not finite: the record is this flag and zeros */
+#define GPSACQ_AID_LOW 4         /* elev_deg < elev_min_deg */
+#define GPSACQ_AID_OFF_GRID 8    /* |lo_center| beyond the engine's Doppler grid */
+typedef struct { double elev_min_deg; double reserved; } gpsacq_aid_params;                                                       /* 16 bytes */
+typedef struct { int32_t flags, ca_center, lo_center, reserved; double tx_frac, doppler_hz, elev_deg; } gpsacq_aid;                /* 40 bytes */
+#define GPSACQ_AIDED_KEPT 1      /* peaks_in[t].snr >= keep_snr: the output peak is the input peak, the record this flag and zeros */
+#define GPSACQ_AIDED_NO_AID 2    /* no usable prediction, a task out of range or no valid Doppler hypothesis: this flag and zeros */
+#define GPSACQ_AIDED_SHORT 4     /* the capture ends before the window does */
+#define GPSACQ_AIDED_FEW 8       /* segments < min_segments */
+#define GPSACQ_AIDED_NO_POWER 16 /* best == 0 */
+#define GPSACQ_AIDED_BELOW 32    /* ratio < ratio_min */
+typedef struct { int32_t blocks, min_segments, code_half, dop_half; double keep_snr, ratio_min; } gpsacq_aided_params;             /* 32 bytes */
+typedef struct { int32_t flags, segments, n_code, n_dop, best_h, best_d, lo_shift, ca_shift; uint64_t best, total, floor;
+                 double ratio; } gpsacq_aided;                                                                                   /* 64 bytes */
+GPSACQ_API int gpsacq_aid_default_params(gpsacq_aid_params* p);       /* host only */
+GPSACQ_API int gpsacq_aided_default_params(gpsacq_aided_params* p);   /* host only */
+GPSACQ_API int gpsacq_aid_predict(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_fix* fix /* [n_fix] */,
+                                  const gpsacq_vel* vel /* [n_fix] or NULL */, size_t n_fix, int n_chans, const gpsacq_aid_params* params,
+                                  gpsacq_aid* aid_out /* [n_fix][n_chans] */);
+GPSACQ_API int gpsacq_aid_predict_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel, size_t n_fix,
+                                         int n_chans, const gpsacq_aid_params* params, void* d_aid, int sync);
+GPSACQ_API int gpsacq_aided_search(gpsacq_engine* e, const uint8_t* bits, size_t n_bytes, size_t stride, const gpsacq_task* tasks, const gpsacq_aid* aid,
+                                   const gpsacq_peak* peaks_in /* or NULL */, size_t n_tasks, const gpsacq_aided_params* params,
+                                   gpsacq_aided* aided_out, gpsacq_peak* peaks_out, uint64_t* powers_out /* [n_tasks][2K + 1][2W + 1] or NULL */);
+GPSACQ_API int gpsacq_aided_search_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_aid,
+                                          const void* d_peaks_in, size_t n_tasks, const gpsacq_aided_params* params, void* d_aided,
+                                          void* d_peaks_out, void* d_powers_out, int sync);
+GPSACQ_API int gpsacq_aided_peaks_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel,
+                                         const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks_in, size_t n_fix,
+                                         int n_chans, const gpsacq_aid_params* aid_params, const gpsacq_aided_params* aided_params, void* d_aid,
+                                         void* d_aided, void* d_peaks_out, int sync);
+/* device time of k_aid_predict and k_aided as last run on this engine, milliseconds (HIP events on its stream; waits for them); a
+ * kernel that has not run reads 0.  Either pointer may be NULL. */
+GPSACQ_API int gpsacq_aided_last_ms(const gpsacq_engine* e, float* predict_ms, float* search_ms);
+
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);
 

@@ -12,7 +12,7 @@ The generator runs every satellite at the Doppler it has in the middle of the ca
 away from that instant the truth is off by the range acceleration (metres over 15 s), well below the 55 m a whole-sample code phase
 is worth at 5.456 MHz.
 
-    python tools/snapshot_bench.py [--blocks 2048] [--reps 5] [--refine [--refine-blocks 16]] [--cold]
+    python tools/snapshot_bench.py [--blocks 2048] [--reps 5] [--refine [--refine-blocks 16]] [--cold] [--aided [--weak-amplitude 0.05]]
 
 --refine: the capture is made K - 1 blocks longer (K = --refine-blocks) so that every searched block has its whole window, and
 each repetition also runs gpsacq_coarse_fix_fine_device on the same capture, tasks and peaks: k_refine (the fine code phases of
@@ -28,6 +28,16 @@ of the repetitions, beside refine_ms and search_ms of the same run), the error o
 and worst over the true hits, beside the bin centres'), their coherence (min, median), the Doppler fixes' place error (median,
 worst), the distribution of their rms in m/s (the default rms_max_mps must stay at or above three times its maximum), and the cold
 fixes' position error beside the warm fine fixes' of the same blocks.
+
+--aided: the --refine scene (it implies --refine) with the constellation's other four satellites as channels 8 to 11: two in the
+capture at --weak-amplitude, two ABSENT (a prediction, no signal).  Every block is searched for all twelve; the first fine fix
+comes from the strong ones (the weak ones stay below the threshold), then each repetition runs gpsacq_aided_peaks_device on those
+fixes -- k_aid_predict and k_aided ("Aided acquisition" of include/gpsacq.h; elev_min_deg = -90, the four extra satellites are not
+all above the horizon) with the search's peaks as peaks_in -- and gpsacq_coarse_fix_fine_device once more on the merged peaks at
+snr_min = ratio_min.  The line gains, all from one run: the weak tasks detected and the false detections on the absent PRNs; the
+code error of the detected weak peaks against the generator's law; the position error with and without the aided satellites on the
+same blocks; aided_ms (k_aided) and aid_predict_ms beside refine_ms and search_ms, and the cost of one hypothesis of k_aided beside
+one replica of k_refine (k_refine's time over three replicas per hit).
 """
 import argparse
 import json
@@ -48,8 +58,10 @@ def main():
     ap.add_argument("--refine", action="store_true", help="also refine the peaks below a sample and fix from the fine code phases")
     ap.add_argument("--refine-blocks", type=int, default=16, help="window of the refinement, in blocks (1 .. 64)")
     ap.add_argument("--cold", action="store_true", help="also fix every block with no prior of place: fine Doppler, Doppler fix, fine fix")
+    ap.add_argument("--aided", action="store_true", help="also search weak satellites around the prediction of the first fix")
+    ap.add_argument("--weak-amplitude", type=float, default=0.05, help="amplitude of the two weak satellites of --aided")
     a = ap.parse_args()
-    a.refine = a.refine or a.cold
+    a.refine = a.refine or a.cold or a.aided
 
     import numpy as np
     import torch
@@ -65,6 +77,12 @@ def main():
     mid = a.blocks // 2
     ref_ms, ref_frac = geo["ref_ms"] + 4321, 0.6180e-3  # the receive time of the first sample of block `mid`
     sats, _ = synth_sats(geo, sel, ref_ms, ref_frac, mid * spb, FS, 0.2)
+    gen_sats = sats
+    if a.aided:  # channels 8 .. 11: two weak, two absent; only the first ten are in the capture
+        rest = [k for k in range(len(geo["ephs"])) if k not in sel]
+        more, _ = synth_sats(geo, rest, ref_ms, ref_frac, mid * spb, FS, a.weak_amplitude)
+        ephs = to_records([geo["ephs"][k] for k in list(sel) + rest])
+        gen_sats, sats = sats + more[:2], sats + more
     blk_ms, blk_frac = block_times(ref_ms, ref_frac - mid * spb / FS, a.blocks, spb, FS)
     prior = priors(geo, blk_ms, seed=3, km=30.0, secs=30.0)
     tasks = np.array([(b, s[0] - 1) for b in range(a.blocks) for s in sats], dtype=np.int32)
@@ -89,7 +107,13 @@ def main():
             d_fix_c, d_info_c = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
             cold_best = [float("inf")] * 3
         torch.cuda.synchronize()
-        eng.generate_device(d_bits.data_ptr(), n_bytes, sats, noise_sigma=1.0, seed=77)
+        if a.aided:
+            sp = gpsacq.aided_params()
+            rp_a = gpsacq.refine_params(blocks=a.refine_blocks, snr_min=float(sp["ratio_min"][0]))
+            d_aided, d_peaks_a = zeros(n_tasks * gpsacq.AIDED_DTYPE.itemsize), zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize)
+            d_fix_a, d_info_a = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
+            aided_best = [float("inf")] * 2
+        eng.generate_device(d_bits.data_ptr(), n_bytes, gen_sats, noise_sigma=1.0, seed=77)
         best, search_best, refine_best = None, float("inf"), float("inf")
         for _ in range(1 + a.reps):  # the first call also allocates the engine's scratch
             eng.search_device(d_bits.data_ptr(), a.blocks, d_peaks.data_ptr(), d_tasks_ptr=d_tasks.data_ptr(), n_tasks=n_tasks, sync=True)
@@ -106,6 +130,22 @@ def main():
                                            d_prior.data_ptr(), d_fix_f.data_ptr(), d_info_f.data_ptr(), d_fine_ptr=d_fine.data_ptr(), refine_params=rp,
                                            sync=True)
                 refine_best = min(refine_best, eng.refine_last_ms()[0])
+            if a.aided:
+                # the receive instant of a coarse-time fix, good below a sample: t0 + s - b / c carries the error of s (cdop times the
+                # range noise, milliseconds) in its sub-millisecond part, t0 + nearbyint(1e3 s) ms - b / c does not (include/gpsacq.h)
+                fx = d_fix_f.cpu().numpy().view(gpsacq.FIX_DTYPE).copy()
+                nf = d_info_f.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
+                t = np.rint(nf["coarse_s"] * 1e3) * 1e-3 - nf["bias_m"] / 2.99792458e8
+                k = np.floor(t * 1e3)
+                fx["rx_ms"] = np.where(fx["status"] == 0, (prior["rx_ms"].astype(np.int64) + k.astype(np.int64)) % 604800000, 0)
+                fx["rx_frac"] = np.where(fx["status"] == 0, t - k * 1e-3, 0.0)
+                d_fix_aid = dev(fx)
+                eng.aided_peaks_device(ephs, d_fix_aid.data_ptr(), d_bits.data_ptr(), n_bytes, d_tasks.data_ptr(), a.blocks, len(sats),
+                                       d_aided.data_ptr(), d_peaks_a.data_ptr(), d_peaks_in_ptr=d_peaks.data_ptr(),
+                                       aid_params=gpsacq.aid_params(-90.0), params=sp, sync=True)
+                aided_best = [min(x, y) for x, y in zip(aided_best, eng.aided_last_ms())]
+                eng.coarse_fix_fine_device(ephs, d_bits.data_ptr(), n_bytes, d_tasks.data_ptr(), d_peaks_a.data_ptr(), a.blocks, len(sats),
+                                           d_prior.data_ptr(), d_fix_a.data_ptr(), d_info_a.data_ptr(), refine_params=rp_a, sync=True)
             if a.cold:
                 eng.cold_fix_device(ephs, d_bits.data_ptr(), n_bytes, d_tasks.data_ptr(), d_peaks.data_ptr(), d_rx.data_ptr(), a.blocks, len(sats),
                                     d_fix_c.data_ptr(), d_info_c.data_ptr(), d_dfix.data_ptr(), d_dopfine_ptr=d_dopfine.data_ptr(),
@@ -116,6 +156,11 @@ def main():
             fine = d_fine.cpu().numpy().view(gpsacq.FINE_DTYPE).reshape(a.blocks, len(sats))
             fix_f = d_fix_f.cpu().numpy().view(gpsacq.FIX_DTYPE)
             info_f = d_info_f.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
+        if a.aided:
+            aided = d_aided.cpu().numpy().view(gpsacq.AIDED_DTYPE).reshape(a.blocks, len(sats))
+            peaks_a = d_peaks_a.cpu().numpy().view(gpsacq.PEAK_DTYPE).reshape(a.blocks, len(sats))
+            fix_a = d_fix_a.cpu().numpy().view(gpsacq.FIX_DTYPE)
+            info_a = d_info_a.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
         if a.cold:
             dopfine = d_dopfine.cpu().numpy().view(gpsacq.DOPFINE_DTYPE).reshape(a.blocks, len(sats))
             dfix = d_dfix.cpu().numpy().view(gpsacq.DOPPLER_FIX_DTYPE)
@@ -185,6 +230,33 @@ def main():
             "position_error_median_warm_fine_same_blocks_m": round(float(np.median(off_f[ok_c])), 2) if ok_c.any() else None,
             "position_error_max_warm_fine_same_blocks_m": round(float(off_f[ok_c].max()), 2) if ok_c.any() else None,
             "cold_against_warm_max_m": float(gap[ok_c].max()) if ok_c.any() else None})
+    if a.aided:
+        searched = (aided["flags"] & (gpsacq.AIDED_KEPT | gpsacq.AIDED_NO_AID)) == 0
+        found = searched & ((aided["flags"] & (gpsacq.AIDED_FEW | gpsacq.AIDED_NO_POWER | gpsacq.AIDED_BELOW)) == 0)
+        weak, absent = slice(8, 10), slice(10, 12)
+        true_w = found[:, weak] & (np.abs(wrap(peaks_a["ca_shift"] / FS - want)[:, weak]) * FS <= 1.5)
+        e_aided = C * wrap(peaks_a["ca_shift"] / FS - want)[:, weak][true_w]
+        ok_a = (fix_a["status"] == 0) & (info_a["flags"] == 0) & ok_f  # the same blocks with and without the aided satellites
+        off_a = np.linalg.norm(np.stack([fix_a["x"], fix_a["y"], fix_a["z"]], 1) - geo["rx"], axis=1)
+        hyps = float(searched.sum()) * int(sp["code_half"][0] * 2 + 1) * int(sp["dop_half"][0] * 2 + 1)
+        per_hyp, per_replica = aided_best[1] * 1e6 / hyps, refine_best * 1e6 / (3.0 * max(int(hit.sum()), 1))
+        r4 = lambda v: round(float(v), 4)
+        extra.update({
+            "weak_amplitude": a.weak_amplitude, "ratio_min": float(sp["ratio_min"][0]), "aid_predict_ms": r4(aided_best[0]), "aided_ms": r4(aided_best[1]),
+            "aided_over_refine": r4(aided_best[1] / refine_best), "aided_tasks_searched": int(searched.sum()),
+            "aided_tasks_kept": int((aided["flags"] & gpsacq.AIDED_KEPT != 0).sum()), "aided_tasks_no_aid": int((aided["flags"] & gpsacq.AIDED_NO_AID != 0).sum()),
+            "aided_ns_per_hypothesis": r4(per_hyp), "refine_ns_per_replica": r4(per_replica), "replica_over_hypothesis": r4(per_replica / per_hyp),
+            "weak_search_hits": int((pk["snr"][:, weak] >= gpsacq.THRESHOLD).sum()), "weak_tasks": int(2 * a.blocks),
+            "weak_detected": int(found[:, weak].sum()), "weak_detected_at_the_true_phase": int(true_w.sum()),
+            "weak_ratio_median": r4(np.median(aided["ratio"][:, weak][searched[:, weak]])) if searched[:, weak].any() else None,
+            "absent_tasks": int(searched[:, absent].sum()), "absent_false_detections": int(found[:, absent].sum()),
+            "absent_ratio_max": r4(aided["ratio"][:, absent].max()),
+            "code_phase_rms_aided_weak_m": round(float(np.sqrt((e_aided ** 2).mean())), 2) if true_w.any() else None,
+            "aided_blocks_compared": int(ok_a.sum()), "aided_sats_used_median": float(np.median(fix_a["n_used"][ok_a])) if ok_a.any() else None,
+            "position_error_median_with_aided_m": round(float(np.median(off_a[ok_a])), 2) if ok_a.any() else None,
+            "position_error_max_with_aided_m": round(float(off_a[ok_a].max()), 2) if ok_a.any() else None,
+            "position_error_median_without_aided_same_blocks_m": round(float(np.median(off_f[ok_a])), 2) if ok_a.any() else None,
+            "position_error_max_without_aided_same_blocks_m": round(float(off_f[ok_a].max()), 2) if ok_a.any() else None})
     print(json.dumps({
         "bench": "snapshot", "device": name, "blocks": a.blocks, "sats": len(sats), "tasks": n_tasks, "prior_off_km": 30.0, "prior_off_s": 30.0,
         "search_ms": round(search_best, 4), "coarse_obs_ms": round(best[0], 4), "coarse_fix_ms": round(best[1], 4),
