@@ -56,12 +56,68 @@ __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
     return (uint64_t)hi << 32 | lo;
 }
 
-// the window of Doppler hypothesis lo_shift: refine's steps 1 to 3 on a peak that is a hit by itself
-__device__ __forceinline__ Window window_at(const AidedArgs& a, size_t t, int64_t lo_shift) {
+// the window of Doppler hypothesis lo_shift: refine's steps 1 to 3 on a peak that is a hit by itself (Args: AidedArgs or AidedCohArgs)
+template <class Args> __device__ __forceinline__ Window window_at(const Args& a, size_t t, int64_t lo_shift) {
     Window w = {false, 0, 0, 0, 0, 0, 0, 0};
     if (lo_shift < -(int64_t)a.kmax || lo_shift > (int64_t)a.kmax) return w;
     const gpsacq_peak pk = {1.0f, (int32_t)lo_shift, 0, 0.0f};
     return window_of(pk, a.tasks, t, a.fc, a.fs, a.step_hz, a.spm, 0.0, a.p.blocks, a.n_bytes, a.lead, a.stride);
+}
+
+// BUILD and WALK of one segment [a0, a1) of a window that starts at sample o, on the calling wave's sx[AIDED_CHUNK] and
+// st_all[AIDED_STREAM]: the ONE copy, for k_aided (PASSES = 4) and k_aided_coh (PASSES = 1).  Pass p serves code hypothesis
+// h = lane + 64 p; ones_i[p], ones_q[p] are the samples of the segment whose product with cos and -sin is -1 (0 for h >= n_code),
+// so that I = spm - 2 ones_i, Q = spm - 2 ones_q
+template <int PASSES>
+__device__ __forceinline__ void segment_ones(const uint32_t* words, size_t n_bytes, uint64_t a0, uint64_t a1, uint64_t o, uint64_t P0, uint32_t lo_rate,
+                                             uint32_t ca_rate, const uint32_t* s_chips, uint4* sx, uint32_t* st_all, int lane, int n_code, int extra,
+                                             uint32_t (&ones_i)[PASSES], uint32_t (&ones_q)[PASSES]) {
+    const uint64_t w1 = (a1 - 1) >> 5;
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) ones_i[p] = ones_q[p] = 0;
+    for (uint64_t c0 = a0 >> 5; c0 <= w1; c0 += AIDED_CHUNK) {
+        const int nw = w1 - c0 + 1 < (uint64_t)AIDED_CHUNK ? (int)(w1 - c0 + 1) : AIDED_CHUNK;
+        for (int i = lane; i < nw + extra; i += 64) {
+            const uint64_t wi = c0 + i;
+            const WordPos w = word_pos(words, n_bytes, wi, a0, i < nw ? a1 : (wi << 5) + 32, o, P0, 0u, lo_rate, ca_rate, s_chips);
+            uint32_t cm, sp, em, pm, lm;
+            word_masks<false>(w, 0u, lo_rate, ca_rate, cm, sp, em, pm, lm);
+            st_all[i] = pm;
+            if (i < nw) sx[i] = make_uint4(w.x ^ cm, w.x ^ ~sp, w.valid, 0u);
+        }
+        wave_sync();
+#pragma unroll
+        for (int p = 0; p < PASSES; ++p) {
+            const int h = lane + 64 * p;
+            if (h < n_code) {
+                const int off = h >> 5;
+                const uint32_t sh = (uint32_t)h & 31u;
+                const uint32_t* st = &st_all[off];
+                // the bits outside the segment, which only its first and last word have, are taken off again: the loop
+                // counts whole words
+                uint32_t below = st[0], above = st[1];
+                const uint4 first = sx[0];
+                uint32_t m = __funnelshift_r(below, above, sh);
+                uint32_t ci = 0u - __popc((first.x ^ m) & ~first.z), cq = 0u - __popc((first.y ^ m) & ~first.z);
+                if (nw > 1) {
+                    const uint4 last = sx[nw - 1];
+                    m = __funnelshift_r(st[nw - 1], st[nw], sh);
+                    ci -= __popc((last.x ^ m) & ~last.z), cq -= __popc((last.y ^ m) & ~last.z);
+                }
+#pragma unroll 4
+                for (int i = 0; i < nw; ++i) {
+                    above = st[i + 1];
+                    m = __funnelshift_r(below, above, sh);
+                    const uint2 x = *reinterpret_cast<const uint2*>(&sx[i]);
+                    ci += __popc(x.x ^ m);
+                    cq += __popc(x.y ^ m);
+                    below = above;
+                }
+                ones_i[p] += ci, ones_q[p] += cq;
+            }
+        }
+        wave_sync();
+    }
 }
 }  // namespace
 
@@ -181,52 +237,10 @@ __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided(AidedArgs a) {
         const uint64_t P0 = (uint64_t)base * ca_rate % FULL;
         uint64_t acc[AIDED_PASSES] = {0, 0, 0, 0};
         for (uint64_t s = wv; s < segments; s += AIDED_WAVES) {
-            const uint64_t a0 = o + s * spm, a1 = a0 + spm;  // the segment's samples [a0, a1), counted from the aligned base
-            const uint64_t w1 = (a1 - 1) >> 5;
-            uint32_t ones_i[AIDED_PASSES] = {0, 0, 0, 0}, ones_q[AIDED_PASSES] = {0, 0, 0, 0};  // samples whose product is -1
-            for (uint64_t c0 = a0 >> 5; c0 <= w1; c0 += AIDED_CHUNK) {
-                const int nw = w1 - c0 + 1 < (uint64_t)AIDED_CHUNK ? (int)(w1 - c0 + 1) : AIDED_CHUNK;
-                for (int i = lane; i < nw + extra; i += 64) {
-                    const uint64_t wi = c0 + i;
-                    const WordPos w = word_pos(a.words, a.n_bytes, wi, a0, i < nw ? a1 : (wi << 5) + 32, o, P0, 0u, lo_rate, ca_rate, s_chips);
-                    uint32_t cm, sp, em, pm, lm;
-                    word_masks<false>(w, 0u, lo_rate, ca_rate, cm, sp, em, pm, lm);
-                    s_stream[wv][i] = pm;
-                    if (i < nw) s_x[wv][i] = make_uint4(w.x ^ cm, w.x ^ ~sp, w.valid, 0u);
-                }
-                wave_sync();
-#pragma unroll
-                for (int p = 0; p < AIDED_PASSES; ++p) {
-                    const int h = lane + 64 * p;
-                    if (h < n_code) {
-                        const int off = h >> 5;
-                        const uint32_t sh = (uint32_t)h & 31u;
-                        const uint32_t* st = &s_stream[wv][off];
-                        // the bits outside the segment, which only its first and last word have, are taken off again: the loop
-                        // counts whole words
-                        uint32_t below = st[0], above = st[1];
-                        const uint4 first = s_x[wv][0];
-                        uint32_t m = __funnelshift_r(below, above, sh);
-                        uint32_t ci = 0u - __popc((first.x ^ m) & ~first.z), cq = 0u - __popc((first.y ^ m) & ~first.z);
-                        if (nw > 1) {
-                            const uint4 last = s_x[wv][nw - 1];
-                            m = __funnelshift_r(st[nw - 1], st[nw], sh);
-                            ci -= __popc((last.x ^ m) & ~last.z), cq -= __popc((last.y ^ m) & ~last.z);
-                        }
-#pragma unroll 4
-                        for (int i = 0; i < nw; ++i) {
-                            above = st[i + 1];
-                            m = __funnelshift_r(below, above, sh);
-                            const uint2 x = *reinterpret_cast<const uint2*>(&s_x[wv][i]);
-                            ci += __popc(x.x ^ m);
-                            cq += __popc(x.y ^ m);
-                            below = above;
-                        }
-                        ones_i[p] += ci, ones_q[p] += cq;
-                    }
-                }
-                wave_sync();
-            }
+            const uint64_t a0 = o + s * spm;  // the segment's samples [a0, a0 + spm), counted from the aligned base
+            uint32_t ones_i[AIDED_PASSES], ones_q[AIDED_PASSES];
+            segment_ones<AIDED_PASSES>(a.words, a.n_bytes, a0, a0 + spm, o, P0, lo_rate, ca_rate, s_chips, s_x[wv], s_stream[wv], lane, n_code, extra, ones_i,
+                                       ones_q);
 #pragma unroll
             for (int p = 0; p < AIDED_PASSES; ++p) {
                 const int64_t I = (int64_t)a.spm - 2 * (int64_t)ones_i[p], Q = (int64_t)a.spm - 2 * (int64_t)ones_q[p];
@@ -273,6 +287,200 @@ __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided(AidedArgs a) {
     if (!(r.flags & (GPSACQ_AIDED_FEW | GPSACQ_AIDED_NO_POWER | GPSACQ_AIDED_BELOW))) pk_out = gpsacq_peak{(float)r.ratio, r.lo_shift, r.ca_shift, (float)r.best};
     a.out[t] = r;
     a.peaks_out[t] = pk_out;
+}
+
+// ---- "Coherent aided acquisition: 20 ms sums, bit edge and fine Doppler" of include/gpsacq.h -------------------------------------
+//
+// k_aided_coh<M>: one workgroup of AIDED_WAVES wave64 per task, two stages per Doppler hypothesis d.
+//   CORRELATION.  k_aided's BUILD and WALK at one pass (2 W + 1 <= 63 hypotheses, lane h owns h): segment_ones<1>() above, the
+//     walk both kernels call; instead of squaring, lane h stores (I, Q) as an int32 pair into s_z[s * n_code + h].
+//   COHERENT.  After a barrier the work item is (h, g), item g * n_code + h on thread item % 256: neighbouring lanes read
+//     neighbouring 8-byte entries of a z row (no bank conflict), lanes of equal h and different g the same entry (a broadcast).
+//     One walk over the segments: the table entry (C | S << 16, one LDS word) at k, k += f u mod 1024; the turned sums go into
+//     the prefix (PA, PB); segment s closes the period of edge e = s mod M alone, as the prefix minus the prefix kept at that
+//     edge's last boundary (LA[e], LB[e]).  The walk is unrolled by M from a multiple of M, so e is the unrolled index and the
+//     three arrays of M live in registers.  The last, partial period of every e closes after the walk.  An edge that closes at
+//     s = 0 (e = 0) or never (e >= S) adds an empty period, 0.
+//   Per d the largest key of the workgroup is found (shuffles, one LDS step) and every thread keeps the running best and the
+//   non-coherent sum of its (h, d), which item (h, g = 0) left in s_nc.  No atomics.
+// LDS: s_chips 136 + s_x 12288 + s_stream 3200 + s_z 40960 + s_tab 4096 + s_nc 512 + s_red 32 = 61224 bytes.  s_z is indexed
+// below segments * n_code <= fit * (2 W + 1) <= COH_MAX_Z (checked by the host), s_tab below 1024 (masked), s_nc below 64.
+namespace {
+__device__ __forceinline__ uint64_t sq2(int64_t a, int64_t b) { return (uint64_t)(a * a + b * b); }
+}  // namespace
+
+template <int M> __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided_coh(AidedCohArgs a) {
+    __shared__ uint32_t s_chips[CHIP_WORDS];
+    __shared__ uint4 s_x[AIDED_WAVES][AIDED_CHUNK];
+    __shared__ uint32_t s_stream[AIDED_WAVES][AIDED_STREAM];
+    __shared__ int2 s_z[COH_MAX_Z];
+    __shared__ uint32_t s_tab[COH_TABLE];  // C[k] in the low half, S[k] in the high half
+    __shared__ unsigned long long s_nc[64];
+    __shared__ unsigned long long s_red[AIDED_WAVES];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t t = blockIdx.x;
+    const int W = a.p.code_half, K = a.p.dop_half, F = a.p.fine_half, n_code = 2 * W + 1, n_dop = 2 * K + 1, n_fine = 2 * F + 1;
+    const int row = n_fine * M * n_code;  // powers of one d
+    unsigned long long* const powers = a.powers ? a.powers + t * (size_t)(n_dop * row) : nullptr;
+
+    // 1. kept, 2. no aid: the flag and zeros
+    int blank = 0;
+    gpsacq_peak pk_out = {0.0f, 0, 0, 0.0f};
+    const gpsacq_aid aid = a.aid[t];
+    if (a.peaks) {
+        const gpsacq_peak pk = a.peaks[t];
+        if ((double)pk.snr >= a.p.keep_snr) blank = GPSACQ_AIDED_KEPT, pk_out = pk;
+    }
+    Window win = {false, 0, 0, 0, 0, 0, 0, 0};
+    if (!blank) {
+        if (aid.flags == 0 && aid.ca_center >= 0 && aid.ca_center < a.spm)
+            for (int d = 0; d < n_dop && !win.hit; ++d) win = window_at(a, t, (int64_t)aid.lo_center - K + d);
+        if (!win.hit) blank = GPSACQ_AIDED_NO_AID;
+    }
+    if (blank) {
+        if (threadIdx.x == 0) {
+            a.out[t] = gpsacq_aided_coh{blank, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0};
+            a.peaks_out[t] = pk_out;
+        }
+        if (powers)
+            for (int i = threadIdx.x; i < n_dop * row; i += 64 * AIDED_WAVES) powers[i] = 0;
+        return;
+    }
+    chips_to_lds(a.chips, win.prn, s_chips);
+    for (int i = threadIdx.x; i < COH_TABLE; i += 64 * AIDED_WAVES)
+        s_tab[i] = (uint32_t)(uint16_t)a.table[i] | (uint32_t)(uint16_t)a.table[COH_TABLE + i] << 16;
+    __syncthreads();
+
+    const uint64_t o = win.o, spm = (uint64_t)a.spm;
+    const int S = (int)win.segments;  // S * n_code <= COH_MAX_Z
+    const uint32_t base = (uint32_t)(((aid.ca_center - W) % a.spm + a.spm) % a.spm);
+    const int extra = (2 * W >> 5) + 1;
+    const int items = n_code * n_fine;
+    uint64_t best_key = 0, best_nc = 0;  // the same in every thread
+    for (int d = 0; d < n_dop; ++d) {
+        const Window wd = window_at(a, t, (int64_t)aid.lo_center - K + d);
+        if (!wd.hit) {  // every lane decides the same
+            if (powers)
+                for (int i = threadIdx.x; i < row; i += 64 * AIDED_WAVES) powers[d * row + i] = 0;
+            continue;
+        }
+        // 4. segment sums
+        const uint64_t P0 = (uint64_t)base * wd.ca_rate % FULL;
+        for (int s = wv; s < S; s += AIDED_WAVES) {
+            const uint64_t a0 = o + (uint64_t)s * spm;
+            uint32_t ones_i[1], ones_q[1];
+            segment_ones<1>(a.words, a.n_bytes, a0, a0 + spm, o, P0, wd.lo_rate, wd.ca_rate, s_chips, s_x[wv], s_stream[wv], lane, n_code, extra, ones_i, ones_q);
+            if (lane < n_code) s_z[s * n_code + lane] = make_int2(a.spm - 2 * (int32_t)ones_i[0], a.spm - 2 * (int32_t)ones_q[0]);
+        }
+        __syncthreads();
+        // 5. coherent sums
+        uint64_t key = 0;
+        for (int it = threadIdx.x; it < items; it += 64 * AIDED_WAVES) {
+            const int g = it / n_code, h = it - g * n_code;
+            const uint32_t step = (uint32_t)((g - F) * a.p.fine_step) & (COH_TABLE - 1);  // (f u) mod 1024, a true modulo
+            uint32_t k = 0;
+            int64_t PA = 0, PB = 0, LA[M], LB[M];
+            uint64_t acc[M], nc = 0;
+#pragma unroll
+            for (int j = 0; j < M; ++j) LA[j] = LB[j] = 0, acc[j] = 0;
+            for (int s0 = 0; s0 < S; s0 += M) {
+#pragma unroll
+                for (int j = 0; j < M; ++j) {
+                    const int s = s0 + j;  // s mod M == j
+                    if (s < S) {
+                        acc[j] += sq2((PA - LA[j]) >> 14, (PB - LB[j]) >> 14);
+                        LA[j] = PA, LB[j] = PB;
+                        const int2 z = s_z[s * n_code + h];
+                        const uint32_t cs = s_tab[k];
+                        const int64_t c = (int16_t)(cs & 0xffffu), sn = (int16_t)(cs >> 16);
+                        PA += z.x * c + z.y * sn;
+                        PB += z.y * c - z.x * sn;
+                        nc += sq2(z.x, z.y);
+                        k = (k + step) & (COH_TABLE - 1);
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < M; ++j) {
+                const uint64_t pw = acc[j] + sq2((PA - LA[j]) >> 14, (PB - LB[j]) >> 14);
+                if (powers) powers[d * row + (g * M + j) * n_code + h] = pw;
+                const uint64_t kd = pw << COH_KEY_SHIFT | (uint64_t)(31 - d) << 15 | (uint64_t)(15 - g) << 11 | (uint64_t)(31 - j) << 6 | (uint64_t)(63 - h);
+                key = kd > key ? kd : key;
+            }
+            if (g == 0) s_nc[h] = nc;
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const uint64_t other = shfl_xor64(key, m);
+            key = other > key ? other : key;
+        }
+        if (lane == 0) s_red[wv] = key;
+        __syncthreads();  // also: every thread is done with s_z before the next d writes it
+        for (int w = 0; w < AIDED_WAVES; ++w) key = s_red[w] > key ? s_red[w] : key;
+        if (key > best_key) best_key = key, best_nc = s_nc[63 - (int)(key & 63)];
+        // s_red and s_nc are written again only behind the next d's first barrier
+    }
+
+    // 6. record and peak
+    if (threadIdx.x != 0) return;
+    gpsacq_aided_coh r = {0, S, n_code, n_dop, n_fine, M, 63 - (int32_t)(best_key & 63), 31 - (int32_t)(best_key >> 15 & 31), 15 - (int32_t)(best_key >> 11 & 15),
+                          31 - (int32_t)(best_key >> 6 & 31), 0, 0, best_key >> COH_KEY_SHIFT, best_nc, 2 * spm * (uint64_t)S, 0.0, 0.0, 0.0};
+    r.lo_shift = aid.lo_center - K + r.best_d;
+    r.ca_shift = (int32_t)((base + (uint32_t)r.best_h) % (uint32_t)a.spm);
+    if (r.floor) r.ratio = (double)r.best / (double)r.floor;
+    const double lo_dop = a.step_hz > 0 ? r.lo_shift * a.step_hz : r.lo_shift * a.fs / 40000.0;
+    r.doppler_hz = lo_dop + ((double)((r.best_f - F) * a.p.fine_step) / 1024.0) * (a.fs / (double)a.spm);
+    if ((uint64_t)S < win.fit) r.flags |= GPSACQ_AIDED_SHORT;
+    if (S < a.p.min_segments) r.flags |= GPSACQ_AIDED_FEW;
+    if (r.best == 0) r.flags |= GPSACQ_AIDED_NO_POWER;
+    if (r.ratio < a.p.ratio_min) r.flags |= GPSACQ_AIDED_BELOW;
+    if (!(r.flags & (GPSACQ_AIDED_FEW | GPSACQ_AIDED_NO_POWER | GPSACQ_AIDED_BELOW))) pk_out = gpsacq_peak{(float)r.ratio, r.lo_shift, r.ca_shift, (float)r.best};
+    a.out[t] = r;
+    a.peaks_out[t] = pk_out;
+}
+
+// "THE RECEIVE INSTANT ON THE DEVICE": one lane per fix; the record travels as ten 64-bit words so that a copy is byte for byte
+__global__ __launch_bounds__(NAV_BLOCK) void k_aid_instant(AidInstantArgs a) {
+    const size_t i = (size_t)blockIdx.x * NAV_BLOCK + threadIdx.x;
+    if (i >= a.n_fix) return;
+    static_assert(sizeof(gpsacq_fix) == 80, "ten words");
+    union {
+        gpsacq_fix f;
+        uint64_t w[10];
+    } u;
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(a.fix + i);
+    for (int k = 0; k < 10; ++k) u.w[k] = src[k];
+    if (u.f.status == GPSACQ_FIX_OK) {
+        const gpsacq_coarse_info in = a.info[i];
+        const double tt = nearbyint(1e3 * in.coarse_s) * 1e-3 - in.bias_m / C;
+        const double k = floor(1e3 * tt);
+        if (!isfinite(in.coarse_s) || !isfinite(in.bias_m) || !(k >= -2147483648.0 && k <= 2147483647.0)) {
+            u.f.status = GPSACQ_FIX_NO_CONVERGE;
+        } else {
+            int64_t ms = ((int64_t)a.prior[i].rx_ms + (int64_t)k) % WEEK_MS;
+            if (ms < 0) ms += WEEK_MS;
+            u.f.rx_ms = (int32_t)ms;
+            u.f.rx_frac = tt - 1e-3 * k;
+        }
+    }
+    uint64_t* dst = reinterpret_cast<uint64_t*>(a.out + i);
+    for (int k = 0; k < 10; ++k) dst[k] = u.w[k];
+}
+
+void launch_aided_coh(const AidedCohArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)a.n_tasks), block(64 * AIDED_WAVES);
+    switch (a.p.coh_ms) {  // the host has checked that it is one of these
+        case 1: hipLaunchKernelGGL(k_aided_coh<1>, grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL(k_aided_coh<2>, grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(k_aided_coh<4>, grid, block, 0, s, a); break;
+        case 5: hipLaunchKernelGGL(k_aided_coh<5>, grid, block, 0, s, a); break;
+        case 10: hipLaunchKernelGGL(k_aided_coh<10>, grid, block, 0, s, a); break;
+        case 20: hipLaunchKernelGGL(k_aided_coh<20>, grid, block, 0, s, a); break;
+    }
+}
+
+void launch_aid_instant(const AidInstantArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_aid_instant, dim3((unsigned)((a.n_fix + NAV_BLOCK - 1) / NAV_BLOCK)), dim3(NAV_BLOCK), 0, s, a);
 }
 
 void launch_aid_predict(const AidPredictArgs& a, hipStream_t s) {

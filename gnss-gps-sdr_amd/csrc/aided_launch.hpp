@@ -50,4 +50,45 @@ struct AidedArgs {
 };
 void launch_aided(const AidedArgs& a, hipStream_t s);
 
+// ---- "Coherent aided acquisition" of include/gpsacq.h: k_aided_coh (one workgroup per task) and k_aid_instant (one lane per fix)
+static constexpr int COH_MAX_CODE_HALF = 31;  // W: 2 W + 1 <= 63 hypotheses, one pass of 64 lanes
+static constexpr int COH_MAX_FINE_HALF = 7;   // F
+static constexpr int COH_MAX_FINE_STEP = 512; // u, in 1/1024 cycle per segment
+static constexpr int COH_MAX_Z = 5120;        // entries of the z matrix in LDS: fit * (2 W + 1) at most
+static constexpr int COH_TABLE = 1024;        // entries of the rotation table: C[0 .. 1023], then S[0 .. 1023]
+// the key is power << 20 | 31 - d << 15 | 15 - g << 11 | 31 - e << 6 | 63 - h: the power may take 44 bits
+static constexpr int COH_KEY_SHIFT = 20;
+static_assert(2 * AIDED_MAX_DOP_HALF + 1 <= 32 && 2 * COH_MAX_FINE_HALF + 1 <= 16 && 2 * COH_MAX_CODE_HALF + 1 <= 64, "the key's fields");
+
+// AidedArgs with this section's parameters and record, and the rotation table
+struct AidedCohArgs {
+    const uint32_t* words;
+    size_t n_bytes;
+    uint32_t lead;
+    size_t stride;
+    const gpsacq_task* tasks;
+    const gpsacq_peak* peaks;
+    size_t n_tasks;
+    const uint32_t* chips;
+    double fc, fs, step_hz;
+    int spm;
+    int kmax;
+    const gpsacq_aid* aid;         // [n_tasks] (device)
+    const int16_t* table;          // [2 * COH_TABLE] (device): gpsacq_aided_coh_table's
+    gpsacq_aided_coh_params p;
+    gpsacq_aided_coh* out;         // [n_tasks] (device)
+    gpsacq_peak* peaks_out;        // [n_tasks]
+    unsigned long long* powers;    // [n_tasks][2 K + 1][2 F + 1][M][2 W + 1], or NULL
+};
+void launch_aided_coh(const AidedCohArgs& a, hipStream_t s);
+
+struct AidInstantArgs {
+    const gpsacq_fix* fix;            // [n_fix] (device)
+    const gpsacq_coarse_info* info;   // [n_fix]
+    const gpsacq_coarse_prior* prior; // [n_fix]
+    size_t n_fix;
+    gpsacq_fix* out;                  // [n_fix]; may be fix itself
+};
+void launch_aid_instant(const AidInstantArgs& a, hipStream_t s);
+
 }  // namespace acq

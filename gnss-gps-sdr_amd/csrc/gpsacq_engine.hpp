@@ -225,6 +225,14 @@ struct gpsacq_engine {
     Scratch<gpsacq_peak> d_aided_peaks;  // host-buffer form: the output peaks
     Scratch<unsigned long long> d_aided_powers;  // host-buffer form: [n_tasks][2 K + 1][2 W + 1]
     Stages<2> aid_predict_t, aided_t;  // around k_aid_predict, around k_aided
+    // coherent aided acquisition (gpsacq_aided_coh_search*, gpsacq_aid_instant*, gpsacq_aided_coh_peaks_device); the host-buffer forms
+    // stage as the aided ones do, the coarse-time records in d_coarse_info / d_coarse_prior
+    Scratch<int16_t> d_coh_table;            // the rotation table, C then S, made once
+    Scratch<gpsacq_aided_coh> d_aided_coh;   // host-buffer form
+    Scratch<unsigned long long> d_coh_powers;  // host-buffer form: [n_tasks][2 K + 1][2 F + 1][M][2 W + 1]
+    Scratch<gpsacq_fix> d_fix_instant;       // k_aid_instant's output: host-buffer form, and where the caller of the chain wants no fixes
+    Stages<4> aided_coh_t;  // before k_aid_instant, between it and k_aid_predict, between that and k_aided_coh, after it
+    int aided_coh_ran = 0;  // bit k: stage k + 1 ran a kernel in the last call
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     Scratch<int> d_persist;
     bool persist = false;

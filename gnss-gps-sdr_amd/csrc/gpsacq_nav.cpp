@@ -1653,10 +1653,9 @@ static int aided_check(const char* who, const gpsacq_engine* e, const void* bits
     return aided_engine_check(who, e);
 }
 
-// the ephemerides up, then k_aid_predict timed; every argument has been checked
-static int aid_predict_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel, size_t n_fix, int n_chans,
-                               const gpsacq_aid_params& ap, void* d_aid) {
-    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+// k_aid_predict, untimed; the ephemerides are up and every argument has been checked
+static void aid_predict_launch(gpsacq_engine* e, int n_eph, const void* d_fix, const void* d_vel, size_t n_fix, int n_chans, const gpsacq_aid_params& ap,
+                               void* d_aid) {
     AidPredictArgs a{};
     a.eph = e->d_nav_eph, a.n_eph = n_eph;
     a.fix = (const gpsacq_fix*)d_fix, a.vel = (const gpsacq_vel*)d_vel;
@@ -1665,8 +1664,15 @@ static int aid_predict_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, in
     a.spm = e->nlags, a.kmax = e->kmax;
     a.p = ap;
     a.out = (gpsacq_aid*)d_aid;
-    if (int rc = e->aid_predict_t.begin(e->stream)) return rc;
     launch_aid_predict(a, e->stream);
+}
+
+// the ephemerides up, then k_aid_predict timed; every argument has been checked
+static int aid_predict_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel, size_t n_fix, int n_chans,
+                               const gpsacq_aid_params& ap, void* d_aid) {
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    if (int rc = e->aid_predict_t.begin(e->stream)) return rc;
+    aid_predict_launch(e, n_eph, d_fix, d_vel, n_fix, n_chans, ap, d_aid);
     if (int rc = e->aid_predict_t.mark(1, e->stream)) return rc;
     return e->aid_predict_t.finish();
 }
@@ -1778,4 +1784,263 @@ extern "C" int gpsacq_aided_last_ms(const gpsacq_engine* e, float* predict_ms, f
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = stage_ms(e->aid_predict_t, predict_ms)) return rc;
     return stage_ms(e->aided_t, search_ms);
+}
+
+// ---- coherent aided acquisition: 20 ms sums, bit edge and fine Doppler (aided_kernels.hip) ----------------------------------------
+extern "C" int gpsacq_aided_coh_table(int16_t* out) {
+    if (!out) return fail(GPSACQ_ERR_ARG, "gpsacq_aided_coh_table: null argument");
+    const double pi = 3.14159265358979323846;
+    for (int k = 0; k < COH_TABLE; ++k) {
+        const double x = 2.0 * pi * (double)k / 1024.0;
+        out[k] = (int16_t)std::nearbyint(16384.0 * std::cos(x));
+        out[COH_TABLE + k] = (int16_t)std::nearbyint(16384.0 * std::sin(x));
+    }
+    return GPSACQ_OK;
+}
+
+// DEFAULT RATIO_MIN of "Coherent aided acquisition" (include/gpsacq.h): measured with tools/aided_floor.py --coherent
+static constexpr double COH_RATIO_MIN = 10.73;  // the largest ratio of 2304 draws, 8.7837, plus a quarter of its excess over 1
+
+extern "C" int gpsacq_aided_coh_default_params(gpsacq_aided_coh_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_aided_coh_default_params: null argument");
+    std::memset(p, 0, sizeof *p);
+    p->blocks = 16;
+    p->min_segments = 20;
+    p->code_half = 16;
+    p->dop_half = 1;
+    p->coh_ms = 20;
+    p->fine_half = 3;
+    p->fine_step = 25;  // 24.4 Hz at 5.456 MHz
+    p->keep_snr = 25.0;
+    p->ratio_min = COH_RATIO_MIN;  // the largest ratio of the measured draws on absent PRNs plus a quarter of its excess over 1: include/gpsacq.h
+    return GPSACQ_OK;
+}
+
+static int aided_coh_params(const char* who, const gpsacq_engine* e, const gpsacq_aided_coh_params* params, gpsacq_aided_coh_params* out) {
+    if (!params) {
+        if (int rc = gpsacq_aided_coh_default_params(out)) return rc;
+    } else {
+        *out = *params;
+    }
+    const int M = out->coh_ms;
+    if (out->blocks < 1 || out->blocks > 64) return fail(GPSACQ_ERR_ARG, "%s: blocks %d outside 1 .. 64", who, (int)out->blocks);
+    if (out->min_segments < 1) return fail(GPSACQ_ERR_ARG, "%s: min_segments %d (must be >= 1)", who, (int)out->min_segments);
+    if (out->code_half < 0 || out->code_half > COH_MAX_CODE_HALF)
+        return fail(GPSACQ_ERR_ARG, "%s: code_half %d outside 0 .. %d", who, (int)out->code_half, COH_MAX_CODE_HALF);
+    if (out->dop_half < 0 || out->dop_half > AIDED_MAX_DOP_HALF)
+        return fail(GPSACQ_ERR_ARG, "%s: dop_half %d outside 0 .. %d", who, (int)out->dop_half, AIDED_MAX_DOP_HALF);
+    if (M != 1 && M != 2 && M != 4 && M != 5 && M != 10 && M != 20) return fail(GPSACQ_ERR_ARG, "%s: coh_ms %d is none of 1, 2, 4, 5, 10, 20", who, M);
+    if (out->fine_half < 0 || out->fine_half > COH_MAX_FINE_HALF)
+        return fail(GPSACQ_ERR_ARG, "%s: fine_half %d outside 0 .. %d", who, (int)out->fine_half, COH_MAX_FINE_HALF);
+    if (out->fine_step < 1 || out->fine_step > COH_MAX_FINE_STEP)
+        return fail(GPSACQ_ERR_ARG, "%s: fine_step %d outside 1 .. %d", who, (int)out->fine_step, COH_MAX_FINE_STEP);
+    if (!std::isfinite(out->keep_snr)) return fail(GPSACQ_ERR_ARG, "%s: keep_snr %g (must be finite)", who, out->keep_snr);
+    if (!std::isfinite(out->ratio_min)) return fail(GPSACQ_ERR_ARG, "%s: ratio_min %g (must be finite)", who, out->ratio_min);
+    if (!e) return GPSACQ_OK;
+    if (int rc = aided_engine_check(who, e)) return rc;
+    const long long fit = (long long)out->blocks * 40000 / e->nlags;
+    if (fit * (2 * out->code_half + 1) > COH_MAX_Z)
+        return fail(GPSACQ_ERR_UNSUPPORTED, "%s: %lld segments of %d code phases (the z matrix holds %d entries)", who, fit, 2 * (int)out->code_half + 1,
+                    COH_MAX_Z);
+    if ((long long)M * 2 * e->nlags * ((long long)out->blocks * 40000) >= 1ll << 43)
+        return fail(GPSACQ_ERR_UNSUPPORTED, "%s: a power of %d ms sums could pass the key's 44 bits", who, M);
+    return GPSACQ_OK;
+}
+
+static int aided_coh_check(const char* who, const gpsacq_engine* e, const void* bits, size_t n_bytes, size_t stride, const void* aid, const void* peaks_in,
+                           size_t n_tasks, const gpsacq_aided_coh_params* params, const void* aided, const void* peaks_out,
+                           gpsacq_aided_coh_params* checked) {
+    if (!aided || !peaks_out || (peaks_in && peaks_in == peaks_out)) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (!e) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (int rc = aided_coh_params(who, nullptr, params, checked)) return rc;  // the parameters' own ranges first: an argument error
+    if (int rc = capture_check(who, e, bits, n_bytes, stride, aid, n_tasks, aided)) return rc;
+    return aided_coh_params(who, e, params, checked);
+}
+
+static int ensure_coh_table(gpsacq_engine* e) {
+    if (e->d_coh_table.p) return GPSACQ_OK;
+    int16_t tab[2 * COH_TABLE];
+    if (int rc = gpsacq_aided_coh_table(tab)) return rc;
+    HIPCHK(e->d_coh_table.alloc(2 * COH_TABLE));
+    HIPCHK(hipMemcpy(e->d_coh_table.p, tab, sizeof tab, hipMemcpyHostToDevice));
+    return GPSACQ_OK;
+}
+
+static int instant_check(const char* who, const gpsacq_engine* e, const void* fix, const void* info, const void* prior, size_t n_fix, const void* out) {
+    if (!e || !fix || !info || !prior || !out || n_fix == 0 || n_fix > ((size_t)1 << 31)) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    return GPSACQ_OK;
+}
+
+// what a call of this section runs: any of the three stages, in this order, each timed; every argument has been checked
+struct CohInstant {
+    const void *d_fix, *d_info, *d_prior;
+    size_t n_fix;
+    void* d_out;
+};
+struct CohPredict {
+    const gpsacq_ephemeris* eph;
+    int n_eph;
+    const void *d_fix, *d_vel;
+    size_t n_fix;
+    int n_chans;
+    gpsacq_aid_params ap;
+    void* d_aid;
+};
+struct CohSearch {
+    const void* d_bits;
+    size_t n_bytes, stride;
+    const void *d_tasks, *d_aid, *d_peaks_in;
+    size_t n_tasks;
+    gpsacq_aided_coh_params sp;
+    void *d_aided, *d_peaks_out, *d_powers;
+};
+
+static int aided_coh_enqueue(gpsacq_engine* e, const CohInstant* in, const CohPredict* pr, const CohSearch* se) {
+    if (se) {
+        if (int rc = ensure_track_chips(e)) return rc;
+        if (int rc = ensure_coh_table(e)) return rc;
+    }
+    if (pr)  // before the first event: the upload is no part of any stage's time
+        if (int rc = nav_upload_eph(e, pr->eph, pr->n_eph)) return rc;
+    e->aided_coh_ran = 0;
+    if (int rc = e->aided_coh_t.begin(e->stream)) return rc;
+    if (in) {
+        AidInstantArgs a{};
+        a.fix = (const gpsacq_fix*)in->d_fix, a.info = (const gpsacq_coarse_info*)in->d_info, a.prior = (const gpsacq_coarse_prior*)in->d_prior;
+        a.n_fix = in->n_fix;
+        a.out = (gpsacq_fix*)in->d_out;
+        launch_aid_instant(a, e->stream);
+        e->aided_coh_ran |= 1;
+    }
+    if (int rc = e->aided_coh_t.mark(1, e->stream)) return rc;
+    if (pr) {
+        aid_predict_launch(e, pr->n_eph, pr->d_fix, pr->d_vel, pr->n_fix, pr->n_chans, pr->ap, pr->d_aid);  // timed here alone: gpsacq_aided_last_ms keeps its own
+        e->aided_coh_ran |= 2;
+    }
+    if (int rc = e->aided_coh_t.mark(2, e->stream)) return rc;
+    if (se) {
+        AidedCohArgs a{};
+        capture_args(e, se->d_bits, se->n_bytes, se->stride, se->d_tasks, se->d_peaks_in, se->n_tasks, a);
+        a.kmax = e->kmax;
+        a.aid = (const gpsacq_aid*)se->d_aid;
+        a.table = e->d_coh_table;
+        a.p = se->sp;
+        a.out = (gpsacq_aided_coh*)se->d_aided;
+        a.peaks_out = (gpsacq_peak*)se->d_peaks_out;
+        a.powers = (unsigned long long*)se->d_powers;
+        launch_aided_coh(a, e->stream);
+        e->aided_coh_ran |= 4;
+    }
+    if (int rc = e->aided_coh_t.mark(3, e->stream)) return rc;
+    return e->aided_coh_t.finish();
+}
+
+static size_t coh_powers_per_task(const gpsacq_aided_coh_params& sp) {
+    return (size_t)(2 * sp.dop_half + 1) * (size_t)(2 * sp.fine_half + 1) * (size_t)sp.coh_ms * (size_t)(2 * sp.code_half + 1);
+}
+
+extern "C" int gpsacq_aided_coh_search_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_aid,
+                                              const void* d_peaks_in, size_t n_tasks, const gpsacq_aided_coh_params* params, void* d_aided,
+                                              void* d_peaks_out, void* d_powers_out, int sync) {
+    CohSearch se{d_bits, n_bytes, stride, d_tasks, d_aid, d_peaks_in, n_tasks, {}, d_aided, d_peaks_out, d_powers_out};
+    if (int rc = aided_coh_check("gpsacq_aided_coh_search", e, d_bits, n_bytes, stride, d_aid, d_peaks_in, n_tasks, params, d_aided, d_peaks_out, &se.sp))
+        return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = aided_coh_enqueue(e, nullptr, nullptr, &se)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_coh_search(gpsacq_engine* e, const uint8_t* bits, size_t n_bytes, size_t stride, const gpsacq_task* tasks, const gpsacq_aid* aid,
+                                       const gpsacq_peak* peaks_in, size_t n_tasks, const gpsacq_aided_coh_params* params, gpsacq_aided_coh* aided_out,
+                                       gpsacq_peak* peaks_out, uint64_t* powers_out) {
+    gpsacq_aided_coh_params sp;
+    if (int rc = aided_coh_check("gpsacq_aided_coh_search", e, bits, n_bytes, stride, aid, peaks_in, n_tasks, params, aided_out, peaks_out, &sp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_pow = n_tasks * coh_powers_per_task(sp);
+    if (int rc = e->d_aided_coh.grow(n_tasks, e->stream)) return rc;
+    if (int rc = e->d_aided_peaks.grow(n_tasks, e->stream)) return rc;
+    if (powers_out)
+        if (int rc = e->d_coh_powers.grow(n_pow, e->stream)) return rc;
+    if (tasks)
+        if (int rc = upload(e, e->d_refine_tasks, tasks, n_tasks)) return rc;
+    if (peaks_in)
+        if (int rc = upload(e, e->d_refine_peaks, peaks_in, n_tasks)) return rc;
+    if (int rc = upload(e, e->d_refine_bits, bits, n_bytes)) return rc;
+    if (int rc = upload(e, e->d_aid, aid, n_tasks)) return rc;
+    const CohSearch se{e->d_refine_bits, n_bytes, stride, tasks ? e->d_refine_tasks.p : nullptr, e->d_aid, peaks_in ? e->d_refine_peaks.p : nullptr, n_tasks, sp,
+                       e->d_aided_coh, e->d_aided_peaks, powers_out ? e->d_coh_powers.p : nullptr};
+    if (int rc = aided_coh_enqueue(e, nullptr, nullptr, &se)) return rc;
+    if (int rc = download(e, aided_out, e->d_aided_coh, n_tasks)) return rc;
+    if (int rc = download(e, peaks_out, e->d_aided_peaks, n_tasks)) return rc;
+    if (int rc = download(e, (unsigned long long*)powers_out, e->d_coh_powers, n_pow)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aid_instant_device(gpsacq_engine* e, const void* d_fix, const void* d_info, const void* d_prior, size_t n_fix, void* d_fix_out,
+                                         int sync) {
+    if (int rc = instant_check("gpsacq_aid_instant", e, d_fix, d_info, d_prior, n_fix, d_fix_out)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    const CohInstant in{d_fix, d_info, d_prior, n_fix, d_fix_out};
+    if (int rc = aided_coh_enqueue(e, &in, nullptr, nullptr)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aid_instant(gpsacq_engine* e, const gpsacq_fix* fix, const gpsacq_coarse_info* coarse_info, const gpsacq_coarse_prior* prior,
+                                  size_t n_fix, gpsacq_fix* fix_out) {
+    if (int rc = instant_check("gpsacq_aid_instant", e, fix, coarse_info, prior, n_fix, fix_out)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = upload(e, e->d_nav_fix, fix, n_fix)) return rc;
+    if (int rc = upload(e, e->d_coarse_info, coarse_info, n_fix)) return rc;
+    if (int rc = upload(e, e->d_coarse_prior, prior, n_fix)) return rc;
+    if (int rc = e->d_fix_instant.grow(n_fix, e->stream)) return rc;
+    const CohInstant in{e->d_nav_fix, e->d_coarse_info, e->d_coarse_prior, n_fix, e->d_fix_instant};
+    if (int rc = aided_coh_enqueue(e, &in, nullptr, nullptr)) return rc;
+    if (int rc = download(e, fix_out, e->d_fix_instant, n_fix)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_coh_peaks_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_info,
+                                             const void* d_prior, const void* d_vel, const void* d_bits, size_t n_bytes, size_t stride,
+                                             const void* d_tasks, const void* d_peaks_in, size_t n_fix, int n_chans, const gpsacq_aid_params* aid_par,
+                                             const gpsacq_aided_coh_params* coh_par, void* d_fix_instant, void* d_aid, void* d_aided, void* d_peaks_out,
+                                             int sync) {
+    const char* who = "gpsacq_aided_coh_peaks";
+    CohPredict pr{eph, n_eph, d_fix, d_vel, n_fix, n_chans, {}, nullptr};
+    // d_aid may be NULL here (engine scratch), so the two checks below are given d_aided where they test the prediction records
+    // for NULL: the chain's own required pointers are d_fix, d_bits, d_aided and d_peaks_out
+    if (int rc = aid_predict_check(who, e, eph, n_eph, d_fix, n_fix, n_chans, aid_par, d_aided, &pr.ap)) return rc;
+    if (d_info && !d_prior) return fail(GPSACQ_ERR_ARG, "%s: coarse-time records without their priors", who);
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    CohSearch se{d_bits, n_bytes, stride, d_tasks, nullptr, d_peaks_in, n_tasks, {}, d_aided, d_peaks_out, nullptr};
+    if (int rc = aided_coh_check(who, e, d_bits, n_bytes, stride, d_aided, d_peaks_in, n_tasks, coh_par, d_aided, d_peaks_out, &se.sp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = or_own(e, d_aid, e->d_aid, n_tasks)) return rc;
+    CohInstant in{d_fix, d_info, d_prior, n_fix, d_fix_instant};
+    if (d_info) {
+        if (int rc = or_own(e, in.d_out, e->d_fix_instant, n_fix)) return rc;
+        pr.d_fix = in.d_out;
+    }
+    pr.d_aid = d_aid, se.d_aid = d_aid;
+    if (int rc = aided_coh_enqueue(e, d_info ? &in : nullptr, &pr, &se)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_coh_last_ms(const gpsacq_engine* e, float* instant_ms, float* predict_ms, float* search_ms) {
+    if (!e || !e->aided_coh_t.ran())
+        return fail(GPSACQ_ERR_ARG, "gpsacq_aided_coh_last_ms: no gpsacq_aided_coh_search, gpsacq_aid_instant or gpsacq_aided_coh_peaks call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = e->aided_coh_t.wait()) return rc;
+    float* const ms[3] = {instant_ms, predict_ms, search_ms};
+    for (int k = 0; k < 3; ++k) {
+        if (!ms[k]) continue;
+        *ms[k] = 0.f;
+        if (e->aided_coh_ran >> k & 1)
+            if (int rc = e->aided_coh_t.elapsed(k, k + 1, ms[k])) return rc;
+    }
+    return GPSACQ_OK;
 }

@@ -135,6 +135,13 @@ AIDED_PARAMS_DTYPE = np.dtype([("blocks", "<i4"), ("min_segments", "<i4"), ("cod
                                ("ratio_min", "<f8")])
 AIDED_DTYPE = np.dtype([("flags", "<i4"), ("segments", "<i4"), ("n_code", "<i4"), ("n_dop", "<i4"), ("best_h", "<i4"), ("best_d", "<i4"),
                         ("lo_shift", "<i4"), ("ca_shift", "<i4"), ("best", "<u8"), ("total", "<u8"), ("floor", "<u8"), ("ratio", "<f8")])
+# coherent aided acquisition (include/gpsacq.h, "Coherent aided acquisition: 20 ms sums, bit edge and fine Doppler"); the flags are AIDED_*
+AIDED_COH_MS = (1, 2, 4, 5, 10, 20)
+AIDED_COH_PARAMS_DTYPE = np.dtype([("blocks", "<i4"), ("min_segments", "<i4"), ("code_half", "<i4"), ("dop_half", "<i4"), ("coh_ms", "<i4"),
+                                   ("fine_half", "<i4"), ("fine_step", "<i4"), ("reserved", "<i4"), ("keep_snr", "<f8"), ("ratio_min", "<f8")])
+AIDED_COH_DTYPE = np.dtype([("flags", "<i4"), ("segments", "<i4"), ("n_code", "<i4"), ("n_dop", "<i4"), ("n_fine", "<i4"), ("n_edge", "<i4"),
+                            ("best_h", "<i4"), ("best_d", "<i4"), ("best_f", "<i4"), ("best_e", "<i4"), ("lo_shift", "<i4"), ("ca_shift", "<i4"),
+                            ("best", "<u8"), ("noncoh", "<u8"), ("floor", "<u8"), ("ratio", "<f8"), ("doppler_hz", "<f8"), ("reserved", "<f8")])
 
 
 # carrier-smoothed observables (include/gpsacq.h "Carrier-smoothed observables")
@@ -193,7 +200,9 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_rate_obs_fine", "gpsacq_rate_obs_fine_device", "gpsacq_doppler_fix_batch", "gpsacq_doppler_fix_batch_device",
            "gpsacq_cold_fix_device", "gpsacq_doppler_last_ms",
            "gpsacq_aid_default_params", "gpsacq_aided_default_params", "gpsacq_aid_predict", "gpsacq_aid_predict_device", "gpsacq_aided_search",
-           "gpsacq_aided_search_device", "gpsacq_aided_peaks_device", "gpsacq_aided_last_ms"]
+           "gpsacq_aided_search_device", "gpsacq_aided_peaks_device", "gpsacq_aided_last_ms",
+           "gpsacq_aided_coh_default_params", "gpsacq_aided_coh_table", "gpsacq_aided_coh_search", "gpsacq_aided_coh_search_device",
+           "gpsacq_aid_instant", "gpsacq_aid_instant_device", "gpsacq_aided_coh_peaks_device", "gpsacq_aided_coh_last_ms"]
 
 _lib = None
 
@@ -518,6 +527,23 @@ def load_library(path=None):
     lib.gpsacq_aided_peaks_device.restype = ctypes.c_int
     lib.gpsacq_aided_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
     lib.gpsacq_aided_last_ms.restype = ctypes.c_int
+    lib.gpsacq_aided_coh_default_params.argtypes = [vp]
+    lib.gpsacq_aided_coh_default_params.restype = ctypes.c_int
+    lib.gpsacq_aided_coh_table.argtypes = [vp]
+    lib.gpsacq_aided_coh_table.restype = ctypes.c_int
+    lib.gpsacq_aided_coh_search.argtypes = [vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.gpsacq_aided_coh_search.restype = ctypes.c_int
+    lib.gpsacq_aided_coh_search_device.argtypes = [vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_aided_coh_search_device.restype = ctypes.c_int
+    lib.gpsacq_aid_instant.argtypes = [vp, vp, vp, vp, sz, vp]
+    lib.gpsacq_aid_instant.restype = ctypes.c_int
+    lib.gpsacq_aid_instant_device.argtypes = [vp, vp, vp, vp, sz, vp, ctypes.c_int]
+    lib.gpsacq_aid_instant_device.restype = ctypes.c_int
+    lib.gpsacq_aided_coh_peaks_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, sz, sz, vp, vp, sz, ctypes.c_int, vp, vp, vp, vp, vp, vp,
+                                                  ctypes.c_int]
+    lib.gpsacq_aided_coh_peaks_device.restype = ctypes.c_int
+    lib.gpsacq_aided_coh_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
+    lib.gpsacq_aided_coh_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -733,6 +759,40 @@ def aided_params(**overrides):
         raise ValueError("aided_params: dop_half %d outside 0 .. 8" % r["dop_half"])
     if not (np.isfinite(r["keep_snr"]) and np.isfinite(r["ratio_min"])):
         raise ValueError("aided_params: keep_snr %g, ratio_min %g (must be finite)" % (r["keep_snr"], r["ratio_min"]))
+    return out
+
+
+def aided_coh_params(**overrides):
+    """gpsacq_aided_coh_default_params: an AIDED_COH_PARAMS_DTYPE record of shape (1,) -- a window of 16 blocks, min_segments 20,
+    code_half 16, dop_half 1, coh_ms 20, fine_half 3, fine_step 25, keep_snr the search threshold, ratio_min the measured default --
+    with the named fields replaced.  Values outside the bounds of include/gpsacq.h ("Coherent aided acquisition", A) raise
+    ValueError here; the entry points check them again."""
+    lib = load_library()
+    out = np.zeros(1, dtype=AIDED_COH_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_aided_coh_default_params(out.ctypes.data_as(ctypes.c_void_p)))
+    for k, v in overrides.items():
+        if k not in AIDED_COH_PARAMS_DTYPE.names:
+            raise TypeError("aided_coh_params: no field %r" % k)
+        if k not in ("keep_snr", "ratio_min") and int(v) != v:
+            raise ValueError("aided_coh_params: %s = %r is no whole number" % (k, v))
+        out[k] = v
+    r = out[0]
+    for k, lo, hi in (("blocks", 1, 64), ("min_segments", 1, 2 ** 31 - 1), ("code_half", 0, 31), ("dop_half", 0, 8), ("fine_half", 0, 7),
+                      ("fine_step", 1, 512)):
+        if not lo <= r[k] <= hi:
+            raise ValueError("aided_coh_params: %s %d outside %d .. %d" % (k, r[k], lo, hi))
+    if r["coh_ms"] not in AIDED_COH_MS:
+        raise ValueError("aided_coh_params: coh_ms %d is none of %s" % (r["coh_ms"], AIDED_COH_MS))
+    if not (np.isfinite(r["keep_snr"]) and np.isfinite(r["ratio_min"])):
+        raise ValueError("aided_coh_params: keep_snr %g, ratio_min %g (must be finite)" % (r["keep_snr"], r["ratio_min"]))
+    return out
+
+
+def aided_coh_table():
+    """gpsacq_aided_coh_table: the rotation table of the coherent sums, int16 (2, 1024): row 0 is C, row 1 is S"""
+    lib = load_library()
+    out = np.zeros((2, 1024), dtype=np.int16)
+    _check(lib, lib.gpsacq_aided_coh_table(out.ctypes.data_as(ctypes.c_void_p)))
     return out
 
 
@@ -1539,6 +1599,84 @@ class Engine:
         a, b = ctypes.c_float(), ctypes.c_float()
         _check(self._lib, self._lib.gpsacq_aided_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    # ---- coherent aided acquisition -----------------------------------------------------------
+    def aided_coh_search(self, bits, aid, tasks=None, peaks_in=None, stride=BLOCK_BYTES, params=None, powers=False):
+        """gpsacq_aided_coh_search: aided_search() with coherent sums of coh_ms segments, a hypothesis for the bit edge and fine
+        Doppler hypotheses.  Returns (AIDED_COH_DTYPE, PEAK_DTYPE) in the shape of aid, and with powers=True also the powers,
+        uint64 [n_tasks][2 K + 1][2 F + 1][M][2 W + 1].  params: aided_coh_params(), None for the defaults."""
+        buf = np.ascontiguousarray(np.frombuffer(bits, dtype=np.uint8) if not isinstance(bits, np.ndarray) else bits.view(np.uint8))
+        if not isinstance(aid, np.ndarray) or aid.dtype != AID_DTYPE:
+            raise TypeError("aid must be an AID_DTYPE array")
+        ad = np.ascontiguousarray(aid)
+        tptr = iptr = wptr = None
+        if tasks is not None:
+            t = np.ascontiguousarray(np.asarray(tasks, dtype=np.int32).reshape(-1, 2))
+            if t.shape[0] != ad.size:
+                raise ValueError("one task per prediction")
+            tptr = t.ctypes.data_as(ctypes.c_void_p)
+        if peaks_in is not None:
+            if not isinstance(peaks_in, np.ndarray) or peaks_in.dtype != PEAK_DTYPE or peaks_in.size != ad.size:
+                raise TypeError("peaks_in must be a PEAK_DTYPE array with one peak per prediction")
+            pi = np.ascontiguousarray(peaks_in)
+            iptr = pi.ctypes.data_as(ctypes.c_void_p)
+        sr, sp = self._record(params, AIDED_COH_PARAMS_DTYPE)
+        prm = aided_coh_params() if sr is None else sr
+        out = np.zeros(ad.shape, dtype=AIDED_COH_DTYPE)
+        pk = np.zeros(ad.shape, dtype=PEAK_DTYPE)
+        if powers:
+            pw = np.zeros((ad.size, 2 * int(prm["dop_half"][0]) + 1, 2 * int(prm["fine_half"][0]) + 1, max(int(prm["coh_ms"][0]), 1),
+                           2 * int(prm["code_half"][0]) + 1), dtype=np.uint64)
+            wptr = pw.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_aided_coh_search(self._h, buf.ctypes.data_as(ctypes.c_void_p), int(buf.size), int(stride), tptr,
+                                                            ad.ctypes.data_as(ctypes.c_void_p), iptr, int(ad.size), sp,
+                                                            out.ctypes.data_as(ctypes.c_void_p), pk.ctypes.data_as(ctypes.c_void_p), wptr))
+        return (out, pk, pw) if powers else (out, pk)
+
+    def aided_coh_search_device(self, d_bits_ptr, n_bytes, d_aid_ptr, n_tasks, d_aided_ptr, d_peaks_out_ptr, stride=BLOCK_BYTES, d_tasks_ptr=None,
+                                d_peaks_in_ptr=None, d_powers_ptr=None, params=None, sync=True):
+        """gpsacq_aided_coh_search_device: aided_search_device()'s arguments; the records are AIDED_COH_DTYPE."""
+        sr, sp = self._record(params, AIDED_COH_PARAMS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_aided_coh_search_device(self._h, d_bits_ptr, int(n_bytes), int(stride), d_tasks_ptr, d_aid_ptr,
+                                                                   d_peaks_in_ptr, int(n_tasks), sp, d_aided_ptr, d_peaks_out_ptr, d_powers_ptr,
+                                                                   1 if sync else 0))
+
+    def aid_instant(self, fix, info, prior):
+        """gpsacq_aid_instant: the coarse-time fixes (FIX_DTYPE [n_fix]) with the receive instant a prediction needs, from their
+        COARSE_INFO_DTYPE records and the COARSE_PRIOR_DTYPE priors they were made from.  Returns FIX_DTYPE [n_fix]."""
+        fx = np.ascontiguousarray(np.asarray(fix, dtype=FIX_DTYPE).ravel())
+        nf = np.ascontiguousarray(np.asarray(info, dtype=COARSE_INFO_DTYPE).ravel())
+        pr = np.ascontiguousarray(np.asarray(prior, dtype=COARSE_PRIOR_DTYPE).ravel())
+        if nf.size != fx.size or pr.size != fx.size:
+            raise ValueError("one coarse-time record and one prior per fix")
+        out = np.zeros(fx.size, dtype=FIX_DTYPE)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_aid_instant(self._h, p(fx), p(nf), p(pr), int(fx.size), p(out)))
+        return out
+
+    def aid_instant_device(self, d_fix_ptr, d_info_ptr, d_prior_ptr, n_fix, d_fix_out_ptr, sync=True):
+        """gpsacq_aid_instant_device: device pointers; d_fix_out_ptr may be d_fix_ptr."""
+        _check(self._lib, self._lib.gpsacq_aid_instant_device(self._h, d_fix_ptr, d_info_ptr, d_prior_ptr, int(n_fix), d_fix_out_ptr, 1 if sync else 0))
+
+    def aided_coh_peaks_device(self, eph, d_fix_ptr, d_bits_ptr, n_bytes, d_tasks_ptr, n_fix, n_chans, d_aided_ptr, d_peaks_out_ptr, d_info_ptr=None,
+                               d_prior_ptr=None, d_vel_ptr=None, d_peaks_in_ptr=None, d_fix_instant_ptr=None, d_aid_ptr=None, stride=BLOCK_BYTES,
+                               aid_params=None, params=None, sync=True):
+        """gpsacq_aided_coh_peaks_device: coarse-time fixes -> receive instants -> predictions -> coherent aided peaks in device
+        memory, no host copy in between; d_info_ptr None skips the first step (the fixes are taken as they are); d_vel_ptr,
+        d_peaks_in_ptr, d_fix_instant_ptr and d_aid_ptr may be None."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        ar, ap = self._record(aid_params, AID_PARAMS_DTYPE)
+        sr, sp = self._record(params, AIDED_COH_PARAMS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_aided_coh_peaks_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_fix_ptr, d_info_ptr,
+                                                                  d_prior_ptr, d_vel_ptr, d_bits_ptr, int(n_bytes), int(stride), d_tasks_ptr,
+                                                                  d_peaks_in_ptr, int(n_fix), int(n_chans), ap, sp, d_fix_instant_ptr, d_aid_ptr,
+                                                                  d_aided_ptr, d_peaks_out_ptr, 1 if sync else 0))
+
+    def aided_coh_last_ms(self):
+        """Device milliseconds of the last coherent aided call: (k_aid_instant or 0, k_aid_predict or 0, k_aided_coh or 0)."""
+        t = [ctypes.c_float() for _ in range(3)]
+        _check(self._lib, self._lib.gpsacq_aided_coh_last_ms(self._h, *[ctypes.byref(x) for x in t]))
+        return tuple(x.value for x in t)
 
     def coarse_obs_device(self, d_peaks_ptr, n_fix, n_chans, d_obs_ptr, snr_min=THRESHOLD, sync=True):
         _check(self._lib, self._lib.gpsacq_coarse_obs_device(self._h, d_peaks_ptr, int(n_fix), int(n_chans), float(snr_min), d_obs_ptr,

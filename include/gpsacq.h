@@ -1751,7 +1751,8 @@ GPSACQ_API int gpsacq_refine_last_ms(const gpsacq_engine* e, float* refine_ms, f
  * nothing.  k_rate_obs_fine: one lane per (fix, channel).  k_doppler_fix: one lane per fix, nothing of the row in registers (the
  * light times live in engine scratch), the orbit from csrc/orbit_device.hpp.  Every loop is bounded by kernel arguments.
  *
- * OUT OF SCOPE.  Coherent sums longer than one code period and signals below about 38 dB-Hz.  Doppler rate over the window.  A
+ * OUT OF SCOPE.  Coherent sums longer than one code period and signals below about 38 dB-Hz (for satellites found from a first fix:
+ * "Coherent aided acquisition" further down).  Doppler rate over the window.  A
  * height constraint for five-satellite rows.  Solving the time error from the Dopplers.  Fusing k_fine_dop into k_refine.  8-bit
  * IQ input, accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.
  */
@@ -1969,6 +1970,157 @@ GPSACQ_API int gpsacq_aided_peaks_device(gpsacq_engine* e, const gpsacq_ephemeri
 /* device time of k_aid_predict and k_aided as last run on this engine, milliseconds (HIP events on its stream; waits for them); a
  * kernel that has not run reads 0.  Either pointer may be NULL. */
 GPSACQ_API int gpsacq_aided_last_ms(const gpsacq_engine* e, float* predict_ms, float* search_ms);
+
+/*
+ * ---- Coherent aided acquisition: 20 ms sums, bit edge and fine Doppler ------------------------------------------------------------
+ *
+ * gpsacq_aided_search squares every 1 ms prompt sum on the spot and throws its sign and phase away; its default detects from about
+ * amplitude 0.04.  gpsacq_aided_coh_search keeps the signed sums (I, Q) of a window's segments, turns them back by a Doppler finer
+ * than the grid, and adds them coherently over a data bit's M = 20 ms with a hypothesis for the bit edge -- the classic
+ * high-sensitivity step.  Its peaks drop into the same calls downstream.  THE MODEL; the kernel (k_aided_coh of
+ * csrc/aided_kernels.hip) and the reference of the tests (tests/aided_coh_ref.py) are both written from this text, with the
+ * conventions of the section above (integers mod 2^N, every fp64 operation rounded by itself).
+ *
+ * A. SEARCH.  gpsacq_aided_coh_search.  INPUTS are gpsacq_aided_search's: bits[n_bytes], stride, tasks[n_tasks] (NULL: the
+ * reference schedule), aid[n_tasks], peaks_in[n_tasks] (optional).  gpsacq_aided_coh_params:
+ *     blocks        1 .. 64          the window
+ *     min_segments  >= 1
+ *     code_half     W, 0 .. 31       2 W + 1 code phases, one pass of 64 lanes
+ *     dop_half      K, 0 .. 8        2 K + 1 Doppler grid points
+ *     coh_ms        M, one of 1, 2, 4, 5, 10, 20: the segments of a coherent sum (the divisors of a data bit worth having)
+ *     fine_half     F, 0 .. 7        2 F + 1 fine Doppler hypotheses per grid point
+ *     fine_step     u, 1 .. 512      their spacing in 1/1024 cycle per segment: u (fs / spm) / 1024 Hz
+ *     reserved      not read
+ *     keep_snr, ratio_min            finite
+ * gpsacq_aided_coh_default_params (host only) sets 16, 20, 16, 1, 20, 3, 25 (24.4 Hz at 5.456 MHz), 0, 25.0 and ratio_min =
+ * 10.73 (DEFAULT RATIO_MIN below).
+ * PER TASK.
+ * 1. KEPT, 2. NO_AID, 3. HYPOTHESES (d, h): steps 1 to 3 of B. WINDOWED SEARCH above, word for word, with this section's blocks,
+ *    min_segments, W and K: base, P0(h, d), one chip stream per (segment, d), the carrier counted from the window's first sample,
+ *    the window's fixed segments s = 0 .. S - 1 (S = `segments`), the flags SHORT and FEW.
+ * 4. SEGMENT SUMS.  z_s = (I_s, Q_s) of hypothesis (h, d): THE CHANNEL MODEL's prompt sums over the spm samples of segment s --
+ *    what step 4 above squares.  |I_s|, |Q_s| <= spm.
+ * 5. COHERENT SUMS.  The ROTATION TABLE is data of the model: C[k] = nearbyint(2^14 cos(2 pi k / 1024)) and S[k] =
+ *    nearbyint(2^14 sin(2 pi k / 1024)), int16, k = 0 .. 1023, built by the host in fp64; gpsacq_aided_coh_table writes C then S.
+ *    (No entry lies within 3.9e-4 of a rounding tie: any sane cos gives the same table.)  For the fine index g = 0 .. 2F let
+ *    f = g - F and k_s = (f u s) mod 1024, a true modulo (0 .. 1023 also for negative f).  In int64
+ *        A_s = I_s C[k_s] + Q_s S[k_s]
+ *        B_s = Q_s C[k_s] - I_s S[k_s]
+ *    -- z_s turned BACK by f u s / 1024 cycles: a positive f is the hypothesis of a Doppler ABOVE lo_shift_d's, by
+ *    f u (fs / spm) / 1024 Hz.  For the edge e = 0 .. M - 1 the period boundaries are {0, S} and every s with 0 < s < S and
+ *    s = e (mod M).  Two consecutive boundaries a < b make one period; the partial periods at both ends count (an e at or beyond S
+ *    leaves the one period [0, S)).  Per period
+ *        A' = floor((sum of A_s over a <= s < b) / 2^14),     B' likewise
+ *    -- an arithmetic shift AFTER the sum, not before -- and
+ *        power(h, d, g, e) = sum over the periods of A'^2 + B'^2,  uint64.
+ *    BOUNDS.  |A_s|, |B_s| <= sqrt(2) spm (2^14 + 1) < 2^31 for spm <= 65535; a period of at most 20 segments stays below 2^36,
+ *    A' below 2^22; a period of n segments adds at most about 2 n^2 spm^2, so power <= M S 2 spm^2 (1 + 2^-13) <= 20 * 2 * 65535 *
+ *    (64 * 40000) (1 + 2^-13) < 2^43: the key of step 6 gives it 44 bits.  (The library still refuses, GPSACQ_ERR_UNSUPPORTED, an
+ *    engine and parameters with M * 2 * spm * (blocks * 40000) >= 2^43; the limits above leave none.)
+ *    With M = 1 and F = 0 every period is one segment and C[0] = 2^14, S[0] = 0: power(h, d, 0, 0) is gpsacq_aided_search's
+ *    power(h, d) bit for bit.
+ * 6. RECORD gpsacq_aided_coh: flags, segments, n_code = 2W + 1, n_dop = 2K + 1, n_fine = 2F + 1, n_edge = M, and
+ *      best    = the largest power over the valid d and all g, e, h; its place (best_d, best_f = g, best_e, best_h) is the
+ *                hypothesis with the largest KEY (power, -d, -g, -e, -h) in lexicographic order -- among equal powers the smallest
+ *                d, then g, then e, then h -- whatever the order of any reduction
+ *      lo_shift = lo_center - K + best_d,     ca_shift = (base + best_h) mod spm
+ *      noncoh  = the sum over the segments of I_s^2 + Q_s^2 at (best_h, best_d): gpsacq_aided_search's power there
+ *      floor   = 2 * spm * segments      the scale of the section above: for a +-1 stream uncorrelated with the replica a period of
+ *                n segments leaves n * 2 spm, whatever the partition
+ *      ratio   = (double)best / (double)floor,   0.0 where floor == 0
+ *      doppler_hz = lo_dop + ((double)((best_f - F) * u) / 1024.0) * (fs / (double)spm), the operations in that order, lo_dop being
+ *                step 1's of "Fine code phases" for lo_shift (lo_shift * doppler_step_hz on a finer grid, else lo_shift * fs / 40000)
+ *      best_e  = the segment index mod M at which a data bit starts: the bit phase of the window's first sample, which a
+ *                coarse-time fix knows to about +-3 ms only
+ *      reserved = 0.0
+ *    The flags are GPSACQ_AIDED_* with the meanings of the section above (NO_POWER: best == 0; BELOW: ratio < ratio_min); KEPT and
+ *    NO_AID records are the flag and zeros.  OUTPUT PEAK as step 6 above: detected, { (float)ratio, lo_shift, ca_shift,
+ *    (float)best }, its snr on THIS section's ratio scale; otherwise 16 zero bytes (KEPT: the input peak).
+ * 7. powers_out[n_tasks][2K + 1][2F + 1][M][2W + 1], optional, uint64: power(h, d, g, e) at [t][d][g][e][h]; rows of invalid d
+ *    are 0, KEPT and NO_AID tasks are all 0.
+ * LIMITS.  The segments are the window's, not the code periods of hypothesis h: the true bit edge falls INSIDE one segment per
+ * bit, and that segment partly cancels -- at worst one of twenty, about 0.2 dB on average.  (Aligning the segments per hypothesis
+ * would give up the one shared chip stream.)  The Doppler's rate over the window and 8-bit IQ input stay out of scope as above.
+ * A coherent sum of M ms is 1 / M kHz wide: u and F must cover half a grid step in steps well below 1000 / (2 M) Hz.
+ * DEFAULT RATIO_MIN.  Measured as the section above did (tools/aided_floor.py --coherent, on the CPU with tests/aided_coh_ref.py):
+ * the scene of tools/snapshot_bench.py with random navigation bits on its eight satellites, searched for its 24 absent PRNs with
+ * the defaults, 2304 draws of 3 * 7 * 20 * 33 = 13 860 hypotheses each: the largest ratio was 8.7837 (median 3.9374, 99.9 % below
+ * 7.8919).  The default is that plus a quarter of its excess over 1: 8.7837 + 7.7837 / 4 = 10.73.  The floor's maximum over so
+ * many hypotheses and only six or seven bit periods is far above the non-coherent 1.74, and its tail is not noise: white noise alone
+ * would put the maximum of 13 860 sums of seven periods near 3 (estimated); the median of 3.9 and the draws above 6 are the C/A
+ * cross-correlation of the eight satellites at amplitude 0.2, 16 dB above the signal sought, which a 20 ms sum adds up coherently
+ * wherever a Doppler difference is close to a multiple of 1 kHz.  The signal still clears this default from a lower amplitude than
+ * the non-coherent one does, but by less than the noise alone would promise.  It belongs to the defaults and to that scene; a
+ * caller who changes either measures again (the scene of tests/test_aided_coh.py, five strong satellites, read at most 3.5).
+ * WHAT TO EXPECT.  Measured on the CPU (tests/test_aided_coh.py and its scene: 16 blocks, five satellites at 0.2 with navigation
+ * bits beside the weak one, the two absent PRNs read 3.23 and 3.49): amplitude 0.03 reads ratio 11.17 (detected, just above the
+ * default; gpsacq_aided_search reads 1.79 there, BELOW), 0.0337 reads 13.67 where the non-coherent search reads 1.911, still BELOW,
+ * 0.034 reads 13.84 against 1.922 and 0.035 reads 14.63 against 1.959.  So the default detects from about amplitude 0.03, where
+ * the section above needs 0.04: some 2.5 dB, not the 8 dB the ratios alone suggest, because the threshold rose with them.
+ * Measured on an MI355X (tools/snapshot_bench.py --aided-coh, 1024 blocks, two satellites at amplitude 0.03 and two absent PRNs per
+ * block, navigation bits on, shader clock not read): 875 of 2048 weak tasks detected (870 at the true code phase, 5 elsewhere),
+ * median ratio 10.36 -- just under the default: 0.03 is where it begins to detect -- where gpsacq_aided_search detects 50; no detection
+ * in 2048 absent tasks, largest ratio 6.08; doppler_hz 6.0 Hz rms from the generator's, best_e equal to its edge in 62 %, within one
+ * segment in 87 %; k_aided_coh 6.64 ms beside k_aided 6.15 ms on the same 4096 tasks.  DESIGN.md 8.5 has the rest.  The dB-Hz scale
+ * is the generator's, estimated, as above.
+ *
+ * B. THE RECEIVE INSTANT ON THE DEVICE.  gpsacq_aid_instant: "THE RECEIVE INSTANT OF A COARSE-TIME FIX" above as a kernel, one
+ * lane per fix.  fix[n_fix] (gpsacq_fix), coarse_info[n_fix] and prior[n_fix] as gpsacq_coarse_fix_batch took and gave them;
+ * fix_out[n_fix] is a copy of the fix with (rx_ms, rx_frac) replaced, c = 2.99792458e8, every operation rounded by itself,
+ * nearbyint to nearest, ties to even:
+ *     t       = nearbyint(1e3 * coarse_s) * 1e-3 - bias_m / c
+ *     k       = floor(1e3 * t)
+ *     rx_ms   = (prior.rx_ms + k) folded into the week (0 .. 604 799 999)
+ *     rx_frac = t - 1e-3 * k
+ * A fix that is not GPSACQ_FIX_OK is copied byte for byte.  A GPSACQ_FIX_OK fix whose coarse_s or bias_m is not finite, or whose
+ * k is outside -2^31 .. 2^31 - 1, is copied with status GPSACQ_FIX_NO_CONVERGE, so that gpsacq_aid_predict refuses it.  fix_out
+ * may be fix.
+ *
+ * C. THE CHAIN.  gpsacq_aided_coh_peaks_device: k_aid_instant, then k_aid_predict (unchanged), then k_aided_coh on the engine's
+ * stream, no host copy in between: gpsacq_aided_peaks_device's arguments plus d_info and d_prior.  d_info == NULL skips the
+ * instant step (the fixes are taken as they are; d_prior is then not read).  d_fix_instant (the fixes predicted from) and d_aid
+ * may be NULL: engine scratch.  The results are exactly what the three calls give.
+ *
+ * The host forms take host pointers and return after completion; the _device forms take device pointers for everything but eph
+ * and the params (NULL: the defaults), bits at any byte address, work on the engine's stream, sync != 0 waits; host and device
+ * form agree byte for byte.  Argument errors as in the section above (and coh_ms outside its set, F, u, W, K outside their
+ * ranges): GPSACQ_ERR_ARG, nothing launched, nothing written.  GPSACQ_ERR_UNSUPPORTED: everything gpsacq_aided_search refuses,
+ * and fit * (2W + 1) > 5120 with fit = blocks * 40000 / spm, the z matrix of the kernel (the defaults need 117 * 33 = 3861).
+ * Kernels (csrc/aided_kernels.hip).  k_aided_coh<M>: one workgroup of four wave64 per task.  Per d: the CORRELATION STAGE is
+ * k_aided's segment walk at one pass (wave w takes segments w, w + 4, ...; lane h stores its (I, Q) as an int32 pair into z[s][h]
+ * in LDS, 40 KB); after a barrier the COHERENT STAGE takes (h, g) as its work item on the z column of h: one walk over the
+ * segments turns z_s by the table (in LDS, 4 KB), keeps the prefix sums of the turned series and, for e = s mod M alone, closes
+ * that edge's period as the difference to the prefix kept at its last boundary -- every e in O(S), M accumulators, the walk
+ * unrolled by M so that no register array is indexed at run time.  The best hypothesis is the maximum of a packed key, reduced
+ * once per d.  No atomics, no scratch; every loop is bounded by kernel arguments, every LDS index by the host-checked limits.
+ * k_aid_instant: one lane per fix.
+ */
+typedef struct { int32_t blocks, min_segments, code_half, dop_half, coh_ms, fine_half, fine_step, reserved;
+                 double keep_snr, ratio_min; } gpsacq_aided_coh_params;                                                         /* 48 bytes */
+typedef struct { int32_t flags, segments, n_code, n_dop, n_fine, n_edge, best_h, best_d, best_f, best_e, lo_shift, ca_shift;
+                 uint64_t best, noncoh, floor; double ratio, doppler_hz, reserved; } gpsacq_aided_coh;                          /* 96 bytes */
+GPSACQ_API int gpsacq_aided_coh_default_params(gpsacq_aided_coh_params* p);   /* host only */
+GPSACQ_API int gpsacq_aided_coh_table(int16_t* out /* [2048]: C[0 .. 1023], then S[0 .. 1023] */);   /* host only */
+GPSACQ_API int gpsacq_aided_coh_search(gpsacq_engine* e, const uint8_t* bits, size_t n_bytes, size_t stride, const gpsacq_task* tasks,
+                                       const gpsacq_aid* aid, const gpsacq_peak* peaks_in /* or NULL */, size_t n_tasks,
+                                       const gpsacq_aided_coh_params* params, gpsacq_aided_coh* aided_out, gpsacq_peak* peaks_out,
+                                       uint64_t* powers_out /* [n_tasks][2 K + 1][2 F + 1][M][2 W + 1] or NULL */);
+GPSACQ_API int gpsacq_aided_coh_search_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks,
+                                              const void* d_aid, const void* d_peaks_in, size_t n_tasks, const gpsacq_aided_coh_params* params,
+                                              void* d_aided, void* d_peaks_out, void* d_powers_out, int sync);
+GPSACQ_API int gpsacq_aid_instant(gpsacq_engine* e, const gpsacq_fix* fix, const gpsacq_coarse_info* coarse_info, const gpsacq_coarse_prior* prior,
+                                  size_t n_fix, gpsacq_fix* fix_out);
+GPSACQ_API int gpsacq_aid_instant_device(gpsacq_engine* e, const void* d_fix, const void* d_info, const void* d_prior, size_t n_fix, void* d_fix_out,
+                                         int sync);
+GPSACQ_API int gpsacq_aided_coh_peaks_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_info /* or NULL */,
+                                             const void* d_prior, const void* d_vel, const void* d_bits, size_t n_bytes, size_t stride,
+                                             const void* d_tasks, const void* d_peaks_in, size_t n_fix, int n_chans, const gpsacq_aid_params* aid_params,
+                                             const gpsacq_aided_coh_params* coh_params, void* d_fix_instant, void* d_aid, void* d_aided,
+                                             void* d_peaks_out, int sync);
+/* device time of k_aid_instant, k_aid_predict and k_aided_coh in the last call of this section on this engine, milliseconds (HIP
+ * events on its stream; waits for them); a kernel that call did not run reads 0.  Any pointer may be NULL.  The chain's prediction
+ * is timed here alone: gpsacq_aided_last_ms keeps the times of the section above's own calls. */
+GPSACQ_API int gpsacq_aided_coh_last_ms(const gpsacq_engine* e, float* instant_ms, float* predict_ms, float* search_ms);
 
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);

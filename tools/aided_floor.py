@@ -8,7 +8,11 @@ made sample by sample with tests/gen_ref.py.  tests/aided_ref.py searches it for
 ratio = best / floor over its 99 hypotheses.  C/A cross-correlation with the eight strong satellites is part of what is measured.
 Prints one JSON line: the draw count, the largest ratio, and the default it gives (largest + a quarter of its excess over 1).
 
-    python tools/aided_floor.py [--windows 8] [--centers 6] [--procs 8]
+    python tools/aided_floor.py [--windows 8] [--centers 6] [--procs 8] [--coherent]
+
+--coherent: the same draws for gpsacq_aided_coh_search ("Coherent aided acquisition", DEFAULT RATIO_MIN) with its defaults (20 ms
+sums, 7 fine Dopplers 25/1024 cycle per segment apart, 20 bit edges: 13 860 hypotheses a draw), by tests/aided_coh_ref.py, on the
+same scene with random navigation bits on its eight satellites (16 per satellite, repeated).
 """
 import argparse
 import json
@@ -69,8 +73,61 @@ def work(job):
     return out
 
 
+COH = dict(min_segments=20, coh_ms=20, fine_half=3, fine_step=25)  # gpsacq_aided_coh_default_params beside BLOCKS, W, K
+NAV_BITS, NAV_SEED = 16, 5
+
+
+def scene_nav(n_blocks, seed):
+    """scene() with random navigation bits, NAV_BITS per satellite (repeated), on the eight satellites"""
+    import numpy as np
+
+    import gen_ref
+    from coarse_helpers import synth_sats
+    from nav_helpers import geometry
+    geo = geometry("north")
+    sel = geo["subsets"][8]
+    sats, _ = synth_sats(geo, sel, geo["ref_ms"] + 4321, 0.6180e-3, 0, FS, 0.2)
+    nav = (1 - 2 * np.random.default_rng(NAV_SEED).integers(0, 2, (len(sats), NAV_BITS))).astype(np.int8)
+    n = n_blocks * BLOCK_BYTES * 8
+    y = np.concatenate([gen_ref.LAW.bits(FC, FS, sats, 1.0, seed, a, min(gen_ref.MAX_SAMPLES, n - a), nav=nav)["y"]
+                        for a in range(0, n, gen_ref.MAX_SAMPLES)])
+    return (y < 0.0).astype(np.uint8), [s[0] for s in sats]
+
+
+def work_coherent(job):
+    """work() for gpsacq_aided_coh_search with its defaults: tests/aided_coh_ref.py on the scene with navigation bits"""
+    import numpy as np
+
+    import aided_coh_ref
+    import aided_ref
+    block, lo_center, prns, centers, n_blocks, seed = job
+    if "nav01" not in _scene:
+        _scene["nav01"], _ = scene_nav(n_blocks, seed)
+    s01 = _scene["nav01"]
+    o = block * BLOCK_BYTES * 8
+    segments = BLOCKS * 40000 // SPM
+    rates, carriers = [], []
+    j = np.arange(segments * SPM, dtype=np.int64)
+    for d in range(2 * K + 1):
+        ok, lo_rate, ca_rate = aided_ref.nco_words(lo_center - K + d, FC, FS)
+        assert ok and abs(lo_center - K + d) <= KMAX
+        rates.append((True, lo_rate, ca_rate))
+        carriers.append(aided_ref.carrier_pm((j * lo_rate) % aided_ref.TWO32))
+    floor = 2 * SPM * segments
+    out = []
+    for prn in prns:
+        for ca in centers:
+            z = aided_coh_ref.segment_sums(s01, o, segments, SPM, prn, (ca - W) % SPM, 2 * W + 1, rates, carriers)
+            best = max(int(np.array(aided_coh_ref.LAW.powers(zi, zq, COH["fine_half"], COH["fine_step"], COH["coh_ms"]), dtype=np.uint64).max())
+                       for zi, zq in z)
+            out.append(best / floor)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--coherent", action="store_true", help="the floor of gpsacq_aided_coh_search (20 ms sums, 7 fine Dopplers, 20 edges) "
+                    "on the scene with navigation bits")
     ap.add_argument("--windows", type=int, default=8, help="window starts: blocks 0 .. windows - 1")
     ap.add_argument("--centers", type=int, default=6, help="lo_center values, spread over the grid")
     ap.add_argument("--procs", type=int, default=8)
@@ -84,10 +141,11 @@ def main():
     rng = np.random.default_rng(a.seed)
     jobs = [(b, lo, absent, rng.integers(0, SPM, 2).tolist(), n_blocks, a.seed) for b in range(a.windows) for lo in los]
     with multiprocessing.Pool(a.procs) as pool:
-        ratios = np.array([r for rows in pool.map(work, jobs) for r in rows])
+        ratios = np.array([r for rows in pool.map(work_coherent if a.coherent else work, jobs) for r in rows])
     worst = float(ratios.max())
+    extra = dict(COH, coherent=True, nav_bits=NAV_BITS, nav_seed=NAV_SEED) if a.coherent else {}
     print(json.dumps({"draws": int(ratios.size), "absent_prns": len(absent), "windows": a.windows, "lo_centers": los, "blocks": BLOCKS, "W": W, "K": K,
-                      "ratio_max": round(worst, 4), "ratio_median": round(float(np.median(ratios)), 4),
+                      **extra, "ratio_max": round(worst, 4), "ratio_median": round(float(np.median(ratios)), 4),
                       "ratio_p999": round(float(np.percentile(ratios, 99.9)), 4), "ratio_min_default": round(worst + 0.25 * (worst - 1.0), 4)}))
 
 

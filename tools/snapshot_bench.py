@@ -13,6 +13,7 @@ away from that instant the truth is off by the range acceleration (metres over 1
 is worth at 5.456 MHz.
 
     python tools/snapshot_bench.py [--blocks 2048] [--reps 5] [--refine [--refine-blocks 16]] [--cold] [--aided [--weak-amplitude 0.05]]
+                                   [--aided-coh [--weak-amplitude 0.03]]
 
 --refine: the capture is made K - 1 blocks longer (K = --refine-blocks) so that every searched block has its whole window, and
 each repetition also runs gpsacq_coarse_fix_fine_device on the same capture, tasks and peaks: k_refine (the fine code phases of
@@ -38,6 +39,15 @@ snr_min = ratio_min.  The line gains, all from one run: the weak tasks detected 
 code error of the detected weak peaks against the generator's law; the position error with and without the aided satellites on the
 same blocks; aided_ms (k_aided) and aid_predict_ms beside refine_ms and search_ms, and the cost of one hypothesis of k_aided beside
 one replica of k_refine (k_refine's time over three replicas per hit).
+
+--aided-coh: the --aided scene (it implies --aided) with the weak pair at --weak-amplitude (default 0.03 here) and random navigation
+bits on every satellite in the capture.  Each repetition also runs gpsacq_aided_coh_peaks_device ("Coherent aided acquisition" of
+include/gpsacq.h) on the same tasks: k_aid_instant on the fine fixes' coarse-time records (what --aided does on the host), k_aid_predict
+and k_aided_coh with the defaults.  The line gains, beside --aided's figures of the same run: aided_coh_ms, aid_instant_ms and the
+ratio of k_aided_coh to k_aided; the weak tasks each search detects (and at the true code phase) and its false detections on the
+absent PRNs with the largest absent ratio; the error of doppler_hz against the generator's Doppler over the true detections; and
+the share of their best_e equal to the generator's bit edge (the segment of the window nearest to where a data bit starts), exactly
+and within one segment.
 """
 import argparse
 import json
@@ -59,8 +69,12 @@ def main():
     ap.add_argument("--refine-blocks", type=int, default=16, help="window of the refinement, in blocks (1 .. 64)")
     ap.add_argument("--cold", action="store_true", help="also fix every block with no prior of place: fine Doppler, Doppler fix, fine fix")
     ap.add_argument("--aided", action="store_true", help="also search weak satellites around the prediction of the first fix")
-    ap.add_argument("--weak-amplitude", type=float, default=0.05, help="amplitude of the two weak satellites of --aided")
+    ap.add_argument("--aided-coh", action="store_true", help="also run the coherent aided search on the same tasks, navigation bits on")
+    ap.add_argument("--weak-amplitude", type=float, default=None, help="amplitude of the two weak satellites of --aided (default 0.05; 0.03 with --aided-coh)")
     a = ap.parse_args()
+    a.aided = a.aided or a.aided_coh
+    if a.weak_amplitude is None:
+        a.weak_amplitude = 0.03 if a.aided_coh else 0.05
     a.refine = a.refine or a.cold or a.aided
 
     import numpy as np
@@ -113,7 +127,13 @@ def main():
             d_aided, d_peaks_a = zeros(n_tasks * gpsacq.AIDED_DTYPE.itemsize), zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize)
             d_fix_a, d_info_a = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
             aided_best = [float("inf")] * 2
-        eng.generate_device(d_bits.data_ptr(), n_bytes, gen_sats, noise_sigma=1.0, seed=77)
+        nav = None
+        if a.aided_coh:
+            cp = gpsacq.aided_coh_params()
+            d_coh, d_peaks_c = zeros(n_tasks * gpsacq.AIDED_COH_DTYPE.itemsize), zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize)
+            coh_best = [float("inf")] * 3
+            nav = (1 - 2 * np.random.default_rng(5).integers(0, 2, (len(gen_sats), 64))).astype(np.int8)
+        eng.generate_device(d_bits.data_ptr(), n_bytes, gen_sats, noise_sigma=1.0, seed=77, nav=nav)
         best, search_best, refine_best = None, float("inf"), float("inf")
         for _ in range(1 + a.reps):  # the first call also allocates the engine's scratch
             eng.search_device(d_bits.data_ptr(), a.blocks, d_peaks.data_ptr(), d_tasks_ptr=d_tasks.data_ptr(), n_tasks=n_tasks, sync=True)
@@ -146,6 +166,11 @@ def main():
                 aided_best = [min(x, y) for x, y in zip(aided_best, eng.aided_last_ms())]
                 eng.coarse_fix_fine_device(ephs, d_bits.data_ptr(), n_bytes, d_tasks.data_ptr(), d_peaks_a.data_ptr(), a.blocks, len(sats),
                                            d_prior.data_ptr(), d_fix_a.data_ptr(), d_info_a.data_ptr(), refine_params=rp_a, sync=True)
+            if a.aided_coh:  # the receive instant on the device, from the same fine fixes
+                eng.aided_coh_peaks_device(ephs, d_fix_f.data_ptr(), d_bits.data_ptr(), n_bytes, d_tasks.data_ptr(), a.blocks, len(sats),
+                                           d_coh.data_ptr(), d_peaks_c.data_ptr(), d_info_ptr=d_info_f.data_ptr(), d_prior_ptr=d_prior.data_ptr(),
+                                           d_peaks_in_ptr=d_peaks.data_ptr(), aid_params=gpsacq.aid_params(-90.0), params=cp, sync=True)
+                coh_best = [min(x, y) for x, y in zip(coh_best, eng.aided_coh_last_ms())]
             if a.cold:
                 eng.cold_fix_device(ephs, d_bits.data_ptr(), n_bytes, d_tasks.data_ptr(), d_peaks.data_ptr(), d_rx.data_ptr(), a.blocks, len(sats),
                                     d_fix_c.data_ptr(), d_info_c.data_ptr(), d_dfix.data_ptr(), d_dopfine_ptr=d_dopfine.data_ptr(),
@@ -161,6 +186,9 @@ def main():
             peaks_a = d_peaks_a.cpu().numpy().view(gpsacq.PEAK_DTYPE).reshape(a.blocks, len(sats))
             fix_a = d_fix_a.cpu().numpy().view(gpsacq.FIX_DTYPE)
             info_a = d_info_a.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
+        if a.aided_coh:
+            coh = d_coh.cpu().numpy().view(gpsacq.AIDED_COH_DTYPE).reshape(a.blocks, len(sats))
+            peaks_c = d_peaks_c.cpu().numpy().view(gpsacq.PEAK_DTYPE).reshape(a.blocks, len(sats))
         if a.cold:
             dopfine = d_dopfine.cpu().numpy().view(gpsacq.DOPFINE_DTYPE).reshape(a.blocks, len(sats))
             dfix = d_dfix.cpu().numpy().view(gpsacq.DOPPLER_FIX_DTYPE)
@@ -257,6 +285,30 @@ def main():
             "position_error_max_with_aided_m": round(float(off_a[ok_a].max()), 2) if ok_a.any() else None,
             "position_error_median_without_aided_same_blocks_m": round(float(np.median(off_f[ok_a])), 2) if ok_a.any() else None,
             "position_error_max_without_aided_same_blocks_m": round(float(off_f[ok_a].max()), 2) if ok_a.any() else None})
+    if a.aided_coh:
+        c_searched = (coh["flags"] & (gpsacq.AIDED_KEPT | gpsacq.AIDED_NO_AID)) == 0
+        c_found = c_searched & ((coh["flags"] & (gpsacq.AIDED_FEW | gpsacq.AIDED_NO_POWER | gpsacq.AIDED_BELOW)) == 0)
+        c_true = c_found[:, weak] & (np.abs(wrap(peaks_c["ca_shift"] / FS - want)[:, weak]) * FS <= 1.5)
+        e_dop = (coh["doppler_hz"][:, weak] - np.array([s[2] for s in sats])[None, weak])[c_true]
+        # the generator's edge: a data bit starts where the chip count (m + code_phase) * chips_per_sample passes a multiple of 20460
+        q0 = (m0 + np.array([s[3] for s in sats])[None, :]) * cps
+        to_edge = ((-q0) % 20460.0) / cps / (FS / 1000.0)  # in segments of the window (5456 samples)
+        e_gen = np.rint(to_edge).astype(np.int64) % 20
+        de = (coh["best_e"] - e_gen + 10) % 20 - 10
+        r4 = lambda v: round(float(v), 4)
+        extra.update({
+            "coh_ratio_min": float(cp["ratio_min"][0]), "nav_bits": True, "aid_instant_ms": r4(coh_best[0]), "aid_predict_coh_ms": r4(coh_best[1]),
+            "aided_coh_ms": r4(coh_best[2]), "aided_coh_over_aided": r4(coh_best[2] / aided_best[1]), "coh_tasks_searched": int(c_searched.sum()),
+            "coh_weak_detected": int(c_found[:, weak].sum()), "coh_weak_detected_at_the_true_phase": int(c_true.sum()),
+            "coh_weak_ratio_median": r4(np.median(coh["ratio"][:, weak][c_searched[:, weak]])) if c_searched[:, weak].any() else None,
+            "coh_weak_noncoh_over_floor_median": r4(np.median((coh["noncoh"] / np.maximum(coh["floor"], 1))[:, weak][c_searched[:, weak]]))
+            if c_searched[:, weak].any() else None,
+            "coh_absent_tasks": int(c_searched[:, absent].sum()), "coh_absent_false_detections": int(c_found[:, absent].sum()),
+            "coh_absent_ratio_max": r4(coh["ratio"][:, absent].max()), "coh_absent_ratio_median": r4(np.median(coh["ratio"][:, absent])),
+            "coh_doppler_error_rms_hz": r4(np.sqrt((e_dop ** 2).mean())) if c_true.any() else None,
+            "coh_doppler_error_max_hz": r4(np.abs(e_dop).max()) if c_true.any() else None,
+            "coh_best_e_equal_share": r4((de[:, weak][c_true] == 0).mean()) if c_true.any() else None,
+            "coh_best_e_within_one_share": r4((np.abs(de[:, weak][c_true]) <= 1).mean()) if c_true.any() else None})
     print(json.dumps({
         "bench": "snapshot", "device": name, "blocks": a.blocks, "sats": len(sats), "tasks": n_tasks, "prior_off_km": 30.0, "prior_off_s": 30.0,
         "search_ms": round(search_best, 4), "coarse_obs_ms": round(best[0], 4), "coarse_fix_ms": round(best[1], 4),
