@@ -61,8 +61,10 @@ oracle:
 	$(MAKE) -C oracle
 
 emul: tests/emul/libemul_acq.so
-tests/emul/libemul_acq.so: tests/emul/emul_acq.cpp $(CSRC)/*.hpp
-	$(CLANGXX) -x c++ $(HOSTFLAGS) -shared -o $@ tests/emul/emul_acq.cpp
+# every source in tests/emul: emul_acq.cpp (the acquisition kernels' index math) and emul_spd.cpp (the solvers' Cholesky piece)
+EMUL_SRC := $(wildcard tests/emul/*.cpp)
+tests/emul/libemul_acq.so: $(EMUL_SRC) $(CSRC)/*.hpp
+	$(CLANGXX) -x c++ $(HOSTFLAGS) -shared -o $@ $(EMUL_SRC)
 
 # Drop-in check (authoring container only): the reference's own front end, compiled from where it lies and never copied,
 # linked against our SearchInit/SearchTask.  The binary goes to oracle/_ref/ (git-ignored).  It travels to the GPU box for ONE

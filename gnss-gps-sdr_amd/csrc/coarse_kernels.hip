@@ -1,5 +1,5 @@
 // coarse_kernels.hip -- "Coarse-time fixes: positions from code phases alone" of include/gpsacq.h, in fp64, written on
-// nav_device.hpp (constants, usable(), geodetic(), blank_fix()) and orbit_device.hpp (the one orbit evaluation).
+// nav_device.hpp (constants, usable(), geodetic(), blank_fix(), and through it spd_device.hpp, the Cholesky piece) and orbit_device.hpp (the one orbit evaluation).
 //
 // k_coarse_obs: one lane per (fix, channel), a search peak into an observation that carries only the sub-millisecond part.
 // k_coarse_fix: one lane per fix, steps A, B and C of the text.  Unlike k_fix it holds NOTHING of the row in registers: twelve
@@ -7,7 +7,7 @@
 // the fifth unknown, so their states have to be evaluated again every pass anyway.  The satellite loop is ONE body (#pragma
 // unroll 1) that reads the observation from `work` (the caller's obs_out or engine scratch, where step A left eph, the whole
 // milliseconds N_k, f_k and the weight: 32 bytes that are cache hits after the first pass), evaluates the orbit, and adds into the
-// 15 + 5 sums of the normal equations.  The pass that follows the last step runs the same body once more with unit weights: the
+// 15 + 5 sums of the normal equations (a Sym<5> of spd_device.hpp, whose factor, solve and inverse the passes end with).  The pass that follows the last step runs the same body once more with unit weights: the
 // sums are then H^T H of the dilution figures at the final state, and the observations go out with their full transmit times.
 // So the orbit code is inlined twice in the kernel: the two passes of step A (one body) and the Newton body.
 // No LDS, no barrier, no atomics; every loop is bounded.  Lanes diverge on the pass count and on Kepler's iteration, which is
@@ -25,71 +25,6 @@
 namespace acq {
 
 namespace {
-// ---- 5x5 ----------------------------------------------------------------------------------------------------------------------
-// the lower triangle of a symmetric 5x5, row by row: entry (i, j), j <= i.  Every index below is a compile-time constant.
-__device__ __forceinline__ constexpr int at(int i, int j) { return i * (i + 1) / 2 + j; }
-
-// Cholesky A = L L^T with factor4's pivot rule; false: singular
-__device__ __forceinline__ bool factor5(const double (&a)[15], double (&l)[15]) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        double p = a[at(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k) p -= l[at(j, k)] * l[at(j, k)];
-        if (!(p > (j == 0 ? 0.0 : TINY * a[at(j, j)]))) return false;
-        l[at(j, j)] = sqrt(p);
-#pragma unroll
-        for (int i = j + 1; i < 5; ++i) {
-            double v = a[at(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= l[at(i, k)] * l[at(j, k)];
-            l[at(i, j)] = v / l[at(j, j)];
-        }
-    }
-    return true;
-}
-
-// L L^T d = g
-__device__ __forceinline__ void solve5(const double (&l)[15], const double (&g)[5], double (&d)[5]) {
-    double y[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        double v = g[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= l[at(i, k)] * y[k];
-        y[i] = v / l[at(i, i)];
-    }
-#pragma unroll
-    for (int i = 4; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 5; ++k) v -= l[at(k, i)] * d[k];
-        d[i] = v / l[at(i, i)];
-    }
-}
-
-// the diagonal of (L L^T)^-1: with M = L^-1 (lower), q_j = sum over i >= j of M_ij^2
-__device__ __forceinline__ void inverse_diagonal5(const double (&l)[15], double (&q)[5]) {
-    double m[15];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        m[at(j, j)] = 1.0 / l[at(j, j)];
-#pragma unroll
-        for (int i = j + 1; i < 5; ++i) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = j; k < i; ++k) v += l[at(i, k)] * m[at(k, j)];
-            m[at(i, j)] = -v / l[at(i, i)];
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        q[j] = 0.0;
-#pragma unroll
-        for (int i = j; i < 5; ++i) q[j] += m[at(i, j)] * m[at(i, j)];
-    }
-}
-
 // ---- time (split() and week_ms() are nav_device.hpp's) ---------------------------------------------------------------------------
 // nearbyint as an int32; what is no count of milliseconds near t0 (beyond 1e6, or not finite) is 0, as in week_ms
 __device__ __forceinline__ int32_t whole(double x) {
@@ -163,9 +98,8 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_coarse_fix(CoarseFixArgs a) {
 #pragma unroll 1
         for (int pass = 0; pass <= FIX_PASSES; ++pass) {
             if (!last && pass == FIX_PASSES) break;
-            double n[15], g[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, swrr = 0.0, sw = 0.0;
-#pragma unroll
-            for (int k = 0; k < 15; ++k) n[k] = 0.0;
+            Sym<5> n = {};
+            double g[5] = {}, swrr = 0.0, sw = 0.0;
 #pragma unroll 1
             for (int s = 0; s < a.sats; ++s) {
                 const gpsacq_obs o = work[s];
@@ -187,13 +121,7 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_coarse_fix(CoarseFixArgs a) {
                 double h[5];
                 h[0] = dx * inv, h[1] = dy * inv, h[2] = dz * inv, h[3] = 1.0;
                 h[4] = -(C * sr.clock_drift + h[0] * (sr.vx * cs - sr.vy * sn) + h[1] * (sr.vx * sn + sr.vy * cs) + h[2] * sr.vz);
-#pragma unroll
-                for (int i = 0; i < 5; ++i) {
-                    const double wh = w * h[i];
-#pragma unroll
-                    for (int j = 0; j <= i; ++j) n[at(i, j)] += wh * h[j];
-                    g[i] += wh * res;
-                }
+                add_row(n, g, h, w, res);
                 swrr += w * res * res;
                 sw += w;
                 if (last) {  // C: the observation with its full transmit time
@@ -202,11 +130,13 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_coarse_fix(CoarseFixArgs a) {
                     work[s] = v;
                 }
             }
-            double l[15];
+            Sym<5> l;
             if (last) {
-                if (factor5(n, l)) {
+                if (factor(n, l)) {
+                    Sym<5> m;
                     double q[5];
-                    inverse_diagonal5(l, q);
+                    inverse_lower(l, m);
+                    inverse_diagonal(m, q);
                     const double pd = sqrt(q[0] + q[1] + q[2]), cd = sqrt(q[4]);
                     if (isfinite(pd) && isfinite(cd)) info.pdop = pd, info.cdop = cd;
                 }
@@ -214,9 +144,9 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_coarse_fix(CoarseFixArgs a) {
                 break;
             }
             rms = sqrt(swrr / sw);
-            if (!factor5(n, l)) break;
+            if (!factor(n, l)) break;
             double d[5];
-            solve5(l, g, d);
+            solve(l, g, d);
             const double step = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
             if (!isfinite(step) || !isfinite(d[3]) || !isfinite(d[4])) break;
             x += d[0], y += d[1], z += d[2], b += d[3], sc += d[4];

@@ -14,7 +14,8 @@
 // k_doppler_fix: one lane per fix.  As k_coarse_fix it holds nothing of the row in registers: the satellite loop of every pass
 // is ONE body (#pragma unroll 1) that reads the column back from memory -- eph and the two valid flags, Doppler and weight, and
 // its light time from `tau` (engine scratch, -1 for a column that is not usable) -- evaluates the orbit (orbit_device.hpp) and
-// adds into the 10 + 4 sums of the weighted normal equations and the 10 of the unweighted ones pdop is read from.  The orbit code
+// adds into the 10 + 4 sums of the weighted normal equations and the 10 of the unweighted ones pdop is read from (two Sym<4>
+// of spd_device.hpp: add_row, factor, solve, and inverse_lower / inverse_diagonal for pdop).  The orbit code
 // is inlined twice: the start (positions only) and the Newton body.  No LDS, no barrier, no atomics; every loop is bounded.
 // Built with -ffp-contract=off (Makefile): the NCO words must be gpsacq_handoff_engine's to the bit, as in refine_kernels.hip.
 #include <hip/hip_runtime.h>
@@ -192,8 +193,8 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_doppler_fix(DopplerFixArgs a) {
         if (start) x = EARTH_R * ux / un, y = EARTH_R * uy / un, z = EARTH_R * uz / un;
 #pragma unroll 1
         for (int pass = 0; start && pass < FIX_PASSES; ++pass) {
-            Normal n = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, m = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // weighted; unweighted over weight > 0
-            double b0 = 0, b1 = 0, b2 = 0, b3 = 0, swrr = 0;
+            Sym<4> n = {}, m = {};  // weighted; unweighted over weight > 0
+            double b[4] = {}, swrr = 0;
 #pragma unroll 1
             for (int s = 0; s < a.sats; ++s) {
                 const double t = tau[s];
@@ -215,43 +216,30 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_doppler_fix(DopplerFixArgs a) {
                 const double ew = ex * wx + ey * wy + ez * wz;
                 const double pred = (ew + g) - C * sr.clock_drift;
                 const double res = -(C / L1_HZ) * c.doppler_hz - pred;
-                const double h0 = -(wx - ew * ex) * inv - OMEGA_E * ey, h1 = -(wy - ew * ey) * inv + OMEGA_E * ex, h2 = -(wz - ew * ez) * inv;
-                const double w = c.weight, w0 = w * h0, w1 = w * h1, w2 = w * h2;
-                n.a00 += w0 * h0;
-                n.a10 += w1 * h0, n.a11 += w1 * h1;
-                n.a20 += w2 * h0, n.a21 += w2 * h1, n.a22 += w2 * h2;
-                n.a30 += w0, n.a31 += w1, n.a32 += w2, n.a33 += w;
-                b0 += w0 * res, b1 += w1 * res, b2 += w2 * res, b3 += w * res;
+                const double h[4] = {-(wx - ew * ex) * inv - OMEGA_E * ey, -(wy - ew * ey) * inv + OMEGA_E * ex, -(wz - ew * ez) * inv, 1.0};
+                const double w = c.weight;
+                add_row(n, b, h, w, res);
                 swrr += w * res * res;
-                if (w > 0.0) {
-                    m.a00 += h0 * h0;
-                    m.a10 += h1 * h0, m.a11 += h1 * h1;
-                    m.a20 += h2 * h0, m.a21 += h2 * h1, m.a22 += h2 * h2;
-                    m.a30 += h0, m.a31 += h1, m.a32 += h2, m.a33 += 1.0;
-                }
+                if (w > 0.0) add_row(m, h, 1.0);
                 tau[s] = range / C;
             }
-            rms = sqrt(swrr / n.a33);
-            Normal l;
-            if (!factor4(n, l)) break;
-            double d0, d1, d2, d3;
-            solve4(l, b0, b1, b2, b3, d0, d1, d2, d3);
-            const double step = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-            if (!isfinite(step) || !isfinite(d3)) break;
-            x += d0, y += d1, z += d2, g += d3;
+            rms = sqrt(swrr / n(3, 3));
+            Sym<4> l;
+            if (!factor(n, l)) break;
+            double d[4];
+            solve(l, b, d);
+            const double step = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+            if (!isfinite(step) || !isfinite(d[3])) break;
+            x += d[0], y += d[1], z += d[2], g += d[3];
             out.iterations += 1;
             if (!(sqrt(x * x + y * y + z * z) <= 1e8)) break;
             if (step < 1e-3) {  // the step just applied was the last one: pdop from the rows it was made from
-                if (factor4(m, l)) {
-                    // M = L^-1 (lower); the diagonal of (L L^T)^-1 is the column sums of its squares
-                    const double m00 = 1.0 / l.a00, m11 = 1.0 / l.a11, m22 = 1.0 / l.a22, m33 = 1.0 / l.a33;
-                    const double m10 = -l.a10 * m00 * m11;
-                    const double m21 = -l.a21 * m11 * m22;
-                    const double m20 = -(l.a20 * m00 + l.a21 * m10) * m22;
-                    const double m32 = -l.a32 * m22 * m33;
-                    const double m31 = -(l.a31 * m11 + l.a32 * m21) * m33;
-                    const double m30 = -(l.a30 * m00 + l.a31 * m10 + l.a32 * m20) * m33;
-                    const double pd = sqrt((m00 * m00 + m10 * m10 + m20 * m20 + m30 * m30) + (m11 * m11 + m21 * m21 + m31 * m31) + (m22 * m22 + m32 * m32));
+                if (factor(m, l)) {
+                    Sym<4> li;
+                    double q[4];
+                    inverse_lower(l, li);
+                    inverse_diagonal(li, q);
+                    const double pd = sqrt(q[0] + q[1] + q[2]);
                     if (isfinite(pd)) pdop = pd;
                 }
                 ok = true;

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_raim_exclude(RaimArgs a) {
         if (stage > 0 || (wmask >> k & 1)) converged = newton(r, mask, st, steps);
         const bool last = stage == rounds;
         double swrr = INFINITY;
-        Normal n;
+        Sym<4> n;
         if (converged && (stage == 0 || last)) swrr = residuals(r, mask, st, n);
         if (stage == 0) {
             // the smallest T_k of the group, on a tie the lowest k: a butterfly over the sixteen lanes, every lane ends with the result

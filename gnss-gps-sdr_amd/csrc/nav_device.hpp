@@ -1,7 +1,8 @@
 // nav_device.hpp -- the device functions the navigation kernels are written on, all in fp64: nav_kernels.hip (k_sat_state,
 // k_sat_state_rate, k_fix, k_vel), fix_kernels.hip (k_sat_view, k_fix_atm, k_raim_detect, k_raim_exclude), coarse_kernels.hip
-// (k_coarse_fix), doppler_kernels.hip (k_doppler_fix) and aided_kernels.hip (k_aid_predict) include it, and orbit_device.hpp, the orbit evaluation, is written on its constants; nothing else does.  Constants, the 4x4 Cholesky piece, geodetic(), the view and the two delays, and the fix solver as functions over a
-// row held in registers: load_row, newton, delays, full_fix, residuals, dop_of, fill_fix.
+// (k_coarse_fix), doppler_kernels.hip (k_doppler_fix) and aided_kernels.hip (k_aid_predict) include it, and orbit_device.hpp, the orbit evaluation, is written on its constants; nothing else does.  Constants, geodetic(), the view and the two delays, and the fix solver as functions over a
+// row held in registers: load_row, newton, delays, full_fix, residuals, dop_of, fill_fix.  The normal equations of the rows
+// (ux, uy, uz, 1) are a Sym<4> of spd_device.hpp, which holds the one Cholesky, its pivot rule and the inverse DOP is read from.
 // No LDS, no barrier, no atomics; every loop is bounded, so a bad fix ends, it never spins.  The row is only ever indexed by
 // compile-time constants (a subset of it is a bit mask, data and not an index), so it stays in registers: the loops over the
 // satellites are unrolled to GPSACQ_FIX_MAX_SATS; the view loop -- a dozen transcendentals per satellite -- keeps ONE body that
@@ -11,6 +12,7 @@
 #include <stdint.h>
 
 #include "nav_launch.hpp"
+#include "spd_device.hpp"
 
 namespace acq {
 
@@ -21,7 +23,6 @@ constexpr int32_t WEEK_MS = 604800000;
 constexpr double WGS84_A = 6378137.0;
 constexpr double WGS84_E2 = 0.00669437999014132;
 constexpr int FIX_PASSES = 20, GEODETIC_PASSES = 10;
-constexpr double TINY = 1e-13;  // a Cholesky pivot below TINY times its diagonal entry: singular
 constexpr int S = GPSACQ_FIX_MAX_SATS;
 
 // difference of two milliseconds of week, folded into half a week either way
@@ -52,43 +53,6 @@ __device__ __forceinline__ bool usable(const gpsacq_obs& o, const NavEph* eph, i
     if (!o.valid || o.eph < 0 || o.eph >= n_eph) return false;
     if (!(o.weight >= 0.0) || !isfinite(o.weight) || !isfinite(o.tx_frac)) return false;
     return eph[o.eph].valid != 0;
-}
-
-// ---- 4x4 ----------------------------------------------------------------------------------------------------------------------
-// the lower triangle of a symmetric 4x4: the normal matrix of the rows (ux, uy, uz, 1), or its Cholesky factor
-struct Normal {
-    double a00, a10, a11, a20, a21, a22, a30, a31, a32, a33;
-};
-
-// Cholesky A = L L^T; false at a pivot that is not positive next to its diagonal entry: singular
-__device__ __forceinline__ bool factor4(const Normal& a, Normal& l) {
-    if (!(a.a00 > 0.0)) return false;
-    l.a00 = sqrt(a.a00);
-    l.a10 = a.a10 / l.a00, l.a20 = a.a20 / l.a00, l.a30 = a.a30 / l.a00;
-    const double p1 = a.a11 - l.a10 * l.a10;
-    if (!(p1 > TINY * a.a11)) return false;
-    l.a11 = sqrt(p1);
-    l.a21 = (a.a21 - l.a20 * l.a10) / l.a11, l.a31 = (a.a31 - l.a30 * l.a10) / l.a11;
-    const double p2 = a.a22 - l.a20 * l.a20 - l.a21 * l.a21;
-    if (!(p2 > TINY * a.a22)) return false;
-    l.a22 = sqrt(p2);
-    l.a32 = (a.a32 - l.a30 * l.a20 - l.a31 * l.a21) / l.a22;
-    const double p3 = a.a33 - l.a30 * l.a30 - l.a31 * l.a31 - l.a32 * l.a32;
-    if (!(p3 > TINY * a.a33)) return false;
-    l.a33 = sqrt(p3);
-    return true;
-}
-
-// L L^T d = b
-__device__ __forceinline__ void solve4(const Normal& l, double b0, double b1, double b2, double b3, double& d0, double& d1, double& d2, double& d3) {
-    const double y0 = b0 / l.a00;
-    const double y1 = (b1 - l.a10 * y0) / l.a11;
-    const double y2 = (b2 - l.a20 * y0 - l.a21 * y1) / l.a22;
-    const double y3 = (b3 - l.a30 * y0 - l.a31 * y1 - l.a32 * y2) / l.a33;
-    d3 = y3 / l.a33;
-    d2 = (y2 - l.a32 * d3) / l.a22;
-    d1 = (y1 - l.a21 * d2 - l.a31 * d3) / l.a11;
-    d0 = (y0 - l.a10 * d1 - l.a20 * d2 - l.a30 * d3) / l.a00;
 }
 
 // the satellite turned with the earth from its corrected transmit time to the fix's receive time: sin and cos of the angle
@@ -305,29 +269,24 @@ __device__ __forceinline__ bool newton(const Row& r, uint32_t mask, State& st, i
         if (PIN) asm volatile("" : "+v"(mask));
         st.trx = r.t0 - st.bias / C;
         // weighted normal equations of the rows h = (ux, uy, uz, 1): lower triangle of A = sum w h h^T, b = sum w h r
-        Normal n = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        double b0 = 0, b1 = 0, b2 = 0, b3 = 0, swrr = 0;
+        Sym<4> n = {};
+        double b[4] = {}, swrr = 0;
 #pragma unroll
         for (int s = 0; s < S; ++s)
             if (mask >> s & 1) {
-                double ux, uy, uz, res;
-                sight(r, s, st, ux, uy, uz, res);
-                const double w = r.ww[s], wx = w * ux, wy = w * uy, wz = w * uz;
-                n.a00 += wx * ux;
-                n.a10 += wy * ux, n.a11 += wy * uy;
-                n.a20 += wz * ux, n.a21 += wz * uy, n.a22 += wz * uz;
-                n.a30 += wx, n.a31 += wy, n.a32 += wz, n.a33 += w;
-                b0 += wx * res, b1 += wy * res, b2 += wz * res, b3 += w * res;
-                swrr += w * res * res;
+                double h[4] = {0.0, 0.0, 0.0, 1.0}, res;
+                sight(r, s, st, h[0], h[1], h[2], res);
+                add_row(n, b, h, r.ww[s], res);
+                swrr += r.ww[s] * res * res;
             }
-        st.rms = sqrt(swrr / n.a33);
-        Normal l;
-        if (!factor4(n, l)) return false;
-        double d0, d1, d2, d3;
-        solve4(l, b0, b1, b2, b3, d0, d1, d2, d3);
-        const double step = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-        if (!isfinite(step) || !isfinite(d3)) return false;
-        st.x += d0, st.y += d1, st.z += d2, st.bias += d3;
+        st.rms = sqrt(swrr / n(3, 3));
+        Sym<4> l;
+        if (!factor(n, l)) return false;
+        double d[4];
+        solve(l, b, d);
+        const double step = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        if (!isfinite(step) || !isfinite(d[3])) return false;
+        st.x += d[0], st.y += d[1], st.z += d[2], st.bias += d[3];
         steps += 1;
         if (step < 1e-4) {  // the step just applied was the last one
             st.trx = r.t0 - st.bias / C;
@@ -414,48 +373,32 @@ __device__ __forceinline__ Full full_fix(Row& r, const gpsacq_atm_params& p) {
 
 // STATISTIC and the sums of DOP in one pass at the state given: returns sum w r^2 over `mask` (a weight-0 observation adds 0),
 // n the unweighted normal matrix over the satellites of `mask` with weight > 0
-__device__ __forceinline__ double residuals(const Row& r, uint32_t mask, const State& st, Normal& n) {
-    n.a00 = n.a10 = n.a11 = n.a20 = n.a21 = n.a22 = n.a30 = n.a31 = n.a32 = n.a33 = 0.0;
+__device__ __forceinline__ double residuals(const Row& r, uint32_t mask, const State& st, Sym<4>& n) {
+    n = {};
     double swrr = 0.0;
     asm volatile("" : "+v"(mask));  // as in newton: the twelve tests stay here
 #pragma unroll
     for (int s = 0; s < S; ++s)
         if ((mask >> s & 1) && r.ww[s] > 0.0) {
-            double ux, uy, uz, res;
-            sight(r, s, st, ux, uy, uz, res);
+            double h[4] = {0.0, 0.0, 0.0, 1.0}, res;
+            sight(r, s, st, h[0], h[1], h[2], res);
             swrr += r.ww[s] * res * res;
-            n.a00 += ux * ux;
-            n.a10 += uy * ux, n.a11 += uy * uy;
-            n.a20 += uz * ux, n.a21 += uz * uy, n.a22 += uz * uz;
-            n.a30 += ux, n.a31 += uy, n.a32 += uz, n.a33 += 1.0;
+            add_row(n, h, 1.0);
         }
     return swrr;
 }
 
 // DOP from the normal matrix of residuals(), at (lat, lon); a failed pivot leaves the five zeros
-__device__ __forceinline__ void dop_of(const Normal& n, double lat, double lon, gpsacq_fix_dop& dop) {
-    Normal l;
-    if (!factor4(n, l)) return;
-    // M = L^-1 (lower); Q = M^T M, so v^T Q v = |M v|^2
-    const double m00 = 1.0 / l.a00, m11 = 1.0 / l.a11, m22 = 1.0 / l.a22, m33 = 1.0 / l.a33;
-    const double m10 = -l.a10 * m00 * m11;
-    const double m21 = -l.a21 * m11 * m22;
-    const double m20 = -(l.a20 * m00 + l.a21 * m10) * m22;
-    const double m32 = -l.a32 * m22 * m33;
-    const double m31 = -(l.a31 * m11 + l.a32 * m21) * m33;
-    const double m30 = -(l.a30 * m00 + l.a31 * m10 + l.a32 * m20) * m33;
+__device__ __forceinline__ void dop_of(const Sym<4>& n, double lat, double lon, gpsacq_fix_dop& dop) {
+    Sym<4> l, m;
+    if (!factor(n, l)) return;
+    inverse_lower(l, m);  // Q = M^T M, so v^T Q v = |M v|^2
     double sp, cp, sl, cl;
     sincos(lat, &sp, &cp);
     sincos(lon, &sl, &cl);
     const double dir[3][3] = {{-sl, cl, 0.0}, {-sp * cl, -sp * sl, cp}, {cp * cl, cp * sl, sp}};  // east, north, up
-    double q[3];
-#pragma unroll
-    for (int k2 = 0; k2 < 3; ++k2) {
-        const double v0 = dir[k2][0], v1 = dir[k2][1], v2 = dir[k2][2];
-        const double c0 = m00 * v0, c1 = m10 * v0 + m11 * v1, c2 = m20 * v0 + m21 * v1 + m22 * v2, c3 = m30 * v0 + m31 * v1 + m32 * v2;
-        q[k2] = c0 * c0 + c1 * c1 + c2 * c2 + c3 * c3;
-    }
-    const double qtt = m33 * m33;
+    const double q[3] = {inverse_along(m, dir[0]), inverse_along(m, dir[1]), inverse_along(m, dir[2])};
+    const double qtt = m(3, 3) * m(3, 3);
     const double gd = sqrt(q[0] + q[1] + q[2] + qtt), pd = sqrt(q[0] + q[1] + q[2]), hd = sqrt(q[0] + q[1]), vd = sqrt(q[2]), td = sqrt(qtt);
     if (!isfinite(gd) || !isfinite(pd) || !isfinite(hd) || !isfinite(vd) || !isfinite(td)) return;
     dop.gdop = gd, dop.pdop = pd, dop.hdop = hd, dop.vdop = vd, dop.tdop = td;
@@ -485,7 +428,7 @@ __device__ __forceinline__ double full_records(const Row& r, const Full& u, gpsa
     dop.n_masked = u.n_masked;
     if (u.status != GPSACQ_FIX_OK) return 0.0;
     fill_fix(out, r, u.st, u.lat, u.lon, u.alt);
-    Normal n;
+    Sym<4> n;
     const double swrr = residuals(r, u.mask, u.st, n);
     dop_of(n, u.lat, u.lon, dop);
     return swrr;

@@ -8,7 +8,7 @@
 // derivative and the clock drift.  k_fix: one lane per fix.  The row into registers, one Newton iteration (newton() without the pin
 // on the set, see there) from the origin with the delays zero.  k_vel, one lane per fix: the row in registers -- every loop over it is unrolled to
 // GPSACQ_FIX_MAX_SATS with the row length as a wave-uniform bound -- and one weighted least-squares solve -- the system is
-// linear -- with the fix solver's Cholesky and pivot test.  No LDS, no barrier, no atomics; every loop is bounded.
+// linear -- with the fix solver's Cholesky and pivot test (add_row, factor and solve of spd_device.hpp, N = 4).  No LDS, no barrier, no atomics; every loop is bounded.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -112,28 +112,22 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_vel(VelArgs a) {
         return;
     }
     // weighted normal equations of the rows h = (ux, uy, uz, 1), as in newton()
-    Normal n = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    double b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+    Sym<4> n = {}, l;
+    double b[4] = {}, d[4] = {};
 #pragma unroll
     for (int s = 0; s < S; ++s)
         if (mask >> s & 1) {
-            const double w = ww[s], r = yy[s];
-            const double wx = w * ux[s], wy = w * uy[s], wz = w * uz[s];
-            n.a00 += wx * ux[s];
-            n.a10 += wy * ux[s], n.a11 += wy * uy[s];
-            n.a20 += wz * ux[s], n.a21 += wz * uy[s], n.a22 += wz * uz[s];
-            n.a30 += wx, n.a31 += wy, n.a32 += wz, n.a33 += w;
-            b0 += wx * r, b1 += wy * r, b2 += wz * r, b3 += w * r;
+            const double h[4] = {ux[s], uy[s], uz[s], 1.0};
+            add_row(n, b, h, ww[s], yy[s]);
         }
     out.status = GPSACQ_VEL_SINGULAR;
     bool ok = false;
-    double d0 = 0, d1 = 0, d2 = 0, d3 = 0;
-    Normal l;
-    if (factor4(n, l)) {
-        solve4(l, b0, b1, b2, b3, d0, d1, d2, d3);
-        ok = isfinite(d0) && isfinite(d1) && isfinite(d2) && isfinite(d3);
+    if (factor(n, l)) {
+        solve(l, b, d);
+        ok = isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]) && isfinite(d[3]);
     }
     if (ok) {
+        const double d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
         double swrr = 0;
 #pragma unroll
         for (int s = 0; s < S; ++s)
@@ -150,7 +144,7 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_vel(VelArgs a) {
         out.vn = -sp * cl * d0 - sp * sl * d1 + cp * d2;
         out.vu = cp * cl * d0 + cp * sl * d1 + sp * d2;
         out.drift = d3 / C;
-        out.rms = sqrt(swrr / n.a33);
+        out.rms = sqrt(swrr / n(3, 3));
     }
     a.out[f] = out;
 }

@@ -304,3 +304,116 @@ def test_argument_errors(eng):
             fresh.fix_raim_last_ms()  # no call made on this engine
     finally:
         fresh.close()
+
+
+# ---- 6. rank-deficient rows beside regular ones: lanes part ways at the Cholesky pivot ------------------------------------------------
+N_DEFICIENT = 2 * 64 + 1  # two whole blocks of k_raim_detect and a row
+
+
+def _pivot_ratios(A):
+    """Cholesky's pivots over their diagonal entries, up to and with the first that is not positive"""
+    n, L, out = len(A), np.zeros(A.shape), []
+    for j in range(n):
+        pv = A[j, j] - (L[j, :j] ** 2).sum()
+        out.append(pv / A[j, j])
+        if not pv > 0:
+            break
+        L[j, j] = math.sqrt(pv)
+        L[j + 1:, j] = (A[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+    return out
+
+
+def _normal(xyz, t, w, pos, t_rx):
+    import atm_ref
+    d = pos - atm_ref.turned(xyz, t, t_rx)
+    H = np.concatenate([d / np.sqrt((d * d).sum(1))[:, None], np.ones((len(d), 1))], 1)
+    return H.T @ (w[:, None] * H)
+
+
+def _regular(A):
+    r = _pivot_ratios(A)
+    return len(r) == 4 and min(r) > 1e-11
+
+
+def _deficient(A):
+    r = _pivot_ratios(A)
+    return r[-1] < 1e-15 and all(x > 1e-11 for x in r[:-1])
+
+
+@pytest.fixture(scope="module")
+def deficient():
+    """The first 129 rows of "mixed".  Every third row holds its first three observations four times over: three directions, FULL's
+    matrix is singular at the first pass ("whole").  Every sixth row, from row 4, holds A B C D and then A B four times over, the first
+    copy of A pulled by 150 m: FULL is regular and fails the test, the candidates without C and without D are left with three
+    directions and are singular, the others are regular ("subset").  The rest are the rows of "mixed" with their shared references.
+    A failing pivot is below 1e-15 of its diagonal entry and every passing one above 1e-11 in the reference's own matrices, a hundred
+    either side of the 1e-13 of the rule: asserted here, before any GPU result."""
+    geo, ob0, p, rp = raim_cases.batch("mixed")
+    shared = raim_cases.references("mixed")
+    ob = ob0[:N_DEFICIENT].copy()
+    kind, refs = [], []
+    for r in range(N_DEFICIENT):
+        if r % 3 == 0:
+            ob[r, 3:] = np.tile(ob[r, :3], 3)
+            kind.append("whole")
+        elif r % 6 == 4:  # of the other strides each has one row (73, 113, 128) whose failing pivot is 1.1e-15 of its entry
+            ob[r, 4:] = np.tile(ob[r, :2], 4)
+            ob[r, 4:5] = raim_cases.shift(ob[r, 4:5].copy(), raim_cases.FAULT_M)
+            kind.append("subset")
+        else:
+            kind.append("regular")
+    for r in range(N_DEFICIENT):
+        ref = shared[r] if kind[r] == "regular" else raim_cases.reference(geo, ob[r], p, rp)
+        refs.append(ref)
+        row = ob[r]
+        xyz, t, ms0, t0 = raim_ref._row(geo["ephs"], row["eph"], row["tx_ms"], row["tx_frac"])
+        w = row["weight"].astype(np.float64)
+        first = _normal(xyz, t, w, np.zeros(3), t0)  # the first pass: from the origin, every observation
+        if kind[r] == "whole":
+            assert _deficient(first), (r, _pivot_ratios(first))
+            continue
+        assert raim_cases.precondition(ref, p, rp) is None, (r, raim_cases.precondition(ref, p, rp))
+        full = ref["full"]
+        S = np.array(full["kept"], bool)
+        assert _regular(first) and _regular(_normal(xyz[S], t[S], w[S], full["xyz"], full["t_rx"])), r
+        if kind[r] == "subset":
+            assert ref["raim"]["status"] == raim_ref.EXCLUDED and ref["excluded"] == 4 and sorted(ref["candidates"]) == [0, 1] + list(range(4, 12))
+            for k in range(12):
+                sub = S.copy()
+                sub[k] = False
+                A = _normal(xyz[sub], t[sub], w[sub], full["xyz"], full["t_rx"])
+                assert _regular(A) if k in ref["candidates"] else _deficient(A), (r, k, _pivot_ratios(A))
+    ob.setflags(write=False)
+    return geo, ob, p, rp, refs, kind
+
+
+def test_rank_deficient_rows_in_a_batch_of_regular_ones(eng, deficient):
+    """The singular return of newton() in k_raim_detect (a whole row) and in k_raim_exclude (a candidate's subset), in lanes whose
+    neighbours go on.  A regular or "subset" row is held to the reference in full.  So is a "whole" row where the reference's own
+    solve gives up at the first pass (numpy's LU meets an exact zero: 17 of the 43); in the others it has no pivot rule and takes
+    steps through the singular matrix, so every "whole" row is also held to what the rule says: no pass, nothing masked, zeros."""
+    import gpsacq
+    geo, ob, p, rp, refs, kind = deficient
+    assert len(ob) == N_DEFICIENT and kind.count("whole") == 43 and kind.count("subset") == 21
+    fix, dop, raim = eng.fix_raim(to_records(geo["ephs"]), ob, gpu_atm(p), gpu_raim(rp))
+    worst, held = np.zeros(4), 0
+    for k, ref in enumerate(refs):
+        if kind[k] != "whole":
+            worst = np.maximum(worst, _compare_row((kind[k], k), ref, fix[k], dop[k], raim[k]))
+            continue
+        if ref["status"] == gpsacq.FIX_NO_CONVERGE and ref["stages"] == [0]:
+            _compare_row((kind[k], k), ref, fix[k], dop[k], raim[k])
+            held += 1
+        assert fix["status"][k] == gpsacq.FIX_NO_CONVERGE and fix["iterations"][k] == 0 and fix["n_used"][k] == 12, k
+        assert fix[k].tobytes()[16:] == bytes(64) and fix["rx_ms"][k] == 0, k
+        assert dop["used_mask"][k] == 0xFFF and dop[k].tobytes()[4:] == bytes(44), k
+        assert raim["status"][k] == gpsacq.RAIM_NONE and raim["excluded"][k] == -1 and raim[k].tobytes()[4:8] == bytes(4) and raim[k].tobytes()[12:] == bytes(28), k
+    assert held == 17
+    print("deficient batch: position %.3g m, receive time %.3g s, DOP %.3g relative, statistic %.3g of its tolerance" % tuple(worst))
+    assert worst[0] <= POS_TOL and worst[1] <= TIME_TOL and worst[2] <= DOP_RTOL and worst[3] <= 1.0
+    sub = [k for k in range(N_DEFICIENT) if kind[k] == "subset"]
+    assert (raim["n_candidates"][sub] == 10).all() and (raim["excluded"][sub] == 4).all() and (raim["status"][sub] == gpsacq.RAIM_EXCLUDED).all()
+    # the regular rows are what they are without the deficient neighbours, bit for bit
+    reg = [k for k in range(N_DEFICIENT) if kind[k] == "regular"]
+    alone = eng.fix_raim(to_records(geo["ephs"]), ob[reg], gpu_atm(p), gpu_raim(rp))
+    assert alone[0].tobytes() == fix[reg].tobytes() and alone[1].tobytes() == dop[reg].tobytes() and alone[2].tobytes() == raim[reg].tobytes()
