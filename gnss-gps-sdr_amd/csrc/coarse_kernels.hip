@@ -14,7 +14,12 @@
 // accepted as in newton() (a fix is 4-6 passes).
 // Built with -mllvm -disable-machine-licm (Makefile), as fix_kernels.hip is and for its reason: hoisted out of the pass loop the
 // fp64 constants of the inlined libm take k_coarse_fix to 256 VGPRs + 12 AGPRs with 12 scalar registers spilled, one wave per SIMD;
-// left where they are used it is 208 VGPRs, 59 SGPRs, no spill, two waves per SIMD.  No scratch either way.
+// left where they are used it is 206 VGPRs, 59 SGPRs, no spill, two waves per SIMD.  No scratch either way.
+//
+// "Coarse-time fix integrity" of include/gpsacq.h runs behind k_coarse_fix: the solve is ONE device function, coarse_solve<SKIP>,
+// which k_coarse_fix instantiates with no column to skip and k_coarse_exclude (sixteen lanes per fix, lane k the candidate without
+// column k, each in a work row of its own) with one.  k_coarse_exclude: 226 VGPRs, 0 AGPRs, 85 SGPRs, no scratch, no LDS, two
+// waves per SIMD.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -47,12 +52,12 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_coarse_obs(CoarseObsArgs a) {
     a.out[i] = o;
 }
 
-__global__ __launch_bounds__(NAV_BLOCK) void k_coarse_fix(CoarseFixArgs a) {
-    const size_t f = (size_t)blockIdx.x * NAV_BLOCK + threadIdx.x;
-    if (f >= a.n_fix) return;
-    const gpsacq_obs* obs = a.obs + f * (size_t)a.sats;
-    gpsacq_obs* work = a.work + f * (size_t)a.sats;
-    const gpsacq_coarse_prior pr = a.prior[f];
+// Steps A, B and C for one row: `work` is the row's [sats] records, where step A leaves eph, the whole milliseconds N_k, f_k and the
+// weight and the last pass the observations with their full transmit times.  SKIP: column `skip` is taken as not usable, the one
+// difference between an exclusion candidate of k_coarse_exclude and the fix itself (k_coarse_fix: SKIP false, skip unread).
+template <bool SKIP>
+__device__ __forceinline__ void coarse_solve(const CoarseFixArgs& a, const gpsacq_obs* obs, gpsacq_obs* work, const gpsacq_coarse_prior& pr,
+                                             int skip, gpsacq_fix& out, gpsacq_coarse_info& info) {
     const bool prior_ok = pr.rx_ms >= 0 && pr.rx_ms < WEEK_MS && isfinite(pr.x) && isfinite(pr.y) && isfinite(pr.z);
 
     // A. whole milliseconds, into work[]
@@ -62,7 +67,7 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_coarse_fix(CoarseFixArgs a) {
     for (int s = 0; s < a.sats; ++s) {
         const gpsacq_obs o = obs[s];
         gpsacq_obs w = {0, 0, 0, 0, 0.0, 0.0};
-        if (prior_ok && usable(o, a.eph, a.n_eph) && o.tx_frac >= 0.0 && o.tx_frac < 1e-3) {
+        if (prior_ok && (!SKIP || s != skip) && usable(o, a.eph, a.n_eph) && o.tx_frac >= 0.0 && o.tx_frac < 1e-3) {
             const NavEph& p = a.eph[o.eph];
             double tau = 75e-3, cc = 0.0;
 #pragma unroll 1
@@ -88,8 +93,8 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_coarse_fix(CoarseFixArgs a) {
     }
 
     // B. five unknowns
-    gpsacq_fix out = blank_fix(GPSACQ_FIX_TOO_FEW, n_used);
-    gpsacq_coarse_info info = {ref, 0, 0.0, 0.0, 0.0, 0.0};
+    out = blank_fix(GPSACQ_FIX_TOO_FEW, n_used);
+    info = {ref, 0, 0.0, 0.0, 0.0, 0.0};
     double x = pr.x, y = pr.y, z = pr.z, b = 0.0, sc = 0.0, rms = 0.0;
     bool ok = false;
     if (n_used >= 5) {
@@ -174,8 +179,128 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_coarse_fix(CoarseFixArgs a) {
 #pragma unroll 1
         for (int s = 0; s < a.sats; ++s) work[s] = none;
     }
+}
+
+__global__ __launch_bounds__(NAV_BLOCK) void k_coarse_fix(CoarseFixArgs a) {
+    const size_t f = (size_t)blockIdx.x * NAV_BLOCK + threadIdx.x;
+    if (f >= a.n_fix) return;
+    const gpsacq_coarse_prior pr = a.prior[f];
+    gpsacq_fix out;
+    gpsacq_coarse_info info;
+    coarse_solve<false>(a, a.obs + f * (size_t)a.sats, a.work + f * (size_t)a.sats, pr, -1, out, info);
     a.out[f] = out;
     a.info[f] = info;
+}
+
+// "Coarse-time fix integrity", steps TEST, EXCLUDE and EXCLUDED, behind k_coarse_fix (FULL).  Sixteen lanes per fix, four fixes
+// per wave64.  Every lane of a group reads FULL's record and sums W and n_w over the caller's row (the same addresses across the
+// group), so the test is made sixteen times and no lane has to tell another its outcome; a group whose row needs no exclusion
+// writes its raim record from lane 0 and returns.  Otherwise lane k solves the row without column k where k is a candidate, in
+// a work row of its own (the whole milliseconds of a candidate that drops the reference column are not FULL's), the smallest
+// (T_k, k) and the count meet in a butterfly of width 16, and the winning lane writes the three records and copies its row out.
+__global__ __launch_bounds__(NAV_BLOCK) void k_coarse_exclude(CoarseRaimArgs a) {
+    const size_t lane = (size_t)blockIdx.x * NAV_BLOCK + threadIdx.x;
+    const size_t f = lane / COARSE_GROUP;
+    const int k = (int)(lane % COARSE_GROUP);
+    if (f >= a.fix.n_fix) return;
+    const int sats = a.fix.sats;
+    const gpsacq_obs* obs = a.fix.obs + f * (size_t)sats;
+    gpsacq_fix_raim raim;
+    raim.status = GPSACQ_RAIM_NONE;
+    raim.dof = 0, raim.excluded = -1, raim.n_candidates = 0;
+    raim.stat_full = raim.stat = raim.threshold = 0.0;
+    const int full_status = a.fix.out[f].status, full_steps = a.fix.out[f].iterations;
+    const double full_rms = a.fix.out[f].rms;
+    if (full_status != GPSACQ_FIX_OK) {  // the same for the sixteen lanes of a group, as every return before the butterfly
+        if (k == 0) a.raim[f] = raim;
+        return;
+    }
+
+    // TEST.  FULL is GPSACQ_FIX_OK, so the prior named an instant and the usable columns are those step A took
+    double W = 0.0, wk = 0.0;
+    int n_w = 0;
+    bool cand = false;
+#pragma unroll 1
+    for (int s = 0; s < sats; ++s) {
+        const gpsacq_obs o = obs[s];
+        if (!usable(o, a.fix.eph, a.fix.n_eph) || !(o.tx_frac >= 0.0 && o.tx_frac < 1e-3)) continue;
+        W += o.weight;
+        if (!(o.weight > 0.0)) continue;
+        n_w += 1;
+        if (s == k) cand = true, wk = o.weight;
+    }
+    const double sigma2 = a.r.sigma_m * a.r.sigma_m;
+    const int d = n_w - 5;
+    const double T = full_rms * full_rms * W / sigma2;
+    raim.dof = d;
+    raim.stat_full = raim.stat = T;
+    // d <= GPSACQ_FIX_MAX_SATS - 5; selects over the table, not an index: thr = threshold[d - 1], thr2 = threshold[d - 2]
+    double thr = a.r.threshold[0], thr2 = a.r.threshold[0];
+#pragma unroll
+    for (int j = 1; j < GPSACQ_RAIM_MAX_DOF; ++j) {
+        thr = d == j + 1 ? a.r.threshold[j] : thr;
+        thr2 = d - 1 == j + 1 ? a.r.threshold[j] : thr2;
+    }
+    bool go = false;
+    if (d < 1) {
+        raim.status = GPSACQ_RAIM_UNCHECKED;
+    } else {
+        raim.threshold = thr;
+        raim.status = T <= thr ? GPSACQ_RAIM_PASS : GPSACQ_RAIM_FAILED;
+        go = !(T <= thr) && a.r.exclude && d >= 2;
+    }
+    if (!go) {
+        if (k == 0) a.raim[f] = raim;
+        return;
+    }
+
+    // EXCLUDE
+    gpsacq_obs* work = a.cand + (f * (size_t)sats + (size_t)k) * (size_t)sats;  // k < sats wherever it is written
+    gpsacq_fix out;
+    gpsacq_coarse_info info;
+    double best = INFINITY;
+    int count = 0;
+    if (cand) {
+        const gpsacq_coarse_prior pr = a.fix.prior[f];
+        coarse_solve<true>(a.fix, obs, work, pr, k, out, info);
+        if (out.status == GPSACQ_FIX_OK) {
+            count = 1;
+            best = out.rms * out.rms * (W - wk) / sigma2;
+            if (!(best < INFINITY)) best = INFINITY;  // a NaN is no candidate's statistic
+        }
+    }
+    const double stat = best;
+    int best_k = k;
+    // the smallest T_k of the group, on a tie the lowest k: a butterfly over the sixteen lanes, every lane ends with the result
+#pragma unroll
+    for (int off = 1; off < COARSE_GROUP; off <<= 1) {
+        const double ot = __shfl_xor(best, off, COARSE_GROUP);
+        const int ok = __shfl_xor(best_k, off, COARSE_GROUP);
+        count += __shfl_xor(count, off, COARSE_GROUP);
+        if (ot < best || (ot == best && ok < best_k)) best = ot, best_k = ok;
+    }
+    raim.n_candidates = count;
+    if (!(best <= thr2)) {  // FAILED stands, with the full solution
+        if (k == 0) a.raim[f] = raim;
+        return;
+    }
+    if (k != best_k) return;
+
+    // EXCLUDED: the winning lane, the row's three records and its observations
+    out.iterations += full_steps;
+    raim.status = GPSACQ_RAIM_EXCLUDED;
+    raim.dof = d - 1;
+    raim.excluded = k;
+    raim.stat = stat;
+    raim.threshold = thr2;
+    a.fix.out[f] = out;
+    a.fix.info[f] = info;
+    a.raim[f] = raim;
+    if (a.obs_out) {
+        gpsacq_obs* dst = a.obs_out + f * (size_t)sats;
+#pragma unroll 1
+        for (int s = 0; s < sats; ++s) dst[s] = work[s];
+    }
 }
 
 void launch_coarse_obs(const CoarseObsArgs& a, hipStream_t s) {
@@ -184,6 +309,11 @@ void launch_coarse_obs(const CoarseObsArgs& a, hipStream_t s) {
 
 void launch_coarse_fix(const CoarseFixArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_coarse_fix, dim3((unsigned)((a.n_fix + NAV_BLOCK - 1) / NAV_BLOCK)), dim3(NAV_BLOCK), 0, s, a);
+}
+
+void launch_coarse_exclude(const CoarseRaimArgs& a, hipStream_t s) {
+    const size_t lanes = a.fix.n_fix * COARSE_GROUP;
+    hipLaunchKernelGGL(k_coarse_exclude, dim3((unsigned)((lanes + NAV_BLOCK - 1) / NAV_BLOCK)), dim3(NAV_BLOCK), 0, s, a);
 }
 
 }  // namespace acq

@@ -204,6 +204,10 @@ struct gpsacq_engine {
     Scratch<gpsacq_coarse_prior> d_coarse_prior;  // host-buffer form
     Scratch<gpsacq_coarse_info> d_coarse_info;    // host-buffer form
     Stages<2> coarse_obs_t, coarse_fix_t;  // around k_coarse_obs, around k_coarse_fix
+    // coarse-time fix integrity (gpsacq_coarse_raim_batch*); the host-buffer form stages as gpsacq_coarse_fix_batch does, the raim
+    // records in d_raim
+    Scratch<gpsacq_obs> d_coarse_cand;  // k_coarse_exclude's candidates, a work row each: [n_fix][sats][sats]
+    Stages<3> coarse_raim_t;  // before k_coarse_fix, between it and k_coarse_exclude, after k_coarse_exclude
     // fine code phases (gpsacq_refine*, gpsacq_coarse_obs_fine*, gpsacq_coarse_fix_fine_device)
     Scratch<uint8_t> d_refine_bits;  // host-buffer form of gpsacq_refine: the capture, its tasks and peaks
     Scratch<gpsacq_task> d_refine_tasks;

@@ -7,7 +7,8 @@
 // "Fix integrity": the chi-square thresholds (host only) and gpsacq_fix_raim_batch*, which run fix_kernels.hip's k_raim_*.
 // Between the velocity and the atmosphere: "Carrier-smoothed observables", gpsacq_smooth_observables* and
 // gpsacq_fix_smooth_track_device, which run smooth_kernels.hip after k_code_pos and k_carrier_acc.  Then "Coarse-time
-// fixes": gpsacq_coarse_obs*, gpsacq_coarse_fix_batch* and gpsacq_coarse_fix_peaks_device, which run coarse_kernels.hip.  Last of
+// fixes": gpsacq_coarse_obs*, gpsacq_coarse_fix_batch* and gpsacq_coarse_fix_peaks_device, which run coarse_kernels.hip, and
+// "Coarse-time fix integrity": gpsacq_coarse_raim_batch*, which run its k_coarse_fix and k_coarse_exclude.  Last of
 // all "Fine code phases": gpsacq_refine*, gpsacq_coarse_obs_fine* and gpsacq_coarse_fix_fine_device, which run refine_kernels.hip, and
 // "Cold snapshot fixes": gpsacq_fine_doppler*, gpsacq_rate_obs_fine*, gpsacq_doppler_fix_batch* and gpsacq_cold_fix_device, which run
 // doppler_kernels.hip, and "Aided acquisition": gpsacq_aid_predict*, gpsacq_aided_search* and gpsacq_aided_peaks_device, which run
@@ -982,10 +983,8 @@ extern "C" int gpsacq_raim_default_params(double sigma_m, double p_fa, gpsacq_ra
     return GPSACQ_OK;
 }
 
-static int raim_check(const char* who, const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* obs, size_t n_fix,
-                      int sats_per_fix, const gpsacq_atm_params* atm_params, const gpsacq_raim_params* rp, const void* fix, const void* raim) {
-    if (int rc = atm_check(who, e, eph, n_eph, obs, n_fix, sats_per_fix, atm_params, fix)) return rc;
-    if (!raim) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+// the raim parameters of gpsacq_fix_raim_batch* and gpsacq_coarse_raim_batch*
+static int raim_params_check(const char* who, const gpsacq_raim_params* rp) {
     if (!rp) return fail(GPSACQ_ERR_ARG, "%s: raim params is NULL", who);
     if (!std::isfinite(rp->sigma_m) || !(rp->sigma_m > 0.0)) return fail(GPSACQ_ERR_ARG, "%s: sigma_m %g (must be finite and > 0)", who, rp->sigma_m);
     for (int k = 0; k < GPSACQ_RAIM_MAX_DOF; ++k)
@@ -993,6 +992,13 @@ static int raim_check(const char* who, const gpsacq_engine* e, const gpsacq_ephe
             return fail(GPSACQ_ERR_ARG, "%s: threshold %d is %g (must be finite and > 0)", who, k, rp->threshold[k]);
     if (rp->exclude != 0 && rp->exclude != 1) return fail(GPSACQ_ERR_ARG, "%s: exclude %d (must be 0 or 1)", who, (int)rp->exclude);
     return GPSACQ_OK;
+}
+
+static int raim_check(const char* who, const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* obs, size_t n_fix,
+                      int sats_per_fix, const gpsacq_atm_params* atm_params, const gpsacq_raim_params* rp, const void* fix, const void* raim) {
+    if (int rc = atm_check(who, e, eph, n_eph, obs, n_fix, sats_per_fix, atm_params, fix)) return rc;
+    if (!raim) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    return raim_params_check(who, rp);
 }
 
 extern "C" int gpsacq_fix_raim_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, size_t n_fix,
@@ -1076,6 +1082,15 @@ static int coarse_fix_check(const char* who, const gpsacq_engine* e, const gpsac
     return coarse_params(who, params, checked);
 }
 
+// the host forms can read their priors: one that names no place or no instant of the week is an argument error
+static int coarse_check_priors(const char* who, const gpsacq_coarse_prior* prior, size_t n_fix) {
+    for (size_t k = 0; k < n_fix; ++k)
+        if (prior[k].rx_ms < 0 || prior[k].rx_ms >= 604800000 || !std::isfinite(prior[k].x) || !std::isfinite(prior[k].y) || !std::isfinite(prior[k].z))
+            return fail(GPSACQ_ERR_ARG, "%s: prior %zu is (%g, %g, %g) at rx_ms %d (must be finite, 0 <= rx_ms < 604800000)", who, k, prior[k].x,
+                        prior[k].y, prior[k].z, (int)prior[k].rx_ms);
+    return GPSACQ_OK;
+}
+
 static int coarse_obs_check(const char* who, const gpsacq_engine* e, const void* peaks, size_t n_fix, int n_chans, double snr_min, const void* obs) {
     if (!e || !peaks || !obs || n_fix == 0 || n_fix > ((size_t)1 << 31)) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
     if (n_chans < 1 || n_chans > GPSACQ_FIX_MAX_SATS) return fail(GPSACQ_ERR_ARG, "%s: n_chans %d outside 1 .. %d", who, n_chans, GPSACQ_FIX_MAX_SATS);
@@ -1144,10 +1159,7 @@ extern "C" int gpsacq_coarse_fix_batch(gpsacq_engine* e, const gpsacq_ephemeris*
         return rc;
     const size_t n_obs = n_fix * (size_t)sats_per_fix;
     if (int rc = nav_check_weights("gpsacq_coarse_fix_batch", obs, n_obs)) return rc;
-    for (size_t k = 0; k < n_fix; ++k)
-        if (prior[k].rx_ms < 0 || prior[k].rx_ms >= 604800000 || !std::isfinite(prior[k].x) || !std::isfinite(prior[k].y) || !std::isfinite(prior[k].z))
-            return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_fix_batch: prior %zu is (%g, %g, %g) at rx_ms %d (must be finite, 0 <= rx_ms < 604800000)", k,
-                        prior[k].x, prior[k].y, prior[k].z, (int)prior[k].rx_ms);
+    if (int rc = coarse_check_priors("gpsacq_coarse_fix_batch", prior, n_fix)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = e->d_coarse_work.grow(n_obs, e->stream)) return rc;
     if (int rc = e->d_nav_fix.grow(n_fix, e->stream)) return rc;
@@ -1184,6 +1196,80 @@ extern "C" int gpsacq_coarse_last_ms(const gpsacq_engine* e, float* obs_ms, floa
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = stage_ms(e->coarse_obs_t, obs_ms)) return rc;
     return stage_ms(e->coarse_fix_t, fix_ms);
+}
+
+// ---- coarse-time fix integrity: residual test and one-satellite exclusion (coarse_kernels.hip) -----------------------------------
+static int coarse_raim_check(const char* who, const gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* obs, const void* prior,
+                             size_t n_fix, int sats_per_fix, const gpsacq_coarse_params* params, const gpsacq_raim_params* rp, const void* fix,
+                             const void* info, const void* obs_out, const void* raim, gpsacq_coarse_params* checked) {
+    if (int rc = coarse_fix_check(who, e, eph, n_eph, obs, prior, n_fix, sats_per_fix, params, fix, info, obs_out, checked)) return rc;
+    if (!raim) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    return raim_params_check(who, rp);
+}
+
+extern "C" int gpsacq_coarse_raim_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_prior,
+                                               size_t n_fix, int sats_per_fix, const gpsacq_coarse_params* coarse_par,
+                                               const gpsacq_raim_params* raim_params, void* d_fix, void* d_info, void* d_obs_out, void* d_raim,
+                                               int sync) {
+    gpsacq_coarse_params cp;
+    if (int rc = coarse_raim_check("gpsacq_coarse_raim_batch", e, eph, n_eph, d_obs, d_prior, n_fix, sats_per_fix, coarse_par, raim_params, d_fix, d_info,
+                                   d_obs_out, d_raim, &cp))
+        return rc;
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
+    void* d_work = d_obs_out;
+    if (int rc = or_own(e, d_work, e->d_coarse_work, n_obs)) return rc;  // FULL's whole milliseconds live somewhere
+    if (int rc = e->d_coarse_cand.grow(n_obs * (size_t)sats_per_fix, e->stream)) return rc;
+    const CoarseFixArgs full{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, (const gpsacq_coarse_prior*)d_prior, n_fix, sats_per_fix, cp,
+                             (gpsacq_fix*)d_fix, (gpsacq_coarse_info*)d_info, (gpsacq_obs*)d_work};
+    if (int rc = e->coarse_raim_t.begin(e->stream)) return rc;
+    launch_coarse_fix(full, e->stream);
+    if (int rc = e->coarse_raim_t.mark(1, e->stream)) return rc;
+    // always: which rows were flagged is known on the device only
+    launch_coarse_exclude(CoarseRaimArgs{full, *raim_params, (gpsacq_fix_raim*)d_raim, e->d_coarse_cand, (gpsacq_obs*)d_obs_out}, e->stream);
+    if (int rc = e->coarse_raim_t.mark(2, e->stream)) return rc;
+    if (int rc = e->coarse_raim_t.finish()) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_raim_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs,
+                                        const gpsacq_coarse_prior* prior, size_t n_fix, int sats_per_fix, const gpsacq_coarse_params* coarse_par,
+                                        const gpsacq_raim_params* raim_params, gpsacq_fix* fix_out, gpsacq_coarse_info* info_out,
+                                        gpsacq_obs* obs_out, gpsacq_fix_raim* raim_out) {
+    gpsacq_coarse_params cp;
+    if (int rc = coarse_raim_check("gpsacq_coarse_raim_batch", e, eph, n_eph, obs, prior, n_fix, sats_per_fix, coarse_par, raim_params, fix_out, info_out,
+                                   obs_out, raim_out, &cp))
+        return rc;
+    const size_t n_obs = n_fix * (size_t)sats_per_fix;
+    if (int rc = nav_check_weights("gpsacq_coarse_raim_batch", obs, n_obs)) return rc;
+    if (int rc = coarse_check_priors("gpsacq_coarse_raim_batch", prior, n_fix)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = e->d_coarse_work.grow(n_obs, e->stream)) return rc;
+    if (int rc = e->d_nav_fix.grow(n_fix, e->stream)) return rc;
+    if (int rc = e->d_coarse_info.grow(n_fix, e->stream)) return rc;
+    if (int rc = e->d_raim.grow(n_fix, e->stream)) return rc;
+    if (int rc = upload(e, e->d_nav_obs, obs, n_obs)) return rc;
+    if (int rc = upload(e, e->d_coarse_prior, prior, n_fix)) return rc;
+    // d_coarse_work as the caller's obs_out: the winning lane of an excluded row copies its observations there
+    if (int rc = gpsacq_coarse_raim_batch_device(e, eph, n_eph, e->d_nav_obs, e->d_coarse_prior, n_fix, sats_per_fix, &cp, raim_params, e->d_nav_fix,
+                                                 e->d_coarse_info, e->d_coarse_work, e->d_raim, 0))
+        return rc;
+    if (int rc = download(e, fix_out, e->d_nav_fix, n_fix)) return rc;
+    if (int rc = download(e, info_out, e->d_coarse_info, n_fix)) return rc;
+    if (int rc = download(e, obs_out, e->d_coarse_work, n_obs)) return rc;
+    if (int rc = download(e, raim_out, e->d_raim, n_fix)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_raim_last_ms(const gpsacq_engine* e, float* fix_ms, float* exclude_ms) {
+    if (!e || !e->coarse_raim_t.ran()) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_raim_last_ms: no gpsacq_coarse_raim_batch call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = e->coarse_raim_t.wait()) return rc;
+    if (int rc = e->coarse_raim_t.elapsed(0, 1, fix_ms)) return rc;
+    return e->coarse_raim_t.elapsed(1, 2, exclude_ms);
 }
 
 // ---- fine code phases: search peaks refined below a sample (refine_kernels.hip) --------------------------------------------------

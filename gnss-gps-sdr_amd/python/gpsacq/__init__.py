@@ -194,6 +194,7 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_fix_quality_track_device", "gpsacq_quality_last_ms",
            "gpsacq_coarse_default_params", "gpsacq_coarse_fix_batch", "gpsacq_coarse_fix_batch_device", "gpsacq_coarse_obs",
            "gpsacq_coarse_obs_device", "gpsacq_coarse_fix_peaks_device", "gpsacq_coarse_last_ms",
+           "gpsacq_coarse_raim_batch", "gpsacq_coarse_raim_batch_device", "gpsacq_coarse_raim_last_ms",
            "gpsacq_refine_default_params", "gpsacq_refine", "gpsacq_refine_device", "gpsacq_coarse_obs_fine", "gpsacq_coarse_obs_fine_device",
            "gpsacq_coarse_fix_fine_device", "gpsacq_refine_last_ms",
            "gpsacq_dopfine_default_params", "gpsacq_doppler_fix_default_params", "gpsacq_fine_doppler", "gpsacq_fine_doppler_device",
@@ -477,6 +478,12 @@ def load_library(path=None):
     lib.gpsacq_coarse_fix_peaks_device.restype = ctypes.c_int
     lib.gpsacq_coarse_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
     lib.gpsacq_coarse_last_ms.restype = ctypes.c_int
+    lib.gpsacq_coarse_raim_batch.argtypes = [vp, vp, ctypes.c_int, vp, vp, sz, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+    lib.gpsacq_coarse_raim_batch.restype = ctypes.c_int
+    lib.gpsacq_coarse_raim_batch_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, sz, ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_coarse_raim_batch_device.restype = ctypes.c_int
+    lib.gpsacq_coarse_raim_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
+    lib.gpsacq_coarse_raim_last_ms.restype = ctypes.c_int
     lib.gpsacq_refine_default_params.argtypes = [vp]
     lib.gpsacq_refine_default_params.restype = ctypes.c_int
     lib.gpsacq_refine.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp]
@@ -1335,6 +1342,44 @@ class Engine:
         _check(self._lib, self._lib.gpsacq_coarse_fix_batch_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_obs_ptr, d_prior_ptr,
                                                                    int(n_fix), int(sats_per_fix), cp, d_fix_ptr, d_info_ptr, d_obs_out_ptr,
                                                                    1 if sync else 0))
+
+    def coarse_fix_raim(self, eph, obs, prior, raim_params, params=None):
+        """gpsacq_coarse_raim_batch: coarse_fix() followed by the chi-square test of its residuals against raim_params
+        (raim_params(), sigma_m the range sigma of a code phase of weight 1) and, where the test fails, the exclusion of the one
+        code phase without which the row passes -- the whole solve again, whole milliseconds included.  Returns (FIX_DTYPE [n_fix],
+        COARSE_INFO_DTYPE [n_fix], OBS_DTYPE [n_fix][sats_per_fix], FIX_RAIM_DTYPE [n_fix]); the first three are coarse_fix()'s of the
+        row, or of the row without the excluded column.  params: coarse_params(), None for the defaults."""
+        ep, ob = self._nav_arrays(eph, obs)
+        if ob.ndim != 2:
+            raise ValueError("obs must be [n_fix][sats_per_fix]")
+        pr = np.ascontiguousarray(np.broadcast_to(np.asarray(prior, dtype=COARSE_PRIOR_DTYPE).ravel(), (ob.shape[0],)))
+        cr, cp = self._coarse_params(params)
+        rr, rp = self._raim_params(raim_params)
+        out = np.zeros(ob.shape[0], dtype=FIX_DTYPE)
+        info = np.zeros(ob.shape[0], dtype=COARSE_INFO_DTYPE)
+        oo = np.zeros(ob.shape, dtype=OBS_DTYPE)
+        rm = np.zeros(ob.shape[0], dtype=FIX_RAIM_DTYPE)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_coarse_raim_batch(self._h, p(ep), int(ep.size), p(ob), p(pr), int(ob.shape[0]), int(ob.shape[1]), cp, rp,
+                                                             p(out), p(info), p(oo), p(rm)))
+        return out, info, oo, rm
+
+    def coarse_fix_raim_device(self, eph, d_obs_ptr, d_prior_ptr, n_fix, sats_per_fix, raim_params, d_fix_ptr, d_info_ptr, d_raim_ptr,
+                               d_obs_out_ptr=None, params=None, sync=True):
+        """gpsacq_coarse_raim_batch_device: device pointers for the observations, the priors and the outputs; d_obs_out_ptr may be
+        None."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        cr, cp = self._coarse_params(params)
+        rr, rp = self._raim_params(raim_params)
+        _check(self._lib, self._lib.gpsacq_coarse_raim_batch_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_obs_ptr, d_prior_ptr,
+                                                                    int(n_fix), int(sats_per_fix), cp, rp, d_fix_ptr, d_info_ptr, d_obs_out_ptr,
+                                                                    d_raim_ptr, 1 if sync else 0))
+
+    def coarse_raim_last_ms(self):
+        """Device milliseconds of the last coarse_fix_raim* call: (k_coarse_fix, k_coarse_exclude)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(self._lib, self._lib.gpsacq_coarse_raim_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def coarse_obs(self, peaks, snr_min=THRESHOLD, fine=None):
         """gpsacq_coarse_obs: search peaks (PEAK_DTYPE [n_fix][n_chans], block outer and channel inner) into code-phase observations

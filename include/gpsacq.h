@@ -1527,6 +1527,87 @@ GPSACQ_API int gpsacq_coarse_fix_peaks_device(gpsacq_engine* e, const gpsacq_eph
 GPSACQ_API int gpsacq_coarse_last_ms(const gpsacq_engine* e, float* obs_ms, float* fix_ms);
 
 /*
+ * ---- Coarse-time fix integrity: residual test and one-satellite exclusion ------------------------------------------------------
+ *
+ * gpsacq_coarse_fix_batch trusts every code phase it is given, and a code phase that is wrong -- a sidelobe at snr_min, a
+ * cross-correlation peak of the aided searches -- is not the 150 m of a slipped chip that "Fix integrity" guards against: it is
+ * up to half a millisecond, 150 km.  All the solver says of it is GPSACQ_COARSE_INCONSISTENT, and the row is lost.
+ * gpsacq_fix_raim_batch on obs_out cannot mend the row either: the false observation has bent the fifth unknown s, every transmit
+ * time of obs_out carries that s, and the other satellites are evaluated seconds from where they were.  This section is the
+ * test and the exclusion on the coarse-time solve itself.  THE MODEL; the kernel (csrc/coarse_kernels.hip: k_coarse_exclude,
+ * behind k_coarse_fix) and tests/coarse_raim_ref.py are both written from this text.  Nothing of the sections above changes:
+ * gpsacq_coarse_fix_batch* computes what it did.
+ *
+ * INPUTS as for gpsacq_coarse_fix_batch, and a gpsacq_raim_params of "Fix integrity" (the same 88 bytes), of which sigma_m,
+ * threshold[] and exclude are read.  sigma_m is the standard deviation, in metres, of the range a code phase of weight 1 stands
+ * for (c times its error in seconds); a weight w means sigma_m^2 / w.  Five unknowns leave at most GPSACQ_FIX_MAX_SATS - 5 = 7
+ * degrees of freedom, so only threshold[0..6] can be reached.  USABLE as in "Coarse-time fixes".  W is the sum of the weights of
+ * the usable observations of the row, n_w the number of them with weight > 0.
+ *
+ * PER ROW:
+ *   1. FULL.  The coarse-time fix of the row, steps A, B and C of "Coarse-time fixes" unchanged: the three records are those
+ *      gpsacq_coarse_fix_batch writes.  Not GPSACQ_FIX_OK: raim status GPSACQ_RAIM_NONE.
+ *   2. TEST.  d = n_w - 5 and
+ *          T = rms^2 W / sigma_m^2,
+ *      rms the value in FULL's gpsacq_fix record: sqrt(sum w res^2 / sum w) over the residuals the last step was made from.  No
+ *      further pass over the orbits is made for it.  This is NOT the statistic of "Fix integrity", whose residuals are
+ *      recomputed at the state after the last step: the two differ by what the last step moved the residuals, and that step is
+ *      below 1e-4 m.  d < 1: GPSACQ_RAIM_UNCHECKED.  T <= threshold[d - 1]: GPSACQ_RAIM_PASS.  In both the outputs are FULL's.
+ *   3. EXCLUDE.  exclude == 0 or d < 2: GPSACQ_RAIM_FAILED, the outputs are FULL's.  Otherwise there is one candidate for every
+ *      usable column k with w_k > 0: the complete coarse-time fix of the row with column k taken as not usable -- from the
+ *      prior, not from FULL's state, AND WITH STEP A DONE AGAIN, so that a candidate which drops the reference column takes the
+ *      next usable one as its reference and rounds every whole millisecond against it.  (A false reference bends delta, and
+ *      with it every N_k of FULL; nothing of FULL's whole milliseconds can be kept.)  A candidate that is not GPSACQ_FIX_OK is no
+ *      candidate.  T_k = rms_k^2 (W - w_k) / sigma_m^2, rms_k the candidate's rms.  The winner is the smallest T_k, on a tie the
+ *      lowest k.  No candidate, or T_k > threshold[d - 2]: GPSACQ_RAIM_FAILED, the outputs are FULL's.
+ *   4. EXCLUDED.  gpsacq_fix, gpsacq_coarse_info and obs_out are the winner's: what gpsacq_coarse_fix_batch gives for the row with
+ *      `valid` of column k cleared -- n_used one less, column k of obs_out 32 zero bytes, ref, pdop / cdop and
+ *      GPSACQ_COARSE_INCONSISTENT the candidate's own.  `iterations` alone differs: it counts FULL's steps and the winner's (not
+ *      the losing candidates'), as gpsacq_fix_raim_batch does.  Status GPSACQ_RAIM_EXCLUDED.
+ *
+ * gpsacq_fix_raim as in "Fix integrity": dof, stat and threshold describe the solution that was output -- PASS and FAILED: d, T,
+ * threshold[d - 1]; UNCHECKED: d (0 or less), T, 0; EXCLUDED: d - 1, T_k, threshold[d - 2], excluded = k.  stat_full = T.
+ * excluded is the column in the row, or -1.  n_candidates is the number of candidates that were GPSACQ_FIX_OK, 0 if step 3 did
+ * not run.  GPSACQ_RAIM_NONE: every other field 0, excluded -1.
+ * Weight-0 observations stay in the solves as they do in "Coarse-time fixes": they add nothing to rms or T, do not count in
+ * n_w, and are never candidates.
+ * What the test can do follows from d.  Eight and nine satellites (d = 3, 4): a false code phase is the one column whose
+ * candidate passes.  Seven (d = 2): a candidate has ONE degree of freedom left, so the smallest T_k need not be the false
+ * column's, as with six satellites in "Fix integrity".  Six (d = 1): every candidate would have zero residual; FAILED, none is
+ * tried.  Five: UNCHECKED.
+ *
+ * gpsacq_coarse_raim_batch: host pointers, returns after completion.  gpsacq_coarse_raim_batch_device: obs, prior and the four
+ * outputs are device pointers, eph and both params host pointers; work on the engine's stream, sync != 0 waits.  Arguments as
+ * gpsacq_coarse_fix_batch* (coarse_params NULL means the defaults; obs_out / d_obs_out may be NULL and must not be obs; the host
+ * form refuses a bad weight or prior, the _device form skips the observation or the row) and as gpsacq_fix_raim_batch* for the
+ * raim parameters: raim_params NULL is GPSACQ_ERR_ARG, sigma_m and all eight thresholds finite and > 0, exclude 0 or 1.  raim_out
+ * / d_raim may not be NULL.  Argument errors launch nothing and write nothing.  The two forms agree byte for byte.
+ * Kernels (csrc/coarse_kernels.hip), two launches on the engine's stream.  k_coarse_fix as it is: FULL.  k_coarse_exclude, sixteen
+ * lanes per fix and four fixes per wave64, always launched (whether a row was flagged is known on the device only): every lane
+ * of a group reads FULL's record and makes the test; a group whose row needs no exclusion writes its raim record and returns,
+ * so exclude_ms is small but never 0; otherwise lane k < sats_per_fix solves the row without column k -- the one solve of
+ * k_coarse_fix with a column to skip, reading the caller's obs and working in a row of its own in engine scratch
+ * ([n_fix][sats_per_fix][sats_per_fix] observations), because the candidates of a fix run side by side and their whole
+ * milliseconds differ -- the smallest (T_k, k) and the count meet in a butterfly across the sixteen lanes, and the winning lane
+ * alone writes the three records and copies its row to obs_out.  No LDS, no atomics, no barrier; every loop is bounded.
+ *
+ * OUT OF SCOPE.  More than one exclusion per fix.  Protection levels.  Exclusion where FULL itself is not GPSACQ_FIX_OK.  A sigma
+ * of our own code phases: the caller passes one (README: 19.93 m whole-sample and 3.41 m fine were measured on the generated
+ * scene at amplitude 0.2).  gps_test and gps_track.
+ */
+GPSACQ_API int gpsacq_coarse_raim_batch(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_obs* obs /* [n_fix][sats_per_fix] */,
+                                        const gpsacq_coarse_prior* prior, size_t n_fix, int sats_per_fix, const gpsacq_coarse_params* coarse_params,
+                                        const gpsacq_raim_params* raim_params, gpsacq_fix* fix_out, gpsacq_coarse_info* info_out,
+                                        gpsacq_obs* obs_out, gpsacq_fix_raim* raim_out);
+GPSACQ_API int gpsacq_coarse_raim_batch_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_obs, const void* d_prior,
+                                               size_t n_fix, int sats_per_fix, const gpsacq_coarse_params* coarse_params,
+                                               const gpsacq_raim_params* raim_params, void* d_fix, void* d_info, void* d_obs_out, void* d_raim,
+                                               int sync);
+/* device time of the two kernels of the last gpsacq_coarse_raim_batch* call on this engine, milliseconds (HIP events on its stream;
+ * waits for them): k_coarse_fix, k_coarse_exclude.  Either pointer may be NULL. */
+GPSACQ_API int gpsacq_coarse_raim_last_ms(const gpsacq_engine* e, float* fix_ms, float* exclude_ms);
+
+/*
  * ---- Fine code phases: search peaks refined below a sample --------------------------------------------------------------------
  *
  * A search peak carries its code phase in whole samples: tx_frac = ca_shift / fs is off by up to half a sample, 27 m of range at
