@@ -214,6 +214,10 @@ struct gpsacq_engine {
     Scratch<gpsacq_peak> d_refine_peaks;  // also the peaks of the host-buffer form of gpsacq_coarse_obs_fine
     Scratch<gpsacq_fine> d_fine;  // host-buffer forms, and k_refine's output where the caller of the chain wants no records
     Stages<2> refine_t, refine_obs_t;  // around k_refine, around k_coarse_obs_fine
+    // snapshot signal quality (gpsacq_snap_quality*, gpsacq_coarse_fix_quality_device); the host-buffer form stages its records in
+    // d_fine and its observations in d_coarse_obs
+    Scratch<gpsacq_quality_info> d_snapq_info;  // host-buffer form, and where the caller of the chain wants no info
+    Stages<2> snapq_t;                          // around k_snap_quality
     // cold snapshot fixes (gpsacq_fine_doppler*, gpsacq_rate_obs_fine*, gpsacq_doppler_fix_batch*, gpsacq_cold_fix_device); the
     // host-buffer forms stage the capture, tasks and peaks in the d_refine_* buffers above and the observations in d_nav_obs / d_rate_obs
     Scratch<gpsacq_dopfine> d_dopfine;  // host-buffer forms, and k_fine_dop's output where the caller of the chain wants no records

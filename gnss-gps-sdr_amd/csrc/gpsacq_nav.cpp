@@ -10,6 +10,7 @@
 // fixes": gpsacq_coarse_obs*, gpsacq_coarse_fix_batch* and gpsacq_coarse_fix_peaks_device, which run coarse_kernels.hip, and
 // "Coarse-time fix integrity": gpsacq_coarse_raim_batch*, which run its k_coarse_fix and k_coarse_exclude.  Last of
 // all "Fine code phases": gpsacq_refine*, gpsacq_coarse_obs_fine* and gpsacq_coarse_fix_fine_device, which run refine_kernels.hip, and
+// "Snapshot signal quality": gpsacq_snap_quality* and gpsacq_coarse_fix_quality_device, which run snapq_kernels.hip, and
 // "Cold snapshot fixes": gpsacq_fine_doppler*, gpsacq_rate_obs_fine*, gpsacq_doppler_fix_batch* and gpsacq_cold_fix_device, which run
 // doppler_kernels.hip, and "Aided acquisition": gpsacq_aid_predict*, gpsacq_aided_search* and gpsacq_aided_peaks_device, which run
 // aided_kernels.hip.
@@ -30,6 +31,7 @@
 #include "refine_launch.hpp"
 #include "aided_launch.hpp"
 #include "smooth_launch.hpp"
+#include "snapq_launch.hpp"
 
 using namespace acq;
 
@@ -1436,6 +1438,104 @@ extern "C" int gpsacq_refine_last_ms(const gpsacq_engine* e, float* refine_ms, f
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = stage_ms(e->refine_t, refine_ms)) return rc;
     return stage_ms(e->refine_obs_t, obs_ms);
+}
+
+// ---- snapshot signal quality: C/N0 and weights of fine code phases (snapq_kernels.hip) -----------------------------------------
+extern "C" int gpsacq_snap_quality_default_params(gpsacq_snap_quality_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_snap_quality_default_params: null argument");
+    std::memset(p, 0, sizeof *p);
+    p->min_segments = 1;
+    p->cn0_min_lin = 500.0;
+    p->cn0_ref_lin = std::pow(10.0, 4.35);
+    return GPSACQ_OK;
+}
+
+// the caller's parameters or the defaults into *out, checked
+static int snap_quality_params(const char* who, const gpsacq_snap_quality_params* params, gpsacq_snap_quality_params* out) {
+    if (!params) return gpsacq_snap_quality_default_params(out);
+    *out = *params;
+    if (out->min_segments < 1) return fail(GPSACQ_ERR_ARG, "%s: min_segments %d (must be >= 1)", who, (int)out->min_segments);
+    if (!(out->cn0_min_lin >= 0.0) || !std::isfinite(out->cn0_min_lin)) return fail(GPSACQ_ERR_ARG, "%s: cn0_min_lin %g must be finite and >= 0", who, out->cn0_min_lin);
+    if (!(out->cn0_ref_lin > 0.0) || !std::isfinite(out->cn0_ref_lin)) return fail(GPSACQ_ERR_ARG, "%s: cn0_ref_lin %g must be finite and > 0", who, out->cn0_ref_lin);
+    return GPSACQ_OK;
+}
+
+static int snap_quality_check(const char* who, const gpsacq_engine* e, const void* fine, size_t n_fix, int n_chans,
+                              const gpsacq_snap_quality_params* params, const void* info, gpsacq_snap_quality_params* checked) {
+    if (!e || !fine || !info || n_fix == 0 || n_fix > ((size_t)1 << 31)) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (n_chans < 1 || n_chans > GPSACQ_FIX_MAX_SATS) return fail(GPSACQ_ERR_ARG, "%s: n_chans %d outside 1 .. %d", who, n_chans, GPSACQ_FIX_MAX_SATS);
+    return snap_quality_params(who, params, checked);
+}
+
+// k_snap_quality on the engine's stream timed; every argument has been checked
+static int snap_quality_enqueue(gpsacq_engine* e, const void* d_fine, size_t n_fix, int n_chans, const gpsacq_snap_quality_params& qp, void* d_obs,
+                                void* d_info) {
+    if (int rc = e->snapq_t.begin(e->stream)) return rc;
+    launch_snap_quality(SnapQualityArgs{(const gpsacq_fine*)d_fine, n_fix * (size_t)n_chans, e->nlags, e->p.fs, qp, (gpsacq_obs*)d_obs,
+                                        (gpsacq_quality_info*)d_info},
+                        e->stream);
+    if (int rc = e->snapq_t.mark(1, e->stream)) return rc;
+    return e->snapq_t.finish();
+}
+
+extern "C" int gpsacq_snap_quality_device(gpsacq_engine* e, const void* d_fine, size_t n_fix, int n_chans, const gpsacq_snap_quality_params* params,
+                                          void* d_obs, void* d_info, int sync) {
+    gpsacq_snap_quality_params qp;
+    if (int rc = snap_quality_check("gpsacq_snap_quality", e, d_fine, n_fix, n_chans, params, d_info, &qp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = snap_quality_enqueue(e, d_fine, n_fix, n_chans, qp, d_obs, d_info)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_snap_quality(gpsacq_engine* e, const gpsacq_fine* fine, size_t n_fix, int n_chans, const gpsacq_snap_quality_params* params,
+                                   gpsacq_obs* obs, gpsacq_quality_info* info) {
+    gpsacq_snap_quality_params qp;
+    if (int rc = snap_quality_check("gpsacq_snap_quality", e, fine, n_fix, n_chans, params, info, &qp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_obs = n_fix * (size_t)n_chans;
+    if (int rc = e->d_snapq_info.grow(n_obs, e->stream)) return rc;
+    if (int rc = upload(e, e->d_fine, fine, n_obs)) return rc;
+    if (obs)
+        if (int rc = upload(e, e->d_coarse_obs, (const gpsacq_obs*)obs, n_obs)) return rc;
+    if (int rc = snap_quality_enqueue(e, e->d_fine, n_fix, n_chans, qp, obs ? e->d_coarse_obs.p : nullptr, e->d_snapq_info)) return rc;
+    if (int rc = download(e, obs, e->d_coarse_obs, n_obs)) return rc;
+    if (int rc = download(e, info, e->d_snapq_info, n_obs)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_fix_quality_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_bits, size_t n_bytes,
+                                                size_t stride, const void* d_tasks, const void* d_peaks, size_t n_fix, int n_chans,
+                                                const gpsacq_refine_params* refine_par, const gpsacq_snap_quality_params* quality_par,
+                                                const void* d_prior, const gpsacq_coarse_params* params, void* d_fine, void* d_obs, void* d_qinfo,
+                                                void* d_fix, void* d_info, void* d_obs_out, int sync) {
+    if (int rc = coarse_obs_check("gpsacq_coarse_fix_quality", e, d_peaks, n_fix, n_chans, 0.0, d_fix)) return rc;
+    if (!eph || n_eph <= 0 || !d_prior || !d_info) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_fix_quality: bad argument");
+    if (d_obs && d_obs_out == d_obs) return fail(GPSACQ_ERR_ARG, "gpsacq_coarse_fix_quality: obs_out must not be obs");
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    gpsacq_refine_params rp;
+    if (int rc = refine_check("gpsacq_coarse_fix_quality", e, d_bits, n_bytes, stride, d_peaks, n_tasks, refine_par, d_fix, &rp)) return rc;
+    gpsacq_snap_quality_params qp;
+    if (int rc = snap_quality_params("gpsacq_coarse_fix_quality", quality_par, &qp)) return rc;
+    gpsacq_coarse_params cp;
+    if (int rc = coarse_params("gpsacq_coarse_fix_quality", params, &cp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = or_own(e, d_fine, e->d_fine, n_tasks)) return rc;
+    if (int rc = or_own(e, d_obs, e->d_coarse_obs, n_tasks)) return rc;
+    if (int rc = or_own(e, d_qinfo, e->d_snapq_info, n_tasks)) return rc;
+    if (int rc = refine_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, rp, d_fine)) return rc;
+    if (int rc = coarse_obs_fine_enqueue(e, d_peaks, d_fine, n_fix, n_chans, rp.snr_min, d_obs)) return rc;
+    if (int rc = snap_quality_enqueue(e, d_fine, n_fix, n_chans, qp, d_obs, d_qinfo)) return rc;
+    if (int rc = coarse_fix_enqueue(e, eph, n_eph, d_obs, d_prior, n_fix, n_chans, cp, d_fix, d_info, d_obs_out)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_snap_quality_last_ms(const gpsacq_engine* e, float* ms) {
+    if (!e || !e->snapq_t.ran()) return fail(GPSACQ_ERR_ARG, "gpsacq_snap_quality_last_ms: no gpsacq_snap_quality call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    return stage_ms(e->snapq_t, ms);
 }
 
 // ---- cold snapshot fixes: fine Doppler and a Doppler-only position solver (doppler_kernels.hip) ----------------------------------

@@ -158,6 +158,9 @@ QUALITY_PARAMS_DTYPE = np.dtype([("epochs", "<i4"), ("min_epochs", "<i4"), ("loc
                                  ("reserved", "<i4"), ("cn0_min_lin", "<f8"), ("cn0_ref_lin", "<f8"), ("cn0_cap_dbhz", "<f8")])
 QUALITY_INFO_DTYPE = np.dtype([("epochs", "<i4"), ("flags", "<i4"), ("sig", "<u8"), ("noise", "<u8"), ("lin", "<f8"), ("cn0_dbhz", "<f8"),
                                ("weight", "<f8")])
+# snapshot signal quality (include/gpsacq.h "Snapshot signal quality"): its info records are QUALITY_INFO_DTYPE with epochs = segments
+QUALITY_NO_RECORD = 32
+SNAP_QUALITY_PARAMS_DTYPE = np.dtype([("min_segments", "<i4"), ("reserved", "<i4"), ("cn0_min_lin", "<f8"), ("cn0_ref_lin", "<f8")])
 
 
 class TrackParams(ctypes.Structure):
@@ -197,6 +200,8 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_coarse_raim_batch", "gpsacq_coarse_raim_batch_device", "gpsacq_coarse_raim_last_ms",
            "gpsacq_refine_default_params", "gpsacq_refine", "gpsacq_refine_device", "gpsacq_coarse_obs_fine", "gpsacq_coarse_obs_fine_device",
            "gpsacq_coarse_fix_fine_device", "gpsacq_refine_last_ms",
+           "gpsacq_snap_quality_default_params", "gpsacq_snap_quality", "gpsacq_snap_quality_device", "gpsacq_coarse_fix_quality_device",
+           "gpsacq_snap_quality_last_ms",
            "gpsacq_dopfine_default_params", "gpsacq_doppler_fix_default_params", "gpsacq_fine_doppler", "gpsacq_fine_doppler_device",
            "gpsacq_rate_obs_fine", "gpsacq_rate_obs_fine_device", "gpsacq_doppler_fix_batch", "gpsacq_doppler_fix_batch_device",
            "gpsacq_cold_fix_device", "gpsacq_doppler_last_ms",
@@ -498,6 +503,17 @@ def load_library(path=None):
     lib.gpsacq_coarse_fix_fine_device.restype = ctypes.c_int
     lib.gpsacq_refine_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
     lib.gpsacq_refine_last_ms.restype = ctypes.c_int
+    lib.gpsacq_snap_quality_default_params.argtypes = [vp]
+    lib.gpsacq_snap_quality_default_params.restype = ctypes.c_int
+    lib.gpsacq_snap_quality.argtypes = [vp, vp, sz, ctypes.c_int, vp, vp, vp]
+    lib.gpsacq_snap_quality.restype = ctypes.c_int
+    lib.gpsacq_snap_quality_device.argtypes = [vp, vp, sz, ctypes.c_int, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_snap_quality_device.restype = ctypes.c_int
+    lib.gpsacq_coarse_fix_quality_device.argtypes = [vp, vp, ctypes.c_int, vp, sz, sz, vp, vp, sz, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                     ctypes.c_int]
+    lib.gpsacq_coarse_fix_quality_device.restype = ctypes.c_int
+    lib.gpsacq_snap_quality_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    lib.gpsacq_snap_quality_last_ms.restype = ctypes.c_int
     lib.gpsacq_dopfine_default_params.argtypes = [vp]
     lib.gpsacq_dopfine_default_params.restype = ctypes.c_int
     lib.gpsacq_doppler_fix_default_params.argtypes = [vp]
@@ -842,6 +858,26 @@ def quality_params(cn0_min_dbhz=30, cn0_ref_dbhz=45, **overrides):
     for k, v in overrides.items():
         if k not in QUALITY_PARAMS_DTYPE.names:
             raise TypeError("quality_params: no field %r" % k)
+        out[k] = v
+    return out
+
+
+def snap_quality_params(min_segments=1, cn0_min_dbhz=None, cn0_ref_dbhz=None, **overrides):
+    """gpsacq_snap_quality_default_params: a SNAP_QUALITY_PARAMS_DTYPE record of shape (1,) -- min_segments 1, the gate cn0_min_lin
+    500.0 (27.0 dB-Hz: 5.4 sigma of noise alone over 117 segments), the reference level cn0_ref_lin 10^4.35 (43.5 dB-Hz, weight 1
+    from there up) -- with min_segments, then the gate 10^(cn0_min_dbhz / 10) and the level 10^(cn0_ref_dbhz / 10) where given, then
+    the named fields replaced.  The entry points that take it check it."""
+    lib = load_library()
+    out = np.zeros(1, dtype=SNAP_QUALITY_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_snap_quality_default_params(out.ctypes.data_as(ctypes.c_void_p)))
+    out["min_segments"] = min_segments
+    if cn0_min_dbhz is not None:
+        out["cn0_min_lin"] = 10.0 ** (float(cn0_min_dbhz) / 10.0)
+    if cn0_ref_dbhz is not None:
+        out["cn0_ref_lin"] = 10.0 ** (float(cn0_ref_dbhz) / 10.0)
+    for k, v in overrides.items():
+        if k not in SNAP_QUALITY_PARAMS_DTYPE.names:
+            raise TypeError("snap_quality_params: no field %r" % k)
         out[k] = v
     return out
 
@@ -1456,6 +1492,61 @@ class Engine:
         a, b = ctypes.c_float(), ctypes.c_float()
         _check(self._lib, self._lib.gpsacq_refine_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    # ---- snapshot signal quality -----------------------------------------------------------
+    @staticmethod
+    def _snap_quality_params(params):
+        if params is None:
+            return None, None
+        pr = np.ascontiguousarray(np.asarray(params, dtype=SNAP_QUALITY_PARAMS_DTYPE).ravel())
+        if pr.size != 1:
+            raise ValueError("params must be one SNAP_QUALITY_PARAMS_DTYPE record")
+        return pr, pr.ctypes.data_as(ctypes.c_void_p)
+
+    def snap_quality(self, fine, obs=None, params=None):
+        """gpsacq_snap_quality: C/N0 (dB-Hz) and the weight of every fine record (FINE_DTYPE [n_fix][n_chans], as refine() returns
+        them for peaks of that shape) from its prompt power over the analytic floor.  params: snap_quality_params() (None: the
+        defaults).  Returns (None, info) with info QUALITY_INFO_DTYPE [n_fix][n_chans] (epochs = segments); with obs (OBS_DTYPE
+        [n_fix][n_chans], made by coarse_obs(peaks, fine=fine)) returns (a copy of obs with the weights set, info)."""
+        if not isinstance(fine, np.ndarray) or fine.dtype != FINE_DTYPE or fine.ndim != 2:
+            raise TypeError("fine must be a FINE_DTYPE array [n_fix][n_chans]")
+        fn = np.ascontiguousarray(fine)
+        ob = None
+        if obs is not None:
+            if not isinstance(obs, np.ndarray) or obs.dtype != OBS_DTYPE or obs.shape != fn.shape:
+                raise TypeError("obs must be an OBS_DTYPE array in the shape of fine")
+            ob = np.array(obs, order="C")
+        pr, pp = self._snap_quality_params(params)
+        inf = np.zeros(fn.shape, dtype=QUALITY_INFO_DTYPE)
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_snap_quality(self._h, p(fn), int(fn.shape[0]), int(fn.shape[1]), pp, p(ob), p(inf)))
+        return ob, inf
+
+    def snap_quality_device(self, d_fine_ptr, n_fix, n_chans, d_info_ptr, d_obs_ptr=None, params=None, sync=True):
+        """gpsacq_snap_quality_device: the records, the info and the in-out observations (may be None) in device memory."""
+        pr, pp = self._snap_quality_params(params)
+        _check(self._lib, self._lib.gpsacq_snap_quality_device(self._h, d_fine_ptr, int(n_fix), int(n_chans), pp, d_obs_ptr, d_info_ptr,
+                                                               1 if sync else 0))
+
+    def coarse_fix_quality_device(self, eph, d_bits_ptr, n_bytes, d_tasks_ptr, d_peaks_ptr, n_fix, n_chans, d_prior_ptr, d_fix_ptr, d_info_ptr,
+                                  d_fine_ptr=None, d_obs_ptr=None, d_qinfo_ptr=None, d_obs_out_ptr=None, stride=BLOCK_BYTES, refine_params=None,
+                                  quality_params=None, params=None, sync=True):
+        """gpsacq_coarse_fix_quality_device: coarse_fix_fine_device with the snapshot quality weights between the observations and
+        the fix, no host copy in between; d_fine_ptr, d_obs_ptr, d_qinfo_ptr and d_obs_out_ptr may be None."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        rr, rp = self._refine_params(refine_params)
+        qr, qp = self._snap_quality_params(quality_params)
+        cr, cp = self._coarse_params(params)
+        _check(self._lib, self._lib.gpsacq_coarse_fix_quality_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_bits_ptr,
+                                                                     int(n_bytes), int(stride), d_tasks_ptr, d_peaks_ptr, int(n_fix), int(n_chans),
+                                                                     rp, qp, d_prior_ptr, cp, d_fine_ptr, d_obs_ptr, d_qinfo_ptr, d_fix_ptr,
+                                                                     d_info_ptr, d_obs_out_ptr, 1 if sync else 0))
+
+    def snap_quality_last_ms(self):
+        """Device milliseconds of k_snap_quality as last run on this engine."""
+        a = ctypes.c_float()
+        _check(self._lib, self._lib.gpsacq_snap_quality_last_ms(self._h, ctypes.byref(a)))
+        return a.value
 
     # ---- cold snapshot fixes ----------------------------------------------------------------
     @staticmethod

@@ -1711,6 +1711,92 @@ GPSACQ_API int gpsacq_coarse_fix_fine_device(gpsacq_engine* e, const gpsacq_ephe
 GPSACQ_API int gpsacq_refine_last_ms(const gpsacq_engine* e, float* refine_ms, float* obs_ms);
 
 /*
+ * ---- Snapshot signal quality: C/N0 and the weight of a code-phase observation ---------------------------------------------------
+ *
+ * gpsacq_coarse_obs and gpsacq_coarse_obs_fine write weight = 1.0, and a satellite that aided acquisition dug out 10 dB below the
+ * search threshold then pulls on a fix as hard as one at 44 dB-Hz, though its fine code phase is three to four times as noisy.
+ * This section is the snapshot chain's counterpart of "Signal quality per observation": a carrier-to-noise density estimate per
+ * fine record and from it a weight in [0, 1].  Nothing goes back to the capture: gpsacq_refine kept the prompt power and the
+ * segment count, and the noise floor of a +-1 stream is analytic.  THE MODEL; the kernel (csrc/snapq_kernels.hip) and the reference
+ * of the tests (tests/snapq_ref.py) are both written from this text.  Integers are uint64; every floating-point step is ONE named
+ * IEEE double operation (no fast-math flag and no contraction in the build).
+ *
+ * INPUTS.  fine[n_fix][n_chans]: the gpsacq_fine records, index-parallel with the peaks and the observations of
+ * gpsacq_coarse_obs_fine.  spm = gpsacq_info.num_lags and fs are the engine's.  A gpsacq_snap_quality_params.
+ *
+ * PER (fix, channel).
+ * 1. NO RECORD.  flags carries any of GPSACQ_FINE_NO_HIT, GPSACQ_FINE_NO_POWER, GPSACQ_FINE_FEW, or segments <= 0: the info is the
+ *    flag GPSACQ_QUALITY_NO_RECORD and zeros (epochs included), and the weight is 0.
+ * 2. FLOOR.  A segment of spm samples of a +-1 stream that is uncorrelated with the replica adds spm to E[I_P^2] and spm to
+ *    E[Q_P^2] (the two-level carrier replicas are +-1 too), so
+ *      floor = 2 * spm * segments          (uint64; spm and segments are below 2^31, nothing overflows)
+ *      sig   = prompt > floor ? prompt - floor : 0
+ *      noise = floor
+ *    -- the floor = 2 * spm * segments of "Aided acquisition".
+ * 3. sig == 0: flag GPSACQ_QUALITY_NO_POWER, lin = cn0_dbhz = weight = 0.
+ * 4. Otherwise
+ *      snr      = (double)sig / (double)floor       both conversions uint64 -> double, round to nearest even; one division
+ *      lin      = snr * (fs / (double)spm)          one division, one product: a segment is spm / fs seconds
+ *      cn0_dbhz = 10.0 * log10(lin)
+ * 5. Flag GPSACQ_QUALITY_SHORT when segments < params.min_segments.
+ * 6. WEIGHT.  weight = 0 if NO_RECORD, NO_POWER, SHORT or lin < params.cn0_min_lin.  Otherwise
+ *      w      = lin / params.cn0_ref_lin            one division
+ *      weight = w < 1.0 ? w : 1.0
+ * 7. The gate and the weight read lin, never cn0_dbhz, so every field but cn0_dbhz is reproducible byte for byte; log10 is the
+ *    only libm call.
+ *
+ * INFO per (fix, channel): the gpsacq_quality_info of "Signal quality per observation", 48 bytes, with epochs = segments (a segment
+ * is one code period, as an epoch is), flags, sig, noise, lin, cn0_dbhz, weight.  GPSACQ_QUALITY_SATURATED, _UNLOCKED and _FULL
+ * are never set here.
+ *
+ * THE OBSERVATION.  When a gpsacq_obs array obs[n_fix][n_chans] is given, every observation with valid != 0 has its weight replaced
+ * by this weight.  No other byte of it is written, and an observation with valid == 0 is not written at all.
+ *
+ * PARAMETERS.  gpsacq_snap_quality_default_params (host only): min_segments 1, reserved 0, cn0_min_lin 500.0, cn0_ref_lin
+ * 10^(43.5/10) (pow(10.0, 4.35)).  Valid: min_segments >= 1, cn0_min_lin finite and >= 0, cn0_ref_lin finite and > 0; anything else
+ * is GPSACQ_ERR_ARG.  params NULL = the defaults.
+ *   THE GATE.  For a stream uncorrelated with the replica prompt / floor has mean 1 and standard deviation 1 / sqrt(segments) (a
+ *   chi-square with two degrees of freedom per segment), so lin of noise alone has standard deviation (fs / spm) / sqrt(segments):
+ *   92 Hz at the default 117 segments, and the default gate of 500 Hz stands 5.4 of those above zero.  A caller with a shorter
+ *   window sets the gate from this law themselves.
+ *   THE REFERENCE LEVEL is what the amplitude-0.2 satellites of the bench scene read (43.6 dB-Hz simulated with tools/
+ *   snap_quality_law.py); sigma_m of gpsacq_raim_params is then the fine code-phase sigma at that level.
+ *
+ * LIMITS OF THE MODEL.  This is the C/N0 AFTER the 1-bit limiter, not the antenna's.  The prompt replica sits at the peak's whole
+ * sample: at 5.456 MHz that is up to 0.094 chips off, and the figure reads up to 0.9 dB low; half a Doppler bin costs another
+ * 0.07 dB.  An aided peak is the largest of its hypotheses, so it reads slightly high.  The weights follow the measured range
+ * variance of the fine code phase within a factor of about two, on the conservative side (amplitudes 0.2 .. 0.03 at 16 blocks:
+ * variance ratio 1 .. 0.05, weight 1 .. 0.024), and make no claim below cn0_min_lin.
+ *
+ * OUT OF SCOPE.  Whole-sample observations without a fine record, a measured noise floor, per-observation sigmas in
+ * gpsacq_raim_params, gps_test and gps_track, 8-bit IQ.
+ *
+ * gpsacq_snap_quality: host pointers, returns after completion; obs in-out and may be NULL.  gpsacq_snap_quality_device: fine, obs
+ * (may be NULL) and info are device pointers, params stays a host pointer; work on the engine's stream, sync != 0 waits.  The two
+ * agree byte for byte.  gpsacq_coarse_fix_quality_device: gpsacq_coarse_fix_fine_device with the weights between the observations
+ * and the fix -- k_refine, k_coarse_obs_fine, k_snap_quality and k_coarse_fix on the engine's stream with no host copy in between;
+ * d_qinfo[n_fix][n_chans] may be NULL (engine scratch), as d_fine and d_obs.  Argument errors -- a NULL fine or info, n_fix == 0,
+ * n_chans outside 1..GPSACQ_FIX_MAX_SATS, a parameter out of range, and for the chain those of gpsacq_coarse_fix_fine_device --
+ * return GPSACQ_ERR_ARG, launch nothing and write nothing.  Kernel (csrc/snapq_kernels.hip): k_snap_quality, one lane per
+ * (fix, channel); no LDS, no atomics, no loop.
+ */
+#define GPSACQ_QUALITY_NO_RECORD 32  /* snapshot quality only: the fine record is not usable; the info is this flag and zeros */
+typedef struct { int32_t min_segments, reserved; double cn0_min_lin, cn0_ref_lin; } gpsacq_snap_quality_params;   /* 24 bytes */
+GPSACQ_API int gpsacq_snap_quality_default_params(gpsacq_snap_quality_params* p);   /* host only */
+GPSACQ_API int gpsacq_snap_quality(gpsacq_engine* e, const gpsacq_fine* fine /* [n_fix][n_chans] */, size_t n_fix, int n_chans,
+                                   const gpsacq_snap_quality_params* params, gpsacq_obs* obs /* in-out, or NULL */, gpsacq_quality_info* info);
+GPSACQ_API int gpsacq_snap_quality_device(gpsacq_engine* e, const void* d_fine, size_t n_fix, int n_chans, const gpsacq_snap_quality_params* params,
+                                          void* d_obs, void* d_info, int sync);
+GPSACQ_API int gpsacq_coarse_fix_quality_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_bits, size_t n_bytes,
+                                                size_t stride, const void* d_tasks, const void* d_peaks, size_t n_fix, int n_chans,
+                                                const gpsacq_refine_params* refine_params, const gpsacq_snap_quality_params* quality_params,
+                                                const void* d_prior, const gpsacq_coarse_params* params, void* d_fine, void* d_obs, void* d_qinfo,
+                                                void* d_fix, void* d_info, void* d_obs_out, int sync);
+/* device time of k_snap_quality as last run on this engine, milliseconds (HIP events on its stream; waits for them).  ms may be
+ * NULL. */
+GPSACQ_API int gpsacq_snap_quality_last_ms(const gpsacq_engine* e, float* ms);
+
+/*
  * ---- Cold snapshot fixes: fine Doppler and a Doppler-only position solver ------------------------------------------------------
  *
  * The coarse-time solver wants a PRIOR: a place good to tens of kilometres (2 |dp| + 1600 m/s |dt| < 150 km, above).  A capture of

@@ -13,7 +13,7 @@ away from that instant the truth is off by the range acceleration (metres over 1
 is worth at 5.456 MHz.
 
     python tools/snapshot_bench.py [--blocks 2048] [--reps 5] [--refine [--refine-blocks 16]] [--cold] [--aided [--weak-amplitude 0.05]]
-                                   [--aided-coh [--weak-amplitude 0.03]] [--raim [--fault-share F] [--sigma-m S]]
+                                   [--aided-coh [--weak-amplitude 0.03]] [--raim [--fault-share F] [--sigma-m S]] [--quality]
 
 --refine: the capture is made K - 1 blocks longer (K = --refine-blocks) so that every searched block has its whole window, and
 each repetition also runs gpsacq_coarse_fix_fine_device on the same capture, tasks and peaks: k_refine (the fine code phases of
@@ -49,6 +49,13 @@ absent PRNs with the largest absent ratio; the error of doppler_hz against the g
 the share of their best_e equal to the generator's bit edge (the segment of the window nearest to where a data bit starts), exactly
 and within one segment.
 
+--quality: the --aided scene (it implies --aided) fixed a third time: each repetition also runs gpsacq_coarse_fix_quality_device on
+the merged peaks -- k_refine, k_coarse_obs_fine, k_snap_quality ("Snapshot signal quality" of include/gpsacq.h, the defaults) and
+k_coarse_fix at snr_min = ratio_min.  The line gains a "quality" object, all from one run: snap_quality_ms (k_snap_quality, best of
+the repetitions) beside refine_ms; the C/N0 the eight strong satellites and the detected weak ones read (median, least, largest)
+and their weights; and the position error (median, worst) of the SAME blocks three ways: from the strong satellites only, from all
+detected at unit weight, from all detected with these weights.
+
 --raim: "Coarse-time fix integrity" of include/gpsacq.h on false peaks.  After the search, in a share --fault-share of the blocks one
 satellite's ca_shift is replaced by a uniformly drawn sample of the code period (seeded), the observations are made once from those
 peaks (with --refine from the fine records, the planted peak keeping its whole-sample phase: a false peak has no fine record worth
@@ -82,11 +89,12 @@ def main():
     ap.add_argument("--aided", action="store_true", help="also search weak satellites around the prediction of the first fix")
     ap.add_argument("--aided-coh", action="store_true", help="also run the coherent aided search on the same tasks, navigation bits on")
     ap.add_argument("--weak-amplitude", type=float, default=None, help="amplitude of the two weak satellites of --aided (default 0.05; 0.03 with --aided-coh)")
+    ap.add_argument("--quality", action="store_true", help="also weight the observations of the aided scene by their C/N0 and fix once more")
     ap.add_argument("--raim", action="store_true", help="also plant false peaks and run the coarse-time fix with integrity on them")
     ap.add_argument("--fault-share", type=float, default=0.01, help="share of the blocks of --raim that get one false peak (0 .. 1)")
     ap.add_argument("--sigma-m", type=float, default=None, help="sigma_m of --raim (default 3.41 with --refine, 19.93 without)")
     a = ap.parse_args()
-    a.aided = a.aided or a.aided_coh
+    a.aided = a.aided or a.aided_coh or a.quality
     if a.weak_amplitude is None:
         a.weak_amplitude = 0.03 if a.aided_coh else 0.05
     a.refine = a.refine or a.cold or a.aided
@@ -141,6 +149,11 @@ def main():
             d_aided, d_peaks_a = zeros(n_tasks * gpsacq.AIDED_DTYPE.itemsize), zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize)
             d_fix_a, d_info_a = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
             aided_best = [float("inf")] * 2
+        if a.quality:
+            d_fine_q, d_qinfo = zeros(n_tasks * gpsacq.FINE_DTYPE.itemsize), zeros(n_tasks * gpsacq.QUALITY_INFO_DTYPE.itemsize)
+            d_obs_q = zeros(n_tasks * gpsacq.OBS_DTYPE.itemsize)
+            d_fix_q, d_info_q = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
+            snapq_best = float("inf")
         nav = None
         if a.aided_coh:
             cp = gpsacq.aided_coh_params()
@@ -180,6 +193,11 @@ def main():
                 aided_best = [min(x, y) for x, y in zip(aided_best, eng.aided_last_ms())]
                 eng.coarse_fix_fine_device(ephs, d_bits.data_ptr(), n_bytes, d_tasks.data_ptr(), d_peaks_a.data_ptr(), a.blocks, len(sats),
                                            d_prior.data_ptr(), d_fix_a.data_ptr(), d_info_a.data_ptr(), refine_params=rp_a, sync=True)
+            if a.quality:  # the merged peaks once more, the weights between the observations and the fix
+                eng.coarse_fix_quality_device(ephs, d_bits.data_ptr(), n_bytes, d_tasks.data_ptr(), d_peaks_a.data_ptr(), a.blocks, len(sats),
+                                              d_prior.data_ptr(), d_fix_q.data_ptr(), d_info_q.data_ptr(), d_fine_ptr=d_fine_q.data_ptr(),
+                                              d_obs_ptr=d_obs_q.data_ptr(), d_qinfo_ptr=d_qinfo.data_ptr(), refine_params=rp_a, sync=True)
+                snapq_best = min(snapq_best, eng.snap_quality_last_ms())
             if a.aided_coh:  # the receive instant on the device, from the same fine fixes
                 eng.aided_coh_peaks_device(ephs, d_fix_f.data_ptr(), d_bits.data_ptr(), n_bytes, d_tasks.data_ptr(), a.blocks, len(sats),
                                            d_coh.data_ptr(), d_peaks_c.data_ptr(), d_info_ptr=d_info_f.data_ptr(), d_prior_ptr=d_prior.data_ptr(),
@@ -238,6 +256,11 @@ def main():
             peaks_a = d_peaks_a.cpu().numpy().view(gpsacq.PEAK_DTYPE).reshape(a.blocks, len(sats))
             fix_a = d_fix_a.cpu().numpy().view(gpsacq.FIX_DTYPE)
             info_a = d_info_a.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
+        if a.quality:
+            qinfo = d_qinfo.cpu().numpy().view(gpsacq.QUALITY_INFO_DTYPE).reshape(a.blocks, len(sats))
+            obs_q = d_obs_q.cpu().numpy().view(gpsacq.OBS_DTYPE).reshape(a.blocks, len(sats))
+            fix_q = d_fix_q.cpu().numpy().view(gpsacq.FIX_DTYPE)
+            info_q = d_info_q.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
         if a.aided_coh:
             coh = d_coh.cpu().numpy().view(gpsacq.AIDED_COH_DTYPE).reshape(a.blocks, len(sats))
             peaks_c = d_peaks_c.cpu().numpy().view(gpsacq.PEAK_DTYPE).reshape(a.blocks, len(sats))
@@ -358,6 +381,29 @@ def main():
             "position_error_max_with_aided_m": round(float(off_a[ok_a].max()), 2) if ok_a.any() else None,
             "position_error_median_without_aided_same_blocks_m": round(float(np.median(off_f[ok_a])), 2) if ok_a.any() else None,
             "position_error_max_without_aided_same_blocks_m": round(float(off_f[ok_a].max()), 2) if ok_a.any() else None})
+    if a.quality:
+        ok_q = (fix_q["status"] == 0) & (info_q["flags"] == 0) & ok_a  # the same blocks three ways
+        off_q = np.linalg.norm(np.stack([fix_q["x"], fix_q["y"], fix_q["z"]], 1) - geo["rx"], axis=1)
+        used = obs_q["valid"] != 0
+        r2 = lambda v: round(float(v), 2)
+        r4 = lambda v: round(float(v), 4)
+        three = lambda v: {"median": r2(np.median(v)), "min": r2(v.min()), "max": r2(v.max())} if v.size else None
+        s_db, w_db = qinfo["cn0_dbhz"][:, :8][used[:, :8]], qinfo["cn0_dbhz"][:, weak][true_w]
+        extra["quality"] = {
+            "snap_quality_ms": r4(snapq_best), "snap_quality_over_refine": r4(snapq_best / refine_best), "shader_clock_read": False,
+            "cn0_min_dbhz": r2(10 * np.log10(float(gpsacq.snap_quality_params()["cn0_min_lin"][0]))),
+            "cn0_ref_dbhz": r2(10 * np.log10(float(gpsacq.snap_quality_params()["cn0_ref_lin"][0]))),
+            "cn0_strong_dbhz": three(s_db), "cn0_weak_dbhz": three(w_db),
+            "weight_strong": three(qinfo["weight"][:, :8][used[:, :8]]),
+            "weight_weak_median": r4(np.median(qinfo["weight"][:, weak][true_w])) if true_w.any() else None,
+            "weak_gated": int((found[:, weak] & (qinfo["weight"][:, weak] == 0)).sum()),
+            "quality_blocks_compared": int(ok_q.sum()),
+            "position_error_median_strong_only_m": r2(np.median(off_f[ok_q])) if ok_q.any() else None,
+            "position_error_max_strong_only_m": r2(off_f[ok_q].max()) if ok_q.any() else None,
+            "position_error_median_unit_weight_m": r2(np.median(off_a[ok_q])) if ok_q.any() else None,
+            "position_error_max_unit_weight_m": r2(off_a[ok_q].max()) if ok_q.any() else None,
+            "position_error_median_weighted_m": r2(np.median(off_q[ok_q])) if ok_q.any() else None,
+            "position_error_max_weighted_m": r2(off_q[ok_q].max()) if ok_q.any() else None}
     if a.aided_coh:
         c_searched = (coh["flags"] & (gpsacq.AIDED_KEPT | gpsacq.AIDED_NO_AID)) == 0
         c_found = c_searched & ((coh["flags"] & (gpsacq.AIDED_FEW | gpsacq.AIDED_NO_POWER | gpsacq.AIDED_BELOW)) == 0)
