@@ -1,5 +1,6 @@
 // capture_words.hpp -- the word loop of the kernels that go back to the 1-bit capture at a search peak, once: refine_kernels.hip
-// (k_refine), doppler_kernels.hip (k_fine_dop) and aided_kernels.hip (k_aided, at a predicted peak) include it, nothing else does.  A segment of the window is walked in the 32-sample
+// (k_refine), doppler_kernels.hip (k_fine_dop) and aided_kernels.hip (k_aided, at a predicted peak) include it; capture_groups.hpp, the
+// 8-bit IQ counterpart, builds on its chip sequence in LDS, mod_full, Window and code_window.  A segment of the window is walked in the 32-sample
 // words of the capture's 4-byte-aligned base; window_of() is steps 1 to 3 of the text (NCO words, no hit, segments); per word word_pos() reads the samples (the capture's last bytes one at a time, nothing
 // at or beyond n_bytes), masks the bits before and after the segment, carries the code position back to the word's bit 0 and cuts
 // the ONE 32-chip window that holds every chip of the word out of the chip sequence in LDS; word_masks() then builds the carrier
@@ -55,28 +56,66 @@ struct Window {
     uint64_t fit, segments;  // the segments of a whole window, and of this one
 };
 
+// step 1's Dopplers of a peak on the engine's grid: lo_dop, and ca_f = 1.023e6 + ca_dop, every operation rounded by itself
+__device__ __forceinline__ void peak_dopplers(const gpsacq_peak& pk, double fs, double step_hz, double& lo_dop, double& ca_f) {
+#pragma clang fp contract(off)  // the NCO words are the host's to the bit
+    const double L1 = 1575.42e6, CPS = 1.023e6;
+    lo_dop = step_hz > 0 ? pk.lo_shift * step_hz : pk.lo_shift * fs / 40000.0;
+    const double ca_dop = lo_dop / L1 * CPS;
+    ca_f = CPS + ca_dop;
+}
+
+// step 3 of a hit whose o, total and ca_rate are set: the start inside the capture, the segments of a whole window and of this one
+__device__ __forceinline__ void window_segments(Window& w, int spm, int blocks) {
+    w.hit = w.o < w.total && w.ca_rate != 0;
+    if (!w.hit) return;
+    const uint64_t have = (w.total - w.o) / (uint64_t)spm;
+    w.fit = (uint64_t)blocks * 40000ull / (uint64_t)spm;
+    w.segments = have < w.fit ? have : w.fit;
+}
+
 __device__ __forceinline__ Window window_of(const gpsacq_peak& pk, const gpsacq_task* tasks, size_t t, double fc, double fs, double step_hz, int spm,
                                             double snr_min, int blocks, size_t n_bytes, uint32_t lead, size_t stride) {
 #pragma clang fp contract(off)  // the NCO words are the host's to the bit
     Window w = {false, (int32_t)(t % 32), 0, 0, 0, (uint64_t)n_bytes * 8, 0, 0};
     int32_t block = (int32_t)t;
     if (tasks) block = tasks[t].block, w.prn = tasks[t].prn;
-    const double L1 = 1575.42e6, CPS = 1.023e6;
-    const double lo_dop = step_hz > 0 ? pk.lo_shift * step_hz : pk.lo_shift * fs / 40000.0;
-    const double ca_dop = lo_dop / L1 * CPS;
-    const double lo_f = fc + lo_dop, ca_f = CPS + ca_dop;
+    double lo_dop, ca_f;
+    peak_dopplers(pk, fs, step_hz, lo_dop, ca_f);
+    const double lo_f = fc + lo_dop;
     w.hit = (double)pk.snr >= snr_min && pk.ca_shift >= 0 && pk.ca_shift < spm && block >= 0 && w.prn >= 0 && w.prn < GPSACQ_NUM_SATS && lo_f >= 0 &&
             lo_f < fs && ca_f >= 0 && ca_f < fs;
     if (!w.hit) return w;
     w.o = 8ull * lead + 8ull * (uint64_t)block * stride;  // stride <= 2^31: no overflow
     w.lo_rate = (uint32_t)(lo_f / fs * 4294967296.0);
     w.ca_rate = (uint32_t)(ca_f / fs * 4294967296.0);
-    w.hit = w.o < w.total && w.ca_rate != 0;
-    if (!w.hit) return w;
-    const uint64_t have = (w.total - w.o) / (uint64_t)spm;
-    w.fit = (uint64_t)blocks * 40000ull / (uint64_t)spm;
-    w.segments = have < w.fit ? have : w.fit;
+    window_segments(w, spm, blocks);
     return w;
+}
+
+// the code side of one unit of a segment (a 32-sample word here, a 16-byte group of capture_groups.hpp): the ONE 32-chip window that
+// holds every chip of the unit, and the prompt position of the unit's sample 0 relative to it
+struct CodeWindow {
+    uint32_t win;  // 32 chips from late's chip at sample 0
+    uint64_t rel;  // the prompt position of sample 0 relative to the window's first chip, chips * 2^32
+};
+
+// j: the window sample index of the unit's first sample that belongs to the segment (j >= 0, j ca_rate < 2^54), which is the
+// unit's sample b_lo; P0: the prompt position of window sample 0; D: early's and late's distance from prompt (0: prompt only)
+__device__ __forceinline__ CodeWindow code_window(uint64_t j, uint32_t b_lo, uint64_t P0, uint32_t D, uint32_t ca_rate, const uint32_t* s_chips) {
+    // the prompt position of sample b_lo, carried back to sample 0 of the unit modulo the period: samples below b_lo are masked
+    // out, the ones from b_lo on get their own position
+    uint64_t P = mod_full(P0 + j * ca_rate);
+    const uint64_t back = (uint64_t)b_lo * ca_rate;  // < 2^37 < FULL
+    P = P >= back ? P - back : P + FULL - back;
+    // the window of 32 chips from late's chip at sample 0, and the prompt position relative to it: rel - D >= 0 and
+    // rel + D + 31 ca_rate < 32 * 2^32, so every chip index is the high word of a sum that does not wrap
+    const uint64_t L0 = P >= D ? P - D : P + FULL - D;
+    const uint32_t cb = (uint32_t)(L0 >> 32);  // 0 .. 1022
+    CodeWindow c;
+    c.win = __funnelshift_r(s_chips[cb >> 5], s_chips[(cb >> 5) + 1], cb & 31);
+    c.rel = (uint64_t)(uint32_t)L0 + D;
+    return c;
 }
 
 // one word of a segment
@@ -98,18 +137,10 @@ __device__ __forceinline__ WordPos word_pos(const uint32_t* words, size_t n_byte
     const uint32_t b_lo = ws < a0 ? (uint32_t)(a0 - ws) : 0u;        // 0 .. 31
     const uint32_t b_hi = ws + 32 > a1 ? (uint32_t)(a1 - ws) : 32u;  // 1 .. 32
     w.valid = (b_hi == 32 ? ~0u : (1u << b_hi) - 1u) & ~((1u << b_lo) - 1u);
-    // the prompt position of the word's first sample of the segment (window sample j >= 0, j ca_rate < 2^54), carried back
-    // to bit 0 of the word modulo the period: bits below b_lo are masked out, the ones from b_lo on get their own position
-    uint64_t P = mod_full(P0 + (ws + b_lo - o) * ca_rate);
-    const uint64_t back = (uint64_t)b_lo * ca_rate;  // < 2^37 < FULL
-    P = P >= back ? P - back : P + FULL - back;
     w.ph = (uint32_t)(ws - o) * lo_rate;  // modulo 2^32 also where the word starts before the window
-    // the window of 32 chips from late's chip at bit 0, and the prompt position relative to it: rel - D >= 0 and
-    // rel + D + 31 ca_rate < 32 * 2^32, so every chip index is the high word of a sum that does not wrap
-    const uint64_t L0 = P >= D ? P - D : P + FULL - D;
-    const uint32_t cb = (uint32_t)(L0 >> 32);  // 0 .. 1022
-    w.win = __funnelshift_r(s_chips[cb >> 5], s_chips[(cb >> 5) + 1], cb & 31);
-    w.rel = (uint64_t)(uint32_t)L0 + D;
+    const CodeWindow c = code_window(ws + b_lo - o, b_lo, P0, D, ca_rate, s_chips);
+    w.win = c.win;
+    w.rel = c.rel;
     return w;
 }
 
@@ -134,6 +165,16 @@ __device__ __forceinline__ void word_masks(const WordPos& w, uint32_t D, uint32_
         ph += lo_rate;
         rel += ca_rate;
     }
+}
+
+// the sum of v over the wave, in every lane: xor shuffles of the two halves, added modulo 2^64
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
+        v += (uint64_t)hi << 32 | lo;
+    }
+    return v;
 }
 
 }  // namespace acq

@@ -33,15 +33,6 @@ constexpr int DOPFINE_UNUSABLE = GPSACQ_DOPFINE_NO_HIT | GPSACQ_DOPFINE_NO_POWER
 constexpr double L1_HZ = 1575.42e6;
 constexpr double EARTH_R = 6371000.0;  // the sphere the solver starts on, metres
 
-// the sum of v over the wave, in every lane: xor shuffles of the two halves, added modulo 2^64
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-        v += (uint64_t)hi << 32 | lo;
-    }
-    return v;
-}
 }  // namespace
 
 __global__ __launch_bounds__(64 * DOP_WAVES) void k_fine_dop(FineDopArgs a) {

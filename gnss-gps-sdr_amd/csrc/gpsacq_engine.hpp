@@ -226,6 +226,9 @@ struct gpsacq_engine {
     Scratch<gpsacq_doppler_fix> d_dop_fix;     // host-buffer form
     Scratch<gpsacq_coarse_prior> d_dop_prior;  // host-buffer form, and the chain's priors where the caller wants none
     Stages<2> dop_fine_t, dop_obs_t, dop_fix_t;  // around k_fine_dop, k_rate_obs_fine, k_doppler_fix
+    // snapshot chain on an 8-bit IQ capture (gpsacq_refine_iq8*, gpsacq_fine_doppler_iq8*, the two *_iq8_device chains): the capture
+    // of the host-buffer forms goes into d_iq, sign mode's 1-bit stream into d_iqbits, tasks, peaks and records as the 1-bit forms'
+    Stages<2> snapiq_conv_t, snapiq_refine_t, snapiq_dop_t;  // around the conversion, the fine-record kernel, the fine-Doppler kernel
     // aided acquisition (gpsacq_aid_predict*, gpsacq_aided_search*, gpsacq_aided_peaks_device); the host-buffer forms stage fixes and
     // velocities in d_nav_fix / d_vel and the capture, tasks and input peaks in the d_refine_* buffers above
     Scratch<gpsacq_aid> d_aid;  // host-buffer forms, and k_aid_predict's output where the caller of the chain wants no records

@@ -12,7 +12,8 @@
 // all "Fine code phases": gpsacq_refine*, gpsacq_coarse_obs_fine* and gpsacq_coarse_fix_fine_device, which run refine_kernels.hip, and
 // "Snapshot signal quality": gpsacq_snap_quality* and gpsacq_coarse_fix_quality_device, which run snapq_kernels.hip, and
 // "Cold snapshot fixes": gpsacq_fine_doppler*, gpsacq_rate_obs_fine*, gpsacq_doppler_fix_batch* and gpsacq_cold_fix_device, which run
-// doppler_kernels.hip, and "Aided acquisition": gpsacq_aid_predict*, gpsacq_aided_search* and gpsacq_aided_peaks_device, which run
+// doppler_kernels.hip, and "Snapshot chain on an 8-bit IQ capture": gpsacq_refine_iq8*, gpsacq_fine_doppler_iq8* and the two *_iq8_device
+// chains, which run snapshot_iq_kernels.hip (sign mode: the conversion, then the 1-bit kernels), and "Aided acquisition": gpsacq_aid_predict*, gpsacq_aided_search* and gpsacq_aided_peaks_device, which run
 // aided_kernels.hip.
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
@@ -32,6 +33,7 @@
 #include "aided_launch.hpp"
 #include "smooth_launch.hpp"
 #include "snapq_launch.hpp"
+#include "snapshot_iq_launch.hpp"
 
 using namespace acq;
 
@@ -1297,17 +1299,22 @@ static int refine_params(const char* who, const gpsacq_refine_params* params, gp
     return GPSACQ_OK;
 }
 
+// the engines the kernels that go back to the capture serve
+static int capture_engine_check(const char* who, const gpsacq_engine* e) {
+    if (e->nlags > 65535) return fail(GPSACQ_ERR_UNSUPPORTED, "%s: %d samples per millisecond (the packed counts hold 65535)", who, e->nlags);
+    if (1.023e6 / e->p.fs + 1.0 / 1540.0 > REFINE_MAX_CHIPS_PER_SAMPLE)
+        return fail(GPSACQ_ERR_UNSUPPORTED, "%s: fs = %g Hz is fewer than %.2f samples per chip (a word's chips leave the kernel's window)", who, e->p.fs,
+                    1.0 / REFINE_MAX_CHIPS_PER_SAMPLE);
+    return GPSACQ_OK;
+}
+
 // the capture, the peaks, the output and the engine of a kernel that goes back to the capture (k_refine, k_fine_dop)
 static int capture_check(const char* who, const gpsacq_engine* e, const void* bits, size_t n_bytes, size_t stride, const void* peaks, size_t n_tasks,
                          const void* out) {
     if (!e || !bits || !peaks || !out || n_bytes == 0 || n_tasks == 0 || n_tasks > 0x7fffffffu) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
     if (stride < 5000 || stride > ((size_t)1 << 31)) return fail(GPSACQ_ERR_ARG, "%s: stride %zu outside 5000 .. 2^31", who, stride);
     if (n_bytes > ((size_t)1 << 56)) return fail(GPSACQ_ERR_ARG, "%s: n_bytes %zu", who, n_bytes);
-    if (e->nlags > 65535) return fail(GPSACQ_ERR_UNSUPPORTED, "%s: %d samples per millisecond (the packed counts hold 65535)", who, e->nlags);
-    if (1.023e6 / e->p.fs + 1.0 / 1540.0 > REFINE_MAX_CHIPS_PER_SAMPLE)
-        return fail(GPSACQ_ERR_UNSUPPORTED, "%s: fs = %g Hz is fewer than %.2f samples per chip (a word's chips leave the kernel's window)", who, e->p.fs,
-                    1.0 / REFINE_MAX_CHIPS_PER_SAMPLE);
-    return GPSACQ_OK;
+    return capture_engine_check(who, e);
 }
 
 static int refine_check(const char* who, const gpsacq_engine* e, const void* bits, size_t n_bytes, size_t stride, const void* peaks, size_t n_tasks,
@@ -1768,6 +1775,271 @@ extern "C" int gpsacq_doppler_last_ms(const gpsacq_engine* e, float* fine_dop_ms
     if (int rc = stage_ms(e->dop_fine_t, fine_dop_ms)) return rc;
     if (int rc = stage_ms(e->dop_obs_t, rate_obs_ms)) return rc;
     return stage_ms(e->dop_fix_t, doppler_fix_ms);
+}
+
+// ---- snapshot chain on an 8-bit IQ capture (snapshot_iq_kernels.hip; sign mode: iq_kernels.hip, then the 1-bit kernels) ----------
+namespace {
+// a checked capture of this section and how its kernels reach it
+struct IqSnap {
+    bool sign = false;          // GPSACQ_SAMPLES_SIGN: the 1-bit kernels on the converted capture
+    Capture cap;                // the conversion of sign mode
+    const uint8_t* d_iq = nullptr;  // device
+    size_t n_samples = 0, stride = 0;
+    double mix_hz = 0.0, fc_lo = 0.0;  // multi-bit: f = lo_dop - mix_hz + fc_lo
+    uint32_t flip = 0;
+    int32_t dc_i = 0, dc_q = 0;
+    const uint8_t* d_bits = nullptr;  // sign mode, after iq_snap_begin: the 1-bit stream in engine scratch
+    size_t n_bytes = 0;
+};
+}  // namespace
+
+// the arguments every form of this section shares; device: iq is a device pointer
+static int iq_snap_check(const char* who, const gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                         const void* peaks, size_t n_tasks, const void* out, bool device, IqSnap* s) {
+    if (!e || !in || !iq || !peaks || !out || n_samples == 0 || n_tasks == 0 || n_tasks > 0x7fffffffu) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (int rc = iq8_capture(e, in, device ? iq : nullptr, stride, &s->cap)) return rc;
+    if (stride % 16 != 0 || stride < 80000 || stride > ((size_t)1 << 31))
+        return fail(GPSACQ_ERR_ARG, "%s: stride %zu (a multiple of 16 in 80000 .. 2^31)", who, stride);
+    if (n_samples > ((size_t)1 << 55)) return fail(GPSACQ_ERR_ARG, "%s: n_samples %zu", who, n_samples);
+    if (device && ((uintptr_t)iq & 15)) return fail(GPSACQ_ERR_ARG, "%s: IQ buffer must be 16-byte aligned", who);
+    s->sign = in->multibit == GPSACQ_SAMPLES_SIGN;
+    s->d_iq = device ? (const uint8_t*)iq : nullptr;
+    s->n_samples = n_samples;
+    s->stride = stride;
+    if (!s->sign) {
+        s->mix_hz = in->mix_hz;
+        s->fc_lo = in->multibit == GPSACQ_SAMPLES_COMPLEX ? 0.0 : e->p.fc;
+        s->flip = in->format == GPSACQ_IQ_U8 ? 0x80808080u : 0u;
+        if (in->remove_dc) {
+            if (!(std::fabs(in->mean_i) <= 128.5) || !(std::fabs(in->mean_q) <= 128.5))
+                return fail(GPSACQ_ERR_ARG, "%s: mean (%g, %g) outside +-128", who, in->mean_i, in->mean_q);
+            s->dc_i = (int32_t)std::nearbyint(in->mean_i);
+            s->dc_q = (int32_t)std::nearbyint(in->mean_q);
+            if (std::abs(s->dc_i) > 128 || std::abs(s->dc_q) > 128) return fail(GPSACQ_ERR_ARG, "%s: mean (%g, %g) outside +-128", who, in->mean_i, in->mean_q);
+        }
+    }
+    return capture_engine_check(who, e);
+}
+
+// the host-buffer forms: the capture, the tasks and the peaks into engine scratch
+static int iq_snap_upload(gpsacq_engine* e, IqSnap& s, const void* iq, const gpsacq_task* tasks, const gpsacq_peak* peaks, size_t n_tasks) {
+    if (int rc = e->d_iq.grow(2 * s.n_samples + 16, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * s.n_samples, hipMemcpyHostToDevice, e->stream));
+    s.d_iq = s.cap.d_src = e->d_iq;
+    if (tasks)
+        if (int rc = upload(e, e->d_refine_tasks, tasks, n_tasks)) return rc;
+    return upload(e, e->d_refine_peaks, peaks, n_tasks);
+}
+
+// a call of this section begins: no timer has run; sign mode converts the capture once, timed, as gpsacq_track_iq8_device does
+static int iq_snap_begin(gpsacq_engine* e, IqSnap& s) {
+    e->snapiq_conv_t.done = e->snapiq_refine_t.done = e->snapiq_dop_t.done = false;
+    if (!s.sign) return GPSACQ_OK;
+    s.n_bytes = (s.n_samples + 7) / 8;
+    if (int rc = e->d_iqbits.grow(s.n_bytes, e->stream)) return rc;
+    const size_t left = s.cap.iq_total > s.cap.iq_first ? s.cap.iq_total - s.cap.iq_first : 0;  // samples of the capture from iq[0] on
+    if (int rc = e->snapiq_conv_t.begin(e->stream)) return rc;
+    if (left < s.n_samples) HIPCHK(hipMemsetAsync(e->d_iqbits, 0, s.n_bytes, e->stream));
+    if (int rc = iq8_to_bits_enqueue(e, s.d_iq, std::min(s.n_samples, left), s.cap.iq, s.cap.iq_first, e->d_iqbits)) return rc;
+    if (int rc = e->snapiq_conv_t.mark(1, e->stream)) return rc;
+    s.d_bits = e->d_iqbits;
+    return e->snapiq_conv_t.finish();
+}
+
+static void iq_capture_args(const gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_peaks, size_t n_tasks, IqCaptureArgs& c) {
+    const bool ref_grid = e->sub == 1 && e->dstride == 1;  // as gpsacq_handoff_engine
+    c.iq = s.d_iq;
+    c.n_samples = s.n_samples;
+    c.stride = s.stride;
+    c.tasks = (const gpsacq_task*)d_tasks;
+    c.peaks = (const gpsacq_peak*)d_peaks;
+    c.n_tasks = n_tasks;
+    c.chips = e->d_track_chips;
+    c.fs = e->p.fs;
+    c.step_hz = ref_grid ? 0.0 : e->p.fs / N_FFT * e->dstride / e->sub;
+    c.mix_hz = s.mix_hz, c.fc_lo = s.fc_lo;
+    c.spm = e->nlags;
+    c.flip = s.flip;
+    c.dc_i = s.dc_i, c.dc_q = s.dc_q;
+}
+
+// k_refine_iq, or k_refine on sign mode's stream, timed; every argument has been checked
+static int refine_iq_enqueue(gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_peaks, size_t n_tasks, const gpsacq_refine_params& rp,
+                             void* d_fine) {
+    if (int rc = ensure_track_chips(e)) return rc;
+    if (int rc = e->snapiq_refine_t.begin(e->stream)) return rc;
+    if (s.sign) {
+        RefineArgs a{};
+        capture_args(e, s.d_bits, s.n_bytes, s.stride / 16, d_tasks, d_peaks, n_tasks, a);
+        a.p = rp;
+        a.out = (gpsacq_fine*)d_fine;
+        launch_refine(a, e->stream);
+    } else {
+        RefineIqArgs a{};
+        iq_capture_args(e, s, d_tasks, d_peaks, n_tasks, a.c);
+        a.p = rp;
+        a.out = (gpsacq_fine*)d_fine;
+        launch_refine_iq(a, e->stream);
+    }
+    if (int rc = e->snapiq_refine_t.mark(1, e->stream)) return rc;
+    return e->snapiq_refine_t.finish();
+}
+
+// k_fine_dop_iq, or k_fine_dop on sign mode's stream, timed; every argument has been checked
+static int fine_dop_iq_enqueue(gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_peaks, size_t n_tasks,
+                               const gpsacq_dopfine_params& dp, void* d_dopfine) {
+    if (int rc = ensure_track_chips(e)) return rc;
+    if (int rc = e->snapiq_dop_t.begin(e->stream)) return rc;
+    if (s.sign) {
+        FineDopArgs a{};
+        capture_args(e, s.d_bits, s.n_bytes, s.stride / 16, d_tasks, d_peaks, n_tasks, a);
+        a.p = dp;
+        a.out = (gpsacq_dopfine*)d_dopfine;
+        launch_fine_dop(a, e->stream);
+    } else {
+        FineDopIqArgs a{};
+        iq_capture_args(e, s, d_tasks, d_peaks, n_tasks, a.c);
+        a.p = dp;
+        a.out = (gpsacq_dopfine*)d_dopfine;
+        launch_fine_dop_iq(a, e->stream);
+    }
+    if (int rc = e->snapiq_dop_t.mark(1, e->stream)) return rc;
+    return e->snapiq_dop_t.finish();
+}
+
+extern "C" int gpsacq_refine_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                        const void* d_tasks, const void* d_peaks, size_t n_tasks, const gpsacq_refine_params* params, void* d_fine,
+                                        int sync) {
+    IqSnap s;
+    gpsacq_refine_params rp;
+    if (int rc = iq_snap_check("gpsacq_refine_iq8", e, in, d_iq, n_samples, stride, d_peaks, n_tasks, d_fine, true, &s)) return rc;
+    if (int rc = refine_params("gpsacq_refine_iq8", params, &rp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = iq_snap_begin(e, s)) return rc;
+    if (int rc = refine_iq_enqueue(e, s, d_tasks, d_peaks, n_tasks, rp, d_fine)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_refine_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride, const gpsacq_task* tasks,
+                                 const gpsacq_peak* peaks, size_t n_tasks, const gpsacq_refine_params* params, gpsacq_fine* fine_out) {
+    IqSnap s;
+    gpsacq_refine_params rp;
+    if (int rc = iq_snap_check("gpsacq_refine_iq8", e, in, iq, n_samples, stride, peaks, n_tasks, fine_out, false, &s)) return rc;
+    if (int rc = refine_params("gpsacq_refine_iq8", params, &rp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = e->d_fine.grow(n_tasks, e->stream)) return rc;
+    if (int rc = iq_snap_upload(e, s, iq, tasks, peaks, n_tasks)) return rc;
+    if (int rc = iq_snap_begin(e, s)) return rc;
+    if (int rc = refine_iq_enqueue(e, s, tasks ? e->d_refine_tasks.p : nullptr, e->d_refine_peaks, n_tasks, rp, e->d_fine)) return rc;
+    if (int rc = download(e, fine_out, e->d_fine, n_tasks)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fine_doppler_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                              const void* d_tasks, const void* d_peaks, size_t n_tasks, const gpsacq_dopfine_params* params,
+                                              void* d_dopfine, int sync) {
+    IqSnap s;
+    gpsacq_dopfine_params dp;
+    if (int rc = iq_snap_check("gpsacq_fine_doppler_iq8", e, in, d_iq, n_samples, stride, d_peaks, n_tasks, d_dopfine, true, &s)) return rc;
+    if (int rc = dopfine_params("gpsacq_fine_doppler_iq8", e, params, &dp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = iq_snap_begin(e, s)) return rc;
+    if (int rc = fine_dop_iq_enqueue(e, s, d_tasks, d_peaks, n_tasks, dp, d_dopfine)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_fine_doppler_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                                       const gpsacq_task* tasks, const gpsacq_peak* peaks, size_t n_tasks, const gpsacq_dopfine_params* params,
+                                       gpsacq_dopfine* dopfine_out) {
+    IqSnap s;
+    gpsacq_dopfine_params dp;
+    if (int rc = iq_snap_check("gpsacq_fine_doppler_iq8", e, in, iq, n_samples, stride, peaks, n_tasks, dopfine_out, false, &s)) return rc;
+    if (int rc = dopfine_params("gpsacq_fine_doppler_iq8", e, params, &dp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = e->d_dopfine.grow(n_tasks, e->stream)) return rc;
+    if (int rc = iq_snap_upload(e, s, iq, tasks, peaks, n_tasks)) return rc;
+    if (int rc = iq_snap_begin(e, s)) return rc;
+    if (int rc = fine_dop_iq_enqueue(e, s, tasks ? e->d_refine_tasks.p : nullptr, e->d_refine_peaks, n_tasks, dp, e->d_dopfine)) return rc;
+    if (int rc = download(e, dopfine_out, e->d_dopfine, n_tasks)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_fix_fine_iq8_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_iq8_input* in, const void* d_iq,
+                                                 size_t n_samples, size_t stride, const void* d_tasks, const void* d_peaks, size_t n_fix, int n_chans,
+                                                 const gpsacq_refine_params* refine_par, const void* d_prior, const gpsacq_coarse_params* params,
+                                                 void* d_fine, void* d_obs, void* d_fix, void* d_info, void* d_obs_out, int sync) {
+    const char* who = "gpsacq_coarse_fix_fine_iq8";
+    if (int rc = coarse_obs_check(who, e, d_peaks, n_fix, n_chans, 0.0, d_fix)) return rc;
+    if (!eph || n_eph <= 0 || !d_prior || !d_info) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (d_obs && d_obs_out == d_obs) return fail(GPSACQ_ERR_ARG, "%s: obs_out must not be obs", who);
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    IqSnap s;
+    gpsacq_refine_params rp;
+    gpsacq_coarse_params cp;
+    if (int rc = iq_snap_check(who, e, in, d_iq, n_samples, stride, d_peaks, n_tasks, d_fix, true, &s)) return rc;
+    if (int rc = refine_params(who, refine_par, &rp)) return rc;
+    if (int rc = coarse_params(who, params, &cp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = or_own(e, d_fine, e->d_fine, n_tasks)) return rc;
+    if (int rc = or_own(e, d_obs, e->d_coarse_obs, n_tasks)) return rc;
+    if (int rc = iq_snap_begin(e, s)) return rc;
+    if (int rc = refine_iq_enqueue(e, s, d_tasks, d_peaks, n_tasks, rp, d_fine)) return rc;
+    if (int rc = coarse_obs_fine_enqueue(e, d_peaks, d_fine, n_fix, n_chans, rp.snr_min, d_obs)) return rc;
+    if (int rc = coarse_fix_enqueue(e, eph, n_eph, d_obs, d_prior, n_fix, n_chans, cp, d_fix, d_info, d_obs_out)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_cold_fix_iq8_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_iq8_input* in, const void* d_iq,
+                                          size_t n_samples, size_t stride, const void* d_tasks, const void* d_peaks, const void* d_rx_ms, size_t n_fix,
+                                          int n_chans, const gpsacq_dopfine_params* dopfine_par, const gpsacq_doppler_fix_params* doppler_par,
+                                          const gpsacq_refine_params* refine_par, const gpsacq_coarse_params* coarse_par, void* d_dopfine,
+                                          void* d_rate_obs, void* d_doppler_fix, void* d_prior, void* d_fine, void* d_obs, void* d_fix, void* d_info,
+                                          void* d_obs_out, int sync) {
+    const char* who = "gpsacq_cold_fix_iq8";
+    if (int rc = coarse_obs_check(who, e, d_peaks, n_fix, n_chans, 0.0, d_fix)) return rc;
+    if (!eph || n_eph <= 0 || !d_rx_ms || !d_info || !d_doppler_fix) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (d_obs && d_obs_out == d_obs) return fail(GPSACQ_ERR_ARG, "%s: obs_out must not be obs", who);
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    IqSnap s;
+    gpsacq_dopfine_params dp;
+    gpsacq_doppler_fix_params fp;
+    gpsacq_refine_params rp;
+    gpsacq_coarse_params cp;
+    if (int rc = iq_snap_check(who, e, in, d_iq, n_samples, stride, d_peaks, n_tasks, d_fix, true, &s)) return rc;
+    if (int rc = refine_params(who, refine_par, &rp)) return rc;
+    if (int rc = dopfine_params(who, e, dopfine_par, &dp)) return rc;
+    if (int rc = doppler_fix_params(who, doppler_par, &fp)) return rc;
+    if (int rc = coarse_params(who, coarse_par, &cp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = or_own(e, d_dopfine, e->d_dopfine, n_tasks)) return rc;
+    if (int rc = or_own(e, d_rate_obs, e->d_rate_obs, n_tasks)) return rc;
+    if (int rc = or_own(e, d_prior, e->d_dop_prior, n_fix)) return rc;
+    if (int rc = or_own(e, d_fine, e->d_fine, n_tasks)) return rc;
+    if (int rc = or_own(e, d_obs, e->d_coarse_obs, n_tasks)) return rc;
+    if (int rc = iq_snap_begin(e, s)) return rc;
+    if (int rc = fine_dop_iq_enqueue(e, s, d_tasks, d_peaks, n_tasks, dp, d_dopfine)) return rc;
+    if (int rc = coarse_obs_enqueue(e, d_peaks, n_fix, n_chans, dp.snr_min, d_obs)) return rc;
+    if (int rc = rate_obs_fine_enqueue(e, d_peaks, d_dopfine, n_fix, n_chans, dp.snr_min, d_rate_obs)) return rc;
+    if (int rc = doppler_fix_enqueue(e, eph, n_eph, d_obs, d_rate_obs, d_rx_ms, n_fix, n_chans, fp, d_doppler_fix, d_prior)) return rc;
+    if (int rc = refine_iq_enqueue(e, s, d_tasks, d_peaks, n_tasks, rp, d_fine)) return rc;
+    if (int rc = coarse_obs_fine_enqueue(e, d_peaks, d_fine, n_fix, n_chans, rp.snr_min, d_obs)) return rc;
+    if (int rc = coarse_fix_enqueue(e, eph, n_eph, d_obs, d_prior, n_fix, n_chans, cp, d_fix, d_info, d_obs_out)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_snapshot_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* refine_ms, float* fine_dop_ms) {
+    if (!e || (!e->snapiq_refine_t.ran() && !e->snapiq_dop_t.ran()))
+        return fail(GPSACQ_ERR_ARG, "gpsacq_snapshot_iq8_last_ms: no gpsacq_refine_iq8, gpsacq_fine_doppler_iq8 or *_iq8_device chain on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = stage_ms(e->snapiq_conv_t, convert_ms)) return rc;
+    if (int rc = stage_ms(e->snapiq_refine_t, refine_ms)) return rc;
+    return stage_ms(e->snapiq_dop_t, fine_dop_ms);
 }
 
 // ---- aided acquisition: predicted code phase and Doppler, windowed search (aided_kernels.hip) ------------------------------------

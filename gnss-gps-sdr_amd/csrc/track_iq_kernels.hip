@@ -8,24 +8,14 @@
 // samples of I_X = sum h (v_i C - v_q S), against (h S, h C, ...) two samples of Q_X = sum h (v_i S + v_q C).  Weights are +1, -1
 // or 0 (a sample outside the epoch).  GPSACQ_IQ_U8 bytes are XORed with 0x80 first (byte ^ 0x80 read as int8 = byte - 128); the
 // removed mean is a correction -dc * sum(weights) that costs two more dot products per dword and only when it is not zero.
+// load_group, dot4 and the weight bytes live in iq_groups.hpp, which the snapshot kernels on an IQ capture share.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "iq_groups.hpp"
 #include "track_channel.hpp"
 
 namespace acq {
-
-// group g of the window: 16 bytes, or what the window still holds of them (zeros beyond)
-__device__ __forceinline__ uint4 load_group(const uint8_t* iq, size_t n_bytes, uint64_t g) {
-    const size_t off = (size_t)g * 16;
-    if (off + 16 <= n_bytes) return *reinterpret_cast<const uint4*>(iq + off);
-    uint32_t v[4] = {0, 0, 0, 0};
-    for (int k = 0; k < 16; ++k)
-        if (off + k < n_bytes) v[k >> 2] |= (uint32_t)iq[off + k] << (8 * (k & 3));
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-
-__device__ __forceinline__ int dot4(uint32_t a, uint32_t b, int acc) { return __builtin_amdgcn_sdot4((int)a, (int)b, acc, false); }
 
 struct IqCorr {
     const uint8_t* iq;
@@ -56,9 +46,8 @@ struct IqCorr {
 #pragma unroll
                     for (int X = 0; X < 3; ++X) {
                         const uint32_t bc = chip[X] ^ nb.cb, bs = chip[X] ^ nb.sb;  // 1: h C = -1, h S = -1
-                        // bytes +1 (0x01) / -1 (0xFF): (h C, -h S) for the I arm, (h S, h C) for the Q arm
-                        const uint32_t pi = (0xFF01u + 0xFEu * bc - 0xFE00u * bs) & keep;
-                        const uint32_t pq = (0x0101u + 0xFEu * bs + 0xFE00u * bc) & keep;
+                        uint32_t pi, pq;  // bytes +1 (0x01) / -1 (0xFF): (h C, -h S) for the I arm, (h S, h C) for the Q arm
+                        weight_bytes(bc, bs, keep, pi, pq);
                         wi[X] |= pi << (16 * h);
                         wq[X] |= pq << (16 * h);
                     }

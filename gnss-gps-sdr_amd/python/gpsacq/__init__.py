@@ -205,6 +205,8 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_dopfine_default_params", "gpsacq_doppler_fix_default_params", "gpsacq_fine_doppler", "gpsacq_fine_doppler_device",
            "gpsacq_rate_obs_fine", "gpsacq_rate_obs_fine_device", "gpsacq_doppler_fix_batch", "gpsacq_doppler_fix_batch_device",
            "gpsacq_cold_fix_device", "gpsacq_doppler_last_ms",
+           "gpsacq_refine_iq8", "gpsacq_refine_iq8_device", "gpsacq_fine_doppler_iq8", "gpsacq_fine_doppler_iq8_device",
+           "gpsacq_coarse_fix_fine_iq8_device", "gpsacq_cold_fix_iq8_device", "gpsacq_snapshot_iq8_last_ms",
            "gpsacq_aid_default_params", "gpsacq_aided_default_params", "gpsacq_aid_predict", "gpsacq_aid_predict_device", "gpsacq_aided_search",
            "gpsacq_aided_search_device", "gpsacq_aided_peaks_device", "gpsacq_aided_last_ms",
            "gpsacq_aided_coh_default_params", "gpsacq_aided_coh_table", "gpsacq_aided_coh_search", "gpsacq_aided_coh_search_device",
@@ -532,6 +534,20 @@ def load_library(path=None):
     lib.gpsacq_doppler_fix_batch_device.restype = ctypes.c_int
     lib.gpsacq_cold_fix_device.argtypes = [vp, vp, ctypes.c_int, vp, sz, sz, vp, vp, vp, sz, ctypes.c_int] + [vp] * 13 + [ctypes.c_int]
     lib.gpsacq_cold_fix_device.restype = ctypes.c_int
+    lib.gpsacq_refine_iq8.argtypes = [vp, iqp, vp, sz, sz, vp, vp, sz, vp, vp]
+    lib.gpsacq_refine_iq8.restype = ctypes.c_int
+    lib.gpsacq_refine_iq8_device.argtypes = [vp, iqp, vp, sz, sz, vp, vp, sz, vp, vp, ctypes.c_int]
+    lib.gpsacq_refine_iq8_device.restype = ctypes.c_int
+    lib.gpsacq_fine_doppler_iq8.argtypes = [vp, iqp, vp, sz, sz, vp, vp, sz, vp, vp]
+    lib.gpsacq_fine_doppler_iq8.restype = ctypes.c_int
+    lib.gpsacq_fine_doppler_iq8_device.argtypes = [vp, iqp, vp, sz, sz, vp, vp, sz, vp, vp, ctypes.c_int]
+    lib.gpsacq_fine_doppler_iq8_device.restype = ctypes.c_int
+    lib.gpsacq_coarse_fix_fine_iq8_device.argtypes = [vp, vp, ctypes.c_int, iqp, vp, sz, sz, vp, vp, sz, ctypes.c_int] + [vp] * 8 + [ctypes.c_int]
+    lib.gpsacq_coarse_fix_fine_iq8_device.restype = ctypes.c_int
+    lib.gpsacq_cold_fix_iq8_device.argtypes = [vp, vp, ctypes.c_int, iqp, vp, sz, sz, vp, vp, vp, sz, ctypes.c_int] + [vp] * 13 + [ctypes.c_int]
+    lib.gpsacq_cold_fix_iq8_device.restype = ctypes.c_int
+    lib.gpsacq_snapshot_iq8_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
+    lib.gpsacq_snapshot_iq8_last_ms.restype = ctypes.c_int
     lib.gpsacq_doppler_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
     lib.gpsacq_doppler_last_ms.restype = ctypes.c_int
     lib.gpsacq_aid_default_params.argtypes = [vp]
@@ -1042,9 +1058,11 @@ class Engine:
             cells.ctypes.data_as(ctypes.c_void_p) if want_cells else None, peaks.ctypes.data_as(ctypes.c_void_p)))
         return cells, peaks
 
-    def search_iq8_device(self, d_iq_ptr, inp, n_blocks, d_peaks_ptr, stride=16 * BLOCK_BYTES, sync=True):
-        _check(self._lib, self._lib.gpsacq_search_iq8_device(self._h, ctypes.byref(inp), d_iq_ptr, n_blocks, stride, None, n_blocks,
-                                                             None, d_peaks_ptr, 1 if sync else 0))
+    def search_iq8_device(self, d_iq_ptr, inp, n_blocks, d_peaks_ptr, stride=16 * BLOCK_BYTES, sync=True, d_tasks_ptr=None, n_tasks=None):
+        """gpsacq_search_iq8_device: the capture (device, 16-byte aligned) searched on the reference schedule, or on a task list in
+        device memory (d_tasks_ptr, n_tasks)."""
+        _check(self._lib, self._lib.gpsacq_search_iq8_device(self._h, ctypes.byref(inp), d_iq_ptr, n_blocks, stride, d_tasks_ptr,
+                                                             n_blocks if n_tasks is None else int(n_tasks), None, d_peaks_ptr, 1 if sync else 0))
 
     # ---- pipelined host-buffer searches (gpsacq_pipe_*) --------------------------------------
     def pipe_buffer(self, slot, nbytes):
@@ -1650,6 +1668,93 @@ class Engine:
         """Device milliseconds of the last cold-fix calls: (k_fine_dop or 0, k_rate_obs_fine or 0, k_doppler_fix or 0)."""
         t = [ctypes.c_float() for _ in range(3)]
         _check(self._lib, self._lib.gpsacq_doppler_last_ms(self._h, *[ctypes.byref(x) for x in t]))
+        return tuple(x.value for x in t)
+
+    # ---- snapshot chain on an 8-bit IQ capture ------------------------------------------------
+    @staticmethod
+    def _iq8_peaks_tasks(iq, peaks, tasks):
+        buf = np.ascontiguousarray(np.asarray(iq).view(np.uint8).ravel())
+        if not isinstance(peaks, np.ndarray) or peaks.dtype != PEAK_DTYPE:
+            raise TypeError("peaks must be a PEAK_DTYPE array")
+        pk = np.ascontiguousarray(peaks)
+        t = None
+        if tasks is not None:
+            t = np.ascontiguousarray(np.asarray(tasks, dtype=np.int32).reshape(-1, 2))
+            if t.shape[0] != pk.size:
+                raise ValueError("one task per peak")
+        return buf, pk, t
+
+    def refine_iq8(self, iq, inp, peaks, tasks=None, stride=16 * BLOCK_BYTES, params=None, n_samples=None):
+        """gpsacq_refine_iq8: refine() on interleaved 8-bit I, Q bytes, for the peaks of search_iq8() with the same inp
+        (Engine.iq8_input(...)): multi-bit complex sums where inp.multibit != 0, the 1-bit path on the converted capture in sign
+        mode.  stride in BYTES (a multiple of 16, >= 80000); n_samples: the capture's length (None: all of iq).  Returns
+        FINE_DTYPE records in the shape of peaks."""
+        buf, pk, t = self._iq8_peaks_tasks(iq, peaks, tasks)
+        n = buf.size // 2 if n_samples is None else int(n_samples)
+        rr, rp = self._refine_params(params)
+        out = np.zeros(pk.shape, dtype=FINE_DTYPE)
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_refine_iq8(self._h, ctypes.byref(inp), p(buf), n, int(stride), p(t), p(pk), int(pk.size), rp, p(out)))
+        return out
+
+    def refine_iq8_device(self, inp, d_iq_ptr, n_samples, d_peaks_ptr, n_tasks, d_fine_ptr, stride=16 * BLOCK_BYTES, d_tasks_ptr=None, params=None,
+                          sync=True):
+        """gpsacq_refine_iq8_device: device pointers for the capture (16-byte aligned), the peaks, the tasks (None: the reference
+        schedule) and the records."""
+        rr, rp = self._refine_params(params)
+        _check(self._lib, self._lib.gpsacq_refine_iq8_device(self._h, ctypes.byref(inp), d_iq_ptr, int(n_samples), int(stride), d_tasks_ptr, d_peaks_ptr,
+                                                             int(n_tasks), rp, d_fine_ptr, 1 if sync else 0))
+
+    def fine_doppler_iq8(self, iq, inp, peaks, tasks=None, stride=16 * BLOCK_BYTES, params=None, n_samples=None):
+        """gpsacq_fine_doppler_iq8: fine_doppler() on interleaved 8-bit I, Q bytes, as refine_iq8().  Returns DOPFINE_DTYPE records
+        in the shape of peaks; doppler_hz is in the search's own sense."""
+        buf, pk, t = self._iq8_peaks_tasks(iq, peaks, tasks)
+        n = buf.size // 2 if n_samples is None else int(n_samples)
+        dr, dp = self._record(params, DOPFINE_PARAMS_DTYPE)
+        out = np.zeros(pk.shape, dtype=DOPFINE_DTYPE)
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_fine_doppler_iq8(self._h, ctypes.byref(inp), p(buf), n, int(stride), p(t), p(pk), int(pk.size), dp, p(out)))
+        return out
+
+    def fine_doppler_iq8_device(self, inp, d_iq_ptr, n_samples, d_peaks_ptr, n_tasks, d_dopfine_ptr, stride=16 * BLOCK_BYTES, d_tasks_ptr=None,
+                                params=None, sync=True):
+        """gpsacq_fine_doppler_iq8_device: device pointers, as refine_iq8_device()."""
+        dr, dp = self._record(params, DOPFINE_PARAMS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_fine_doppler_iq8_device(self._h, ctypes.byref(inp), d_iq_ptr, int(n_samples), int(stride), d_tasks_ptr,
+                                                                   d_peaks_ptr, int(n_tasks), dp, d_dopfine_ptr, 1 if sync else 0))
+
+    def coarse_fix_fine_iq8_device(self, eph, inp, d_iq_ptr, n_samples, d_tasks_ptr, d_peaks_ptr, n_fix, n_chans, d_prior_ptr, d_fix_ptr, d_info_ptr,
+                                   d_fine_ptr=None, d_obs_ptr=None, d_obs_out_ptr=None, stride=16 * BLOCK_BYTES, refine_params=None, params=None,
+                                   sync=True):
+        """gpsacq_coarse_fix_fine_iq8_device: coarse_fix_fine_device() on an 8-bit IQ capture."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        rr, rp = self._refine_params(refine_params)
+        cr, cp = self._coarse_params(params)
+        _check(self._lib, self._lib.gpsacq_coarse_fix_fine_iq8_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), ctypes.byref(inp),
+                                                                      d_iq_ptr, int(n_samples), int(stride), d_tasks_ptr, d_peaks_ptr, int(n_fix),
+                                                                      int(n_chans), rp, d_prior_ptr, cp, d_fine_ptr, d_obs_ptr, d_fix_ptr, d_info_ptr,
+                                                                      d_obs_out_ptr, 1 if sync else 0))
+
+    def cold_fix_iq8_device(self, eph, inp, d_iq_ptr, n_samples, d_tasks_ptr, d_peaks_ptr, d_rx_ms_ptr, n_fix, n_chans, d_fix_ptr, d_info_ptr,
+                            d_doppler_fix_ptr, d_dopfine_ptr=None, d_rate_obs_ptr=None, d_prior_ptr=None, d_fine_ptr=None, d_obs_ptr=None,
+                            d_obs_out_ptr=None, stride=16 * BLOCK_BYTES, dopfine_params=None, doppler_params=None, refine_params=None, params=None,
+                            sync=True):
+        """gpsacq_cold_fix_iq8_device: cold_fix_device() on an 8-bit IQ capture."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        dr, dp = self._record(dopfine_params, DOPFINE_PARAMS_DTYPE)
+        fr, fp = self._record(doppler_params, DOPPLER_FIX_PARAMS_DTYPE)
+        rr, rp = self._refine_params(refine_params)
+        cr, cp = self._coarse_params(params)
+        _check(self._lib, self._lib.gpsacq_cold_fix_iq8_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), ctypes.byref(inp), d_iq_ptr,
+                                                               int(n_samples), int(stride), d_tasks_ptr, d_peaks_ptr, d_rx_ms_ptr, int(n_fix),
+                                                               int(n_chans), dp, fp, rp, cp, d_dopfine_ptr, d_rate_obs_ptr, d_doppler_fix_ptr,
+                                                               d_prior_ptr, d_fine_ptr, d_obs_ptr, d_fix_ptr, d_info_ptr, d_obs_out_ptr,
+                                                               1 if sync else 0))
+
+    def snapshot_iq8_last_ms(self):
+        """Device milliseconds of the last *_iq8 snapshot call: (conversion or 0, fine-record kernel or 0, fine-Doppler kernel or 0)."""
+        t = [ctypes.c_float() for _ in range(3)]
+        _check(self._lib, self._lib.gpsacq_snapshot_iq8_last_ms(self._h, *[ctypes.byref(x) for x in t]))
         return tuple(x.value for x in t)
 
     # ---- aided acquisition ------------------------------------------------------------------

@@ -1681,11 +1681,12 @@ GPSACQ_API int gpsacq_coarse_raim_last_ms(const gpsacq_engine* e, float* fix_ms,
  * Doppler half a bin off (68 Hz at 5.456 MHz) moves it by at most 0.044 chips/s * T / 2, which is 0.75 m at 16 blocks.  The
  * triangle is linear only for |offset| <= d, and a 1-bit front end rounds its corners.  The segments are added non-coherently, so
  * data-bit flips and the half-bin carrier error cost little.  Subtracting the analytic noise floor from the three powers did not
- * help consistently in simulation and is left out.  For the peaks of plain 1-bit searches only.
+ * help consistently in simulation and is left out.  For the peaks of plain 1-bit searches; those of gpsacq_search_iq8 go through
+ * "Snapshot chain on an 8-bit IQ capture" below.
  *
  * OUT OF SCOPE.  Accumulated or re-aligned searches (gpsacq_set_noncoherent, creep compensation, block alignment), fs above
- * 10 MHz where ca_shift refers to block 0 of several passes, 8-bit IQ input, multi-GPU, gps_test and gps_track.  The correlator
- * and gpsacq_peak do not change.
+ * 10 MHz where ca_shift refers to block 0 of several passes, multi-GPU, gps_test and gps_track.  The correlator and gpsacq_peak
+ * do not change.  (8-bit IQ captures: "Snapshot chain on an 8-bit IQ capture" below.)
  */
 #define GPSACQ_FINE_NO_HIT 1     /* the peak is no hit, or its task or NCO words are out of range: the record is this flag and zeros */
 #define GPSACQ_FINE_SHORT 2      /* the capture ends before the window does */
@@ -1769,7 +1770,8 @@ GPSACQ_API int gpsacq_refine_last_ms(const gpsacq_engine* e, float* refine_ms, f
  * variance ratio 1 .. 0.05, weight 1 .. 0.024), and make no claim below cn0_min_lin.
  *
  * OUT OF SCOPE.  Whole-sample observations without a fine record, a measured noise floor, per-observation sigmas in
- * gpsacq_raim_params, gps_test and gps_track, 8-bit IQ.
+ * gpsacq_raim_params, gps_test and gps_track.  The records of a multi-bit gpsacq_refine_iq8 ("Snapshot chain on an 8-bit IQ capture"
+ * below): the analytic floor of step 2 is that of a +-1 stream, and their prompt power scales with the capture's amplitude.
  *
  * gpsacq_snap_quality: host pointers, returns after completion; obs in-out and may be NULL.  gpsacq_snap_quality_device: fine, obs
  * (may be NULL) and info are device pointers, params stays a host pointer; work on the engine's stream, sync != 0 waits.  The two
@@ -1920,8 +1922,9 @@ GPSACQ_API int gpsacq_snap_quality_last_ms(const gpsacq_engine* e, float* ms);
  *
  * OUT OF SCOPE.  Coherent sums longer than one code period and signals below about 38 dB-Hz (for satellites found from a first fix:
  * "Coherent aided acquisition" further down).  Doppler rate over the window.  A
- * height constraint for five-satellite rows.  Solving the time error from the Dopplers.  Fusing k_fine_dop into k_refine.  8-bit
- * IQ input, accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.
+ * height constraint for five-satellite rows.  Solving the time error from the Dopplers.  Fusing k_fine_dop into k_refine.
+ * Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.  (8-bit IQ captures: "Snapshot chain on an 8-bit IQ
+ * capture" below.)
  */
 #define GPSACQ_DOPFINE_NO_HIT 1     /* the peak is no hit, or its task or NCO words are out of range: the record is this flag and zeros */
 #define GPSACQ_DOPFINE_SHORT 2      /* the capture ends before the window does */
@@ -1959,6 +1962,108 @@ GPSACQ_API int gpsacq_cold_fix_device(gpsacq_engine* e, const gpsacq_ephemeris* 
 /* device time of k_fine_dop, k_rate_obs_fine and k_doppler_fix as last run on this engine, milliseconds (HIP events on its
  * stream; waits for them); a kernel that has not run reads 0.  Any pointer may be NULL. */
 GPSACQ_API int gpsacq_doppler_last_ms(const gpsacq_engine* e, float* fine_dop_ms, float* rate_obs_ms, float* doppler_fix_ms);
+
+/*
+ * ---- Snapshot chain on an 8-bit IQ capture: multi-bit fine code phase and fine Doppler -------------------------------------------
+ *
+ * gpsacq_search_iq8 searches an rtl-sdr / HackRF file as it is and gpsacq_track_iq8 tracks it, but gpsacq_refine and
+ * gpsacq_fine_doppler read a 1-bit real-IF stream: a snapshot fix from an 8-bit IQ file had to go through gpsacq_iq8_to_bits first,
+ * which throws one arm away (3 dB) and puts the other through a limiter (about 2 dB), in the one chain whose point is to work with
+ * little signal.  gpsacq_refine_iq8 and gpsacq_fine_doppler_iq8 go back to the IQ bytes themselves.  The records are gpsacq_fine and
+ * gpsacq_dopfine as they are, and everything downstream takes them unchanged: gpsacq_coarse_obs_fine*, gpsacq_rate_obs_fine*,
+ * gpsacq_doppler_fix_batch*, gpsacq_coarse_fix_batch*, gpsacq_coarse_raim_batch*, gpsacq_vel_batch*.  THE MODEL; the kernels
+ * (csrc/snapshot_iq_kernels.hip) and the references of the tests (tests/refine_iq_ref.py, tests/dop_iq_ref.py) are both written
+ * from this text.  "Step n" is step n of "Fine code phases", PER TASK.
+ *
+ * INPUTS.  A gpsacq_iq8_input `in`, as for gpsacq_search_iq8.  iq[2 * n_samples]: interleaved I, Q bytes, sample m in bytes 2 m and
+ * 2 m + 1; the device form takes a 16-byte-aligned device pointer.  stride: BYTES between blocks with gpsacq_search_iq8's bounds, a
+ * multiple of 16, 80000 <= stride <= 2^31.  tasks[n_tasks], or NULL for the reference schedule, and peaks[n_tasks] as returned by
+ * gpsacq_search_iq8 with the same `in`.  gpsacq_refine_params / gpsacq_dopfine_params as they are.
+ *
+ * in->multibit != 0 (GPSACQ_SAMPLES_REAL and GPSACQ_SAMPLES_COMPLEX alike): THE MULTI-BIT PATH.
+ *   SAMPLE.  v_i, v_q are exactly the sample of "Tracking channels on an 8-bit IQ capture": v_i = I - off - dc_i, v_q = Q - off - dc_q,
+ *     off = 128 for GPSACQ_IQ_U8 and 0 for GPSACQ_IQ_S8, dc = nearbyint(mean) (ties to even) when remove_dc, else 0; |v| <= 256.  No
+ *     floating-point mixer: mix_hz goes into the carrier word.  in->fs, first_sample and total_samples are not read.
+ *   NCO WORDS.  lo_dop, ca_dop and ca_rate are step 1's.  The carrier word is gpsacq_track_start_iq8's, where the satellite sits in
+ *     the raw capture:
+ *         f = lo_dop - mix_hz + fc      (GPSACQ_SAMPLES_COMPLEX: f = lo_dop - mix_hz), left to right,
+ *         lo_rate = (uint32)(int64)llround(f / fs * 2^32)                 (round half away from zero; two's complement for f < 0)
+ *   NOT A HIT is step 2 with `|f| >= fs / 2` (or f not a number) in place of the test of fc + lo_dop in [0, fs), and with o and the
+ *     capture's length as below.
+ *   WINDOW.  o = block * (stride / 2), the first sample of the block, against n_samples: a block at or beyond sample n_samples is no
+ *     hit.  Segments, GPSACQ_FINE_SHORT and GPSACQ_FINE_FEW are step 3 word for word with n_samples for 8 n_bytes.  Nothing at or
+ *     beyond byte 2 * n_samples is read.
+ *   SUMS.  Chips at (P0 + j ca_rate -+ D) mod FULL and the carrier phase j lo_rate (mod 2^32) as in step 4; with C = 1 - 2 (cos bit),
+ *     S = 1 - 2 (sin bit) and h_X = 1 - 2 chip_X, per segment the six sums of the multi-bit channel model,
+ *         I_X = sum h_X (v_i C - v_q S),   Q_X = sum h_X (v_i S + v_q C),   X in E, P, L,
+ *     and early = sum over the segments of I_E^2 + Q_E^2, prompt and late likewise, as uint64.  |I_X|, |Q_X| <= 512 spm < 2^25 (spm
+ *     <= 65535), a segment adds less than 2^51 and there are fewer than 2^12 segments (64 * 40000 / 1137 = 2251): nothing overflows.
+ *   ESTIMATE, FLAGS, USABLE.  Steps 5 and 6 unchanged.
+ *   FINE DOPPLER (gpsacq_fine_doppler_iq8).  The prompt sums I_s = I_P, Q_s = Q_P of the segments go into the lag-1 law of "Cold
+ *     snapshot fixes" with gpsacq_dopfine_params' blocks, min_segments and snr_min.  Its OVERFLOW bound (a term at most 4 spm^4) does
+ *     not hold for 25-bit sums, so they are normalised first, exactly and in integers:
+ *         M   = the largest |I_s| or |Q_s| over the segments
+ *         k   = max(0, bitlength(M) - 12)                    bitlength(0) = 0, bitlength(4095) = 12, bitlength(4096) = 13
+ *         I'_s = (I_s + 2^(k-1)) >> k                        arithmetic shift (floor); I_s itself when k = 0.  Q'_s likewise
+ *     A, B, re, im and mag are formed from I', Q': |I'| <= 2^12, so |A|, |B| <= 2^25, a term is at most 2^50 and the sum of fewer than
+ *     2^12 of them below 2^62.  There is no new GPSACQ_ERR_UNSUPPORTED case.  power stays the sum of the UNSHIFTED squares.  df_hz
+ *     and coherence are ratios and do not see k (the shifted estimate differed from the unshifted one by at most 0.018 Hz in
+ *     simulation, against an error of 0.6 to 4 Hz).  The Doppler is the search's own sense, the replica's frequency less what
+ *     was not Doppler in it:
+ *         doppler_hz = (((double)(int32)lo_rate * fs) / 2^32 - (f - lo_dop)) + df_hz
+ *     (int32)lo_rate is the word read as two's complement; f - lo_dop is the fp64 difference of the two values above.
+ *
+ * in->multibit == GPSACQ_SAMPLES_SIGN: the capture is converted once per call into engine scratch, by the path
+ * gpsacq_track_iq8_device uses (iq_convert.hpp's arithmetic, in->mean_i / mean_q, mix_hz, fs and first_sample as there), and the
+ * 1-bit kernels of "Fine code phases" and "Cold snapshot fixes" run on it with n_bytes = ceil(n_samples / 8) and stride / 16: the
+ * result is byte for byte gpsacq_iq8_to_bits_device followed by gpsacq_refine_device / gpsacq_fine_doppler_device.
+ *
+ * gpsacq_refine_iq8, gpsacq_fine_doppler_iq8: host pointers, return after completion.  The _device forms: iq, tasks, peaks and the
+ * records are device pointers, `in` and the params stay host pointers (params NULL: the defaults); work on the engine's stream, sync
+ * != 0 waits; host and device form agree byte for byte.  gpsacq_coarse_fix_fine_iq8_device is gpsacq_coarse_fix_fine_device and
+ * gpsacq_cold_fix_iq8_device is gpsacq_cold_fix_device with (in, d_iq, n_samples) for (d_bits, n_bytes): the same kernels downstream
+ * of the two that read the capture, one stream, no host copy in between, the same optional scratch buffers; in sign mode the capture
+ * is converted once for both kernels.  Argument errors are those of the 1-bit forms plus in == NULL, a format or multibit value that
+ * gpsacq_search_iq8 refuses, a mean beyond +-128 where it is removed, a stride outside the bounds above and a misaligned device
+ * pointer: GPSACQ_ERR_ARG, nothing launched and nothing written.  Engines the 1-bit forms refuse are GPSACQ_ERR_UNSUPPORTED here too.
+ * Kernels (csrc/snapshot_iq_kernels.hip).  k_refine_iq and k_fine_dop_iq: one workgroup of four wave64 per task; wave w takes
+ * segments w, w + 4, ..., lane l the 16-byte groups (8 samples) l, l + 64, ... of a segment; bytes XORed with 0x80 for
+ * GPSACQ_IQ_U8, weight dwords of +1 / -1 / 0 bytes and 4 x int8 dot products, 24 per group (8 for the prompt alone), the mean as a
+ * correction applied only when it is not zero; the 24 chips of a group are bits of one 32-chip window cut out of the chip sequence in
+ * LDS; int32 sums per lane, xor shuffles over the wave, 64-bit integer squares; no atomics and no float before the estimate, so
+ * the record does not depend on the order of anything.  Every loop is bounded by kernel arguments.
+ *
+ * gpsacq_snap_quality* stays for 1-bit records (sign mode's included): its analytic floor is that of a +-1 stream.
+ *
+ * OUT OF SCOPE.  A noise floor for multi-bit records (gpsacq_snap_quality).  Multi-bit aided and coherent aided searches.
+ * Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.
+ */
+GPSACQ_API int gpsacq_refine_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride, const gpsacq_task* tasks,
+                                 const gpsacq_peak* peaks, size_t n_tasks, const gpsacq_refine_params* params, gpsacq_fine* fine_out);
+GPSACQ_API int gpsacq_refine_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                        const void* d_tasks, const void* d_peaks, size_t n_tasks, const gpsacq_refine_params* params, void* d_fine,
+                                        int sync);
+GPSACQ_API int gpsacq_fine_doppler_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                                       const gpsacq_task* tasks, const gpsacq_peak* peaks, size_t n_tasks, const gpsacq_dopfine_params* params,
+                                       gpsacq_dopfine* dopfine_out);
+GPSACQ_API int gpsacq_fine_doppler_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                              const void* d_tasks, const void* d_peaks, size_t n_tasks, const gpsacq_dopfine_params* params,
+                                              void* d_dopfine, int sync);
+GPSACQ_API int gpsacq_coarse_fix_fine_iq8_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_iq8_input* in, const void* d_iq,
+                                                 size_t n_samples, size_t stride, const void* d_tasks, const void* d_peaks, size_t n_fix, int n_chans,
+                                                 const gpsacq_refine_params* refine_params, const void* d_prior, const gpsacq_coarse_params* params,
+                                                 void* d_fine, void* d_obs, void* d_fix, void* d_info, void* d_obs_out, int sync);
+GPSACQ_API int gpsacq_cold_fix_iq8_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_iq8_input* in, const void* d_iq,
+                                          size_t n_samples, size_t stride, const void* d_tasks, const void* d_peaks, const void* d_rx_ms, size_t n_fix,
+                                          int n_chans, const gpsacq_dopfine_params* dopfine_params, const gpsacq_doppler_fix_params* doppler_params,
+                                          const gpsacq_refine_params* refine_params, const gpsacq_coarse_params* coarse_params, void* d_dopfine,
+                                          void* d_rate_obs, void* d_doppler_fix, void* d_prior, void* d_fine, void* d_obs, void* d_fix, void* d_info,
+                                          void* d_obs_out, int sync);
+/* device time of the last call of this section on this engine, milliseconds (HIP events on its stream; waits for them): the 8-bit ->
+ * 1-bit conversion (sign mode), the kernel that wrote the fine records (k_refine_iq, in sign mode k_refine) and the one that wrote
+ * the fine Dopplers (k_fine_dop_iq, in sign mode k_fine_dop).  A kernel that the last call did not run reads 0.  Any pointer may be
+ * NULL. */
+GPSACQ_API int gpsacq_snapshot_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* refine_ms, float* fine_dop_ms);
 
 /*
  * ---- Aided acquisition: predicted code phase and Doppler, windowed search -------------------------------------------------------

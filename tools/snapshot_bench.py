@@ -14,6 +14,7 @@ is worth at 5.456 MHz.
 
     python tools/snapshot_bench.py [--blocks 2048] [--reps 5] [--refine [--refine-blocks 16]] [--cold] [--aided [--weak-amplitude 0.05]]
                                    [--aided-coh [--weak-amplitude 0.03]] [--raim [--fault-share F] [--sigma-m S]] [--quality]
+    python tools/snapshot_bench.py --iq8 [--blocks 2048] [--reps 5] [--refine-blocks 16] [--amplitude 0.2] [--if-hz 400000]
 
 --refine: the capture is made K - 1 blocks longer (K = --refine-blocks) so that every searched block has its whole window, and
 each repetition also runs gpsacq_coarse_fix_fine_device on the same capture, tasks and peaks: k_refine (the fine code phases of
@@ -66,6 +67,15 @@ sample within 1.5 samples of the true phase is no fault and is not counted as pl
 and EXCLUDED rows beside that of the unchecked fixes of the same observations.  --sigma-m defaults to the measured code-phase rms
 of this scene (README): 3.41 m with --refine, 19.93 m without.  Times are HIP events on the engine's stream; the shader clock is
 not read.
+
+--iq8: a run of its own on ONE 8-bit IQ capture ("Snapshot chain on an 8-bit IQ capture" of include/gpsacq.h): the --refine scene made
+by gpsacq_generate_iq8_range_device (int8, scale 16, sigma 1, a residual IF of --if-hz), searched by gpsacq_search_iq8_device in
+multi-bit mode, and the peaks then taken through gpsacq_coarse_fix_fine_iq8_device and gpsacq_fine_doppler_iq8_device BOTH ways:
+multi-bit (k_refine_iq, k_fine_dop_iq) and sign mode (the conversion once per call, then k_refine / k_fine_dop).  The line carries
+refine_iq_ms and fine_dop_iq_ms beside convert_ms + refine_ms and convert_ms + fine_dop_ms of the sign path (best of --reps, HIP
+events) and search_ms of the same run; the code-phase error of both paths against the generator's law (rms and worst over the true
+hits both have); the fine Dopplers' error; the position error (median, worst) of the blocks both fixed; and the bytes a hit reads
+over the kernel's time.  The shader clock is not read.
 """
 import argparse
 import json
@@ -77,6 +87,111 @@ sys.path.insert(0, os.path.join(ROOT, "gnss-gps-sdr_amd", "python"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 FS, FC = 5.456e6, 4.092e6
+
+
+def main_iq8(a):
+    import numpy as np
+    import torch
+
+    import gpsacq
+    from coarse_helpers import block_times, priors, synth_sats
+    from nav_helpers import geometry, to_records
+
+    geo = geometry("north")
+    sel = geo["subsets"][8]
+    ephs = to_records([geo["ephs"][k] for k in sel])
+    spb = gpsacq.BLOCK_BYTES * 8  # samples per block: 40960, so 81920 bytes of I, Q
+    stride = 2 * spb
+    mid = a.blocks // 2
+    ref_ms, ref_frac = geo["ref_ms"] + 4321, 0.6180e-3  # the receive time of the first sample of block `mid`
+    sats, _ = synth_sats(geo, sel, ref_ms, ref_frac, mid * spb, FS, a.amplitude)
+    blk_ms, blk_frac = block_times(ref_ms, ref_frac - mid * spb / FS, a.blocks, spb, FS)
+    prior = priors(geo, blk_ms, seed=3, km=30.0, secs=30.0)
+    tasks = np.array([(b, s[0] - 1) for b in range(a.blocks) for s in sats], dtype=np.int32)
+    n_samples, n_tasks, m = (a.blocks + a.refine_blocks - 1) * spb, len(tasks), len(sats)
+    rp, dp = gpsacq.refine_params(blocks=a.refine_blocks), gpsacq.dopfine_params(blocks=a.refine_blocks)
+    modes = ("multibit", "sign")
+    with gpsacq.Engine(FC, FS, 5000.0, device=0) as eng:
+        dev = lambda arr: torch.from_numpy(arr.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+        zeros = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, device="cuda:0")
+        d_iq, d_tasks, d_prior = zeros(2 * n_samples), dev(tasks), dev(prior)
+        d_peaks = zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize)
+        buf = {k: dict(fine=zeros(n_tasks * gpsacq.FINE_DTYPE.itemsize), dop=zeros(n_tasks * gpsacq.DOPFINE_DTYPE.itemsize),
+                       fix=zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), info=zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)) for k in modes}
+        inp = {"multibit": eng.iq8_input(signed=True, remove_dc=False, mix_hz=FC - a.if_hz, multibit=1),
+               "sign": eng.iq8_input(signed=True, remove_dc=False, mix_hz=FC - a.if_hz, multibit=0)}  # GPSACQ_SAMPLES_REAL, GPSACQ_SAMPLES_SIGN
+        torch.cuda.synchronize()
+        eng.generate_iq8_device(d_iq.data_ptr(), n_samples, sats, if_hz=a.if_hz, scale=16.0, signed=True, noise_sigma=1.0, seed=77)
+        search_best = float("inf")
+        best = {k: dict(convert_refine=(float("inf"), 0.0, 0.0), convert_dop=(float("inf"), 0.0, 0.0)) for k in modes}
+        for _ in range(1 + a.reps):  # the first call also allocates the engine's scratch
+            eng.search_iq8_device(d_iq.data_ptr(), inp["multibit"], a.blocks, d_peaks.data_ptr(), stride=stride, d_tasks_ptr=d_tasks.data_ptr(),
+                                  n_tasks=n_tasks, sync=True)
+            search_best = min(search_best, eng.last_timing()["ms_total"])
+            for k in modes:
+                b = buf[k]
+                eng.coarse_fix_fine_iq8_device(ephs, inp[k], d_iq.data_ptr(), n_samples, d_tasks.data_ptr(), d_peaks.data_ptr(), a.blocks, m,
+                                               d_prior.data_ptr(), b["fix"].data_ptr(), b["info"].data_ptr(), d_fine_ptr=b["fine"].data_ptr(),
+                                               stride=stride, refine_params=rp, sync=True)
+                c, r, _ = eng.snapshot_iq8_last_ms()
+                best[k]["convert_refine"] = min(best[k]["convert_refine"], (c + r, c, r))
+                eng.fine_doppler_iq8_device(inp[k], d_iq.data_ptr(), n_samples, d_peaks.data_ptr(), n_tasks, b["dop"].data_ptr(), stride=stride,
+                                            d_tasks_ptr=d_tasks.data_ptr(), params=dp, sync=True)
+                c, _, d = eng.snapshot_iq8_last_ms()
+                best[k]["convert_dop"] = min(best[k]["convert_dop"], (c + d, c, d))
+        peaks = d_peaks.cpu().numpy().view(gpsacq.PEAK_DTYPE).reshape(a.blocks, m)
+        out = {k: dict(fine=buf[k]["fine"].cpu().numpy().view(gpsacq.FINE_DTYPE).reshape(a.blocks, m),
+                       dop=buf[k]["dop"].cpu().numpy().view(gpsacq.DOPFINE_DTYPE).reshape(a.blocks, m),
+                       fix=buf[k]["fix"].cpu().numpy().view(gpsacq.FIX_DTYPE), info=buf[k]["info"].cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE))
+               for k in modes}
+        name = eng.device_name
+    # the generator's law: at sample m satellite s shows the code position (m + code_phase) * chips_per_sample
+    C, L1, CPS = 2.99792458e8, 1575.42e6, 1.023e6
+    m0 = np.arange(a.blocks, dtype=np.float64)[:, None] * spb
+    cps = np.array([CPS * (1.0 + s[2] / L1) / FS for s in sats])[None, :]
+    want = ((m0 + np.array([s[3] for s in sats])[None, :]) * cps % 1023.0) / CPS
+    dops = np.array([s[2] for s in sats])[None, :]
+    wrap = lambda t: (t + 0.5e-3) % 1e-3 - 0.5e-3
+    hit = (peaks["snr"] >= gpsacq.THRESHOLD) & (np.abs(wrap(peaks["ca_shift"] / FS - want)) * FS <= 1.5)  # true peaks only
+    dop_hit = hit.copy()
+    for k in modes:
+        hit &= (out[k]["fine"]["flags"] & (gpsacq.FINE_NO_HIT | gpsacq.FINE_NO_POWER | gpsacq.FINE_FEW)) == 0
+        dop_hit &= (out[k]["dop"]["flags"] & (gpsacq.DOPFINE_NO_HIT | gpsacq.DOPFINE_NO_POWER | gpsacq.DOPFINE_FEW | gpsacq.DOPFINE_WEAK)) == 0
+    ok = np.ones(a.blocks, bool)
+    for k in modes:
+        ok &= (out[k]["fix"]["status"] == 0) & (out[k]["info"]["flags"] == 0)  # the same blocks both ways
+    r2, r4 = (lambda v: round(float(v), 2)), (lambda v: round(float(v), 4))
+    e_whole = C * wrap(peaks["ca_shift"] / FS - want)[hit]
+    res = {"bench": "snapshot_iq8", "device": name, "blocks": a.blocks, "sats": m, "tasks": n_tasks, "amplitude": a.amplitude, "if_hz": a.if_hz,
+           "scale": 16.0, "refine_blocks": a.refine_blocks, "prior_off_km": 30.0, "prior_off_s": 30.0, "shader_clock_read": False,
+           "search_ms": r4(search_best), "peaks_above_threshold": int((peaks["snr"] >= gpsacq.THRESHOLD).sum()), "fine_hits": int(hit.sum()),
+           "doppler_hits": int(dop_hit.sum()), "blocks_compared": int(ok.sum()),
+           "code_phase_rms_whole_m": r2(np.sqrt((e_whole ** 2).mean())) if hit.any() else None,
+           "refine_iq_ms": r4(best["multibit"]["convert_refine"][2]), "fine_dop_iq_ms": r4(best["multibit"]["convert_dop"][2]),
+           "sign_convert_ms": r4(best["sign"]["convert_refine"][1]), "sign_refine_ms": r4(best["sign"]["convert_refine"][2]),
+           "sign_convert_plus_refine_ms": r4(best["sign"]["convert_refine"][0]), "sign_fine_dop_ms": r4(best["sign"]["convert_dop"][2]),
+           "sign_convert_plus_fine_dop_ms": r4(best["sign"]["convert_dop"][0])}
+    res["refine_iq_over_sign"] = r4(res["refine_iq_ms"] / res["sign_convert_plus_refine_ms"])
+    res["refine_iq_over_search"] = r4(res["refine_iq_ms"] / search_best)
+    for k in modes:
+        e = C * wrap(out[k]["fine"]["tx_frac"] - want)[hit]
+        e_hz = (out[k]["dop"]["doppler_hz"] - dops)[dop_hit]
+        off = np.linalg.norm(np.stack([out[k]["fix"][c] for c in "xyz"], 1) - geo["rx"], axis=1)
+        res.update({"code_phase_rms_%s_m" % k: r2(np.sqrt((e ** 2).mean())) if hit.any() else None,
+                    "code_phase_worst_%s_m" % k: r2(np.abs(e).max()) if hit.any() else None,
+                    "doppler_error_rms_%s_hz" % k: r4(np.sqrt((e_hz ** 2).mean())) if dop_hit.any() else None,
+                    "doppler_error_worst_%s_hz" % k: r4(np.abs(e_hz).max()) if dop_hit.any() else None,
+                    "fixes_ok_%s" % k: int((out[k]["fix"]["status"] == 0).sum()),
+                    "position_error_median_%s_m" % k: r2(np.median(off[ok])) if ok.any() else None,
+                    "position_error_worst_%s_m" % k: r2(off[ok].max()) if ok.any() else None})
+    # what a hit reads: its window of I, Q bytes (the segments of a whole window), over the kernel's time
+    seg = a.refine_blocks * 40000 // int(FS / 1000.0)
+    per_hit = 2 * seg * int(FS / 1000.0)
+    n_hits = int((peaks["snr"] >= float(rp["snr_min"][0])).sum())
+    res.update({"bytes_read_per_hit": per_hit, "refine_iq_read_GBps": r2(per_hit * n_hits / (res["refine_iq_ms"] * 1e-3) / 1e9),
+                "fine_dop_iq_read_GBps": r2(per_hit * n_hits / (res["fine_dop_iq_ms"] * 1e-3) / 1e9),
+                "capture_MB": r2(2 * n_samples / 1e6)})
+    print(json.dumps(res))
 
 
 def main():
@@ -93,7 +208,12 @@ def main():
     ap.add_argument("--raim", action="store_true", help="also plant false peaks and run the coarse-time fix with integrity on them")
     ap.add_argument("--fault-share", type=float, default=0.01, help="share of the blocks of --raim that get one false peak (0 .. 1)")
     ap.add_argument("--sigma-m", type=float, default=None, help="sigma_m of --raim (default 3.41 with --refine, 19.93 without)")
+    ap.add_argument("--iq8", action="store_true", help="the snapshot chain on an 8-bit IQ capture, multi-bit and sign mode, a run of its own")
+    ap.add_argument("--amplitude", type=float, default=0.2, help="amplitude of the eight satellites of --iq8")
+    ap.add_argument("--if-hz", type=float, default=0.4e6, help="residual IF of the capture of --iq8")
     a = ap.parse_args()
+    if a.iq8:
+        return main_iq8(a)
     a.aided = a.aided or a.aided_coh or a.quality
     if a.weak_amplitude is None:
         a.weak_amplitude = 0.03 if a.aided_coh else 0.05
