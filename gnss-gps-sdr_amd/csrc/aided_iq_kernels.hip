@@ -1,0 +1,285 @@
+// aided_iq_kernels.hip -- "Aided acquisition on an 8-bit IQ capture" of include/gpsacq.h, multi-bit mode: the windowed search of
+// "Aided acquisition" B on the IQ bytes themselves, both arms and every amplitude bit.
+//
+// k_aided_iq: one workgroup of AIDED_IQ_WAVES wave64 per task.  The PRN's chips go into LDS as in k_refine_iq; wave w takes the
+// segments w, w + 4, ... of the window.  The 2 W + 1 code hypotheses of one (segment, d) share one carrier-wiped series
+// a_j = (v_i C - v_q S, v_i S + v_q C) and one chip stream s'[m] = +-1: hypothesis h wants sum_j s'[j + h] a_j.  Summed by parts
+// over a chunk of n samples that is
+//     R(h) = s'[M] A[n] - sum over m in [1, M] of D[m] A[m - h],      M = n + 2 W - 1,
+// with A[k] the inclusive prefix sums of a (A[k] = 0 for k <= 0, A[k] = A[n] for k >= n) and D[m] = s'[m] - s'[m - 1], which is 0
+// except at the chip TRANSITIONS of the stream (0.19 per sample at 5.456 MHz).  Exact, in integers.  Per (segment, d) and chunk of
+// AIDED_IQ_CHUNK samples (counted from the 8-sample group the segment starts in; samples of the chunk before or after the
+// segment count as a = 0):
+//   WIPE.  Lane l takes the 16-byte groups l, l + 64 of the chunk (iq_groups.hpp: load_group and the flip word): per sample the
+//     mean is taken off, the carrier signs come from ph = j lo_rate, the eight a's are summed up inside the lane, a wave scan
+//     (shuffles) of the lanes' totals plus the total carried from the groups before gives A[1 .. n], int2, into the wave's LDS;
+//     2 W copies of A[n] go behind.  The slots in front are zero from the kernel's start.
+//   STREAM.  The lanes evaluate the chip of stream position m = 0 .. M, 64 at a time; a ballot gives the chips as one mask, the
+//     mask xor itself shifted by one position (the last chip of the 64 before carried in) the transitions, and a popcount below the
+//     lane the transition's place in the wave's list: 15 bits of m and the new chip, in order.  The list is filled up to a
+//     multiple of four with entries that read a zero.
+//   SUM.  Lane h (h + 64, ... in further passes over the same list) walks the list: one 8-byte broadcast read brings four
+//     entries, per entry one ds_read_b64 of A[m - h] -- neighbouring lanes read neighbouring int2 -- added or subtracted in
+//     wrap-around uint32; R(h) of the chunk adds into the lane's (I, Q) of the segment.
+// At the segment's end the lane squares its own I and Q into its own uint64.  The floor's sum v_i^2 + v_q^2 is taken in WIPE at
+// the first valid d alone.  Once per d the four waves' sums meet in LDS (the waves' own prefix arrays serve: two barriers); thread h
+// adds them, writes power(h, d) and keeps its total and the largest (power, 31 - d, 255 - h): a power may take 62 bits here, so
+// the key is a pair.  No atomics, no float before the ratio.  Every loop is bounded by kernel arguments; the prefix array is
+// read at slot AIDED_IQ_PAD + m - h with m in [0, n + 2 W - 1] and h in [0, 255] (the lanes beyond 2 W read and are not used), so in
+// [1, AIDED_IQ_SLOTS - 3], written in [0, AIDED_IQ_PAD + n + 2 W - 1], and the list is indexed below n + 2 W + 2 <= AIDED_IQ_LIST
+// (W <= 127 and n <= 1024 are the host's check and the chunk); nothing at or beyond byte 2 * n_samples is read (load_group).
+// Static LDS: s_chips 136 + s_a 49152 + s_list 10240 + s_red 128 = 59656 bytes (59664 with alignment in the compiler's report), below k_aided_coh's 61224: two workgroups per CU.
+// Built with -ffp-contract=off (Makefile): the NCO words must be the host's to the bit, as in refine_kernels.hip.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "aided_iq_launch.hpp"
+#include "capture_groups.hpp"
+
+namespace acq {
+
+namespace {
+typedef uint16_t __attribute__((may_alias)) list_u16;  // the list is written entry by entry and read four entries at a time
+
+// the lanes of ONE wave hand LDS to each other: the wave's LDS operations execute in program order, so all that is needed is
+// that the compiler keeps them in it
+__device__ __forceinline__ void wave_sync_iq() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the window of Doppler hypothesis lo_shift: the IQ section's steps 1 to 3 on a peak that is a hit by itself
+__device__ __forceinline__ Window window_at_iq(const AidedIqArgs& a, size_t t, int64_t lo_shift) {
+    Window w = {false, 0, 0, 0, 0, 0, 0, 0};
+    if (lo_shift < -(int64_t)a.kmax || lo_shift > (int64_t)a.kmax) return w;
+    const gpsacq_peak pk = {1.0f, (int32_t)lo_shift, 0, 0.0f};
+    double base_hz;
+    return window_of_iq(pk, a.c, t, 0.0, a.p.blocks, base_hz);
+}
+
+// the larger of two keys (power, tag): the power first, then the tag
+__device__ __forceinline__ void key_max(uint64_t& pw, uint32_t& tag, uint64_t opw, uint32_t otag) {
+    if (opw > pw || (opw == pw && otag > tag)) pw = opw, tag = otag;
+}
+
+__device__ __forceinline__ uint64_t shfl_xor64_iq(uint64_t v, int m) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
+    return (uint64_t)hi << 32 | lo;
+}
+}  // namespace
+
+__global__ __launch_bounds__(64 * AIDED_IQ_WAVES) void k_aided_iq(AidedIqArgs a) {
+    __shared__ uint32_t s_chips[CHIP_WORDS];
+    __shared__ int2 s_a[AIDED_IQ_WAVES][AIDED_IQ_SLOTS];         // slot AIDED_IQ_PAD + k holds A[k]
+    __shared__ uint2 s_list[AIDED_IQ_WAVES][AIDED_IQ_LIST / 4];  // four 16-bit entries per uint2
+    __shared__ unsigned long long s_red[AIDED_IQ_WAVES][4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t t = blockIdx.x;
+    const int W = a.p.code_half, K = a.p.dop_half, n_code = 2 * W + 1, n_dop = 2 * K + 1;
+    unsigned long long* const powers = a.powers ? a.powers + t * (size_t)(n_dop * n_code) : nullptr;
+
+    // 1. kept, 2. no aid: the flag and zeros
+    int blank = 0;
+    gpsacq_peak pk_out = {0.0f, 0, 0, 0.0f};
+    const gpsacq_aid aid = a.aid[t];
+    if (a.c.peaks) {
+        const gpsacq_peak pk = a.c.peaks[t];
+        if ((double)pk.snr >= a.p.keep_snr) blank = GPSACQ_AIDED_KEPT, pk_out = pk;
+    }
+    Window win = {false, 0, 0, 0, 0, 0, 0, 0};
+    int d_first = 0;  // the first valid d: the floor is summed there
+    if (!blank) {
+        if (aid.flags == 0 && aid.ca_center >= 0 && aid.ca_center < a.c.spm)
+            for (int d = 0; d < n_dop && !win.hit; ++d) win = window_at_iq(a, t, (int64_t)aid.lo_center - K + d), d_first = d;
+        if (!win.hit) blank = GPSACQ_AIDED_NO_AID;
+    }
+    if (blank) {
+        if (threadIdx.x == 0) {
+            a.out[t] = gpsacq_aided{blank, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0};
+            a.peaks_out[t] = pk_out;
+        }
+        if (powers)
+            for (int i = threadIdx.x; i < n_dop * n_code; i += 64 * AIDED_IQ_WAVES) powers[i] = 0;
+        return;
+    }
+    chips_to_lds(a.c.chips, win.prn, s_chips);
+    int2* const A = s_a[wv];
+    list_u16* const list = reinterpret_cast<list_u16*>(s_list[wv]);
+    for (int i = lane; i <= AIDED_IQ_PAD; i += 64) A[i] = make_int2(0, 0);  // A[k] = 0 for k <= 0: never written again
+    __syncthreads();
+
+    // 3. hypotheses, 4. sums
+    const uint64_t o = win.o, spm = (uint64_t)a.c.spm, segments = win.segments;  // o is a multiple of 8: stride is one of 16
+    const uint32_t base = (uint32_t)(((aid.ca_center - W) % a.c.spm + a.c.spm) % a.c.spm);
+    const size_t iq_bytes = 2 * a.c.n_samples;
+    const int dc_i = a.c.dc_i, dc_q = a.c.dc_q;
+    uint64_t total = 0, best = 0, floor_sum = 0;  // of hypothesis h = threadIdx.x; floor_sum of the lane's samples
+    uint32_t tag = 0;
+    for (int d = 0; d < n_dop; ++d) {
+        const Window wd = window_at_iq(a, t, (int64_t)aid.lo_center - K + d);
+        if (!wd.hit) {  // every lane decides the same
+            if (powers && (int)threadIdx.x < n_code) powers[d * n_code + threadIdx.x] = 0;
+            continue;
+        }
+        const uint32_t lo_rate = wd.lo_rate, ca_rate = wd.ca_rate;
+        const bool with_floor = d == d_first;
+        uint64_t acc[AIDED_PASSES] = {0, 0, 0, 0};
+        for (uint64_t s = wv; s < segments; s += AIDED_IQ_WAVES) {
+            const uint64_t a0 = o + s * spm, a1 = a0 + spm;  // the segment's samples [a0, a1) of the capture
+            uint32_t Ri[AIDED_PASSES] = {0, 0, 0, 0}, Rq[AIDED_PASSES] = {0, 0, 0, 0};
+            uint32_t fl = 0;  // < 2^27: at most 1032 samples of a lane in a segment, 2^17 each
+            for (uint64_t cs = a0 & ~7ull; cs < a1; cs += AIDED_IQ_CHUNK) {
+                const int n = a1 - cs < (uint64_t)AIDED_IQ_CHUNK ? (int)((a1 - cs + 7) & ~7ull) : AIDED_IQ_CHUNK;  // a multiple of 8
+                const int M = n + 2 * W - 1;
+                // WIPE
+                uint32_t ci = 0, cq = 0;  // A of the groups before, the same in every lane
+                for (int g0 = 0; g0 < n / 8; g0 += 64) {
+                    const int gl = g0 + lane;
+                    const bool mine = gl < n / 8;
+                    const uint64_t gs = cs + 8ull * (uint64_t)gl;
+                    uint32_t x[4] = {0, 0, 0, 0};
+                    if (mine) {
+                        const uint4 raw = load_group(a.c.iq, iq_bytes, gs >> 3);
+                        x[0] = raw.x ^ a.c.flip, x[1] = raw.y ^ a.c.flip, x[2] = raw.z ^ a.c.flip, x[3] = raw.w ^ a.c.flip;
+                    }
+                    const uint32_t b_lo = gs < a0 ? (uint32_t)(a0 - gs) : 0u;                       // 0 .. 7
+                    const uint32_t b_hi = !mine || gs >= a1 ? 0u : gs + 8 > a1 ? (uint32_t)(a1 - gs) : 8u;  // 0 .. 8
+                    uint32_t ph = (uint32_t)(gs - o) * lo_rate;
+                    uint32_t pi[8], pq[8], si = 0, sq = 0;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const uint32_t w = x[k >> 1] >> (16 * (k & 1));
+                        const bool keep = (uint32_t)k >= b_lo && (uint32_t)k < b_hi;
+                        const int vi = keep ? (int)(int8_t)(w & 0xffu) - dc_i : 0, vq = keep ? (int)(int8_t)((w >> 8) & 0xffu) - dc_q : 0;
+                        const bool cneg = ((ph >> 31) ^ (ph >> 30)) & 1u, sneg = (~ph >> 31) & 1u;  // the carrier bits of THE CHANNEL MODEL
+                        const int vic = cneg ? -vi : vi, vqc = cneg ? -vq : vq, vis = sneg ? -vi : vi, vqs = sneg ? -vq : vq;
+                        si += (uint32_t)(vic - vqs);  // v_i C - v_q S
+                        sq += (uint32_t)(vis + vqc);  // v_i S + v_q C
+                        pi[k] = si, pq[k] = sq;
+                        if (with_floor) fl += (uint32_t)(vi * vi + vq * vq);
+                        ph += lo_rate;
+                    }
+                    // the lanes' totals, summed up over the wave
+                    uint32_t ti = si, tq = sq;
+#pragma unroll
+                    for (int m = 1; m < 64; m <<= 1) {
+                        const uint32_t ui = (uint32_t)__shfl_up((int)ti, m, 64), uq = (uint32_t)__shfl_up((int)tq, m, 64);
+                        if (lane >= m) ti += ui, tq += uq;
+                    }
+                    const uint32_t bi = ci + ti - si, bq = cq + tq - sq;  // A before the lane's group
+                    if (mine) {
+                        int2* dst = A + AIDED_IQ_PAD + 8 * gl + 1;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) dst[k] = make_int2((int)(bi + pi[k]), (int)(bq + pq[k]));
+                    }
+                    ci += (uint32_t)__shfl((int)ti, 63, 64), cq += (uint32_t)__shfl((int)tq, 63, 64);
+                }
+                for (int i = lane + 1; i < 2 * W; i += 64) A[AIDED_IQ_PAD + n + i] = make_int2((int)ci, (int)cq);  // A[k] = A[n] for k > n
+                // STREAM: the chip of position m is that of window sample (cs - o) + m at h = 0
+                int count = 0;
+                uint32_t chip_M = 0;
+                uint64_t before = 0;
+                const uint64_t q0 = cs - o;
+                for (int m0 = 0; m0 <= M; m0 += 64) {
+                    const uint64_t P = mod_full(((uint64_t)base + q0 + (uint64_t)(m0 + lane)) * ca_rate);  // below 2^23 * 2^32
+                    const uint32_t cb = (uint32_t)(P >> 32);                                                // 0 .. 1022
+                    const uint32_t chip = (s_chips[cb >> 5] >> (cb & 31)) & 1u;
+                    const uint64_t bits = __ballot(chip != 0);
+                    const uint64_t prev = m0 == 0 ? bits & 1ull : before >> 63;
+                    const int left = M - m0;  // the positions of this round are 0 .. min(left, 63)
+                    const uint64_t valid = left >= 63 ? ~0ull : (2ull << left) - 1ull;
+                    const uint64_t trans = (bits ^ (bits << 1 | prev)) & valid;
+                    if (trans >> lane & 1ull) list[count + __popcll(trans & ((1ull << lane) - 1ull))] = (uint16_t)((uint32_t)(m0 + lane) | chip << 15);
+                    count += __popcll(trans);
+                    if (left <= 63) chip_M = (uint32_t)(bits >> left) & 1u;
+                    before = bits;
+                }
+                if (lane < 3 && count + lane < ((count + 3) & ~3)) list[count + lane] = 0;  // up to a multiple of four: entries that read A[-h] = 0
+                const int quads = (count + 3) >> 2;
+                wave_sync_iq();
+                // SUM
+                const uint2* const lq = s_list[wv];
+#pragma unroll
+                for (int p = 0; p < AIDED_PASSES; ++p) {
+                    if (64 * p < n_code) {  // the lanes beyond n_code read slots that exist and are not used
+                        const int2* const Ah = A + AIDED_IQ_PAD - (lane + 64 * p);
+                        uint32_t sx = 0, sy = 0;
+                        for (int i = 0; i < quads; ++i) {
+                            const uint2 e = lq[i];
+                            const uint32_t ent[4] = {e.x & 0xffffu, e.x >> 16, e.y & 0xffffu, e.y >> 16};
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                const int2 v = Ah[ent[k] & 0x7fffu];
+                                const uint32_t msk = (ent[k] >> 15) - 1u;  // the new chip 1 (s' falls, D = -2): + A; 0 (D = +2): - A
+                                sx += ((uint32_t)v.x ^ msk) - msk;
+                                sy += ((uint32_t)v.y ^ msk) - msk;
+                            }
+                        }
+                        const uint32_t sM = chip_M ? ~0u : 0u;  // s'[M] A[n]
+                        Ri[p] += ((ci ^ sM) - sM) + 2u * sx;
+                        Rq[p] += ((cq ^ sM) - sM) + 2u * sy;
+                    }
+                }
+                wave_sync_iq();
+            }
+#pragma unroll
+            for (int p = 0; p < AIDED_PASSES; ++p) {
+                const int64_t I = (int32_t)Ri[p], Q = (int32_t)Rq[p];
+                acc[p] += (uint64_t)(I * I + Q * Q);
+            }
+            floor_sum += fl;
+        }
+        // the waves' sums meet in their prefix arrays: slot h of wave w holds its acc of hypothesis h
+#pragma unroll
+        for (int p = 0; p < AIDED_PASSES; ++p) A[AIDED_IQ_PAD + 1 + lane + 64 * p] = make_int2((int)(uint32_t)acc[p], (int)(uint32_t)(acc[p] >> 32));
+        __syncthreads();
+        if ((int)threadIdx.x < n_code) {
+            uint64_t pw = 0;
+            for (int w = 0; w < AIDED_IQ_WAVES; ++w) {
+                const int2 v = s_a[w][AIDED_IQ_PAD + 1 + threadIdx.x];
+                pw += (uint64_t)(uint32_t)v.y << 32 | (uint32_t)v.x;
+            }
+            if (powers) powers[d * n_code + threadIdx.x] = pw;
+            total += pw;
+            key_max(best, tag, pw, (uint32_t)(31 - d) << 8 | (uint32_t)(255 - threadIdx.x) | 1u << 16);
+        }
+        __syncthreads();
+    }
+
+    // 5. record, 6. peak
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint64_t opw = shfl_xor64_iq(best, m);
+        const uint32_t otag = (uint32_t)__shfl_xor((int)tag, m, 64);
+        key_max(best, tag, opw, otag);
+        total += shfl_xor64_iq(total, m);
+        floor_sum += shfl_xor64_iq(floor_sum, m);
+    }
+    if (lane == 0) s_red[wv][0] = best, s_red[wv][1] = tag, s_red[wv][2] = total, s_red[wv][3] = floor_sum;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    best = total = floor_sum = 0, tag = 0;
+    for (int w = 0; w < AIDED_IQ_WAVES; ++w) {
+        key_max(best, tag, s_red[w][0], (uint32_t)s_red[w][1]);
+        total += s_red[w][2];
+        floor_sum += s_red[w][3];
+    }
+    gpsacq_aided r = {0, (int32_t)segments, n_code, n_dop, 255 - (int32_t)(tag & 255), 31 - (int32_t)(tag >> 8 & 31), 0, 0, best, total, 2 * floor_sum, 0.0};
+    r.lo_shift = aid.lo_center - K + r.best_d;
+    r.ca_shift = (int32_t)((base + (uint32_t)r.best_h) % (uint32_t)a.c.spm);
+    if (r.floor) r.ratio = (double)r.best / (double)r.floor;
+    if (segments < win.fit) r.flags |= GPSACQ_AIDED_SHORT;
+    if (segments < (uint64_t)a.p.min_segments) r.flags |= GPSACQ_AIDED_FEW;
+    if (r.best == 0) r.flags |= GPSACQ_AIDED_NO_POWER;
+    if (r.ratio < a.p.ratio_min) r.flags |= GPSACQ_AIDED_BELOW;
+    if (!(r.flags & (GPSACQ_AIDED_FEW | GPSACQ_AIDED_NO_POWER | GPSACQ_AIDED_BELOW))) pk_out = gpsacq_peak{(float)r.ratio, r.lo_shift, r.ca_shift, (float)r.best};
+    a.out[t] = r;
+    a.peaks_out[t] = pk_out;
+}
+
+void launch_aided_iq(const AidedIqArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_aided_iq, dim3((unsigned)a.c.n_tasks), dim3(64 * AIDED_IQ_WAVES), 0, s, a);
+}
+
+}  // namespace acq

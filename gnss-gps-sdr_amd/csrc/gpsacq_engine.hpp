@@ -236,6 +236,9 @@ struct gpsacq_engine {
     Scratch<gpsacq_peak> d_aided_peaks;  // host-buffer form: the output peaks
     Scratch<unsigned long long> d_aided_powers;  // host-buffer form: [n_tasks][2 K + 1][2 W + 1]
     Stages<2> aid_predict_t, aided_t;  // around k_aid_predict, around k_aided
+    // aided acquisition on an 8-bit IQ capture (gpsacq_aided_search_iq8*, gpsacq_aided_peaks_iq8_device): the capture of the
+    // host-buffer form goes into d_iq, sign mode's 1-bit stream into d_iqbits, everything else as the 1-bit forms'
+    Stages<2> aidiq_conv_t, aidiq_predict_t, aidiq_search_t;  // around the conversion, k_aid_predict, k_aided_iq (sign mode: k_aided)
     // coherent aided acquisition (gpsacq_aided_coh_search*, gpsacq_aid_instant*, gpsacq_aided_coh_peaks_device); the host-buffer forms
     // stage as the aided ones do, the coarse-time records in d_coarse_info / d_coarse_prior
     Scratch<int16_t> d_coh_table;            // the rotation table, C then S, made once

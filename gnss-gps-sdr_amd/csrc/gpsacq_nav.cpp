@@ -14,7 +14,8 @@
 // "Cold snapshot fixes": gpsacq_fine_doppler*, gpsacq_rate_obs_fine*, gpsacq_doppler_fix_batch* and gpsacq_cold_fix_device, which run
 // doppler_kernels.hip, and "Snapshot chain on an 8-bit IQ capture": gpsacq_refine_iq8*, gpsacq_fine_doppler_iq8* and the two *_iq8_device
 // chains, which run snapshot_iq_kernels.hip (sign mode: the conversion, then the 1-bit kernels), and "Aided acquisition": gpsacq_aid_predict*, gpsacq_aided_search* and gpsacq_aided_peaks_device, which run
-// aided_kernels.hip.
+// aided_kernels.hip, and "Aided acquisition on an 8-bit IQ capture": gpsacq_aided_search_iq8* and gpsacq_aided_peaks_iq8_device, which
+// run aided_iq_kernels.hip (sign mode: the conversion, then k_aided).
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -30,6 +31,7 @@
 #include "obs_launch.hpp"
 #include "raim_launch.hpp"
 #include "refine_launch.hpp"
+#include "aided_iq_launch.hpp"
 #include "aided_launch.hpp"
 #include "smooth_launch.hpp"
 #include "snapq_launch.hpp"
@@ -1831,19 +1833,24 @@ static int iq_snap_upload(gpsacq_engine* e, IqSnap& s, const void* iq, const gps
     return upload(e, e->d_refine_peaks, peaks, n_tasks);
 }
 
-// a call of this section begins: no timer has run; sign mode converts the capture once, timed, as gpsacq_track_iq8_device does
-static int iq_snap_begin(gpsacq_engine* e, IqSnap& s) {
-    e->snapiq_conv_t.done = e->snapiq_refine_t.done = e->snapiq_dop_t.done = false;
-    if (!s.sign) return GPSACQ_OK;
+// sign mode converts the capture once per call, timed by `timer`, as gpsacq_track_iq8_device does
+static int iq_snap_convert(gpsacq_engine* e, IqSnap& s, Stages<2>& timer) {
     s.n_bytes = (s.n_samples + 7) / 8;
     if (int rc = e->d_iqbits.grow(s.n_bytes, e->stream)) return rc;
     const size_t left = s.cap.iq_total > s.cap.iq_first ? s.cap.iq_total - s.cap.iq_first : 0;  // samples of the capture from iq[0] on
-    if (int rc = e->snapiq_conv_t.begin(e->stream)) return rc;
+    if (int rc = timer.begin(e->stream)) return rc;
     if (left < s.n_samples) HIPCHK(hipMemsetAsync(e->d_iqbits, 0, s.n_bytes, e->stream));
     if (int rc = iq8_to_bits_enqueue(e, s.d_iq, std::min(s.n_samples, left), s.cap.iq, s.cap.iq_first, e->d_iqbits)) return rc;
-    if (int rc = e->snapiq_conv_t.mark(1, e->stream)) return rc;
+    if (int rc = timer.mark(1, e->stream)) return rc;
     s.d_bits = e->d_iqbits;
-    return e->snapiq_conv_t.finish();
+    return timer.finish();
+}
+
+// a call of this section begins: no timer has run; sign mode converts the capture
+static int iq_snap_begin(gpsacq_engine* e, IqSnap& s) {
+    e->snapiq_conv_t.done = e->snapiq_refine_t.done = e->snapiq_dop_t.done = false;
+    if (!s.sign) return GPSACQ_OK;
+    return iq_snap_convert(e, s, e->snapiq_conv_t);
 }
 
 static void iq_capture_args(const gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_peaks, size_t n_tasks, IqCaptureArgs& c) {
@@ -2125,19 +2132,20 @@ static void aid_predict_launch(gpsacq_engine* e, int n_eph, const void* d_fix, c
     launch_aid_predict(a, e->stream);
 }
 
-// the ephemerides up, then k_aid_predict timed; every argument has been checked
+// the ephemerides up, then k_aid_predict timed by `timer`; every argument has been checked
 static int aid_predict_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel, size_t n_fix, int n_chans,
-                               const gpsacq_aid_params& ap, void* d_aid) {
+                               const gpsacq_aid_params& ap, void* d_aid, Stages<2>& timer) {
     if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
-    if (int rc = e->aid_predict_t.begin(e->stream)) return rc;
+    if (int rc = timer.begin(e->stream)) return rc;
     aid_predict_launch(e, n_eph, d_fix, d_vel, n_fix, n_chans, ap, d_aid);
-    if (int rc = e->aid_predict_t.mark(1, e->stream)) return rc;
-    return e->aid_predict_t.finish();
+    if (int rc = timer.mark(1, e->stream)) return rc;
+    return timer.finish();
 }
 
-// k_aided timed; every argument has been checked
+// k_aided timed by `timer`; every argument has been checked
 static int aided_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_aid,
-                         const void* d_peaks_in, size_t n_tasks, const gpsacq_aided_params& sp, void* d_aided, void* d_peaks_out, void* d_powers) {
+                         const void* d_peaks_in, size_t n_tasks, const gpsacq_aided_params& sp, void* d_aided, void* d_peaks_out, void* d_powers,
+                         Stages<2>& timer) {
     if (int rc = ensure_track_chips(e)) return rc;
     AidedArgs a{};
     capture_args(e, d_bits, n_bytes, stride, d_tasks, d_peaks_in, n_tasks, a);
@@ -2147,10 +2155,10 @@ static int aided_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes, s
     a.out = (gpsacq_aided*)d_aided;
     a.peaks_out = (gpsacq_peak*)d_peaks_out;
     a.powers = (unsigned long long*)d_powers;
-    if (int rc = e->aided_t.begin(e->stream)) return rc;
+    if (int rc = timer.begin(e->stream)) return rc;
     launch_aided(a, e->stream);
-    if (int rc = e->aided_t.mark(1, e->stream)) return rc;
-    return e->aided_t.finish();
+    if (int rc = timer.mark(1, e->stream)) return rc;
+    return timer.finish();
 }
 
 extern "C" int gpsacq_aid_predict_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel, size_t n_fix,
@@ -2158,7 +2166,7 @@ extern "C" int gpsacq_aid_predict_device(gpsacq_engine* e, const gpsacq_ephemeri
     gpsacq_aid_params ap;
     if (int rc = aid_predict_check("gpsacq_aid_predict", e, eph, n_eph, d_fix, n_fix, n_chans, params, d_aid, &ap)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = aid_predict_enqueue(e, eph, n_eph, d_fix, d_vel, n_fix, n_chans, ap, d_aid)) return rc;
+    if (int rc = aid_predict_enqueue(e, eph, n_eph, d_fix, d_vel, n_fix, n_chans, ap, d_aid, e->aid_predict_t)) return rc;
     if (sync) HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -2173,7 +2181,7 @@ extern "C" int gpsacq_aid_predict(gpsacq_engine* e, const gpsacq_ephemeris* eph,
     if (int rc = upload(e, e->d_nav_fix, fix, n_fix)) return rc;
     if (vel)
         if (int rc = upload(e, e->d_vel, vel, n_fix)) return rc;
-    if (int rc = aid_predict_enqueue(e, eph, n_eph, e->d_nav_fix, vel ? e->d_vel.p : nullptr, n_fix, n_chans, ap, e->d_aid)) return rc;
+    if (int rc = aid_predict_enqueue(e, eph, n_eph, e->d_nav_fix, vel ? e->d_vel.p : nullptr, n_fix, n_chans, ap, e->d_aid, e->aid_predict_t)) return rc;
     if (int rc = download(e, aid_out, e->d_aid, n)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
@@ -2185,7 +2193,7 @@ extern "C" int gpsacq_aided_search_device(gpsacq_engine* e, const void* d_bits, 
     gpsacq_aided_params sp;
     if (int rc = aided_check("gpsacq_aided_search", e, d_bits, n_bytes, stride, d_aid, d_peaks_in, n_tasks, params, d_aided, d_peaks_out, &sp)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
-    if (int rc = aided_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_aid, d_peaks_in, n_tasks, sp, d_aided, d_peaks_out, d_powers_out)) return rc;
+    if (int rc = aided_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_aid, d_peaks_in, n_tasks, sp, d_aided, d_peaks_out, d_powers_out, e->aided_t)) return rc;
     if (sync) HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -2209,7 +2217,7 @@ extern "C" int gpsacq_aided_search(gpsacq_engine* e, const uint8_t* bits, size_t
     if (int rc = upload(e, e->d_aid, aid, n_tasks)) return rc;
     if (int rc = aided_enqueue(e, e->d_refine_bits, n_bytes, stride, tasks ? e->d_refine_tasks.p : nullptr, e->d_aid,
                                peaks_in ? e->d_refine_peaks.p : nullptr, n_tasks, sp, e->d_aided, e->d_aided_peaks,
-                               powers_out ? e->d_aided_powers.p : nullptr))
+                               powers_out ? e->d_aided_powers.p : nullptr, e->aided_t))
         return rc;
     if (int rc = download(e, aided_out, e->d_aided, n_tasks)) return rc;
     if (int rc = download(e, peaks_out, e->d_aided_peaks, n_tasks)) return rc;
@@ -2230,8 +2238,8 @@ extern "C" int gpsacq_aided_peaks_device(gpsacq_engine* e, const gpsacq_ephemeri
     if (int rc = aided_check(who, e, d_bits, n_bytes, stride, d_aided, d_peaks_in, n_tasks, aided_par, d_aided, d_peaks_out, &sp)) return rc;
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = or_own(e, d_aid, e->d_aid, n_tasks)) return rc;
-    if (int rc = aid_predict_enqueue(e, eph, n_eph, d_fix, d_vel, n_fix, n_chans, ap, d_aid)) return rc;
-    if (int rc = aided_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_aid, d_peaks_in, n_tasks, sp, d_aided, d_peaks_out, nullptr)) return rc;
+    if (int rc = aid_predict_enqueue(e, eph, n_eph, d_fix, d_vel, n_fix, n_chans, ap, d_aid, e->aid_predict_t)) return rc;
+    if (int rc = aided_enqueue(e, d_bits, n_bytes, stride, d_tasks, d_aid, d_peaks_in, n_tasks, sp, d_aided, d_peaks_out, nullptr, e->aided_t)) return rc;
     if (sync) HIPCHK(hipStreamSynchronize(e->stream));
     return GPSACQ_OK;
 }
@@ -2242,6 +2250,130 @@ extern "C" int gpsacq_aided_last_ms(const gpsacq_engine* e, float* predict_ms, f
     HIPCHK(hipSetDevice(e->p.device));
     if (int rc = stage_ms(e->aid_predict_t, predict_ms)) return rc;
     return stage_ms(e->aided_t, search_ms);
+}
+
+// ---- aided acquisition on an 8-bit IQ capture (aided_iq_kernels.hip; sign mode: iq_kernels.hip, then k_aided) ---------------------
+extern "C" int gpsacq_aided_default_params_iq8(gpsacq_aided_params* p) {
+    if (int rc = gpsacq_aided_default_params(p)) return rc;
+    // the largest multi-bit ratio of 2304 measured draws on absent PRNs (2.9517) plus a quarter of its excess over 1: include/gpsacq.h
+    p->ratio_min = 3.44;
+    return GPSACQ_OK;
+}
+
+static int aided_iq_check(const char* who, const gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                          const void* aid, const void* peaks_in, size_t n_tasks, const gpsacq_aided_params* params, const void* aided,
+                          const void* peaks_out, bool device, IqSnap* s, gpsacq_aided_params* checked) {
+    if (!aided || !peaks_out || (peaks_in && peaks_in == peaks_out)) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (int rc = iq_snap_check(who, e, in, iq, n_samples, stride, aid, n_tasks, aided, device, s)) return rc;
+    if (!params) {  // the defaults of the path that runs: sign mode is gpsacq_aided_search's, byte for byte
+        if (int rc = s->sign ? gpsacq_aided_default_params(checked) : gpsacq_aided_default_params_iq8(checked)) return rc;
+    } else if (int rc = aided_params(who, params, checked)) {
+        return rc;
+    }
+    return aided_engine_check(who, e);
+}
+
+// a call of this section begins: no timer has run; sign mode converts the capture once
+static int aided_iq_begin(gpsacq_engine* e, IqSnap& s) {
+    e->aidiq_conv_t.done = e->aidiq_predict_t.done = e->aidiq_search_t.done = false;
+    if (!s.sign) return GPSACQ_OK;
+    return iq_snap_convert(e, s, e->aidiq_conv_t);
+}
+
+// k_aided_iq, or k_aided on sign mode's stream, timed; every argument has been checked
+static int aided_iq_enqueue(gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_aid, const void* d_peaks_in, size_t n_tasks,
+                            const gpsacq_aided_params& sp, void* d_aided, void* d_peaks_out, void* d_powers) {
+    if (s.sign) return aided_enqueue(e, s.d_bits, s.n_bytes, s.stride / 16, d_tasks, d_aid, d_peaks_in, n_tasks, sp, d_aided, d_peaks_out, d_powers, e->aidiq_search_t);
+    if (int rc = ensure_track_chips(e)) return rc;
+    AidedIqArgs a{};
+    iq_capture_args(e, s, d_tasks, d_peaks_in, n_tasks, a.c);
+    a.kmax = e->kmax;
+    a.aid = (const gpsacq_aid*)d_aid;
+    a.p = sp;
+    a.out = (gpsacq_aided*)d_aided;
+    a.peaks_out = (gpsacq_peak*)d_peaks_out;
+    a.powers = (unsigned long long*)d_powers;
+    if (int rc = e->aidiq_search_t.begin(e->stream)) return rc;
+    launch_aided_iq(a, e->stream);
+    if (int rc = e->aidiq_search_t.mark(1, e->stream)) return rc;
+    return e->aidiq_search_t.finish();
+}
+
+extern "C" int gpsacq_aided_search_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                              const void* d_tasks, const void* d_aid, const void* d_peaks_in, size_t n_tasks,
+                                              const gpsacq_aided_params* params, void* d_aided, void* d_peaks_out, void* d_powers_out, int sync) {
+    IqSnap s;
+    gpsacq_aided_params sp;
+    if (int rc = aided_iq_check("gpsacq_aided_search_iq8", e, in, d_iq, n_samples, stride, d_aid, d_peaks_in, n_tasks, params, d_aided, d_peaks_out, true, &s,
+                                &sp))
+        return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = aided_iq_begin(e, s)) return rc;
+    if (int rc = aided_iq_enqueue(e, s, d_tasks, d_aid, d_peaks_in, n_tasks, sp, d_aided, d_peaks_out, d_powers_out)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_search_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                                       const gpsacq_task* tasks, const gpsacq_aid* aid, const gpsacq_peak* peaks_in, size_t n_tasks,
+                                       const gpsacq_aided_params* params, gpsacq_aided* aided_out, gpsacq_peak* peaks_out, uint64_t* powers_out) {
+    IqSnap s;
+    gpsacq_aided_params sp;
+    if (int rc = aided_iq_check("gpsacq_aided_search_iq8", e, in, iq, n_samples, stride, aid, peaks_in, n_tasks, params, aided_out, peaks_out, false, &s, &sp))
+        return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_pow = n_tasks * (size_t)(2 * sp.dop_half + 1) * (size_t)(2 * sp.code_half + 1);
+    if (int rc = e->d_aided.grow(n_tasks, e->stream)) return rc;
+    if (int rc = e->d_aided_peaks.grow(n_tasks, e->stream)) return rc;
+    if (powers_out)
+        if (int rc = e->d_aided_powers.grow(n_pow, e->stream)) return rc;
+    if (int rc = e->d_iq.grow(2 * n_samples + 16, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * n_samples, hipMemcpyHostToDevice, e->stream));
+    s.d_iq = s.cap.d_src = e->d_iq;
+    if (tasks)
+        if (int rc = upload(e, e->d_refine_tasks, tasks, n_tasks)) return rc;
+    if (peaks_in)
+        if (int rc = upload(e, e->d_refine_peaks, peaks_in, n_tasks)) return rc;
+    if (int rc = upload(e, e->d_aid, aid, n_tasks)) return rc;
+    if (int rc = aided_iq_begin(e, s)) return rc;
+    if (int rc = aided_iq_enqueue(e, s, tasks ? e->d_refine_tasks.p : nullptr, e->d_aid, peaks_in ? e->d_refine_peaks.p : nullptr, n_tasks, sp, e->d_aided,
+                                  e->d_aided_peaks, powers_out ? e->d_aided_powers.p : nullptr))
+        return rc;
+    if (int rc = download(e, aided_out, e->d_aided, n_tasks)) return rc;
+    if (int rc = download(e, peaks_out, e->d_aided_peaks, n_tasks)) return rc;
+    if (int rc = download(e, (unsigned long long*)powers_out, e->d_aided_powers, n_pow)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_peaks_iq8_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel,
+                                             const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride, const void* d_tasks,
+                                             const void* d_peaks_in, size_t n_fix, int n_chans, const gpsacq_aid_params* aid_par,
+                                             const gpsacq_aided_params* aided_par, void* d_aid, void* d_aided, void* d_peaks_out, int sync) {
+    const char* who = "gpsacq_aided_peaks_iq8";
+    gpsacq_aid_params ap;
+    gpsacq_aided_params sp;
+    IqSnap s;
+    // d_aid may be NULL here (engine scratch), so the two checks are given d_aided where they test the prediction records for NULL
+    if (int rc = aid_predict_check(who, e, eph, n_eph, d_fix, n_fix, n_chans, aid_par, d_aided, &ap)) return rc;
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    if (int rc = aided_iq_check(who, e, in, d_iq, n_samples, stride, d_aided, d_peaks_in, n_tasks, aided_par, d_aided, d_peaks_out, true, &s, &sp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = or_own(e, d_aid, e->d_aid, n_tasks)) return rc;
+    if (int rc = aided_iq_begin(e, s)) return rc;
+    if (int rc = aid_predict_enqueue(e, eph, n_eph, d_fix, d_vel, n_fix, n_chans, ap, d_aid, e->aidiq_predict_t)) return rc;
+    if (int rc = aided_iq_enqueue(e, s, d_tasks, d_aid, d_peaks_in, n_tasks, sp, d_aided, d_peaks_out, nullptr)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* predict_ms, float* search_ms) {
+    if (!e || !e->aidiq_search_t.ran())
+        return fail(GPSACQ_ERR_ARG, "gpsacq_aided_iq8_last_ms: no gpsacq_aided_search_iq8 or gpsacq_aided_peaks_iq8 call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = stage_ms(e->aidiq_conv_t, convert_ms)) return rc;
+    if (int rc = stage_ms(e->aidiq_predict_t, predict_ms)) return rc;
+    return stage_ms(e->aidiq_search_t, search_ms);
 }
 
 // ---- coherent aided acquisition: 20 ms sums, bit edge and fine Doppler (aided_kernels.hip) ----------------------------------------

@@ -2035,8 +2035,8 @@ GPSACQ_API int gpsacq_doppler_last_ms(const gpsacq_engine* e, float* fine_dop_ms
  *
  * gpsacq_snap_quality* stays for 1-bit records (sign mode's included): its analytic floor is that of a +-1 stream.
  *
- * OUT OF SCOPE.  A noise floor for multi-bit records (gpsacq_snap_quality).  Multi-bit aided and coherent aided searches.
- * Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.
+ * OUT OF SCOPE.  A noise floor for multi-bit records (gpsacq_snap_quality).  A multi-bit coherent aided search (the non-coherent
+ * one is "Aided acquisition on an 8-bit IQ capture" below).  Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.
  */
 GPSACQ_API int gpsacq_refine_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride, const gpsacq_task* tasks,
                                  const gpsacq_peak* peaks, size_t n_tasks, const gpsacq_refine_params* params, gpsacq_fine* fine_out);
@@ -2204,8 +2204,8 @@ GPSACQ_API int gpsacq_snapshot_iq8_last_ms(const gpsacq_engine* e, float* conver
  * maximum of a packed key.  Every loop is bounded by kernel arguments, every LDS index by the host-checked limits
  * (spm <= 65535, W <= 127, K <= 8).
  *
- * OUT OF SCOPE.  8-bit IQ input, accumulated or re-aligned searches, fs above 10 MHz, multi-GPU, gps_test and gps_track.  The
- * correlator, the search and every existing record stay as they are.
+ * OUT OF SCOPE.  Accumulated or re-aligned searches, fs above 10 MHz, multi-GPU, gps_test and gps_track.  (8-bit IQ input:
+ * "Aided acquisition on an 8-bit IQ capture" below.)  The correlator, the search and every existing record stay as they are.
  */
 #define GPSACQ_AID_NO_FIX 1      /* the fix is not GPSACQ_FIX_OK: the record is this flag and zeros */
 #define GPSACQ_AID_NO_EPH 2      /* no valid ephemeris, or a state that is not finite: the record is this flag and zeros */
@@ -2393,6 +2393,126 @@ GPSACQ_API int gpsacq_aided_coh_peaks_device(gpsacq_engine* e, const gpsacq_ephe
  * events on its stream; waits for them); a kernel that call did not run reads 0.  Any pointer may be NULL.  The chain's prediction
  * is timed here alone: gpsacq_aided_last_ms keeps the times of the section above's own calls. */
 GPSACQ_API int gpsacq_aided_coh_last_ms(const gpsacq_engine* e, float* instant_ms, float* predict_ms, float* search_ms);
+
+/*
+ * ---- Aided acquisition on an 8-bit IQ capture: multi-bit windowed search ----------------------------------------------------------
+ *
+ * gpsacq_search_iq8 finds the strong satellites of an rtl-sdr / HackRF file, gpsacq_coarse_fix_fine_iq8_device fixes from them and
+ * gpsacq_aid_predict says where the others must be -- but gpsacq_aided_search, the one step whose purpose is to find satellites
+ * BELOW the search threshold, read a 1-bit real-IF stream: gpsacq_iq8_to_bits first, which drops one arm (3 dB) and puts the other
+ * through a limiter (about 2 dB, more beside strong satellites), exactly where every dB decides.  gpsacq_aided_search_iq8 goes back
+ * to the IQ bytes themselves.  The record is gpsacq_aided as it is, and its peaks drop into gpsacq_refine_iq8,
+ * gpsacq_fine_doppler_iq8 and everything behind them unchanged.  THE MODEL; the kernel (csrc/aided_iq_kernels.hip) and the
+ * reference of the tests (tests/aided_iq_ref.py) are both written from this text.  "Step n" is step n of "Aided acquisition" B,
+ * WINDOWED SEARCH, which holds word for word except where this text changes it.
+ *
+ * INPUTS.  `in`, iq[2 * n_samples], n_samples and stride exactly as for gpsacq_refine_iq8: stride in BYTES, a multiple of 16,
+ * 80000 <= stride <= 2^31; the device form takes a 16-byte-aligned device pointer.  tasks[n_tasks] (NULL: the reference schedule),
+ * aid[n_tasks], peaks_in[n_tasks] (optional), gpsacq_aided_params and powers_out as for gpsacq_aided_search; peaks_in are the peaks of
+ * gpsacq_search_iq8 with the same `in`.
+ *
+ * in->multibit != 0 (GPSACQ_SAMPLES_REAL and GPSACQ_SAMPLES_COMPLEX alike): THE MULTI-BIT PATH.
+ *   SAMPLE.  v_i, v_q are the SAMPLE of "Snapshot chain on an 8-bit IQ capture": v = byte - off - dc, off = 128 for GPSACQ_IQ_U8 and 0
+ *     for GPSACQ_IQ_S8, dc = nearbyint(mean) (ties to even) when remove_dc, else 0; |v| <= 256.  No floating-point mixer.
+ *   WINDOW.  o = block * (stride / 2) against n_samples; segments, GPSACQ_AIDED_SHORT and GPSACQ_AIDED_FEW as that section's WINDOW
+ *     has them, with this call's blocks and min_segments.  Nothing at or beyond byte 2 * n_samples is read.
+ *   Step 1 (KEPT) is unchanged.  Step 2 (NO_AID) is unchanged, with "o at or beyond sample n_samples" as the range test.
+ *   Step 3 (HYPOTHESES) is unchanged except for the carrier.  For Doppler index d, with lo_dop_d, ca_dop_d and ca_rate_d from step
+ *     1 of "Fine code phases" for lo_shift_d:
+ *         f_d = lo_dop_d - mix_hz + fc      (GPSACQ_SAMPLES_COMPLEX: f_d = lo_dop_d - mix_hz), left to right,
+ *         lo_rate_d = (uint32)(int64)llround(f_d / fs * 2^32)             (round half away from zero; two's complement for f < 0)
+ *     d is VALID when |lo_shift_d| lies on the engine's grid, |f_d| < fs / 2, 1.023e6 + ca_dop_d lies in [0, fs) and ca_rate_d != 0.
+ *     base, P0(h, d), ca_shift_h, the ONE chip stream per (segment, d) and the carrier phase j * lo_rate_d (mod 2^32) counted from
+ *     the window's first sample stay word for word.
+ *   Step 4 (SUMS).  With C = 1 - 2 (cos bit), S = 1 - 2 (sin bit) and h_P = 1 - 2 chip as in that section's SUMS, per segment
+ *         I_P = sum h_P (v_i C - v_q S),   Q_P = sum h_P (v_i S + v_q C)
+ *     and power(h, d) = sum over the segments of I_P^2 + Q_P^2, uint64.  |I_P|, |Q_P| <= 512 spm < 2^25, a segment adds less than
+ *     2^51 and there are fewer than 2^12 segments: nothing overflows.  For base + h < spm, power(h, d) is bit for bit the `prompt`
+ *     field gpsacq_refine_iq8 returns for a peak (ca_shift_h, lo_shift_d) with the same `in` and blocks (a test uses it); across
+ *     the wrap the two differ by the code Doppler's creep over one millisecond, as step 4 says of gpsacq_refine.
+ *   Step 5 (RECORD), THE MEASURED FLOOR.  A +-1 replica uncorrelated with the samples leaves
+ *         E[I_P^2 + Q_P^2] = 2 * sum (v_i^2 + v_q^2)     over the segment's samples
+ *     -- exactly: C^2 = S^2 = 1, and the cross terms v_i v_q C S cancel between I and Q.  So
+ *         floor = 2 * (sum over the samples of the window's segments of v_i^2 + v_q^2),
+ *     an exact integer below 2^46 (2 * 2^17 per sample, fewer than 2^12 segments of at most 65535 samples).  For a +-1 real stream it
+ *     is the 2 * spm * segments of gpsacq_aided_search: ratio stays on the same scale, 1 = the floor.  best <= spm * floor (Cauchy-
+ *     Schwarz), below 2^62.  total is the sum mod 2^64; only a capture on the rails, correlated with every replica alike, could
+ *     bring it near 2^64 (255 hypotheses * 9 grid points * 2^62 would need every one of them at the bound).
+ *     ratio = (double)best / (double)floor, 0.0 where floor == 0.  The flags, the key (power, -d, -h), the output peak (step 6) and
+ *     powers_out (step 7) are unchanged.
+ *
+ * in->multibit == GPSACQ_SAMPLES_SIGN: the capture is converted once per call into engine scratch by the path gpsacq_refine_iq8
+ * uses, and k_aided runs on it with n_bytes = ceil(n_samples / 8) and stride / 16: the result is byte for byte
+ * gpsacq_iq8_to_bits_device followed by gpsacq_aided_search_device.
+ *
+ * DEFAULT RATIO_MIN.  gpsacq_aided_default_params_iq8 (host only) sets gpsacq_aided_default_params' values with ratio_min measured
+ * for the multi-bit path; a NULL params of this section's calls means these in multi-bit mode and gpsacq_aided_default_params' in
+ * sign mode.  Without the limiter the strong satellites'
+ * cross-correlation sits differently against the floor, and 1.922 does not transfer.  Measured (tools/aided_floor.py --iq8, on
+ * the CPU with tests/aided_iq_ref.py): the scene of tools/snapshot_bench.py --iq8 (eight satellites at amplitude 0.2, noise sigma 1,
+ * fs = 5.456 MHz, IF 0.4 MHz, scale 16, int8, the mean not removed) made with tests/gen_ref.py's 8-bit IQ generator and searched for
+ * its 24 ABSENT PRNs with the defaults, 2304 draws of (window start, lo_center, PRN, ca_center), 99 hypotheses each: the largest
+ * ratio was 2.9517 (median 1.7357, 99.9 % below 2.6363).  The default is that plus a quarter of its excess over 1: 2.9517 + 1.9517 / 4 =
+ * 3.44.  That is far above the sign path's 1.7376, and it is not noise (the same capture without satellites read a median of 1.22 and at
+ * most 1.35 over 48 draws): it is the C/A cross-correlation of the eight satellites at amplitude 0.2, which keeps both arms and passes
+ * no limiter here exactly as the signal sought does -- some 5 dB more of either against the same floor.  It
+ * belongs to 16 blocks, W = 16, K = 1 and to sign mode not at all: sign mode's callers take gpsacq_aided_default_params' 1.922.
+ * WHAT TO EXPECT.  Measured on the CPU (tests/test_aided_iq.py: 16 blocks, five satellites at 0.2 with Dopplers spread evenly over
+ * the range beside the weak one, the same capture searched both ways, three captures per amplitude): amplitude 0.03 reads ratio 2.67
+ * to 3.07 where the sign path reads 1.58 to 1.70, 0.04 reads 3.83 to 4.40 against 1.96 to 2.03, 0.05 reads 5.45 to 6.09 against 2.44 to
+ * 2.49.  At 0.04 the excess over 1 is 2.95, 3.09 and 3.42 times the sign path's: the median gain is 3.09, 4.9 dB -- the arm and the
+ * limiter.  The two absent PRNs read 1.39 to 2.02 where the sign path reads 1.23 to 1.43, and the threshold rose with them: this
+ * default detects from about amplitude 0.035, the sign path's 1.922 from about 0.039 (interpolated on ratio - 1 ~ amplitude^2).  So in
+ * this scene most of the 4.9 dB go into a threshold that eight strong satellites set; a caller with fewer or weaker ones beside the
+ * signal measures a lower one (tools/aided_floor.py --iq8) and keeps more of it.  Measured on an MI355X (tools/snapshot_bench.py --iq8
+ * --aided, 1024 blocks, eight satellites at 0.2, two weak ones and two absent PRNs per block, both searches on the same tasks in the
+ * same run, HIP events, shader clock not read): at amplitude 0.05 the multi-bit search detects 1815 of the 1815 weak tasks the
+ * plain search had missed and the sign path 1811, median ratios 5.60 and 2.51; at 0.04 it detects 1986 of 2023 where the sign path
+ * detects 1486, median ratios 4.05 and 2.02; every detection at the true code phase, none in 2047 absent tasks either way (largest
+ * ratios 2.71 and 1.74).  k_aided_iq 40.98 ms for 3862 tasks of 99 hypotheses beside 6.54 ms for the conversion and k_aided (6.3
+ * times), and beside the 150 ms that one k_refine_iq group walk per hypothesis would take (9.93 ms for 8426 hits of three replicas
+ * in the same run).
+ *
+ * THE CHAIN.  gpsacq_aided_peaks_iq8_device is gpsacq_aided_peaks_device with (in, d_iq, n_samples) for (d_bits, n_bytes):
+ * k_aid_predict, then the search, one stream, no host copy in between; d_aid may be NULL (engine scratch).
+ *
+ * gpsacq_aided_search_iq8: host pointers, returns after completion.  The _device forms: iq, tasks, aid, peaks and the records are
+ * device pointers, `in`, eph and the params stay host pointers; work on the engine's stream, sync != 0 waits; host and device form
+ * agree byte for byte.  peaks_out must not be peaks_in.  Argument errors are those of gpsacq_aided_search plus those
+ * gpsacq_refine_iq8 adds -- in == NULL, a format or multibit value that gpsacq_search_iq8 refuses, a mean beyond +-128 where it is
+ * removed, a stride outside the bounds above, a misaligned device pointer: GPSACQ_ERR_ARG, nothing launched and nothing written.
+ * GPSACQ_ERR_UNSUPPORTED as gpsacq_aided_search.
+ * Kernel (csrc/aided_iq_kernels.hip).  k_aided_iq: one workgroup of four wave64 per task; a wave owns whole segments.  The
+ * hypotheses of one (segment, d) share one carrier-wiped series a_j = (v_i C - v_q S, v_i S + v_q C) and one chip stream s', and
+ * summation by parts turns sum_j s'[j + h] a_j over a chunk of n samples into
+ *     R(h) = s'[M] A[n] - sum over the chip transitions m of the stream of (s'[m] - s'[m - 1]) A[m - h],      M = n + 2 W - 1,
+ * with A the prefix sums of a -- exactly, in integers, so the model above does not see it.  Per chunk of 1024 samples the wave
+ * writes A into LDS (16-byte groups, the mean taken off per sample, a wave scan) and compacts the stream's transitions into a list
+ * (ballot and popcount); lane h then reads one int2 of A per transition, neighbouring lanes neighbouring entries: about 1040 reads
+ * per segment at 5.456 MHz where the direct sum has 5456 multiply-adds per hypothesis.  The lane squares its own I and Q into its
+ * own uint64; the four waves' sums meet in LDS once per d; the best hypothesis is the maximum of the pair (power, 31 - d, 255 - h).
+ * The floor is summed once per segment from the same bytes.  No atomics, no float before the ratio.  Every loop is bounded by
+ * kernel arguments, every LDS index by the host-checked limits (spm <= 65535, W <= 127, K <= 8).  DESIGN.md 8.9 has the rest.
+ *
+ * OUT OF SCOPE.  A multi-bit coherent aided search.  The measured floor for gpsacq_snap_quality on gpsacq_refine_iq8 records (the
+ * floor law above is the one it would use).  Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.
+ */
+GPSACQ_API int gpsacq_aided_default_params_iq8(gpsacq_aided_params* p);   /* host only */
+GPSACQ_API int gpsacq_aided_search_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                                       const gpsacq_task* tasks, const gpsacq_aid* aid, const gpsacq_peak* peaks_in /* or NULL */, size_t n_tasks,
+                                       const gpsacq_aided_params* params, gpsacq_aided* aided_out, gpsacq_peak* peaks_out,
+                                       uint64_t* powers_out /* [n_tasks][2K + 1][2W + 1] or NULL */);
+GPSACQ_API int gpsacq_aided_search_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                              const void* d_tasks, const void* d_aid, const void* d_peaks_in, size_t n_tasks,
+                                              const gpsacq_aided_params* params, void* d_aided, void* d_peaks_out, void* d_powers_out, int sync);
+GPSACQ_API int gpsacq_aided_peaks_iq8_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel,
+                                             const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride, const void* d_tasks,
+                                             const void* d_peaks_in, size_t n_fix, int n_chans, const gpsacq_aid_params* aid_params,
+                                             const gpsacq_aided_params* aided_params, void* d_aid, void* d_aided, void* d_peaks_out, int sync);
+/* device time of the last call of this section on this engine, milliseconds (HIP events on its stream; waits for them): the 8-bit ->
+ * 1-bit conversion (sign mode), k_aid_predict (the chain) and the search (k_aided_iq, in sign mode k_aided).  A kernel that the last
+ * call did not run reads 0.  Any pointer may be NULL. */
+GPSACQ_API int gpsacq_aided_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* predict_ms, float* search_ms);
 
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);

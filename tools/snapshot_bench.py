@@ -15,6 +15,7 @@ is worth at 5.456 MHz.
     python tools/snapshot_bench.py [--blocks 2048] [--reps 5] [--refine [--refine-blocks 16]] [--cold] [--aided [--weak-amplitude 0.05]]
                                    [--aided-coh [--weak-amplitude 0.03]] [--raim [--fault-share F] [--sigma-m S]] [--quality]
     python tools/snapshot_bench.py --iq8 [--blocks 2048] [--reps 5] [--refine-blocks 16] [--amplitude 0.2] [--if-hz 400000]
+                                   [--aided [--weak-amplitude 0.05]]
 
 --refine: the capture is made K - 1 blocks longer (K = --refine-blocks) so that every searched block has its whole window, and
 each repetition also runs gpsacq_coarse_fix_fine_device on the same capture, tasks and peaks: k_refine (the fine code phases of
@@ -76,6 +77,16 @@ refine_iq_ms and fine_dop_iq_ms beside convert_ms + refine_ms and convert_ms + f
 events) and search_ms of the same run; the code-phase error of both paths against the generator's law (rms and worst over the true
 hits both have); the fine Dopplers' error; the position error (median, worst) of the blocks both fixed; and the bytes a hit reads
 over the kernel's time.  The shader clock is not read.
+
+--iq8 --aided: the --aided scene (eight satellites at --amplitude, two at --weak-amplitude, two absent PRNs per block) written as ONE
+8-bit IQ capture ("Aided acquisition on an 8-bit IQ capture" of include/gpsacq.h): searched in multi-bit mode, fixed from the
+strong ones (gpsacq_coarse_fix_fine_iq8_device, k_refine_iq timed), predicted, and then gpsacq_aided_peaks_iq8_device BOTH ways on the
+same tasks in the same run: multi-bit (k_aided_iq, the defaults of gpsacq_aided_default_params_iq8) and sign mode (the conversion,
+then k_aided with gpsacq_aided_default_params).  The multi-bit detections are refined with gpsacq_refine_iq8 and fixed again.  The
+line carries aided_iq_ms beside convert_ms + aided_sign_ms and refine_iq_ms (best of --reps, HIP events; the shader clock is not
+read), what one group walk per hypothesis would cost (tasks searched x hypotheses x refine_iq_ms / (3 x hits)), the weak satellites
+detected and at the true code phase, the false detections and ratios on the absent tasks both ways, and the position error of the
+same blocks with and without the weak pair.
 """
 import argparse
 import json
@@ -194,6 +205,127 @@ def main_iq8(a):
     print(json.dumps(res))
 
 
+def main_iq8_aided(a):
+    """--iq8 --aided: the --aided scene as ONE 8-bit IQ capture, the aided search both ways on the same tasks in the same run"""
+    import numpy as np
+    import torch
+
+    import gpsacq
+    from coarse_helpers import block_times, priors, synth_sats
+    from nav_helpers import geometry, to_records
+
+    geo = geometry("north")
+    sel = geo["subsets"][8]
+    rest = [k for k in range(len(geo["ephs"])) if k not in sel]
+    ephs = to_records([geo["ephs"][k] for k in list(sel) + rest])
+    spb = gpsacq.BLOCK_BYTES * 8
+    stride = 2 * spb
+    mid = a.blocks // 2
+    ref_ms, ref_frac = geo["ref_ms"] + 4321, 0.6180e-3  # the receive time of the first sample of block `mid`
+    strong, _ = synth_sats(geo, sel, ref_ms, ref_frac, mid * spb, FS, a.amplitude)
+    more, _ = synth_sats(geo, rest, ref_ms, ref_frac, mid * spb, FS, a.weak_amplitude)
+    gen_sats, sats = strong + more[:2], strong + more  # channels 8, 9: weak; 10, 11: absent
+    blk_ms, blk_frac = block_times(ref_ms, ref_frac - mid * spb / FS, a.blocks, spb, FS)
+    prior = priors(geo, blk_ms, seed=3, km=30.0, secs=30.0)
+    tasks = np.array([(b, s[0] - 1) for b in range(a.blocks) for s in sats], dtype=np.int32)
+    n_samples, n_tasks, m = (a.blocks + a.refine_blocks - 1) * spb, len(tasks), len(sats)
+    modes = ("multibit", "sign")
+    sp = {"multibit": gpsacq.aided_params_iq8(blocks=a.refine_blocks), "sign": gpsacq.aided_params(blocks=a.refine_blocks)}
+    rp = gpsacq.refine_params(blocks=a.refine_blocks)
+    rp_a = gpsacq.refine_params(blocks=a.refine_blocks, snr_min=float(sp["multibit"]["ratio_min"][0]))
+    with gpsacq.Engine(FC, FS, 5000.0, device=0) as eng:
+        dev = lambda arr: torch.from_numpy(arr.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+        zeros = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, device="cuda:0")
+        d_iq, d_tasks, d_prior = zeros(2 * n_samples), dev(tasks), dev(prior)
+        d_peaks, d_fine = zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize), zeros(n_tasks * gpsacq.FINE_DTYPE.itemsize)
+        d_fix_f, d_info_f = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
+        d_fix_a, d_info_a = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
+        buf = {k: dict(aided=zeros(n_tasks * gpsacq.AIDED_DTYPE.itemsize), peaks=zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize)) for k in modes}
+        inp = {"multibit": eng.iq8_input(signed=True, remove_dc=False, mix_hz=FC - a.if_hz, multibit=1),
+               "sign": eng.iq8_input(signed=True, remove_dc=False, mix_hz=FC - a.if_hz, multibit=0)}  # GPSACQ_SAMPLES_REAL, GPSACQ_SAMPLES_SIGN
+        torch.cuda.synchronize()
+        eng.generate_iq8_device(d_iq.data_ptr(), n_samples, gen_sats, if_hz=a.if_hz, scale=16.0, signed=True, noise_sigma=1.0, seed=77)
+        search_best = refine_best = refine_a_best = float("inf")
+        best = {k: (float("inf"), 0.0, 0.0) for k in modes}  # (convert + search, convert, search)
+        predict_best = float("inf")
+        for _ in range(1 + a.reps):  # the first call also allocates the engine's scratch
+            eng.search_iq8_device(d_iq.data_ptr(), inp["multibit"], a.blocks, d_peaks.data_ptr(), stride=stride, d_tasks_ptr=d_tasks.data_ptr(),
+                                  n_tasks=n_tasks, sync=True)
+            search_best = min(search_best, eng.last_timing()["ms_total"])
+            eng.coarse_fix_fine_iq8_device(ephs, inp["multibit"], d_iq.data_ptr(), n_samples, d_tasks.data_ptr(), d_peaks.data_ptr(), a.blocks, m,
+                                           d_prior.data_ptr(), d_fix_f.data_ptr(), d_info_f.data_ptr(), d_fine_ptr=d_fine.data_ptr(), stride=stride,
+                                           refine_params=rp, sync=True)
+            refine_best = min(refine_best, eng.snapshot_iq8_last_ms()[1])
+            # the receive instant of a coarse-time fix, good below a sample (include/gpsacq.h, "Aided acquisition" A)
+            fx = d_fix_f.cpu().numpy().view(gpsacq.FIX_DTYPE).copy()
+            nf = d_info_f.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
+            t = np.rint(nf["coarse_s"] * 1e3) * 1e-3 - nf["bias_m"] / 2.99792458e8
+            k = np.floor(t * 1e3)
+            fx["rx_ms"] = np.where(fx["status"] == 0, (prior["rx_ms"].astype(np.int64) + k.astype(np.int64)) % 604800000, 0)
+            fx["rx_frac"] = np.where(fx["status"] == 0, t - k * 1e-3, 0.0)
+            d_fix_aid = dev(fx)
+            for md in modes:
+                eng.aided_peaks_iq8_device(ephs, d_fix_aid.data_ptr(), inp[md], d_iq.data_ptr(), n_samples, d_tasks.data_ptr(), a.blocks, m,
+                                           buf[md]["aided"].data_ptr(), buf[md]["peaks"].data_ptr(), d_peaks_in_ptr=d_peaks.data_ptr(), stride=stride,
+                                           aid_params=gpsacq.aid_params(-90.0), params=sp[md], sync=True)
+                c, p, s = eng.aided_iq8_last_ms()
+                best[md] = min(best[md], (c + s, c, s))
+                predict_best = min(predict_best, p)
+            eng.coarse_fix_fine_iq8_device(ephs, inp["multibit"], d_iq.data_ptr(), n_samples, d_tasks.data_ptr(), buf["multibit"]["peaks"].data_ptr(),
+                                           a.blocks, m, d_prior.data_ptr(), d_fix_a.data_ptr(), d_info_a.data_ptr(), stride=stride, refine_params=rp_a,
+                                           sync=True)
+            refine_a_best = min(refine_a_best, eng.snapshot_iq8_last_ms()[1])
+        peaks = d_peaks.cpu().numpy().view(gpsacq.PEAK_DTYPE).reshape(a.blocks, m)
+        fine = d_fine.cpu().numpy().view(gpsacq.FINE_DTYPE).reshape(a.blocks, m)
+        fix_f, info_f = d_fix_f.cpu().numpy().view(gpsacq.FIX_DTYPE), d_info_f.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
+        fix_a, info_a = d_fix_a.cpu().numpy().view(gpsacq.FIX_DTYPE), d_info_a.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
+        out = {k: dict(aided=buf[k]["aided"].cpu().numpy().view(gpsacq.AIDED_DTYPE).reshape(a.blocks, m),
+                       peaks=buf[k]["peaks"].cpu().numpy().view(gpsacq.PEAK_DTYPE).reshape(a.blocks, m)) for k in modes}
+        name = eng.device_name
+    L1, CPS = 1575.42e6, 1.023e6
+    m0 = np.arange(a.blocks, dtype=np.float64)[:, None] * spb
+    cps = np.array([CPS * (1.0 + s[2] / L1) / FS for s in sats])[None, :]
+    want = ((m0 + np.array([s[3] for s in sats])[None, :]) * cps % 1023.0) / CPS
+    wrap = lambda t: (t + 0.5e-3) % 1e-3 - 0.5e-3
+    weak, absent = slice(8, 10), slice(10, 12)
+    r2, r4 = (lambda v: round(float(v), 2)), (lambda v: round(float(v), 4))
+    n_hits = int((peaks["snr"] >= float(rp["snr_min"][0])).sum())  # the windows k_refine_iq walked, three replicas each
+    searched = (out["multibit"]["aided"]["flags"] & (gpsacq.AIDED_KEPT | gpsacq.AIDED_NO_AID)) == 0
+    n_hyp = int(sp["multibit"]["code_half"][0] * 2 + 1) * int(sp["multibit"]["dop_half"][0] * 2 + 1)
+    bound = float(searched.sum()) * n_hyp * refine_best / (3.0 * max(n_hits, 1))
+    ok_f = (fix_f["status"] == 0) & (info_f["flags"] == 0)
+    ok_a = (fix_a["status"] == 0) & (info_a["flags"] == 0) & ok_f  # the same blocks with and without the weak pair
+    off_f = np.linalg.norm(np.stack([fix_f[c] for c in "xyz"], 1) - geo["rx"], axis=1)
+    off_a = np.linalg.norm(np.stack([fix_a[c] for c in "xyz"], 1) - geo["rx"], axis=1)
+    res = {"bench": "snapshot_iq8_aided", "device": name, "blocks": a.blocks, "sats": m, "tasks": n_tasks, "amplitude": a.amplitude,
+           "weak_amplitude": a.weak_amplitude, "if_hz": a.if_hz, "scale": 16.0, "window_blocks": a.refine_blocks, "shader_clock_read": False,
+           "search_ms": r4(search_best), "refine_iq_ms": r4(refine_best), "refine_iq_hits": n_hits, "refine_iq_merged_ms": r4(refine_a_best),
+           "aid_predict_ms": r4(predict_best), "aided_iq_ms": r4(best["multibit"][2]), "convert_ms": r4(best["sign"][1]),
+           "aided_sign_ms": r4(best["sign"][2]), "convert_plus_aided_sign_ms": r4(best["sign"][0]),
+           "aided_iq_over_sign_path": r4(best["multibit"][2] / best["sign"][0]), "aided_tasks_searched": int(searched.sum()),
+           "hypotheses_per_task": n_hyp, "per_hypothesis_walk_bound_ms": r4(bound), "aided_iq_below_bound": bool(best["multibit"][2] < bound),
+           "aided_iq_ns_per_hypothesis": r4(best["multibit"][2] * 1e6 / (float(searched.sum()) * n_hyp)),
+           "refine_iq_ns_per_replica": r4(refine_best * 1e6 / (3.0 * max(n_hits, 1))),
+           "weak_search_hits": int((peaks["snr"][:, weak] >= gpsacq.THRESHOLD).sum()), "weak_tasks": int(2 * a.blocks)}
+    for k in modes:
+        ad, pk = out[k]["aided"], out[k]["peaks"]
+        srch = (ad["flags"] & (gpsacq.AIDED_KEPT | gpsacq.AIDED_NO_AID)) == 0
+        found = srch & ((ad["flags"] & (gpsacq.AIDED_FEW | gpsacq.AIDED_NO_POWER | gpsacq.AIDED_BELOW)) == 0)
+        true_w = found[:, weak] & (np.abs(wrap(pk["ca_shift"] / FS - want)[:, weak]) * FS <= 1.5)
+        res.update({"ratio_min_%s" % k: float(sp[k]["ratio_min"][0]), "weak_detected_%s" % k: int(found[:, weak].sum()),
+                    "weak_detected_at_the_true_phase_%s" % k: int(true_w.sum()),
+                    "weak_ratio_median_%s" % k: r4(np.median(ad["ratio"][:, weak][srch[:, weak]])) if srch[:, weak].any() else None,
+                    "absent_tasks_%s" % k: int(srch[:, absent].sum()), "absent_false_detections_%s" % k: int(found[:, absent].sum()),
+                    "absent_ratio_median_%s" % k: r4(np.median(ad["ratio"][:, absent][srch[:, absent]])) if srch[:, absent].any() else None,
+                    "absent_ratio_max_%s" % k: r4(ad["ratio"][:, absent].max())})
+    res.update({"blocks_compared": int(ok_a.sum()), "sats_used_median_with_weak": float(np.median(fix_a["n_used"][ok_a])) if ok_a.any() else None,
+                "position_error_median_with_weak_m": r2(np.median(off_a[ok_a])) if ok_a.any() else None,
+                "position_error_worst_with_weak_m": r2(off_a[ok_a].max()) if ok_a.any() else None,
+                "position_error_median_without_weak_m": r2(np.median(off_f[ok_a])) if ok_a.any() else None,
+                "position_error_worst_without_weak_m": r2(off_f[ok_a].max()) if ok_a.any() else None})
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=2048)
@@ -212,6 +344,10 @@ def main():
     ap.add_argument("--amplitude", type=float, default=0.2, help="amplitude of the eight satellites of --iq8")
     ap.add_argument("--if-hz", type=float, default=0.4e6, help="residual IF of the capture of --iq8")
     a = ap.parse_args()
+    if a.iq8 and a.aided:
+        if a.weak_amplitude is None:
+            a.weak_amplitude = 0.05
+        return main_iq8_aided(a)
     if a.iq8:
         return main_iq8(a)
     a.aided = a.aided or a.aided_coh or a.quality
