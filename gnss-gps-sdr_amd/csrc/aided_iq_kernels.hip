@@ -7,8 +7,9 @@
 // over a chunk of n samples that is
 //     R(h) = s'[M] A[n] - sum over m in [1, M] of D[m] A[m - h],      M = n + 2 W - 1,
 // with A[k] the inclusive prefix sums of a (A[k] = 0 for k <= 0, A[k] = A[n] for k >= n) and D[m] = s'[m] - s'[m - 1], which is 0
-// except at the chip TRANSITIONS of the stream (0.19 per sample at 5.456 MHz).  Exact, in integers.  Per (segment, d) and chunk of
-// AIDED_IQ_CHUNK samples (counted from the 8-sample group the segment starts in; samples of the chunk before or after the
+// except at the chip TRANSITIONS of the stream (0.19 per sample at 5.456 MHz).  Exact, in integers.  The walk itself is
+// aided_iq_walk.hpp's segment_sums_by_parts, which k_aided_coh_iq shares, here at four passes on AidedIqGeometry.  Per (segment, d)
+// and chunk of AIDED_IQ_CHUNK samples (counted from the 8-sample group the segment starts in; samples of the chunk before or after the
 // segment count as a = 0):
 //   WIPE.  Lane l takes the 16-byte groups l, l + 64 of the chunk (iq_groups.hpp: load_group and the flip word): per sample the
 //     mean is taken off, the carrier signs come from ph = j lo_rate, the eight a's are summed up inside the lane, a wave scan
@@ -34,21 +35,11 @@
 #include <stdint.h>
 
 #include "aided_iq_launch.hpp"
-#include "capture_groups.hpp"
+#include "aided_iq_walk.hpp"
 
 namespace acq {
 
 namespace {
-typedef uint16_t __attribute__((may_alias)) list_u16;  // the list is written entry by entry and read four entries at a time
-
-// the lanes of ONE wave hand LDS to each other: the wave's LDS operations execute in program order, so all that is needed is
-// that the compiler keeps them in it
-__device__ __forceinline__ void wave_sync_iq() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // the window of Doppler hypothesis lo_shift: the IQ section's steps 1 to 3 on a peak that is a hit by itself
 __device__ __forceinline__ Window window_at_iq(const AidedIqArgs& a, size_t t, int64_t lo_shift) {
     Window w = {false, 0, 0, 0, 0, 0, 0, 0};
@@ -105,15 +96,12 @@ __global__ __launch_bounds__(64 * AIDED_IQ_WAVES) void k_aided_iq(AidedIqArgs a)
     }
     chips_to_lds(a.c.chips, win.prn, s_chips);
     int2* const A = s_a[wv];
-    list_u16* const list = reinterpret_cast<list_u16*>(s_list[wv]);
     for (int i = lane; i <= AIDED_IQ_PAD; i += 64) A[i] = make_int2(0, 0);  // A[k] = 0 for k <= 0: never written again
     __syncthreads();
 
     // 3. hypotheses, 4. sums
     const uint64_t o = win.o, spm = (uint64_t)a.c.spm, segments = win.segments;  // o is a multiple of 8: stride is one of 16
     const uint32_t base = (uint32_t)(((aid.ca_center - W) % a.c.spm + a.c.spm) % a.c.spm);
-    const size_t iq_bytes = 2 * a.c.n_samples;
-    const int dc_i = a.c.dc_i, dc_q = a.c.dc_q;
     uint64_t total = 0, best = 0, floor_sum = 0;  // of hypothesis h = threadIdx.x; floor_sum of the lane's samples
     uint32_t tag = 0;
     for (int d = 0; d < n_dop; ++d) {
@@ -127,102 +115,9 @@ __global__ __launch_bounds__(64 * AIDED_IQ_WAVES) void k_aided_iq(AidedIqArgs a)
         uint64_t acc[AIDED_PASSES] = {0, 0, 0, 0};
         for (uint64_t s = wv; s < segments; s += AIDED_IQ_WAVES) {
             const uint64_t a0 = o + s * spm, a1 = a0 + spm;  // the segment's samples [a0, a1) of the capture
-            uint32_t Ri[AIDED_PASSES] = {0, 0, 0, 0}, Rq[AIDED_PASSES] = {0, 0, 0, 0};
-            uint32_t fl = 0;  // < 2^27: at most 1032 samples of a lane in a segment, 2^17 each
-            for (uint64_t cs = a0 & ~7ull; cs < a1; cs += AIDED_IQ_CHUNK) {
-                const int n = a1 - cs < (uint64_t)AIDED_IQ_CHUNK ? (int)((a1 - cs + 7) & ~7ull) : AIDED_IQ_CHUNK;  // a multiple of 8
-                const int M = n + 2 * W - 1;
-                // WIPE
-                uint32_t ci = 0, cq = 0;  // A of the groups before, the same in every lane
-                for (int g0 = 0; g0 < n / 8; g0 += 64) {
-                    const int gl = g0 + lane;
-                    const bool mine = gl < n / 8;
-                    const uint64_t gs = cs + 8ull * (uint64_t)gl;
-                    uint32_t x[4] = {0, 0, 0, 0};
-                    if (mine) {
-                        const uint4 raw = load_group(a.c.iq, iq_bytes, gs >> 3);
-                        x[0] = raw.x ^ a.c.flip, x[1] = raw.y ^ a.c.flip, x[2] = raw.z ^ a.c.flip, x[3] = raw.w ^ a.c.flip;
-                    }
-                    const uint32_t b_lo = gs < a0 ? (uint32_t)(a0 - gs) : 0u;                       // 0 .. 7
-                    const uint32_t b_hi = !mine || gs >= a1 ? 0u : gs + 8 > a1 ? (uint32_t)(a1 - gs) : 8u;  // 0 .. 8
-                    uint32_t ph = (uint32_t)(gs - o) * lo_rate;
-                    uint32_t pi[8], pq[8], si = 0, sq = 0;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const uint32_t w = x[k >> 1] >> (16 * (k & 1));
-                        const bool keep = (uint32_t)k >= b_lo && (uint32_t)k < b_hi;
-                        const int vi = keep ? (int)(int8_t)(w & 0xffu) - dc_i : 0, vq = keep ? (int)(int8_t)((w >> 8) & 0xffu) - dc_q : 0;
-                        const bool cneg = ((ph >> 31) ^ (ph >> 30)) & 1u, sneg = (~ph >> 31) & 1u;  // the carrier bits of THE CHANNEL MODEL
-                        const int vic = cneg ? -vi : vi, vqc = cneg ? -vq : vq, vis = sneg ? -vi : vi, vqs = sneg ? -vq : vq;
-                        si += (uint32_t)(vic - vqs);  // v_i C - v_q S
-                        sq += (uint32_t)(vis + vqc);  // v_i S + v_q C
-                        pi[k] = si, pq[k] = sq;
-                        if (with_floor) fl += (uint32_t)(vi * vi + vq * vq);
-                        ph += lo_rate;
-                    }
-                    // the lanes' totals, summed up over the wave
-                    uint32_t ti = si, tq = sq;
-#pragma unroll
-                    for (int m = 1; m < 64; m <<= 1) {
-                        const uint32_t ui = (uint32_t)__shfl_up((int)ti, m, 64), uq = (uint32_t)__shfl_up((int)tq, m, 64);
-                        if (lane >= m) ti += ui, tq += uq;
-                    }
-                    const uint32_t bi = ci + ti - si, bq = cq + tq - sq;  // A before the lane's group
-                    if (mine) {
-                        int2* dst = A + AIDED_IQ_PAD + 8 * gl + 1;
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) dst[k] = make_int2((int)(bi + pi[k]), (int)(bq + pq[k]));
-                    }
-                    ci += (uint32_t)__shfl((int)ti, 63, 64), cq += (uint32_t)__shfl((int)tq, 63, 64);
-                }
-                for (int i = lane + 1; i < 2 * W; i += 64) A[AIDED_IQ_PAD + n + i] = make_int2((int)ci, (int)cq);  // A[k] = A[n] for k > n
-                // STREAM: the chip of position m is that of window sample (cs - o) + m at h = 0
-                int count = 0;
-                uint32_t chip_M = 0;
-                uint64_t before = 0;
-                const uint64_t q0 = cs - o;
-                for (int m0 = 0; m0 <= M; m0 += 64) {
-                    const uint64_t P = mod_full(((uint64_t)base + q0 + (uint64_t)(m0 + lane)) * ca_rate);  // below 2^23 * 2^32
-                    const uint32_t cb = (uint32_t)(P >> 32);                                                // 0 .. 1022
-                    const uint32_t chip = (s_chips[cb >> 5] >> (cb & 31)) & 1u;
-                    const uint64_t bits = __ballot(chip != 0);
-                    const uint64_t prev = m0 == 0 ? bits & 1ull : before >> 63;
-                    const int left = M - m0;  // the positions of this round are 0 .. min(left, 63)
-                    const uint64_t valid = left >= 63 ? ~0ull : (2ull << left) - 1ull;
-                    const uint64_t trans = (bits ^ (bits << 1 | prev)) & valid;
-                    if (trans >> lane & 1ull) list[count + __popcll(trans & ((1ull << lane) - 1ull))] = (uint16_t)((uint32_t)(m0 + lane) | chip << 15);
-                    count += __popcll(trans);
-                    if (left <= 63) chip_M = (uint32_t)(bits >> left) & 1u;
-                    before = bits;
-                }
-                if (lane < 3 && count + lane < ((count + 3) & ~3)) list[count + lane] = 0;  // up to a multiple of four: entries that read A[-h] = 0
-                const int quads = (count + 3) >> 2;
-                wave_sync_iq();
-                // SUM
-                const uint2* const lq = s_list[wv];
-#pragma unroll
-                for (int p = 0; p < AIDED_PASSES; ++p) {
-                    if (64 * p < n_code) {  // the lanes beyond n_code read slots that exist and are not used
-                        const int2* const Ah = A + AIDED_IQ_PAD - (lane + 64 * p);
-                        uint32_t sx = 0, sy = 0;
-                        for (int i = 0; i < quads; ++i) {
-                            const uint2 e = lq[i];
-                            const uint32_t ent[4] = {e.x & 0xffffu, e.x >> 16, e.y & 0xffffu, e.y >> 16};
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                const int2 v = Ah[ent[k] & 0x7fffu];
-                                const uint32_t msk = (ent[k] >> 15) - 1u;  // the new chip 1 (s' falls, D = -2): + A; 0 (D = +2): - A
-                                sx += ((uint32_t)v.x ^ msk) - msk;
-                                sy += ((uint32_t)v.y ^ msk) - msk;
-                            }
-                        }
-                        const uint32_t sM = chip_M ? ~0u : 0u;  // s'[M] A[n]
-                        Ri[p] += ((ci ^ sM) - sM) + 2u * sx;
-                        Rq[p] += ((cq ^ sM) - sM) + 2u * sy;
-                    }
-                }
-                wave_sync_iq();
-            }
+            uint32_t Ri[AIDED_PASSES], Rq[AIDED_PASSES], fl;
+            segment_sums_by_parts<AIDED_PASSES, AidedIqGeometry>(a.c, a0, a1, o, base, lo_rate, ca_rate, s_chips, A, s_list[wv], lane, W, n_code, with_floor, Ri,
+                                                                 Rq, fl);
 #pragma unroll
             for (int p = 0; p < AIDED_PASSES; ++p) {
                 const int64_t I = (int32_t)Ri[p], Q = (int32_t)Rq[p];

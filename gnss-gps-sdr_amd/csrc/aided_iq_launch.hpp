@@ -19,6 +19,11 @@ static constexpr int AIDED_IQ_LIST = AIDED_IQ_CHUNK + 256;                  // t
 static_assert(2 * AIDED_MAX_CODE_HALF <= AIDED_IQ_PAD - 2 && AIDED_IQ_CHUNK % 8 == 0 && AIDED_IQ_LIST % 4 == 0, "the pads");
 static_assert(AIDED_IQ_CHUNK + 2 * AIDED_MAX_CODE_HALF < (1 << 15), "a list entry: 15 bits of position, one of sign");
 
+// the prefix array of a k_aided_iq wave as aided_iq_walk.hpp's segment_sums_by_parts takes it
+struct AidedIqGeometry {
+    static constexpr int CHUNK = AIDED_IQ_CHUNK, PAD = AIDED_IQ_PAD;
+};
+
 // c.peaks is peaks_in and may be NULL
 struct AidedIqArgs {
     IqCaptureArgs c;

@@ -247,6 +247,11 @@ struct gpsacq_engine {
     Scratch<gpsacq_fix> d_fix_instant;       // k_aid_instant's output: host-buffer form, and where the caller of the chain wants no fixes
     Stages<4> aided_coh_t;  // before k_aid_instant, between it and k_aid_predict, between that and k_aided_coh, after it
     int aided_coh_ran = 0;  // bit k: stage k + 1 ran a kernel in the last call
+    // coherent aided acquisition on an 8-bit IQ capture (gpsacq_aided_coh_search_iq8*, gpsacq_aided_coh_peaks_iq8_device): the capture
+    // of the host-buffer form goes into d_iq, sign mode's 1-bit stream into d_iqbits, everything else as the 1-bit forms'
+    Stages<2> aidcohiq_conv_t;  // around the conversion (sign mode)
+    Stages<4> aidcohiq_t;       // as aided_coh_t, the search being k_aided_coh_iq (sign mode: k_aided_coh)
+    int aidcohiq_ran = 0;       // bit k: stage k + 1 ran a kernel in the last call
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     Scratch<int> d_persist;
     bool persist = false;

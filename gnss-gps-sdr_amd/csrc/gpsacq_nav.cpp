@@ -15,7 +15,9 @@
 // doppler_kernels.hip, and "Snapshot chain on an 8-bit IQ capture": gpsacq_refine_iq8*, gpsacq_fine_doppler_iq8* and the two *_iq8_device
 // chains, which run snapshot_iq_kernels.hip (sign mode: the conversion, then the 1-bit kernels), and "Aided acquisition": gpsacq_aid_predict*, gpsacq_aided_search* and gpsacq_aided_peaks_device, which run
 // aided_kernels.hip, and "Aided acquisition on an 8-bit IQ capture": gpsacq_aided_search_iq8* and gpsacq_aided_peaks_iq8_device, which
-// run aided_iq_kernels.hip (sign mode: the conversion, then k_aided).
+// run aided_iq_kernels.hip (sign mode: the conversion, then k_aided), and "Coherent aided acquisition on an 8-bit IQ capture":
+// gpsacq_aided_coh_search_iq8* and gpsacq_aided_coh_peaks_iq8_device, which run aided_coh_iq_kernels.hip (sign mode: the conversion,
+// then k_aided_coh).
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -31,6 +33,7 @@
 #include "obs_launch.hpp"
 #include "raim_launch.hpp"
 #include "refine_launch.hpp"
+#include "aided_coh_iq_launch.hpp"
 #include "aided_iq_launch.hpp"
 #include "aided_launch.hpp"
 #include "smooth_launch.hpp"
@@ -2485,44 +2488,56 @@ struct CohSearch {
     void *d_aided, *d_peaks_out, *d_powers;
 };
 
-static int aided_coh_enqueue(gpsacq_engine* e, const CohInstant* in, const CohPredict* pr, const CohSearch* se) {
-    if (se) {
-        if (int rc = ensure_track_chips(e)) return rc;
-        if (int rc = ensure_coh_table(e)) return rc;
-    }
+// the chain's three stages on the engine's stream between the four events of `timer`; `ran` gets bit k for stage k + 1; `search`
+// launches the search kernel, or is empty
+template <class Search> static int coh_chain_enqueue(gpsacq_engine* e, Stages<4>& timer, int& ran, const CohInstant* in, const CohPredict* pr, bool has_search,
+                                                     Search&& search) {
     if (pr)  // before the first event: the upload is no part of any stage's time
         if (int rc = nav_upload_eph(e, pr->eph, pr->n_eph)) return rc;
-    e->aided_coh_ran = 0;
-    if (int rc = e->aided_coh_t.begin(e->stream)) return rc;
+    ran = 0;
+    if (int rc = timer.begin(e->stream)) return rc;
     if (in) {
         AidInstantArgs a{};
         a.fix = (const gpsacq_fix*)in->d_fix, a.info = (const gpsacq_coarse_info*)in->d_info, a.prior = (const gpsacq_coarse_prior*)in->d_prior;
         a.n_fix = in->n_fix;
         a.out = (gpsacq_fix*)in->d_out;
         launch_aid_instant(a, e->stream);
-        e->aided_coh_ran |= 1;
+        ran |= 1;
     }
-    if (int rc = e->aided_coh_t.mark(1, e->stream)) return rc;
+    if (int rc = timer.mark(1, e->stream)) return rc;
     if (pr) {
         aid_predict_launch(e, pr->n_eph, pr->d_fix, pr->d_vel, pr->n_fix, pr->n_chans, pr->ap, pr->d_aid);  // timed here alone: gpsacq_aided_last_ms keeps its own
-        e->aided_coh_ran |= 2;
+        ran |= 2;
     }
-    if (int rc = e->aided_coh_t.mark(2, e->stream)) return rc;
+    if (int rc = timer.mark(2, e->stream)) return rc;
+    if (has_search) {
+        search();
+        ran |= 4;
+    }
+    if (int rc = timer.mark(3, e->stream)) return rc;
+    return timer.finish();
+}
+
+// k_aided_coh on a 1-bit stream; every argument has been checked
+static void aided_coh_launch(gpsacq_engine* e, const CohSearch& se) {
+    AidedCohArgs a{};
+    capture_args(e, se.d_bits, se.n_bytes, se.stride, se.d_tasks, se.d_peaks_in, se.n_tasks, a);
+    a.kmax = e->kmax;
+    a.aid = (const gpsacq_aid*)se.d_aid;
+    a.table = e->d_coh_table;
+    a.p = se.sp;
+    a.out = (gpsacq_aided_coh*)se.d_aided;
+    a.peaks_out = (gpsacq_peak*)se.d_peaks_out;
+    a.powers = (unsigned long long*)se.d_powers;
+    launch_aided_coh(a, e->stream);
+}
+
+static int aided_coh_enqueue(gpsacq_engine* e, const CohInstant* in, const CohPredict* pr, const CohSearch* se) {
     if (se) {
-        AidedCohArgs a{};
-        capture_args(e, se->d_bits, se->n_bytes, se->stride, se->d_tasks, se->d_peaks_in, se->n_tasks, a);
-        a.kmax = e->kmax;
-        a.aid = (const gpsacq_aid*)se->d_aid;
-        a.table = e->d_coh_table;
-        a.p = se->sp;
-        a.out = (gpsacq_aided_coh*)se->d_aided;
-        a.peaks_out = (gpsacq_peak*)se->d_peaks_out;
-        a.powers = (unsigned long long*)se->d_powers;
-        launch_aided_coh(a, e->stream);
-        e->aided_coh_ran |= 4;
+        if (int rc = ensure_track_chips(e)) return rc;
+        if (int rc = ensure_coh_table(e)) return rc;
     }
-    if (int rc = e->aided_coh_t.mark(3, e->stream)) return rc;
-    return e->aided_coh_t.finish();
+    return coh_chain_enqueue(e, e->aided_coh_t, e->aided_coh_ran, in, pr, se != nullptr, [&] { aided_coh_launch(e, *se); });
 }
 
 static size_t coh_powers_per_task(const gpsacq_aided_coh_params& sp) {
@@ -2631,6 +2646,166 @@ extern "C" int gpsacq_aided_coh_last_ms(const gpsacq_engine* e, float* instant_m
         *ms[k] = 0.f;
         if (e->aided_coh_ran >> k & 1)
             if (int rc = e->aided_coh_t.elapsed(k, k + 1, ms[k])) return rc;
+    }
+    return GPSACQ_OK;
+}
+
+// ---- coherent aided acquisition on an 8-bit IQ capture (aided_coh_iq_kernels.hip; sign mode: iq_kernels.hip, then k_aided_coh) ------
+// DEFAULT RATIO_MIN of "Coherent aided acquisition on an 8-bit IQ capture" (include/gpsacq.h): tools/aided_floor.py --iq8 --coherent
+static constexpr double COH_IQ_RATIO_MIN = 28.56;  // the largest ratio of 2304 draws, 23.0511, plus a quarter of its excess over 1
+
+extern "C" int gpsacq_aided_coh_default_params_iq8(gpsacq_aided_coh_params* p) {
+    if (int rc = gpsacq_aided_coh_default_params(p)) return rc;
+    p->ratio_min = COH_IQ_RATIO_MIN;  // the largest multi-bit ratio of the measured draws on absent PRNs plus a quarter of its excess over 1
+    return GPSACQ_OK;
+}
+
+// what the multi-bit path refuses: gpsacq_aided_search's engines, the z matrix, and a power that could pass 63 bits (the header's
+// BOUNDS: power <= M * (2^18 + 2^5) * spm * (blocks * 40000); the limits leave none)
+static int aided_coh_iq_engine_check(const char* who, const gpsacq_engine* e, const gpsacq_aided_coh_params& sp) {
+    if (int rc = aided_engine_check(who, e)) return rc;
+    const long long fit = (long long)sp.blocks * 40000 / e->nlags;
+    if (fit * (2 * sp.code_half + 1) > COH_MAX_Z)
+        return fail(GPSACQ_ERR_UNSUPPORTED, "%s: %lld segments of %d code phases (the z matrix holds %d entries)", who, fit, 2 * (int)sp.code_half + 1, COH_MAX_Z);
+    const unsigned __int128 bound = (unsigned __int128)sp.coh_ms * ((1u << 18) + (1u << 5)) * (unsigned)e->nlags * ((unsigned long long)sp.blocks * 40000ull);
+    if (bound >= (unsigned __int128)1 << 63) return fail(GPSACQ_ERR_UNSUPPORTED, "%s: a power of %d ms sums could pass 63 bits", who, (int)sp.coh_ms);
+    return GPSACQ_OK;
+}
+
+static int aided_coh_iq_check(const char* who, const gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                              const void* aid, const void* peaks_in, size_t n_tasks, const gpsacq_aided_coh_params* params, const void* aided,
+                              const void* peaks_out, bool device, IqSnap* s, gpsacq_aided_coh_params* checked) {
+    if (!aided || !peaks_out || (peaks_in && peaks_in == peaks_out)) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (!e) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (params)  // the parameters' own ranges first: an argument error
+        if (int rc = aided_coh_params(who, nullptr, params, checked)) return rc;
+    if (int rc = iq_snap_check(who, e, in, iq, n_samples, stride, aid, n_tasks, aided, device, s)) return rc;
+    if (!params)  // the defaults of the path that runs: sign mode is gpsacq_aided_coh_search's, byte for byte
+        if (int rc = s->sign ? gpsacq_aided_coh_default_params(checked) : gpsacq_aided_coh_default_params_iq8(checked)) return rc;
+    if (s->sign) return aided_coh_params(who, e, checked, checked);
+    return aided_coh_iq_engine_check(who, e, *checked);
+}
+
+// what the search stage of a call of this section runs; every argument has been checked
+struct CohIqSearch {
+    IqSnap s;
+    const void *d_tasks, *d_aid, *d_peaks_in;
+    size_t n_tasks;
+    gpsacq_aided_coh_params sp;
+    void *d_aided, *d_peaks_out, *d_powers;
+};
+
+// a call of this section: sign mode converts the capture once, then the chain's stages, each timed
+static int aided_coh_iq_enqueue(gpsacq_engine* e, const CohInstant* in, const CohPredict* pr, CohIqSearch& se) {
+    if (int rc = ensure_track_chips(e)) return rc;
+    if (int rc = ensure_coh_table(e)) return rc;
+    e->aidcohiq_conv_t.done = e->aidcohiq_t.done = false;
+    if (se.s.sign)
+        if (int rc = iq_snap_convert(e, se.s, e->aidcohiq_conv_t)) return rc;
+    return coh_chain_enqueue(e, e->aidcohiq_t, e->aidcohiq_ran, in, pr, true, [&] {
+        if (se.s.sign) {
+            aided_coh_launch(e, CohSearch{se.s.d_bits, se.s.n_bytes, se.s.stride / 16, se.d_tasks, se.d_aid, se.d_peaks_in, se.n_tasks, se.sp, se.d_aided,
+                                          se.d_peaks_out, se.d_powers});
+            return;
+        }
+        AidedCohIqArgs a{};
+        iq_capture_args(e, se.s, se.d_tasks, se.d_peaks_in, se.n_tasks, a.c);
+        a.kmax = e->kmax;
+        a.aid = (const gpsacq_aid*)se.d_aid;
+        a.table = e->d_coh_table;
+        a.p = se.sp;
+        a.out = (gpsacq_aided_coh*)se.d_aided;
+        a.peaks_out = (gpsacq_peak*)se.d_peaks_out;
+        a.powers = (unsigned long long*)se.d_powers;
+        launch_aided_coh_iq(a, e->stream);
+    });
+}
+
+extern "C" int gpsacq_aided_coh_search_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                                  const void* d_tasks, const void* d_aid, const void* d_peaks_in, size_t n_tasks,
+                                                  const gpsacq_aided_coh_params* params, void* d_aided, void* d_peaks_out, void* d_powers_out, int sync) {
+    CohIqSearch se{{}, d_tasks, d_aid, d_peaks_in, n_tasks, {}, d_aided, d_peaks_out, d_powers_out};
+    if (int rc = aided_coh_iq_check("gpsacq_aided_coh_search_iq8", e, in, d_iq, n_samples, stride, d_aid, d_peaks_in, n_tasks, params, d_aided, d_peaks_out, true,
+                                    &se.s, &se.sp))
+        return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = aided_coh_iq_enqueue(e, nullptr, nullptr, se)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_coh_search_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                                           const gpsacq_task* tasks, const gpsacq_aid* aid, const gpsacq_peak* peaks_in, size_t n_tasks,
+                                           const gpsacq_aided_coh_params* params, gpsacq_aided_coh* aided_out, gpsacq_peak* peaks_out,
+                                           uint64_t* powers_out) {
+    CohIqSearch se{};
+    if (int rc = aided_coh_iq_check("gpsacq_aided_coh_search_iq8", e, in, iq, n_samples, stride, aid, peaks_in, n_tasks, params, aided_out, peaks_out, false,
+                                    &se.s, &se.sp))
+        return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_pow = n_tasks * coh_powers_per_task(se.sp);
+    if (int rc = e->d_aided_coh.grow(n_tasks, e->stream)) return rc;
+    if (int rc = e->d_aided_peaks.grow(n_tasks, e->stream)) return rc;
+    if (powers_out)
+        if (int rc = e->d_coh_powers.grow(n_pow, e->stream)) return rc;
+    if (int rc = e->d_iq.grow(2 * n_samples + 16, e->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * n_samples, hipMemcpyHostToDevice, e->stream));
+    se.s.d_iq = se.s.cap.d_src = e->d_iq;
+    if (tasks)
+        if (int rc = upload(e, e->d_refine_tasks, tasks, n_tasks)) return rc;
+    if (peaks_in)
+        if (int rc = upload(e, e->d_refine_peaks, peaks_in, n_tasks)) return rc;
+    if (int rc = upload(e, e->d_aid, aid, n_tasks)) return rc;
+    se.d_tasks = tasks ? e->d_refine_tasks.p : nullptr, se.d_aid = e->d_aid, se.d_peaks_in = peaks_in ? e->d_refine_peaks.p : nullptr;
+    se.n_tasks = n_tasks;
+    se.d_aided = e->d_aided_coh, se.d_peaks_out = e->d_aided_peaks, se.d_powers = powers_out ? e->d_coh_powers.p : nullptr;
+    if (int rc = aided_coh_iq_enqueue(e, nullptr, nullptr, se)) return rc;
+    if (int rc = download(e, aided_out, e->d_aided_coh, n_tasks)) return rc;
+    if (int rc = download(e, peaks_out, e->d_aided_peaks, n_tasks)) return rc;
+    if (int rc = download(e, (unsigned long long*)powers_out, e->d_coh_powers, n_pow)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_coh_peaks_iq8_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_info,
+                                                 const void* d_prior, const void* d_vel, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples,
+                                                 size_t stride, const void* d_tasks, const void* d_peaks_in, size_t n_fix, int n_chans,
+                                                 const gpsacq_aid_params* aid_par, const gpsacq_aided_coh_params* coh_par, void* d_fix_instant, void* d_aid,
+                                                 void* d_aided, void* d_peaks_out, int sync) {
+    const char* who = "gpsacq_aided_coh_peaks_iq8";
+    CohPredict pr{eph, n_eph, d_fix, d_vel, n_fix, n_chans, {}, nullptr};
+    // d_aid may be NULL here (engine scratch), so the two checks are given d_aided where they test the prediction records for NULL
+    if (int rc = aid_predict_check(who, e, eph, n_eph, d_fix, n_fix, n_chans, aid_par, d_aided, &pr.ap)) return rc;
+    if (d_info && !d_prior) return fail(GPSACQ_ERR_ARG, "%s: coarse-time records without their priors", who);
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    CohIqSearch se{{}, d_tasks, nullptr, d_peaks_in, n_tasks, {}, d_aided, d_peaks_out, nullptr};
+    if (int rc = aided_coh_iq_check(who, e, in, d_iq, n_samples, stride, d_aided, d_peaks_in, n_tasks, coh_par, d_aided, d_peaks_out, true, &se.s, &se.sp))
+        return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = or_own(e, d_aid, e->d_aid, n_tasks)) return rc;
+    CohInstant ins{d_fix, d_info, d_prior, n_fix, d_fix_instant};
+    if (d_info) {
+        if (int rc = or_own(e, ins.d_out, e->d_fix_instant, n_fix)) return rc;
+        pr.d_fix = ins.d_out;
+    }
+    pr.d_aid = d_aid, se.d_aid = d_aid;
+    if (int rc = aided_coh_iq_enqueue(e, d_info ? &ins : nullptr, &pr, se)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_aided_coh_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* instant_ms, float* predict_ms, float* search_ms) {
+    if (!e || !e->aidcohiq_t.ran())
+        return fail(GPSACQ_ERR_ARG, "gpsacq_aided_coh_iq8_last_ms: no gpsacq_aided_coh_search_iq8 or gpsacq_aided_coh_peaks_iq8 call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = stage_ms(e->aidcohiq_conv_t, convert_ms)) return rc;
+    if (int rc = e->aidcohiq_t.wait()) return rc;
+    float* const ms[3] = {instant_ms, predict_ms, search_ms};
+    for (int k = 0; k < 3; ++k) {
+        if (!ms[k]) continue;
+        *ms[k] = 0.f;
+        if (e->aidcohiq_ran >> k & 1)
+            if (int rc = e->aidcohiq_t.elapsed(k, k + 1, ms[k])) return rc;
     }
     return GPSACQ_OK;
 }

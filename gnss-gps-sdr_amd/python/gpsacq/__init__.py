@@ -212,7 +212,8 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_aided_coh_default_params", "gpsacq_aided_coh_table", "gpsacq_aided_coh_search", "gpsacq_aided_coh_search_device",
            "gpsacq_aid_instant", "gpsacq_aid_instant_device", "gpsacq_aided_coh_peaks_device", "gpsacq_aided_coh_last_ms",
            "gpsacq_aided_default_params_iq8", "gpsacq_aided_search_iq8", "gpsacq_aided_search_iq8_device", "gpsacq_aided_peaks_iq8_device",
-           "gpsacq_aided_iq8_last_ms"]
+           "gpsacq_aided_iq8_last_ms", "gpsacq_aided_coh_default_params_iq8", "gpsacq_aided_coh_search_iq8", "gpsacq_aided_coh_search_iq8_device",
+           "gpsacq_aided_coh_peaks_iq8_device", "gpsacq_aided_coh_iq8_last_ms"]
 
 _lib = None
 
@@ -595,6 +596,17 @@ def load_library(path=None):
     lib.gpsacq_aided_peaks_iq8_device.restype = ctypes.c_int
     lib.gpsacq_aided_iq8_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 3
     lib.gpsacq_aided_iq8_last_ms.restype = ctypes.c_int
+    lib.gpsacq_aided_coh_default_params_iq8.argtypes = [vp]
+    lib.gpsacq_aided_coh_default_params_iq8.restype = ctypes.c_int
+    lib.gpsacq_aided_coh_search_iq8.argtypes = [vp, iqp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.gpsacq_aided_coh_search_iq8.restype = ctypes.c_int
+    lib.gpsacq_aided_coh_search_iq8_device.argtypes = [vp, iqp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_aided_coh_search_iq8_device.restype = ctypes.c_int
+    lib.gpsacq_aided_coh_peaks_iq8_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp, iqp, vp, sz, sz, vp, vp, sz, ctypes.c_int, vp, vp, vp, vp, vp, vp,
+                                                      ctypes.c_int]
+    lib.gpsacq_aided_coh_peaks_iq8_device.restype = ctypes.c_int
+    lib.gpsacq_aided_coh_iq8_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 4
+    lib.gpsacq_aided_coh_iq8_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -847,6 +859,16 @@ def aided_coh_params(**overrides):
     if not (np.isfinite(r["keep_snr"]) and np.isfinite(r["ratio_min"])):
         raise ValueError("aided_coh_params: keep_snr %g, ratio_min %g (must be finite)" % (r["keep_snr"], r["ratio_min"]))
     return out
+
+
+def aided_coh_params_iq8(**overrides):
+    """gpsacq_aided_coh_default_params_iq8: aided_coh_params() with the ratio_min measured for the multi-bit path of
+    aided_coh_search_iq8() (include/gpsacq.h, "Coherent aided acquisition on an 8-bit IQ capture"), the named fields replaced."""
+    lib = load_library()
+    d = np.zeros(1, dtype=AIDED_COH_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_aided_coh_default_params_iq8(d.ctypes.data_as(ctypes.c_void_p)))
+    overrides.setdefault("ratio_min", float(d["ratio_min"][0]))
+    return aided_coh_params(**overrides)
 
 
 def aided_coh_table():
@@ -2001,6 +2023,70 @@ class Engine:
         """Device milliseconds of the last coherent aided call: (k_aid_instant or 0, k_aid_predict or 0, k_aided_coh or 0)."""
         t = [ctypes.c_float() for _ in range(3)]
         _check(self._lib, self._lib.gpsacq_aided_coh_last_ms(self._h, *[ctypes.byref(x) for x in t]))
+        return tuple(x.value for x in t)
+
+    # ---- coherent aided acquisition on an 8-bit IQ capture --------------------------------------
+    def aided_coh_search_iq8(self, iq, inp, aid, tasks=None, peaks_in=None, stride=16 * BLOCK_BYTES, params=None, powers=False, n_samples=None):
+        """gpsacq_aided_coh_search_iq8: aided_coh_search() on interleaved 8-bit I, Q bytes, with inp (Engine.iq8_input(...)) as given
+        to search_iq8(): multi-bit segment sums against the measured floor where inp.multibit != 0, the 1-bit path on the converted
+        capture in sign mode.  stride in BYTES (a multiple of 16, >= 80000); n_samples: the capture's length (None: all of iq).
+        params: aided_coh_params_iq8() or aided_coh_params(), None for the defaults of gpsacq_aided_coh_default_params_iq8 (sign
+        mode: gpsacq_aided_coh_default_params).  Returns (AIDED_COH_DTYPE, PEAK_DTYPE) in the shape of aid, and with powers=True also
+        uint64 [n_tasks][2 K + 1][2 F + 1][M][2 W + 1]."""
+        buf = np.ascontiguousarray(np.asarray(iq).view(np.uint8).ravel())
+        n = buf.size // 2 if n_samples is None else int(n_samples)
+        if not isinstance(aid, np.ndarray) or aid.dtype != AID_DTYPE:
+            raise TypeError("aid must be an AID_DTYPE array")
+        ad = np.ascontiguousarray(aid)
+        tptr = iptr = wptr = None
+        if tasks is not None:
+            t = np.ascontiguousarray(np.asarray(tasks, dtype=np.int32).reshape(-1, 2))
+            if t.shape[0] != ad.size:
+                raise ValueError("one task per prediction")
+            tptr = t.ctypes.data_as(ctypes.c_void_p)
+        if peaks_in is not None:
+            if not isinstance(peaks_in, np.ndarray) or peaks_in.dtype != PEAK_DTYPE or peaks_in.size != ad.size:
+                raise TypeError("peaks_in must be a PEAK_DTYPE array with one peak per prediction")
+            pi = np.ascontiguousarray(peaks_in)
+            iptr = pi.ctypes.data_as(ctypes.c_void_p)
+        sr, sp = self._record(params, AIDED_COH_PARAMS_DTYPE)
+        prm = aided_coh_params() if sr is None else sr  # the shape of the powers: the two defaults differ in ratio_min alone
+        out = np.zeros(ad.shape, dtype=AIDED_COH_DTYPE)
+        pk = np.zeros(ad.shape, dtype=PEAK_DTYPE)
+        if powers:
+            pw = np.zeros((ad.size, 2 * int(prm["dop_half"][0]) + 1, 2 * int(prm["fine_half"][0]) + 1, max(int(prm["coh_ms"][0]), 1),
+                           2 * int(prm["code_half"][0]) + 1), dtype=np.uint64)
+            wptr = pw.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_aided_coh_search_iq8(self._h, ctypes.byref(inp), buf.ctypes.data_as(ctypes.c_void_p), n, int(stride), tptr,
+                                                                ad.ctypes.data_as(ctypes.c_void_p), iptr, int(ad.size), sp,
+                                                                out.ctypes.data_as(ctypes.c_void_p), pk.ctypes.data_as(ctypes.c_void_p), wptr))
+        return (out, pk, pw) if powers else (out, pk)
+
+    def aided_coh_search_iq8_device(self, inp, d_iq_ptr, n_samples, d_aid_ptr, n_tasks, d_aided_ptr, d_peaks_out_ptr, stride=16 * BLOCK_BYTES,
+                                    d_tasks_ptr=None, d_peaks_in_ptr=None, d_powers_ptr=None, params=None, sync=True):
+        """gpsacq_aided_coh_search_iq8_device: aided_search_iq8_device()'s arguments; the records are AIDED_COH_DTYPE."""
+        sr, sp = self._record(params, AIDED_COH_PARAMS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_aided_coh_search_iq8_device(self._h, ctypes.byref(inp), d_iq_ptr, int(n_samples), int(stride), d_tasks_ptr,
+                                                                       d_aid_ptr, d_peaks_in_ptr, int(n_tasks), sp, d_aided_ptr, d_peaks_out_ptr,
+                                                                       d_powers_ptr, 1 if sync else 0))
+
+    def aided_coh_peaks_iq8_device(self, eph, d_fix_ptr, inp, d_iq_ptr, n_samples, d_tasks_ptr, n_fix, n_chans, d_aided_ptr, d_peaks_out_ptr,
+                                   d_info_ptr=None, d_prior_ptr=None, d_vel_ptr=None, d_peaks_in_ptr=None, d_fix_instant_ptr=None, d_aid_ptr=None,
+                                   stride=16 * BLOCK_BYTES, aid_params=None, params=None, sync=True):
+        """gpsacq_aided_coh_peaks_iq8_device: aided_coh_peaks_device() on an 8-bit IQ capture."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        ar, ap = self._record(aid_params, AID_PARAMS_DTYPE)
+        sr, sp = self._record(params, AIDED_COH_PARAMS_DTYPE)
+        _check(self._lib, self._lib.gpsacq_aided_coh_peaks_iq8_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), d_fix_ptr, d_info_ptr,
+                                                                      d_prior_ptr, d_vel_ptr, ctypes.byref(inp), d_iq_ptr, int(n_samples), int(stride),
+                                                                      d_tasks_ptr, d_peaks_in_ptr, int(n_fix), int(n_chans), ap, sp, d_fix_instant_ptr,
+                                                                      d_aid_ptr, d_aided_ptr, d_peaks_out_ptr, 1 if sync else 0))
+
+    def aided_coh_iq8_last_ms(self):
+        """Device milliseconds of the last coherent aided *_iq8 call: (conversion or 0, k_aid_instant or 0, k_aid_predict or 0, the
+        search kernel)."""
+        t = [ctypes.c_float() for _ in range(4)]
+        _check(self._lib, self._lib.gpsacq_aided_coh_iq8_last_ms(self._h, *[ctypes.byref(x) for x in t]))
         return tuple(x.value for x in t)
 
     def coarse_obs_device(self, d_peaks_ptr, n_fix, n_chans, d_obs_ptr, snr_min=THRESHOLD, sync=True):

@@ -2035,8 +2035,9 @@ GPSACQ_API int gpsacq_doppler_last_ms(const gpsacq_engine* e, float* fine_dop_ms
  *
  * gpsacq_snap_quality* stays for 1-bit records (sign mode's included): its analytic floor is that of a +-1 stream.
  *
- * OUT OF SCOPE.  A noise floor for multi-bit records (gpsacq_snap_quality).  A multi-bit coherent aided search (the non-coherent
- * one is "Aided acquisition on an 8-bit IQ capture" below).  Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.
+ * OUT OF SCOPE.  A noise floor for multi-bit records (gpsacq_snap_quality).  (The aided searches on the IQ bytes are "Aided
+ * acquisition on an 8-bit IQ capture" and "Coherent aided acquisition on an 8-bit IQ capture" below.)  Accumulated or re-aligned
+ * searches, multi-GPU, gps_test and gps_track.
  */
 GPSACQ_API int gpsacq_refine_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride, const gpsacq_task* tasks,
                                  const gpsacq_peak* peaks, size_t n_tasks, const gpsacq_refine_params* params, gpsacq_fine* fine_out);
@@ -2494,8 +2495,8 @@ GPSACQ_API int gpsacq_aided_coh_last_ms(const gpsacq_engine* e, float* instant_m
  * The floor is summed once per segment from the same bytes.  No atomics, no float before the ratio.  Every loop is bounded by
  * kernel arguments, every LDS index by the host-checked limits (spm <= 65535, W <= 127, K <= 8).  DESIGN.md 8.9 has the rest.
  *
- * OUT OF SCOPE.  A multi-bit coherent aided search.  The measured floor for gpsacq_snap_quality on gpsacq_refine_iq8 records (the
- * floor law above is the one it would use).  Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.
+ * OUT OF SCOPE.  The measured floor for gpsacq_snap_quality on gpsacq_refine_iq8 records (the floor law above is the one it would
+ * use).  Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.  (The multi-bit coherent search is the next section.)
  */
 GPSACQ_API int gpsacq_aided_default_params_iq8(gpsacq_aided_params* p);   /* host only */
 GPSACQ_API int gpsacq_aided_search_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
@@ -2513,6 +2514,130 @@ GPSACQ_API int gpsacq_aided_peaks_iq8_device(gpsacq_engine* e, const gpsacq_ephe
  * 1-bit conversion (sign mode), k_aid_predict (the chain) and the search (k_aided_iq, in sign mode k_aided).  A kernel that the last
  * call did not run reads 0.  Any pointer may be NULL. */
 GPSACQ_API int gpsacq_aided_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* predict_ms, float* search_ms);
+
+/*
+ * ---- Coherent aided acquisition on an 8-bit IQ capture: multi-bit 20 ms sums ------------------------------------------------------
+ *
+ * gpsacq_aided_coh_search, the most sensitive step of the library, read a 1-bit stream: a caller with an rtl-sdr or HackRF file went
+ * through gpsacq_iq8_to_bits first and paid one arm (3 dB) and the limiter (about 2 dB) exactly where the coherent sums had won their
+ * 2.5 dB.  gpsacq_aided_coh_search_iq8 runs the 20 ms sums on the IQ bytes themselves.  THE MODEL; the kernel
+ * (csrc/aided_coh_iq_kernels.hip) and the reference of the tests (tests/aided_coh_iq_ref.py) are both written from this text.  It adds
+ * no arithmetic of its own: it COMPOSES two sections above, "IQ" = "Aided acquisition on an 8-bit IQ capture" and "COH" = "Coherent
+ * aided acquisition", A. SEARCH, each holding word for word except where this text says otherwise.
+ *
+ * INPUTS.  `in`, iq[2 * n_samples], n_samples, stride (BYTES, a multiple of 16, 80000 <= stride <= 2^31), tasks[n_tasks] (NULL: the
+ * reference schedule), aid[n_tasks] and peaks_in[n_tasks] (optional) are IQ's.  The parameters are COH's gpsacq_aided_coh_params with
+ * COH's limits: blocks 1 .. 64, min_segments >= 1, W 0 .. 31, K 0 .. 8, M one of 1, 2, 4, 5, 10, 20, F 0 .. 7, u 1 .. 512, keep_snr and
+ * ratio_min finite, and fit * (2 W + 1) <= 5120 with fit = blocks * 40000 / spm.
+ *
+ * in->multibit != 0 (GPSACQ_SAMPLES_REAL and GPSACQ_SAMPLES_COMPLEX alike): THE MULTI-BIT PATH.  PER TASK:
+ *   SAMPLE, WINDOW, step 1 (KEPT), step 2 (NO_AID) and step 3 (HYPOTHESES: f_d, lo_rate_d, the valid d, base, P0(h, d), the ONE chip
+ *     stream per (segment, d), the carrier phase counted from the window's first sample) are IQ's.
+ *   Step 4 (SEGMENT SUMS).  z_s = (I_s, Q_s) of hypothesis (h, d) are IQ's per-segment sums of step 4,
+ *         I_s = sum h_P (v_i C - v_q S),   Q_s = sum h_P (v_i S + v_q C)     over the spm samples of segment s,
+ *     kept with their signs and NOT squared.
+ *   Step 5 (COHERENT SUMS) is COH's step 5 on these z_s: the same ROTATION TABLE, k_s = (f u s) mod 1024, A_s = I_s C[k_s] + Q_s S[k_s],
+ *     B_s = Q_s C[k_s] - I_s S[k_s] in int64, the period boundaries {0, S} and every 0 < s < S with s = e (mod M), the partial
+ *     periods at both ends counted, A' = floor((sum of A_s over the period) / 2^14) -- the shift AFTER the sum -- and
+ *         power(h, d, g, e) = sum over the periods of A'^2 + B'^2,  uint64.
+ *     BOUNDS.  They differ from COH's and decide the kernel's integer types.  |v_i|, |v_q| <= 256, so a sample adds at most 512 to
+ *     either sum: |I_s|, |Q_s| <= 512 spm < 2^25.  By Cauchy-Schwarz I_s^2 <= spm * sum (v_i C - v_q S)^2 and likewise Q_s^2, and the
+ *     two sums of squares add up to 2 sum (v_i^2 + v_q^2) <= spm * 2^18: I_s^2 + Q_s^2 <= 2^18 spm^2.  |A_s|, |B_s| <=
+ *     sqrt(I_s^2 + Q_s^2) sqrt(C^2 + S^2) <= 2^9 spm (2^14 + 1) < 2^40: every product with the int16 table is a 64-bit product.  A
+ *     prefix over fewer than 2^12 segments stays below 2^52, a period of at most 20 segments below 2^45, A' below 2^30 (so A'^2 +
+ *     B'^2 < 2^61).  A period of n segments adds at most n^2 2^18 spm^2 (1 + 2^-13), and the n of a partition add up to S with n <=
+ *     M: power <= M S 2^18 spm^2 (1 + 2^-13) <= 20 * 2^18 * 65535 * (64 * 40000) * (1 + 2^-13) = 2^59.6 < 2^60 -- it fits uint64,
+ *     and it does NOT fit the 44 bits COH's packed key gives a power.  (The library still refuses, GPSACQ_ERR_UNSUPPORTED, an engine
+ *     and parameters with M * (2^18 + 2^5) * spm * (blocks * 40000) >= 2^63; the limits above leave none.)
+ *     With M = 1 and F = 0 every period is one segment and C[0] = 2^14, S[0] = 0: power(h, d, 0, 0) is gpsacq_aided_search_iq8's
+ *     power(h, d) bit for bit (a test uses it).
+ *   Step 6 (RECORD) is COH's gpsacq_aided_coh with
+ *       best, its place (best_d, best_f, best_e, best_h): the largest KEY (power, -d, -g, -e, -h) in lexicographic order, whatever the
+ *                 order of any reduction (the kernel compares the pair (power, 31 - d << 15 | 15 - g << 11 | 31 - e << 6 | 63 - h))
+ *       noncoh  = the sum over the segments of I_s^2 + Q_s^2 at (best_h, best_d): gpsacq_aided_search_iq8's power there
+ *       floor   = IQ's MEASURED FLOOR, 2 * (sum over the samples of the window's segments of v_i^2 + v_q^2): what a +-1 replica
+ *                 uncorrelated with the samples leaves in a period of n segments is the sum of its segments' floors, so the
+ *                 partition into periods does not change it
+ *       ratio, lo_shift, ca_shift, doppler_hz, best_e, reserved, the flags and the OUTPUT PEAK as in COH.
+ *   Step 7: powers_out[n_tasks][2K + 1][2F + 1][M][2W + 1] as in COH.
+ *
+ * in->multibit == GPSACQ_SAMPLES_SIGN: the capture is converted once per call into engine scratch by the path gpsacq_aided_search_iq8
+ * uses, and k_aided_coh runs on it with n_bytes = ceil(n_samples / 8) and stride / 16: the result is byte for byte
+ * gpsacq_iq8_to_bits_device followed by gpsacq_aided_coh_search_device.
+ *
+ * DEFAULT RATIO_MIN.  gpsacq_aided_coh_default_params_iq8 (host only) sets gpsacq_aided_coh_default_params' values with ratio_min
+ * measured for the multi-bit path; a NULL params of this section's calls means these in multi-bit mode and
+ * gpsacq_aided_coh_default_params' in sign mode.  Measured as both sections above did (tools/aided_floor.py --iq8 --coherent, on the
+ * CPU with tests/aided_coh_iq_ref.py's quick spellings): the --iq8 scene (eight satellites at amplitude 0.2, noise sigma 1, fs = 5.456
+ * MHz, IF 0.4 MHz, scale 16, int8, the mean not removed) with the random navigation bits of --coherent on its eight satellites,
+ * searched for its 24 ABSENT PRNs with the defaults, 2304 draws of 13 860 hypotheses each: the largest ratio was 23.0511 (median
+ * 7.4827, 99.9 % below 19.0240).  The default is that plus a quarter of its excess over 1: 23.0511 + 22.0511 / 4 = 28.56.  That is 2.7
+ * times COH's 10.73, and as there it is not noise: it is the C/A cross-correlation of the eight satellites at amplitude 0.2, which a
+ * 20 ms sum adds up coherently wherever a Doppler difference is close to a multiple of 1 kHz, and which keeps both arms and passes no
+ * limiter here exactly as the signal sought does.  It belongs to the defaults and to that scene; a caller with fewer or weaker
+ * satellites beside the signal measures a lower one and keeps more of the gain.
+ * WHAT TO EXPECT.  Measured on the CPU (tests/test_aided_coh_iq.py: tests/test_aided_coh.py's scene -- 16 blocks, five satellites at
+ * 0.2 with navigation bits beside the weak one, two absent PRNs -- written as an 8-bit IQ capture, the same bytes searched multi-bit
+ * and through the sign path, tests/iq_ref.py's conversion followed by tests/aided_coh_ref.py): at amplitude 0.0337 the weak satellite
+ * reads ratio 28.19 multi-bit where the sign path reads 10.64, both at the true code phase, bit edge 7 and 384.8 Hz against the
+ * generator's 389.8; the absent PRNs read 3.36 and 7.35 against 3.11 and 3.89, so the weak satellite stands 3.84 times above the
+ * larger absent ratio multi-bit and 2.74 times through the sign path.  Over amplitudes (one capture each): 0.02 reads 9.28 against
+ * 4.50, 0.025 reads 14.76 against 6.39, 0.03 reads 21.88 against 8.71, 0.035 reads 30.58 against 11.34 and 0.04 reads 40.79 against
+ * 14.69 (gpsacq_aided_search_iq8 reads 1.76, 2.07, 2.45, 2.91 and 3.45 there).  The excess over 1 is 2.7 to 2.9 times the sign path's, about 4.5 dB --
+ * the arm and the limiter -- but in this scene the measured thresholds rose alike (28.56 against 10.73): both defaults begin to
+ * detect at about amplitude 0.034, where gpsacq_aided_search_iq8's 3.44 needs 0.04.  What the multi-bit sums buy with the defaults is
+ * the margin over the absent PRNs, not a lower first amplitude; a caller whose scene has no eight satellites at 0.2 measures a lower
+ * ratio_min (tools/aided_floor.py --iq8 --coherent) and keeps the 4.5 dB.  Measured on an MI355X
+ * (tools/snapshot_bench.py --iq8 --aided-coh, 1024 blocks, eight satellites at 0.2, two weak ones and two absent PRNs per block,
+ * navigation bits on, the three searches on the same tasks in the same run with their own defaults, HIP events, shader clock not read):
+ * at amplitude 0.03 this search detects 1309 of the 2047 weak tasks the plain search had missed, the sign-path coherent search 960
+ * and gpsacq_aided_search_iq8 77 (median ratios 30.23, 10.59 and 2.83); at 0.025 it detects 194 of 2048, the sign path 168 (one of them
+ * off the true code phase) and the non-coherent search none (21.60, 7.91, 2.37); at 0.035 1990, 1807 and 878 of 2042 (40.47, 13.82,
+ * 3.38).  Every other detection lies at the true code phase, and no search detects any of the 2048 absent tasks (largest ratios 11.45,
+ * 6.83 and 2.75).  At 0.03 doppler_hz is 5.6 Hz rms from the generator's (sign path 6.1) and best_e equals its edge in 78 % of the
+ * detections, within one segment in 98 % (sign path 64 % and 93 %).  k_aided_coh_iq 44.16 ms for 4095 tasks of 13 860 hypotheses beside
+ * k_aided_iq 40.87 ms (1.08 times) and 6.93 ms for the conversion and k_aided_coh (6.4 times).  So on the bench scene, whose measured
+ * floor it is, the default detects about a third more weak satellites at 0.03 than the sign path does; DESIGN.md 8.10 has the rest.
+ *
+ * THE CHAIN.  gpsacq_aided_coh_peaks_iq8_device is gpsacq_aided_coh_peaks_device with (in, d_iq, n_samples) for (d_bits, n_bytes):
+ * k_aid_instant (skipped where d_info == NULL; d_prior is then not read), then k_aid_predict, then the search, one stream, no host
+ * copy in between; d_fix_instant and d_aid may be NULL (engine scratch).  The results are exactly what the three calls give.
+ *
+ * gpsacq_aided_coh_search_iq8: host pointers, returns after completion.  The _device forms: iq, tasks, aid, peaks and the records are
+ * device pointers (iq 16-byte aligned), `in`, eph and the params stay host pointers; work on the engine's stream, sync != 0 waits;
+ * host and device form agree byte for byte.  peaks_out must not be peaks_in.  Argument errors are those of gpsacq_aided_search_iq8
+ * plus those of gpsacq_aided_coh_search (coh_ms outside its set, F, u, W, K outside their ranges; the chain: coarse-time records
+ * without their priors): GPSACQ_ERR_ARG, nothing launched and nothing written.  GPSACQ_ERR_UNSUPPORTED: everything
+ * gpsacq_aided_search_iq8 refuses, fit * (2W + 1) > 5120, and the bound of step 5; nothing launched and nothing written either.
+ * Kernel (csrc/aided_coh_iq_kernels.hip).  k_aided_coh_iq<M>: one workgroup of four wave64 per task, two stages per d.  The
+ * CORRELATION STAGE is k_aided_iq's WIPE / STREAM / SUM by summation by parts at one pass (W <= 31: lane h serves hypothesis h), the
+ * one chunk walk both kernels call (csrc/aided_iq_walk.hpp), entered once per (segment, d) and never per g or e; lane h stores (I, Q)
+ * as an int32 pair into z[s][h] in LDS, and the floor's sum rides along at the first valid d.  The COHERENT STAGE is k_aided_coh's
+ * walk over the work items (h, g) -- prefix sums of the turned series, M accumulators with constant indices, edge e = s mod M closed
+ * at segment s -- with 64-bit products, reducing the pair key.  A chunk of 512 samples keeps its LDS at 70 864 bytes: two workgroups
+ * per CU.  No atomics, no scratch, no float before the ratio; every loop is bounded by kernel arguments, every LDS index by the
+ * host-checked limits.  DESIGN.md 8.10 has the rest.
+ *
+ * OUT OF SCOPE.  W above 31.  A measured floor for gpsacq_snap_quality.  Accumulated or re-aligned searches, multi-GPU, gps_test and
+ * gps_track.
+ */
+GPSACQ_API int gpsacq_aided_coh_default_params_iq8(gpsacq_aided_coh_params* p);   /* host only */
+GPSACQ_API int gpsacq_aided_coh_search_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                                           const gpsacq_task* tasks, const gpsacq_aid* aid, const gpsacq_peak* peaks_in /* or NULL */, size_t n_tasks,
+                                           const gpsacq_aided_coh_params* params, gpsacq_aided_coh* aided_out, gpsacq_peak* peaks_out,
+                                           uint64_t* powers_out /* [n_tasks][2 K + 1][2 F + 1][M][2 W + 1] or NULL */);
+GPSACQ_API int gpsacq_aided_coh_search_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                                  const void* d_tasks, const void* d_aid, const void* d_peaks_in, size_t n_tasks,
+                                                  const gpsacq_aided_coh_params* params, void* d_aided, void* d_peaks_out, void* d_powers_out, int sync);
+GPSACQ_API int gpsacq_aided_coh_peaks_iq8_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_info /* or NULL */,
+                                                 const void* d_prior, const void* d_vel, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples,
+                                                 size_t stride, const void* d_tasks, const void* d_peaks_in, size_t n_fix, int n_chans,
+                                                 const gpsacq_aid_params* aid_params, const gpsacq_aided_coh_params* coh_params, void* d_fix_instant,
+                                                 void* d_aid, void* d_aided, void* d_peaks_out, int sync);
+/* device time of the last call of this section on this engine, milliseconds (HIP events on its stream; waits for them): the 8-bit ->
+ * 1-bit conversion (sign mode), k_aid_instant and k_aid_predict (the chain) and the search (k_aided_coh_iq, in sign mode k_aided_coh).
+ * A kernel that the last call did not run reads 0.  Any pointer may be NULL. */
+GPSACQ_API int gpsacq_aided_coh_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* instant_ms, float* predict_ms, float* search_ms);
 
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);

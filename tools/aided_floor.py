@@ -8,7 +8,7 @@ made sample by sample with tests/gen_ref.py.  tests/aided_ref.py searches it for
 ratio = best / floor over its 99 hypotheses.  C/A cross-correlation with the eight strong satellites is part of what is measured.
 Prints one JSON line: the draw count, the largest ratio, and the default it gives (largest + a quarter of its excess over 1).
 
-    python tools/aided_floor.py [--windows 8] [--centers 6] [--procs 8] [--coherent | --iq8]
+    python tools/aided_floor.py [--windows 8] [--centers 6] [--procs 8] [--coherent] [--iq8]
 
 --coherent: the same draws for gpsacq_aided_coh_search ("Coherent aided acquisition", DEFAULT RATIO_MIN) with its defaults (20 ms
 sums, 7 fine Dopplers 25/1024 cycle per segment apart, 20 bit edges: 13 860 hypotheses a draw), by tests/aided_coh_ref.py, on the
@@ -18,6 +18,10 @@ same scene with random navigation bits on its eight satellites (16 per satellite
 RATIO_MIN), by tests/aided_iq_ref.py against its measured floor: the same satellites written as an 8-bit IQ capture with
 tests/gen_ref.py's generator as tools/snapshot_bench.py --iq8 has it (int8, scale 16, sigma 1, IF 0.4 MHz, the mean not removed,
 GPSACQ_SAMPLES_REAL with mix_hz = fc - IF).
+
+--iq8 --coherent: the same draws for the multi-bit path of gpsacq_aided_coh_search_iq8 ("Coherent aided acquisition on an 8-bit IQ
+capture", DEFAULT RATIO_MIN) with --coherent's defaults, by tests/aided_coh_iq_ref.py's quick spellings against the measured
+floor: --iq8's capture with --coherent's navigation bits.
 """
 import argparse
 import json
@@ -132,8 +136,8 @@ def work_coherent(job):
 IF_HZ, SCALE = 0.4e6, 16.0  # tools/snapshot_bench.py --iq8
 
 
-def scene_iq8(n_blocks, seed):
-    """scene() as interleaved int8 I, Q bytes"""
+def scene_iq8(n_blocks, seed, with_nav=False):
+    """scene() as interleaved int8 I, Q bytes; with_nav: scene_nav()'s navigation bits on the eight satellites"""
     import numpy as np
 
     import gen_ref
@@ -142,9 +146,10 @@ def scene_iq8(n_blocks, seed):
     geo = geometry("north")
     sel = geo["subsets"][8]
     sats, _ = synth_sats(geo, sel, geo["ref_ms"] + 4321, 0.6180e-3, 0, FS, 0.2)
+    nav = (1 - 2 * np.random.default_rng(NAV_SEED).integers(0, 2, (len(sats), NAV_BITS))).astype(np.int8) if with_nav else None
     n = n_blocks * BLOCK_BYTES * 8
-    return np.concatenate([gen_ref.LAW.quantise(gen_ref.LAW.iq8(FS, sats, IF_HZ, SCALE, 1.0, seed, a, min(gen_ref.MAX_SAMPLES, n - a))["v"], True).ravel()
-                           for a in range(0, n, gen_ref.MAX_SAMPLES)])
+    return np.concatenate([gen_ref.LAW.quantise(gen_ref.LAW.iq8(FS, sats, IF_HZ, SCALE, 1.0, seed, a, min(gen_ref.MAX_SAMPLES, n - a), nav=nav)["v"],
+                                                True).ravel() for a in range(0, n, gen_ref.MAX_SAMPLES)])
 
 
 def work_iq8(job):
@@ -169,6 +174,32 @@ def work_iq8(job):
     return out
 
 
+def work_iq8_coherent(job):
+    """work_iq8() for the multi-bit path of gpsacq_aided_coh_search_iq8 with its defaults: tests/aided_coh_iq_ref.py's quick
+    spellings on the capture with navigation bits, against the measured floor"""
+    import aided_coh_iq_ref
+    import aided_iq_ref
+    import refine_iq_ref
+    block, lo_center, prns, centers, n_blocks, seed = job
+    if "iqnav" not in _scene:
+        _scene["iqnav"] = refine_iq_ref.samples(scene_iq8(n_blocks, seed, True), True)
+    vi, vq = _scene["iqnav"]
+    o = block * BLOCK_BYTES * 8
+    segments = BLOCKS * 40000 // SPM
+    law = aided_coh_iq_ref.LAW
+    rates = [aided_iq_ref.nco_words(lo_center - K + d, FC, FS, FC - IF_HZ, aided_iq_ref.REAL, KMAX) for d in range(2 * K + 1)]
+    assert all(r[0] for r in rates)
+    floor = law.floor_of(vi, vq, o, segments, SPM)
+    out = []
+    for prn in prns:
+        for ca in centers:
+            z = law.segment_sums_stream(vi, vq, o, segments, SPM, prn, law.base_of(ca, W, SPM), 2 * W + 1, rates)
+            best = max(max(max(max(row) for row in rows) for rows in law.powers_quick(zi, zq, COH["fine_half"], COH["fine_step"], COH["coh_ms"]))
+                       for zi, zq in z)
+            out.append(best / floor)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--coherent", action="store_true", help="the floor of gpsacq_aided_coh_search (20 ms sums, 7 fine Dopplers, 20 edges) "
@@ -187,9 +218,11 @@ def main():
     rng = np.random.default_rng(a.seed)
     jobs = [(b, lo, absent, rng.integers(0, SPM, 2).tolist(), n_blocks, a.seed) for b in range(a.windows) for lo in los]
     with multiprocessing.Pool(a.procs) as pool:
-        ratios = np.array([r for rows in pool.map(work_coherent if a.coherent else work_iq8 if a.iq8 else work, jobs) for r in rows])
+        ratios = np.array([r for rows in pool.map(work_iq8_coherent if a.coherent and a.iq8 else work_coherent if a.coherent else work_iq8 if a.iq8 else work, jobs) for r in rows])
     worst = float(ratios.max())
-    extra = dict(COH, coherent=True, nav_bits=NAV_BITS, nav_seed=NAV_SEED) if a.coherent else dict(iq8=True, if_hz=IF_HZ, scale=SCALE) if a.iq8 else {}
+    extra = dict(COH, coherent=True, nav_bits=NAV_BITS, nav_seed=NAV_SEED) if a.coherent else {}
+    if a.iq8:
+        extra.update(iq8=True, if_hz=IF_HZ, scale=SCALE)
     print(json.dumps({"draws": int(ratios.size), "absent_prns": len(absent), "windows": a.windows, "lo_centers": los, "blocks": BLOCKS, "W": W, "K": K,
                       **extra, "ratio_max": round(worst, 4), "ratio_median": round(float(np.median(ratios)), 4),
                       "ratio_p999": round(float(np.percentile(ratios, 99.9)), 4), "ratio_min_default": round(worst + 0.25 * (worst - 1.0), 4)}))

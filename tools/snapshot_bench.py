@@ -87,6 +87,15 @@ line carries aided_iq_ms beside convert_ms + aided_sign_ms and refine_iq_ms (bes
 read), what one group walk per hypothesis would cost (tasks searched x hypotheses x refine_iq_ms / (3 x hits)), the weak satellites
 detected and at the true code phase, the false detections and ratios on the absent tasks both ways, and the position error of the
 same blocks with and without the weak pair.
+
+--iq8 --aided-coh: the --iq8 --aided scene with random navigation bits on every satellite and the weak pair at --weak-amplitude
+(default 0.03 here), fixed from the strong ones, and then on the same tasks in the same run ("Coherent aided acquisition on an 8-bit
+IQ capture" of include/gpsacq.h): gpsacq_aided_coh_peaks_iq8_device in multi-bit mode (k_aided_coh_iq, the defaults of
+gpsacq_aided_coh_default_params_iq8) and in sign mode (the conversion, then k_aided_coh with gpsacq_aided_coh_default_params), the
+receive instant made on the device, and gpsacq_aided_peaks_iq8_device in multi-bit mode (k_aided_iq) from the same instants.  The
+line carries aided_coh_iq_ms beside aided_iq_ms and convert_ms + aided_coh_sign_ms (best of --reps, HIP events; the shader clock is
+not read), and per search the weak tasks detected, at and off the true code phase, the false detections and the largest ratio on
+the absent tasks, and for the two coherent searches the error of doppler_hz and the agreement of best_e against the generator.
 """
 import argparse
 import json
@@ -326,6 +335,117 @@ def main_iq8_aided(a):
     print(json.dumps(res))
 
 
+def main_iq8_aided_coh(a):
+    """--iq8 --aided-coh: the --iq8 --aided scene with navigation bits on every satellite, and on the same tasks in the same run the
+    multi-bit coherent search (k_aided_coh_iq), the sign-path coherent search (the conversion, then k_aided_coh) and the multi-bit
+    non-coherent search (k_aided_iq), each with its own defaults"""
+    import numpy as np
+    import torch
+
+    import gpsacq
+    from coarse_helpers import block_times, priors, synth_sats
+    from nav_helpers import geometry, to_records
+
+    geo = geometry("north")
+    sel = geo["subsets"][8]
+    rest = [k for k in range(len(geo["ephs"])) if k not in sel]
+    ephs = to_records([geo["ephs"][k] for k in list(sel) + rest])
+    spb = gpsacq.BLOCK_BYTES * 8
+    stride = 2 * spb
+    mid = a.blocks // 2
+    ref_ms, ref_frac = geo["ref_ms"] + 4321, 0.6180e-3  # the receive time of the first sample of block `mid`
+    strong, _ = synth_sats(geo, sel, ref_ms, ref_frac, mid * spb, FS, a.amplitude)
+    more, _ = synth_sats(geo, rest, ref_ms, ref_frac, mid * spb, FS, a.weak_amplitude)
+    gen_sats, sats = strong + more[:2], strong + more  # channels 8, 9: weak; 10, 11: absent
+    nav = (1 - 2 * np.random.default_rng(5).integers(0, 2, (len(gen_sats), 64))).astype(np.int8)
+    blk_ms, blk_frac = block_times(ref_ms, ref_frac - mid * spb / FS, a.blocks, spb, FS)
+    prior = priors(geo, blk_ms, seed=3, km=30.0, secs=30.0)
+    tasks = np.array([(b, s[0] - 1) for b in range(a.blocks) for s in sats], dtype=np.int32)
+    n_samples, n_tasks, m = (a.blocks + a.refine_blocks - 1) * spb, len(tasks), len(sats)
+    modes = ("coh_iq", "coh_sign", "iq")
+    sp = {"coh_iq": gpsacq.aided_coh_params_iq8(blocks=a.refine_blocks), "coh_sign": gpsacq.aided_coh_params(blocks=a.refine_blocks),
+          "iq": gpsacq.aided_params_iq8(blocks=a.refine_blocks)}
+    rp = gpsacq.refine_params(blocks=a.refine_blocks)
+    with gpsacq.Engine(FC, FS, 5000.0, device=0) as eng:
+        dev = lambda arr: torch.from_numpy(arr.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+        zeros = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, device="cuda:0")
+        d_iq, d_tasks, d_prior = zeros(2 * n_samples), dev(tasks), dev(prior)
+        d_peaks = zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize)
+        d_fix_f, d_info_f = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
+        d_instant = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize)
+        size = {"coh_iq": gpsacq.AIDED_COH_DTYPE.itemsize, "coh_sign": gpsacq.AIDED_COH_DTYPE.itemsize, "iq": gpsacq.AIDED_DTYPE.itemsize}
+        buf = {k: dict(aided=zeros(n_tasks * size[k]), peaks=zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize)) for k in modes}
+        inp_m = eng.iq8_input(signed=True, remove_dc=False, mix_hz=FC - a.if_hz, multibit=1)  # GPSACQ_SAMPLES_REAL
+        inp_s = eng.iq8_input(signed=True, remove_dc=False, mix_hz=FC - a.if_hz, multibit=0)  # GPSACQ_SAMPLES_SIGN
+        torch.cuda.synchronize()
+        eng.generate_iq8_device(d_iq.data_ptr(), n_samples, gen_sats, if_hz=a.if_hz, scale=16.0, signed=True, noise_sigma=1.0, seed=77, nav=nav)
+        inf = float("inf")
+        search_best, coh_iq, coh_sign, iq_best = inf, (inf, 0.0, 0.0), (inf, 0.0, 0.0), inf  # coherent: (search, instant, predict); sign: (convert + search, ...)
+        for _ in range(1 + a.reps):  # the first call also allocates the engine's scratch
+            eng.search_iq8_device(d_iq.data_ptr(), inp_m, a.blocks, d_peaks.data_ptr(), stride=stride, d_tasks_ptr=d_tasks.data_ptr(), n_tasks=n_tasks,
+                                  sync=True)
+            search_best = min(search_best, eng.last_timing()["ms_total"])
+            eng.coarse_fix_fine_iq8_device(ephs, inp_m, d_iq.data_ptr(), n_samples, d_tasks.data_ptr(), d_peaks.data_ptr(), a.blocks, m, d_prior.data_ptr(),
+                                           d_fix_f.data_ptr(), d_info_f.data_ptr(), stride=stride, refine_params=rp, sync=True)
+            for md, inp in (("coh_iq", inp_m), ("coh_sign", inp_s)):  # the receive instant on the device, from the same fine fixes
+                eng.aided_coh_peaks_iq8_device(ephs, d_fix_f.data_ptr(), inp, d_iq.data_ptr(), n_samples, d_tasks.data_ptr(), a.blocks, m,
+                                               buf[md]["aided"].data_ptr(), buf[md]["peaks"].data_ptr(), d_info_ptr=d_info_f.data_ptr(),
+                                               d_prior_ptr=d_prior.data_ptr(), d_peaks_in_ptr=d_peaks.data_ptr(), d_fix_instant_ptr=d_instant.data_ptr(),
+                                               stride=stride, aid_params=gpsacq.aid_params(-90.0), params=sp[md], sync=True)
+                c, i, p, t = eng.aided_coh_iq8_last_ms()
+                if md == "coh_iq":
+                    coh_iq = min(coh_iq, (t, i, p))
+                else:
+                    coh_sign = min(coh_sign, (c + t, c, t))
+            eng.aided_peaks_iq8_device(ephs, d_instant.data_ptr(), inp_m, d_iq.data_ptr(), n_samples, d_tasks.data_ptr(), a.blocks, m,
+                                       buf["iq"]["aided"].data_ptr(), buf["iq"]["peaks"].data_ptr(), d_peaks_in_ptr=d_peaks.data_ptr(), stride=stride,
+                                       aid_params=gpsacq.aid_params(-90.0), params=sp["iq"], sync=True)
+            iq_best = min(iq_best, eng.aided_iq8_last_ms()[2])
+        peaks = d_peaks.cpu().numpy().view(gpsacq.PEAK_DTYPE).reshape(a.blocks, m)
+        dt = {"coh_iq": gpsacq.AIDED_COH_DTYPE, "coh_sign": gpsacq.AIDED_COH_DTYPE, "iq": gpsacq.AIDED_DTYPE}
+        out = {k: dict(aided=buf[k]["aided"].cpu().numpy().view(dt[k]).reshape(a.blocks, m),
+                       peaks=buf[k]["peaks"].cpu().numpy().view(gpsacq.PEAK_DTYPE).reshape(a.blocks, m)) for k in modes}
+        name = eng.device_name
+    L1, CPS = 1575.42e6, 1.023e6
+    m0 = np.arange(a.blocks, dtype=np.float64)[:, None] * spb
+    cps = np.array([CPS * (1.0 + s[2] / L1) / FS for s in sats])[None, :]
+    q0 = (m0 + np.array([s[3] for s in sats])[None, :]) * cps
+    want = (q0 % 1023.0) / CPS
+    # the generator's edge: a data bit starts where the chip count (m + code_phase) * chips_per_sample passes a multiple of 20460
+    e_gen = np.rint(((-q0) % 20460.0) / cps / (FS / 1000.0)).astype(np.int64) % 20
+    wrap = lambda t: (t + 0.5e-3) % 1e-3 - 0.5e-3
+    weak, absent = slice(8, 10), slice(10, 12)
+    r4 = lambda v: round(float(v), 4)
+    searched = (out["coh_iq"]["aided"]["flags"] & (gpsacq.AIDED_KEPT | gpsacq.AIDED_NO_AID)) == 0
+    res = {"bench": "snapshot_iq8_aided_coh", "device": name, "blocks": a.blocks, "sats": m, "tasks": n_tasks, "amplitude": a.amplitude,
+           "weak_amplitude": a.weak_amplitude, "if_hz": a.if_hz, "scale": 16.0, "window_blocks": a.refine_blocks, "nav_bits": True,
+           "shader_clock_read": False, "search_ms": r4(search_best), "aid_instant_ms": r4(coh_iq[1]), "aid_predict_ms": r4(coh_iq[2]),
+           "aided_coh_iq_ms": r4(coh_iq[0]), "aided_iq_ms": r4(iq_best), "convert_ms": r4(coh_sign[1]), "aided_coh_sign_ms": r4(coh_sign[2]),
+           "convert_plus_aided_coh_sign_ms": r4(coh_sign[0]), "aided_coh_iq_over_aided_iq": r4(coh_iq[0] / iq_best),
+           "aided_coh_iq_over_sign_path": r4(coh_iq[0] / coh_sign[0]), "tasks_searched": int(searched.sum()),
+           "hypotheses_per_task": int(np.prod([2 * int(sp["coh_iq"][k][0]) + 1 for k in ("code_half", "dop_half", "fine_half")])) * int(sp["coh_iq"]["coh_ms"][0]),
+           "weak_search_hits": int((peaks["snr"][:, weak] >= gpsacq.THRESHOLD).sum()), "weak_tasks": int(2 * a.blocks)}
+    for k in modes:
+        ad, pk = out[k]["aided"], out[k]["peaks"]
+        srch = (ad["flags"] & (gpsacq.AIDED_KEPT | gpsacq.AIDED_NO_AID)) == 0
+        found = srch & ((ad["flags"] & (gpsacq.AIDED_FEW | gpsacq.AIDED_NO_POWER | gpsacq.AIDED_BELOW)) == 0)
+        true_w = found[:, weak] & (np.abs(wrap(pk["ca_shift"] / FS - want)[:, weak]) * FS <= 1.5)
+        res.update({"ratio_min_%s" % k: float(sp[k]["ratio_min"][0]), "weak_searched_%s" % k: int(srch[:, weak].sum()),
+                    "weak_detected_%s" % k: int(found[:, weak].sum()), "weak_detected_at_the_true_phase_%s" % k: int(true_w.sum()),
+                    "weak_detected_off_the_true_phase_%s" % k: int(found[:, weak].sum() - true_w.sum()),
+                    "weak_ratio_median_%s" % k: r4(np.median(ad["ratio"][:, weak][srch[:, weak]])) if srch[:, weak].any() else None,
+                    "absent_tasks_%s" % k: int(srch[:, absent].sum()), "absent_false_detections_%s" % k: int(found[:, absent].sum()),
+                    "absent_ratio_median_%s" % k: r4(np.median(ad["ratio"][:, absent][srch[:, absent]])) if srch[:, absent].any() else None,
+                    "absent_ratio_max_%s" % k: r4(ad["ratio"][:, absent].max())})
+        if k != "iq":  # against the generator: the fine Doppler and the bit edge of the detections at the true code phase
+            e_dop = (ad["doppler_hz"][:, weak] - np.array([s[2] for s in sats])[None, weak])[true_w]
+            de = ((ad["best_e"] - e_gen + 10) % 20 - 10)[:, weak][true_w]
+            res.update({"doppler_error_rms_hz_%s" % k: r4(np.sqrt((e_dop ** 2).mean())) if true_w.any() else None,
+                        "best_e_equal_share_%s" % k: r4((de == 0).mean()) if true_w.any() else None,
+                        "best_e_within_one_share_%s" % k: r4((np.abs(de) <= 1).mean()) if true_w.any() else None})
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=2048)
@@ -344,6 +464,10 @@ def main():
     ap.add_argument("--amplitude", type=float, default=0.2, help="amplitude of the eight satellites of --iq8")
     ap.add_argument("--if-hz", type=float, default=0.4e6, help="residual IF of the capture of --iq8")
     a = ap.parse_args()
+    if a.iq8 and a.aided_coh:
+        if a.weak_amplitude is None:
+            a.weak_amplitude = 0.03
+        return main_iq8_aided_coh(a)
     if a.iq8 and a.aided:
         if a.weak_amplitude is None:
             a.weak_amplitude = 0.05
