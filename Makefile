@@ -14,7 +14,7 @@ HOSTFLAGS:= -O2 -std=c++17 -fPIC -Wall -Wno-unknown-pragmas -ffp-contract=off
 all: lib host oracle emul
 
 lib: $(LIBDIR)/libgpsacq.so
-$(LIBDIR)/libgpsacq.so: $(CSRC)/acq_kernels.hip $(CSRC)/key_kernels.hip $(CSRC)/iq_kernels.hip $(CSRC)/gen_kernels.hip $(CSRC)/track_kernels.hip $(CSRC)/track_iq_kernels.hip $(CSRC)/nav_kernels.hip $(CSRC)/obs_kernels.hip $(CSRC)/smooth_kernels.hip $(CSRC)/quality_kernels.hip $(CSRC)/fix_kernels.hip $(CSRC)/coarse_kernels.hip $(CSRC)/refine_kernels.hip $(CSRC)/snapq_kernels.hip $(CSRC)/doppler_kernels.hip $(CSRC)/aided_kernels.hip $(CSRC)/aided_iq_kernels.hip $(CSRC)/aided_coh_iq_kernels.hip $(CSRC)/snapshot_iq_kernels.hip $(CSRC)/gpsacq_engine.cpp $(CSRC)/gpsacq_multi.cpp $(CSRC)/gpsacq_track.cpp $(CSRC)/gpsacq_nav.cpp $(CSRC)/*.hpp include/gpsacq.h
+$(LIBDIR)/libgpsacq.so: $(CSRC)/acq_kernels.hip $(CSRC)/key_kernels.hip $(CSRC)/iq_kernels.hip $(CSRC)/gen_kernels.hip $(CSRC)/track_kernels.hip $(CSRC)/track_iq_kernels.hip $(CSRC)/nav_kernels.hip $(CSRC)/obs_kernels.hip $(CSRC)/smooth_kernels.hip $(CSRC)/quality_kernels.hip $(CSRC)/fix_kernels.hip $(CSRC)/coarse_kernels.hip $(CSRC)/refine_kernels.hip $(CSRC)/snapq_kernels.hip $(CSRC)/doppler_kernels.hip $(CSRC)/aided_kernels.hip $(CSRC)/aided_iq_kernels.hip $(CSRC)/aided_coh_iq_kernels.hip $(CSRC)/snapshot_iq_kernels.hip $(CSRC)/snapq_iq_kernels.hip $(CSRC)/gpsacq_engine.cpp $(CSRC)/gpsacq_multi.cpp $(CSRC)/gpsacq_track.cpp $(CSRC)/gpsacq_nav.cpp $(CSRC)/*.hpp include/gpsacq.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $(CSRC)/gpsacq_engine.cpp -o $(LIBDIR)/gpsacq_engine.o
 	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/gpsacq_multi.cpp -o $(LIBDIR)/gpsacq_multi.o
@@ -38,8 +38,9 @@ $(LIBDIR)/libgpsacq.so: $(CSRC)/acq_kernels.hip $(CSRC)/key_kernels.hip $(CSRC)/
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $(CSRC)/aided_iq_kernels.hip -o $(LIBDIR)/aided_iq_kernels.o   # the NCO words as refine_kernels.hip
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $(CSRC)/aided_coh_iq_kernels.hip -o $(LIBDIR)/aided_coh_iq_kernels.o   # the NCO words as refine_kernels.hip
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $(CSRC)/snapshot_iq_kernels.hip -o $(LIBDIR)/snapshot_iq_kernels.o   # the NCO words as refine_kernels.hip
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $(CSRC)/snapq_iq_kernels.hip -o $(LIBDIR)/snapq_iq_kernels.o   # lin and weight as snapq_kernels.hip
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $(CSRC)/gpsacq_nav.cpp -o $(LIBDIR)/gpsacq_nav.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(LIBDIR)/acq_kernels.o $(LIBDIR)/key_kernels.o $(LIBDIR)/iq_kernels.o $(LIBDIR)/gen_kernels.o $(LIBDIR)/track_kernels.o $(LIBDIR)/track_iq_kernels.o $(LIBDIR)/nav_kernels.o $(LIBDIR)/obs_kernels.o $(LIBDIR)/smooth_kernels.o $(LIBDIR)/quality_kernels.o $(LIBDIR)/fix_kernels.o $(LIBDIR)/coarse_kernels.o $(LIBDIR)/refine_kernels.o $(LIBDIR)/snapq_kernels.o $(LIBDIR)/doppler_kernels.o $(LIBDIR)/aided_kernels.o $(LIBDIR)/aided_iq_kernels.o $(LIBDIR)/aided_coh_iq_kernels.o $(LIBDIR)/snapshot_iq_kernels.o $(LIBDIR)/gpsacq_engine.o $(LIBDIR)/gpsacq_multi.o $(LIBDIR)/gpsacq_track.o $(LIBDIR)/gpsacq_nav.o -ldl -pthread
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(LIBDIR)/acq_kernels.o $(LIBDIR)/key_kernels.o $(LIBDIR)/iq_kernels.o $(LIBDIR)/gen_kernels.o $(LIBDIR)/track_kernels.o $(LIBDIR)/track_iq_kernels.o $(LIBDIR)/nav_kernels.o $(LIBDIR)/obs_kernels.o $(LIBDIR)/smooth_kernels.o $(LIBDIR)/quality_kernels.o $(LIBDIR)/fix_kernels.o $(LIBDIR)/coarse_kernels.o $(LIBDIR)/refine_kernels.o $(LIBDIR)/snapq_kernels.o $(LIBDIR)/doppler_kernels.o $(LIBDIR)/aided_kernels.o $(LIBDIR)/aided_iq_kernels.o $(LIBDIR)/aided_coh_iq_kernels.o $(LIBDIR)/snapshot_iq_kernels.o $(LIBDIR)/snapq_iq_kernels.o $(LIBDIR)/gpsacq_engine.o $(LIBDIR)/gpsacq_multi.o $(LIBDIR)/gpsacq_track.o $(LIBDIR)/gpsacq_nav.o -ldl -pthread
 
 host: $(LIBDIR)/libgps_search.so $(BINDIR)/gps_test $(BINDIR)/gps_track $(BINDIR)/hip_floor $(BINDIR)/pk_fma_stream
 # measurement aid of bench.py's roofline: the rate of a pure v_pk_fma_f32 stream on this box (roofline.pk_fma_stream_TF)

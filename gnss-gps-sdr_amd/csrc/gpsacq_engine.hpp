@@ -252,6 +252,12 @@ struct gpsacq_engine {
     Stages<2> aidcohiq_conv_t;  // around the conversion (sign mode)
     Stages<4> aidcohiq_t;       // as aided_coh_t, the search being k_aided_coh_iq (sign mode: k_aided_coh)
     int aidcohiq_ran = 0;       // bit k: stage k + 1 ran a kernel in the last call
+    // snapshot signal quality on an 8-bit IQ capture (gpsacq_snap_floor_iq8*, gpsacq_snap_quality_iq8*,
+    // gpsacq_coarse_fix_quality_iq8_device): the capture of the host-buffer forms goes into d_iq, tasks, records, observations and
+    // info as the 1-bit forms'
+    Scratch<uint64_t> d_chunk_energy;  // k_iq_energy's E: one entry per whole chunk of the capture
+    Scratch<uint64_t> d_snap_floor;    // host-buffer forms, and k_snap_floor's output where the caller wants no floors
+    Stages<2> snapqiq_floor_t, snapqiq_quality_t;  // around k_iq_energy and k_snap_floor, around k_snap_quality_iq (sign mode: k_snap_quality)
     // k_corr<..., PERSIST>: the hand-out state of a launch (9 counters 64 bytes apart, then [8][slots] task slots), zeroed before it
     Scratch<int> d_persist;
     bool persist = false;

@@ -17,7 +17,8 @@
 // aided_kernels.hip, and "Aided acquisition on an 8-bit IQ capture": gpsacq_aided_search_iq8* and gpsacq_aided_peaks_iq8_device, which
 // run aided_iq_kernels.hip (sign mode: the conversion, then k_aided), and "Coherent aided acquisition on an 8-bit IQ capture":
 // gpsacq_aided_coh_search_iq8* and gpsacq_aided_coh_peaks_iq8_device, which run aided_coh_iq_kernels.hip (sign mode: the conversion,
-// then k_aided_coh).
+// then k_aided_coh), and "Snapshot signal quality on an 8-bit IQ capture": gpsacq_snap_floor_iq8*, gpsacq_snap_quality_iq8* and
+// gpsacq_coarse_fix_quality_iq8_device, which run snapq_iq_kernels.hip (sign mode: k_snap_quality).
 // Compiled with -ffp-contract=off: the scaled fields are host floating point that tests pin bit for bit.
 #include <hip/hip_runtime.h>
 
@@ -37,6 +38,7 @@
 #include "aided_iq_launch.hpp"
 #include "aided_launch.hpp"
 #include "smooth_launch.hpp"
+#include "snapq_iq_launch.hpp"
 #include "snapq_launch.hpp"
 #include "snapshot_iq_launch.hpp"
 
@@ -2808,4 +2810,193 @@ extern "C" int gpsacq_aided_coh_iq8_last_ms(const gpsacq_engine* e, float* conve
             if (int rc = e->aidcohiq_t.elapsed(k, k + 1, ms[k])) return rc;
     }
     return GPSACQ_OK;
+}
+
+// ---- snapshot signal quality on an 8-bit IQ capture (snapq_iq_kernels.hip; sign mode: snapq_kernels.hip) ---------------------------
+static constexpr double SNAPQ_IQ_CN0_MIN_LIN = 1432.4;  // the largest lin of 2304 absent draws, 1145.93 Hz, plus a quarter of it
+
+extern "C" int gpsacq_snap_quality_default_params_iq8(gpsacq_snap_quality_params* p) {
+    if (!p) return fail(GPSACQ_ERR_ARG, "gpsacq_snap_quality_default_params_iq8: null argument");
+    std::memset(p, 0, sizeof *p);
+    p->min_segments = 1;
+    p->cn0_min_lin = SNAPQ_IQ_CN0_MIN_LIN;
+    p->cn0_ref_lin = std::pow(10.0, 4.86);  // 48.6 dB-Hz: what the amplitude-0.2 satellites of the bench scene read
+    return GPSACQ_OK;
+}
+
+// the caller's parameters, or the defaults of the capture's mode, into *out, checked
+static int snap_quality_iq_params(const char* who, const IqSnap& s, const gpsacq_snap_quality_params* params, gpsacq_snap_quality_params* out) {
+    if (!params && !s.sign) return gpsacq_snap_quality_default_params_iq8(out);
+    return snap_quality_params(who, params, out);
+}
+
+static int snap_quality_iq_check(const char* who, const gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                                 const void* fine, size_t n_fix, int n_chans, const gpsacq_snap_quality_params* params, const void* info, bool device,
+                                 IqSnap* s, gpsacq_snap_quality_params* checked) {
+    if (n_fix > ((size_t)1 << 31)) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (n_chans < 1 || n_chans > GPSACQ_FIX_MAX_SATS) return fail(GPSACQ_ERR_ARG, "%s: n_chans %d outside 1 .. %d", who, n_chans, GPSACQ_FIX_MAX_SATS);
+    if (int rc = iq_snap_check(who, e, in, iq, n_samples, stride, fine, n_fix * (size_t)n_chans, info, device, s)) return rc;
+    return snap_quality_iq_params(who, *s, params, checked);
+}
+
+static SnapIqCapture snap_iq_capture(const IqSnap& s) { return SnapIqCapture{s.d_iq, s.n_samples, s.flip, s.dc_i, s.dc_q}; }
+
+static SnapWindowArgs snap_window_args(const gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_fine, size_t n_tasks) {
+    return SnapWindowArgs{(const gpsacq_task*)d_tasks, (const gpsacq_fine*)d_fine, n_tasks, s.n_samples, s.stride, e->nlags};
+}
+
+// a call of this section begins: no timer has run
+static void snap_quality_iq_begin(gpsacq_engine* e) { e->snapqiq_floor_t.done = e->snapqiq_quality_t.done = false; }
+
+// k_iq_energy over the capture's whole chunks and k_snap_floor (sign mode: k_snap_floor alone), timed; every argument has been checked
+static int snap_floor_iq_enqueue(gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_fine, size_t n_tasks, void* d_floor) {
+    const size_t n_chunks = s.sign ? 0 : s.n_samples / SNAPQ_CHUNK;
+    if (int rc = e->d_chunk_energy.grow(n_chunks, e->stream)) return rc;
+    if (int rc = e->snapqiq_floor_t.begin(e->stream)) return rc;
+    if (!s.sign) launch_iq_energy(IqEnergyArgs{snap_iq_capture(s), n_chunks, e->d_chunk_energy}, e->stream);
+    launch_snap_floor(SnapFloorArgs{snap_iq_capture(s), snap_window_args(e, s, d_tasks, d_fine, n_tasks), e->d_chunk_energy, n_chunks, s.sign ? 1 : 0,
+                                    (uint64_t*)d_floor},
+                      e->stream);
+    if (int rc = e->snapqiq_floor_t.mark(1, e->stream)) return rc;
+    return e->snapqiq_floor_t.finish();
+}
+
+// k_snap_quality_iq on k_snap_floor's floors, or k_snap_quality in sign mode, timed; every argument has been checked
+static int snap_quality_iq_enqueue(gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_fine, size_t n_fix, int n_chans,
+                                   const gpsacq_snap_quality_params& qp, void* d_obs, const void* d_floor, void* d_info) {
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    if (int rc = e->snapqiq_quality_t.begin(e->stream)) return rc;
+    if (s.sign)
+        launch_snap_quality(SnapQualityArgs{(const gpsacq_fine*)d_fine, n_tasks, e->nlags, e->p.fs, qp, (gpsacq_obs*)d_obs, (gpsacq_quality_info*)d_info},
+                            e->stream);
+    else
+        launch_snap_quality_iq(SnapQualityIqArgs{snap_window_args(e, s, d_tasks, d_fine, n_tasks), (const uint64_t*)d_floor, e->p.fs, qp, (gpsacq_obs*)d_obs,
+                                                 (gpsacq_quality_info*)d_info},
+                               e->stream);
+    if (int rc = e->snapqiq_quality_t.mark(1, e->stream)) return rc;
+    return e->snapqiq_quality_t.finish();
+}
+
+// floors, then quality: in sign mode the floors are written only where the caller asked for them
+static int snap_floor_quality_iq_enqueue(gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_fine, size_t n_fix, int n_chans,
+                                         const gpsacq_snap_quality_params& qp, void* d_obs, void* d_floor, void* d_info) {
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    if (!s.sign || d_floor) {
+        if (int rc = or_own(e, d_floor, e->d_snap_floor, n_tasks)) return rc;
+        if (int rc = snap_floor_iq_enqueue(e, s, d_tasks, d_fine, n_tasks, d_floor)) return rc;
+    }
+    return snap_quality_iq_enqueue(e, s, d_tasks, d_fine, n_fix, n_chans, qp, d_obs, d_floor, d_info);
+}
+
+// the host-buffer forms: the capture (multi-bit mode only: sign mode does not read it), the tasks and the records into engine scratch
+static int snap_quality_iq_upload(gpsacq_engine* e, IqSnap& s, const void* iq, const gpsacq_task* tasks, const gpsacq_fine* fine, size_t n_tasks) {
+    if (!s.sign) {
+        if (int rc = e->d_iq.grow(2 * s.n_samples + 16, e->stream)) return rc;
+        HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * s.n_samples, hipMemcpyHostToDevice, e->stream));
+        s.d_iq = e->d_iq;
+    }
+    if (tasks)
+        if (int rc = upload(e, e->d_refine_tasks, tasks, n_tasks)) return rc;
+    return upload(e, e->d_fine, fine, n_tasks);
+}
+
+extern "C" int gpsacq_snap_floor_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                            const void* d_tasks, const void* d_fine, size_t n_tasks, void* d_floor, int sync) {
+    IqSnap s;
+    if (int rc = iq_snap_check("gpsacq_snap_floor_iq8", e, in, d_iq, n_samples, stride, d_fine, n_tasks, d_floor, true, &s)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    snap_quality_iq_begin(e);
+    if (int rc = snap_floor_iq_enqueue(e, s, d_tasks, d_fine, n_tasks, d_floor)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_snap_floor_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride, const gpsacq_task* tasks,
+                                     const gpsacq_fine* fine, size_t n_tasks, uint64_t* floor_out) {
+    IqSnap s;
+    if (int rc = iq_snap_check("gpsacq_snap_floor_iq8", e, in, iq, n_samples, stride, fine, n_tasks, floor_out, false, &s)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = e->d_snap_floor.grow(n_tasks, e->stream)) return rc;
+    if (int rc = snap_quality_iq_upload(e, s, iq, tasks, fine, n_tasks)) return rc;
+    snap_quality_iq_begin(e);
+    if (int rc = snap_floor_iq_enqueue(e, s, tasks ? e->d_refine_tasks.p : nullptr, e->d_fine, n_tasks, e->d_snap_floor)) return rc;
+    if (int rc = download(e, floor_out, e->d_snap_floor, n_tasks)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_snap_quality_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                              const void* d_tasks, const void* d_fine, size_t n_fix, int n_chans,
+                                              const gpsacq_snap_quality_params* params, void* d_obs, void* d_floor, void* d_info, int sync) {
+    IqSnap s;
+    gpsacq_snap_quality_params qp;
+    if (int rc = snap_quality_iq_check("gpsacq_snap_quality_iq8", e, in, d_iq, n_samples, stride, d_fine, n_fix, n_chans, params, d_info, true, &s, &qp))
+        return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    snap_quality_iq_begin(e);
+    if (int rc = snap_floor_quality_iq_enqueue(e, s, d_tasks, d_fine, n_fix, n_chans, qp, d_obs, d_floor, d_info)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_snap_quality_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                                       const gpsacq_task* tasks, const gpsacq_fine* fine, size_t n_fix, int n_chans,
+                                       const gpsacq_snap_quality_params* params, gpsacq_obs* obs, gpsacq_quality_info* info) {
+    IqSnap s;
+    gpsacq_snap_quality_params qp;
+    if (int rc = snap_quality_iq_check("gpsacq_snap_quality_iq8", e, in, iq, n_samples, stride, fine, n_fix, n_chans, params, info, false, &s, &qp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    const size_t n_obs = n_fix * (size_t)n_chans;
+    if (int rc = e->d_snapq_info.grow(n_obs, e->stream)) return rc;
+    if (int rc = snap_quality_iq_upload(e, s, iq, tasks, fine, n_obs)) return rc;
+    if (obs)
+        if (int rc = upload(e, e->d_coarse_obs, (const gpsacq_obs*)obs, n_obs)) return rc;
+    snap_quality_iq_begin(e);
+    if (int rc = snap_floor_quality_iq_enqueue(e, s, tasks ? e->d_refine_tasks.p : nullptr, e->d_fine, n_fix, n_chans, qp, obs ? e->d_coarse_obs.p : nullptr,
+                                               nullptr, e->d_snapq_info))
+        return rc;
+    if (int rc = download(e, obs, e->d_coarse_obs, n_obs)) return rc;
+    if (int rc = download(e, info, e->d_snapq_info, n_obs)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_coarse_fix_quality_iq8_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_iq8_input* in, const void* d_iq,
+                                                    size_t n_samples, size_t stride, const void* d_tasks, const void* d_peaks, size_t n_fix, int n_chans,
+                                                    const gpsacq_refine_params* refine_par, const gpsacq_snap_quality_params* quality_par,
+                                                    const void* d_prior, const gpsacq_coarse_params* params, void* d_fine, void* d_obs, void* d_floor,
+                                                    void* d_qinfo, void* d_fix, void* d_info, void* d_obs_out, int sync) {
+    const char* who = "gpsacq_coarse_fix_quality_iq8";
+    if (int rc = coarse_obs_check(who, e, d_peaks, n_fix, n_chans, 0.0, d_fix)) return rc;
+    if (!eph || n_eph <= 0 || !d_prior || !d_info) return fail(GPSACQ_ERR_ARG, "%s: bad argument", who);
+    if (d_obs && d_obs_out == d_obs) return fail(GPSACQ_ERR_ARG, "%s: obs_out must not be obs", who);
+    const size_t n_tasks = n_fix * (size_t)n_chans;
+    IqSnap s;
+    gpsacq_refine_params rp;
+    gpsacq_snap_quality_params qp;
+    gpsacq_coarse_params cp;
+    if (int rc = iq_snap_check(who, e, in, d_iq, n_samples, stride, d_peaks, n_tasks, d_fix, true, &s)) return rc;
+    if (int rc = refine_params(who, refine_par, &rp)) return rc;
+    if (int rc = snap_quality_iq_params(who, s, quality_par, &qp)) return rc;
+    if (int rc = coarse_params(who, params, &cp)) return rc;
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = or_own(e, d_fine, e->d_fine, n_tasks)) return rc;
+    if (int rc = or_own(e, d_obs, e->d_coarse_obs, n_tasks)) return rc;
+    if (int rc = or_own(e, d_qinfo, e->d_snapq_info, n_tasks)) return rc;
+    if (int rc = iq_snap_begin(e, s)) return rc;
+    snap_quality_iq_begin(e);
+    if (int rc = refine_iq_enqueue(e, s, d_tasks, d_peaks, n_tasks, rp, d_fine)) return rc;
+    if (int rc = coarse_obs_fine_enqueue(e, d_peaks, d_fine, n_fix, n_chans, rp.snr_min, d_obs)) return rc;
+    if (int rc = snap_floor_quality_iq_enqueue(e, s, d_tasks, d_fine, n_fix, n_chans, qp, d_obs, d_floor, d_qinfo)) return rc;
+    if (int rc = coarse_fix_enqueue(e, eph, n_eph, d_obs, d_prior, n_fix, n_chans, cp, d_fix, d_info, d_obs_out)) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+    return GPSACQ_OK;
+}
+
+extern "C" int gpsacq_snap_quality_iq8_last_ms(const gpsacq_engine* e, float* floor_ms, float* quality_ms) {
+    if (!e || (!e->snapqiq_floor_t.ran() && !e->snapqiq_quality_t.ran()))
+        return fail(GPSACQ_ERR_ARG, "gpsacq_snap_quality_iq8_last_ms: no gpsacq_snap_floor_iq8, gpsacq_snap_quality_iq8 or gpsacq_coarse_fix_quality_iq8 call on this engine");
+    HIPCHK(hipSetDevice(e->p.device));
+    if (int rc = stage_ms(e->snapqiq_floor_t, floor_ms)) return rc;
+    return stage_ms(e->snapqiq_quality_t, quality_ms);
 }

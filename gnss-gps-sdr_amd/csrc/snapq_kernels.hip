@@ -5,53 +5,23 @@
 // k_snap_quality: one lane per (fix, channel), SNAPQ_BLOCK lanes per workgroup, a bounds check on the flat index.  No LDS, no
 // barrier, no atomics, no loop.  Reads 56 bytes, writes the 48-byte info and, where the observation is valid, the 8 bytes of its
 // weight.
+// Steps 2 (sig, noise) to 7 are snapq_device.hpp's snap_quality_info, which k_snap_quality_iq (snapq_iq_kernels.hip) calls too.
 // Built with -ffp-contract=off (Makefile): every step is one IEEE operation, so lin and weight are the reference's to the bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "snapq_device.hpp"
 #include "snapq_launch.hpp"
 
 namespace acq {
-
-namespace {
-constexpr int FINE_UNUSABLE = GPSACQ_FINE_NO_HIT | GPSACQ_FINE_NO_POWER | GPSACQ_FINE_FEW;
-}  // namespace
 
 __global__ __launch_bounds__(SNAPQ_BLOCK) void k_snap_quality(SnapQualityArgs a) {
     const size_t i = (size_t)blockIdx.x * SNAPQ_BLOCK + threadIdx.x;
     if (i >= a.n_obs) return;
     const gpsacq_fine r = a.fine[i];
-    gpsacq_quality_info f;
-    f.epochs = 0;
-    f.flags = GPSACQ_QUALITY_NO_RECORD;
-    f.sig = f.noise = 0;
-    f.lin = f.cn0_dbhz = f.weight = 0.0;
-    if (!(r.flags & FINE_UNUSABLE) && r.segments > 0) {
-        const uint64_t floor = 2 * (uint64_t)a.spm * (uint64_t)r.segments;
-        const uint64_t sig = r.prompt > floor ? r.prompt - floor : 0;
-        int32_t flags = r.segments < a.par.min_segments ? GPSACQ_QUALITY_SHORT : 0;
-        double lin = 0.0, db = 0.0;
-        if (sig == 0) {
-            flags |= GPSACQ_QUALITY_NO_POWER;
-        } else {
-            const double snr = (double)sig / (double)floor;
-            lin = snr * (a.fs / (double)a.spm);
-            db = 10.0 * log10(lin);
-        }
-        double weight = 0.0;
-        const bool gated = (flags & (GPSACQ_QUALITY_NO_POWER | GPSACQ_QUALITY_SHORT)) != 0 || lin < a.par.cn0_min_lin;
-        if (!gated) {
-            const double w = lin / a.par.cn0_ref_lin;
-            weight = w < 1.0 ? w : 1.0;
-        }
-        f.epochs = r.segments;
-        f.flags = flags;
-        f.sig = sig;
-        f.noise = floor;
-        f.lin = lin;
-        f.cn0_dbhz = db;
-        f.weight = weight;
-    }
+    const bool record = !(r.flags & SNAPQ_FINE_UNUSABLE) && r.segments > 0;          // step 1
+    const uint64_t floor = record ? 2 * (uint64_t)a.spm * (uint64_t)r.segments : 0;  // step 2, the analytic floor
+    const gpsacq_quality_info f = snap_quality_info(r, record, floor, a.spm, a.fs, a.par);
     a.info[i] = f;
     if (a.obs && a.obs[i].valid != 0) a.obs[i].weight = f.weight;
 }

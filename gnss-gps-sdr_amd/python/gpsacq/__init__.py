@@ -213,7 +213,9 @@ EXPORTS = ["gpsacq_generate", "gpsacq_generate_device", "gpsacq_generate_range",
            "gpsacq_aid_instant", "gpsacq_aid_instant_device", "gpsacq_aided_coh_peaks_device", "gpsacq_aided_coh_last_ms",
            "gpsacq_aided_default_params_iq8", "gpsacq_aided_search_iq8", "gpsacq_aided_search_iq8_device", "gpsacq_aided_peaks_iq8_device",
            "gpsacq_aided_iq8_last_ms", "gpsacq_aided_coh_default_params_iq8", "gpsacq_aided_coh_search_iq8", "gpsacq_aided_coh_search_iq8_device",
-           "gpsacq_aided_coh_peaks_iq8_device", "gpsacq_aided_coh_iq8_last_ms"]
+           "gpsacq_aided_coh_peaks_iq8_device", "gpsacq_aided_coh_iq8_last_ms",
+           "gpsacq_snap_quality_default_params_iq8", "gpsacq_snap_floor_iq8", "gpsacq_snap_floor_iq8_device", "gpsacq_snap_quality_iq8",
+           "gpsacq_snap_quality_iq8_device", "gpsacq_coarse_fix_quality_iq8_device", "gpsacq_snap_quality_iq8_last_ms"]
 
 _lib = None
 
@@ -607,6 +609,21 @@ def load_library(path=None):
     lib.gpsacq_aided_coh_peaks_iq8_device.restype = ctypes.c_int
     lib.gpsacq_aided_coh_iq8_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 4
     lib.gpsacq_aided_coh_iq8_last_ms.restype = ctypes.c_int
+    lib.gpsacq_snap_quality_default_params_iq8.argtypes = [vp]
+    lib.gpsacq_snap_quality_default_params_iq8.restype = ctypes.c_int
+    lib.gpsacq_snap_floor_iq8.argtypes = [vp, iqp, vp, sz, sz, vp, vp, sz, vp]
+    lib.gpsacq_snap_floor_iq8.restype = ctypes.c_int
+    lib.gpsacq_snap_floor_iq8_device.argtypes = [vp, iqp, vp, sz, sz, vp, vp, sz, vp, ctypes.c_int]
+    lib.gpsacq_snap_floor_iq8_device.restype = ctypes.c_int
+    lib.gpsacq_snap_quality_iq8.argtypes = [vp, iqp, vp, sz, sz, vp, vp, sz, ctypes.c_int, vp, vp, vp]
+    lib.gpsacq_snap_quality_iq8.restype = ctypes.c_int
+    lib.gpsacq_snap_quality_iq8_device.argtypes = [vp, iqp, vp, sz, sz, vp, vp, sz, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int]
+    lib.gpsacq_snap_quality_iq8_device.restype = ctypes.c_int
+    lib.gpsacq_coarse_fix_quality_iq8_device.argtypes = [vp, vp, ctypes.c_int, iqp, vp, sz, sz, vp, vp, sz, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                         vp, vp, ctypes.c_int]
+    lib.gpsacq_coarse_fix_quality_iq8_device.restype = ctypes.c_int
+    lib.gpsacq_snap_quality_iq8_last_ms.argtypes = [vp] + [ctypes.POINTER(ctypes.c_float)] * 2
+    lib.gpsacq_snap_quality_iq8_last_ms.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -940,6 +957,20 @@ def snap_quality_params(min_segments=1, cn0_min_dbhz=None, cn0_ref_dbhz=None, **
             raise TypeError("snap_quality_params: no field %r" % k)
         out[k] = v
     return out
+
+
+def snap_quality_params_iq8(min_segments=1, cn0_min_dbhz=None, cn0_ref_dbhz=None, **overrides):
+    """gpsacq_snap_quality_default_params_iq8: snap_quality_params() with the gate and the reference level measured for the multi-bit
+    records of refine_iq8() (include/gpsacq.h, "Snapshot signal quality on an 8-bit IQ capture": cn0_min_lin 1432.4, 31.6 dB-Hz, and
+    cn0_ref_lin 10^4.86, 48.6 dB-Hz), then the arguments applied as snap_quality_params() applies them."""
+    lib = load_library()
+    d = np.zeros(1, dtype=SNAP_QUALITY_PARAMS_DTYPE)
+    _check(lib, lib.gpsacq_snap_quality_default_params_iq8(d.ctypes.data_as(ctypes.c_void_p)))
+    if cn0_min_dbhz is None:
+        overrides.setdefault("cn0_min_lin", float(d["cn0_min_lin"][0]))
+    if cn0_ref_dbhz is None:
+        overrides.setdefault("cn0_ref_lin", float(d["cn0_ref_lin"][0]))
+    return snap_quality_params(min_segments, cn0_min_dbhz, cn0_ref_dbhz, **overrides)
 
 
 def code_sigma_m(info):
@@ -2087,6 +2118,86 @@ class Engine:
         search kernel)."""
         t = [ctypes.c_float() for _ in range(4)]
         _check(self._lib, self._lib.gpsacq_aided_coh_iq8_last_ms(self._h, *[ctypes.byref(x) for x in t]))
+        return tuple(x.value for x in t)
+
+    # ---- snapshot signal quality on an 8-bit IQ capture ---------------------------------------
+    @staticmethod
+    def _iq8_fine_tasks(iq, fine, tasks):
+        buf = np.ascontiguousarray(np.asarray(iq).view(np.uint8).ravel())
+        if not isinstance(fine, np.ndarray) or fine.dtype != FINE_DTYPE:
+            raise TypeError("fine must be a FINE_DTYPE array")
+        fn = np.ascontiguousarray(fine)
+        t = None
+        if tasks is not None:
+            t = np.ascontiguousarray(np.asarray(tasks, dtype=np.int32).reshape(-1, 2))
+            if t.shape[0] != fn.size:
+                raise ValueError("one task per fine record")
+        return buf, fn, t
+
+    def snap_floor_iq8(self, iq, inp, fine, tasks=None, stride=16 * BLOCK_BYTES, n_samples=None):
+        """gpsacq_snap_floor_iq8: the measured noise floor 2 * sum (v_i^2 + v_q^2) over the window of every fine record (FINE_DTYPE,
+        as refine_iq8() returned them for these tasks with the same inp and stride); 0 where the record is not usable or not of this
+        capture; 2 * spm * segments in sign mode.  Returns uint64 in the shape of fine."""
+        buf, fn, t = self._iq8_fine_tasks(iq, fine, tasks)
+        n = buf.size // 2 if n_samples is None else int(n_samples)
+        out = np.zeros(fn.shape, dtype=np.uint64)
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_snap_floor_iq8(self._h, ctypes.byref(inp), p(buf), n, int(stride), p(t), p(fn), int(fn.size), p(out)))
+        return out
+
+    def snap_floor_iq8_device(self, inp, d_iq_ptr, n_samples, d_fine_ptr, n_tasks, d_floor_ptr, stride=16 * BLOCK_BYTES, d_tasks_ptr=None, sync=True):
+        """gpsacq_snap_floor_iq8_device: device pointers for the capture (16-byte aligned), the records, the tasks (None: the
+        reference schedule) and the floors."""
+        _check(self._lib, self._lib.gpsacq_snap_floor_iq8_device(self._h, ctypes.byref(inp), d_iq_ptr, int(n_samples), int(stride), d_tasks_ptr, d_fine_ptr,
+                                                                 int(n_tasks), d_floor_ptr, 1 if sync else 0))
+
+    def snap_quality_iq8(self, iq, inp, fine, tasks=None, obs=None, stride=16 * BLOCK_BYTES, params=None, n_samples=None):
+        """gpsacq_snap_quality_iq8: snap_quality() for the records of refine_iq8() (FINE_DTYPE [n_fix][n_chans]) against the floor
+        measured on the capture's own bytes; params: snap_quality_params_iq8() (None: those in multi-bit mode, snap_quality_params()
+        in sign mode).  Returns (None or a copy of obs with the weights set, info QUALITY_INFO_DTYPE [n_fix][n_chans])."""
+        if not isinstance(fine, np.ndarray) or fine.ndim != 2:
+            raise TypeError("fine must be a FINE_DTYPE array [n_fix][n_chans]")
+        buf, fn, t = self._iq8_fine_tasks(iq, fine, tasks)
+        n = buf.size // 2 if n_samples is None else int(n_samples)
+        ob = None
+        if obs is not None:
+            if not isinstance(obs, np.ndarray) or obs.dtype != OBS_DTYPE or obs.shape != fn.shape:
+                raise TypeError("obs must be an OBS_DTYPE array in the shape of fine")
+            ob = np.array(obs, order="C")
+        pr, pp = self._snap_quality_params(params)
+        inf = np.zeros(fn.shape, dtype=QUALITY_INFO_DTYPE)
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(self._lib, self._lib.gpsacq_snap_quality_iq8(self._h, ctypes.byref(inp), p(buf), n, int(stride), p(t), p(fn), int(fn.shape[0]),
+                                                            int(fn.shape[1]), pp, p(ob), p(inf)))
+        return ob, inf
+
+    def snap_quality_iq8_device(self, inp, d_iq_ptr, n_samples, d_fine_ptr, n_fix, n_chans, d_info_ptr, d_obs_ptr=None, d_floor_ptr=None,
+                                stride=16 * BLOCK_BYTES, d_tasks_ptr=None, params=None, sync=True):
+        """gpsacq_snap_quality_iq8_device: the capture, the records, the info, the in-out observations (may be None) and the floors
+        (may be None: engine scratch) in device memory."""
+        pr, pp = self._snap_quality_params(params)
+        _check(self._lib, self._lib.gpsacq_snap_quality_iq8_device(self._h, ctypes.byref(inp), d_iq_ptr, int(n_samples), int(stride), d_tasks_ptr,
+                                                                   d_fine_ptr, int(n_fix), int(n_chans), pp, d_obs_ptr, d_floor_ptr, d_info_ptr,
+                                                                   1 if sync else 0))
+
+    def coarse_fix_quality_iq8_device(self, eph, inp, d_iq_ptr, n_samples, d_tasks_ptr, d_peaks_ptr, n_fix, n_chans, d_prior_ptr, d_fix_ptr, d_info_ptr,
+                                      d_fine_ptr=None, d_obs_ptr=None, d_floor_ptr=None, d_qinfo_ptr=None, d_obs_out_ptr=None, stride=16 * BLOCK_BYTES,
+                                      refine_params=None, quality_params=None, params=None, sync=True):
+        """gpsacq_coarse_fix_quality_iq8_device: coarse_fix_quality_device() on an 8-bit IQ capture -- refine, observations, measured
+        floors, weights and fix on one stream; d_fine_ptr, d_obs_ptr, d_floor_ptr, d_qinfo_ptr and d_obs_out_ptr may be None."""
+        ep = np.ascontiguousarray(np.asarray(eph, dtype=EPHEMERIS_DTYPE).ravel())
+        rr, rp = self._refine_params(refine_params)
+        qr, qp = self._snap_quality_params(quality_params)
+        cr, cp = self._coarse_params(params)
+        _check(self._lib, self._lib.gpsacq_coarse_fix_quality_iq8_device(self._h, ep.ctypes.data_as(ctypes.c_void_p), int(ep.size), ctypes.byref(inp),
+                                                                         d_iq_ptr, int(n_samples), int(stride), d_tasks_ptr, d_peaks_ptr, int(n_fix),
+                                                                         int(n_chans), rp, qp, d_prior_ptr, cp, d_fine_ptr, d_obs_ptr, d_floor_ptr,
+                                                                         d_qinfo_ptr, d_fix_ptr, d_info_ptr, d_obs_out_ptr, 1 if sync else 0))
+
+    def snap_quality_iq8_last_ms(self):
+        """Device milliseconds of the last snapshot-quality *_iq8 call: (k_iq_energy and k_snap_floor together or 0, the quality kernel or 0)."""
+        t = [ctypes.c_float() for _ in range(2)]
+        _check(self._lib, self._lib.gpsacq_snap_quality_iq8_last_ms(self._h, *[ctypes.byref(x) for x in t]))
         return tuple(x.value for x in t)
 
     def coarse_obs_device(self, d_peaks_ptr, n_fix, n_chans, d_obs_ptr, snr_min=THRESHOLD, sync=True):

@@ -1769,9 +1769,10 @@ GPSACQ_API int gpsacq_refine_last_ms(const gpsacq_engine* e, float* refine_ms, f
  * variance of the fine code phase within a factor of about two, on the conservative side (amplitudes 0.2 .. 0.03 at 16 blocks:
  * variance ratio 1 .. 0.05, weight 1 .. 0.024), and make no claim below cn0_min_lin.
  *
- * OUT OF SCOPE.  Whole-sample observations without a fine record, a measured noise floor, per-observation sigmas in
- * gpsacq_raim_params, gps_test and gps_track.  The records of a multi-bit gpsacq_refine_iq8 ("Snapshot chain on an 8-bit IQ capture"
- * below): the analytic floor of step 2 is that of a +-1 stream, and their prompt power scales with the capture's amplitude.
+ * OUT OF SCOPE.  Whole-sample observations without a fine record, per-observation sigmas in gpsacq_raim_params, gps_test and
+ * gps_track.  The records of a multi-bit gpsacq_refine_iq8 ("Snapshot chain on an 8-bit IQ capture" below) do not belong here: the
+ * analytic floor of step 2 is that of a +-1 stream, and their prompt power scales with the capture's amplitude.  Their floor is
+ * measured: "Snapshot signal quality on an 8-bit IQ capture", gpsacq_snap_quality_iq8.
  *
  * gpsacq_snap_quality: host pointers, returns after completion; obs in-out and may be NULL.  gpsacq_snap_quality_device: fine, obs
  * (may be NULL) and info are device pointers, params stays a host pointer; work on the engine's stream, sync != 0 waits.  The two
@@ -2033,11 +2034,11 @@ GPSACQ_API int gpsacq_doppler_last_ms(const gpsacq_engine* e, float* fine_dop_ms
  * LDS; int32 sums per lane, xor shuffles over the wave, 64-bit integer squares; no atomics and no float before the estimate, so
  * the record does not depend on the order of anything.  Every loop is bounded by kernel arguments.
  *
- * gpsacq_snap_quality* stays for 1-bit records (sign mode's included): its analytic floor is that of a +-1 stream.
+ * gpsacq_snap_quality* stays for 1-bit records (sign mode's included): its analytic floor is that of a +-1 stream.  The multi-bit
+ * records' floor is measured on the capture: "Snapshot signal quality on an 8-bit IQ capture" below, gpsacq_snap_quality_iq8.
  *
- * OUT OF SCOPE.  A noise floor for multi-bit records (gpsacq_snap_quality).  (The aided searches on the IQ bytes are "Aided
- * acquisition on an 8-bit IQ capture" and "Coherent aided acquisition on an 8-bit IQ capture" below.)  Accumulated or re-aligned
- * searches, multi-GPU, gps_test and gps_track.
+ * OUT OF SCOPE.  (The aided searches on the IQ bytes are "Aided acquisition on an 8-bit IQ capture" and "Coherent aided acquisition
+ * on an 8-bit IQ capture" below.)  Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.
  */
 GPSACQ_API int gpsacq_refine_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride, const gpsacq_task* tasks,
                                  const gpsacq_peak* peaks, size_t n_tasks, const gpsacq_refine_params* params, gpsacq_fine* fine_out);
@@ -2495,8 +2496,8 @@ GPSACQ_API int gpsacq_aided_coh_last_ms(const gpsacq_engine* e, float* instant_m
  * The floor is summed once per segment from the same bytes.  No atomics, no float before the ratio.  Every loop is bounded by
  * kernel arguments, every LDS index by the host-checked limits (spm <= 65535, W <= 127, K <= 8).  DESIGN.md 8.9 has the rest.
  *
- * OUT OF SCOPE.  The measured floor for gpsacq_snap_quality on gpsacq_refine_iq8 records (the floor law above is the one it would
- * use).  Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.  (The multi-bit coherent search is the next section.)
+ * OUT OF SCOPE.  Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.  (The multi-bit coherent search is the next
+ * section; the weights of gpsacq_refine_iq8 records from the floor law above are "Snapshot signal quality on an 8-bit IQ capture".)
  */
 GPSACQ_API int gpsacq_aided_default_params_iq8(gpsacq_aided_params* p);   /* host only */
 GPSACQ_API int gpsacq_aided_search_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
@@ -2618,8 +2619,8 @@ GPSACQ_API int gpsacq_aided_iq8_last_ms(const gpsacq_engine* e, float* convert_m
  * per CU.  No atomics, no scratch, no float before the ratio; every loop is bounded by kernel arguments, every LDS index by the
  * host-checked limits.  DESIGN.md 8.10 has the rest.
  *
- * OUT OF SCOPE.  W above 31.  A measured floor for gpsacq_snap_quality.  Accumulated or re-aligned searches, multi-GPU, gps_test and
- * gps_track.
+ * OUT OF SCOPE.  W above 31.  Accumulated or re-aligned searches, multi-GPU, gps_test and gps_track.  (C/N0 and weights for the peaks
+ * found here: the next section.)
  */
 GPSACQ_API int gpsacq_aided_coh_default_params_iq8(gpsacq_aided_coh_params* p);   /* host only */
 GPSACQ_API int gpsacq_aided_coh_search_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
@@ -2638,6 +2639,117 @@ GPSACQ_API int gpsacq_aided_coh_peaks_iq8_device(gpsacq_engine* e, const gpsacq_
  * 1-bit conversion (sign mode), k_aid_instant and k_aid_predict (the chain) and the search (k_aided_coh_iq, in sign mode k_aided_coh).
  * A kernel that the last call did not run reads 0.  Any pointer may be NULL. */
 GPSACQ_API int gpsacq_aided_coh_iq8_last_ms(const gpsacq_engine* e, float* convert_ms, float* instant_ms, float* predict_ms, float* search_ms);
+
+/*
+ * ---- Snapshot signal quality on an 8-bit IQ capture: measured floor, C/N0 and weights ----------------------------------------------
+ *
+ * gpsacq_aided_search_iq8 and gpsacq_aided_coh_search_iq8 dig out satellites 10 to 15 dB below the search threshold, their peaks go
+ * through gpsacq_refine_iq8 and gpsacq_coarse_obs_fine into gpsacq_coarse_fix_batch -- at weight 1.0, the problem "Snapshot signal
+ * quality" solved for the 1-bit chain.  Its floor, 2 * spm * segments, is that of a +-1 stream; the prompt power of a multi-bit record
+ * scales with the capture's amplitude.  This section measures the floor on the capture's own bytes, by the law of "Aided acquisition
+ * on an 8-bit IQ capture", step 5, and everything after the floor is "Snapshot signal quality" word for word.  THE MODEL; the kernels
+ * (csrc/snapq_iq_kernels.hip) and the reference of the tests (tests/snapq_iq_ref.py) are both written from this text.
+ *
+ * INPUTS.  `in`, iq[2 * n_samples], n_samples and stride exactly as for gpsacq_refine_iq8: stride in BYTES, a multiple of 16,
+ * 80000 <= stride <= 2^31; the device form takes a 16-byte-aligned device pointer.  tasks[n_tasks] (NULL: the reference schedule,
+ * task t = block t).  fine[n_fix][n_chans]: the records gpsacq_refine_iq8 returned for those tasks with the same `in` and stride,
+ * n_tasks = n_fix * n_chans, index-parallel.  A gpsacq_snap_quality_params.  spm = gpsacq_info.num_lags and fs are the engine's.
+ *
+ * in->multibit != 0 (GPSACQ_SAMPLES_REAL and GPSACQ_SAMPLES_COMPLEX alike): THE MULTI-BIT PATH, per record.
+ * 1. NO RECORD is step 1 of "Snapshot signal quality" (a flag of GPSACQ_FINE_NO_HIT, _NO_POWER, _FEW, or segments <= 0), and also
+ *    a record that is not of this capture: with o = block * (stride / 2), a block < 0, o beyond n_samples or o + segments * spm
+ *    beyond n_samples.  The info is the flag GPSACQ_QUALITY_NO_RECORD and zeros, the floor reads 0, the weight is 0.  Nothing at or
+ *    beyond byte 2 * n_samples is read, and such a record reads no byte at all.
+ * 2. FLOOR.
+ *      floor = 2 * (sum over the samples o .. o + segments * spm - 1 of v_i^2 + v_q^2)
+ *    with v the SAMPLE of "Snapshot chain on an 8-bit IQ capture": v = byte - off - dc, off = 128 for GPSACQ_IQ_U8 and 0 for
+ *    GPSACQ_IQ_S8, dc = nearbyint(mean) (ties to even) when remove_dc, else 0.  The window is the record's own `segments`: there is no
+ *    blocks parameter that could disagree with the record.  uint64, below 2^46 by that section's bound (2 * 2^17 per sample, fewer than
+ *    2^12 segments of at most 65535 samples for a record of gpsacq_refine_iq8).  For the same task, blocks and min_segments it is bit
+ *    for bit the `floor` field of gpsacq_aided_search_iq8's record (a test uses it), and for a +-1 real stream it is 2 * spm * segments.
+ *    floor == 0 (an all-zero window): sig = 0, noise = 0 and the flag GPSACQ_QUALITY_NO_POWER, as step 3 below has it.
+ * 3. sig = prompt > floor ? prompt - floor : 0 and noise = floor; then steps 3 to 7 of "Snapshot signal quality" word for word: snr,
+ *    lin, cn0_dbhz, GPSACQ_QUALITY_SHORT, the gate, the weight.  The INFO record and THE OBSERVATION are that section's.
+ *
+ * in->multibit == GPSACQ_SAMPLES_SIGN: the records are 1-bit records, the capture is not read, and the result is byte for byte
+ * gpsacq_snap_quality's; gpsacq_snap_floor_iq8 writes 2 * spm * segments, 0 where step 1 of "Snapshot signal quality" says NO RECORD.
+ *
+ * PARAMETERS.  gpsacq_snap_quality_default_params_iq8 (host only): min_segments 1, reserved 0, cn0_min_lin 1432.4, cn0_ref_lin
+ * 10^(48.6/10) (pow(10.0, 4.86)); the valid ranges are gpsacq_snap_quality_default_params'.  params NULL = these in multi-bit mode and
+ * gpsacq_snap_quality_default_params' in sign mode.  Both are CPU measurements with the references alone, no GPU:
+ *   THE REFERENCE LEVEL is the median C/N0 of the amplitude-0.2 satellites of the bench scene rounded to 0.1 dB, as the 1-bit default
+ *   was set: `python tools/snap_quality_law.py --iq8 --scene bench` (60 captures of the eight satellites as an 8-bit IQ capture by
+ *   tests/gen_ref.py: int8, scale 16, sigma 1, IF 0.4 MHz, the mean not removed; tests/refine_iq_ref.py, tests/snapq_iq_ref.py) reads a
+ *   median of 48.565 dB-Hz over 480 records (47.96 .. 48.94).  That is 5.0 dB above the 1-bit chain's 43.5: the arm and the limiter.
+ *   THE GATE.  The largest lin of absent PRNs, one hypothesis each at a random code phase and Doppler bin, on the scene of
+ *   tools/aided_floor.py --iq8: `python tools/snap_quality_floor.py` (2304 draws: 8 window starts x 6 bins x 24 absent PRNs x 2 code
+ *   phases, 16-block windows) reads at most 1145.93 Hz (median 270.13, 99.9 % below 1069.02).  The default is the larger of 500.0 and
+ *   that maximum plus a quarter of it: 1145.93 + 286.48 = 1432.4 Hz (31.6 dB-Hz).  Noise alone would stand at 92 Hz as in "Snapshot
+ *   signal quality"; the rest is the C/A cross-correlation of eight satellites at 0.2, which keeps both arms and passes no limiter here
+ *   exactly as the signal sought does (as DEFAULT RATIO_MIN of "Aided acquisition on an 8-bit IQ capture" found).  A caller with fewer
+ *   or weaker satellites beside the signal measures a lower gate with the same tool and keeps more: on a scene of four satellites at
+ *   0.2 (tests/test_snap_quality_iq.py, 24 captures) 48 absent records read at most 384 Hz and an amplitude of 0.025 reads 756 Hz
+ *   and more.
+ *
+ * LIMITS OF THE MODEL.  The figure is C over (N0 plus every other satellite's power in the band), not C / N0 of the antenna: the
+ * floor is everything in the samples, the strong satellites included -- four of them at 0.2 beside sigma 1 are 0.08 of the power,
+ * about 0.3 dB -- and the satellite's own power too.  The prompt replica sits at the peak's whole sample and bin, as in "Snapshot
+ * signal quality" (up to 0.9 dB and 0.07 dB low).  An aided peak is the largest of its hypotheses and reads high.  The weights against
+ * the measured range variance, on the CPU (`python tools/snap_quality_law.py --iq8`, 60 captures, amplitudes 0.2 .. 0.03 at 16
+ * blocks): C/N0 48.5, 42.6, 39.5, 36.7, 34.9 and 32.7 dB-Hz, variance ratio 1, 0.85, 0.42, 0.18, 0.13 and 0.07; the table of the
+ * weights is in README.md.  No claim below cn0_min_lin.
+ *
+ * THE ENERGY PASS.  Every call of the multi-bit path reads the capture once, bytes 0 .. 2 * n_samples - 1 whatever the tasks are
+ * (k_iq_energy, below), into engine scratch of n_samples / 1024 uint64: a caller with few tasks on a long capture passes the stretch
+ * its tasks lie in.  The floors then cost a few reads per task.  Measured on an MI355X (tools/snapshot_bench.py --iq8 --aided
+ * --quality: 2048 blocks, a 169 MB capture that k_refine_iq had just read, 24 576 records, HIP events, best of 5, shader clock not
+ * read): k_iq_energy and k_snap_floor together 0.044 ms and k_snap_quality_iq 0.007 ms beside k_refine_iq 26.42 ms of the same call,
+ * and a device-to-device copy of the same capture 0.074 ms in the same run; the strong satellites read 48.37 dB-Hz in the median and
+ * the weak pair at amplitude 0.05 36.60; position error of the same 2048 blocks, median / worst, 3.53 / 11.75 m from the strong
+ * eight, 4.02 / 11.93 m with the weak pair at unit weight, 3.40 / 11.31 m with these weights.  A capture that is not in cache was
+ * not measured.
+ *
+ * gpsacq_snap_floor_iq8 writes floor_out[n_tasks], 0 where step 1 says NO RECORD.  gpsacq_snap_quality_iq8: obs in-out and may be
+ * NULL, info out.  Host pointers, return after completion.  The _device forms: iq, tasks, fine, obs, floor and info are device
+ * pointers, `in` and params stay host pointers; work on the engine's stream, sync != 0 waits; host and device form agree byte for
+ * byte.  d_floor[n_tasks] of gpsacq_snap_quality_iq8_device and of the chain may be NULL (engine scratch), as d_fine elsewhere; in
+ * sign mode it is written only where it is given.  gpsacq_coarse_fix_quality_iq8_device is gpsacq_coarse_fix_quality_device with (in,
+ * d_iq, n_samples) for (d_bits, n_bytes): refine, observations, floors, weights and fix on one stream with no host copy in between,
+ * the same optional buffers.  Argument errors are those of gpsacq_refine_iq8 with fine for peaks -- a NULL in, iq, fine or output, no
+ * task, a format or multibit value that gpsacq_search_iq8 refuses, a mean beyond +-128 where it is removed, a stride outside the
+ * bounds above, a misaligned device pointer -- plus n_chans outside 1..GPSACQ_FIX_MAX_SATS, a parameter out of range and for the
+ * chain those of gpsacq_coarse_fix_fine_iq8_device: GPSACQ_ERR_ARG, nothing launched and nothing written.
+ * Kernels (csrc/snapq_iq_kernels.hip).  k_iq_energy: one streaming pass, one wave64 per chunk of 1024 samples; 16-byte loads, bytes
+ * XORed with 0x80 for GPSACQ_IQ_U8, the squares of a dword as its 4 x int8 dot product with itself, the mean as the exact correction
+ * S2 - 2 (dc_i S_i + dc_q S_q) + n (dc_i^2 + dc_q^2) only where it is not zero; xor shuffles, one writer per chunk.  k_snap_floor: one
+ * wave64 per task; the window is a head up to the next chunk boundary, whole chunks (their E entries, summed by the wave) and a tail;
+ * only head and tail are read from the bytes.  k_snap_quality_iq: one lane per (fix, channel), k_snap_quality's arithmetic
+ * (csrc/snapq_device.hpp, one copy for both).  No atomics, no float before snr, nothing that depends on an order; every loop is
+ * bounded by kernel arguments.  DESIGN.md 8.11 has the rest.
+ *
+ * OUT OF SCOPE.  Per-observation sigmas in gpsacq_raim_params, weights for whole-sample observations without a fine record, a floor
+ * for the tracking chain's multi-bit channels, gps_test and gps_track, multi-GPU.
+ */
+GPSACQ_API int gpsacq_snap_quality_default_params_iq8(gpsacq_snap_quality_params* p);   /* host only */
+GPSACQ_API int gpsacq_snap_floor_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                                     const gpsacq_task* tasks, const gpsacq_fine* fine, size_t n_tasks, uint64_t* floor_out);
+GPSACQ_API int gpsacq_snap_floor_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                            const void* d_tasks, const void* d_fine, size_t n_tasks, void* d_floor, int sync);
+GPSACQ_API int gpsacq_snap_quality_iq8(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* iq, size_t n_samples, size_t stride,
+                                       const gpsacq_task* tasks, const gpsacq_fine* fine /* [n_fix][n_chans] */, size_t n_fix, int n_chans,
+                                       const gpsacq_snap_quality_params* params, gpsacq_obs* obs /* in-out, or NULL */, gpsacq_quality_info* info);
+GPSACQ_API int gpsacq_snap_quality_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
+                                              const void* d_tasks, const void* d_fine, size_t n_fix, int n_chans,
+                                              const gpsacq_snap_quality_params* params, void* d_obs, void* d_floor, void* d_info, int sync);
+GPSACQ_API int gpsacq_coarse_fix_quality_iq8_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const gpsacq_iq8_input* in, const void* d_iq,
+                                                    size_t n_samples, size_t stride, const void* d_tasks, const void* d_peaks, size_t n_fix, int n_chans,
+                                                    const gpsacq_refine_params* refine_params, const gpsacq_snap_quality_params* quality_params,
+                                                    const void* d_prior, const gpsacq_coarse_params* params, void* d_fine, void* d_obs, void* d_floor,
+                                                    void* d_qinfo, void* d_fix, void* d_info, void* d_obs_out, int sync);
+/* device time of the last call of this section on this engine, milliseconds (HIP events on its stream; waits for them): the floor
+ * kernels (k_iq_energy and k_snap_floor together) and the quality kernel (k_snap_quality_iq, in sign mode k_snap_quality).  A stage
+ * that the last call did not run reads 0.  Either pointer may be NULL. */
+GPSACQ_API int gpsacq_snap_quality_iq8_last_ms(const gpsacq_engine* e, float* floor_ms, float* quality_ms);
 
 /* SearchCode(): chips to clock PRN sv's generator until its G1 register reads g1 (-1 if never) */
 GPSACQ_API int gpsacq_search_code(int sv, int g1);

@@ -88,6 +88,16 @@ read), what one group walk per hypothesis would cost (tasks searched x hypothese
 detected and at the true code phase, the false detections and ratios on the absent tasks both ways, and the position error of the
 same blocks with and without the weak pair.
 
+--iq8 --aided --quality: the --iq8 --aided run (--quality implies --aided) with the merged multi-bit peaks fixed a third time: each
+repetition also runs gpsacq_coarse_fix_quality_iq8_device on them ("Snapshot signal quality on an 8-bit IQ capture" of
+include/gpsacq.h, the defaults of gpsacq_snap_quality_default_params_iq8) -- k_refine_iq, k_coarse_obs_fine, k_iq_energy, k_snap_floor,
+k_snap_quality_iq and k_coarse_fix at snr_min = ratio_min.  The line gains a "quality" object, all from one run: snap_floor_ms
+(k_iq_energy and k_snap_floor together) and snap_quality_ms (best of the repetitions, HIP events) beside refine_iq_ms of the same
+calls; capture_copy_ms, a device-to-device copy of the same capture in the same run (the streaming bound the energy pass is held
+against; no threshold on any of these is a pass condition); the C/N0 the eight strong satellites and the detected weak ones read
+(median, least, largest) and their weights; and the position error (median, worst) of the SAME blocks three ways: from the strong
+eight only, with the weak pair at unit weight, with the weak pair weighted.
+
 --iq8 --aided-coh: the --iq8 --aided scene with random navigation bits on every satellite and the weak pair at --weak-amplitude
 (default 0.03 here), fixed from the strong ones, and then on the same tasks in the same run ("Coherent aided acquisition on an 8-bit
 IQ capture" of include/gpsacq.h): gpsacq_aided_coh_peaks_iq8_device in multi-bit mode (k_aided_coh_iq, the defaults of
@@ -249,6 +259,11 @@ def main_iq8_aided(a):
         d_peaks, d_fine = zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize), zeros(n_tasks * gpsacq.FINE_DTYPE.itemsize)
         d_fix_f, d_info_f = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
         d_fix_a, d_info_a = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
+        if a.quality:
+            d_fix_q, d_info_q = zeros(a.blocks * gpsacq.FIX_DTYPE.itemsize), zeros(a.blocks * gpsacq.COARSE_INFO_DTYPE.itemsize)
+            d_qinfo, d_copy = zeros(n_tasks * gpsacq.QUALITY_INFO_DTYPE.itemsize), zeros(2 * n_samples)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            floor_best = quality_best = refine_q_best = copy_best = float("inf")
         buf = {k: dict(aided=zeros(n_tasks * gpsacq.AIDED_DTYPE.itemsize), peaks=zeros(n_tasks * gpsacq.PEAK_DTYPE.itemsize)) for k in modes}
         inp = {"multibit": eng.iq8_input(signed=True, remove_dc=False, mix_hz=FC - a.if_hz, multibit=1),
                "sign": eng.iq8_input(signed=True, remove_dc=False, mix_hz=FC - a.if_hz, multibit=0)}  # GPSACQ_SAMPLES_REAL, GPSACQ_SAMPLES_SIGN
@@ -284,6 +299,20 @@ def main_iq8_aided(a):
                                            a.blocks, m, d_prior.data_ptr(), d_fix_a.data_ptr(), d_info_a.data_ptr(), stride=stride, refine_params=rp_a,
                                            sync=True)
             refine_a_best = min(refine_a_best, eng.snapshot_iq8_last_ms()[1])
+            if a.quality:  # the merged peaks once more, the weights between the observations and the fix
+                eng.coarse_fix_quality_iq8_device(ephs, inp["multibit"], d_iq.data_ptr(), n_samples, d_tasks.data_ptr(), buf["multibit"]["peaks"].data_ptr(),
+                                                  a.blocks, m, d_prior.data_ptr(), d_fix_q.data_ptr(), d_info_q.data_ptr(), d_qinfo_ptr=d_qinfo.data_ptr(),
+                                                  stride=stride, refine_params=rp_a, sync=True)
+                fl, ql = eng.snap_quality_iq8_last_ms()
+                floor_best, quality_best, refine_q_best = min(floor_best, fl), min(quality_best, ql), min(refine_q_best, eng.snapshot_iq8_last_ms()[1])
+                ev[0].record()
+                d_copy.copy_(d_iq)
+                ev[1].record()
+                torch.cuda.synchronize()
+                copy_best = min(copy_best, ev[0].elapsed_time(ev[1]))
+        if a.quality:
+            fix_q, info_q = d_fix_q.cpu().numpy().view(gpsacq.FIX_DTYPE), d_info_q.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
+            qinfo = d_qinfo.cpu().numpy().view(gpsacq.QUALITY_INFO_DTYPE).reshape(a.blocks, m)
         peaks = d_peaks.cpu().numpy().view(gpsacq.PEAK_DTYPE).reshape(a.blocks, m)
         fine = d_fine.cpu().numpy().view(gpsacq.FINE_DTYPE).reshape(a.blocks, m)
         fix_f, info_f = d_fix_f.cpu().numpy().view(gpsacq.FIX_DTYPE), d_info_f.cpu().numpy().view(gpsacq.COARSE_INFO_DTYPE)
@@ -332,6 +361,25 @@ def main_iq8_aided(a):
                 "position_error_worst_with_weak_m": r2(off_a[ok_a].max()) if ok_a.any() else None,
                 "position_error_median_without_weak_m": r2(np.median(off_f[ok_a])) if ok_a.any() else None,
                 "position_error_worst_without_weak_m": r2(off_f[ok_a].max()) if ok_a.any() else None})
+    if a.quality:
+        ok_q = ok_a & (fix_q["status"] == 0) & (info_q["flags"] == 0)  # the same blocks three ways
+        off_q = np.linalg.norm(np.stack([fix_q[c] for c in "xyz"], 1) - geo["rx"], axis=1)
+        usable = (qinfo["flags"] & (gpsacq.QUALITY_NO_RECORD | gpsacq.QUALITY_NO_POWER)) == 0
+        s_db, s_w = qinfo["cn0_dbhz"][:, :8][usable[:, :8]], qinfo["weight"][:, :8][usable[:, :8]]
+        w_db, w_w = qinfo["cn0_dbhz"][:, weak][usable[:, weak]], qinfo["weight"][:, weak][usable[:, weak]]
+        qp = gpsacq.snap_quality_params_iq8()
+        stat = lambda v: [r2(np.median(v)), r2(v.min()), r2(v.max())] if v.size else None
+        res["quality"] = {
+            "snap_floor_ms": r4(floor_best), "snap_quality_ms": r4(quality_best), "refine_iq_ms": r4(refine_q_best), "capture_copy_ms": r4(copy_best),
+            "capture_MB": r2(2 * n_samples / 1e6), "snap_floor_over_refine_iq": r4(floor_best / refine_q_best),
+            "snap_floor_over_capture_copy": r4(floor_best / copy_best), "shader_clock_read": False,
+            "cn0_min_dbhz": r2(10 * np.log10(float(qp["cn0_min_lin"][0]))), "cn0_ref_dbhz": r2(10 * np.log10(float(qp["cn0_ref_lin"][0]))),
+            "strong_records": int(s_db.size), "strong_cn0_dbhz_median_min_max": stat(s_db), "strong_weight_median_min_max": stat(s_w),
+            "weak_records": int(w_db.size), "weak_cn0_dbhz_median_min_max": stat(w_db), "weak_weight_median_min_max": stat(w_w),
+            "weak_gated": int((w_w == 0).sum()), "quality_blocks_compared": int(ok_q.sum()),
+            "position_error_median_worst_strong_only_m": [r2(np.median(off_f[ok_q])), r2(off_f[ok_q].max())] if ok_q.any() else None,
+            "position_error_median_worst_unit_weight_m": [r2(np.median(off_a[ok_q])), r2(off_a[ok_q].max())] if ok_q.any() else None,
+            "position_error_median_worst_weighted_m": [r2(np.median(off_q[ok_q])), r2(off_q[ok_q].max())] if ok_q.any() else None}
     print(json.dumps(res))
 
 
@@ -468,7 +516,7 @@ def main():
         if a.weak_amplitude is None:
             a.weak_amplitude = 0.03
         return main_iq8_aided_coh(a)
-    if a.iq8 and a.aided:
+    if a.iq8 and (a.aided or a.quality):
         if a.weak_amplitude is None:
             a.weak_amplitude = 0.05
         return main_iq8_aided(a)
