@@ -18,7 +18,9 @@
 //     tag = 31 - d << 15 | 15 - g << 11 | 31 - e << 6 | 63 - h, compared lexicographically, as in k_aided_iq.  That kernel's walk
 //     is not shared through a header: its key and its products would have to become template parameters of its own source.
 //   Per d the largest pair of the workgroup is found (shuffles, one LDS step) and every thread keeps the running best and the
-//   non-coherent sum of its (h, d), which item (h, g = 0) left in s_nc.  No atomics, no scratch, no float before the ratio.
+//   non-coherent sum of its (h, d), which item (h, g = 0) left in s_nc.  Steps 1 and 2 and the record and peak are aided_prologue
+//   and aided_coh_record of snapshot_records.hpp, k_aided_coh's: this file unpacks its tag and brings the measured floor.
+//   No atomics, no scratch, no float before the ratio.
 // Every loop is bounded by kernel arguments.  The prefix array is read at slot PAD + m - h with m in [0, n + 2 W - 1] and h in
 // [0, 63], so in [1, AIDED_COH_IQ_SLOTS - 3], written in [0, PAD + n + 2 W - 1]; the list is indexed below n + 2 W + 2 <=
 // AIDED_COH_IQ_LIST (W <= 31 is the host's check, n <= 512 the chunk); s_z is indexed below segments * n_code <= fit * (2 W + 1)
@@ -32,31 +34,9 @@
 
 #include "aided_coh_iq_launch.hpp"
 #include "aided_iq_walk.hpp"
+#include "snapshot_records.hpp"
 
 namespace acq {
-
-namespace {
-// the window of Doppler hypothesis lo_shift: the IQ section's steps 1 to 3 on a peak that is a hit by itself
-__device__ __forceinline__ Window window_at_coh_iq(const AidedCohIqArgs& a, size_t t, int64_t lo_shift) {
-    Window w = {false, 0, 0, 0, 0, 0, 0, 0};
-    if (lo_shift < -(int64_t)a.kmax || lo_shift > (int64_t)a.kmax) return w;
-    const gpsacq_peak pk = {1.0f, (int32_t)lo_shift, 0, 0.0f};
-    double base_hz;
-    return window_of_iq(pk, a.c, t, 0.0, a.p.blocks, base_hz);
-}
-
-// the larger of two keys (power, tag): the power first, then the tag
-__device__ __forceinline__ void pair_max(uint64_t& pw, uint32_t& tag, uint64_t opw, uint32_t otag) {
-    if (opw > pw || (opw == pw && otag > tag)) pw = opw, tag = otag;
-}
-
-__device__ __forceinline__ uint64_t shfl_xor64_coh_iq(uint64_t v, int m) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-    return (uint64_t)hi << 32 | lo;
-}
-
-__device__ __forceinline__ uint64_t sq2_64(int64_t a, int64_t b) { return (uint64_t)(a * a + b * b); }
-}  // namespace
 
 template <int M> __global__ __launch_bounds__(64 * AIDED_COH_IQ_WAVES) void k_aided_coh_iq(AidedCohIqArgs a) {
     __shared__ uint32_t s_chips[CHIP_WORDS];
@@ -73,30 +53,12 @@ template <int M> __global__ __launch_bounds__(64 * AIDED_COH_IQ_WAVES) void k_ai
     const int row = n_fine * M * n_code;  // powers of one d
     unsigned long long* const powers = a.powers ? a.powers + t * (size_t)(n_dop * row) : nullptr;
 
-    // 1. kept, 2. no aid: the flag and zeros
-    int blank = 0;
-    gpsacq_peak pk_out = {0.0f, 0, 0, 0.0f};
+    // 1. kept, 2. no aid: the flag and zeros (snapshot_records.hpp)
     const gpsacq_aid aid = a.aid[t];
-    if (a.c.peaks) {
-        const gpsacq_peak pk = a.c.peaks[t];
-        if ((double)pk.snr >= a.p.keep_snr) blank = GPSACQ_AIDED_KEPT, pk_out = pk;
-    }
-    Window win = {false, 0, 0, 0, 0, 0, 0, 0};
-    int d_first = 0;  // the first valid d: the floor is summed there
-    if (!blank) {
-        if (aid.flags == 0 && aid.ca_center >= 0 && aid.ca_center < a.c.spm)
-            for (int d = 0; d < n_dop && !win.hit; ++d) win = window_at_coh_iq(a, t, (int64_t)aid.lo_center - K + d), d_first = d;
-        if (!win.hit) blank = GPSACQ_AIDED_NO_AID;
-    }
-    if (blank) {
-        if (threadIdx.x == 0) {
-            a.out[t] = gpsacq_aided_coh{blank, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0};
-            a.peaks_out[t] = pk_out;
-        }
-        if (powers)
-            for (int i = threadIdx.x; i < n_dop * row; i += 64 * AIDED_COH_IQ_WAVES) powers[i] = 0;
-        return;
-    }
+    gpsacq_peak pk_out;
+    Window win;
+    int d_first;  // the first valid d: the floor is summed there
+    if (!aided_prologue(a, t, aid, powers, n_dop * row, pk_out, win, d_first)) return;
     chips_to_lds(a.c.chips, win.prn, s_chips);
     for (int i = threadIdx.x; i < COH_TABLE; i += 64 * AIDED_COH_IQ_WAVES)
         s_tab[i] = (uint32_t)(uint16_t)a.table[i] | (uint32_t)(uint16_t)a.table[COH_TABLE + i] << 16;
@@ -106,12 +68,12 @@ template <int M> __global__ __launch_bounds__(64 * AIDED_COH_IQ_WAVES) void k_ai
 
     const uint64_t o = win.o, spm = (uint64_t)a.c.spm;  // o is a multiple of 8: stride is one of 16
     const int S = (int)win.segments;                    // S * n_code <= COH_MAX_Z
-    const uint32_t base = (uint32_t)(((aid.ca_center - W) % a.c.spm + a.c.spm) % a.c.spm);
+    const uint32_t base = aided_base(aid, W, a.c.spm);
     const int items = n_code * n_fine;
     uint64_t best = 0, best_nc = 0, floor_sum = 0;  // best, best_nc and tag the same in every thread; floor_sum of the lane's samples
     uint32_t tag = 0;
     for (int d = 0; d < n_dop; ++d) {
-        const Window wd = window_at_coh_iq(a, t, (int64_t)aid.lo_center - K + d);
+        const Window wd = window_at(a, t, (int64_t)aid.lo_center - K + d);
         if (!wd.hit) {  // every lane decides the same
             if (powers)
                 for (int i = threadIdx.x; i < row; i += 64 * AIDED_COH_IQ_WAVES) powers[d * row + i] = 0;
@@ -144,62 +106,50 @@ template <int M> __global__ __launch_bounds__(64 * AIDED_COH_IQ_WAVES) void k_ai
                 for (int j = 0; j < M; ++j) {
                     const int s = s0 + j;  // s mod M == j
                     if (s < S) {
-                        acc[j] += sq2_64((PA - LA[j]) >> 14, (PB - LB[j]) >> 14);
+                        acc[j] += sq2((PA - LA[j]) >> 14, (PB - LB[j]) >> 14);
                         LA[j] = PA, LB[j] = PB;
                         const int2 z = s_z[s * n_code + h];
                         const uint32_t cs = s_tab[k];
                         const int64_t c = (int16_t)(cs & 0xffffu), sn = (int16_t)(cs >> 16), zi = z.x, zq = z.y;
                         PA += zi * c + zq * sn;
                         PB += zq * c - zi * sn;
-                        nc += sq2_64(zi, zq);
+                        nc += sq2(zi, zq);
                         k = (k + step) & (COH_TABLE - 1);
                     }
                 }
             }
 #pragma unroll
             for (int j = 0; j < M; ++j) {
-                const uint64_t pw = acc[j] + sq2_64((PA - LA[j]) >> 14, (PB - LB[j]) >> 14);
+                const uint64_t pw = acc[j] + sq2((PA - LA[j]) >> 14, (PB - LB[j]) >> 14);
                 if (powers) powers[d * row + (g * M + j) * n_code + h] = pw;
-                pair_max(kpw, ktag, pw, (uint32_t)(31 - d) << 15 | (uint32_t)(15 - g) << 11 | (uint32_t)(31 - j) << 6 | (uint32_t)(63 - h));
+                key_max(kpw, ktag, pw, (uint32_t)(31 - d) << 15 | (uint32_t)(15 - g) << 11 | (uint32_t)(31 - j) << 6 | (uint32_t)(63 - h));
             }
             if (g == 0) s_nc[h] = nc;
         }
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) {
-            const uint64_t opw = shfl_xor64_coh_iq(kpw, m);
+            const uint64_t opw = shfl_xor64(kpw, m);
             const uint32_t otag = (uint32_t)__shfl_xor((int)ktag, m, 64);
-            pair_max(kpw, ktag, opw, otag);
+            key_max(kpw, ktag, opw, otag);
         }
         if (lane == 0) s_red[wv][0] = kpw, s_red[wv][1] = ktag;
         __syncthreads();  // also: every thread is done with s_z before the next d writes it
-        for (int w = 0; w < AIDED_COH_IQ_WAVES; ++w) pair_max(kpw, ktag, s_red[w][0], (uint32_t)s_red[w][1]);
+        for (int w = 0; w < AIDED_COH_IQ_WAVES; ++w) key_max(kpw, ktag, s_red[w][0], (uint32_t)s_red[w][1]);
         if (kpw > best || (kpw == best && ktag > tag)) best = kpw, tag = ktag, best_nc = s_nc[63 - (int)(ktag & 63)];
         // s_red and s_nc are written again only behind the next d's first barrier
     }
 
     // 6. record and peak: the floor's sum over the workgroup first; the barrier in front lets every thread finish reading s_red
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) floor_sum += shfl_xor64_coh_iq(floor_sum, m);
+    floor_sum = wave_sum(floor_sum);
     __syncthreads();
     if (lane == 0) s_red[wv][0] = floor_sum;
     __syncthreads();
     if (threadIdx.x != 0) return;
     floor_sum = 0;
     for (int w = 0; w < AIDED_COH_IQ_WAVES; ++w) floor_sum += s_red[w][0];
-    gpsacq_aided_coh r = {0, S, n_code, n_dop, n_fine, M, 63 - (int32_t)(tag & 63), 31 - (int32_t)(tag >> 15 & 31), 15 - (int32_t)(tag >> 11 & 15),
-                          31 - (int32_t)(tag >> 6 & 31), 0, 0, best, best_nc, 2 * floor_sum, 0.0, 0.0, 0.0};
-    r.lo_shift = aid.lo_center - K + r.best_d;
-    r.ca_shift = (int32_t)((base + (uint32_t)r.best_h) % (uint32_t)a.c.spm);
-    if (r.floor) r.ratio = (double)r.best / (double)r.floor;
-    const double lo_dop = a.c.step_hz > 0 ? r.lo_shift * a.c.step_hz : r.lo_shift * a.c.fs / 40000.0;
-    r.doppler_hz = lo_dop + ((double)((r.best_f - F) * a.p.fine_step) / 1024.0) * (a.c.fs / (double)a.c.spm);
-    if ((uint64_t)S < win.fit) r.flags |= GPSACQ_AIDED_SHORT;
-    if (S < a.p.min_segments) r.flags |= GPSACQ_AIDED_FEW;
-    if (r.best == 0) r.flags |= GPSACQ_AIDED_NO_POWER;
-    if (r.ratio < a.p.ratio_min) r.flags |= GPSACQ_AIDED_BELOW;
-    if (!(r.flags & (GPSACQ_AIDED_FEW | GPSACQ_AIDED_NO_POWER | GPSACQ_AIDED_BELOW))) pk_out = gpsacq_peak{(float)r.ratio, r.lo_shift, r.ca_shift, (float)r.best};
-    a.out[t] = r;
-    a.peaks_out[t] = pk_out;
+    // the tag unpacked and the measured floor, then snapshot_records.hpp
+    aided_coh_record(a, t, aid, base, (uint64_t)S, win.fit, M, best, 63 - (int32_t)(tag & 63), 31 - (int32_t)(tag >> 15 & 31), 15 - (int32_t)(tag >> 11 & 15),
+                     31 - (int32_t)(tag >> 6 & 31), best_nc, 2 * floor_sum, pk_out);
 }
 
 void launch_aided_coh_iq(const AidedCohIqArgs& a, hipStream_t s) {

@@ -21,7 +21,6 @@ static constexpr int AIDED_COH_IQ_SLOTS = AidedCohIqGeometry::PAD + AidedCohIqGe
 static constexpr int AIDED_COH_IQ_LIST = AidedCohIqGeometry::CHUNK + 64;                             // transitions of a chunk's stream: at most n + 2 W - 1 <= 573
 static_assert(2 * COH_MAX_CODE_HALF <= AidedCohIqGeometry::PAD - 2 && ((AidedCohIqGeometry::CHUNK + 2 * COH_MAX_CODE_HALF - 1 + 3) & ~3) <= AIDED_COH_IQ_LIST && AidedCohIqGeometry::CHUNK % 8 == 0, "the pads");
 
-// c.peaks is peaks_in and may be NULL
 struct AidedCohIqArgs {
     IqCaptureArgs c;
     int kmax;                     // the grid is -kmax .. +kmax

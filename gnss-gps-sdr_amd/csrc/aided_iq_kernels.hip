@@ -25,7 +25,9 @@
 // At the segment's end the lane squares its own I and Q into its own uint64.  The floor's sum v_i^2 + v_q^2 is taken in WIPE at
 // the first valid d alone.  Once per d the four waves' sums meet in LDS (the waves' own prefix arrays serve: two barriers); thread h
 // adds them, writes power(h, d) and keeps its total and the largest (power, 31 - d, 255 - h): a power may take 62 bits here, so
-// the key is a pair.  No atomics, no float before the ratio.  Every loop is bounded by kernel arguments; the prefix array is
+// the key is a pair.  Steps 1 and 2 and the record and peak are aided_prologue and aided_record of snapshot_records.hpp, k_aided's:
+// this file unpacks its tag and brings the measured floor.
+// No atomics, no float before the ratio.  Every loop is bounded by kernel arguments; the prefix array is
 // read at slot AIDED_IQ_PAD + m - h with m in [0, n + 2 W - 1] and h in [0, 255] (the lanes beyond 2 W read and are not used), so in
 // [1, AIDED_IQ_SLOTS - 3], written in [0, AIDED_IQ_PAD + n + 2 W - 1], and the list is indexed below n + 2 W + 2 <= AIDED_IQ_LIST
 // (W <= 127 and n <= 1024 are the host's check and the chunk); nothing at or beyond byte 2 * n_samples is read (load_group).
@@ -36,29 +38,9 @@
 
 #include "aided_iq_launch.hpp"
 #include "aided_iq_walk.hpp"
+#include "snapshot_records.hpp"
 
 namespace acq {
-
-namespace {
-// the window of Doppler hypothesis lo_shift: the IQ section's steps 1 to 3 on a peak that is a hit by itself
-__device__ __forceinline__ Window window_at_iq(const AidedIqArgs& a, size_t t, int64_t lo_shift) {
-    Window w = {false, 0, 0, 0, 0, 0, 0, 0};
-    if (lo_shift < -(int64_t)a.kmax || lo_shift > (int64_t)a.kmax) return w;
-    const gpsacq_peak pk = {1.0f, (int32_t)lo_shift, 0, 0.0f};
-    double base_hz;
-    return window_of_iq(pk, a.c, t, 0.0, a.p.blocks, base_hz);
-}
-
-// the larger of two keys (power, tag): the power first, then the tag
-__device__ __forceinline__ void key_max(uint64_t& pw, uint32_t& tag, uint64_t opw, uint32_t otag) {
-    if (opw > pw || (opw == pw && otag > tag)) pw = opw, tag = otag;
-}
-
-__device__ __forceinline__ uint64_t shfl_xor64_iq(uint64_t v, int m) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-    return (uint64_t)hi << 32 | lo;
-}
-}  // namespace
 
 __global__ __launch_bounds__(64 * AIDED_IQ_WAVES) void k_aided_iq(AidedIqArgs a) {
     __shared__ uint32_t s_chips[CHIP_WORDS];
@@ -70,30 +52,12 @@ __global__ __launch_bounds__(64 * AIDED_IQ_WAVES) void k_aided_iq(AidedIqArgs a)
     const int W = a.p.code_half, K = a.p.dop_half, n_code = 2 * W + 1, n_dop = 2 * K + 1;
     unsigned long long* const powers = a.powers ? a.powers + t * (size_t)(n_dop * n_code) : nullptr;
 
-    // 1. kept, 2. no aid: the flag and zeros
-    int blank = 0;
-    gpsacq_peak pk_out = {0.0f, 0, 0, 0.0f};
+    // 1. kept, 2. no aid: the flag and zeros (snapshot_records.hpp)
     const gpsacq_aid aid = a.aid[t];
-    if (a.c.peaks) {
-        const gpsacq_peak pk = a.c.peaks[t];
-        if ((double)pk.snr >= a.p.keep_snr) blank = GPSACQ_AIDED_KEPT, pk_out = pk;
-    }
-    Window win = {false, 0, 0, 0, 0, 0, 0, 0};
-    int d_first = 0;  // the first valid d: the floor is summed there
-    if (!blank) {
-        if (aid.flags == 0 && aid.ca_center >= 0 && aid.ca_center < a.c.spm)
-            for (int d = 0; d < n_dop && !win.hit; ++d) win = window_at_iq(a, t, (int64_t)aid.lo_center - K + d), d_first = d;
-        if (!win.hit) blank = GPSACQ_AIDED_NO_AID;
-    }
-    if (blank) {
-        if (threadIdx.x == 0) {
-            a.out[t] = gpsacq_aided{blank, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0};
-            a.peaks_out[t] = pk_out;
-        }
-        if (powers)
-            for (int i = threadIdx.x; i < n_dop * n_code; i += 64 * AIDED_IQ_WAVES) powers[i] = 0;
-        return;
-    }
+    gpsacq_peak pk_out;
+    Window win;
+    int d_first;  // the first valid d: the floor is summed there
+    if (!aided_prologue(a, t, aid, powers, n_dop * n_code, pk_out, win, d_first)) return;
     chips_to_lds(a.c.chips, win.prn, s_chips);
     int2* const A = s_a[wv];
     for (int i = lane; i <= AIDED_IQ_PAD; i += 64) A[i] = make_int2(0, 0);  // A[k] = 0 for k <= 0: never written again
@@ -101,11 +65,11 @@ __global__ __launch_bounds__(64 * AIDED_IQ_WAVES) void k_aided_iq(AidedIqArgs a)
 
     // 3. hypotheses, 4. sums
     const uint64_t o = win.o, spm = (uint64_t)a.c.spm, segments = win.segments;  // o is a multiple of 8: stride is one of 16
-    const uint32_t base = (uint32_t)(((aid.ca_center - W) % a.c.spm + a.c.spm) % a.c.spm);
+    const uint32_t base = aided_base(aid, W, a.c.spm);
     uint64_t total = 0, best = 0, floor_sum = 0;  // of hypothesis h = threadIdx.x; floor_sum of the lane's samples
     uint32_t tag = 0;
     for (int d = 0; d < n_dop; ++d) {
-        const Window wd = window_at_iq(a, t, (int64_t)aid.lo_center - K + d);
+        const Window wd = window_at(a, t, (int64_t)aid.lo_center - K + d);
         if (!wd.hit) {  // every lane decides the same
             if (powers && (int)threadIdx.x < n_code) powers[d * n_code + threadIdx.x] = 0;
             continue;
@@ -142,14 +106,14 @@ __global__ __launch_bounds__(64 * AIDED_IQ_WAVES) void k_aided_iq(AidedIqArgs a)
         __syncthreads();
     }
 
-    // 5. record, 6. peak
+    // 5. record, 6. peak: the largest pair, the total and the floor over the workgroup, then snapshot_records.hpp
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
-        const uint64_t opw = shfl_xor64_iq(best, m);
+        const uint64_t opw = shfl_xor64(best, m);
         const uint32_t otag = (uint32_t)__shfl_xor((int)tag, m, 64);
         key_max(best, tag, opw, otag);
-        total += shfl_xor64_iq(total, m);
-        floor_sum += shfl_xor64_iq(floor_sum, m);
+        total += shfl_xor64(total, m);
+        floor_sum += shfl_xor64(floor_sum, m);
     }
     if (lane == 0) s_red[wv][0] = best, s_red[wv][1] = tag, s_red[wv][2] = total, s_red[wv][3] = floor_sum;
     __syncthreads();
@@ -160,17 +124,8 @@ __global__ __launch_bounds__(64 * AIDED_IQ_WAVES) void k_aided_iq(AidedIqArgs a)
         total += s_red[w][2];
         floor_sum += s_red[w][3];
     }
-    gpsacq_aided r = {0, (int32_t)segments, n_code, n_dop, 255 - (int32_t)(tag & 255), 31 - (int32_t)(tag >> 8 & 31), 0, 0, best, total, 2 * floor_sum, 0.0};
-    r.lo_shift = aid.lo_center - K + r.best_d;
-    r.ca_shift = (int32_t)((base + (uint32_t)r.best_h) % (uint32_t)a.c.spm);
-    if (r.floor) r.ratio = (double)r.best / (double)r.floor;
-    if (segments < win.fit) r.flags |= GPSACQ_AIDED_SHORT;
-    if (segments < (uint64_t)a.p.min_segments) r.flags |= GPSACQ_AIDED_FEW;
-    if (r.best == 0) r.flags |= GPSACQ_AIDED_NO_POWER;
-    if (r.ratio < a.p.ratio_min) r.flags |= GPSACQ_AIDED_BELOW;
-    if (!(r.flags & (GPSACQ_AIDED_FEW | GPSACQ_AIDED_NO_POWER | GPSACQ_AIDED_BELOW))) pk_out = gpsacq_peak{(float)r.ratio, r.lo_shift, r.ca_shift, (float)r.best};
-    a.out[t] = r;
-    a.peaks_out[t] = pk_out;
+    // the tag unpacked; the measured floor
+    aided_record(a, t, aid, base, segments, win.fit, best, 255 - (int32_t)(tag & 255), 31 - (int32_t)(tag >> 8 & 31), total, 2 * floor_sum, pk_out);
 }
 
 void launch_aided_iq(const AidedIqArgs& a, hipStream_t s) {

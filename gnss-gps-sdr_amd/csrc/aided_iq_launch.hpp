@@ -24,7 +24,6 @@ struct AidedIqGeometry {
     static constexpr int CHUNK = AIDED_IQ_CHUNK, PAD = AIDED_IQ_PAD;
 };
 
-// c.peaks is peaks_in and may be NULL
 struct AidedIqArgs {
     IqCaptureArgs c;
     int kmax;               // the grid is -kmax .. +kmax

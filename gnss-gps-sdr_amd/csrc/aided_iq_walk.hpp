@@ -20,14 +20,6 @@ namespace acq {
 
 typedef uint16_t __attribute__((may_alias)) list_u16;  // the list is written entry by entry and read four entries at a time
 
-// the lanes of ONE wave hand LDS to each other: the wave's LDS operations execute in program order, so all that is needed is
-// that the compiler keeps them in it
-__device__ __forceinline__ void wave_sync_iq() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // The segment [a0, a1) (capture samples) of a window that starts at sample o (a multiple of 8), on the calling wave's prefix array
 // A and list lq: pass p serves code hypothesis h = lane + 64 p, and Ri[p], Rq[p] come back as the segment's (I_P, Q_P) of that
 // hypothesis in wrap-around uint32 (the lanes beyond n_code hold sums that are not used).  fl is the lane's share of the
@@ -113,7 +105,7 @@ __device__ __forceinline__ void segment_sums_by_parts(const IqCaptureArgs& c, ui
         }
         if (lane < 3 && count + lane < ((count + 3) & ~3)) list[count + lane] = 0;  // up to a multiple of four: entries that read A[-h] = 0
         const int quads = (count + 3) >> 2;
-        wave_sync_iq();
+        wave_sync();
         // SUM
 #pragma unroll
         for (int p = 0; p < PASSES; ++p) {
@@ -136,7 +128,7 @@ __device__ __forceinline__ void segment_sums_by_parts(const IqCaptureArgs& c, ui
                 Rq[p] += ((cq ^ sM) - sM) + 2u * sy;
             }
         }
-        wave_sync_iq();
+        wave_sync();
     }
 }
 

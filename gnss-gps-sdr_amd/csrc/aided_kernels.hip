@@ -22,8 +22,10 @@
 // A segment of more than AIDED_CHUNK words (spm above 6100) is built and walked in chunks; the counts carry over.  Once per d the four
 // waves' sums meet in LDS (two barriers), thread h adds them, writes power(h, d), and keeps its total and the largest KEY
 // power << 13 | (31 - d) << 8 | (255 - h) (power < 2^39: include/gpsacq.h, step 4): the maximum of the keys over the workgroup is
-// the record's best, whatever the order.  No atomics.  Every loop is bounded by kernel arguments; s_x is indexed below
-// AIDED_CHUNK, s_stream below AIDED_CHUNK + 2 W / 32 + 1 <= AIDED_CHUNK + 8, s_pow below 2 W + 1 <= 255 (W <= 127 is checked by the
+// the record's best, whatever the order.  Steps 1 and 2 (kept, no aid) and the record and peak are built in snapshot_records.hpp
+// (aided_prologue, aided_record; aided_coh_record for k_aided_coh), which the kernels of aided_iq_kernels.hip and
+// aided_coh_iq_kernels.hip call too: this file unpacks its key and brings the floor 2 spm segments.
+// No atomics.  Every loop is bounded by kernel arguments; s_x is indexed below AIDED_CHUNK, s_stream below AIDED_CHUNK + 2 W / 32 + 1 <= AIDED_CHUNK + 8, s_pow below 2 W + 1 <= 255 (W <= 127 is checked by the
 // host); nothing is read at or beyond byte n_bytes (word_at).
 // Built with -ffp-contract=off (Makefile): the NCO words must be gpsacq_handoff_engine's to the bit, as in refine_kernels.hip.
 #include <hip/hip_runtime.h>
@@ -33,6 +35,7 @@
 #include "capture_words.hpp"
 #include "nav_device.hpp"
 #include "orbit_device.hpp"
+#include "snapshot_records.hpp"
 
 namespace acq {
 
@@ -42,27 +45,6 @@ constexpr int AIDED_CHUNK = 192;               // capture words built and walked
 constexpr int AIDED_STREAM = AIDED_CHUNK + 8;  // and the stream words that go with them
 static_assert((2 * AIDED_MAX_CODE_HALF >> 5) + 1 <= AIDED_STREAM - AIDED_CHUNK, "the stream's tail");
 static_assert(2 * AIDED_MAX_CODE_HALF + 1 <= 64 * AIDED_PASSES && 2 * AIDED_MAX_DOP_HALF + 1 <= 32, "passes and key");
-
-// the lanes of ONE wave hand LDS to each other: the wave's LDS operations execute in program order, so all that is needed is
-// that the compiler keeps them in it
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-    return (uint64_t)hi << 32 | lo;
-}
-
-// the window of Doppler hypothesis lo_shift: refine's steps 1 to 3 on a peak that is a hit by itself (Args: AidedArgs or AidedCohArgs)
-template <class Args> __device__ __forceinline__ Window window_at(const Args& a, size_t t, int64_t lo_shift) {
-    Window w = {false, 0, 0, 0, 0, 0, 0, 0};
-    if (lo_shift < -(int64_t)a.kmax || lo_shift > (int64_t)a.kmax) return w;
-    const gpsacq_peak pk = {1.0f, (int32_t)lo_shift, 0, 0.0f};
-    return window_of(pk, a.tasks, t, a.fc, a.fs, a.step_hz, a.spm, 0.0, a.p.blocks, a.n_bytes, a.lead, a.stride);
-}
 
 // BUILD and WALK of one segment [a0, a1) of a window that starts at sample o, on the calling wave's sx[AIDED_CHUNK] and
 // st_all[AIDED_STREAM]: the ONE copy, for k_aided (PASSES = 4) and k_aided_coh (PASSES = 1).  Pass p serves code hypothesis
@@ -196,35 +178,18 @@ __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided(AidedArgs a) {
     const int W = a.p.code_half, K = a.p.dop_half, n_code = 2 * W + 1, n_dop = 2 * K + 1;
     unsigned long long* const powers = a.powers ? a.powers + t * (size_t)(n_dop * n_code) : nullptr;
 
-    // 1. kept, 2. no aid: the flag and zeros
-    int blank = 0;
-    gpsacq_peak pk_out = {0.0f, 0, 0, 0.0f};
+    // 1. kept, 2. no aid: the flag and zeros (snapshot_records.hpp)
     const gpsacq_aid aid = a.aid[t];
-    if (a.peaks) {
-        const gpsacq_peak pk = a.peaks[t];
-        if ((double)pk.snr >= a.p.keep_snr) blank = GPSACQ_AIDED_KEPT, pk_out = pk;
-    }
-    Window win = {false, 0, 0, 0, 0, 0, 0, 0};
-    if (!blank) {
-        if (aid.flags == 0 && aid.ca_center >= 0 && aid.ca_center < a.spm)
-            for (int d = 0; d < n_dop && !win.hit; ++d) win = window_at(a, t, (int64_t)aid.lo_center - K + d);
-        if (!win.hit) blank = GPSACQ_AIDED_NO_AID;
-    }
-    if (blank) {
-        if (threadIdx.x == 0) {
-            a.out[t] = gpsacq_aided{blank, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0};
-            a.peaks_out[t] = pk_out;
-        }
-        if (powers)
-            for (int i = threadIdx.x; i < n_dop * n_code; i += 64 * AIDED_WAVES) powers[i] = 0;
-        return;
-    }
-    chips_to_lds(a.chips, win.prn, s_chips);
+    gpsacq_peak pk_out;
+    Window win;
+    int d_first;
+    if (!aided_prologue(a, t, aid, powers, n_dop * n_code, pk_out, win, d_first)) return;
+    chips_to_lds(a.c.chips, win.prn, s_chips);
     __syncthreads();
 
     // 3. hypotheses, 4. sums
-    const uint64_t o = win.o, spm = (uint64_t)a.spm, segments = win.segments;
-    const uint32_t base = (uint32_t)(((aid.ca_center - W) % a.spm + a.spm) % a.spm);
+    const uint64_t o = win.o, spm = (uint64_t)a.c.spm, segments = win.segments;
+    const uint32_t base = aided_base(aid, W, a.c.spm);
     const int extra = (2 * W >> 5) + 1;  // stream words behind a chunk's capture words
     uint64_t total = 0, key = 0;         // of hypothesis h = threadIdx.x
     for (int d = 0; d < n_dop; ++d) {
@@ -239,11 +204,11 @@ __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided(AidedArgs a) {
         for (uint64_t s = wv; s < segments; s += AIDED_WAVES) {
             const uint64_t a0 = o + s * spm;  // the segment's samples [a0, a0 + spm), counted from the aligned base
             uint32_t ones_i[AIDED_PASSES], ones_q[AIDED_PASSES];
-            segment_ones<AIDED_PASSES>(a.words, a.n_bytes, a0, a0 + spm, o, P0, lo_rate, ca_rate, s_chips, s_x[wv], s_stream[wv], lane, n_code, extra, ones_i,
+            segment_ones<AIDED_PASSES>(a.c.words, a.c.n_bytes, a0, a0 + spm, o, P0, lo_rate, ca_rate, s_chips, s_x[wv], s_stream[wv], lane, n_code, extra, ones_i,
                                        ones_q);
 #pragma unroll
             for (int p = 0; p < AIDED_PASSES; ++p) {
-                const int64_t I = (int64_t)a.spm - 2 * (int64_t)ones_i[p], Q = (int64_t)a.spm - 2 * (int64_t)ones_q[p];
+                const int64_t I = (int64_t)a.c.spm - 2 * (int64_t)ones_i[p], Q = (int64_t)a.c.spm - 2 * (int64_t)ones_q[p];
                 acc[p] += (uint64_t)(I * I + Q * Q);
             }
         }
@@ -261,7 +226,7 @@ __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided(AidedArgs a) {
         __syncthreads();
     }
 
-    // 5. record, 6. peak
+    // 5. record, 6. peak: the largest key and the total over the workgroup, then snapshot_records.hpp
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         const uint64_t other = shfl_xor64(key, m);
@@ -276,17 +241,8 @@ __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided(AidedArgs a) {
         key = s_red[w][0] > key ? s_red[w][0] : key;
         total += s_red[w][1];
     }
-    gpsacq_aided r = {0, (int32_t)segments, n_code, n_dop, 255 - (int32_t)(key & 255), 31 - (int32_t)(key >> 8 & 31), 0, 0, key >> 13, total, 2 * spm * segments, 0.0};
-    r.lo_shift = aid.lo_center - K + r.best_d;
-    r.ca_shift = (int32_t)((base + (uint32_t)r.best_h) % (uint32_t)a.spm);
-    if (r.floor) r.ratio = (double)r.best / (double)r.floor;
-    if (segments < win.fit) r.flags |= GPSACQ_AIDED_SHORT;
-    if (segments < (uint64_t)a.p.min_segments) r.flags |= GPSACQ_AIDED_FEW;
-    if (r.best == 0) r.flags |= GPSACQ_AIDED_NO_POWER;
-    if (r.ratio < a.p.ratio_min) r.flags |= GPSACQ_AIDED_BELOW;
-    if (!(r.flags & (GPSACQ_AIDED_FEW | GPSACQ_AIDED_NO_POWER | GPSACQ_AIDED_BELOW))) pk_out = gpsacq_peak{(float)r.ratio, r.lo_shift, r.ca_shift, (float)r.best};
-    a.out[t] = r;
-    a.peaks_out[t] = pk_out;
+    // the key unpacked; the floor of a +-1 stream
+    aided_record(a, t, aid, base, segments, win.fit, key >> 13, 255 - (int32_t)(key & 255), 31 - (int32_t)(key >> 8 & 31), total, 2 * spm * segments, pk_out);
 }
 
 // ---- "Coherent aided acquisition: 20 ms sums, bit edge and fine Doppler" of include/gpsacq.h -------------------------------------
@@ -305,10 +261,6 @@ __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided(AidedArgs a) {
 //   non-coherent sum of its (h, d), which item (h, g = 0) left in s_nc.  No atomics.
 // LDS: s_chips 136 + s_x 12288 + s_stream 3200 + s_z 40960 + s_tab 4096 + s_nc 512 + s_red 32 = 61224 bytes.  s_z is indexed
 // below segments * n_code <= fit * (2 W + 1) <= COH_MAX_Z (checked by the host), s_tab below 1024 (masked), s_nc below 64.
-namespace {
-__device__ __forceinline__ uint64_t sq2(int64_t a, int64_t b) { return (uint64_t)(a * a + b * b); }
-}  // namespace
-
 template <int M> __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided_coh(AidedCohArgs a) {
     __shared__ uint32_t s_chips[CHIP_WORDS];
     __shared__ uint4 s_x[AIDED_WAVES][AIDED_CHUNK];
@@ -323,37 +275,20 @@ template <int M> __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided_coh
     const int row = n_fine * M * n_code;  // powers of one d
     unsigned long long* const powers = a.powers ? a.powers + t * (size_t)(n_dop * row) : nullptr;
 
-    // 1. kept, 2. no aid: the flag and zeros
-    int blank = 0;
-    gpsacq_peak pk_out = {0.0f, 0, 0, 0.0f};
+    // 1. kept, 2. no aid: the flag and zeros (snapshot_records.hpp)
     const gpsacq_aid aid = a.aid[t];
-    if (a.peaks) {
-        const gpsacq_peak pk = a.peaks[t];
-        if ((double)pk.snr >= a.p.keep_snr) blank = GPSACQ_AIDED_KEPT, pk_out = pk;
-    }
-    Window win = {false, 0, 0, 0, 0, 0, 0, 0};
-    if (!blank) {
-        if (aid.flags == 0 && aid.ca_center >= 0 && aid.ca_center < a.spm)
-            for (int d = 0; d < n_dop && !win.hit; ++d) win = window_at(a, t, (int64_t)aid.lo_center - K + d);
-        if (!win.hit) blank = GPSACQ_AIDED_NO_AID;
-    }
-    if (blank) {
-        if (threadIdx.x == 0) {
-            a.out[t] = gpsacq_aided_coh{blank, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0};
-            a.peaks_out[t] = pk_out;
-        }
-        if (powers)
-            for (int i = threadIdx.x; i < n_dop * row; i += 64 * AIDED_WAVES) powers[i] = 0;
-        return;
-    }
-    chips_to_lds(a.chips, win.prn, s_chips);
+    gpsacq_peak pk_out;
+    Window win;
+    int d_first;
+    if (!aided_prologue(a, t, aid, powers, n_dop * row, pk_out, win, d_first)) return;
+    chips_to_lds(a.c.chips, win.prn, s_chips);
     for (int i = threadIdx.x; i < COH_TABLE; i += 64 * AIDED_WAVES)
         s_tab[i] = (uint32_t)(uint16_t)a.table[i] | (uint32_t)(uint16_t)a.table[COH_TABLE + i] << 16;
     __syncthreads();
 
-    const uint64_t o = win.o, spm = (uint64_t)a.spm;
+    const uint64_t o = win.o, spm = (uint64_t)a.c.spm;
     const int S = (int)win.segments;  // S * n_code <= COH_MAX_Z
-    const uint32_t base = (uint32_t)(((aid.ca_center - W) % a.spm + a.spm) % a.spm);
+    const uint32_t base = aided_base(aid, W, a.c.spm);
     const int extra = (2 * W >> 5) + 1;
     const int items = n_code * n_fine;
     uint64_t best_key = 0, best_nc = 0;  // the same in every thread
@@ -369,8 +304,8 @@ template <int M> __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided_coh
         for (int s = wv; s < S; s += AIDED_WAVES) {
             const uint64_t a0 = o + (uint64_t)s * spm;
             uint32_t ones_i[1], ones_q[1];
-            segment_ones<1>(a.words, a.n_bytes, a0, a0 + spm, o, P0, wd.lo_rate, wd.ca_rate, s_chips, s_x[wv], s_stream[wv], lane, n_code, extra, ones_i, ones_q);
-            if (lane < n_code) s_z[s * n_code + lane] = make_int2(a.spm - 2 * (int32_t)ones_i[0], a.spm - 2 * (int32_t)ones_q[0]);
+            segment_ones<1>(a.c.words, a.c.n_bytes, a0, a0 + spm, o, P0, wd.lo_rate, wd.ca_rate, s_chips, s_x[wv], s_stream[wv], lane, n_code, extra, ones_i, ones_q);
+            if (lane < n_code) s_z[s * n_code + lane] = make_int2(a.c.spm - 2 * (int32_t)ones_i[0], a.c.spm - 2 * (int32_t)ones_q[0]);
         }
         __syncthreads();
         // 5. coherent sums
@@ -421,22 +356,10 @@ template <int M> __global__ __launch_bounds__(64 * AIDED_WAVES) void k_aided_coh
         // s_red and s_nc are written again only behind the next d's first barrier
     }
 
-    // 6. record and peak
+    // 6. record and peak: the key unpacked and the floor of a +-1 stream, then snapshot_records.hpp
     if (threadIdx.x != 0) return;
-    gpsacq_aided_coh r = {0, S, n_code, n_dop, n_fine, M, 63 - (int32_t)(best_key & 63), 31 - (int32_t)(best_key >> 15 & 31), 15 - (int32_t)(best_key >> 11 & 15),
-                          31 - (int32_t)(best_key >> 6 & 31), 0, 0, best_key >> COH_KEY_SHIFT, best_nc, 2 * spm * (uint64_t)S, 0.0, 0.0, 0.0};
-    r.lo_shift = aid.lo_center - K + r.best_d;
-    r.ca_shift = (int32_t)((base + (uint32_t)r.best_h) % (uint32_t)a.spm);
-    if (r.floor) r.ratio = (double)r.best / (double)r.floor;
-    const double lo_dop = a.step_hz > 0 ? r.lo_shift * a.step_hz : r.lo_shift * a.fs / 40000.0;
-    r.doppler_hz = lo_dop + ((double)((r.best_f - F) * a.p.fine_step) / 1024.0) * (a.fs / (double)a.spm);
-    if ((uint64_t)S < win.fit) r.flags |= GPSACQ_AIDED_SHORT;
-    if (S < a.p.min_segments) r.flags |= GPSACQ_AIDED_FEW;
-    if (r.best == 0) r.flags |= GPSACQ_AIDED_NO_POWER;
-    if (r.ratio < a.p.ratio_min) r.flags |= GPSACQ_AIDED_BELOW;
-    if (!(r.flags & (GPSACQ_AIDED_FEW | GPSACQ_AIDED_NO_POWER | GPSACQ_AIDED_BELOW))) pk_out = gpsacq_peak{(float)r.ratio, r.lo_shift, r.ca_shift, (float)r.best};
-    a.out[t] = r;
-    a.peaks_out[t] = pk_out;
+    aided_coh_record(a, t, aid, base, (uint64_t)S, win.fit, M, best_key >> COH_KEY_SHIFT, 63 - (int32_t)(best_key & 63), 31 - (int32_t)(best_key >> 15 & 31),
+                     15 - (int32_t)(best_key >> 11 & 15), 31 - (int32_t)(best_key >> 6 & 31), best_nc, 2 * spm * (uint64_t)S, pk_out);
 }
 
 // "THE RECEIVE INSTANT ON THE DEVICE": one lane per fix; the record travels as ten 64-bit words so that a copy is byte for byte
@@ -468,7 +391,7 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_aid_instant(AidInstantArgs a) {
 }
 
 void launch_aided_coh(const AidedCohArgs& a, hipStream_t s) {
-    const dim3 grid((unsigned)a.n_tasks), block(64 * AIDED_WAVES);
+    const dim3 grid((unsigned)a.c.n_tasks), block(64 * AIDED_WAVES);
     switch (a.p.coh_ms) {  // the host has checked that it is one of these
         case 1: hipLaunchKernelGGL(k_aided_coh<1>, grid, block, 0, s, a); break;
         case 2: hipLaunchKernelGGL(k_aided_coh<2>, grid, block, 0, s, a); break;
@@ -489,7 +412,7 @@ void launch_aid_predict(const AidPredictArgs& a, hipStream_t s) {
 }
 
 void launch_aided(const AidedArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_aided, dim3((unsigned)a.n_tasks), dim3(64 * AIDED_WAVES), 0, s, a);
+    hipLaunchKernelGGL(k_aided, dim3((unsigned)a.c.n_tasks), dim3(64 * AIDED_WAVES), 0, s, a);
 }
 
 }  // namespace acq

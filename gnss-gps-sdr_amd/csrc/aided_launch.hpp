@@ -7,6 +7,7 @@
 
 #include "../../include/gpsacq.h"
 #include "nav_launch.hpp"
+#include "refine_launch.hpp"
 
 namespace acq {
 
@@ -29,18 +30,8 @@ struct AidPredictArgs {
 };
 void launch_aid_predict(const AidPredictArgs& a, hipStream_t s);
 
-// the first twelve fields are RefineArgs's (gpsacq_nav.cpp fills them alike); `peaks` is peaks_in and may be NULL
 struct AidedArgs {
-    const uint32_t* words;
-    size_t n_bytes;
-    uint32_t lead;
-    size_t stride;
-    const gpsacq_task* tasks;
-    const gpsacq_peak* peaks;
-    size_t n_tasks;
-    const uint32_t* chips;
-    double fc, fs, step_hz;
-    int spm;
+    BitCaptureArgs c;
     int kmax;               // the grid is -kmax .. +kmax
     const gpsacq_aid* aid;  // [n_tasks] (device)
     gpsacq_aided_params p;
@@ -62,16 +53,7 @@ static_assert(2 * AIDED_MAX_DOP_HALF + 1 <= 32 && 2 * COH_MAX_FINE_HALF + 1 <= 1
 
 // AidedArgs with this section's parameters and record, and the rotation table
 struct AidedCohArgs {
-    const uint32_t* words;
-    size_t n_bytes;
-    uint32_t lead;
-    size_t stride;
-    const gpsacq_task* tasks;
-    const gpsacq_peak* peaks;
-    size_t n_tasks;
-    const uint32_t* chips;
-    double fc, fs, step_hz;
-    int spm;
+    BitCaptureArgs c;
     int kmax;
     const gpsacq_aid* aid;         // [n_tasks] (device)
     const int16_t* table;          // [2 * COH_TABLE] (device): gpsacq_aided_coh_table's

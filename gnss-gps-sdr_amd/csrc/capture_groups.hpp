@@ -1,7 +1,7 @@
 // capture_groups.hpp -- the group loop of the kernels that go back to an 8-bit IQ capture at a search peak, once:
 // snapshot_iq_kernels.hip (k_refine_iq, k_fine_dop_iq) includes it, nothing else does.  It is capture_words.hpp's word loop with a
 // 16-byte group (8 samples) where that has a 32-sample word, and iq_groups.hpp's dot products where that has popcounts:
-// window_of_iq() is steps 1 to 3 of the text with the carrier word of gpsacq_track_start_iq8; segment_sums() walks one segment,
+// the IqCaptureArgs overload of window_of() is steps 1 to 3 of the text with the carrier word of gpsacq_track_start_iq8; segment_sums() walks one segment,
 // lane l the groups l, l + 64, ... -- per group the mask of the samples before and after the segment, the carrier phase of sample
 // 0, capture_words.hpp's code_window (the ONE 32-chip window that holds every chip of the group: 8 samples advance by fewer than
 // 8 chips, early lies at most one chip past late's start plus that), then per dword the weight bytes of two samples and two dot
@@ -20,7 +20,7 @@ namespace acq {
 // steps 1 to 3 of "Fine code phases", PER TASK, as "Snapshot chain on an 8-bit IQ capture" changes them: the carrier word is
 // gpsacq_track_start_iq8's, a hit needs |f| < fs / 2, the window starts at sample block * (stride / 2) of n_samples.  base_hz is
 // f - lo_dop, what the fine Doppler takes off the replica's frequency.  Every lane of the workgroup decides the same
-__device__ __forceinline__ Window window_of_iq(const gpsacq_peak& pk, const IqCaptureArgs& c, size_t t, double snr_min, int blocks, double& base_hz) {
+__device__ __forceinline__ Window window_of(const gpsacq_peak& pk, const IqCaptureArgs& c, size_t t, double snr_min, int blocks, double& base_hz) {
 #pragma clang fp contract(off)  // the NCO words are the host's to the bit
     Window w = {false, (int32_t)(t % 32), 0, 0, 0, (uint64_t)c.n_samples, 0, 0};
     int32_t block = (int32_t)t;

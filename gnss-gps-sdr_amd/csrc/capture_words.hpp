@@ -5,13 +5,16 @@
 // at or beyond n_bytes), masks the bits before and after the segment, carries the code position back to the word's bit 0 and cuts
 // the ONE 32-chip window that holds every chip of the word out of the chip sequence in LDS; word_masks() then builds the carrier
 // and chip masks one sample at a time from the two NCOs.  k_refine's head comment has the reasoning; "Fine code phases" of
-// include/gpsacq.h, steps 3 and 4, is the text.
+// include/gpsacq.h, steps 3 and 4, is the text.  The capture comes as the BitCaptureArgs of refine_launch.hpp; what lanes of a wave
+// do with each other (wave_sync, shfl_xor64, wave_sum) is wave_ops.hpp's, and what follows the sums snapshot_records.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/gpsacq.h"
+#include "refine_launch.hpp"
+#include "wave_ops.hpp"
 
 namespace acq {
 
@@ -74,22 +77,24 @@ __device__ __forceinline__ void window_segments(Window& w, int spm, int blocks) 
     w.segments = have < w.fit ? have : w.fit;
 }
 
-__device__ __forceinline__ Window window_of(const gpsacq_peak& pk, const gpsacq_task* tasks, size_t t, double fc, double fs, double step_hz, int spm,
-                                            double snr_min, int blocks, size_t n_bytes, uint32_t lead, size_t stride) {
+// base_hz is what the fine Doppler takes off the replica's frequency: c.fc here.  capture_groups.hpp has the overload for an
+// IqCaptureArgs
+__device__ __forceinline__ Window window_of(const gpsacq_peak& pk, const BitCaptureArgs& c, size_t t, double snr_min, int blocks, double& base_hz) {
 #pragma clang fp contract(off)  // the NCO words are the host's to the bit
-    Window w = {false, (int32_t)(t % 32), 0, 0, 0, (uint64_t)n_bytes * 8, 0, 0};
+    Window w = {false, (int32_t)(t % 32), 0, 0, 0, (uint64_t)c.n_bytes * 8, 0, 0};
     int32_t block = (int32_t)t;
-    if (tasks) block = tasks[t].block, w.prn = tasks[t].prn;
+    if (c.tasks) block = c.tasks[t].block, w.prn = c.tasks[t].prn;
     double lo_dop, ca_f;
-    peak_dopplers(pk, fs, step_hz, lo_dop, ca_f);
-    const double lo_f = fc + lo_dop;
-    w.hit = (double)pk.snr >= snr_min && pk.ca_shift >= 0 && pk.ca_shift < spm && block >= 0 && w.prn >= 0 && w.prn < GPSACQ_NUM_SATS && lo_f >= 0 &&
-            lo_f < fs && ca_f >= 0 && ca_f < fs;
+    peak_dopplers(pk, c.fs, c.step_hz, lo_dop, ca_f);
+    const double lo_f = c.fc + lo_dop;
+    base_hz = c.fc;
+    w.hit = (double)pk.snr >= snr_min && pk.ca_shift >= 0 && pk.ca_shift < c.spm && block >= 0 && w.prn >= 0 && w.prn < GPSACQ_NUM_SATS && lo_f >= 0 &&
+            lo_f < c.fs && ca_f >= 0 && ca_f < c.fs;
     if (!w.hit) return w;
-    w.o = 8ull * lead + 8ull * (uint64_t)block * stride;  // stride <= 2^31: no overflow
-    w.lo_rate = (uint32_t)(lo_f / fs * 4294967296.0);
-    w.ca_rate = (uint32_t)(ca_f / fs * 4294967296.0);
-    window_segments(w, spm, blocks);
+    w.o = 8ull * c.lead + 8ull * (uint64_t)block * c.stride;  // stride <= 2^31: no overflow
+    w.lo_rate = (uint32_t)(lo_f / c.fs * 4294967296.0);
+    w.ca_rate = (uint32_t)(ca_f / c.fs * 4294967296.0);
+    window_segments(w, c.spm, blocks);
     return w;
 }
 
@@ -165,16 +170,6 @@ __device__ __forceinline__ void word_masks(const WordPos& w, uint32_t D, uint32_
         ph += lo_rate;
         rel += ca_rate;
     }
-}
-
-// the sum of v over the wave, in every lane: xor shuffles of the two halves, added modulo 2^64
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-        v += (uint64_t)hi << 32 | lo;
-    }
-    return v;
 }
 
 }  // namespace acq

@@ -7,7 +7,8 @@
 // i, i + 256, ...: the power of s and, from s = 1 on, the lag-1 product of the squares of s and s - 1.  The four 64-bit sums are
 // added in unsigned arithmetic modulo 2^64 (re and im are read back as int64: the host has refused every engine whose sums could
 // leave the int64 range, so the wrap-around never shows), reduced over the wave with 32-bit shuffles of their halves, and meet in
-// LDS, where thread 0 adds the four waves' and writes the record.  No atomics, no float before the estimate: the record does not
+// LDS, where thread 0 adds the four waves' and writes the record (dopfine_record of snapshot_records.hpp builds it, for this kernel
+// and for k_fine_dop_iq).  No atomics, no float before the estimate: the record does not
 // depend on the order of anything.  Two barriers; every loop is bounded by kernel arguments; s < segments <= DOP_MAX_SEGMENTS
 // (checked by the host) bounds every LDS index.
 // k_rate_obs_fine: one lane per (fix, channel), a record into the rate observation k_vel and k_doppler_fix read.
@@ -25,6 +26,7 @@
 #include "doppler_launch.hpp"
 #include "nav_device.hpp"
 #include "orbit_device.hpp"
+#include "snapshot_records.hpp"
 
 namespace acq {
 
@@ -41,17 +43,18 @@ __global__ __launch_bounds__(64 * DOP_WAVES) void k_fine_dop(FineDopArgs a) {
     __shared__ unsigned long long s_part[DOP_WAVES][4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t t = blockIdx.x;
-    const gpsacq_peak pk = a.peaks[t];
+    const gpsacq_peak pk = a.c.peaks[t];
 
     // steps 1 to 3 of "Fine code phases"
-    const Window win = window_of(pk, a.tasks, t, a.fc, a.fs, a.step_hz, a.spm, a.p.snr_min, a.p.blocks, a.n_bytes, a.lead, a.stride);
-    const uint64_t o = win.o, spm = (uint64_t)a.spm, segments = win.segments;
+    double base_hz;
+    const Window win = window_of(pk, a.c, t, a.p.snr_min, a.p.blocks, base_hz);
+    const uint64_t o = win.o, spm = (uint64_t)a.c.spm, segments = win.segments;
     const uint32_t lo_rate = win.lo_rate, ca_rate = win.ca_rate;
     if (!win.hit) {
         if (threadIdx.x == 0) a.out[t] = gpsacq_dopfine{GPSACQ_DOPFINE_NO_HIT, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0};
         return;
     }
-    chips_to_lds(a.chips, win.prn, s_chips);
+    chips_to_lds(a.c.chips, win.prn, s_chips);
     __syncthreads();
 
     // prompt sums
@@ -61,7 +64,7 @@ __global__ __launch_bounds__(64 * DOP_WAVES) void k_fine_dop(FineDopArgs a) {
         const uint64_t w1 = (a1 - 1) >> 5;
         uint32_t ones_i = 0, ones_q = 0;  // samples whose product is -1
         for (uint64_t wi = (a0 >> 5) + lane; wi <= w1; wi += 64) {
-            const WordPos w = word_pos(a.words, a.n_bytes, wi, a0, a1, o, P0, 0u, lo_rate, ca_rate, s_chips);
+            const WordPos w = word_pos(a.c.words, a.c.n_bytes, wi, a0, a1, o, P0, 0u, lo_rate, ca_rate, s_chips);
             uint32_t cm, sp, em, pm, lm;
             word_masks<false>(w, 0u, lo_rate, ca_rate, cm, sp, em, pm, lm);
             ones_i += __popc((w.x ^ pm ^ cm) & w.valid);
@@ -71,8 +74,8 @@ __global__ __launch_bounds__(64 * DOP_WAVES) void k_fine_dop(FineDopArgs a) {
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) pkd += (uint32_t)__shfl_xor((int)pkd, m, 64);
         if (lane == 0) {
-            s_iq[s][0] = a.spm - 2 * (int32_t)(pkd & 0xFFFF);
-            s_iq[s][1] = a.spm - 2 * (int32_t)(pkd >> 16);
+            s_iq[s][0] = a.c.spm - 2 * (int32_t)(pkd & 0xFFFF);
+            s_iq[s][1] = a.c.spm - 2 * (int32_t)(pkd >> 16);
         }
     }
     __syncthreads();
@@ -97,22 +100,11 @@ __global__ __launch_bounds__(64 * DOP_WAVES) void k_fine_dop(FineDopArgs a) {
     __syncthreads();
     if (threadIdx.x != 0) return;
 
-    // estimate, flags
+    // estimate, flags: snapshot_records.hpp.  lo_rate is read UNSIGNED: fc + lo_dop may pass fs / 2 on a real capture
     re = im = mag = power = 0;
     for (int w = 0; w < DOP_WAVES; ++w) re += s_part[w][0], im += s_part[w][1], mag += s_part[w][2], power += s_part[w][3];
-    gpsacq_dopfine r = {0, (int32_t)segments, lo_rate, ca_rate, (int64_t)re, (int64_t)im, mag, power, 0.0, 0.0, 0.0};
-    if (segments < win.fit) r.flags |= GPSACQ_DOPFINE_SHORT;
-    if (segments < (uint64_t)a.p.min_segments) r.flags |= GPSACQ_DOPFINE_FEW;
-    if (r.mag == 0 || (r.re == 0 && r.im == 0)) {
-        r.flags |= GPSACQ_DOPFINE_NO_POWER;
-    } else {
-        const double T = (double)a.spm / a.fs;
-        r.df_hz = atan2((double)r.im, (double)r.re) / ((4.0 * PI) * T);
-        r.coherence = hypot((double)r.re, (double)r.im) / (double)r.mag;
-        r.doppler_hz = (((double)lo_rate * a.fs) / 4294967296.0 - a.fc) + r.df_hz;
-    }
-    if (r.coherence < a.p.coherence_min) r.flags |= GPSACQ_DOPFINE_WEAK;
-    a.out[t] = r;
+    const double nco_hz = ((double)lo_rate * a.c.fs) / 4294967296.0;
+    a.out[t] = dopfine_record(segments, win.fit, a.p, lo_rate, ca_rate, re, im, mag, power, nco_hz, base_hz, (double)a.c.spm / a.c.fs);
 }
 
 __global__ __launch_bounds__(NAV_BLOCK) void k_rate_obs_fine(RateObsFineArgs a) {
@@ -255,7 +247,7 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_doppler_fix(DopplerFixArgs a) {
 }
 
 void launch_fine_dop(const FineDopArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_fine_dop, dim3((unsigned)a.n_tasks), dim3(64 * DOP_WAVES), 0, s, a);
+    hipLaunchKernelGGL(k_fine_dop, dim3((unsigned)a.c.n_tasks), dim3(64 * DOP_WAVES), 0, s, a);
 }
 
 void launch_rate_obs_fine(const RateObsFineArgs& a, hipStream_t s) {

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "nav_launch.hpp"
+#include "refine_launch.hpp"
 
 namespace acq {
 
@@ -16,16 +17,7 @@ static constexpr int DOP_WAVES = 4;  // wave64s of a k_fine_dop workgroup; wave 
 static constexpr int DOP_MAX_SEGMENTS = 2304;
 
 struct FineDopArgs {
-    const uint32_t* words;  // the capture from its 4-byte-aligned base (device): the caller's pointer rounded down
-    size_t n_bytes;         // bytes that may be read from `words` (the caller's n_bytes + lead)
-    uint32_t lead;          // bytes between `words` and the caller's pointer, 0..3
-    size_t stride;          // bytes between blocks
-    const gpsacq_task* tasks;  // [n_tasks] (device), or NULL: task t = (block t, PRN t % 32)
-    const gpsacq_peak* peaks;  // [n_tasks] (device)
-    size_t n_tasks;
-    const uint32_t* chips;  // [32][32] C/A chip words (device)
-    double fc, fs, step_hz;  // step_hz: the engine's Doppler grid step, 0 on the reference grid (lo_shift in FFT bins)
-    int spm;                 // samples per millisecond, <= 65535
+    BitCaptureArgs c;
     gpsacq_dopfine_params p;
     gpsacq_dopfine* out;  // [n_tasks] (device)
 };

@@ -63,6 +63,13 @@ template <class T> static int or_own(gpsacq_engine* e, void*& d, Scratch<T>& own
     d = own.p;
     return GPSACQ_OK;
 }
+// a one-kernel stage: the timer's two events around whatever `launch` enqueues on the stream
+template <class Launch> static int timed_stage(Stages<2>& t, hipStream_t stream, Launch launch) {
+    if (int rc = t.begin(stream)) return rc;
+    launch();
+    if (int rc = t.mark(1, stream)) return rc;
+    return t.finish();
+}
 // the time of a one-kernel stage: waited for where it ran, exactly 0 where it did not
 static int stage_ms(const Stages<2>& t, float* ms) {
     float v = 0.f;
@@ -1111,10 +1118,9 @@ static int coarse_obs_check(const char* who, const gpsacq_engine* e, const void*
 
 // k_coarse_obs on the engine's stream timed; every argument has been checked
 static int coarse_obs_enqueue(gpsacq_engine* e, const void* d_peaks, size_t n_fix, int n_chans, double snr_min, void* d_obs) {
-    if (int rc = e->coarse_obs_t.begin(e->stream)) return rc;
-    launch_coarse_obs(CoarseObsArgs{(const gpsacq_peak*)d_peaks, n_fix * (size_t)n_chans, n_chans, e->p.fs, snr_min, (gpsacq_obs*)d_obs}, e->stream);
-    if (int rc = e->coarse_obs_t.mark(1, e->stream)) return rc;
-    return e->coarse_obs_t.finish();
+    return timed_stage(e->coarse_obs_t, e->stream, [&] {
+        launch_coarse_obs(CoarseObsArgs{(const gpsacq_peak*)d_peaks, n_fix * (size_t)n_chans, n_chans, e->p.fs, snr_min, (gpsacq_obs*)d_obs}, e->stream);
+    });
 }
 
 // the ephemerides up, then k_coarse_fix timed; every argument has been checked
@@ -1122,12 +1128,11 @@ static int coarse_fix_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, int
                               int sats_per_fix, const gpsacq_coarse_params& cp, void* d_fix, void* d_info, void* d_obs_out) {
     if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
     if (int rc = or_own(e, d_obs_out, e->d_coarse_work, n_fix * (size_t)sats_per_fix)) return rc;  // the whole milliseconds live somewhere
-    if (int rc = e->coarse_fix_t.begin(e->stream)) return rc;
-    launch_coarse_fix(CoarseFixArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, (const gpsacq_coarse_prior*)d_prior, n_fix, sats_per_fix, cp,
-                                    (gpsacq_fix*)d_fix, (gpsacq_coarse_info*)d_info, (gpsacq_obs*)d_obs_out},
-                      e->stream);
-    if (int rc = e->coarse_fix_t.mark(1, e->stream)) return rc;
-    return e->coarse_fix_t.finish();
+    return timed_stage(e->coarse_fix_t, e->stream, [&] {
+        launch_coarse_fix(CoarseFixArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, (const gpsacq_coarse_prior*)d_prior, n_fix, sats_per_fix, cp,
+                                        (gpsacq_fix*)d_fix, (gpsacq_coarse_info*)d_info, (gpsacq_obs*)d_obs_out},
+                          e->stream);
+    });
 }
 
 extern "C" int gpsacq_coarse_obs_device(gpsacq_engine* e, const void* d_peaks, size_t n_fix, int n_chans, double snr_min, void* d_obs, int sync) {
@@ -1330,23 +1335,24 @@ static int refine_check(const char* who, const gpsacq_engine* e, const void* bit
     return refine_params(who, params, checked);
 }
 
-// what k_refine and k_fine_dop are told alike (the twelve fields RefineArgs and FineDopArgs share): the capture, its tasks and
-// peaks, the chip table and the engine's grid
-template <class Args> static void capture_args(const gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks,
-                                               const void* d_peaks, size_t n_tasks, Args& a) {
+// what every kernel on a 1-bit capture is told alike: the capture, its tasks and peaks, the chip table and the engine's grid
+static BitCaptureArgs capture_args(const gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
+                                   size_t n_tasks) {
     const uint32_t lead = (uint32_t)((uintptr_t)d_bits & 3u);  // the kernel loads whole words from the aligned address below
     const bool ref_grid = e->sub == 1 && e->dstride == 1;       // as gpsacq_handoff_engine
-    a.words = (const uint32_t*)((uintptr_t)d_bits - lead);
-    a.n_bytes = n_bytes + lead;
-    a.lead = lead;
-    a.stride = stride;
-    a.tasks = (const gpsacq_task*)d_tasks;
-    a.peaks = (const gpsacq_peak*)d_peaks;
-    a.n_tasks = n_tasks;
-    a.chips = e->d_track_chips;
-    a.fc = e->p.fc, a.fs = e->p.fs;
-    a.step_hz = ref_grid ? 0.0 : e->p.fs / N_FFT * e->dstride / e->sub;
-    a.spm = e->nlags;
+    BitCaptureArgs c{};
+    c.words = (const uint32_t*)((uintptr_t)d_bits - lead);
+    c.n_bytes = n_bytes + lead;
+    c.lead = lead;
+    c.stride = stride;
+    c.tasks = (const gpsacq_task*)d_tasks;
+    c.peaks = (const gpsacq_peak*)d_peaks;
+    c.n_tasks = n_tasks;
+    c.chips = e->d_track_chips;
+    c.fc = e->p.fc, c.fs = e->p.fs;
+    c.step_hz = ref_grid ? 0.0 : e->p.fs / N_FFT * e->dstride / e->sub;
+    c.spm = e->nlags;
+    return c;
 }
 
 // k_refine on the engine's stream timed; every argument has been checked
@@ -1354,23 +1360,19 @@ static int refine_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes, 
                           size_t n_tasks, const gpsacq_refine_params& rp, void* d_fine) {
     if (int rc = ensure_track_chips(e)) return rc;
     RefineArgs a{};
-    capture_args(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, a);
+    a.c = capture_args(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks);
     a.p = rp;
     a.out = (gpsacq_fine*)d_fine;
-    if (int rc = e->refine_t.begin(e->stream)) return rc;
-    launch_refine(a, e->stream);
-    if (int rc = e->refine_t.mark(1, e->stream)) return rc;
-    return e->refine_t.finish();
+    return timed_stage(e->refine_t, e->stream, [&] { launch_refine(a, e->stream); });
 }
 
 // k_coarse_obs_fine timed; every argument has been checked
 static int coarse_obs_fine_enqueue(gpsacq_engine* e, const void* d_peaks, const void* d_fine, size_t n_fix, int n_chans, double snr_min, void* d_obs) {
-    if (int rc = e->refine_obs_t.begin(e->stream)) return rc;
-    launch_coarse_obs_fine(CoarseObsFineArgs{(const gpsacq_peak*)d_peaks, (const gpsacq_fine*)d_fine, n_fix * (size_t)n_chans, n_chans, e->p.fs, snr_min,
-                                             (gpsacq_obs*)d_obs},
-                           e->stream);
-    if (int rc = e->refine_obs_t.mark(1, e->stream)) return rc;
-    return e->refine_obs_t.finish();
+    return timed_stage(e->refine_obs_t, e->stream, [&] {
+        launch_coarse_obs_fine(CoarseObsFineArgs{(const gpsacq_peak*)d_peaks, (const gpsacq_fine*)d_fine, n_fix * (size_t)n_chans, n_chans, e->p.fs, snr_min,
+                                                 (gpsacq_obs*)d_obs},
+                               e->stream);
+    });
 }
 
 extern "C" int gpsacq_refine_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
@@ -1484,12 +1486,11 @@ static int snap_quality_check(const char* who, const gpsacq_engine* e, const voi
 // k_snap_quality on the engine's stream timed; every argument has been checked
 static int snap_quality_enqueue(gpsacq_engine* e, const void* d_fine, size_t n_fix, int n_chans, const gpsacq_snap_quality_params& qp, void* d_obs,
                                 void* d_info) {
-    if (int rc = e->snapq_t.begin(e->stream)) return rc;
-    launch_snap_quality(SnapQualityArgs{(const gpsacq_fine*)d_fine, n_fix * (size_t)n_chans, e->nlags, e->p.fs, qp, (gpsacq_obs*)d_obs,
-                                        (gpsacq_quality_info*)d_info},
-                        e->stream);
-    if (int rc = e->snapq_t.mark(1, e->stream)) return rc;
-    return e->snapq_t.finish();
+    return timed_stage(e->snapq_t, e->stream, [&] {
+        launch_snap_quality(SnapQualityArgs{(const gpsacq_fine*)d_fine, n_fix * (size_t)n_chans, e->nlags, e->p.fs, qp, (gpsacq_obs*)d_obs,
+                                            (gpsacq_quality_info*)d_info},
+                            e->stream);
+    });
 }
 
 extern "C" int gpsacq_snap_quality_device(gpsacq_engine* e, const void* d_fine, size_t n_fix, int n_chans, const gpsacq_snap_quality_params* params,
@@ -1613,24 +1614,20 @@ static int fine_dop_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes
                             size_t n_tasks, const gpsacq_dopfine_params& dp, void* d_dopfine) {
     if (int rc = ensure_track_chips(e)) return rc;
     FineDopArgs a{};
-    capture_args(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks, a);
+    a.c = capture_args(e, d_bits, n_bytes, stride, d_tasks, d_peaks, n_tasks);
     a.p = dp;
     a.out = (gpsacq_dopfine*)d_dopfine;
-    if (int rc = e->dop_fine_t.begin(e->stream)) return rc;
-    launch_fine_dop(a, e->stream);
-    if (int rc = e->dop_fine_t.mark(1, e->stream)) return rc;
-    return e->dop_fine_t.finish();
+    return timed_stage(e->dop_fine_t, e->stream, [&] { launch_fine_dop(a, e->stream); });
 }
 
 // k_rate_obs_fine timed; every argument has been checked
 static int rate_obs_fine_enqueue(gpsacq_engine* e, const void* d_peaks, const void* d_dopfine, size_t n_fix, int n_chans, double snr_min,
                                  void* d_rate_obs) {
-    if (int rc = e->dop_obs_t.begin(e->stream)) return rc;
-    launch_rate_obs_fine(RateObsFineArgs{(const gpsacq_peak*)d_peaks, (const gpsacq_dopfine*)d_dopfine, n_fix * (size_t)n_chans, snr_min,
-                                         (gpsacq_rate_obs*)d_rate_obs},
-                         e->stream);
-    if (int rc = e->dop_obs_t.mark(1, e->stream)) return rc;
-    return e->dop_obs_t.finish();
+    return timed_stage(e->dop_obs_t, e->stream, [&] {
+        launch_rate_obs_fine(RateObsFineArgs{(const gpsacq_peak*)d_peaks, (const gpsacq_dopfine*)d_dopfine, n_fix * (size_t)n_chans, snr_min,
+                                             (gpsacq_rate_obs*)d_rate_obs},
+                             e->stream);
+    });
 }
 
 // the ephemerides up, then k_doppler_fix timed; every argument has been checked
@@ -1638,12 +1635,11 @@ static int doppler_fix_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, in
                                size_t n_fix, int sats_per_fix, const gpsacq_doppler_fix_params& fp, void* d_fix, void* d_prior) {
     if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
     if (int rc = e->d_dop_tau.grow(n_fix * (size_t)sats_per_fix, e->stream)) return rc;
-    if (int rc = e->dop_fix_t.begin(e->stream)) return rc;
-    launch_doppler_fix(DopplerFixArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, (const gpsacq_rate_obs*)d_rate_obs, (const int32_t*)d_rx_ms, n_fix,
-                                      sats_per_fix, fp, e->d_dop_tau, (gpsacq_doppler_fix*)d_fix, (gpsacq_coarse_prior*)d_prior},
-                       e->stream);
-    if (int rc = e->dop_fix_t.mark(1, e->stream)) return rc;
-    return e->dop_fix_t.finish();
+    return timed_stage(e->dop_fix_t, e->stream, [&] {
+        launch_doppler_fix(DopplerFixArgs{e->d_nav_eph, n_eph, (const gpsacq_obs*)d_obs, (const gpsacq_rate_obs*)d_rate_obs, (const int32_t*)d_rx_ms, n_fix,
+                                          sats_per_fix, fp, e->d_dop_tau, (gpsacq_doppler_fix*)d_fix, (gpsacq_coarse_prior*)d_prior},
+                           e->stream);
+    });
 }
 
 extern "C" int gpsacq_fine_doppler_device(gpsacq_engine* e, const void* d_bits, size_t n_bytes, size_t stride, const void* d_tasks, const void* d_peaks,
@@ -1828,14 +1824,17 @@ static int iq_snap_check(const char* who, const gpsacq_engine* e, const gpsacq_i
     return capture_engine_check(who, e);
 }
 
-// the host-buffer forms: the capture, the tasks and the peaks into engine scratch
+// the host-buffer forms: the capture into engine scratch, and the tasks and the peaks where the caller gave some (the aided
+// searches' peaks_in may be NULL)
 static int iq_snap_upload(gpsacq_engine* e, IqSnap& s, const void* iq, const gpsacq_task* tasks, const gpsacq_peak* peaks, size_t n_tasks) {
     if (int rc = e->d_iq.grow(2 * s.n_samples + 16, e->stream)) return rc;
     HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * s.n_samples, hipMemcpyHostToDevice, e->stream));
     s.d_iq = s.cap.d_src = e->d_iq;
     if (tasks)
         if (int rc = upload(e, e->d_refine_tasks, tasks, n_tasks)) return rc;
-    return upload(e, e->d_refine_peaks, peaks, n_tasks);
+    if (peaks)
+        if (int rc = upload(e, e->d_refine_peaks, peaks, n_tasks)) return rc;
+    return GPSACQ_OK;
 }
 
 // sign mode converts the capture once per call, timed by `timer`, as gpsacq_track_iq8_device does
@@ -1879,44 +1878,42 @@ static void iq_capture_args(const gpsacq_engine* e, const IqSnap& s, const void*
 static int refine_iq_enqueue(gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_peaks, size_t n_tasks, const gpsacq_refine_params& rp,
                              void* d_fine) {
     if (int rc = ensure_track_chips(e)) return rc;
-    if (int rc = e->snapiq_refine_t.begin(e->stream)) return rc;
-    if (s.sign) {
-        RefineArgs a{};
-        capture_args(e, s.d_bits, s.n_bytes, s.stride / 16, d_tasks, d_peaks, n_tasks, a);
-        a.p = rp;
-        a.out = (gpsacq_fine*)d_fine;
-        launch_refine(a, e->stream);
-    } else {
-        RefineIqArgs a{};
-        iq_capture_args(e, s, d_tasks, d_peaks, n_tasks, a.c);
-        a.p = rp;
-        a.out = (gpsacq_fine*)d_fine;
-        launch_refine_iq(a, e->stream);
-    }
-    if (int rc = e->snapiq_refine_t.mark(1, e->stream)) return rc;
-    return e->snapiq_refine_t.finish();
+    return timed_stage(e->snapiq_refine_t, e->stream, [&] {
+        if (s.sign) {
+            RefineArgs a{};
+            a.c = capture_args(e, s.d_bits, s.n_bytes, s.stride / 16, d_tasks, d_peaks, n_tasks);
+            a.p = rp;
+            a.out = (gpsacq_fine*)d_fine;
+            launch_refine(a, e->stream);
+        } else {
+            RefineIqArgs a{};
+            iq_capture_args(e, s, d_tasks, d_peaks, n_tasks, a.c);
+            a.p = rp;
+            a.out = (gpsacq_fine*)d_fine;
+            launch_refine_iq(a, e->stream);
+        }
+    });
 }
 
 // k_fine_dop_iq, or k_fine_dop on sign mode's stream, timed; every argument has been checked
 static int fine_dop_iq_enqueue(gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_peaks, size_t n_tasks,
                                const gpsacq_dopfine_params& dp, void* d_dopfine) {
     if (int rc = ensure_track_chips(e)) return rc;
-    if (int rc = e->snapiq_dop_t.begin(e->stream)) return rc;
-    if (s.sign) {
-        FineDopArgs a{};
-        capture_args(e, s.d_bits, s.n_bytes, s.stride / 16, d_tasks, d_peaks, n_tasks, a);
-        a.p = dp;
-        a.out = (gpsacq_dopfine*)d_dopfine;
-        launch_fine_dop(a, e->stream);
-    } else {
-        FineDopIqArgs a{};
-        iq_capture_args(e, s, d_tasks, d_peaks, n_tasks, a.c);
-        a.p = dp;
-        a.out = (gpsacq_dopfine*)d_dopfine;
-        launch_fine_dop_iq(a, e->stream);
-    }
-    if (int rc = e->snapiq_dop_t.mark(1, e->stream)) return rc;
-    return e->snapiq_dop_t.finish();
+    return timed_stage(e->snapiq_dop_t, e->stream, [&] {
+        if (s.sign) {
+            FineDopArgs a{};
+            a.c = capture_args(e, s.d_bits, s.n_bytes, s.stride / 16, d_tasks, d_peaks, n_tasks);
+            a.p = dp;
+            a.out = (gpsacq_dopfine*)d_dopfine;
+            launch_fine_dop(a, e->stream);
+        } else {
+            FineDopIqArgs a{};
+            iq_capture_args(e, s, d_tasks, d_peaks, n_tasks, a.c);
+            a.p = dp;
+            a.out = (gpsacq_dopfine*)d_dopfine;
+            launch_fine_dop_iq(a, e->stream);
+        }
+    });
 }
 
 extern "C" int gpsacq_refine_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
@@ -2141,10 +2138,7 @@ static void aid_predict_launch(gpsacq_engine* e, int n_eph, const void* d_fix, c
 static int aid_predict_enqueue(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel, size_t n_fix, int n_chans,
                                const gpsacq_aid_params& ap, void* d_aid, Stages<2>& timer) {
     if (int rc = nav_upload_eph(e, eph, n_eph)) return rc;
-    if (int rc = timer.begin(e->stream)) return rc;
-    aid_predict_launch(e, n_eph, d_fix, d_vel, n_fix, n_chans, ap, d_aid);
-    if (int rc = timer.mark(1, e->stream)) return rc;
-    return timer.finish();
+    return timed_stage(timer, e->stream, [&] { aid_predict_launch(e, n_eph, d_fix, d_vel, n_fix, n_chans, ap, d_aid); });
 }
 
 // k_aided timed by `timer`; every argument has been checked
@@ -2153,17 +2147,14 @@ static int aided_enqueue(gpsacq_engine* e, const void* d_bits, size_t n_bytes, s
                          Stages<2>& timer) {
     if (int rc = ensure_track_chips(e)) return rc;
     AidedArgs a{};
-    capture_args(e, d_bits, n_bytes, stride, d_tasks, d_peaks_in, n_tasks, a);
+    a.c = capture_args(e, d_bits, n_bytes, stride, d_tasks, d_peaks_in, n_tasks);
     a.kmax = e->kmax;
     a.aid = (const gpsacq_aid*)d_aid;
     a.p = sp;
     a.out = (gpsacq_aided*)d_aided;
     a.peaks_out = (gpsacq_peak*)d_peaks_out;
     a.powers = (unsigned long long*)d_powers;
-    if (int rc = timer.begin(e->stream)) return rc;
-    launch_aided(a, e->stream);
-    if (int rc = timer.mark(1, e->stream)) return rc;
-    return timer.finish();
+    return timed_stage(timer, e->stream, [&] { launch_aided(a, e->stream); });
 }
 
 extern "C" int gpsacq_aid_predict_device(gpsacq_engine* e, const gpsacq_ephemeris* eph, int n_eph, const void* d_fix, const void* d_vel, size_t n_fix,
@@ -2298,10 +2289,7 @@ static int aided_iq_enqueue(gpsacq_engine* e, const IqSnap& s, const void* d_tas
     a.out = (gpsacq_aided*)d_aided;
     a.peaks_out = (gpsacq_peak*)d_peaks_out;
     a.powers = (unsigned long long*)d_powers;
-    if (int rc = e->aidiq_search_t.begin(e->stream)) return rc;
-    launch_aided_iq(a, e->stream);
-    if (int rc = e->aidiq_search_t.mark(1, e->stream)) return rc;
-    return e->aidiq_search_t.finish();
+    return timed_stage(e->aidiq_search_t, e->stream, [&] { launch_aided_iq(a, e->stream); });
 }
 
 extern "C" int gpsacq_aided_search_iq8_device(gpsacq_engine* e, const gpsacq_iq8_input* in, const void* d_iq, size_t n_samples, size_t stride,
@@ -2332,13 +2320,7 @@ extern "C" int gpsacq_aided_search_iq8(gpsacq_engine* e, const gpsacq_iq8_input*
     if (int rc = e->d_aided_peaks.grow(n_tasks, e->stream)) return rc;
     if (powers_out)
         if (int rc = e->d_aided_powers.grow(n_pow, e->stream)) return rc;
-    if (int rc = e->d_iq.grow(2 * n_samples + 16, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * n_samples, hipMemcpyHostToDevice, e->stream));
-    s.d_iq = s.cap.d_src = e->d_iq;
-    if (tasks)
-        if (int rc = upload(e, e->d_refine_tasks, tasks, n_tasks)) return rc;
-    if (peaks_in)
-        if (int rc = upload(e, e->d_refine_peaks, peaks_in, n_tasks)) return rc;
+    if (int rc = iq_snap_upload(e, s, iq, tasks, peaks_in, n_tasks)) return rc;
     if (int rc = upload(e, e->d_aid, aid, n_tasks)) return rc;
     if (int rc = aided_iq_begin(e, s)) return rc;
     if (int rc = aided_iq_enqueue(e, s, tasks ? e->d_refine_tasks.p : nullptr, e->d_aid, peaks_in ? e->d_refine_peaks.p : nullptr, n_tasks, sp, e->d_aided,
@@ -2523,7 +2505,7 @@ template <class Search> static int coh_chain_enqueue(gpsacq_engine* e, Stages<4>
 // k_aided_coh on a 1-bit stream; every argument has been checked
 static void aided_coh_launch(gpsacq_engine* e, const CohSearch& se) {
     AidedCohArgs a{};
-    capture_args(e, se.d_bits, se.n_bytes, se.stride, se.d_tasks, se.d_peaks_in, se.n_tasks, a);
+    a.c = capture_args(e, se.d_bits, se.n_bytes, se.stride, se.d_tasks, se.d_peaks_in, se.n_tasks);
     a.kmax = e->kmax;
     a.aid = (const gpsacq_aid*)se.d_aid;
     a.table = e->d_coh_table;
@@ -2750,13 +2732,7 @@ extern "C" int gpsacq_aided_coh_search_iq8(gpsacq_engine* e, const gpsacq_iq8_in
     if (int rc = e->d_aided_peaks.grow(n_tasks, e->stream)) return rc;
     if (powers_out)
         if (int rc = e->d_coh_powers.grow(n_pow, e->stream)) return rc;
-    if (int rc = e->d_iq.grow(2 * n_samples + 16, e->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(e->d_iq, iq, 2 * n_samples, hipMemcpyHostToDevice, e->stream));
-    se.s.d_iq = se.s.cap.d_src = e->d_iq;
-    if (tasks)
-        if (int rc = upload(e, e->d_refine_tasks, tasks, n_tasks)) return rc;
-    if (peaks_in)
-        if (int rc = upload(e, e->d_refine_peaks, peaks_in, n_tasks)) return rc;
+    if (int rc = iq_snap_upload(e, se.s, iq, tasks, peaks_in, n_tasks)) return rc;
     if (int rc = upload(e, e->d_aid, aid, n_tasks)) return rc;
     se.d_tasks = tasks ? e->d_refine_tasks.p : nullptr, se.d_aid = e->d_aid, se.d_peaks_in = peaks_in ? e->d_refine_peaks.p : nullptr;
     se.n_tasks = n_tasks;
@@ -2865,16 +2841,15 @@ static int snap_floor_iq_enqueue(gpsacq_engine* e, const IqSnap& s, const void* 
 static int snap_quality_iq_enqueue(gpsacq_engine* e, const IqSnap& s, const void* d_tasks, const void* d_fine, size_t n_fix, int n_chans,
                                    const gpsacq_snap_quality_params& qp, void* d_obs, const void* d_floor, void* d_info) {
     const size_t n_tasks = n_fix * (size_t)n_chans;
-    if (int rc = e->snapqiq_quality_t.begin(e->stream)) return rc;
-    if (s.sign)
-        launch_snap_quality(SnapQualityArgs{(const gpsacq_fine*)d_fine, n_tasks, e->nlags, e->p.fs, qp, (gpsacq_obs*)d_obs, (gpsacq_quality_info*)d_info},
-                            e->stream);
-    else
-        launch_snap_quality_iq(SnapQualityIqArgs{snap_window_args(e, s, d_tasks, d_fine, n_tasks), (const uint64_t*)d_floor, e->p.fs, qp, (gpsacq_obs*)d_obs,
-                                                 (gpsacq_quality_info*)d_info},
-                               e->stream);
-    if (int rc = e->snapqiq_quality_t.mark(1, e->stream)) return rc;
-    return e->snapqiq_quality_t.finish();
+    return timed_stage(e->snapqiq_quality_t, e->stream, [&] {
+        if (s.sign)
+            launch_snap_quality(SnapQualityArgs{(const gpsacq_fine*)d_fine, n_tasks, e->nlags, e->p.fs, qp, (gpsacq_obs*)d_obs, (gpsacq_quality_info*)d_info},
+                                e->stream);
+        else
+            launch_snap_quality_iq(SnapQualityIqArgs{snap_window_args(e, s, d_tasks, d_fine, n_tasks), (const uint64_t*)d_floor, e->p.fs, qp, (gpsacq_obs*)d_obs,
+                                                     (gpsacq_quality_info*)d_info},
+                                   e->stream);
+    });
 }
 
 // floors, then quality: in sign mode the floors are written only where the caller asked for them

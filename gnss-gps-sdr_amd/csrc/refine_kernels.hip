@@ -16,8 +16,8 @@
 //   * the last bytes of the capture are read bytewise, nothing at or beyond byte n_bytes.
 // The six counts of ones pack in pairs (a segment has spm <= 65535 samples) and are summed over the wave with xor shuffles; every
 // lane then adds the three squares I^2 + Q^2 into 64-bit partials, the four waves' partials meet in LDS and thread 0 writes the
-// record.  Integer sums, no atomics: the record does not depend on the order of anything.  Two barriers; every loop is bounded by
-// kernel arguments.  The word loop's pieces (word_at, mod_full, the chips in LDS, the per-word window and masks) live in
+// record, which fine_record of snapshot_records.hpp builds from the three sums for this kernel and for k_refine_iq.  Integer
+// sums, no atomics: the record does not depend on the order of anything.  Two barriers; every loop is bounded by kernel arguments.  The word loop's pieces (word_at, mod_full, the chips in LDS, the per-word window and masks) live in
 // capture_words.hpp, which k_fine_dop of doppler_kernels.hip shares.
 // k_coarse_obs_fine: one lane per (fix, channel), k_coarse_obs of coarse_kernels.hip with the code phase of a usable record.
 // Built with -ffp-contract=off (Makefile): the NCO words must be gpsacq_handoff_engine's to the bit, and `lo_shift * step + fc`
@@ -28,29 +28,27 @@
 #include "capture_words.hpp"
 #include "nav_launch.hpp"
 #include "refine_launch.hpp"
+#include "snapshot_records.hpp"
 
 namespace acq {
-
-namespace {
-constexpr int FINE_UNUSABLE = GPSACQ_FINE_NO_HIT | GPSACQ_FINE_NO_POWER | GPSACQ_FINE_FEW;
-}  // namespace
 
 __global__ __launch_bounds__(64 * REFINE_WAVES) void k_refine(RefineArgs a) {
     __shared__ uint32_t s_chips[CHIP_WORDS];
     __shared__ unsigned long long s_part[REFINE_WAVES][3];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t t = blockIdx.x;
-    const gpsacq_peak pk = a.peaks[t];
+    const gpsacq_peak pk = a.c.peaks[t];
 
     // 1. the NCO words of gpsacq_handoff_engine, 2. what is no hit, 3. window and segments
-    const Window win = window_of(pk, a.tasks, t, a.fc, a.fs, a.step_hz, a.spm, a.p.snr_min, a.p.blocks, a.n_bytes, a.lead, a.stride);
-    const uint64_t o = win.o, spm = (uint64_t)a.spm, fit = win.fit, segments = win.segments;
+    double base_hz;
+    const Window win = window_of(pk, a.c, t, a.p.snr_min, a.p.blocks, base_hz);
+    const uint64_t o = win.o, spm = (uint64_t)a.c.spm, segments = win.segments;
     const uint32_t lo_rate = win.lo_rate, ca_rate = win.ca_rate;
     if (!win.hit) {
         if (threadIdx.x == 0) a.out[t] = gpsacq_fine{GPSACQ_FINE_NO_HIT, 0, 0, 0, 0, 0, 0, 0.0, 0.0};
         return;
     }
-    chips_to_lds(a.chips, win.prn, s_chips);
+    chips_to_lds(a.c.chips, win.prn, s_chips);
     __syncthreads();
 
     // 4. sums
@@ -62,7 +60,7 @@ __global__ __launch_bounds__(64 * REFINE_WAVES) void k_refine(RefineArgs a) {
         const uint64_t w1 = (a1 - 1) >> 5;
         uint32_t ones[6] = {0, 0, 0, 0, 0, 0};  // IE QE IP QP IL QL: samples whose product is -1
         for (uint64_t wi = (a0 >> 5) + lane; wi <= w1; wi += 64) {
-            const WordPos w = word_pos(a.words, a.n_bytes, wi, a0, a1, o, P0, D, lo_rate, ca_rate, s_chips);
+            const WordPos w = word_pos(a.c.words, a.c.n_bytes, wi, a0, a1, o, P0, D, lo_rate, ca_rate, s_chips);
             const uint32_t x = w.x, valid = w.valid;
             uint32_t cm, sp, em, pm, lm;
             word_masks<true>(w, D, lo_rate, ca_rate, cm, sp, em, pm, lm);
@@ -81,7 +79,7 @@ __global__ __launch_bounds__(64 * REFINE_WAVES) void k_refine(RefineArgs a) {
             for (int q = 0; q < 3; ++q) pkd[q] += (uint32_t)__shfl_xor((int)pkd[q], m, 64);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            const int64_t I = (int64_t)a.spm - 2 * (int64_t)(pkd[q] & 0xFFFF), Q = (int64_t)a.spm - 2 * (int64_t)(pkd[q] >> 16);
+            const int64_t I = (int64_t)a.c.spm - 2 * (int64_t)(pkd[q] & 0xFFFF), Q = (int64_t)a.c.spm - 2 * (int64_t)(pkd[q] >> 16);
             acc[q] += (uint64_t)(I * I + Q * Q);
         }
     }
@@ -90,23 +88,10 @@ __global__ __launch_bounds__(64 * REFINE_WAVES) void k_refine(RefineArgs a) {
     __syncthreads();
     if (threadIdx.x != 0) return;
 
-    // 5. estimate, 6. usable
-    gpsacq_fine r = {0, (int32_t)segments, lo_rate, ca_rate, 0, 0, 0, 0.0, 0.0};
-    for (int w = 0; w < REFINE_WAVES; ++w) r.early += s_part[w][0], r.prompt += s_part[w][1], r.late += s_part[w][2];
-    if (segments < fit) r.flags |= GPSACQ_FINE_SHORT;
-    if (segments < (uint64_t)a.p.min_segments) r.flags |= GPSACQ_FINE_FEW;
-    if (r.early + r.late == 0) {
-        r.flags |= GPSACQ_FINE_NO_POWER;
-    } else {
-        const double d = (double)D / 4294967296.0, aE = sqrt((double)r.early), aL = sqrt((double)r.late);
-        r.offset_chips = (1.0 - d) * (aE - aL) / (aE + aL);
-        double pos = (double)P0 / 4294967296.0 + r.offset_chips;
-        if (pos < 0.0) pos += 1023.0;
-        else if (pos >= 1023.0) pos -= 1023.0;
-        r.tx_frac = pos / 1.023e6;
-        if (!(r.tx_frac < 1e-3)) r.tx_frac = 0.0;
-    }
-    a.out[t] = r;
+    // 5. estimate, 6. usable: snapshot_records.hpp
+    uint64_t early = 0, prompt = 0, late = 0;
+    for (int w = 0; w < REFINE_WAVES; ++w) early += s_part[w][0], prompt += s_part[w][1], late += s_part[w][2];
+    a.out[t] = fine_record(segments, win.fit, a.p.min_segments, lo_rate, ca_rate, D, P0, early, prompt, late);
 }
 
 __global__ __launch_bounds__(NAV_BLOCK) void k_coarse_obs_fine(CoarseObsFineArgs a) {
@@ -126,7 +111,7 @@ __global__ __launch_bounds__(NAV_BLOCK) void k_coarse_obs_fine(CoarseObsFineArgs
 }
 
 void launch_refine(const RefineArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_refine, dim3((unsigned)a.n_tasks), dim3(64 * REFINE_WAVES), 0, s, a);
+    hipLaunchKernelGGL(k_refine, dim3((unsigned)a.c.n_tasks), dim3(64 * REFINE_WAVES), 0, s, a);
 }
 
 void launch_coarse_obs_fine(const CoarseObsFineArgs& a, hipStream_t s) {

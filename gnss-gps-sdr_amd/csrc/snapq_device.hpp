@@ -8,10 +8,9 @@
 #include <stdint.h>
 
 #include "../../include/gpsacq.h"
+#include "refine_launch.hpp"  // FINE_UNUSABLE, step 1's mask
 
 namespace acq {
-
-static constexpr int SNAPQ_FINE_UNUSABLE = GPSACQ_FINE_NO_HIT | GPSACQ_FINE_NO_POWER | GPSACQ_FINE_FEW;
 
 // record == false is step 1, NO RECORD: the flag and zeros.  floor == 0 (only a measured floor can be: an all-zero window) is
 // GPSACQ_QUALITY_NO_POWER with sig = 0.

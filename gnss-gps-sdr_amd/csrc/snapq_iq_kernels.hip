@@ -21,10 +21,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "capture_words.hpp"
 #include "iq_groups.hpp"
 #include "snapq_device.hpp"
 #include "snapq_iq_launch.hpp"
+#include "wave_ops.hpp"
 
 namespace acq {
 
@@ -87,7 +87,7 @@ __device__ __forceinline__ void range_sums(const SnapIqCapture& c, uint64_t a0, 
 // (sign mode): step 1 of "Snapshot signal quality" alone.  Every lane of a wave decides the same.
 __device__ __forceinline__ bool snap_window(const SnapWindowArgs& w, size_t t, const gpsacq_fine& r, bool capture, uint64_t& o, uint64_t& n) {
     o = n = 0;
-    if ((r.flags & SNAPQ_FINE_UNUSABLE) || r.segments <= 0) return false;
+    if ((r.flags & FINE_UNUSABLE) || r.segments <= 0) return false;
     if (!capture) return true;
     int32_t block = (int32_t)t;
     if (w.tasks) block = w.tasks[t].block;

@@ -19,7 +19,7 @@ __global__ __launch_bounds__(SNAPQ_BLOCK) void k_snap_quality(SnapQualityArgs a)
     const size_t i = (size_t)blockIdx.x * SNAPQ_BLOCK + threadIdx.x;
     if (i >= a.n_obs) return;
     const gpsacq_fine r = a.fine[i];
-    const bool record = !(r.flags & SNAPQ_FINE_UNUSABLE) && r.segments > 0;          // step 1
+    const bool record = !(r.flags & FINE_UNUSABLE) && r.segments > 0;          // step 1
     const uint64_t floor = record ? 2 * (uint64_t)a.spm * (uint64_t)r.segments : 0;  // step 2, the analytic floor
     const gpsacq_quality_info f = snap_quality_info(r, record, floor, a.spm, a.fs, a.par);
     a.info[i] = f;

@@ -8,25 +8,22 @@
 // against weight bytes +1 / -1 / 0 -- 0 for a sample before or after the segment, so a block may start at any sample and the
 // capture may end anywhere.  The six int32 sums of a segment meet over the wave through xor shuffles; every lane adds the three
 // squares I^2 + Q^2 (|I|, |Q| <= 512 spm < 2^25) into 64-bit partials, the four waves' partials meet in LDS and thread 0 writes the
-// record.  Integer sums, no atomics, no float before the estimate: the record does not depend on the order of anything.  Two
+// record (fine_record of snapshot_records.hpp, k_refine's).  Integer sums, no atomics, no float before the estimate: the record does not depend on the order of anything.  Two
 // barriers; every loop is bounded by kernel arguments.
 // k_fine_dop_iq: the same loop with the prompt replica alone (8 dot products per group); every segment's (I, Q) goes into LDS as
 // k_fine_dop's do.  The 25-bit sums are then normalised exactly: thread i takes the largest |I_s|, |Q_s| of the segments i, i + 256,
 // ..., an integer max over the wave and over LDS gives M in every thread, k = max(0, bitlength(M) - 12), and the lag-1 sums are
 // formed from I' = (I + 2^(k-1)) >> k, |I'| <= 2^12: a term is at most 2^50 and fewer than 2^12 of them stay below 2^62.  power is
-// the sum of the unshifted squares.  Four barriers.
+// the sum of the unshifted squares; the record is dopfine_record's (snapshot_records.hpp), k_fine_dop's.  Four barriers.
 // Built with -ffp-contract=off (Makefile): the NCO words must be the host's to the bit, as in refine_kernels.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "capture_groups.hpp"
 #include "snapshot_iq_launch.hpp"
+#include "snapshot_records.hpp"
 
 namespace acq {
-
-namespace {
-constexpr double PI = 3.141592653589793;
-}  // namespace
 
 __global__ __launch_bounds__(64 * SNAP_IQ_WAVES) void k_refine_iq(RefineIqArgs a) {
     __shared__ uint32_t s_chips[CHIP_WORDS];
@@ -37,8 +34,8 @@ __global__ __launch_bounds__(64 * SNAP_IQ_WAVES) void k_refine_iq(RefineIqArgs a
 
     // 1. the NCO words, 2. what is no hit, 3. window and segments
     double base_hz;
-    const Window win = window_of_iq(pk, a.c, t, a.p.snr_min, a.p.blocks, base_hz);
-    const uint64_t o = win.o, spm = (uint64_t)a.c.spm, fit = win.fit, segments = win.segments;
+    const Window win = window_of(pk, a.c, t, a.p.snr_min, a.p.blocks, base_hz);
+    const uint64_t o = win.o, spm = (uint64_t)a.c.spm, segments = win.segments;
     const uint32_t lo_rate = win.lo_rate, ca_rate = win.ca_rate;
     if (!win.hit) {
         if (threadIdx.x == 0) a.out[t] = gpsacq_fine{GPSACQ_FINE_NO_HIT, 0, 0, 0, 0, 0, 0, 0.0, 0.0};
@@ -66,23 +63,10 @@ __global__ __launch_bounds__(64 * SNAP_IQ_WAVES) void k_refine_iq(RefineIqArgs a
     __syncthreads();
     if (threadIdx.x != 0) return;
 
-    // 5. estimate, 6. usable
-    gpsacq_fine r = {0, (int32_t)segments, lo_rate, ca_rate, 0, 0, 0, 0.0, 0.0};
-    for (int w = 0; w < SNAP_IQ_WAVES; ++w) r.early += s_part[w][0], r.prompt += s_part[w][1], r.late += s_part[w][2];
-    if (segments < fit) r.flags |= GPSACQ_FINE_SHORT;
-    if (segments < (uint64_t)a.p.min_segments) r.flags |= GPSACQ_FINE_FEW;
-    if (r.early + r.late == 0) {
-        r.flags |= GPSACQ_FINE_NO_POWER;
-    } else {
-        const double d = (double)D / 4294967296.0, aE = sqrt((double)r.early), aL = sqrt((double)r.late);
-        r.offset_chips = (1.0 - d) * (aE - aL) / (aE + aL);
-        double pos = (double)P0 / 4294967296.0 + r.offset_chips;
-        if (pos < 0.0) pos += 1023.0;
-        else if (pos >= 1023.0) pos -= 1023.0;
-        r.tx_frac = pos / 1.023e6;
-        if (!(r.tx_frac < 1e-3)) r.tx_frac = 0.0;
-    }
-    a.out[t] = r;
+    // 5. estimate, 6. usable: snapshot_records.hpp
+    uint64_t early = 0, prompt = 0, late = 0;
+    for (int w = 0; w < SNAP_IQ_WAVES; ++w) early += s_part[w][0], prompt += s_part[w][1], late += s_part[w][2];
+    a.out[t] = fine_record(segments, win.fit, a.p.min_segments, lo_rate, ca_rate, D, P0, early, prompt, late);
 }
 
 __global__ __launch_bounds__(64 * SNAP_IQ_WAVES) void k_fine_dop_iq(FineDopIqArgs a) {
@@ -96,7 +80,7 @@ __global__ __launch_bounds__(64 * SNAP_IQ_WAVES) void k_fine_dop_iq(FineDopIqArg
 
     // steps 1 to 3
     double base_hz;
-    const Window win = window_of_iq(pk, a.c, t, a.p.snr_min, a.p.blocks, base_hz);
+    const Window win = window_of(pk, a.c, t, a.p.snr_min, a.p.blocks, base_hz);
     const uint64_t o = win.o, spm = (uint64_t)a.c.spm, segments = win.segments;  // segments <= DOP_MAX_SEGMENTS: the host's check
     const uint32_t lo_rate = win.lo_rate, ca_rate = win.ca_rate;
     if (!win.hit) {
@@ -152,22 +136,11 @@ __global__ __launch_bounds__(64 * SNAP_IQ_WAVES) void k_fine_dop_iq(FineDopIqArg
     __syncthreads();
     if (threadIdx.x != 0) return;
 
-    // estimate, flags
+    // estimate, flags: snapshot_records.hpp.  lo_rate is read SIGNED: complex baseband
     re = im = mag = power = 0;
     for (int w = 0; w < SNAP_IQ_WAVES; ++w) re += s_part[w][0], im += s_part[w][1], mag += s_part[w][2], power += s_part[w][3];
-    gpsacq_dopfine r = {0, (int32_t)segments, lo_rate, ca_rate, (int64_t)re, (int64_t)im, mag, power, 0.0, 0.0, 0.0};
-    if (segments < win.fit) r.flags |= GPSACQ_DOPFINE_SHORT;
-    if (segments < (uint64_t)a.p.min_segments) r.flags |= GPSACQ_DOPFINE_FEW;
-    if (r.mag == 0 || (r.re == 0 && r.im == 0)) {
-        r.flags |= GPSACQ_DOPFINE_NO_POWER;
-    } else {
-        const double T = (double)a.c.spm / a.c.fs;
-        r.df_hz = atan2((double)r.im, (double)r.re) / ((4.0 * PI) * T);
-        r.coherence = hypot((double)r.re, (double)r.im) / (double)r.mag;
-        r.doppler_hz = (((double)(int32_t)lo_rate * a.c.fs) / 4294967296.0 - base_hz) + r.df_hz;
-    }
-    if (r.coherence < a.p.coherence_min) r.flags |= GPSACQ_DOPFINE_WEAK;
-    a.out[t] = r;
+    const double nco_hz = ((double)(int32_t)lo_rate * a.c.fs) / 4294967296.0;
+    a.out[t] = dopfine_record(segments, win.fit, a.p, lo_rate, ca_rate, re, im, mag, power, nco_hz, base_hz, (double)a.c.spm / a.c.fs);
 }
 
 void launch_refine_iq(const RefineIqArgs& a, hipStream_t s) {

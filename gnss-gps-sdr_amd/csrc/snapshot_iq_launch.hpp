@@ -13,16 +13,17 @@ namespace acq {
 
 static constexpr int SNAP_IQ_WAVES = 4;  // wave64s of a workgroup of either kernel; wave w takes segments w, w + 4, ...
 
-// what both kernels are told alike: the capture, its tasks and peaks, the chip table, the engine's grid and the sample's law
+// an 8-bit IQ capture as the snapshot kernels are told of it, ONCE (BitCaptureArgs of refine_launch.hpp is the 1-bit one): the
+// capture, its tasks and peaks, the chip table, the engine's grid and the sample's law
 struct IqCaptureArgs {
     const uint8_t* iq;   // interleaved I, Q bytes (device), 16-byte aligned
     size_t n_samples;    // bytes at or beyond 2 * n_samples are not read
     size_t stride;       // bytes between blocks, a multiple of 16
     const gpsacq_task* tasks;  // [n_tasks] (device), or NULL: task t = (block t, PRN t % 32)
-    const gpsacq_peak* peaks;  // [n_tasks] (device)
+    const gpsacq_peak* peaks;  // [n_tasks] (device); the aided searches' peaks_in, which may be NULL
     size_t n_tasks;
     const uint32_t* chips;  // [32][32] C/A chip words (device)
-    double fs, step_hz;     // step_hz: the engine's Doppler grid step, 0 on the reference grid (lo_shift in FFT bins)
+    double fs, step_hz;    // step_hz: the engine's Doppler grid step, 0 on the reference grid (lo_shift in FFT bins)
     double mix_hz, fc_lo;   // f = lo_dop - mix_hz + fc_lo: fc_lo is the engine's fc, 0 for GPSACQ_SAMPLES_COMPLEX
     int spm;                // samples per millisecond, <= 65535
     uint32_t flip;          // 0x80808080 for GPSACQ_IQ_U8 (byte ^ 0x80 read as int8 = byte - 128), 0 for GPSACQ_IQ_S8
